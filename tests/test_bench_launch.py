@@ -93,3 +93,32 @@ def test_two_ranks_with_the_engine_on_one_gpu():
     j = _json_line(r.stdout)
     assert j["n_gpus"] == 1 and j["config"]["world_size"] == 2 and j["value"] > 0 and j["scaling"] == "weak"
     assert j["config"]["pairs_per_step_per_gpu"] == 16 and "rehearsal" in j["config"]["parallelism"]
+
+
+@pytest.mark.gpu
+def test_plain_run_dumps_what_the_timed_path_returned(tmp_path):
+    """A plain run prints the headline without the --full keys, times exactly --steps steps, and --dump-outputs writes the poses
+    the timed path returned in its last step: equal, bit for bit, to an engine registering the same seeded pairs."""
+    import numpy as np
+    r = _run(["--pairs", "4", "--points", "2048", "--steps", "2", "--warmup", "1", "--streams", "1", "--dump-outputs", str(tmp_path)],
+             timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    j = _json_line(r.stdout)
+    assert j["steps"] == 2 and j["ms_per_step"] > 0 and abs(j["value"] * j["ms_per_step"] / 1e3 - 4) < 0.05
+    assert not {"roofline", "cpu_baseline", "parity_check", "batch1_latency", "model_only"} & set(j)
+    T = np.load(tmp_path / "transforms.npy")
+    assert T.dtype == np.float32 and T.shape == (4, 5, 3, 4) and np.isfinite(T).all()
+
+    import torch
+    from deepsir_amd.arch import NetConfig
+    from deepsir_amd.engine import Engine
+    from deepsir_amd.synth import make_batch
+    from deepsir_amd.weights import generate_state_dict
+    cfg = NetConfig(feat_len=3)
+    eng = Engine(cfg, 0, max_points=2048, max_pairs=4)
+    eng.load_state_dict(generate_state_dict(cfg, 0, "plain"))
+    b = make_batch(2048, [10_000 + i for i in range(4)], 3, "3dmatch", False)     # bench.py's seeds of rank 0
+    dev = torch.device("cuda", 0)
+    out = eng.register(torch.from_numpy(b["points_src"]).to(dev), torch.from_numpy(b["points_ref"]).to(dev), 5, want_aux=False)
+    assert np.array_equal(out["transforms"].cpu().numpy(), T)
+    eng.close()

@@ -6,7 +6,7 @@ tag=${1:-r05}
 out=gpurun_out
 mkdir -p $out
 export TMPDIR=/tmp
-echo "== default bench"; python3 bench.py > $out/${tag}_bench_default.json 2> $out/${tag}_bench_default.err || { tail -5 $out/${tag}_bench_default.err; exit 1; }
+echo "== default bench"; python3 bench.py --full > $out/${tag}_bench_default.json 2> $out/${tag}_bench_default.err || { tail -5 $out/${tag}_bench_default.err; exit 1; }
 echo "== kernel trace + PMC passes of the bench command"; bash tools/profile_bench.sh $tag || exit 1
 python3 tools/step_hbm.py $out/${tag}_pmc_fetch.csv $out/${tag}_pmc_write.csv 4 256 5000 2 5 $out/${tag}_step_hbm.json > /dev/null || exit 1
 python3 tools/trace_gaps.py /tmp/prof_trace $out/${tag}_trace_gaps.json > /dev/null || echo "(trace_gaps skipped)"
@@ -25,9 +25,9 @@ for c in FETCH_SIZE WRITE_SIZE; do
 done
 python3 tools/pmc_traffic.py /tmp/nm_FETCH_SIZE /tmp/nm_WRITE_SIZE 128 5000 $out/${tag}_nn_match_pmc.json screened > /dev/null || exit 1
 echo "== other BASELINE configurations"
-python3 bench.py --points 2048 --pairs 512 --steps 10 > $out/${tag}_bench_c1.json 2> $out/${tag}_bench_c1.err || { tail -3 $out/${tag}_bench_c1.err; exit 1; }
-python3 bench.py --points 16384 --feat-len 4 --shape kitti --pairs 128 --streams 4 --steps 6 > $out/${tag}_bench_c3.json 2> $out/${tag}_bench_c3.err || { tail -3 $out/${tag}_bench_c3.err; exit 1; }
-python3 bench.py --points 65536 --partial-overlap --pairs 16 --steps 4 --warmup 1 --no-cpu-baseline > $out/${tag}_bench_c5.json 2> $out/${tag}_bench_c5.err || { tail -3 $out/${tag}_bench_c5.err; exit 1; }
+python3 bench.py --full --points 2048 --pairs 512 --steps 10 > $out/${tag}_bench_c1.json 2> $out/${tag}_bench_c1.err || { tail -3 $out/${tag}_bench_c1.err; exit 1; }
+python3 bench.py --full --points 16384 --feat-len 4 --shape kitti --pairs 128 --streams 4 --steps 6 > $out/${tag}_bench_c3.json 2> $out/${tag}_bench_c3.err || { tail -3 $out/${tag}_bench_c3.err; exit 1; }
+python3 bench.py --full --points 65536 --partial-overlap --pairs 16 --steps 4 --warmup 1 --no-cpu-baseline > $out/${tag}_bench_c5.json 2> $out/${tag}_bench_c5.err || { tail -3 $out/${tag}_bench_c5.err; exit 1; }
 for f in default c1 c3 c5; do python3 - $out/${tag}_bench_$f.json $f <<'PY'
 import json, sys
 j = json.load(open(sys.argv[1]))
