@@ -124,20 +124,6 @@ struct dsir_ctx {
   // single-pair requests into one call replays K graphs in turn (deepsir_amd/serve.py); the oldest is evicted beyond kMaxGraphs
   struct Graph { std::vector<unsigned char> key; hipGraphExec_t exec; void* walk_block; };   // walk_block: the graph's walker programs (device)
   int64_t graph_nodes[4] = {0, 0, 0, 0};   // the latest captured registration: nodes in all, kernel / memset / memcpy nodes (dsir_graph_stats)
-  // ---- independent branches of the schedule on auxiliary streams (fork / join through events; captured into a registration's graph as
-  // parallel branches).  With a few clouds in flight the chip is nearly empty and a registration is one long chain of dependent
-  // launches; the KNN searches of the four levels, a level's position-encoding branch (lfa.mlp1 -> lfa.mlp2), its mlp_skip and the
-  // loop-invariant halves of the aggregation do not depend on the chain beside them and can run beside it.  Same kernels, same
-  // operands: same bits (tests/test_gpu_walk.py).  An experiment that did NOT pay (see fork_mode): kept as a switch.
-  static constexpr int kAux = 2;
-  static constexpr int kForkClouds = 16;
-  hipStream_t aux[kAux] = {nullptr, nullptr};
-  std::vector<hipEvent_t> fork_events;
-  size_t fork_events_used = 0;
-  int fork_mode = 0;                           // 1: fork (dsir_enable_fork / DSIR_FORK=1).  OFF by default: measured SLOWER - one pair replayed
-                                               // from its graph 3.08 ms on one stream, 3.37 - 4.06 ms with any of the branches forked (a
-                                               // captured graph with parallel branches leaves the runtime's single-queue fast path:
-                                               // even ONE fork / join costs 0.3 ms; profiles/README.md round 5)
   // ---- deep-level walker (walk.hip): the programs of one call's RandLA passes live in device memory
   static constexpr int kWalkSlots = 12;        // programs per call (1 extractor pass or 2, up to 10 inlier passes)
   static constexpr int kWalkClouds = 16;       // the walker serves launches of up to that many clouds
@@ -203,6 +189,13 @@ int fail(dsir_ctx* c, const char* fmt, ...) {
     hipError_t e__ = (expr);                                                            \
     if (e__ != hipSuccess) return fail((c), "%s: %s", #expr, hipGetErrorString(e__));   \
   } while (0)
+
+// ws.overflow is set: report the launcher's refusal that stopped the schedule (Sched::refuse), else the arena's exhaustion
+int overflow_fail(dsir_ctx* c, const char* exhausted) {
+  const char* why = c->sched_error;
+  c->sched_error = nullptr;
+  return fail(c, "%s", why ? why : exhausted);
+}
 
 static_assert(kMaxLevels == DSIR_MAX_LEVELS, "kernels.h and dsir.h disagree on the level count");
 
@@ -519,7 +512,6 @@ int walk_flush(dsir_ctx* c, WalkProgram& P, hipStream_t st) {
 // may still be queued) after making sure that set's own last copy has run
 int walk_begin_call(dsir_ctx* c) {
   c->walk_used = 0;
-  c->fork_events_used = 0;
   if (c->capturing || !c->walk_dev) return 0;
   c->walk_set ^= 1;
   if (c->walk_ev_armed[c->walk_set]) { HIP_OK(c, hipEventSynchronize(c->walk_ev[c->walk_set])); c->walk_ev_armed[c->walk_set] = false; }
@@ -530,37 +522,6 @@ int walk_end_call(dsir_ctx* c) {
   HIP_OK(c, hipEventRecord(c->walk_ev[c->walk_set], c->stream));
   c->walk_ev_armed[c->walk_set] = true;
   return 0;
-}
-
-// `to` continues after everything enqueued on `from` so far (fork: main -> auxiliary; join: auxiliary -> main).  Events are taken
-// from a per-context pool that restarts with every call; a wait binds to the event's latest record at the time it is enqueued.
-hipEvent_t fork_mark(dsir_ctx* c, hipStream_t from) {
-  if (c->fork_events_used == c->fork_events.size()) {
-    hipEvent_t e = nullptr;
-    hipEventCreateWithFlags(&e, hipEventDisableTiming);
-    c->fork_events.push_back(e);
-  }
-  hipEvent_t e = c->fork_events[c->fork_events_used++];
-  hipEventRecord(e, from);
-  return e;
-}
-void fork_wait(hipStream_t to, hipEvent_t e) { hipStreamWaitEvent(to, e, 0); }
-void fork_to(dsir_ctx* c, hipStream_t from, hipStream_t to) { fork_wait(to, fork_mark(c, from)); }
-// what: 1 = the KNN pyramid's levels, 2 = a block's position-encoding branch, 4 = a block's mlp_skip, 8 = the aggregation's loop invariants
-// (DSIR_FORK_MASK: tuning hook - a dependency between streams has a price of its own, only the longer branches pay for it)
-// The auxiliary streams of the forked schedule exist only in a context that forks: every stream a process creates takes a hardware
-// queue in turn (GPU_MAX_HW_QUEUES of them), and two engines' main streams that land on one queue do not overlap - creating two idle
-// streams per context moved the serving scheduler's second engine onto the first one's queue (profiles/r05_serving_queues.txt).
-void ensure_aux_streams(dsir_ctx* c) {
-  if (c->aux[0]) return;
-  for (int k = 0; k < dsir_ctx::kAux; ++k)
-    if (hipStreamCreateWithFlags(&c->aux[k], hipStreamNonBlocking) != hipSuccess) c->aux[k] = nullptr;
-  if (!c->aux[0] || !c->aux[1]) { for (int k = 0; k < dsir_ctx::kAux; ++k) { if (c->aux[k]) hipStreamDestroy(c->aux[k]); c->aux[k] = nullptr; } }
-}
-
-bool fork_on(const dsir_ctx* c, int clouds, int what) {
-  static const int mask = (int)tuning_int("DSIR_FORK_MASK", 15);
-  return c->fork_mode && (mask & what) && c->aux[0] && clouds <= dsir_ctx::kForkClouds;
 }
 
 struct Sched {
@@ -587,6 +548,11 @@ struct Sched {
     ++rec->nphases;
     return true;
   }
+  // a launcher refused the layer: nothing more runs (as on an exhausted arena), the schedule's caller reports why
+  void refuse(const char* why) {
+    if (!c->ws.overflow) c->sched_error = why;
+    c->ws.overflow = true;
+  }
   // a point-wise GEMM launch: a phase when recording and plannable, else (after flushing what was recorded: order) its own launch
   void gemm(const GemmArgs& a) {
     if (rec) {
@@ -594,7 +560,7 @@ struct Sched {
       if (walk_plan_gemm(a, &j) && rec_push(j)) return;
       rec_flush();
     }
-    launch_pw_gemm(a, st);
+    if (!launch_pw_gemm(a, st)) refuse("point-wise GEMM: no kernel took the layer");
   }
 
   double* stats_slot(int groups) {
@@ -634,7 +600,7 @@ struct Sched {
     if ((s0.uv && !s0.x) || (s1 && s1->uv && !s1->x)) {
       // table-only rows (lse_uv.hip) exist for ONE loader, pw_stream.hip's S_UV: the generic kernels would dereference the null row base
       rec_flush();
-      if (!launch_pw_stream(a, st)) { c->sched_error = "MLP2D: no kernel took the table-only position encoding"; c->ws.overflow = true; }
+      if (launch_pw_stream(a, st) != Launch::done) refuse("MLP2D: no kernel took the table-only position encoding");
       return y;
     }
     gemm(a);
@@ -682,7 +648,7 @@ struct Sched {
     a.uv = uv; a.uv_cs = (int64_t)n * 2 * w.cout; a.dist = dist; a.dist_cs = M;
     a.stats_out = st_out; a.groups = w.groups; a.n = n; a.clouds = clouds; a.KH = w.cout;
     rec_flush();
-    if (!c->ws.overflow && !launch_lse_uv_stats(a, st)) { c->sched_error = "lse_uv: layer outside the kernel's envelope"; c->ws.overflow = true; }
+    if (!c->ws.overflow && !launch_lse_uv_stats(a, st)) refuse("lse_uv: layer outside the kernel's envelope");
     return y;
   }
   Act mlp2d_lse(const Mlp2dW& w, const float* xyz, int64_t xyz_cs, const int32_t* neigh, int64_t neigh_cs, int n,
@@ -699,7 +665,8 @@ struct Sched {
     a.Y = y.p; a.y_cloud_stride = (int64_t)M * w.cout; a.ldy = w.cout; a.stats_out = st_out; a.groups_out = w.groups;
     split_of(a);
     rec_flush();
-    if (!c->ws.overflow) launch_pw_gemm(a, st);   // an exhausted arena hands out its base: nothing may run on it
+    // an exhausted arena hands out its base: nothing may run on it
+    if (!c->ws.overflow && !launch_pw_gemm(a, st)) refuse("lfa.mlp1: no kernel took the relative-position layer");
     return y;
   }
   // Att_pooling up to (not including) its MLP2D: softmax_k(fc [gather(f); enc]) . [gather(f); enc]
@@ -730,8 +697,7 @@ struct Sched {
       if (launch_att_full(a, w.d / 2, st)) return y;
     }
     if (!enc.p && w.d >= 64) {     // table-only rows have no other consumer (lse_uv_enabled() excludes this)
-      if (!c->ws.overflow) c->sched_error = "attentive pooling: no kernel took the table-only position encoding";
-      c->ws.overflow = true;
+      refuse("attentive pooling: no kernel took the table-only position encoding");
       return y;
     }
     if (!no_att2 && w.d >= 64 && w.fc_g && f.C * 2 == w.d && enc.C * 2 == w.d) {   // d = 16: the extra gathers cost more than the MFMAs saved
@@ -758,7 +724,7 @@ struct Sched {
         if (walk_plan_gemm(a2, &j) && rec_push(j)) return y;
       }
       rec_flush();
-      if (w.d <= 128 ? launch_pw_stream(a2, st) : launch_pw_tile(a2, st)) return y;
+      if (w.d <= 128 ? launch_pw_stream(a2, st) == Launch::done : launch_pw_tile(a2, st)) return y;
     }
     if (att_pool_enabled() && w.d == 16 && f.C == 8 && enc.C == 8 && c->dweights16 && w.fc >= c->dweights && w.fc < c->dweights + c->nweights) {
       // att_pool.hip, level 0: four points per wave, fp16-split scores, softmax in registers
@@ -774,8 +740,7 @@ struct Sched {
       if (!c->ws.overflow && launch_att_pool16(a, st)) return y;
     }
     if (!enc.p) {     // table-only rows have no other consumer (lse_uv_enabled() excludes this)
-      if (!c->ws.overflow) c->sched_error = "attentive pooling: no kernel took the table-only position encoding";
-      c->ws.overflow = true;
+      refuse("attentive pooling: no kernel took the table-only position encoding");
       return y;
     }
     GemmArgs a;
@@ -786,7 +751,8 @@ struct Sched {
     a.Y = y.p; a.y_cloud_stride = (int64_t)n * w.d; a.ldy = w.d;
     split_of(a);
     rec_flush();
-    if (!c->ws.overflow) launch_pw_gemm(a, st);   // an exhausted arena hands out its base: nothing may run on it
+    // an exhausted arena hands out its base: nothing may run on it
+    if (!c->ws.overflow && !launch_pw_gemm(a, st)) refuse("attentive pooling: no kernel took the score layer");
     return y;
   }
   Act linear(const LinW& w, const Seg& s0, const Seg* s1, int M, int epi, float* out = nullptr,
@@ -801,7 +767,8 @@ struct Sched {
     a.residual = residual; a.res_cloud_stride = (int64_t)M * w.cout; a.ldres = w.cout;
     split_of(a);
     rec_flush();
-    if (!c->ws.overflow) launch_pw_gemm(a, st);   // an exhausted arena hands out its base: nothing may run on it
+    // an exhausted arena hands out its base: nothing may run on it
+    if (!c->ws.overflow && !launch_pw_gemm(a, st)) refuse("linear layer: no kernel took the layer");
     return y;
   }
 };
@@ -890,46 +857,18 @@ int randla_forward(dsir_ctx* c, const RandlaW& w, const Seg& in0, const Seg* in1
     const Seg xin = Sched::seg_of(x);
     Act f, skipb;
     const bool ahead = walk && l >= walk_from;       // computed before the chain started (below)
-    // Few clouds in flight: the block's independent branches leave the chain mlp1 -> pooling 1 -> pooling 2 -> mlp2 and run beside it
-    // on the auxiliary streams - the position-encoding branch (lfa.mlp1 -> lfa.mlp2: inputs the pyramid alone), joined where the two
-    // poolings read it, and mlp_skip (input the block's input), joined at the residual sum.
-    const bool fork_enc = fork_on(c, py.clouds, 2) && !walk && !reuse && !ahead, fork_skip = fork_on(c, py.clouds, 4) && !walk;
-    hipEvent_t ev_enc = nullptr, ev_enc2 = nullptr, ev_skip = nullptr;
-    const hipEvent_t block_in = (fork_enc || fork_skip) ? fork_mark(c, st) : nullptr;      // x (and everything before it) is in flight on the main stream
-    Act enc, enc2;
-    if (fork_enc) {
-      fork_wait(c->aux[0], block_in);
-      s.st = c->aux[0];
-      enc = enc_of(l); ev_enc = fork_mark(c, c->aux[0]);
-      enc2 = enc2_of(l, enc); ev_enc2 = fork_mark(c, c->aux[0]);
-      s.st = st;
-    }
     const bool paired = s.mlp2d_pair(b, xin, n, f, skipb);
-    if (!paired) {
-      f = s.mlp2d(b.mlp1, xin, nullptr, n, true);
-      if (fork_skip) {
-        fork_wait(c->aux[1], block_in);
-        s.st = c->aux[1];
-        skipb = s.mlp2d(b.skip, xin, nullptr, n, false);
-        ev_skip = fork_mark(c, c->aux[1]);
-        s.st = st;
-      }
-    }
-    if (!ev_enc) enc = ahead ? enc_pre[l] : enc_of(l);
-    else fork_wait(st, ev_enc);
+    if (!paired) f = s.mlp2d(b.mlp1, xin, nullptr, n, true);
+    const Act enc = ahead ? enc_pre[l] : enc_of(l);
     const int s2_mode = reuse ? 2 : 1;      // iteration 0 stores the pyramid-only half of the scores, later iterations load it
     Act agg = s.att(b.att1, f, enc, nb_l, neigh_cs, n, cache ? cache->s2_buf[l][0] : nullptr, s2_mode);
     Act a1 = s.mlp2d(b.att1.mlp, Sched::seg_of(agg), nullptr, n, true);
-    if (!ev_enc2) enc2 = ahead ? enc2_pre[l] : enc2_of(l, enc);
-    else fork_wait(st, ev_enc2);
+    const Act enc2 = ahead ? enc2_pre[l] : enc2_of(l, enc);
     if (cache && !reuse) { cache->enc[l] = enc; cache->enc2[l] = enc2; }
     Act agg2 = s.att(b.att2, a1, enc2, nb_l, neigh_cs, n, cache ? cache->s2_buf[l][1] : nullptr, s2_mode);
     Act a2 = s.mlp2d(b.att2.mlp, Sched::seg_of(agg2), nullptr, n, true);
     Act mainb = s.mlp2d(b.mlp2, Sched::seg_of(a2), nullptr, n, false);
-    if (!paired) {
-      if (ev_skip) fork_wait(st, ev_skip);
-      else skipb = s.mlp2d(b.skip, xin, nullptr, n, false);
-    }
+    if (!paired) skipb = s.mlp2d(b.skip, xin, nullptr, n, false);
     Act enc_out;
     enc_out.C = 2 * b.d; enc_out.rows = n;
     Act samp;
@@ -949,7 +888,7 @@ int randla_forward(dsir_ctx* c, const RandlaW& w, const Seg& in0, const Seg* in1
       if (walk && l == walk_from - 1) {
         // the chain starts with this level's pooling: first the deep levels' position-encoding branch, as launches of their own
         for (int q = walk_from; q < L; ++q) { enc_pre[q] = enc_of(q); enc2_pre[q] = enc2_of(q, enc_pre[q]); }
-        if (c->ws.overflow) return fail(c, "workspace exhausted in randla_forward (raise max_points / max_pairs)");
+        if (c->ws.overflow) return overflow_fail(c, "workspace exhausted in randla_forward (raise max_points / max_pairs)");
         s.rec = &wprog; s.rec_wpc = wprog.wpc;
       }
       // deeper levels: only the pooled ("randomly sampled") rows are ever read — combine inside the pooling kernel
@@ -985,7 +924,7 @@ int randla_forward(dsir_ctx* c, const RandlaW& w, const Seg& in0, const Seg* in1
     h.in = Sched::seg_of(x);
     h.W1 = w.out_w; h.W2 = w.fc[0].W; h.b2 = w.fc[0].b; h.W3 = w.fc[1].W; h.b3 = w.fc[1].b; h.W4 = w.fc[2].W; h.b4 = w.fc[2].b;
     h.ncls = w.ncls; h.M = n0; h.clouds = py.clouds; h.feat_out = feat_out; h.logits_out = logits_out;
-    if (c->ws.overflow) return fail(c, "workspace exhausted in randla_forward (raise max_points / max_pairs)");
+    if (c->ws.overflow) return overflow_fail(c, "workspace exhausted in randla_forward (raise max_points / max_pairs)");
     // default: the head's four layers as fp16-split products (head_mlp_h.hip; fp32 accuracy); dsir_enable_agg_split(0) /
     // DSIR_AGG_F32: the exact-fp32 head, bit-identical to the four separate launches
     if (c->agg_split) {
@@ -1002,7 +941,7 @@ int randla_forward(dsir_ctx* c, const RandlaW& w, const Seg& in0, const Seg* in1
     h = s.linear(w.fc[1], Sched::seg_of(h), nullptr, n0, EPI_ACT);
     s.linear(w.fc[2], Sched::seg_of(h), nullptr, n0, EPI_LINEAR, logits_out);
   }
-  if (c->ws.overflow) return fail(c, "workspace exhausted in randla_forward (raise max_points / max_pairs)");
+  if (c->ws.overflow) return overflow_fail(c, "workspace exhausted in randla_forward (raise max_points / max_pairs)");
   if (cache) cache->valid = true;
   return 0;
 }
@@ -1081,39 +1020,6 @@ int build_pyramid(dsir_ctx* c, const float* points, int stride, int clouds, int 
   // interpolation search (in cell order: a wave's lanes walk neighbouring cells)
   const size_t mark = c->ws.mark();
   const void* prev_scratch = nullptr;
-  bool any_nn1_grid = false;
-  for (int l = 0; l < g.num_layers; ++l) any_nn1_grid = any_nn1_grid || nn1_by_grid(l);
-  if (fork_on(c, clouds, 1) && !any_nn1_grid && g.num_layers == 4) {
-    // few clouds: the searches of the four levels (and the four interpolation searches) read the input points alone - three branches
-    // of about equal length instead of a chain of eight launches: {level 0} | {level 1, its interpolation search} | {the rest}
-    hipStream_t a0 = c->aux[0], a1 = c->aux[1];
-    const hipEvent_t start = fork_mark(c, st);
-    fork_wait(a0, start); fork_wait(a1, start);
-    auto knn_level = [&](int l, hipStream_t s_) -> bool {
-      if (p.nl[l] >= grid_min && !no_grid) {
-        void* scratch = c->ws.raw(knn_grid_scratch_bytes(clouds, p.nl[l]));
-        if (c->ws.overflow) return false;
-        launch_knn16_grid(points, (int64_t)n * stride, stride, p.nl[l], clouds, neigh + (int64_t)p.off[l] * kKnn, neigh_cs, scratch, s_);
-      } else {
-        launch_knn16(points, (int64_t)n * stride, stride, p.nl[l], clouds, neigh + (int64_t)p.off[l] * kKnn, neigh_cs, s_);
-      }
-      return true;
-    };
-    auto nn1_level = [&](int l, hipStream_t s_) {
-      launch_nn1(points, (int64_t)n * stride, stride, p.nl[l], p.nl[l + 1], clouds, interp + p.off[l], p.S, s_);
-    };
-    bool ok = knn_level(0, st);
-    ok = ok && knn_level(1, a0);
-    nn1_level(1, a0);
-    nn1_level(0, a1);
-    ok = ok && knn_level(2, a1) && knn_level(3, a1);
-    nn1_level(2, a1); nn1_level(3, a1);
-    fork_to(c, a0, st); fork_to(c, a1, st);          // join before anything re-uses the scratch or reads the lists
-    if (!ok) return fail(c, "workspace exhausted in the KNN pyramid");
-    c->ws.release(mark);
-    launch_copy_sub_levels(neigh, neigh_cs, lv, clouds, sub, sub_cs, st);
-    return 0;
-  }
   // Every level's searches read the input points alone (the levels are prefixes of the cloud), so the pyramid is THREE launches instead
   // of a chain of ten - the grids of the large levels, their searches, and everything else (the interpolation searches of all levels,
   // the 16-NN of the levels without a grid) - plus one per interpolation search that walks a grid (large launches).  With one pair in
@@ -1182,7 +1088,7 @@ int check_ready(dsir_ctx* c) {
 }
 
 int post(dsir_ctx* c) {
-  if (c->ws.overflow) return fail(c, "workspace exhausted (raise max_points / max_pairs in dsir_cfg)");
+  if (c->ws.overflow) return overflow_fail(c, "workspace exhausted (raise max_points / max_pairs in dsir_cfg)");
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(c, "HIP launch error: %s", hipGetErrorString(e));
   return 0;
@@ -1238,8 +1144,6 @@ int dsir_create(int device, const dsir_cfg* cfg, dsir_ctx** out) {
     return fail(nullptr, "cannot initialise device %d", device);
   }
   c->own_stream = c->stream;
-  c->fork_mode = tuning_flag("DSIR_FORK") ? 1 : 0;
-  if (c->fork_mode) ensure_aux_streams(c);
   // which sub-networks exist follows args.pipeline (model.py:131-193)
   add_randla(c, "feat_extractor", cfg->feat_len, cfg->num_classes);
   if (cfg->pipeline != DSIR_PIPELINE_LABEL) {
@@ -1325,8 +1229,6 @@ void dsir_destroy(dsir_ctx* c) {
   if (c->walk_trace) hipFree(c->walk_trace);
   if (c->stats) hipFree(c->stats);
   if (c->ws.base) hipFree(c->ws.base);
-  for (int k = 0; k < dsir_ctx::kAux; ++k) if (c->aux[k]) { hipStreamSynchronize(c->aux[k]); hipStreamDestroy(c->aux[k]); }
-  for (hipEvent_t e : c->fork_events) hipEventDestroy(e);
   hipStreamDestroy(c->own_stream);     // a caller's stream (dsir_set_stream) is the caller's to destroy
   delete c;
 }
@@ -1480,7 +1382,6 @@ int dsir_knn_pyramid(dsir_ctx* c, const float* points, int stride, int clouds, i
   HIP_OK(c, hipSetDevice(c->device));
   if (clouds < 1 || stride < 3) return fail(c, "dsir_knn_pyramid: bad arguments");
   c->ws.top = 0; c->ws.overflow = false;
-  c->fork_events_used = 0;
   if (int r = build_pyramid(c, points, stride, clouds, n, xyz, neigh, sub, interp)) return r;
   return post(c);
 }
@@ -1684,6 +1585,7 @@ static int forward_pair_stage(dsir_ctx* c, const dsir_pair_batch* in, bool want_
     pre.copy(pxyz, in->src_xyz, sizeof(float) * P * ps.S * 3);
     pre.copy(rxyz, in->ref_xyz, sizeof(float) * P * pr.S * 3);
   }
+  if (pre.overflow) return fail(c, "forward_pair: more than %d opening fills / copies", MemOps::kMax);
   launch_mem_ops(pre, st);
   if (have_py) {
     // caller-supplied indices: copied with every entry clamped into its level's range (a bad index can never fault a
@@ -1852,15 +1754,8 @@ static int register_enqueue(dsir_ctx* c, const dsir_pair_batch* in, int n_iter, 
   if (ws.overflow) return fail(c, "workspace exhausted (raise max_points / max_pairs)");
   const size_t mark1 = ws.mark();
   {
-    // the two loop-invariant halves are independent of each other: with few clouds in flight mlp_feat(feat_src) (and the copy of the
-    // src coordinates) runs on an auxiliary stream beside the ref side's chain; its temporaries keep their own arena space until the join
-    const bool forked = fork_on(c, 2 * P, 8);
-    hipStream_t side = forked ? c->aux[0] : st;
-    if (forked) fork_to(c, st, side);
-    c->stream = side;                         // run_mlp_feat launches on the context's stream
     run_mlp_feat(c, feat_s, P, J, F_s);       // straight into the storage that outlives the iterations
-    c->stream = st;
-    launch_copy_xyz(pxyz, (int64_t)ps.S * 3, 3, J, P, xyz_cur, (int64_t)J * 3, side);      // xyz_cur = level-0 src coordinates
+    launch_copy_xyz(pxyz, (int64_t)ps.S * 3, 3, J, P, xyz_cur, (int64_t)J * 3, st);      // xyz_cur = level-0 src coordinates
     float* F_r = run_mlp_feat(c, feat_r, P, K);
     AggExtras exr;
     if (screen) { exr.sq = sc_sb; exr.hi = sc_bh; exr.lo = sc_bl; }
@@ -1870,7 +1765,6 @@ static int register_enqueue(dsir_ctx* c, const dsir_pair_batch* in, int n_iter, 
       launch_split16_norm(desc_r, (int64_t)P * K, sc_bh, sc_bl, sc_sb, st);
     }
     if (prune && launch_prune_ref(rxyz, (int64_t)pr.S * 3, desc_r, sc_bh, sc_bl, sc_sb, P, J, K, pr_scratch, st)) return fail(c, "pruned search: sorting the ref side failed");
-    if (forked) fork_to(c, side, st);
     ws.release(mark1);
   }
 
@@ -1933,8 +1827,74 @@ static int register_enqueue(dsir_ctx* c, const dsir_pair_batch* in, int n_iter, 
     a.part = kab_part; a.chunk_min = c->kabsch_chunked_min;
     launch_kabsch(a, st);
   }
-  if (c->ws.overflow) return fail(c, "workspace exhausted (raise max_points / max_pairs in dsir_cfg)");
+  if (c->ws.overflow) return overflow_fail(c, "workspace exhausted (raise max_points / max_pairs in dsir_cfg)");
   if (int r = walk_end_call(c)) return r;
+  return 0;
+}
+
+// Graph mode: capture one registration, instantiate it and keep it in c->graphs (the oldest evicted beyond kMaxGraphs).  Every exit
+// leaves the context clean (Capture's destructor): the capture ended, the graph destroyed, the walker programs' block freed unless
+// c->graphs holds it, capturing / cap_dev cleared.
+static int capture_register(dsir_ctx* c, const dsir_pair_batch* in, int n_iter, const dsir_pair_result* out,
+                            const std::vector<unsigned char>& key, hipGraphExec_t* exec) {
+  struct Capture {
+    dsir_ctx* c;
+    bool open = false;
+    hipGraph_t graph = nullptr;
+    void* walk_block = nullptr;
+    ~Capture() {
+      if (open) { hipGraph_t g = nullptr; hipStreamEndCapture(c->stream, &g); if (g) hipGraphDestroy(g); }
+      if (graph) hipGraphDestroy(graph);
+      if (walk_block) hipFree(walk_block);
+      c->capturing = false;
+      c->cap_dev = nullptr;
+    }
+  } cap{c};
+  HIP_OK(c, hipStreamSynchronize(c->stream));
+  // the walker programs of this registration get a device block of their own (the kernel nodes hold addresses inside it); they are
+  // collected on the host while the launches are captured and uploaded once, below
+  if (c->walk_mode && c->walk_dev) {
+    HIP_OK(c, hipMalloc(&cap.walk_block, sizeof(WalkProgram) * dsir_ctx::kWalkSlots));
+    c->cap_host.assign(sizeof(WalkProgram) * dsir_ctx::kWalkSlots, 0);
+    c->cap_dev = reinterpret_cast<WalkProgram*>(cap.walk_block);
+  }
+  for (int64_t& v : c->graph_nodes) v = 0;     // a failed capture leaves no census
+  HIP_OK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
+  cap.open = true;
+  c->capturing = true;
+  if (int r = register_enqueue(c, in, n_iter, out)) return r;
+  c->capturing = false;
+  cap.open = false;
+  HIP_OK(c, hipStreamEndCapture(c->stream, &cap.graph));
+  if (!cap.graph) return fail(c, "hipStreamEndCapture: no graph");
+  if (cap.walk_block && c->walk_used > 0)
+    HIP_OK(c, hipMemcpy(cap.walk_block, c->cap_host.data(), sizeof(WalkProgram) * (size_t)c->walk_used, hipMemcpyHostToDevice));
+  {
+    // what one registration costs in launches: the node census of the captured graph (dsir_graph_stats)
+    size_t nn = 0;
+    if (hipGraphGetNodes(cap.graph, nullptr, &nn) == hipSuccess && nn > 0) {
+      std::vector<hipGraphNode_t> nodes(nn);
+      if (hipGraphGetNodes(cap.graph, nodes.data(), &nn) == hipSuccess) {
+        c->graph_nodes[0] = (int64_t)nn;
+        for (size_t i = 0; i < nn; ++i) {
+          hipGraphNodeType t;
+          if (hipGraphNodeGetType(nodes[i], &t) != hipSuccess) continue;
+          if (t == hipGraphNodeTypeKernel) ++c->graph_nodes[1];
+          else if (t == hipGraphNodeTypeMemset) ++c->graph_nodes[2];
+          else if (t == hipGraphNodeTypeMemcpy) ++c->graph_nodes[3];
+        }
+      }
+    }
+  }
+  HIP_OK(c, hipGraphInstantiate(exec, cap.graph, nullptr, nullptr, 0));
+  c->graphs.push_back({key, *exec, cap.walk_block});
+  cap.walk_block = nullptr;                          // c->graphs owns it now
+  if (c->graphs.size() > dsir_ctx::kMaxGraphs) {
+    HIP_OK(c, hipStreamSynchronize(c->stream));     // the evicted graph may still be replaying
+    hipGraphExecDestroy(c->graphs.front().exec);
+    if (c->graphs.front().walk_block) hipFree(c->graphs.front().walk_block);
+    c->graphs.erase(c->graphs.begin());
+  }
   return 0;
 }
 
@@ -1957,57 +1917,7 @@ int dsir_register(dsir_ctx* c, const dsir_pair_batch* in, int n_iter, const dsir
   for (auto& g : c->graphs)
     if (g.key == key) { exec = g.exec; break; }
   if (!exec) {
-    HIP_OK(c, hipStreamSynchronize(c->stream));
-    // the walker programs of this registration get a device block of their own (the kernel nodes hold addresses inside it); they are
-    // collected on the host while the launches are captured and uploaded once, below
-    void* walk_block = nullptr;
-    if (c->walk_mode && c->walk_dev) {
-      HIP_OK(c, hipMalloc(&walk_block, sizeof(WalkProgram) * dsir_ctx::kWalkSlots));
-      c->cap_host.assign(sizeof(WalkProgram) * dsir_ctx::kWalkSlots, 0);
-      c->cap_dev = reinterpret_cast<WalkProgram*>(walk_block);
-    }
-    if (hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
-      if (walk_block) hipFree(walk_block);
-      return fail(c, "hipStreamBeginCapture failed");
-    }
-    c->capturing = true;
-    const int rc = register_enqueue(c, in, n_iter, out);
-    c->capturing = false;
-    hipGraph_t graph = nullptr;
-    const hipError_t e = hipStreamEndCapture(c->stream, &graph);
-    if (rc != 0) { if (graph) hipGraphDestroy(graph); if (walk_block) hipFree(walk_block); return rc; }
-    if (e != hipSuccess || !graph) { if (walk_block) hipFree(walk_block); return fail(c, "hipStreamEndCapture: %s", hipGetErrorString(e)); }
-    if (walk_block && c->walk_used > 0)
-      HIP_OK(c, hipMemcpy(walk_block, c->cap_host.data(), sizeof(WalkProgram) * (size_t)c->walk_used, hipMemcpyHostToDevice));
-    c->cap_dev = nullptr;
-    {
-      // what one registration costs in launches: the node census of the captured graph (dsir_graph_stats)
-      size_t nn = 0;
-      c->graph_nodes[0] = c->graph_nodes[1] = c->graph_nodes[2] = c->graph_nodes[3] = 0;
-      if (hipGraphGetNodes(graph, nullptr, &nn) == hipSuccess && nn > 0) {
-        std::vector<hipGraphNode_t> nodes(nn);
-        if (hipGraphGetNodes(graph, nodes.data(), &nn) == hipSuccess) {
-          c->graph_nodes[0] = (int64_t)nn;
-          for (size_t i = 0; i < nn; ++i) {
-            hipGraphNodeType t;
-            if (hipGraphNodeGetType(nodes[i], &t) != hipSuccess) continue;
-            if (t == hipGraphNodeTypeKernel) ++c->graph_nodes[1];
-            else if (t == hipGraphNodeTypeMemset) ++c->graph_nodes[2];
-            else if (t == hipGraphNodeTypeMemcpy) ++c->graph_nodes[3];
-          }
-        }
-      }
-    }
-    const hipError_t e2 = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-    hipGraphDestroy(graph);
-    if (e2 != hipSuccess) { if (walk_block) hipFree(walk_block); return fail(c, "hipGraphInstantiate: %s", hipGetErrorString(e2)); }
-    if (c->graphs.size() >= dsir_ctx::kMaxGraphs) {
-      HIP_OK(c, hipStreamSynchronize(c->stream));     // the evicted graph may still be replaying
-      hipGraphExecDestroy(c->graphs.front().exec);
-      if (c->graphs.front().walk_block) hipFree(c->graphs.front().walk_block);
-      c->graphs.erase(c->graphs.begin());
-    }
-    c->graphs.push_back({key, exec, walk_block});
+    if (int r = capture_register(c, in, n_iter, out, key, &exec)) return r;
   }
   HIP_OK(c, hipGraphLaunch(exec, c->stream));
   return post(c);
@@ -2358,15 +2268,6 @@ int dsir_walk_trace(dsir_ctx* c, int reset, int64_t* out, int64_t* clock_khz) {
     if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, c->device) != hipSuccess || khz <= 0) khz = 100000;
     *clock_khz = khz;
   }
-  return 0;
-}
-
-int dsir_enable_fork(dsir_ctx* c, int enable) {
-  if (!c) return 1;
-  c->fork_mode = enable != 0;
-  if (c->fork_mode) ensure_aux_streams(c);
-  // a captured registration has the choice baked in
-  c->drop_graphs();
   return 0;
 }
 

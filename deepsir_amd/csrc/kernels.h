@@ -115,10 +115,14 @@ int pw_stream_gn_contributions(int M, int Cout);        // pw_stream.hip: the VI
 int pw_tile_gn_contributions(int M, int Cout, int groups);   // pw_tile.hip: row blocks x column blocks a group spans
 int lse_uv_gn_contributions(int n, int KH);             // lse_uv.hip: virtual workgroups per cloud
 
-void launch_pw_gemm(const GemmArgs& a, hipStream_t st);
+// false: no kernel took the layer (the caller reports it; nothing was launched)
+bool launch_pw_gemm(const GemmArgs& a, hipStream_t st);
 bool pw_gemm_serves_pair(const GemmArgs& a);   // would launch_pw_gemm serve this launch with GemmArgs::c_split set? (ask before fusing two layers)
-// narrow-layer fast path (pw_stream.hip); false => not applicable
-bool launch_pw_stream(const GemmArgs& a, hipStream_t st);
+// what a launcher made of a layer: launched it; left it to another kernel family (outside its envelope); or refused it - an error the
+// caller reports, never a layer for another family (whose summation order would differ)
+enum class Launch { done, not_mine, refused };
+// narrow-layer fast path (pw_stream.hip); refused: a GroupNorm layer beyond kGnMaxContrib contributions per statistic
+Launch launch_pw_stream(const GemmArgs& a, hipStream_t st);
 // wide-layer path, LDS-tiled 128/64 x 64 x 32 (pw_tile.hip): Cin a multiple of 32 in [64,768], Cout >= 64
 bool launch_pw_tile(const GemmArgs& a, hipStream_t st);
 // does launch_pw_tile serve this layer with pw_tile_small_kernel (the one kernel that takes GemmArgs::c_split)?
@@ -288,9 +292,10 @@ struct MemOps {
   static constexpr int kMax = 10;
   int n = 0;
   MemOp op[kMax];
-  void fill(void* dst, size_t bytes, uint32_t word = 0) { if (dst && bytes) op[n++] = MemOp{dst, nullptr, bytes, word}; }
-  void copy(void* dst, const void* src, size_t bytes) { if (dst && src && bytes) op[n++] = MemOp{dst, src, bytes, 0u}; }
-  bool full() const { return n >= kMax; }
+  bool overflow = false;     // more than kMax operations were asked for: the caller fails the call, nothing is launched
+  void fill(void* dst, size_t bytes, uint32_t word = 0) { if (dst && bytes) add(MemOp{dst, nullptr, bytes, word}); }
+  void copy(void* dst, const void* src, size_t bytes) { if (dst && src && bytes) add(MemOp{dst, src, bytes, 0u}); }
+  void add(const MemOp& o) { if (n < kMax) op[n++] = o; else overflow = true; }
 };
 void launch_mem_ops(const MemOps& m, hipStream_t st);    // no-op when m.n == 0
 

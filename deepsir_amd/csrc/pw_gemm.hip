@@ -20,11 +20,8 @@
 // LDS as [row][16+2] (the +2 pad makes the fragment reads bank-conflict free:
 // 18*r mod 32 is a permutation of the even banks for r = 0..15); the next
 // chunk's global loads are issued before the MFMAs of the current one.
-#include <cstdio>
-#include <cstdlib>
 #include "kernels.h"
 #include "device_utils.h"
-#include <cstdlib>
 
 namespace dsir {
 
@@ -304,25 +301,26 @@ bool pw_gemm_serves_pair(const GemmArgs& a) {
   return !no_tile && !no_pair && pw_tile_small_serves(a);
 }
 
-void launch_pw_gemm(const GemmArgs& a, hipStream_t st) {
-  if (a.M <= 0 || a.clouds <= 0) return;
+bool launch_pw_gemm(const GemmArgs& a, hipStream_t st) {
+  if (a.M <= 0 || a.clouds <= 0) return true;
   static const bool no_stream = tuning_flag("DSIR_NO_STREAM");   // A/B switch for tests and profiling
-  if (!no_stream && launch_pw_stream(a, st)) return;
+  if (!no_stream) {
+    const Launch r = launch_pw_stream(a, st);
+    if (r != Launch::not_mine) return r == Launch::done;
+  }
   static const bool no_tile = tuning_flag("DSIR_NO_TILE");
-  if (!no_tile && launch_pw_tile(a, st)) return;
+  if (!no_tile && launch_pw_tile(a, st)) return true;
   if (a.amode == A_LSE) {
     launch_bn<EPI_GN, A_LSE>(a, st);
-    return;
+    return true;
   }
   switch (a.epi) {
-    case EPI_GN: launch_bn<EPI_GN, A_SEGS>(a, st); break;
-    case EPI_ACT: launch_bn<EPI_ACT, A_SEGS>(a, st); break;
-    case EPI_LINEAR: launch_bn<EPI_LINEAR, A_SEGS>(a, st); break;
-    case EPI_L2NORM: launch_t<64, EPI_L2NORM, A_SEGS>(a, st); break;
-    case EPI_ATT: launch_bn<EPI_ATT, A_SEGS>(a, st); break;
-    default:   // EPI_ATT2 exists only in pw_stream / pw_tile; the engine falls back to EPI_ATT itself (Sched::att)
-      fprintf(stderr, "dsir: launch_pw_gemm: epilogue %d has no generic kernel\n", a.epi);
-      abort();
+    case EPI_GN: launch_bn<EPI_GN, A_SEGS>(a, st); return true;
+    case EPI_ACT: launch_bn<EPI_ACT, A_SEGS>(a, st); return true;
+    case EPI_LINEAR: launch_bn<EPI_LINEAR, A_SEGS>(a, st); return true;
+    case EPI_L2NORM: launch_t<64, EPI_L2NORM, A_SEGS>(a, st); return true;
+    case EPI_ATT: launch_bn<EPI_ATT, A_SEGS>(a, st); return true;
+    default: return false;   // EPI_ATT2 exists only in pw_stream / pw_tile; the engine falls back to EPI_ATT itself (Sched::att)
   }
 }
 

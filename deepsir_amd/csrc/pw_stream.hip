@@ -18,10 +18,8 @@
 // different (fixed) order; results are deterministic.
 // Loader modes: vector (aligned segments), element-wise (tiny Cin: xyz / score /
 // 6-channel inlier input), and the relative position encoding (RandLANet.py:197-212).
-#include <cstdio>
 #include "kernels.h"
 #include "device_utils.h"
-#include <cstdlib>
 
 namespace dsir {
 
@@ -588,11 +586,7 @@ void launch_s(const GemmArgs& a, hipStream_t st) {
   // cloud whether it is registered alone or inside a batch (bitwise batch invariance).
   const int natural = (ntiles + 31) / 32;
   const bool big = EPI != EPI_GN && (int64_t)natural * gy * a.clouds >= 512;   // no statistics, chip already full: ~8 tiles per wave stand
-  int blocks = stream_blocks(a.M, gy, big);
-  if (EPI == EPI_GN && blocks > kGnMaxContrib) {     // dsir_create bounds max_points so that this cannot happen (kernels.h)
-    fprintf(stderr, "dsir: pw_stream: %d contributions per GroupNorm statistic exceed the exactness bound %d\n", blocks, kGnMaxContrib);
-    abort();
-  }
+  int blocks = stream_blocks(a.M, gy, big);     // EPI_GN: at most kGnMaxContrib (launch_epi)
   // Epilogues without a cross-workgroup reduction (everything but the GroupNorm statistics) give the same bits under any
   // tile -> wave assignment, so their grid may follow the launch size: with one or two clouds in flight (batch-1 latency)
   // a cloud spreads over enough workgroups to reach ~2 per CU; with many clouds nothing changes.
@@ -625,17 +619,21 @@ void launch_s(const GemmArgs& a, hipStream_t st) {
 }
 
 template <int KQ, int NT, int MODE>
-bool launch_epi(const GemmArgs& a, hipStream_t st) {
+Launch launch_epi(const GemmArgs& a, hipStream_t st) {
   switch (a.epi) {
-    case EPI_GN: launch_s<KQ, NT, EPI_GN, MODE>(a, st); return true;
-    case EPI_ACT: if (MODE == S_LSE) return false; launch_s<KQ, NT, EPI_ACT, MODE == S_LSE ? S_VEC : MODE>(a, st); return true;
-    case EPI_LINEAR: if (MODE == S_LSE) return false; launch_s<KQ, NT, EPI_LINEAR, MODE == S_LSE ? S_VEC : MODE>(a, st); return true;
-    default: return false;
+    case EPI_GN:
+      // the statistics' summation order is this family's own (launch_s): beyond the exactness bound the layer is refused, not handed
+      // on - dsir_create bounds max_points so that this cannot happen (kernels.h)
+      if (stream_blocks(a.M, (a.Cout + NT * 16 - 1) / (NT * 16), false) > kGnMaxContrib) return Launch::refused;
+      launch_s<KQ, NT, EPI_GN, MODE>(a, st); return Launch::done;
+    case EPI_ACT: if (MODE == S_LSE) return Launch::not_mine; launch_s<KQ, NT, EPI_ACT, MODE == S_LSE ? S_VEC : MODE>(a, st); return Launch::done;
+    case EPI_LINEAR: if (MODE == S_LSE) return Launch::not_mine; launch_s<KQ, NT, EPI_LINEAR, MODE == S_LSE ? S_VEC : MODE>(a, st); return Launch::done;
+    default: return Launch::not_mine;
   }
 }
 
 template <int KQ, int MODE>
-bool launch_nt(const GemmArgs& a, hipStream_t st) {
+Launch launch_nt(const GemmArgs& a, hipStream_t st) {
   if (a.Cout <= 16) return launch_epi<KQ, 1, MODE>(a, st);
   if (a.Cout <= 32) return launch_epi<KQ, 2, MODE>(a, st);
   return launch_epi<KQ, 4, MODE>(a, st);
@@ -655,21 +653,21 @@ int pw_stream_gn_contributions(int M, int Cout) {
   return stream_blocks(M, (Cout + nt16 - 1) / nt16, false);
 }
 
-// Returns false when the layer is outside this kernel's envelope (caller falls back to pw_gemm.hip).
-bool launch_pw_stream(const GemmArgs& a, hipStream_t st) {
-  if (a.M <= 0 || a.clouds <= 0) return true;
-  if (a.c_split > 0) return false;             // two-layer launches: pw_tile_small_kernel only
+// not_mine: the layer is outside this kernel's envelope (the caller falls back to pw_gemm.hip).
+Launch launch_pw_stream(const GemmArgs& a, hipStream_t st) {
+  if (a.M <= 0 || a.clouds <= 0) return Launch::done;
+  if (a.c_split > 0) return Launch::not_mine;             // two-layer launches: pw_tile_small_kernel only
   if (a.amode == A_LSE) {
-    if (a.epi != EPI_GN) return false;
+    if (a.epi != EPI_GN) return Launch::not_mine;
     return launch_nt<3, S_LSE>(a, st);
   }
-  if (a.Cin > 64) return false;
+  if (a.Cin > 64) return Launch::not_mine;
   if (a.seg[0].uv) {     // rows rebuilt from per-point tables (lse_uv.hip): one segment of 8 or 32 channels, GroupNorm epilogue
-    if (a.nseg != 1 || a.epi != EPI_GN || !a.seg[0].idx || !a.seg[0].dist || !a.seg[0].w8 || (a.M % 16) != 0) return false;
-    if ((reinterpret_cast<uintptr_t>(a.seg[0].uv) % 16) != 0 || (a.seg[0].uv_cloud_stride % 4) != 0) return false;
+    if (a.nseg != 1 || a.epi != EPI_GN || !a.seg[0].idx || !a.seg[0].dist || !a.seg[0].w8 || (a.M % 16) != 0) return Launch::not_mine;
+    if ((reinterpret_cast<uintptr_t>(a.seg[0].uv) % 16) != 0 || (a.seg[0].uv_cloud_stride % 4) != 0) return Launch::not_mine;
     if (a.Cin == 8) return launch_nt<2, S_UV>(a, st);
     if (a.Cin == 32) return launch_nt<8, S_UV>(a, st);
-    return false;
+    return Launch::not_mine;
   }
   const int C0 = a.seg[0].C;
   // vector mode: Cin = 4 KQ exactly, chunks do not straddle the segment boundary, aligned rows
@@ -678,30 +676,30 @@ bool launch_pw_stream(const GemmArgs& a, hipStream_t st) {
     bool ok = seg_vec_ok(a.seg[0], KQ) && (a.nseg == 1 || (seg_vec_ok(a.seg[1], KQ) && (C0 % KQ) == 0));
     if (!ok) break;
     if (a.epi == EPI_ATT) {
-      if (KQ == 4 && a.Cout == 16) { launch_s<4, 1, EPI_ATT, S_VEC>(a, st); return true; }
-      if (KQ == 16 && a.Cout == 64) { launch_s<16, 4, EPI_ATT, S_VEC>(a, st); return true; }
-      return false;
+      if (KQ == 4 && a.Cout == 16) { launch_s<4, 1, EPI_ATT, S_VEC>(a, st); return Launch::done; }
+      if (KQ == 16 && a.Cout == 64) { launch_s<16, 4, EPI_ATT, S_VEC>(a, st); return Launch::done; }
+      return Launch::not_mine;
     }
     if (a.epi == EPI_L2NORM) {
-      if (KQ == 16 && a.Cout == 64) { launch_s<16, 4, EPI_L2NORM, S_VEC>(a, st); return true; }
-      return false;
+      if (KQ == 16 && a.Cout == 64) { launch_s<16, 4, EPI_L2NORM, S_VEC>(a, st); return Launch::done; }
+      return Launch::not_mine;
     }
     if (a.epi == EPI_ATT2) {   // A = enc (Cin = d/2), Cout = d
-      if (a.nseg != 1 || a.Cout != 2 * a.Cin || !a.g || !a.fseg.idx) return false;
+      if (a.nseg != 1 || a.Cout != 2 * a.Cin || !a.g || !a.fseg.idx) return Launch::not_mine;
       const int sc = a.s2 ? a.s2_mode : 0;
       if (KQ == 8) {                                                            // d = 64
         if (sc == 1) launch_s<8, 4, EPI_ATT2, S_VEC, 1>(a, st);
         else if (sc == 2) launch_s<8, 4, EPI_ATT2, S_VEC, 2>(a, st);
         else launch_s<8, 4, EPI_ATT2, S_VEC>(a, st);
-        return true;
+        return Launch::done;
       }
       if (KQ == 16) {                                                           // d = 128 (two column blocks)
         if (sc == 1) launch_s<16, 4, EPI_ATT2, S_VEC, 1>(a, st);
         else if (sc == 2) launch_s<16, 4, EPI_ATT2, S_VEC, 2>(a, st);
         else launch_s<16, 4, EPI_ATT2, S_VEC>(a, st);
-        return true;
+        return Launch::done;
       }
-      return false;
+      return Launch::not_mine;
     }
     switch (KQ) {
       case 2: return launch_nt<2, S_VEC>(a, st);
@@ -714,7 +712,7 @@ bool launch_pw_stream(const GemmArgs& a, hipStream_t st) {
     if (a.Cin <= 4) return launch_nt<1, S_ELEM>(a, st);
     return launch_nt<2, S_ELEM>(a, st);
   }
-  return false;
+  return Launch::not_mine;
 }
 
 }  // namespace dsir
