@@ -273,7 +273,8 @@ class Network(nn.Module):
     def _train_engine(self, st, n_points: int, pairs: int) -> Engine:
         eng = st["engine"]
         if n_points > eng.max_points or pairs > eng.max_pairs:
-            eng.close()
+            # not closed: the endpoints of an earlier forward may still hold it for their loss (_AlignLoss); Engine.__del__
+            # frees it once the last of them is gone
             eng = Engine(self.cfg, st["dev"].index or 0, max(n_points, eng.max_points), max(pairs, eng.max_pairs))
             eng.load_state_dict({k: v for k, v in self.state_dict().items()})
             st["engine"] = eng
@@ -314,8 +315,11 @@ class Network(nn.Module):
         batch = self._pyramids(eng, data, src, ref)
         self._dirty = self._pool_dirty = self._server_dirty = True      # running statistics move now, the weights at optimizer.step()
 
+        # every back() below starts with zero_grad (the flat gradient buffer and the scatter plans) and returns its OWN tape's
+        # gradient, which autograd adds into param.grad: two training forwards alive before their backwards (or one backward of
+        # loss_A + loss_B) give gA + gB, as torch's autograd does.  The forward needs no plan (only the backward scatters).
         def param_grads(tr):
-            g = tr.flat_g.clone()              # ONE copy: autograd may keep what it is handed, the trainer's buffer is zeroed by the next forward
+            g = tr.flat_g.clone()             # ONE copy: autograd may keep what it is handed, the trainer's buffer is zeroed by the next backward
             out = []
             for k, p in zip(names, params):
                 v = tr.grads[k]
@@ -330,11 +334,11 @@ class Network(nn.Module):
             box = {}
 
             def run():
-                main.zero_grad()
                 fw = T.forward_align_train(eng, main, fe, ag, batch, n_iter, masks)
                 box["fw"] = fw
 
                 def back(grads):
+                    main.zero_grad()
                     g = grads[0]
                     for it in range(n_iter):
                         main.backward(fw["tapes"][it], g[it].contiguous(), shared=fw["shared"])
@@ -362,7 +366,6 @@ class Network(nn.Module):
             box = {}
 
             def run():
-                main.zero_grad()
                 outs, tapes = [], []
                 for s_ in ("src", "ref"):
                     lg, tape = main.forward(batch[f"points_{s_}"], batch[f"{s_}_xyz"], batch[f"{s_}_neigh"], batch[f"{s_}_sub"], batch[f"{s_}_interp"],
@@ -371,6 +374,7 @@ class Network(nn.Module):
                 box["tapes"] = tapes
 
                 def back(grads):
+                    main.zero_grad()
                     for tape, g, lg in zip(tapes, grads, outs):
                         if g is not None:
                             main.backward(tape, g.reshape(-1, lg.shape[-1]).contiguous())
@@ -392,11 +396,11 @@ class Network(nn.Module):
         inp = T.feat_pipeline_inputs_train(eng, frozen[0], batch, self.cfg.num_sub, masks)
 
         def run():
-            main.zero_grad()
             d_s, tape_s = main.forward(inp["xyz_src"], inp["feat_src"], inp["score_src"])
             d_r, tape_r = main.forward(inp["xyz_ref"], inp["feat_ref"], inp["score_ref"])
 
             def back(grads):
+                main.zero_grad()
                 if grads[0] is not None:
                     main.backward(tape_s, grads[0])
                 if grads[1] is not None:

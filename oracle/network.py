@@ -33,13 +33,17 @@ def _gather_pts(x: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
 
 
 class OracleNet:
-    def __init__(self, cfg: NetConfig, state_dict: Dict[str, "np.ndarray | torch.Tensor"]):
+    def __init__(self, cfg: NetConfig, state_dict: Dict[str, "np.ndarray | torch.Tensor"], dtype: torch.dtype = torch.float32):
+        """dtype: of every floating tensor (parameters, running statistics, constants); torch.float64 makes the same function
+        an fp64 reference for error bounds (inputs are then handed over in fp64 too)."""
         self.cfg = cfg
+        self.dtype = dtype
         self.p: Dict[str, torch.Tensor] = {}
         for k, v in state_dict.items():
             t = v if isinstance(v, torch.Tensor) else torch.from_numpy(np.array(v))
-            self.p[k] = t.detach().clone()
-        self.label_weights = torch.tensor(LABEL_WEIGHTS, dtype=torch.float32)
+            t = t.detach().clone()
+            self.p[k] = t.to(dtype) if t.is_floating_point() else t
+        self.label_weights = torch.tensor(LABEL_WEIGHTS, dtype=dtype)
 
     # ------------------------------------------------------------------ layers
     def mlp2d(self, prefix: str, x: torch.Tensor, act: bool = True) -> torch.Tensor:
@@ -139,7 +143,7 @@ class OracleNet:
         fn = feat / (fmax.view(B, 1, 1) + _EPS)
         saliency = F.softplus(fn - _gather_nbr(fn, idx).mean(dim=3))
         rel = _gather_nbr(xyz, idx) - xyz.unsqueeze(-1)
-        density = (torch.norm(rel, dim=1, keepdim=True).mean(dim=-1) < 2.0).float()
+        density = (torch.norm(rel, dim=1, keepdim=True).mean(dim=-1) < 2.0).to(feat.dtype)
         chan = fn / (fn.max(dim=1, keepdim=True)[0] + _EPS)
         ls = self.label_weights[label.reshape(-1).long()].view(B, 1, N)
         ls = ls / (ls.max(dim=-1, keepdim=True)[0] + _EPS)
@@ -233,8 +237,8 @@ class OracleNet:
     @staticmethod
     def kabsch(src: torch.Tensor, tgt: torch.Tensor, w: torch.Tensor) -> Tuple[torch.Tensor, bool]:
         """Weighted Kabsch (compute_rigid_transform_2, model.py:22-66):
-        fp32 moments, fp64 SVD, R = V U^T with V[:,2] flipped when det < 0,
-        R cast to fp32 before t = -R c_s + c_t.  SVD failure -> identity + flag."""
+        moments in the inputs' precision (fp32 as the reference's), fp64 SVD, R = V U^T with V[:,2] flipped when
+        det < 0, R cast back to the inputs' precision before t = -R c_s + c_t.  SVD failure -> identity + flag."""
         wn = w / (torch.sum(torch.abs(w), dim=1, keepdim=True) + _EPS)
         cs = torch.sum(src * wn, dim=1)
         ct = torch.sum(tgt * wn, dim=1)
@@ -248,11 +252,11 @@ class OracleNet:
             Vn = V.clone()
             Vn[:, :, 2] *= -1
             Rn = Vn @ U.transpose(-1, -2)
-            R = torch.where(torch.det(Rp)[:, None, None] > 0, Rp, Rn).float()
+            R = torch.where(torch.det(Rp)[:, None, None] > 0, Rp, Rn).to(src.dtype)
             t = -R @ cs[:, :, None] + ct[:, :, None]
             return torch.cat((R, t), dim=2), False
         except Exception:
-            return torch.eye(3, 4)[None].repeat(len(src), 1, 1), True
+            return torch.eye(3, 4, dtype=src.dtype)[None].repeat(len(src), 1, 1), True
 
     # ------------------------------------------------------------------ SE(3) (common/math/se3_torch.py:28-77)
     @staticmethod
@@ -303,9 +307,14 @@ class OracleNet:
         return transforms, ep
 
 
-def to_torch(data: Dict[str, np.ndarray]) -> Dict[str, torch.Tensor]:
+def to_torch(data: Dict[str, np.ndarray], dtype: Optional[torch.dtype] = None) -> Dict[str, torch.Tensor]:
+    """Index arrays -> int64; floating arrays -> ``dtype`` (None: as they are)."""
     out = {}
     for k, v in data.items():
         t = torch.from_numpy(np.ascontiguousarray(v))
-        out[k] = t.long() if t.dtype in (torch.int32, torch.int64) else t
+        if t.dtype in (torch.int32, torch.int64):
+            t = t.long()
+        elif dtype is not None and t.is_floating_point():
+            t = t.to(dtype)
+        out[k] = t
     return out
