@@ -19,7 +19,6 @@ from __future__ import annotations
 
 from typing import Dict, List, Optional
 
-import numpy as np
 import torch
 import torch.nn as nn
 
@@ -106,6 +105,18 @@ class _LazyFlag:
         return repr(bool(self))
 
 
+class _TrainState:
+    """The training state of one ``Network``, shared by the training-mode forward and ``train_step``: the pipeline's trainers
+    (deepsir_amd/train.py), whose flat device buffers ARE the module's parameters and BatchNorm running statistics.
+    ``main`` receives gradients and holds the Adam moments and step count; ``frozen`` only move their running statistics."""
+
+    def __init__(self, dev: torch.device, main, frozen: tuple, names: List[str], params: List[nn.Parameter]):
+        self.dev, self.main, self.frozen = dev, main, frozen
+        self.names, self.params = names, params          # what receives gradients, in ``main``'s order
+        self.engine: Optional[Engine] = None             # the training forward's own engine (Network._train_engine)
+        self.stepper = self.stepper_key = None           # AlignTrainStep of train_step(frozen_mode='eval'): fixed batch geometry
+
+
 class Network(nn.Module):
     POOL_MIN_PAIRS = 64
     """Batches of that many pairs and more run on an ``EnginePool`` (two HIP streams): same bits, higher throughput."""
@@ -149,14 +160,14 @@ class Network(nn.Module):
             self.loss_feat_fun = DetDesLoss(self, args)
         else:
             self.loss_label_fun = SemanticLoss(self, args)
-        self._tstate = None               # trainers of the training-mode forward (their storage IS the module's parameters)
+        self._tstate: Optional[_TrainState] = None    # built by the first training call (_training_state)
         self.dropout_masks = None         # test aid: {'fe_src', 'fe_ref', 'inlier'} keep flags instead of random Dropout draws
 
     # ---- checkpoint plumbing
     def load_state_dict(self, state_dict, strict: bool = True):
         r = super().load_state_dict(state_dict, strict=strict)
         self._dirty = self._pool_dirty = self._server_dirty = True
-        self._trainer = self._frozen_trainers = self._stepper = self._stepper_key = None     # they hold the previous weights
+        self._tstate = None           # Adam moments and step count start again; rebuilt over the new weights by the next training call
         return r
 
     def _device_index(self) -> int:
@@ -239,45 +250,43 @@ class Network(nn.Module):
         return None, endpoints
 
     # ---- forward in TRAINING mode (train.py:379 my_model.train(); :401): outputs with a grad_fn that leads into the parameters
-    def _training_state(self, dev: torch.device):
-        """The pipeline's trainers (deepsir_amd/train.py) over THIS module's tensors: after the first training forward a trainable
+    def _training_state(self, dev: torch.device) -> _TrainState:
+        """The pipeline's trainers (deepsir_amd/train.py) over THIS module's tensors: from the first training call on a trainable
         ``nn.Parameter`` (and every BatchNorm running statistic) is a view of its trainer's flat device buffer, so what
-        ``optimizer.step()`` writes is what the next training forward computes with - no copies either way."""
+        ``optimizer.step()`` or ``train_step`` writes is what the next training forward computes with - no copies either way."""
         from . import train as T
         st = self._tstate
         named = dict(self.named_parameters())
         named.update(dict(self.named_buffers()))
         if st is not None:
-            k0, v0 = next(iter(st["main"].params.items()))
-            if st["dev"] == dev and named[k0].data_ptr() == v0.data_ptr():
+            k0, v0 = next(iter(st.main.params.items()))
+            if st.dev == dev and named[k0].data_ptr() == v0.data_ptr():
                 return st
         sd = self.state_dict()
+        extractor = lambda: T.RandlaTrainer(self.cfg, sd, "feat_extractor", self.cfg.feat_len, self.cfg.num_classes, dev)
         if self.pipeline == "align":
-            main = T.RandlaTrainer(self.cfg, sd, "inlier_model", 6, 1, dev)
-            frozen = (T.RandlaTrainer(self.cfg, sd, "feat_extractor", self.cfg.feat_len, self.cfg.num_classes, dev), T.AggregationTrainer(self.cfg, sd, dev))
+            main, frozen = T.RandlaTrainer(self.cfg, sd, "inlier_model", 6, 1, dev), (extractor(), T.AggregationTrainer(self.cfg, sd, dev))
         elif self.pipeline == "label":
-            main, frozen = T.RandlaTrainer(self.cfg, sd, "feat_extractor", self.cfg.feat_len, self.cfg.num_classes, dev), ()
+            main, frozen = extractor(), ()
         else:
-            main = T.AggregationTrainer(self.cfg, sd, dev)
-            frozen = (T.RandlaTrainer(self.cfg, sd, "feat_extractor", self.cfg.feat_len, self.cfg.num_classes, dev),)
+            main, frozen = T.AggregationTrainer(self.cfg, sd, dev), (extractor(),)
         with torch.no_grad():
-            for tr in (main,) + tuple(frozen):
+            for tr in (main,) + frozen:
                 for k, v in list(tr.params.items()) + list(tr.buffers.items()):
                     named[k].data = v.view(named[k].shape)
-        eng = Engine(self.cfg, dev.index or 0, 1024, 1)          # the weight-free operators of the training forward (score, arg-min, Kabsch, loss)
-        eng.load_state_dict({k: v for k, v in sd.items()})
-        self._tstate = st = {"dev": dev, "main": main, "frozen": frozen, "engine": eng, "names": [k for k in main.params if named[k].requires_grad]}
-        st["params"] = [named[k] for k in st["names"]]
+        names = [k for k in main.params if named[k].requires_grad]
+        self._tstate = st = _TrainState(dev, main, frozen, names, [named[k] for k in names])
         return st
 
-    def _train_engine(self, st, n_points: int, pairs: int) -> Engine:
-        eng = st["engine"]
-        if n_points > eng.max_points or pairs > eng.max_pairs:
-            # not closed: the endpoints of an earlier forward may still hold it for their loss (_AlignLoss); Engine.__del__
-            # frees it once the last of them is gone
-            eng = Engine(self.cfg, st["dev"].index or 0, max(n_points, eng.max_points), max(pairs, eng.max_pairs))
+    def _train_engine(self, st: _TrainState, n_points: int, pairs: int) -> Engine:
+        """The weight-free operators of the training forward (score, arg-min, Kabsch, loss)."""
+        eng = st.engine
+        have = (eng.max_points, eng.max_pairs) if eng is not None else (1024, 1)
+        if eng is None or n_points > have[0] or pairs > have[1]:
+            # an outgrown engine is not closed: the endpoints of an earlier forward may still hold it for their loss (_AlignLoss);
+            # Engine.__del__ frees it once the last of them is gone
+            st.engine = eng = Engine(self.cfg, st.dev.index or 0, max(n_points, have[0]), max(pairs, have[1]))
             eng.load_state_dict({k: v for k, v in self.state_dict().items()})
-            st["engine"] = eng
         return eng
 
     def _pyramids(self, eng: Engine, data, src, ref) -> dict:
@@ -299,6 +308,18 @@ class Network(nn.Module):
         seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
         return {k: T.dropout_keep_masks(seed + 7919 * i, shp, dev) for i, (k, shp) in enumerate(shapes.items())}
 
+    @staticmethod
+    def _seeded_masks(seed: Optional[int], B: int, J: int, K: int, dev, n_iter: Optional[int] = None) -> Optional[dict]:
+        """Keep flags of one ``train_step`` with ``dropout_seed`` (None: dropout off): the frozen extractor's from 3 seed + 1 (src) and
+        3 seed + 2 (ref); with ``n_iter`` the inlier model's from the seed itself, as the frozen_mode='eval' variant draws them."""
+        from . import train as T
+        if seed is None:
+            return None
+        masks = {"fe_src": T.dropout_keep_masks(3 * int(seed) + 1, (B, J, 64), dev), "fe_ref": T.dropout_keep_masks(3 * int(seed) + 2, (B, K, 64), dev)}
+        if n_iter is not None:
+            masks["inlier"] = T.dropout_keep_masks(int(seed), (n_iter, B, J, 64), dev)
+        return masks
+
     def _forward_train(self, data: Dict[str, torch.Tensor], opt=None):
         from . import se3
         from . import train as T
@@ -311,7 +332,7 @@ class Network(nn.Module):
         K = ref.shape[1]
         st = self._training_state(dev)
         eng = self._train_engine(st, max(J, K), B)
-        main, frozen, params, names = st["main"], st["frozen"], st["params"], st["names"]
+        main, frozen, params, names = st.main, st.frozen, st.params, st.names
         batch = self._pyramids(eng, data, src, ref)
         self._dirty = self._pool_dirty = self._server_dirty = True      # running statistics move now, the weights at optimizer.step()
 
@@ -474,46 +495,26 @@ class Network(nn.Module):
           label: trains ``feat_extractor`` through SemanticLoss (data: labels_src / labels_ref [B,N] in 0..19);
           feat:  trains ``mlp_feat`` / ``mlp_att`` / ``mlp_proj`` through DetDesLoss (data: transform_gt; needs num_sub > 0); frozen_mode
                  as for align: 'train' runs the frozen extractor in training mode, 'eval' takes the key points from the engine.
-        The updated tensors are written back into this module's buffers (``state_dict()`` is the trained checkpoint) and
-        serve the next ``forward``.  Adam state lives in the trainer kept on the module.  Returns the step's dict (loss ...)."""
+        The step updates this module's own tensors - they are views of the trainers' device buffers (``_training_state``), shared with
+        the training-mode forward - so ``state_dict()`` is the trained checkpoint and the next ``forward`` serves it.  Adam state lives
+        in that state's main trainer; ``load_state_dict`` resets it.  Returns the step's dict (loss ...)."""
         from . import train as T
         src, ref = data["points_src"].float(), data["points_ref"].float()
         B, J, _ = src.shape
-        eng = self._ensure_engine(max(J, ref.shape[1]), B)
+        K = ref.shape[1]
         dev = src.device
-        sd = self.state_dict()
-        if getattr(self, "_trainer", None) is None:
-            if self.pipeline == "align":
-                self._trainer = T.RandlaTrainer(self.cfg, sd, "inlier_model", 6, 1, dev)
-            elif self.pipeline == "label":
-                self._trainer = T.RandlaTrainer(self.cfg, sd, "feat_extractor", self.cfg.feat_len, self.cfg.num_classes, dev)
-            else:
-                self._trainer = T.AggregationTrainer(self.cfg, sd, dev)
-        tr = self._trainer
-        batch = {"points_src": src, "points_ref": ref}
-        for s_, pts in (("src", src), ("ref", ref)):
-            if all(f"points_{s_}_{k}" in data for k in _PYR_KEYS):
-                pyr = [data[f"points_{s_}_xyz"].float()] + [data[f"points_{s_}_{k}"].to(torch.int32) for k in _PYR_KEYS[1:]]
-            else:
-                pyr = eng.knn_pyramid(pts)
-            batch[f"{s_}_xyz"], batch[f"{s_}_neigh"], batch[f"{s_}_sub"], batch[f"{s_}_interp"] = [t.contiguous() for t in pyr]
+        eng = self._ensure_engine(max(J, K), B)
+        st = self._training_state(dev)
+        tr = st.main
+        batch = self._pyramids(eng, data, src, ref)
         if self.pipeline == "align" and frozen_mode == "train":
             n_iter = int(opt[0]) if opt is not None else self.cfg.num_reg_iter
-            if getattr(self, "_frozen_trainers", None) is None:
-                self._frozen_trainers = (T.RandlaTrainer(self.cfg, sd, "feat_extractor", self.cfg.feat_len, self.cfg.num_classes, dev),
-                                         T.AggregationTrainer(self.cfg, sd, dev))
-            fe, ag = self._frozen_trainers
-            masks = None
-            if dropout_seed is not None:     # the inlier model's masks are those of the 'eval' variant (train.dropout_keep_masks)
-                sd_ = int(dropout_seed)
-                masks = {"inlier": T.dropout_keep_masks(sd_, (n_iter, B, J, 64), dev),
-                         "fe_src": T.dropout_keep_masks(3 * sd_ + 1, (B, J, 64), dev),
-                         "fe_ref": T.dropout_keep_masks(3 * sd_ + 2, (B, ref.shape[1], 64), dev)}
+            fe, ag = st.frozen
             fn = None
             if "matches" in data:
                 fn = lambda idx: torch.from_numpy(T.find_correct_correspondence(data["matches"], idx, J)).to(dev)
-            out = T.train_step_align_full(eng, tr, fe, ag, batch, data["transform_gt"].float().to(dev), n_iter, fn, lr, masks, loss_kwargs,
-                                          dist=dist)
+            out = T.train_step_align_full(eng, tr, fe, ag, batch, data["transform_gt"].float().to(dev), n_iter, fn, lr,
+                                          self._seeded_masks(dropout_seed, B, J, K, dev, n_iter), loss_kwargs, dist=dist)
             out["loss"] = out["losses"]["total"]
         elif self.pipeline == "align":
             n_iter = int(opt[0]) if opt is not None else self.cfg.num_reg_iter
@@ -521,10 +522,10 @@ class Network(nn.Module):
             labels = None
             if "matches" in data:
                 labels = torch.from_numpy(T.find_correct_correspondence(data["matches"], res["idx"], J)).to(dev)
-            key = (id(eng), B, J, ref.shape[1], n_iter)
-            if getattr(self, "_stepper_key", None) != key:                      # hipGraph-replayed halves, fixed batch geometry
-                self._stepper, self._stepper_key = T.AlignTrainStep(eng, tr, B, J, ref.shape[1], n_iter), key
-            out = self._stepper.step(batch, res, data["transform_gt"].float().to(dev), labels, lr, dropout_seed, loss_kwargs, dist=dist)
+            key = (id(eng), B, J, K, n_iter)
+            if st.stepper_key != key:                                           # hipGraph-replayed halves, fixed batch geometry
+                st.stepper, st.stepper_key = T.AlignTrainStep(eng, tr, B, J, K, n_iter), key
+            out = st.stepper.step(batch, res, data["transform_gt"].float().to(dev), labels, lr, dropout_seed, loss_kwargs, dist=dist)
             out["loss"] = out["losses"]["total"]
         elif self.pipeline == "label":
             out = T.train_step_label(tr, batch, data["labels_src"].to(torch.int32).to(dev), data["labels_ref"].to(torch.int32).to(dev), lr,
@@ -533,27 +534,14 @@ class Network(nn.Module):
             if self.cfg.num_sub <= 0:
                 raise EngineError("pipeline='feat' trains on the top-num_sub key points: set args.num_sub > 0")
             if frozen_mode == "train":      # the frozen extractor in training mode, as my_model.train() leaves it
-                if getattr(self, "_frozen_trainers", None) is None:
-                    self._frozen_trainers = (T.RandlaTrainer(self.cfg, sd, "feat_extractor", self.cfg.feat_len, self.cfg.num_classes, dev),)
-                masks = None
-                if dropout_seed is not None:
-                    masks = {f"fe_{s_}": T.dropout_keep_masks(3 * int(dropout_seed) + o_, (B, n_, 64), dev)
-                             for s_, n_, o_ in (("src", J, 1), ("ref", ref.shape[1], 2))}
-                inp = T.feat_pipeline_inputs_train(eng, self._frozen_trainers[0], batch, self.cfg.num_sub, masks)
+                inp = T.feat_pipeline_inputs_train(eng, st.frozen[0], batch, self.cfg.num_sub, self._seeded_masks(dropout_seed, B, J, K, dev))
             else:
                 inp = T.feat_pipeline_inputs(eng, batch, self.cfg.num_sub)
             out = T.train_step_feat(tr, inp, data["transform_gt"].float().to(dev), thres_radius, det_loss_weight, lr, dist=dist)
-        # written back on skipped steps too: the parameters are then unchanged, but the BatchNorm running statistics moved in
-        # the forward pass whatever optimizer.step() did afterwards (train.py:401 runs before :437-446)
-        new = tr.state_dict()
-        for ft in (getattr(self, "_frozen_trainers", None) or ()):          # frozen weights, moving running statistics
-            new.update({k: v.detach().cpu().numpy().reshape(ft._shapes[k]) for k, v in ft.buffers.items()})
-        with torch.no_grad():
-            own = dict(self.named_buffers())
-            own.update(dict(self.named_parameters()))
-            for k, v in new.items():
-                own[k].copy_(torch.from_numpy(np.ascontiguousarray(v)).to(own[k].device))
-        self._dirty = True
+        # on skipped steps too: the parameters are then unchanged, but the BatchNorm running statistics moved in the forward pass
+        # whatever optimizer.step() did afterwards (train.py:401 runs before :437-446).  The kernels wrote the shared buffers
+        # directly, which bumps no version counter (_check_weights_touched): the inference engines are told here.
+        self._dirty = self._pool_dirty = self._server_dirty = True
         return out
 
     # ---- the optimiser's checkpoint entry (CheckPointManager saves optimizer.state_dict(), common/torch_utils.py:62-67)
@@ -565,7 +553,7 @@ class Network(nn.Module):
         """What ``torch.optim.Adam(my_model.parameters(), lr).state_dict()`` would hold after the steps taken through
         ``train_step``: state entries (by parameter index) for the tensors that received gradients, one param group."""
         order = self._param_order()
-        tr = getattr(self, "_trainer", None)
+        tr = self._tstate.main if self._tstate is not None else None
         named = tr.adam_state() if tr is not None and tr.step_count > 0 else {}
         state = {i: named[k] for i, k in enumerate(order) if k in named}
         group = {"lr": lr, "betas": (0.9, 0.999), "eps": 1e-8, "weight_decay": 0, "amsgrad": False, "maximize": False, "foreach": None,
@@ -573,22 +561,13 @@ class Network(nn.Module):
         return {"state": state, "param_groups": [group]}
 
     def load_optimizer_state_dict(self, sd: dict) -> None:
-        """Resume the device optimiser from a reference checkpoint's 'optimizer' entry (call after the first ``train_step`` built
-        the trainer, or after ``prepare_training``)."""
-        tr = getattr(self, "_trainer", None)
-        if tr is None:
-            raise EngineError("no trainer yet: call prepare_training(device) or train_step first")
+        """Resume the device optimiser from a reference checkpoint's 'optimizer' entry (call after ``prepare_training``, or after the
+        first ``train_step`` built the training state)."""
+        if self._tstate is None:
+            raise EngineError("no trainer yet: call prepare_training() or train_step first")
         order = self._param_order()
-        tr.load_adam_state({order[int(i)]: st for i, st in sd["state"].items()})
+        self._tstate.main.load_adam_state({order[int(i)]: st for i, st in sd["state"].items()})
 
     def prepare_training(self) -> None:
-        """Builds the pipeline's trainer from the current weights (train_step does it lazily)."""
-        from . import train as T
-        dev = next(self.buffers()).device
-        sd = self.state_dict()
-        if self.pipeline == "align":
-            self._trainer = T.RandlaTrainer(self.cfg, sd, "inlier_model", 6, 1, dev)
-        elif self.pipeline == "label":
-            self._trainer = T.RandlaTrainer(self.cfg, sd, "feat_extractor", self.cfg.feat_len, self.cfg.num_classes, dev)
-        else:
-            self._trainer = T.AggregationTrainer(self.cfg, sd, dev)
+        """Builds the training state from the current weights (train_step and the training forward do it lazily)."""
+        self._training_state(torch.device("cuda", self._device_index()))

@@ -155,7 +155,7 @@ def test_interleaved_training_passes_accumulate_like_autograd(pipeline, order):
         C = cs["C"]
         ep_a = _forward(net, A)
         ep_c = _forward(net, C)
-        assert net._tstate["engine"].max_points >= SIZES["C"]
+        assert net._tstate.engine.max_points >= SIZES["C"]
         _loss(net, ep_a, A).backward()
         _loss(net, ep_c, C).backward()
         want = {k: g["A"][k] + g["C"][k] for k in g["A"]}

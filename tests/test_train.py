@@ -838,7 +838,7 @@ def test_optimizer_state_round_trips_with_torch_adam():
     net.load_state_dict(to_torch_state_dict(sd))
     net.cuda()
     net.prepare_training()
-    tr = net._trainer
+    tr = net._tstate.main
     order = net._param_order()
     ref_params = [torch.nn.Parameter(torch.from_numpy(np.array(sd[k])).clone()) for k in order]
     opt = torch.optim.Adam(ref_params, lr=2e-3)
@@ -868,14 +868,15 @@ def test_optimizer_state_round_trips_with_torch_adam():
     net2.cuda()
     net2.prepare_training()
     net2.load_optimizer_state_dict(theirs)
+    tr2 = net2._tstate.main
     for i in trained:
         gr = torch.randn(ref_params[i].shape, generator=g)
         ref_params[i].grad = gr.clone()
-        net2._trainer.grads[order[i]].copy_(gr.reshape(net2._trainer.grads[order[i]].shape).cuda())
+        tr2.grads[order[i]].copy_(gr.reshape(tr2.grads[order[i]].shape).cuda())
     opt.step()
-    net2._trainer.adam_step(2e-3)
+    tr2.adam_step(2e-3)
     for i in trained:
-        assert torch.allclose(net2._trainer.params[order[i]].cpu().reshape(ref_params[i].shape), ref_params[i].detach(), rtol=1e-5, atol=2e-6)
+        assert torch.allclose(tr2.params[order[i]].cpu().reshape(ref_params[i].shape), ref_params[i].detach(), rtol=1e-5, atol=2e-6)
 
 
 # --------------------------------------------------------------------------- dW scratch sizing
