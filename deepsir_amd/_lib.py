@@ -169,6 +169,18 @@ SYMBOLS = {
     "dsir_t_any_nan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "dsir_t_adam": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_float,
                               C.c_float, C.c_int]),
+    # ground-truth matches and inlier targets (csrc/match_targets.hip)
+    "dsir_t_radius_matches_scratch": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "dsir_t_radius_matches_count": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float,
+                                              C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dsir_t_radius_matches_fill": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
+    "dsir_t_inlier_targets_radius": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                               C.c_int, C.c_float, C.c_void_p]),
+    "dsir_t_match_keys_scratch": (C.c_size_t, [C.c_int64, C.c_int]),
+    "dsir_t_match_keys": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]),
+    "dsir_t_inlier_targets_matches": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64,
+                                                C.c_void_p]),
 }
 
 _lib = None

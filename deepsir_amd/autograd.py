@@ -77,12 +77,16 @@ class _AlignLoss(torch.autograd.Function):
 class ScanAlignmentLoss:
     """``my_model.loss_align_fun`` (reference network/loss.py:705-851; wt_pose_loss = 0, its default).  data: the endpoints of an
     `align` forward plus 'transform_gt' [B,3,4] and optionally 'matches' (per pair an int [n',2] array, as the reference's loader
-    gives) for the correspondence-confidence term.  reduction 'mean': scalar tensors, 'total' carries the gradient back into the
+    gives, or a ``train.MatchKeys``) for the correspondence-confidence term; without a list, 'match_radius' in data or ``match_radius=``
+    here (or ``args.match_radius``) gives the same 0/1 targets from the geometry: |T_gt src_j - ref_idx[j]| < radius.  Either way
+    the targets are made on the device (``deepsir_amd.train.inlier_targets``).  reduction 'mean': scalar tensors, 'total' carries the gradient back into the
     inlier model (through the forward's tape when the forward ran in training mode); 'none': per-pair values [B] (validation,
     train.py:136), no gradient."""
 
-    def __init__(self, net, args):
+    def __init__(self, net, args, match_radius: Optional[float] = None):
         self._net = net
+        self._ops = None
+        self.match_radius = match_radius if match_radius is not None else getattr(args, "match_radius", None)
         self.loss_type = getattr(args, "loss_type", "mae")
         self.wt_ptDist_loss = float(getattr(args, "wt_ptDist_loss", 1.0))
         self.wt_inlier_loss = float(getattr(args, "wt_inlier_loss", 1.0))
@@ -94,7 +98,7 @@ class ScanAlignmentLoss:
             raise NotImplementedError("wt_pose_loss > 0 (off by default, arguments.py:57) is outside the accelerated path")
 
     def __call__(self, data: Dict, reduction=None):
-        from .train import find_correct_correspondence
+        from .train import _Ops, inlier_targets
         if reduction not in ("mean", "none"):
             raise AssertionError("reduction must be 'mean' or 'none' (reference loss.py:765)")
         tr = data.get("_train")
@@ -109,10 +113,14 @@ class ScanAlignmentLoss:
         if idx is None:     # materialised CPU pairs [B, J, 2] per iteration (the reference's own layout)
             idx = torch.stack([torch.as_tensor(p)[:, :, 1] for p in pp]).to(torch.int32).to(dev)
         idx = idx.to(torch.int32).contiguous()
-        labels = None
-        if self.wt_inlier_loss > 0 and "matches" in data:
-            labels = torch.from_numpy(find_correct_correspondence(data["matches"], idx, J)).to(dev)
         T_gt = data["transform_gt"].float().to(dev).contiguous()
+        # the confidence term's targets, on the device: from the match list when there is one, else from a radius and the geometry
+        labels = None
+        radius = data.get("match_radius", self.match_radius)
+        if self.wt_inlier_loss > 0 and ("matches" in data or radius is not None):
+            if self._ops is None or self._ops.device != dev:
+                self._ops = _Ops(dev)
+            labels = inlier_targets(self._ops, idx, J, data.get("matches"), radius, pt_src, pt_ref, T_gt)
         eng = tr["engine"] if tr is not None else self._net._ensure_engine(max(J, pt_ref.shape[1]), B)
         kw = dict(loss_type=self.loss_type, wt_ptDist_loss=self.wt_ptDist_loss, wt_inlier_loss=self.wt_inlier_loss,
                   loss_discount_factor=self.discount_factor)

@@ -494,6 +494,36 @@ class Engine:
             out["losses_per_pair"] = dd
         return out
 
+    # ------------------------------------------------------------------ ground-truth matches / inlier targets (include/dsir_train.h)
+    def _train_ops(self):
+        """The stream-ordered training operators on torch's current stream (deepsir_amd/train.py::_Ops)."""
+        from .train import _Ops
+        if getattr(self, "_tops", None) is None:
+            self._tops = _Ops(self.device)
+        self._tops.begin()
+        return self._tops
+
+    def radius_matches(self, src, ref, transform_gt, radius: float):
+        """The reference loader's get_matching_indices (K = None) for P pairs, brute force on the device: src [P,J,C], ref [P,K,C],
+        transform_gt [P,3,4] -> the CSR (offsets [P J + 1] i32, cols [total] i32, ascending per row) of every (j, k) with
+        |T_gt src_j - ref_k| < radius.  ``train.as_reference_matches`` turns it into data['matches']."""
+        src, ref = _chk(src, torch.float32, "src"), _chk(ref, torch.float32, "ref")
+        return self._train_ops().radius_matches(src, ref, _chk(transform_gt, torch.float32, "transform_gt"), radius)
+
+    def match_keys(self, matches: Sequence, hash_seed: int):
+        """A batch's match lists (per pair int [n',2] of (src, ref)) hashed and sorted on the device, once per batch."""
+        return self._train_ops().match_keys(matches, hash_seed)
+
+    def inlier_targets_matches(self, keys, idx):
+        """find_correct_correspondence on the device: idx [n_iter,P,J] i32 -> fp32 0/1 [n_iter,P,J]."""
+        return self._train_ops().inlier_targets_matches(keys, _chk(idx, torch.int32, "idx"))
+
+    def inlier_targets_radius(self, src, ref, idx, transform_gt, radius: float):
+        """The same targets from geometry alone (the rule of ``radius_matches``): 1 iff |T_gt src_j - ref_idx[j]| < radius."""
+        src, ref = _chk(src, torch.float32, "src"), _chk(ref, torch.float32, "ref")
+        return self._train_ops().inlier_targets_radius(src, ref, _chk(idx, torch.int32, "idx"), _chk(transform_gt, torch.float32, "transform_gt"),
+                                                       radius)
+
     def enable_graph(self, on=True):
         """Replay dsir_register through a captured hipGraph (same buffers on every call; one graph per call signature)."""
         if on:

@@ -483,11 +483,14 @@ class Network(nn.Module):
     # ---- one optimisation step of the pipeline: train.py:396-448 without autograd (deepsir_amd/train.py)
     def train_step(self, data: Dict[str, torch.Tensor], opt=None, lr: float = 1e-3, dropout_seed: Optional[int] = None,
                    thres_radius: float = 0.1, det_loss_weight: float = 1.0, loss_kwargs: Optional[dict] = None, dist=None,
-                   frozen_mode: str = "train") -> dict:
+                   frozen_mode: str = "train", match_radius: Optional[float] = None) -> dict:
         """What the reference's loop does per batch - ``my_model(train_data, opt)``, ``loss_*_fun``, ``loss.backward()``,
         ``optimizer.step()`` (train.py:396-448) - for this network's pipeline, on the device:
           align: trains ``inlier_model`` (the only sub-network ScanAlignmentLoss reaches; data: transform_gt [B,3,4] and,
-                 for the confidence term, ``matches`` = per pair an int [n',2] array as the reference's data loader gives).
+                 for the confidence term, ``matches`` = per pair an int [n',2] array as the reference's data loader gives, or a
+                 ``train.MatchKeys``; without a list, ``match_radius`` - the argument or data['match_radius'] - gives the same
+                 targets from the geometry: (j, idx[j]) is a match iff |T_gt src_j - ref_idx[j]| < radius.  The targets are
+                 made on the device, ``deepsir_amd.train.inlier_targets``).
                  frozen_mode 'train' (default): the whole network in training mode as ``my_model.train()`` leaves it - the
                  frozen sub-networks' BatchNorm on batch statistics, their running statistics moving, Dropout on
                  (``train_step_align_full``); 'eval': the frozen half from ONE inference pass of the engine (faster; the
@@ -507,21 +510,30 @@ class Network(nn.Module):
         st = self._training_state(dev)
         tr = st.main
         batch = self._pyramids(eng, data, src, ref)
+        # the confidence term's 0/1 targets, on the device (deepsir_amd/train.py::inlier_targets): from the caller's match list - its
+        # keys are built ONCE per step, not per iteration -, else from the radius and the geometry, else no term
+        targets = None
+        if self.pipeline == "align":
+            radius = data.get("match_radius", match_radius)
+            if "matches" in data:
+                m = data["matches"]
+                tr.ops.begin()
+                targets = {"matches": m if isinstance(m, T.MatchKeys) else tr.ops.match_keys(m, J)}
+            elif radius is not None:
+                targets = {"match_radius": float(radius), "src": src, "ref": ref, "transform_gt": data["transform_gt"].to(dev)}
         if self.pipeline == "align" and frozen_mode == "train":
             n_iter = int(opt[0]) if opt is not None else self.cfg.num_reg_iter
             fe, ag = st.frozen
             fn = None
-            if "matches" in data:
-                fn = lambda idx: torch.from_numpy(T.find_correct_correspondence(data["matches"], idx, J)).to(dev)
+            if targets is not None:
+                fn = lambda idx: T.inlier_targets(tr.ops, idx, J, **targets)
             out = T.train_step_align_full(eng, tr, fe, ag, batch, data["transform_gt"].float().to(dev), n_iter, fn, lr,
                                           self._seeded_masks(dropout_seed, B, J, K, dev, n_iter), loss_kwargs, dist=dist)
             out["loss"] = out["losses"]["total"]
         elif self.pipeline == "align":
             n_iter = int(opt[0]) if opt is not None else self.cfg.num_reg_iter
             res = eng.register(src, ref, n_iter)
-            labels = None
-            if "matches" in data:
-                labels = torch.from_numpy(T.find_correct_correspondence(data["matches"], res["idx"], J)).to(dev)
+            labels = None if targets is None else T.inlier_targets(tr.ops, res["idx"], J, **targets)
             key = (id(eng), B, J, K, n_iter)
             if st.stepper_key != key:                                           # hipGraph-replayed halves, fixed batch geometry
                 st.stepper, st.stepper_key = T.AlignTrainStep(eng, tr, B, J, K, n_iter), key

@@ -33,7 +33,9 @@ def find_correct_correspondence(matches: Sequence, idx: "np.ndarray | torch.Tens
     """ScanAlignmentLoss.find_correct_correspondence with ``_hash`` (network/loss.py:280-294, :723-749; host work in the
     reference too): is the predicted pair (j, idx[j]) among the ground-truth matches of its cloud pair?
     matches: per pair an int array [n', 2] of (src, ref) indices; idx [n_iter][P][J] (``pred_pairs[i][..., 1]``);
-    hash_seed: the reference passes points_src.shape[1] (:819).  -> float32 [n_iter][P][J] of 0 / 1 (the BCE targets)."""
+    hash_seed: the reference passes points_src.shape[1] (:819).  -> float32 [n_iter][P][J] of 0 / 1 (the BCE targets).
+    The host restatement: ``inlier_targets`` below computes the same values on the device (csrc/match_targets.hip) and is what the
+    training step calls; the tests compare the two."""
     ix = idx.detach().cpu().numpy() if isinstance(idx, torch.Tensor) else np.asarray(idx)
     n_iter, P, J = ix.shape
     out = np.zeros((n_iter, P, J), np.float32)
@@ -278,6 +280,109 @@ class _Ops:
         self._ok(self.lib.dsir_t_inlier_input(self.stream, _ptr(xyz_src), _ptr(xyz_ref), _ptr(idx), _ptr(T), 0 if T is None else T.stride(0),
                                               P, J, xyz_ref.shape[1], _ptr(out)), "dsir_t_inlier_input")
         return out
+
+    # ---- ground-truth matches and inlier targets (csrc/match_targets.hip; the distance rule is stated in include/dsir_train.h)
+    def radius_matches(self, src: torch.Tensor, ref: torch.Tensor, transform_gt: torch.Tensor, radius: float):
+        """get_matching_indices with K = None (dataloader/data_base.py:436-449) for P pairs: every (j, k) with
+        |T_gt src_j - ref_k| < radius, as a device CSR.  src [P][J][C], ref [P][K][C] (first three columns), transform_gt [P][3][4]
+        -> (offsets [P J + 1] i32, cols [total] i32: row (p, j)'s reference indices in ascending order).  Two brute-force passes
+        and ONE 4-byte read of the total in between, to size ``cols``: data-path work, once per batch."""
+        P, J, stride = src.shape
+        K = ref.shape[1]
+        if ref.shape[0] != P or ref.shape[2] != stride or tuple(transform_gt.shape) != (P, 3, 4):
+            raise ValueError("radius_matches: src [P,J,C], ref [P,K,C] and transform_gt [P,3,4] expected")
+        nb = int(self.lib.dsir_t_radius_matches_scratch(P, J, K))
+        if nb == 0:
+            raise ValueError(f"radius_matches: {P} x {J} x {K} distance tests exceed the int32 range of the offsets: split the batch")
+        counts = self.empty(P * J, dtype=torch.int32)
+        offsets = self.empty(P * J + 1, dtype=torch.int32)
+        scratch = torch.empty(nb, dtype=torch.uint8, device=self.device)
+        self._ok(self.lib.dsir_t_radius_matches_count(self.stream, _ptr(src), _ptr(ref), stride, _ptr(transform_gt), P, J, K, float(radius),
+                                                      _ptr(counts), _ptr(offsets), _ptr(scratch)), "dsir_t_radius_matches_count")
+        total = int(offsets[-1].item())
+        if total < 0:
+            raise RuntimeError("radius_matches: more than 2^31 - 1 matches: split the batch or lower the radius")
+        cols = self.empty(total, dtype=torch.int32)
+        self._ok(self.lib.dsir_t_radius_matches_fill(self.stream, _ptr(src), _ptr(ref), stride, _ptr(transform_gt), P, J, K, float(radius),
+                                                     _ptr(offsets), _ptr(scratch), _ptr(cols) if total else None, total),
+                 "dsir_t_radius_matches_fill")
+        return offsets, cols
+
+    def inlier_targets_radius(self, src: torch.Tensor, ref: torch.Tensor, idx: torch.Tensor, transform_gt: torch.Tensor, radius: float):
+        """The BCE targets from geometry alone: labels[i][p][j] = 1 iff |T_gt src_j - ref_idx[i][p][j]| < radius (the rule of
+        ``radius_matches``, bit for bit).  idx [n_iter][P][J] i32 -> fp32 [n_iter][P][J]."""
+        n_iter, P, J = idx.shape
+        labels = self.empty(n_iter, P, J)
+        self._ok(self.lib.dsir_t_inlier_targets_radius(self.stream, _ptr(src), _ptr(ref), src.shape[2], _ptr(idx), _ptr(transform_gt), n_iter, P, J,
+                                                       ref.shape[1], float(radius), _ptr(labels)), "dsir_t_inlier_targets_radius")
+        return labels
+
+    def match_keys(self, matches: Sequence, hash_seed: int) -> "MatchKeys":
+        """The reference's hashed match list (loss.py:280-294) on the device, sorted per pair.  matches: per pair an int array or
+        tensor [n', 2] of (src, ref), host or device; one upload of the concatenated list per batch."""
+        P = len(matches)
+        n = [int(m.shape[0]) for m in matches]
+        total = int(sum(n))
+        seg = torch.tensor(np.concatenate([[0], np.cumsum(n)]).astype(np.int32), device=self.device)
+        keys = torch.empty(total, dtype=torch.int64, device=self.device)
+        if total:
+            if all(isinstance(m, torch.Tensor) and m.is_cuda for m in matches):
+                flat = torch.cat([m.reshape(-1, 2) for m in matches]).to(torch.int32).contiguous()
+            else:
+                host = np.concatenate([(m.detach().cpu().numpy() if isinstance(m, torch.Tensor) else np.asarray(m)).reshape(-1, 2) for m in matches])
+                if host.size and (host.min() < -2 ** 31 or host.max() >= 2 ** 31):
+                    raise ValueError("match_keys: indices outside the int32 range")
+                flat = torch.from_numpy(np.ascontiguousarray(host.astype(np.int32))).to(self.device)
+            scratch = torch.empty(int(self.lib.dsir_t_match_keys_scratch(total, P)), dtype=torch.uint8, device=self.device)
+            self._ok(self.lib.dsir_t_match_keys(self.stream, _ptr(flat), _ptr(seg), total, P, int(hash_seed), _ptr(keys), _ptr(scratch)),
+                     "dsir_t_match_keys")
+        return MatchKeys(keys, seg, P, int(hash_seed))
+
+    def inlier_targets_matches(self, keys: "MatchKeys", idx: torch.Tensor) -> torch.Tensor:
+        """find_correct_correspondence on the device: labels[i][p][j] = 1 iff j + idx[i][p][j] * hash_seed is among pair p's keys."""
+        n_iter, P, J = idx.shape
+        if P != keys.pairs:
+            raise ValueError(f"inlier_targets_matches: idx holds {P} pairs, the match list {keys.pairs}")
+        labels = self.empty(n_iter, P, J)
+        self._ok(self.lib.dsir_t_inlier_targets_matches(self.stream, _ptr(keys.keys) if keys.keys.numel() else None, _ptr(keys.offsets), _ptr(idx),
+                                                        n_iter, P, J, keys.hash_seed, _ptr(labels)), "dsir_t_inlier_targets_matches")
+        return labels
+
+
+class MatchKeys:
+    """A batch's ground-truth matches as ``_Ops.match_keys`` leaves them: keys int64 [n'] sorted within each pair, offsets [P + 1] i32.
+    May be handed over as ``data['matches']`` in place of the lists, so that a loader builds it once per batch."""
+    __slots__ = ("keys", "offsets", "pairs", "hash_seed")
+
+    def __init__(self, keys: torch.Tensor, offsets: torch.Tensor, pairs: int, hash_seed: int):
+        self.keys, self.offsets, self.pairs, self.hash_seed = keys, offsets, pairs, hash_seed
+
+
+def as_reference_matches(offsets: torch.Tensor, cols: torch.Tensor, P: int, J: int) -> List[np.ndarray]:
+    """The device CSR of ``radius_matches`` as the reference's data contract (``data['matches']``): per pair an int64 array
+    [n', 2] of (src, ref), source rows ascending and within a row the reference indices ascending (open3d lists a row by
+    distance; every consumer treats the list as a set)."""
+    off = offsets.detach().cpu().numpy().astype(np.int64)
+    col = cols.detach().cpu().numpy().astype(np.int64)
+    out = []
+    for p in range(P):
+        o = off[p * J:(p + 1) * J + 1]
+        out.append(np.stack([np.repeat(np.arange(J, dtype=np.int64), np.diff(o)), col[o[0]:o[-1]]], 1))
+    return out
+
+
+def inlier_targets(ops: "_Ops", idx: torch.Tensor, hash_seed: int, matches=None, match_radius: Optional[float] = None, src=None, ref=None,
+                   transform_gt=None) -> Optional[torch.Tensor]:
+    """The confidence term's targets for idx [n_iter][P][J], on the device: from ``matches`` (the reference's lists, or a ``MatchKeys``)
+    when given, else from ``match_radius`` and the geometry (src / ref [P][.][>=3], transform_gt [P][3][4]), else None (no term)."""
+    if matches is None and match_radius is None:
+        return None
+    ops.begin()
+    idx = idx.to(torch.int32).contiguous()
+    if matches is not None:
+        keys = matches if isinstance(matches, MatchKeys) else ops.match_keys(matches, hash_seed)
+        return ops.inlier_targets_matches(keys, idx)
+    return ops.inlier_targets_radius(src.float().contiguous(), ref.float().contiguous(), idx, transform_gt.float().contiguous(), float(match_radius))
 
 
 class _ParamStore:

@@ -138,6 +138,48 @@ int dsir_t_any_nan(void* stream, const float* x, int64_t n, int32_t* flag);
 int dsir_t_adam(void* stream, float* p, const float* g, float* m, float* v, int64_t n, float lr, float b1, float b2, float eps,
                 int step);
 
+/* ---- ground-truth matches and inlier targets of the `align` step (csrc/match_targets.hip) -------------------------------
+ * The reference's loader builds data['matches'] with an open3d KD-tree radius search around every T_gt src_i
+ * (dataloader/data_base.py:436-449, K = None: ALL reference points inside radius = voxel_size * positive_pair_radius_multiplier);
+ * ScanAlignmentLoss.find_correct_correspondence (network/loss.py:723-749) asks on the host whether (j, idx[j]) is in that list:
+ * the 0/1 targets of the confidence term.  open3d is not installable here: parity is unpinned, the engine owns the rule -
+ *   moved point, fp32, no fused multiply-add:  c_r = ((T[r][0] x + T[r][1] y) + T[r][2] z) + T[r][3]
+ *   squared distance as csrc/icp.hip forms it: d2 = (dx dx + dy dy) + dz dz, d = ref - c, every operation rounded
+ *   match  <=>  d2 < r r, r r one fp32 product; strict, as nanoflann's radius result set compares (from memory: it cannot be
+ *   checked here).
+ * Every operator below decides through this one rule, so they agree bit for bit.  No atomics: two runs give the same bytes.
+ * src [pairs][J][stride], ref [pairs][K][stride] (first three columns, stride >= 3), transform_gt [pairs][3][4]; pairs J K <= 2^31 - 1.
+ *
+ * The match list as CSR, in two passes (brute force, pairs J K distance tests each):
+ *   _count: counts [pairs J] = matches of every source row, offsets [pairs J + 1] = their exclusive sum (offsets[pairs J] = total);
+ *           scratch: dsir_t_radius_matches_scratch(pairs, J, K) bytes - it carries the per-slice counts over to _fill.
+ *   the caller reads offsets[pairs J] from the device and sizes cols;
+ *   _fill:  the SAME inputs, offsets and scratch -> cols [n_cols]: row (p, j)'s matching reference indices, ascending, at
+ *           offsets[p J + j].  Nothing is written at or past n_cols. */
+size_t dsir_t_radius_matches_scratch(int pairs, int J, int K);
+int dsir_t_radius_matches_count(void* stream, const float* src, const float* ref, int stride, const float* transform_gt, int pairs, int J,
+                                int K, float radius, int32_t* counts, int32_t* offsets, void* scratch);
+int dsir_t_radius_matches_fill(void* stream, const float* src, const float* ref, int stride, const float* transform_gt, int pairs, int J,
+                               int K, float radius, const int32_t* offsets, const void* scratch, int32_t* cols, int64_t n_cols);
+
+/* Targets from geometry: labels[i][p][j] = rule(T_gt[p], src[p][j], ref[p][idx[i][p][j]]) ? 1 : 0; idx [n_iter][pairs][J] (clamped
+ * into [0, K)), labels [n_iter][pairs][J] fp32 - what dsir_align_loss_backward2 takes as `labels`.  With the reference's K = None
+ * list this IS "(j, idx[j]) is among the matches": no list is needed. */
+int dsir_t_inlier_targets_radius(void* stream, const float* src, const float* ref, int stride, const int32_t* idx, const float* transform_gt,
+                                 int n_iter, int pairs, int J, int K, float radius, float* labels);
+
+/* Targets from a caller's list, the reference's semantics, hash included (loss.py:280-294, :723-749): matches [n_matches][2] =
+ * (src, ref) of all pairs concatenated, pair_offsets [pairs + 1] (device) the rows of every pair; keys [n_matches] int64 =
+ * src + ref * hash_seed, sorted within each pair (hipCUB segmented radix sort).  Duplicates, an empty list and a src index
+ * >= hash_seed alias exactly as on the host.  scratch: dsir_t_match_keys_scratch(n_matches, pairs) bytes; n_matches = 0: no-op.
+ * _targets_matches: labels[i][p][j] = (j + idx[i][p][j] * hash_seed is among pair p's keys) ? 1 : 0; idx is not clamped (it is
+ * never used as an address); keys may be NULL when every pair's list is empty.  The reference passes hash_seed = J (:819). */
+size_t dsir_t_match_keys_scratch(int64_t n_matches, int pairs);
+int dsir_t_match_keys(void* stream, const int32_t* matches, const int32_t* pair_offsets, int64_t n_matches, int pairs, int64_t hash_seed,
+                      int64_t* keys, void* scratch);
+int dsir_t_inlier_targets_matches(void* stream, const int64_t* keys, const int32_t* pair_offsets, const int32_t* idx, int n_iter, int pairs,
+                                  int J, int64_t hash_seed, float* labels);
+
 #ifdef __cplusplus
 }
 #endif
