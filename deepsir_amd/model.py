@@ -336,17 +336,22 @@ class Network(nn.Module):
         batch = self._pyramids(eng, data, src, ref)
         self._dirty = self._pool_dirty = self._server_dirty = True      # running statistics move now, the weights at optimizer.step()
 
-        # every back() below starts with zero_grad (the flat gradient buffer and the scatter plans) and returns its OWN tape's
+        # every backward starts with zero_grad (the flat gradient buffer and the scatter plans) and returns its OWN tape's
         # gradient, which autograd adds into param.grad: two training forwards alive before their backwards (or one backward of
         # loss_A + loss_B) give gA + gB, as torch's autograd does.  The forward needs no plan (only the backward scatters).
-        def param_grads(tr):
-            g = tr.flat_g.clone()             # ONE copy: autograd may keep what it is handed, the trainer's buffer is zeroed by the next backward
-            out = []
-            for k, p in zip(names, params):
-                v = tr.grads[k]
-                off = v.data_ptr() - tr.flat_g.data_ptr()
-                out.append(g[off // 4: off // 4 + v.numel()].view(p.shape))
-            return out
+        def taped(outputs, backward):
+            """``run_taped``'s pair for the main trainer: ``backward(grads)`` walks this forward's tapes back into ``main.grads``."""
+            def back(grads):
+                main.zero_grad()
+                backward(grads)
+                g = main.flat_g.clone()       # ONE copy: autograd may keep what it is handed, the trainer's buffer is zeroed by the next backward
+                out = []
+                for k, p in zip(names, params):
+                    v = main.grads[k]
+                    off = v.data_ptr() - main.flat_g.data_ptr()
+                    out.append(g[off // 4: off // 4 + v.numel()].view(p.shape))
+                return out
+            return outputs, back
 
         if self.pipeline == "align":
             n_iter = int(opt[0]) if opt is not None else self.cfg.num_reg_iter
@@ -357,15 +362,7 @@ class Network(nn.Module):
             def run():
                 fw = T.forward_align_train(eng, main, fe, ag, batch, n_iter, masks)
                 box["fw"] = fw
-
-                def back(grads):
-                    main.zero_grad()
-                    g = grads[0]
-                    for it in range(n_iter):
-                        main.backward(fw["tapes"][it], g[it].contiguous(), shared=fw["shared"])
-                    main.backward_shared(fw["shared"])
-                    return param_grads(main)
-                return (fw["logits"],), back
+                return taped((fw["logits"],), lambda grads: T.inlier_backwards(main, fw["tapes"], grads[0], fw["shared"]))
 
             (logits,) = run_taped(params, run, 1)
             fw = box["fw"]
@@ -394,13 +391,11 @@ class Network(nn.Module):
                     outs.append(lg); tapes.append(tape)
                 box["tapes"] = tapes
 
-                def back(grads):
-                    main.zero_grad()
+                def backward(grads):
                     for tape, g, lg in zip(tapes, grads, outs):
                         if g is not None:
                             main.backward(tape, g.reshape(-1, lg.shape[-1]).contiguous())
-                    return param_grads(main)
-                return tuple(outs), back
+                return taped(tuple(outs), backward)
 
             lg_s, lg_r = run_taped(params, run, 2)
             endpoints = {}
@@ -420,14 +415,11 @@ class Network(nn.Module):
             d_s, tape_s = main.forward(inp["xyz_src"], inp["feat_src"], inp["score_src"])
             d_r, tape_r = main.forward(inp["xyz_ref"], inp["feat_ref"], inp["score_ref"])
 
-            def back(grads):
-                main.zero_grad()
-                if grads[0] is not None:
-                    main.backward(tape_s, grads[0])
-                if grads[1] is not None:
-                    main.backward(tape_r, grads[1])
-                return param_grads(main)
-            return (d_s, d_r), back
+            def backward(grads):
+                for tape, g in ((tape_s, grads[0]), (tape_r, grads[1])):
+                    if g is not None:
+                        main.backward(tape, g)
+            return taped((d_s, d_r), backward)
 
         d_s, d_r = run_taped(params, run, 2)
         endpoints = {}

@@ -55,6 +55,7 @@ class _Ops:
         if device.type != "cuda":
             raise RuntimeError("deepsir_amd.train needs a GPU: the training operators are HIP kernels, there is no CPU path")
         self.lib = _lib.load()
+        self._fn = {name: getattr(self.lib, name) for name in _lib.SYMBOLS if name.startswith("dsir_t_") and not name.endswith("_scratch")}
         self.device = device
         self._scratch: Optional[torch.Tensor] = None
         self._plans: dict = {}
@@ -66,9 +67,11 @@ class _Ops:
         looking the stream up per launch costs more host time than most of these kernels run)."""
         self.stream = torch.cuda.current_stream(self.device).cuda_stream
 
-    def _ok(self, rc: int, what: str) -> None:
+    def _launch(self, symbol: str, *args) -> None:
+        """One operator of include/dsir_train.h on the bound stream: ``args`` are the symbol's arguments after the stream."""
+        rc = self._fn[symbol](self.stream, *args)
         if rc != 0:
-            raise RuntimeError(f"{what} failed (hipError {rc})")
+            raise RuntimeError(f"{symbol} failed (hipError {rc})")
 
     def scratch(self, nbytes: int) -> torch.Tensor:
         if self._scratch is None or self._scratch.numel() * 4 < nbytes:
@@ -84,8 +87,7 @@ class _Ops:
         rows, cin = x.shape[0], x.shape[1]
         cout = w.shape[0]
         y = self.empty(rows, cout)
-        self._ok(self.lib.dsir_t_gemm(self.stream, _ptr(x), cin, _ptr(w), cin, 1, _ptr(bias), _ptr(y), cout, rows, cin, cout, 0.0),
-                 "dsir_t_gemm")
+        self._launch("dsir_t_gemm", _ptr(x), cin, _ptr(w), cin, 1, _ptr(bias), _ptr(y), cout, rows, cin, cout, 0.0)
         return y
 
     def conv_dx(self, dy: torch.Tensor, w: torch.Tensor, into: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -93,16 +95,15 @@ class _Ops:
         rows, cout = dy.shape
         cin = w.numel() // cout
         dx = into if into is not None else self.empty(rows, cin)
-        self._ok(self.lib.dsir_t_gemm(self.stream, _ptr(dy), cout, _ptr(w), 1, cin, None, _ptr(dx), cin, rows, cout, cin,
-                                      1.0 if into is not None else 0.0), "dsir_t_gemm (dX)")
+        self._launch("dsir_t_gemm", _ptr(dy), cout, _ptr(w), 1, cin, None, _ptr(dx), cin, rows, cout, cin,
+                     1.0 if into is not None else 0.0)
         return dx
 
     def conv_dw(self, dy: torch.Tensor, x: torch.Tensor, dw: torch.Tensor, db: Optional[torch.Tensor]) -> None:
         rows, cout = dy.shape
         cin = x.shape[1]
         sc = self.scratch(self.lib.dsir_t_gemm_dw_scratch(rows, cout, cin))
-        self._ok(self.lib.dsir_t_gemm_dw(self.stream, _ptr(dy), cout, _ptr(x), cin, rows, cout, cin, _ptr(dw), _ptr(db), _ptr(sc)),
-                 "dsir_t_gemm_dw")
+        self._launch("dsir_t_gemm_dw", _ptr(dy), cout, _ptr(x), cin, rows, cout, cin, _ptr(dw), _ptr(db), _ptr(sc))
 
     # ---- normalisation
     def gn_fwd(self, y: torch.Tensor, clouds: int, groups: int, gamma, beta, act: bool):
@@ -111,8 +112,8 @@ class _Ops:
         out = self.empty(y.shape[0], C_)
         stats = self.empty(clouds, groups, 2)
         sc = self.scratch(self.lib.dsir_t_gn_scratch(clouds, M, C_))
-        self._ok(self.lib.dsir_t_gn_fwd(self.stream, _ptr(y), clouds, M, C_, groups, _ptr(gamma), _ptr(beta), int(act), _ptr(out),
-                                        _ptr(stats), _ptr(sc)), "dsir_t_gn_fwd")
+        self._launch("dsir_t_gn_fwd", _ptr(y), clouds, M, C_, groups, _ptr(gamma), _ptr(beta), int(act), _ptr(out),
+                     _ptr(stats), _ptr(sc))
         return out, stats
 
     def gn_bwd(self, dout, y, stats, clouds, groups, gamma, beta, act, dgamma, dbeta) -> torch.Tensor:
@@ -120,17 +121,20 @@ class _Ops:
         M = y.shape[0] // clouds
         dy = self.empty(y.shape[0], C_)
         sc = self.scratch(self.lib.dsir_t_gn_scratch(clouds, M, C_))
-        self._ok(self.lib.dsir_t_gn_bwd(self.stream, _ptr(dout), _ptr(y), _ptr(stats), clouds, M, C_, groups, _ptr(gamma), _ptr(beta),
-                                        int(act), _ptr(dy), _ptr(dgamma), _ptr(dbeta), _ptr(sc)), "dsir_t_gn_bwd")
+        self._launch("dsir_t_gn_bwd", _ptr(dout), _ptr(y), _ptr(stats), clouds, M, C_, groups, _ptr(gamma), _ptr(beta),
+                     int(act), _ptr(dy), _ptr(dgamma), _ptr(dbeta), _ptr(sc))
         return dy
+
+    def bn_running(self, stats: torch.Tensor, channels: int, rows: int, mean: torch.Tensor, var: torch.Tensor) -> None:
+        """BatchNorm1d's running statistics from the batch statistics of ``gn_fwd`` (one cloud, one group per channel), momentum 0.1."""
+        self._launch("dsir_t_bn_running", _ptr(stats), channels, rows, 0.1, _ptr(mean), _ptr(var))
 
     # ---- gathers
     def gather(self, x: torch.Tensor, idx: torch.Tensor, out: torch.Tensor, col_off: int) -> None:
         """x [clouds][n][C], idx [clouds][m] -> out[clouds * m][col_off : col_off + C] (out's row length = its ld)."""
         clouds, n, C_ = x.shape
         m = idx.shape[1]
-        self._ok(self.lib.dsir_t_gather(self.stream, _ptr(x), n, C_, _ptr(idx), m, clouds, _ptr(out), out.shape[-1], col_off),
-                 "dsir_t_gather")
+        self._launch("dsir_t_gather", _ptr(x), n, C_, _ptr(idx), m, clouds, _ptr(out), out.shape[-1], col_off)
 
     def plan(self, idx: torch.Tensor, n: int):
         """The inverse of a gather index idx [clouds][m] into [clouds][n] (include/dsir_train.h, dsir_t_scatter_plan): (order, offsets).
@@ -146,8 +150,7 @@ class _Ops:
         offsets = torch.empty(clouds * n + 1, dtype=torch.int32, device=self.device)
         nb = int(self.lib.dsir_t_scatter_plan_scratch(clouds * m))
         scratch = torch.empty(nb, dtype=torch.uint8, device=self.device)
-        self._ok(self.lib.dsir_t_scatter_plan(self.stream, _ptr(idx), m, clouds, n, _ptr(order), _ptr(offsets), _ptr(scratch)),
-                 "dsir_t_scatter_plan")
+        self._launch("dsir_t_scatter_plan", _ptr(idx), m, clouds, n, _ptr(order), _ptr(offsets), _ptr(scratch))
         self._plans[key] = (idx, order, offsets)
         return order, offsets
 
@@ -159,27 +162,25 @@ class _Ops:
         clouds, m = idx.shape
         order, offsets = self.plan(idx, n)
         dx = torch.empty(clouds, n, C_, dtype=torch.float32, device=self.device)
-        self._ok(self.lib.dsir_t_scatter_add(self.stream, _ptr(dy), dy.shape[-1], col_off, _ptr(order), _ptr(offsets), clouds, _ptr(dx), n, C_),
-                 "dsir_t_scatter_add")
+        self._launch("dsir_t_scatter_add", _ptr(dy), dy.shape[-1], col_off, _ptr(order), _ptr(offsets), clouds, _ptr(dx), n, C_)
         return dx
 
     def relpos(self, xyz: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
         clouds, n, k = idx.shape
         out = self.empty(clouds * n * k, 10)
-        self._ok(self.lib.dsir_t_relpos(self.stream, _ptr(xyz), _ptr(idx), n, k, clouds, _ptr(out)), "dsir_t_relpos")
+        self._launch("dsir_t_relpos", _ptr(xyz), _ptr(idx), n, k, clouds, _ptr(out))
         return out
 
     def attpool_fwd(self, cat: torch.Tensor, scores: torch.Tensor, points: int) -> torch.Tensor:
         C_ = cat.shape[1]
         out = self.empty(points, C_)
-        self._ok(self.lib.dsir_t_attpool_fwd(self.stream, _ptr(cat), _ptr(scores), points, K_NN, C_, _ptr(out)), "dsir_t_attpool_fwd")
+        self._launch("dsir_t_attpool_fwd", _ptr(cat), _ptr(scores), points, K_NN, C_, _ptr(out))
         return out
 
     def attpool_bwd(self, dout, cat, att, points):
         C_ = cat.shape[1]
         dcat, ds = self.empty(cat.shape[0], C_), self.empty(cat.shape[0], C_)
-        self._ok(self.lib.dsir_t_attpool_bwd(self.stream, _ptr(dout), _ptr(cat), _ptr(att), points, K_NN, C_, _ptr(dcat), _ptr(ds)),
-                 "dsir_t_attpool_bwd")
+        self._launch("dsir_t_attpool_bwd", _ptr(dout), _ptr(cat), _ptr(att), points, K_NN, C_, _ptr(dcat), _ptr(ds))
         return dcat, ds
 
     def maxpool_fwd(self, x: torch.Tensor, pool: torch.Tensor):
@@ -187,8 +188,7 @@ class _Ops:
         m, k = pool.shape[1], pool.shape[2]
         out = self.empty(clouds, m, C_)
         arg = self.empty(clouds, m, C_, dtype=torch.int32)
-        self._ok(self.lib.dsir_t_maxpool_fwd(self.stream, _ptr(x), n, C_, _ptr(pool), m, k, clouds, _ptr(out), _ptr(arg)),
-                 "dsir_t_maxpool_fwd")
+        self._launch("dsir_t_maxpool_fwd", _ptr(x), n, C_, _ptr(pool), m, k, clouds, _ptr(out), _ptr(arg))
         return out, arg
 
     def maxpool_bwd(self, dout: torch.Tensor, arg: torch.Tensor, pool: torch.Tensor, n: int) -> torch.Tensor:
@@ -197,27 +197,26 @@ class _Ops:
         k = pool.shape[2]
         order, offsets = self.plan(pool.reshape(clouds, m * k), n)
         dx = torch.empty(clouds, n, C_, dtype=torch.float32, device=self.device)
-        self._ok(self.lib.dsir_t_maxpool_bwd(self.stream, _ptr(dout), _ptr(arg), _ptr(order), _ptr(offsets), m, k, C_, clouds, _ptr(dx), n),
-                 "dsir_t_maxpool_bwd")
+        self._launch("dsir_t_maxpool_bwd", _ptr(dout), _ptr(arg), _ptr(order), _ptr(offsets), m, k, C_, clouds, _ptr(dx), n)
         return dx
 
     def add_leaky_fwd(self, a, b):
         out = torch.empty_like(a)
-        self._ok(self.lib.dsir_t_add_leaky_fwd(self.stream, _ptr(a), _ptr(b), a.numel(), _ptr(out)), "dsir_t_add_leaky_fwd")
+        self._launch("dsir_t_add_leaky_fwd", _ptr(a), _ptr(b), a.numel(), _ptr(out))
         return out
 
     def add_leaky_bwd(self, dout, out):
         d = torch.empty_like(out)
-        self._ok(self.lib.dsir_t_add_leaky_bwd(self.stream, _ptr(dout), _ptr(out), out.numel(), _ptr(d)), "dsir_t_add_leaky_bwd")
+        self._launch("dsir_t_add_leaky_bwd", _ptr(dout), _ptr(out), out.numel(), _ptr(d))
         return d
 
     def mul_mask(self, x, mask, scale):
         y = torch.empty_like(x)
-        self._ok(self.lib.dsir_t_mul_mask(self.stream, _ptr(x), _ptr(mask), scale, x.numel(), _ptr(y)), "dsir_t_mul_mask")
+        self._launch("dsir_t_mul_mask", _ptr(x), _ptr(mask), scale, x.numel(), _ptr(y))
         return y
 
     def axpy(self, a: float, x: torch.Tensor, y: torch.Tensor) -> None:
-        self._ok(self.lib.dsir_t_axpy(self.stream, a, _ptr(x), x.numel(), _ptr(y)), "dsir_t_axpy")
+        self._launch("dsir_t_axpy", a, _ptr(x), x.numel(), _ptr(y))
 
     def weighted_ce(self, logits: torch.Tensor, labels: torch.Tensor, class_weights: torch.Tensor, grad_scale: float = 1.0):
         """SemanticLoss.compute_loss: logits [rows][C], labels [rows] int32 (0 = ignored, class = label - 1)
@@ -226,18 +225,18 @@ class _Ops:
         d = self.empty(rows, C_)
         out = self.empty(4, dtype=torch.float64)
         sc = self.scratch(self.lib.dsir_t_weighted_ce_scratch(rows))
-        self._ok(self.lib.dsir_t_weighted_ce(self.stream, _ptr(logits), _ptr(labels), _ptr(class_weights), rows, C_, grad_scale, _ptr(d),
-                                             _ptr(out), _ptr(sc)), "dsir_t_weighted_ce")
+        self._launch("dsir_t_weighted_ce", _ptr(logits), _ptr(labels), _ptr(class_weights), rows, C_, grad_scale, _ptr(d),
+                     _ptr(out), _ptr(sc))
         return d, out
 
     def l2norm_fwd(self, x: torch.Tensor):
         y, nrm = torch.empty_like(x), self.empty(x.shape[0])
-        self._ok(self.lib.dsir_t_l2norm_fwd(self.stream, _ptr(x), x.shape[0], x.shape[1], _ptr(y), _ptr(nrm)), "dsir_t_l2norm_fwd")
+        self._launch("dsir_t_l2norm_fwd", _ptr(x), x.shape[0], x.shape[1], _ptr(y), _ptr(nrm))
         return y, nrm
 
     def l2norm_bwd(self, dy: torch.Tensor, y: torch.Tensor, nrm: torch.Tensor) -> torch.Tensor:
         dx = torch.empty_like(y)
-        self._ok(self.lib.dsir_t_l2norm_bwd(self.stream, _ptr(dy), _ptr(y), _ptr(nrm), y.shape[0], y.shape[1], _ptr(dx)), "dsir_t_l2norm_bwd")
+        self._launch("dsir_t_l2norm_bwd", _ptr(dy), _ptr(y), _ptr(nrm), y.shape[0], y.shape[1], _ptr(dx))
         return dx
 
     def det_des_loss(self, feat_ref, feat_src, pt_ref, pt_src, score_ref, transform_gt, thres_radius: float, det_loss_weight: float = 1.0):
@@ -247,9 +246,9 @@ class _Ops:
         out = self.empty(4, dtype=torch.float64)
         d_ref, d_src = torch.empty_like(feat_ref), torch.empty_like(feat_src)
         sc = self.scratch(self.lib.dsir_t_det_des_loss_scratch(P, M))
-        self._ok(self.lib.dsir_t_det_des_loss(self.stream, _ptr(feat_ref), _ptr(feat_src), _ptr(pt_ref), _ptr(pt_src), _ptr(score_ref),
-                                              _ptr(transform_gt), P, M, C_, float(thres_radius), float(det_loss_weight), _ptr(out), _ptr(d_ref),
-                                              _ptr(d_src), _ptr(sc)), "dsir_t_det_des_loss")
+        self._launch("dsir_t_det_des_loss", _ptr(feat_ref), _ptr(feat_src), _ptr(pt_ref), _ptr(pt_src), _ptr(score_ref),
+                     _ptr(transform_gt), P, M, C_, float(thres_radius), float(det_loss_weight), _ptr(out), _ptr(d_ref),
+                     _ptr(d_src), _ptr(sc))
         return out, d_ref, d_src
 
     def topk(self, score: torch.Tensor, k: int):
@@ -257,12 +256,12 @@ class _Ops:
         clouds, n = score.shape
         idx, out = self.empty(clouds, k, dtype=torch.int32), self.empty(clouds, k)
         sc = self.scratch(self.lib.dsir_t_topk_scratch(clouds, n))
-        self._ok(self.lib.dsir_t_topk(self.stream, _ptr(score), clouds, n, k, _ptr(idx), _ptr(out), _ptr(sc)), "dsir_t_topk")
+        self._launch("dsir_t_topk", _ptr(score), clouds, n, k, _ptr(idx), _ptr(out), _ptr(sc))
         return idx, out
 
     def sigmoid(self, x: torch.Tensor) -> torch.Tensor:
         y = torch.empty_like(x)
-        self._ok(self.lib.dsir_t_sigmoid(self.stream, _ptr(x), x.numel(), _ptr(y)), "dsir_t_sigmoid")
+        self._launch("dsir_t_sigmoid", _ptr(x), x.numel(), _ptr(y))
         return y
 
     def acc(self, dst: Optional[torch.Tensor], src: torch.Tensor) -> torch.Tensor:
@@ -273,12 +272,21 @@ class _Ops:
         self.axpy(1.0, src, dst)
         return dst
 
+    def any_nan(self, x: torch.Tensor) -> bool:
+        """One kernel, one 4-byte read."""
+        flag = torch.empty(1, dtype=torch.int32, device=self.device)
+        self._launch("dsir_t_any_nan", _ptr(x), x.numel(), _ptr(flag))
+        return bool(flag.item())
+
+    def adam(self, p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, lr: float, betas, eps: float, step: int) -> None:
+        self._launch("dsir_t_adam", _ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), lr, betas[0], betas[1], eps, step)
+
     def inlier_input(self, xyz_src, xyz_ref, idx, T: Optional[torch.Tensor]) -> torch.Tensor:
         """[P][J][6] = [T x_src ; x_ref[idx]]; T [P][..][3][4] view of one iteration (row stride taken from it) or None."""
         P, J, _ = xyz_src.shape
         out = self.empty(P, J, 6)
-        self._ok(self.lib.dsir_t_inlier_input(self.stream, _ptr(xyz_src), _ptr(xyz_ref), _ptr(idx), _ptr(T), 0 if T is None else T.stride(0),
-                                              P, J, xyz_ref.shape[1], _ptr(out)), "dsir_t_inlier_input")
+        self._launch("dsir_t_inlier_input", _ptr(xyz_src), _ptr(xyz_ref), _ptr(idx), _ptr(T), 0 if T is None else T.stride(0),
+                     P, J, xyz_ref.shape[1], _ptr(out))
         return out
 
     # ---- ground-truth matches and inlier targets (csrc/match_targets.hip; the distance rule is stated in include/dsir_train.h)
@@ -297,15 +305,14 @@ class _Ops:
         counts = self.empty(P * J, dtype=torch.int32)
         offsets = self.empty(P * J + 1, dtype=torch.int32)
         scratch = torch.empty(nb, dtype=torch.uint8, device=self.device)
-        self._ok(self.lib.dsir_t_radius_matches_count(self.stream, _ptr(src), _ptr(ref), stride, _ptr(transform_gt), P, J, K, float(radius),
-                                                      _ptr(counts), _ptr(offsets), _ptr(scratch)), "dsir_t_radius_matches_count")
+        self._launch("dsir_t_radius_matches_count", _ptr(src), _ptr(ref), stride, _ptr(transform_gt), P, J, K, float(radius),
+                     _ptr(counts), _ptr(offsets), _ptr(scratch))
         total = int(offsets[-1].item())
         if total < 0:
             raise RuntimeError("radius_matches: more than 2^31 - 1 matches: split the batch or lower the radius")
         cols = self.empty(total, dtype=torch.int32)
-        self._ok(self.lib.dsir_t_radius_matches_fill(self.stream, _ptr(src), _ptr(ref), stride, _ptr(transform_gt), P, J, K, float(radius),
-                                                     _ptr(offsets), _ptr(scratch), _ptr(cols) if total else None, total),
-                 "dsir_t_radius_matches_fill")
+        self._launch("dsir_t_radius_matches_fill", _ptr(src), _ptr(ref), stride, _ptr(transform_gt), P, J, K, float(radius),
+                     _ptr(offsets), _ptr(scratch), _ptr(cols) if total else None, total)
         return offsets, cols
 
     def inlier_targets_radius(self, src: torch.Tensor, ref: torch.Tensor, idx: torch.Tensor, transform_gt: torch.Tensor, radius: float):
@@ -313,8 +320,8 @@ class _Ops:
         ``radius_matches``, bit for bit).  idx [n_iter][P][J] i32 -> fp32 [n_iter][P][J]."""
         n_iter, P, J = idx.shape
         labels = self.empty(n_iter, P, J)
-        self._ok(self.lib.dsir_t_inlier_targets_radius(self.stream, _ptr(src), _ptr(ref), src.shape[2], _ptr(idx), _ptr(transform_gt), n_iter, P, J,
-                                                       ref.shape[1], float(radius), _ptr(labels)), "dsir_t_inlier_targets_radius")
+        self._launch("dsir_t_inlier_targets_radius", _ptr(src), _ptr(ref), src.shape[2], _ptr(idx), _ptr(transform_gt), n_iter, P, J,
+                     ref.shape[1], float(radius), _ptr(labels))
         return labels
 
     def match_keys(self, matches: Sequence, hash_seed: int) -> "MatchKeys":
@@ -334,8 +341,7 @@ class _Ops:
                     raise ValueError("match_keys: indices outside the int32 range")
                 flat = torch.from_numpy(np.ascontiguousarray(host.astype(np.int32))).to(self.device)
             scratch = torch.empty(int(self.lib.dsir_t_match_keys_scratch(total, P)), dtype=torch.uint8, device=self.device)
-            self._ok(self.lib.dsir_t_match_keys(self.stream, _ptr(flat), _ptr(seg), total, P, int(hash_seed), _ptr(keys), _ptr(scratch)),
-                     "dsir_t_match_keys")
+            self._launch("dsir_t_match_keys", _ptr(flat), _ptr(seg), total, P, int(hash_seed), _ptr(keys), _ptr(scratch))
         return MatchKeys(keys, seg, P, int(hash_seed))
 
     def inlier_targets_matches(self, keys: "MatchKeys", idx: torch.Tensor) -> torch.Tensor:
@@ -344,8 +350,8 @@ class _Ops:
         if P != keys.pairs:
             raise ValueError(f"inlier_targets_matches: idx holds {P} pairs, the match list {keys.pairs}")
         labels = self.empty(n_iter, P, J)
-        self._ok(self.lib.dsir_t_inlier_targets_matches(self.stream, _ptr(keys.keys) if keys.keys.numel() else None, _ptr(keys.offsets), _ptr(idx),
-                                                        n_iter, P, J, keys.hash_seed, _ptr(labels)), "dsir_t_inlier_targets_matches")
+        self._launch("dsir_t_inlier_targets_matches", _ptr(keys.keys) if keys.keys.numel() else None, _ptr(keys.offsets), _ptr(idx),
+                     n_iter, P, J, keys.hash_seed, _ptr(labels))
         return labels
 
 
@@ -451,12 +457,9 @@ class _ParamStore:
         self.ops.new_step()
 
     def grads_have_nan(self) -> bool:
-        """train.py:437-441 ("Gradients include NaN values. Parameters will not be updated"): one kernel, one 4-byte read."""
-        o = self.ops
-        o.begin()
-        flag = torch.empty(1, dtype=torch.int32, device=self.device)
-        o._ok(o.lib.dsir_t_any_nan(o.stream, _ptr(self.flat_g), self.flat_g.numel(), _ptr(flag)), "dsir_t_any_nan")
-        return bool(flag.item())
+        """train.py:437-441 ("Gradients include NaN values. Parameters will not be updated")."""
+        self.ops.begin()
+        return self.ops.any_nan(self.flat_g)
 
     def state_dict(self) -> Dict[str, np.ndarray]:
         """Parameters and BatchNorm running statistics in the reference's shapes (host)."""
@@ -468,10 +471,18 @@ class _ParamStore:
     def adam_step(self, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8) -> None:
         """torch.optim.Adam.step (train.py:323, :446) over the flat buffer (the alignment padding stays 0)."""
         self.step_count += 1
-        o = self.ops
-        o.begin()
-        o._ok(o.lib.dsir_t_adam(o.stream, _ptr(self.flat_p), _ptr(self.flat_g), _ptr(self.flat_m), _ptr(self.flat_v), self.flat_p.numel(),
-                                lr, betas[0], betas[1], eps, self.step_count), "dsir_t_adam")
+        self.ops.begin()
+        self.ops.adam(self.flat_p, self.flat_g, self.flat_m, self.flat_v, lr, betas, eps, self.step_count)
+
+    def finish_step(self, lr: float, apply: bool, dist, invalid=None) -> bool:
+        """The end of every optimisation step (train.py:437-446): the data-parallel mean of the gradients, then Adam unless a gradient
+        is NaN or a pose of ``invalid`` (the flags ``any_pose_invalid`` reads; None: a pipeline without poses, no test) was degenerate.
+        -> whether the update was skipped for that reason."""
+        all_reduce_gradients(self, dist)
+        bad = self.grads_have_nan() or (invalid is not None and any_pose_invalid(invalid, dist))
+        if apply and not bad:
+            self.adam_step(lr)
+        return bad
 
     # ---- MLP (RandLANet.py:34-55) in training mode: Conv1d + BatchNorm1d (batch statistics) + LeakyReLU, last layer bare
     def _mlp1d(self, saved: list, prefix: str, x: torch.Tensor, n_layers: int, update_running: bool = True) -> torch.Tensor:
@@ -484,9 +495,8 @@ class _ParamStore:
                 g, be = self.params[f"{prefix}.{pos + 1}.weight"], self.params[f"{prefix}.{pos + 1}.bias"]
                 out, stats = o.gn_fwd(y, 1, w.shape[0], g, be, True)
                 if update_running:
-                    o._ok(o.lib.dsir_t_bn_running(o.stream, _ptr(stats), w.shape[0], y.shape[0], 0.1,
-                                                  _ptr(self.buffers[f"{prefix}.{pos + 1}.running_mean"]),
-                                                  _ptr(self.buffers[f"{prefix}.{pos + 1}.running_var"])), "dsir_t_bn_running")
+                    o.bn_running(stats, w.shape[0], y.shape[0], self.buffers[f"{prefix}.{pos + 1}.running_mean"],
+                                 self.buffers[f"{prefix}.{pos + 1}.running_var"])
                 saved.append((prefix, pos, x, y, stats))
                 x = out
                 pos += 3
@@ -709,26 +719,9 @@ class RandlaTrainer(_ParamStore):
         xf = x.reshape(clouds * N, -1)
         feat = o.conv(xf, self.params[pf + ".mlp_out.weight"], None)
         h = o.mul_mask(feat, dropout_mask.reshape(-1).contiguous(), 2.0) if dropout_mask is not None else feat
-        # fc_label: Conv1d + BatchNorm1d (batch statistics) + LeakyReLU, twice, then Conv1d (RandLANet.py:34-55, :272-273)
-        fc = []
-        pos = 0
-        for i in range(3):
-            w, bias = self.params[f"{pf}.fc_label.{pos}.weight"], self.params[f"{pf}.fc_label.{pos}.bias"]
-            y = o.conv(h, w, bias)
-            if i < 2:
-                g, be = self.params[f"{pf}.fc_label.{pos + 1}.weight"], self.params[f"{pf}.fc_label.{pos + 1}.bias"]
-                out, stats = o.gn_fwd(y, 1, w.shape[0], g, be, True)
-                if update_running_stats:
-                    o._ok(o.lib.dsir_t_bn_running(o.stream, _ptr(stats), w.shape[0], y.shape[0], 0.1,
-                                                  _ptr(self.buffers[f"{pf}.fc_label.{pos + 1}.running_mean"]),
-                                                  _ptr(self.buffers[f"{pf}.fc_label.{pos + 1}.running_var"])), "dsir_t_bn_running")
-                fc.append((pos, h, y, stats))
-                h = out
-                pos += 3
-            else:
-                fc.append((pos, h, None, None))
-                h = y
-        tape.misc["net"] = dict(clouds=clouds, N=N, n=n, skips_shapes=[s.shape for s in skips], args=args, pools=pyr["sub"], dec=dec, xf=xf, fc=fc,
+        fc = tape.misc[pf + ".fc_label"] = []                      # fc_label (RandLANet.py:272-273): three layers of the MLP chain
+        h = self._mlp1d(fc, pf + ".fc_label", h, 3, update_running_stats)
+        tape.misc["net"] = dict(clouds=clouds, N=N, n=n, skips_shapes=[s.shape for s in skips], args=args, pools=pyr["sub"], dec=dec, xf=xf,
                                 mask=dropout_mask, L=L)
         tape.misc["feat"] = feat.reshape(clouds, N, -1)            # RandLA.forward's first output (before the dropout)
         return h.reshape(clouds, N, self.num_classes), tape
@@ -743,14 +736,7 @@ class RandlaTrainer(_ParamStore):
         net = tape.misc["net"]
         clouds, N, n, L = net["clouds"], net["N"], net["n"], net["L"]
         d = dlogits.reshape(clouds * N, self.num_classes).contiguous().float()
-        for pos, hin, y, stats in reversed(net["fc"]):
-            w = self.params[f"{pf}.fc_label.{pos}.weight"]
-            if y is not None:
-                g, be = self.params[f"{pf}.fc_label.{pos + 1}.weight"], self.params[f"{pf}.fc_label.{pos + 1}.bias"]
-                d = o.gn_bwd(d, y, stats, 1, w.shape[0], g, be, True, self.grads[f"{pf}.fc_label.{pos + 1}.weight"],
-                             self.grads[f"{pf}.fc_label.{pos + 1}.bias"])
-            o.conv_dw(d, hin, self.grads[f"{pf}.fc_label.{pos}.weight"], self.grads[f"{pf}.fc_label.{pos}.bias"])
-            d = o.conv_dx(d, w)
+        d = self._mlp1d_bwd(tape.misc[pf + ".fc_label"], d)
         if net["mask"] is not None:
             d = o.mul_mask(d, net["mask"].reshape(-1).contiguous(), 2.0)
         if dfeat is not None:
@@ -782,7 +768,7 @@ def dropout_keep_masks(seed: Optional[int], shape, device) -> Optional[torch.Ten
     """Dropout(0.5) keep flags (RandLANet.py:363-367) of one optimisation step, uint8 ``shape`` on ``device``: ONE draw from a
     device generator seeded with ``seed``.  Every entry point that takes ``dropout_seed`` (``train_step_align``,
     ``AlignTrainStep.step``, ``train_step_label``, ``Network.train_step``) draws through this function, so the same seed gives
-    the same masks - hence the same gradients up to the order of the fp32 atomics - on the eager and the hipGraph path.
+    the same masks - hence the same gradients: the scatter-adds run over a sorted plan, not atomics - on the eager and the hipGraph path.
     None: dropout off."""
     if seed is None:
         return None
@@ -809,6 +795,42 @@ def any_pose_invalid(flags, dist=None) -> bool:
     return bad
 
 
+def _extractor_side(engine, extractor: RandlaTrainer, batch: dict, side: str, masks: dict):
+    """The frozen feature extractor on one side ('src' / 'ref') in training mode, and the engine's key-point score on its outputs.
+    -> points [P][N][C], features [P][N][64], score [P][N]."""
+    pts = batch[f"points_{side}"].contiguous()
+    logits, tape = extractor.forward(pts, batch[f"{side}_xyz"], batch[f"{side}_neigh"], batch[f"{side}_sub"], batch[f"{side}_interp"],
+                                     masks.get(f"fe_{side}"))
+    feat = tape.misc["feat"].contiguous()
+    score, _label = engine.score(feat, logits.contiguous(), batch[f"{side}_xyz"], batch[f"{side}_neigh"])
+    return pts, feat, score
+
+
+def inlier_forwards(trainer: RandlaTrainer, xyz_s, xyz_r, idx, T, pyramid, masks):
+    """The inlier model's training-mode forwards over the registration iterations of one step, given the matching idx [n_iter][P][N]
+    and the cumulative poses T [P][n_iter][3][4] of the no_grad half.  pyramid: (src_xyz, src_neigh, src_sub, src_interp);
+    masks: [n_iter][P][N][64] keep flags or None.  -> per iteration the logits [P][N] and the tape, and the dict the passes share
+    (the position-encoding branch, once per step: ``RandlaTrainer.forward``)."""
+    o = trainer.ops
+    o.begin()
+    P, N, _ = xyz_s.shape
+    logits, tapes, shared = [], [], {}
+    for it in range(idx.shape[0]):
+        # the src cloud moved by the previous cumulative pose (model.py:587; R_t.detach()) next to its correspondences
+        cat = o.inlier_input(xyz_s, xyz_r, idx[it], None if it == 0 else T[:, it - 1])
+        lg, tape = trainer.forward(cat, *pyramid, None if masks is None else masks[it], shared=shared)
+        logits.append(lg.reshape(P, N))
+        tapes.append(tape)
+    return logits, tapes, shared
+
+
+def inlier_backwards(trainer: RandlaTrainer, tapes, grad_logits, shared: dict) -> None:
+    """The backwards of those passes from d loss / d logits [n_iter][P][N] (their gradients add up), then the shared branch once."""
+    for tape, g in zip(tapes, grad_logits):
+        trainer.backward(tape, g, shared=shared)
+    trainer.backward_shared(shared)
+
+
 def forward_align_train(engine, inlier: RandlaTrainer, extractor: RandlaTrainer, aggregation: "AggregationTrainer", batch: dict,
                         n_iter: int, masks: Optional[dict] = None) -> dict:
     """``forward_align_4`` (network/model.py:520-607) as the reference's training loop runs it: ``my_model.train()`` (train.py:379)
@@ -821,16 +843,9 @@ def forward_align_train(engine, inlier: RandlaTrainer, extractor: RandlaTrainer,
     -> idx [n_iter][P][J] i32, logits [n_iter][P][J], tapes, xyz_src / xyz_ref [P][.][3] (for the loss)."""
     o = inlier.ops
     masks = masks or {}
-    side = {}
-    for s_ in ("src", "ref"):
-        pts = batch[f"points_{s_}"].contiguous()
-        logits, tape = extractor.forward(pts, batch[f"{s_}_xyz"], batch[f"{s_}_neigh"], batch[f"{s_}_sub"], batch[f"{s_}_interp"],
-                                         masks.get(f"fe_{s_}"))
-        feat = tape.misc["feat"].contiguous()
-        score, _label = engine.score(feat, logits.contiguous(), batch[f"{s_}_xyz"], batch[f"{s_}_neigh"])
-        side[s_] = (pts[:, :, :3].contiguous(), feat, score)
-    xyz0, f_s, sc_s = side["src"]
-    xyz_r, f_r, sc_r = side["ref"]
+    pts_s, f_s, sc_s = _extractor_side(engine, extractor, batch, "src", masks)
+    pts_r, f_r, sc_r = _extractor_side(engine, extractor, batch, "ref", masks)
+    xyz0, xyz_r = pts_s[:, :, :3].contiguous(), pts_r[:, :, :3].contiguous()
     P, J, _ = xyz0.shape
     idxs, logits, tapes, invalid, Ts = [], [], [], [], []
     pt_ref_new = None
@@ -866,13 +881,8 @@ def train_step_align_full(engine, inlier: RandlaTrainer, extractor: RandlaTraine
     fw = forward_align_train(engine, inlier, extractor, aggregation, batch, n_iter, masks)
     labels = None if labels_fn is None else labels_fn(fw["idx"])
     out = engine.align_loss_backward(fw["xyz_src"], fw["xyz_ref"], fw["idx"], fw["logits"], labels, transform_gt, **(loss_kwargs or {}))
-    for it in range(n_iter):
-        inlier.backward(fw["tapes"][it], out["grad_logits"][it], shared=fw["shared"])
-    inlier.backward_shared(fw["shared"])
-    all_reduce_gradients(inlier, dist)
-    bad = inlier.grads_have_nan() or any_pose_invalid(fw["invalid"], dist)      # train.py:437-446: NaN gradient OR invalid_gradient
-    if apply and not bad:
-        inlier.adam_step(lr)
+    inlier_backwards(inlier, fw["tapes"], out["grad_logits"], fw["shared"])
+    bad = inlier.finish_step(lr, apply, dist, fw["invalid"])
     out.update(logits=fw["logits"], idx=fw["idx"], skipped=bad)
     return out
 
@@ -889,36 +899,19 @@ def train_step_align(engine, trainer: RandlaTrainer, batch: dict, result: dict, 
     from them, run forward in training mode, the alignment loss and its gradient w.r.t. the logits come from
     ``Engine.align_loss_backward``, and the gradients of all iterations are accumulated before ONE Adam step - skipped,
     like the reference's (train.py:437-446), when a gradient is NaN or a pose was degenerate."""
-    dev = trainer.device
     xyz_s = batch["points_src"][:, :, :3].contiguous()
     xyz_r = batch["points_ref"][:, :, :3].contiguous()
     idx = result["idx"]
-    T = result["transforms"]
     n_iter, P, N = idx.shape
     trainer.zero_grad()
-    logits, tapes = [], []
-    masks = dropout_keep_masks(dropout_seed, (n_iter, P, N, trainer.cfg.out_feat_dim), dev)
-    shared: dict = {}                       # position-encoding branch of the inlier model: once per step (RandlaTrainer.forward)
-    trainer.ops.begin()
-    for it in range(n_iter):
-        # the src cloud moved by the previous cumulative pose (model.py:587; R_t.detach()) next to its correspondences
-        cat = trainer.ops.inlier_input(xyz_s, xyz_r, idx[it], None if it == 0 else T[:, it - 1])
-        mask = None if masks is None else masks[it]
-        lg, tape = trainer.forward(cat, batch["src_xyz"], batch["src_neigh"], batch["src_sub"], batch["src_interp"], mask, shared=shared)
-        logits.append(lg.reshape(P, N))
-        tapes.append(tape)
+    masks = dropout_keep_masks(dropout_seed, (n_iter, P, N, trainer.cfg.out_feat_dim), trainer.device)
+    logits, tapes, shared = inlier_forwards(trainer, xyz_s, xyz_r, idx, result["transforms"],
+                                            (batch["src_xyz"], batch["src_neigh"], batch["src_sub"], batch["src_interp"]), masks)
     lg_all = torch.stack(logits).contiguous()
     out = engine.align_loss_backward(xyz_s, xyz_r, idx, lg_all, labels, transform_gt, **(loss_kwargs or {}))
-    g = out["grad_logits"]
-    for it in range(n_iter):
-        trainer.backward(tapes[it], g[it], shared=shared)
-    trainer.backward_shared(shared)
-    all_reduce_gradients(trainer, dist)
-    bad = trainer.grads_have_nan() or any_pose_invalid([result.get("invalid")], dist)   # train.py:437-446
-    if apply and not bad:
-        trainer.adam_step(lr)
+    inlier_backwards(trainer, tapes, out["grad_logits"], shared)
     out["logits"] = lg_all
-    out["skipped"] = bad
+    out["skipped"] = trainer.finish_step(lr, apply, dist, [result.get("invalid")])
     return out
 
 
@@ -1013,11 +1006,7 @@ def feat_pipeline_inputs_train(engine, extractor: RandlaTrainer, batch: dict, nu
     masks = masks or {}
     out = {}
     for side in ("src", "ref"):
-        pts = batch[f"points_{side}"].contiguous()
-        logits, tape = extractor.forward(pts, batch[f"{side}_xyz"], batch[f"{side}_neigh"], batch[f"{side}_sub"], batch[f"{side}_interp"],
-                                         masks.get(f"fe_{side}"))
-        feat = tape.misc["feat"].contiguous()
-        score, _ = engine.score(feat, logits.contiguous(), batch[f"{side}_xyz"], batch[f"{side}_neigh"])
+        pts, feat, score = _extractor_side(engine, extractor, batch, side, masks)
         o.begin()
         idx, sel_score = o.topk(score, num_sub)
         P, M = idx.shape
@@ -1043,10 +1032,7 @@ def train_step_feat(trainer: AggregationTrainer, inp: dict, transform_gt: torch.
     trainer.backward(tape_s, g_src)
     trainer.backward(tape_r, g_ref)
     vals = out.cpu().numpy()
-    all_reduce_gradients(trainer, dist)
-    bad = trainer.grads_have_nan()
-    if apply and not bad:
-        trainer.adam_step(lr)
+    bad = trainer.finish_step(lr, apply, dist)
     return {"loss": float(vals[0]), "loss_feat": float(vals[1]), "loss_det": float(vals[2]), "acc": float(vals[3]),
             "desc_src": d_src, "desc_ref": d_ref, "skipped": bad}
 
@@ -1078,11 +1064,7 @@ def train_step_label(trainer: RandlaTrainer, batch: dict, labels_src: torch.Tens
     vals = torch.stack(outs).cpu().numpy()                      # one host read for both sides
     res["loss"] = float(vals[0, 0] + vals[1, 0])
     res["acc"] = float(vals[0, 2] / max(vals[0, 3], 1.0) + vals[1, 2] / max(vals[1, 3], 1.0))    # acc_src + acc_ref (loss.py:994)
-    all_reduce_gradients(trainer, dist)
-    bad = trainer.grads_have_nan()
-    if apply and not bad:
-        trainer.adam_step(lr)
-    res["skipped"] = bad
+    res["skipped"] = trainer.finish_step(lr, apply, dist)
     return res
 
 
@@ -1097,8 +1079,8 @@ class AlignTrainStep:
     Adam launch over the flat parameter buffer, whose bias corrections change per step and therefore stay outside.
     The first call runs eagerly (it IS a training step), the second captures, later ones replay.  Inputs are copied into
     static device buffers; with the same ``dropout_seed`` the masks are those of ``train_step_align`` (``dropout_keep_masks``) and the
-    results equal its results except for the order of the fp32 atomics (tests/test_train.py::test_graph_replayed_step_equals_the_eager_step
-    runs the comparison with dropout on)."""
+    results are those of ``train_step_align``: both run ``inlier_forwards`` / ``inlier_backwards``, and the scatter-adds sum over a sorted
+    plan, not with float atomics (tests/test_train.py::test_graph_replayed_step_equals_the_eager_step compares the two)."""
 
     def __init__(self, engine, trainer: RandlaTrainer, pairs: int, n_src: int, n_ref: int, n_iter: int, dropout: bool = True,
                  use_graph: bool = True):
@@ -1120,22 +1102,15 @@ class AlignTrainStep:
         self.gen = torch.Generator(device=dev)
 
     def _forward_all(self) -> None:
-        tr = self.tr
-        tr.ops.begin()
-        self.tapes = []
-        self.shared = {}                    # position-encoding branch: computed by iteration 0, re-used by the others
-        for it in range(self.n_iter):
-            cat = tr.ops.inlier_input(self.xyz_s, self.xyz_r, self.idx[it], None if it == 0 else self.T[:, it - 1])
-            lg, tape = tr.forward(cat, self.src_xyz, self.neigh, self.sub, self.interp, None if self.masks is None else self.masks[it],
-                                  shared=self.shared)
-            self.logits[it].copy_(lg.reshape(self.P, self.N))
-            self.tapes.append(tape)
+        self.tapes, self.shared = [], {}        # the previous step's activations go before this step's are made
+        logits, self.tapes, self.shared = inlier_forwards(self.tr, self.xyz_s, self.xyz_r, self.idx, self.T,
+                                                          (self.src_xyz, self.neigh, self.sub, self.interp), self.masks)
+        for it, lg in enumerate(logits):
+            self.logits[it].copy_(lg)
 
     def _backward_all(self) -> None:
         self.tr.zero_grad()
-        for it in range(self.n_iter):
-            self.tr.backward(self.tapes[it], self.grad[it], shared=self.shared)
-        self.tr.backward_shared(self.shared)
+        inlier_backwards(self.tr, self.tapes, self.grad, self.shared)
 
     def step(self, batch: dict, result: dict, transform_gt, labels=None, lr: float = 1e-3, dropout_seed: Optional[int] = None,
              loss_kwargs: Optional[dict] = None, apply: bool = True, dist=None) -> dict:
@@ -1172,10 +1147,6 @@ class AlignTrainStep:
             self.gb.replay()
         else:
             self._backward_all()
-        all_reduce_gradients(tr, dist)
-        bad = tr.grads_have_nan() or any_pose_invalid([result.get("invalid")], dist)   # train.py:437-446
-        if apply and not bad:
-            tr.adam_step(lr)
         out["logits"] = self.logits
-        out["skipped"] = bad
+        out["skipped"] = tr.finish_step(lr, apply, dist, [result.get("invalid")])
         return out

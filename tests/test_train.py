@@ -404,7 +404,8 @@ def test_train_step_align_gradients_match_the_oracle():
 @pytest.mark.gpu
 def test_graph_replayed_step_equals_the_eager_step():
     """AlignTrainStep (forward and backward halves replayed from hipGraphs) against train_step_align, three steps each from
-    the same start: same losses and, up to the order of the fp32 atomics in the scatter-adds, the same weights."""
+    the same start: same losses and the same weights within what one Adam update can move them (the scatter-adds sum over a
+    sorted plan: there are no float atomics whose order could differ between the two)."""
     from deepsir_amd.engine import Engine
     from deepsir_amd.synth import make_pair
     from deepsir_amd.train import AlignTrainStep, train_step_align
