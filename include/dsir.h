@@ -248,7 +248,13 @@ int dsir_eval_metrics(dsir_ctx* ctx, const float* pred_T, int64_t pred_stride, c
  * for P pairs at once, entirely on device.  points_src [P][J][stride], points_ref [P][K][stride] (xyz first);
  * T_init / T_out [P][3][4]; stats [P][4] float64 {fitness, inlier_rmse, converged (0/1), iterations} or NULL.
  * The branch is disabled in the reference and open3d is not pinned: the rule (open3d's RegistrationICP loop, exact
- * brute-force nearest neighbours in fp32 with ties to the lower index) is restated in oracle/icp.py. */
+ * brute-force nearest neighbours in fp32 with ties to the lower index) is restated in oracle/icp.py.
+ * max_iter == 0 returns the first search's {fitness, rmse} with T_out = T_init, converged = 0, iterations = 0; converged = 0
+ * also when max_iter updates were made without meeting the criteria.  No correspondence: the update is the identity.
+ * Pairs are independent: a pair's T_out and stats do not depend, bit for bit, on the other pairs of the call.
+ * Non-finite coordinates (not an error): such a point is never part of a correspondence; a pair that holds one in
+ * points_src, or in a reference point that an update gathers, takes identity updates from then on, so its T_out stays a
+ * finite rotation and translation and its stats stay finite; the other pairs are not affected. */
 int dsir_icp_refine(dsir_ctx* ctx, const float* points_src, const float* points_ref, int pairs, int J, int K, int stride,
                     float max_corr_dist, int max_iter, float rel_fitness, float rel_rmse, const float* T_init,
                     float* T_out, double* stats);
@@ -262,7 +268,12 @@ int dsir_icp_refine(dsir_ctx* ctx, const float* points_src, const float* points_
  * weights [P][m] or NULL (unweighted mean); weights_are_logits != 0: sigmoid applied on the fly (perm_matrices[-1]);
  * T_init / T_out [P][3][4]; stats [P][3] float64 {iterations, loss, break_count} (opt_result) or NULL.
  * The branch is disabled in the reference (use_tune = False) and test.py / DGR.py cannot be imported offline (open3d):
- * the rule is restated with the same torch calls in oracle/finetune.py (parity unpinned). */
+ * the rule is restated with the same torch calls in oracle/finetune.py (parity unpinned).
+ * stats.iterations is the reference's loop index of the last step: max_iter steps report max_iter - 1; stats.loss is the
+ * loss before the last update.  Pairs are independent, bit for bit.
+ * Weights that sum to zero (all zero, or logits so negative that the fp32 sigmoid is 0, e.g. -100) divide by zero as the
+ * reference does: that pair's T_out and stats.loss are NaN, it runs all max_iter steps with break_count 0, and the other
+ * pairs are not affected. */
 int dsir_pose_finetune(dsir_ctx* ctx, const float* xyz_src, const float* xyz_ref, const float* weights, int weights_are_logits,
                        int pairs, int m, const float* T_init, float quantization_size, int max_iter, float break_threshold_ratio,
                        int max_break_count, float* T_out, double* stats);

@@ -36,18 +36,21 @@ def ortho2rotation(poses: torch.Tensor) -> torch.Tensor:
 def smooth_l1(X: torch.Tensor, Y: torch.Tensor, weights, q: float, delta: float = 1.0) -> torch.Tensor:
     """HighDimSmoothL1Loss.__call__ (test.py:112-131). X, Y [1,N,3]; weights [1,N,1] or None."""
     sq = torch.sum(((X - Y) / q) ** 2, dim=2, keepdim=True)
-    half = 0.5 * (sq < delta).float()
+    half = 0.5 * (sq < delta).to(sq.dtype)
     loss = (0.5 - half) * (torch.sqrt(sq + _EPS32) - 0.5 * delta ** 2) + half * sq
     return loss.mean() if weights is None else (loss * weights).sum() / weights.sum()
 
 
 def transformation_finetune(xyz_src: np.ndarray, xyz_ref: np.ndarray, pose: np.ndarray, weights=None, quantization_size: float = 1.0,
-                            max_iter: int = 1000, break_threshold_ratio: float = 1e-4, max_break_count: int = 20):
-    """xyz_* [N,3] matched points, pose [3,4], weights [N] or None -> (pose [3,4] float32, dict(iterations, loss, break_count))."""
-    X = torch.from_numpy(np.ascontiguousarray(xyz_src, np.float32))[None]
-    Y = torch.from_numpy(np.ascontiguousarray(xyz_ref, np.float32))[None]
-    W = None if weights is None else torch.from_numpy(np.ascontiguousarray(weights, np.float32)).reshape(1, -1, 1)
-    P = torch.from_numpy(np.ascontiguousarray(pose, np.float32))
+                            max_iter: int = 1000, break_threshold_ratio: float = 1e-4, max_break_count: int = 20,
+                            dtype: torch.dtype = torch.float32):
+    """xyz_* [N,3] matched points, pose [3,4], weights [N] or None -> (pose [3,4], dict(iterations, loss, break_count)).
+    ``dtype`` (test hook): the reference computes in float32; float64 runs the same steps on the same fp32 inputs in double
+    (the pose comes back in that precision), so the difference of the two is the rule's own rounding error."""
+    X = torch.from_numpy(np.ascontiguousarray(xyz_src, np.float32))[None].to(dtype)
+    Y = torch.from_numpy(np.ascontiguousarray(xyz_ref, np.float32))[None].to(dtype)
+    W = None if weights is None else torch.from_numpy(np.ascontiguousarray(weights, np.float32)).reshape(1, -1, 1).to(dtype)
+    P = torch.from_numpy(np.ascontiguousarray(pose, np.float32)).to(dtype)
     rot6d = torch.nn.Parameter(torch.cat([P[:3, 0], P[:3, 1]])[None].clone())      # Transformation.__init__ (DGR.py:111-123)
     trans = torch.nn.Parameter(P[:3, 3][None].clone())
 
@@ -72,7 +75,7 @@ def transformation_finetune(xyz_src: np.ndarray, xyz_ref: np.ndarray, pose: np.n
             if brk >= max_break_count:
                 break
         loss_prev = loss.item()
-    out = np.zeros((3, 4), np.float32)
+    out = np.zeros((3, 4), np.float32 if dtype == torch.float32 else np.float64)
     out[:, :3] = ortho2rotation(rot6d.detach())[0].numpy()
     out[:, 3] = trans[0].detach().numpy()
     return out, {"iterations": i, "loss": float(loss.item()) if loss is not None else float(loss_prev), "break_count": brk}

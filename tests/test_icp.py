@@ -54,10 +54,13 @@ def test_gpu_icp_matches_oracle(n, seed, noise):
     T, stats = T.cpu().numpy(), stats.cpu().numpy()
     for k, (s, r, t0, t_gt) in enumerate(cases):
         To, fitness, rmse, converged, iters = icp(s, r, t0, 0.1)
+        print(f"[icp] n={n} case {k}: iterations device {int(stats[k, 3])} / oracle {iters}")
         assert abs(stats[k, 0] - fitness) < 2e-3 and abs(stats[k, 1] - rmse) < 1e-5, (stats[k], fitness, rmse)
         assert _rot_err(T[k][:, :3].astype(np.float64), To[:, :3]) < 2e-5
         assert np.linalg.norm(T[k][:, 3] - To[:, 3]) < 2e-5
-        assert stats[k, 2] == 1.0 and abs(stats[k, 3] - iters) <= 2
+        # exact: the device stopped at the oracle's iteration in all nine cases here (4..11 iterations) and in every case of
+        # test_gpu_icp_edges.py (1..25 iterations, 5000 partially overlapping points included)
+        assert stats[k, 2] == 1.0 and stats[k, 3] == iters
         if noise == 0.0:
             assert _rot_err(T[k][:, :3].astype(np.float64), t_gt[:, :3]) < 1e-4
     # nothing within reach: the initial pose comes back
