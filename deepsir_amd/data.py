@@ -19,12 +19,16 @@ File parsing is host IO in numpy.  Every per-point step runs on the device throu
 (ascending voxel index; open3d's hash order is not reproducible without open3d, see include/dsir.h), which is
 immaterial to the network: its input is a point SET that the resampler permutes anyway.
 
-The train / val branches (augmentation, pickled 3DMatch fragments, SemanticKITTI labels) feed training, which is out of
-scope."""
+The train / val branches (bottom of this file): `ThreeDMatchTrain` (pickled fragments + overlap table,
+threeDMatch_loader.py:39-115, :139-159), `KittiOdometryTrain` (prepare_kitti, kitti_loader.py:80-96, :299-346, :384-406) and
+`TrainBatches`, which turns either into device-resident training batches: host parsing, then voxel grid -> augmentation
+(`Engine.augment`, csrc/augment.hip; the rule is deepsir_amd/augment.py) -> ground-truth matches (`Engine.radius_matches`), all
+on the device."""
 from __future__ import annotations
 
 import glob
 import os
+import pickle
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -347,3 +351,219 @@ class KittiOdometryTest:
             out["labels_src"] = pts[0, :, 4].to(torch.int32)       # astype(np.int32): truncation of the voxel mean
             out["labels_ref"] = pts[1, :, 4].to(torch.int32)
         return out
+
+
+# ================================================================================================== train / val splits
+KITTI_TRAIN_SEQUENCES = (0, 1, 2, 3, 4, 5)       # the reference's dataloader/split/train_kitti.txt, val_kitti.txt
+KITTI_VAL_SEQUENCES = (6, 7)
+
+
+class ThreeDMatchTrain:
+    """The 3DMatch train / val split as the reference reads it (threeDMatch_loader.py:39-115, :139-159): fragments from
+    `<root>/3dmatch_train_val/3DMatch_{split}_0.030_points.pkl` ({id: [n, 3]}), pairs "src@ref" of `..._overlap.pkl` whose
+    overlap exceeds 0.3 in the file's order, ground truth the identity (the fragments are stored in a common frame);
+    `num_val` > 0 truncates the val split.  Augmentation switches per split as :54-69: val keeps the rotation and drops
+    jitter and scale."""
+
+    def __init__(self, root: str, engine, split: str = "train", num_points: int = 18000, num_val: int = -1, voxel_size: float = 0.03,
+                 overlap_thres: float = 0.3, positive_pair_radius_multiplier: float = 3.0, reference_gt: bool = False):
+        from .augment import AugmentConfig
+        if split not in ("train", "val"):
+            raise ValueError("ThreeDMatchTrain: split is 'train' or 'val' (the test split is ThreeDMatchTest)")
+        self.root_path = os.path.join(root, "3dmatch_train_val")
+        pts_fn = os.path.join(self.root_path, f"3DMatch_{split}_0.030_points.pkl")
+        ovl_fn = os.path.join(self.root_path, f"3DMatch_{split}_0.030_overlap.pkl")
+        for fn in (pts_fn, ovl_fn):
+            if not os.path.exists(fn):
+                raise FileNotFoundError(fn)
+        with open(pts_fn, "rb") as f:
+            self.points = pickle.load(f)
+        with open(ovl_fn, "rb") as f:
+            overlap = pickle.load(f)
+        self.engine, self.split, self.voxel_size, self.crop = engine, split, float(voxel_size), None
+        self.files = self.select_pairs(overlap, overlap_thres)
+        if num_val > 0 and split == "val":
+            self.files = self.files[:num_val]
+        train = split == "train"
+        self.feat_len, self.label_col = 3, None
+        self.match_radius = self.voxel_size * float(positive_pair_radius_multiplier)
+        self.augment_cfg = AugmentConfig(variant="v1", num_points=int(num_points), random_rotation=True, rotation_range=90.0,
+                                         random_jitter=train, jitter_scale=0.005, random_scale=train, min_scale=0.8, max_scale=1.2,
+                                         reference_gt=reference_gt)
+
+    @staticmethod
+    def select_pairs(overlap: Dict[str, float], thres: float = 0.3) -> List[Tuple[str, str]]:
+        """prepare_files (:110-115)."""
+        return [tuple(k.split("@")) for k, v in overlap.items() if v > thres]
+
+    def __len__(self):
+        return len(self.files)
+
+    def raw(self, index: int):
+        """Host part of get_data (:141-159): (src [n, 3], ref [n, 3] float32, pose [4, 4], others)."""
+        src_id, ref_id = self.files[index]
+        others = {"seq": src_id.split("/")[0], "id_ref": int(ref_id.split("_")[-1]), "id_src": int(src_id.split("_")[-1])}
+        return (np.asarray(self.points[src_id], np.float32)[:, :3], np.asarray(self.points[ref_id], np.float32)[:, :3], np.identity(4),
+                others)
+
+
+class KittiOdometryTrain(KittiOdometryTest):
+    """KITTI odometry / SemanticKITTI train and val pairs (kitti_loader.py:16-96, :299-346, :384-406).  train: `prepare_kitti`,
+    every scan paired with the one MIN_TIME_DIFF = 2 later (time differences range(2, MAX_TIME_DIFF = 3); for drive 1 the
+    reference would shorten the range, which its own condition never does with these constants - kept as written).  val: the
+    >= 10 m selection of the test split (`KittiOdometryTest.pairs`) on the val sequences.  A sample is both scans cropped and
+    voxel-averaged as in the test branch, columns [x, y, z, reflectance, class]; ground truth from the same ICP-refined cache.
+    Augmentation (apply_augment_V2): train rotates and jitters, val does neither; neither scales; both permute."""
+
+    MIN_TIME_DIFF, MAX_TIME_DIFF = 2, 3
+
+    def __init__(self, root: str, engine, split: str = "train", sequences: Optional[Sequence[int]] = None, voxel_size: float = 0.3,
+                 feat_len: int = 4, num_points: int = 18000, num_val: int = -1, refine_pose: bool = True, with_labels: bool = True,
+                 positive_pair_radius_multiplier: float = 3.0, rot_mag: float = 45.0, trans_mag: float = 2.0, xy_rot_scale: float = 0.1):
+        from .augment import AugmentConfig
+        if split not in ("train", "val"):
+            raise ValueError("KittiOdometryTrain: split is 'train' or 'val' (the test split is KittiOdometryTest)")
+        if sequences is None:
+            sequences = KITTI_TRAIN_SEQUENCES if split == "train" else KITTI_VAL_SEQUENCES
+        self.split = split
+        if split == "train":
+            super().__init__(root, engine, (), voxel_size, feat_len, num_points, 0, refine_pose, with_labels)
+            for drive in sequences:
+                self.files.extend(self.train_pairs(int(drive), self.scan_ids(int(drive))))
+        else:
+            super().__init__(root, engine, sequences, voxel_size, feat_len, num_points, 0, refine_pose, with_labels)
+            if num_val > 0:
+                self.files = self.files[:num_val]
+        train = split == "train"
+        self.crop = (3.0, 60.0, -3.0, 10.0)
+        self.label_col = 4 if self.with_labels else None
+        self.match_radius = self.voxel_size * float(positive_pair_radius_multiplier)
+        self.augment_cfg = AugmentConfig(variant="v2", num_points=int(num_points), random_rotation=train, random_jitter=train,
+                                         random_scale=False, rot_mag=rot_mag, trans_mag=trans_mag, xy_rot_scale=xy_rot_scale)
+
+    @classmethod
+    def train_pairs(cls, drive: int, inames: Sequence[int]) -> List[Tuple[int, int, int]]:
+        """prepare_kitti (:80-96) for one drive."""
+        if drive == 1 and (cls.MAX_TIME_DIFF - 1) > cls.MIN_TIME_DIFF:
+            max_time_diff = cls.MAX_TIME_DIFF - 1
+        else:
+            max_time_diff = cls.MAX_TIME_DIFF
+        have, out = set(inames), []
+        for start in inames:
+            for diff in range(cls.MIN_TIME_DIFF, max_time_diff):
+                if start + diff in have:
+                    out.append((drive, start, start + diff))
+        return out
+
+    def raw(self, index: int):
+        """Host part of get_data (:299-346): both scans as [n, 4 | 5] float32 (uncropped: the crop runs with the voxel grid on the
+        device), the refined pose [4, 4], others."""
+        drive, t0, t1 = self.files[index]
+        seq = os.path.join(self.root_path, "sequences", "%02d" % drive)
+        scans = [read_velodyne(os.path.join(seq, "velodyne", "%06d.bin" % t)) for t in (t0, t1)]
+        c = self.crop
+
+        def crop_host(a):
+            r2 = (a[:, :3].astype(np.float64) ** 2).sum(1)
+            return a[(r2 <= c[1] ** 2) & (r2 > c[0] ** 2) & (a[:, 2] >= c[2]) & (a[:, 2] <= c[3])]
+        M = self.gt_pose(drive, t0, t1, crop_host(scans[0]), crop_host(scans[1]))
+        if self.with_labels:
+            scans = [np.concatenate([a, read_semantic_labels(os.path.join(seq, "labels", "%06d.label" % t), len(a))[:, None].astype(np.float32)], 1)
+                     for a, t in zip(scans, (t0, t1))]
+        return scans[0], scans[1], M, {"seq": drive, "id_src": t0, "id_ref": t1}
+
+
+class TrainBatches:
+    """Device-resident training batches of a train / val dataset above: an iterable with `set_epoch(e)`.
+
+    Per batch: host parsing of the samples not seen before; then on the device the voxel grid (`Engine.voxel_downsample`, every
+    new cloud of the batch in ONE ragged call; the voxelised clouds are cached per dataset index, at most `cache_size` samples like
+    the reference's cache, so later epochs skip parsing and voxelising), `Engine.augment`, and for `pipeline='align'` the
+    reference's `get_matches` on the augmented clouds: `Engine.radius_matches` + `as_reference_matches` with the dataset's radius
+    voxel_size * positive_pair_radius_multiplier, or - `match_radius` given - just that radius in the dict, from which
+    `Network.train_step` forms the same targets without a list.
+
+    Yields the reference's collate dict (data_base.py:196-219): points_src / points_ref [B, N, feat_len] fp32 and transform_gt
+    [B, 3, 4] fp32 on the device, labels_src / labels_ref [B, N] int64 when the dataset has labels, matches (list of B int64
+    arrays [n', 2]) or match_radius, others (list of B dicts), plus `invalid` [2, B] int32 (`Engine.augment`).
+
+    Every random number comes from (seed, epoch, dataset index): a sample is the same bytes whatever batch it lands in, and the
+    epoch's order is a permutation drawn from the same counter RNG (`augment.epoch_order`)."""
+
+    def __init__(self, dataset, batch_size: int, seed: int, shuffle: bool = True, pipeline: str = "align",
+                 match_radius: Optional[float] = None, drop_last: bool = True, cache_size: int = 8000):
+        self.dataset, self.engine = dataset, dataset.engine
+        self.batch_size, self.seed, self.shuffle, self.pipeline = int(batch_size), int(seed), bool(shuffle), pipeline
+        self.match_radius, self.drop_last, self.cache_size = match_radius, bool(drop_last), int(cache_size)
+        self.epoch = 0
+        self.cache: Dict[int, tuple] = {}
+
+    def set_epoch(self, epoch: int) -> None:
+        self.epoch = int(epoch)
+
+    def __len__(self):
+        n = len(self.dataset)
+        return n // self.batch_size if self.drop_last else -(-n // self.batch_size)
+
+    def order(self) -> np.ndarray:
+        from .augment import epoch_order
+        return epoch_order(self.seed, self.epoch, len(self.dataset), self.shuffle)
+
+    def __iter__(self):
+        order = self.order()
+        for b in range(len(self)):
+            yield self.batch(order[b * self.batch_size:(b + 1) * self.batch_size].tolist())
+
+    def voxels(self, indices: Sequence[int]) -> List[tuple]:
+        """(voxels_src [n, C], voxels_ref [n', C] on the device, pose [4, 4], others) of every index, from the cache where present."""
+        ds = self.dataset
+        new = [i for i in dict.fromkeys(indices) if i not in self.cache]
+        fresh = {}
+        if new:
+            raws = [ds.raw(i) for i in new]
+            clouds = [_to_device(self.engine, c) for r in raws for c in r[:2]]
+            vox, counts = self.engine.voxel_downsample(clouds, ds.voxel_size, ds.crop)
+            n = counts.cpu().tolist()
+            for j, i in enumerate(new):
+                fresh[i] = (vox[2 * j, :n[2 * j]].clone(), vox[2 * j + 1, :n[2 * j + 1]].clone(), raws[j][2], raws[j][3])
+                if len(self.cache) < self.cache_size:
+                    self.cache[i] = fresh[i]
+        return [self.cache[i] if i in self.cache else fresh[i] for i in indices]
+
+    def assemble(self, items: Sequence[tuple]):
+        """Cached ragged clouds -> (voxels [2, B, cap, C], counts [2, B] i32, poses [B, 4, 4]): copies only."""
+        B = len(items)
+        cap = max(1, max(int(t.shape[0]) for it in items for t in it[:2]))
+        vox = torch.zeros((2, B, cap, items[0][0].shape[1]), dtype=torch.float32, device=self.engine.device)
+        counts = np.zeros((2, B), np.int32)
+        for b, it in enumerate(items):
+            for s in (0, 1):
+                counts[s, b] = it[s].shape[0]
+                vox[s, b, :counts[s, b]] = it[s]
+        return vox, torch.from_numpy(counts).to(self.engine.device), np.stack([it[2] for it in items])
+
+    def finish(self, vox, counts, poses, indices, others) -> Dict[str, object]:
+        """Voxel tensors -> the finished dict, all on the device."""
+        ds = self.dataset
+        src, ref, gt, invalid = self.engine.augment(vox[0], counts[0], vox[1], counts[1], poses, ds.augment_cfg, self.seed, self.epoch,
+                                                    indices)
+        F = int(ds.feat_len)
+        out = {"points_src": src[:, :, :F].contiguous() if src.shape[2] != F else src,
+               "points_ref": ref[:, :, :F].contiguous() if ref.shape[2] != F else ref, "transform_gt": gt, "others": list(others),
+               "invalid": invalid}
+        if ds.label_col is not None:
+            out["labels_src"] = src[:, :, ds.label_col].to(torch.int64)       # truncation of the voxel mean, then .long()
+            out["labels_ref"] = ref[:, :, ds.label_col].to(torch.int64)
+        if self.pipeline == "align":
+            if self.match_radius is not None:
+                out["match_radius"] = float(self.match_radius)
+            else:
+                from .train import as_reference_matches
+                off, cols = self.engine.radius_matches(out["points_src"], out["points_ref"], gt, ds.match_radius)
+                out["matches"] = as_reference_matches(off, cols, src.shape[0], src.shape[1])
+        return out
+
+    def batch(self, indices: Sequence[int]) -> Dict[str, object]:
+        items = self.voxels(indices)
+        vox, counts, poses = self.assemble(items)
+        return self.finish(vox, counts, poses, indices, [it[3] for it in items])

@@ -385,6 +385,51 @@ class Engine:
         vox, counts = self.voxel_downsample(clouds, voxel_size, crop)
         return self.resample(vox, counts, k, seed, mode), counts
 
+    def augment(self, vox_src: torch.Tensor, counts_src: torch.Tensor, vox_ref: torch.Tensor, counts_ref: torch.Tensor, transform,
+                cfg, seed: int, epoch: int, indices: Sequence[int], k: Optional[int] = None, return_rows: bool = False):
+        """DataBase.apply_augment / apply_augment_V2 for P pairs on the device (csrc/augment.hip; the rule: deepsir_amd/augment.py).
+        vox_* [P, cap, C] + counts_* [P] as ``voxel_downsample`` writes them, transform [P, 3|4, 4] (host, float64; None = identity),
+        cfg an ``augment.AugmentConfig``, indices the samples' DATASET indices (the random keys come from (seed, epoch, index), never
+        from the position in this call) -> (points_src [P,k,C], points_ref [P,k,C], transform_gt [P,3,4], invalid [2,P] i32: bit 0
+        empty cloud, bit 1 non-finite centroid).  Host work: the per-cloud numbers, uploaded as ONE tensor; no synchronisation."""
+        from . import augment as A
+        ops = self._train_ops()
+        P = len(indices)
+        k = int(k or cfg.num_points)
+        if k < 1:
+            raise EngineError("augment: the number of output points (k or cfg.num_points) must be positive")
+        M = np.tile(np.eye(4)[:3], (P, 1, 1)) if transform is None else np.asarray(transform, np.float64)[:, :3, :]
+        pp = [A.pair_params(cfg, seed, epoch, int(i)) for i in indices]
+        blocks = [A.pack_params([p[s] for p in pp]) for s in (0, 1)]
+        host = np.concatenate([blocks[0].reshape(-1), blocks[1].reshape(-1), np.ascontiguousarray(M).reshape(-1)])
+        dev = torch.from_numpy(host).to(self.device, non_blocking=True)
+        n_prm = P * A.PARAM_SLOTS
+        prm = (dev[:n_prm], dev[n_prm:2 * n_prm])
+        cen = self._empty((2, P, 3), torch.float64)
+        invalid = self._empty((2, P), torch.int32)
+        out, rows = [], []
+        for s, (vox, counts) in enumerate(((vox_src, counts_src), (vox_ref, counts_ref))):
+            vox, counts = _chk(vox, torch.float32, "voxels"), _chk(counts, torch.int32, "counts")
+            if vox.dim() != 3 or vox.shape[0] != P or counts.numel() != P or vox.shape[2] < 3:
+                raise EngineError("augment: voxels [P, cap, C >= 3] and counts [P] expected for both sides")
+            _, cap, stride = vox.shape
+            sc = ops.scratch(max(int(self.lib.dsir_t_cloud_centroids_scratch(P)), int(self.lib.dsir_t_resample_keyed_scratch(P, cap))))
+            ops._launch("dsir_t_cloud_centroids", _ptr(vox), _ptr(counts), P, cap, stride, _ptr(cen[s]), _ptr(invalid[s]), _ptr(sc))
+            pts = self._empty((P, k, stride))
+            r = self._empty((P, k), torch.int32) if return_rows else None
+            need_perm = int(any(p[s].resample_mode != A.RESAMPLE_FIXED for p in pp))
+            ops._launch("dsir_t_resample_keyed", _ptr(vox), _ptr(counts), P, cap, stride, k, _ptr(prm[s]), need_perm, _ptr(pts), _ptr(r),
+                        _ptr(sc))
+            ops._launch("dsir_t_augment", _ptr(pts), _ptr(counts), P, k, stride, _ptr(prm[s]), _ptr(cen[s]), _ptr(pts))
+            out.append(pts)
+            rows.append(r)
+        gt = self._empty((P, 3, 4))
+        ops._launch("dsir_t_augment_gt", _ptr(dev[2 * n_prm:]), _ptr(prm[0]), _ptr(prm[1]), _ptr(cen[0]), _ptr(cen[1]), P,
+                    int(bool(cfg.reference_gt)), _ptr(gt))
+        if return_rows:
+            return out[0], out[1], gt, invalid, rows[0], rows[1]
+        return out[0], out[1], gt, invalid
+
     # ------------------------------------------------------------------ after the path: metrics
     METRIC_NAMES = ("r_mse", "r_mae", "t_mse", "t_mae", "err_r_deg", "err_t", "succ", "chamfer_dist")
 

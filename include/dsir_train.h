@@ -180,6 +180,39 @@ int dsir_t_match_keys(void* stream, const int32_t* matches, const int32_t* pair_
 int dsir_t_inlier_targets_matches(void* stream, const int64_t* keys, const int32_t* pair_offsets, const int32_t* idx, int n_iter, int pairs,
                                   int J, int64_t hash_seed, float* labels);
 
+/* ---- training augmentation (csrc/augment.hip) ------------------------------------------------------------------------------------
+ * DataBase.apply_augment / apply_augment_V2 (dataloader/data_base.py:221-296) between the voxel grid and the ground-truth matches.
+ * The reference's random sources cannot be pinned; the rule is this engine's and is written down in deepsir_amd/augment.py (the
+ * host restatement the tests compare against): counter-keyed splitmix64 draws, fp32 point arithmetic in one order without fused
+ * multiply-add, float64 for the centroid, the jitter and the pose.  No atomics: the same inputs give the same bytes, and a cloud's
+ * rows depend on its own key alone, never on the other clouds of the call.
+ * params [clouds][24] eight-byte slots per cloud: R[9], t[3], scale, jitter scale, jitter clip (doubles), jitter mode (0 none,
+ * 1 uniform, 2 clipped normal), centered, normals (int64), key (uint64), resample mode (0 Resampler, 1 FixedResampler, 2 permute
+ * then FixedResampler), scaled (int64), 3 unused.
+ *
+ * _cloud_centroids: float64 mean xyz of the first min(counts[c], cap) rows of points [clouds][cap][stride] (dsir_voxel_downsample's
+ * output) -> centroids [clouds][3]; invalid [clouds] int32: bit 0 = no rows (centroid 0), bit 1 = non-finite centroid.  Two-stage
+ * sum in a fixed order; scratch: dsir_t_cloud_centroids_scratch(clouds) bytes. */
+size_t dsir_t_cloud_centroids_scratch(int clouds);
+int dsir_t_cloud_centroids(void* stream, const float* points, const int32_t* counts, int clouds, int cap, int stride, double* centroids,
+                           int32_t* invalid, void* scratch);
+/* The rule of dsir_resample with a key per cloud (params[c].key, mode params[c].rmode) in place of (seed, position in the call):
+ * cloud c's rows are the same whatever else the call holds.  in [clouds][cap][stride] -> out [clouds][k][stride]; rows (may be NULL) [clouds][k] =
+ * the source row of every output row; an empty cloud gives zeros.  need_perm = 0 skips the sort when every cloud's mode is 1.
+ * scratch: dsir_t_resample_keyed_scratch(clouds, cap) bytes. */
+size_t dsir_t_resample_keyed_scratch(int clouds, int cap);
+int dsir_t_resample_keyed(void* stream, const float* in, const int32_t* counts, int clouds, int cap, int stride, int k, const void* params,
+                          int need_perm, float* out, int32_t* rows, void* scratch);
+/* One pass over in [clouds][k][stride] (out may be in): row j of cloud c -> s ((R (p - m) + t) + jitter(key, j)), columns 3:6 rotated
+ * by R when params[c].normals and stride >= 6, every other column copied.  A cloud with counts[c] <= 0 is written as zeros. */
+int dsir_t_augment(void* stream, const float* in, const int32_t* counts, int clouds, int k, int stride, const void* params,
+                   const double* centroids, float* out);
+/* transform_gt [pairs][3][4] fp32 = A_ref M A_src^-1, A = [R | t - R m] (m: the fp32-rounded centroid where centered, else 0), M
+ * [pairs][3][4] float64, composed in float64 and rounded once; the translation is multiplied by the pair's scale unless
+ * reference_gt (the reference leaves it unscaled, data_base.py:250-256). */
+int dsir_t_augment_gt(void* stream, const double* M, const void* params_src, const void* params_ref, const double* centroids_src,
+                      const double* centroids_ref, int pairs, int reference_gt, float* transform_gt);
+
 #ifdef __cplusplus
 }
 #endif
