@@ -43,27 +43,6 @@ struct AlignLossArgs {
   float* grad;                                // [n_iter][P][J]
 };
 
-template <int NV>
-__device__ __forceinline__ void block_sum_d(double (&v)[NV], double* sh /* [AL_WAVES][NV] + [NV] */) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-  for (int i = 0; i < NV; ++i) v[i] = wave_sum(v[i]);
-  __syncthreads();
-  if (lane == 0) {
-#pragma unroll
-    for (int i = 0; i < NV; ++i) sh[w * NV + i] = v[i];
-  }
-  __syncthreads();
-  if (threadIdx.x < NV) {
-    double s = 0.0;
-    for (int ww = 0; ww < AL_WAVES; ++ww) s += sh[ww * NV + threadIdx.x];
-    sh[AL_WAVES * NV + threadIdx.x] = s;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < NV; ++i) v[i] = sh[AL_WAVES * NV + i];
-}
-
 struct IterState {
   double R[3][3], t[3];        // this iteration's transform
   double Rc[3][3], tc[3];      // cumulative transform after it
@@ -103,7 +82,7 @@ __global__ __launch_bounds__(AL_THREADS) void align_loss_kernel(AlignLossArgs a)
   for (int it = 0; it < a.n_iter; ++it) {
     double v1[1] = {0.0};
     for (int j = tid; j < J; j += AL_THREADS) v1[0] += fabs(weight(it, j));
-    block_sum_d<1>(v1, sh);
+    block_sum<AL_WAVES>(v1, sh);
     const double den = (double)((float)v1[0] + 1e-16f);
     double v7[7] = {0, 0, 0, 0, 0, 0, 0};
     for (int j = tid; j < J; j += AL_THREADS) {
@@ -114,7 +93,7 @@ __global__ __launch_bounds__(AL_THREADS) void align_loss_kernel(AlignLossArgs a)
       for (int k = 0; k < 3; ++k) { v7[k] += (double)((float)s[k] * (float)wn); v7[3 + k] += (double)((float)t[k] * (float)wn); }
       v7[6] += wn;
     }
-    block_sum_d<7>(v7, sh);
+    block_sum<AL_WAVES>(v7, sh);
     const double cs[3] = {(double)(float)v7[0], (double)(float)v7[1], (double)(float)v7[2]};
     const double ct[3] = {(double)(float)v7[3], (double)(float)v7[4], (double)(float)v7[5]};
     double v9[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -130,20 +109,18 @@ __global__ __launch_bounds__(AL_THREADS) void align_loss_kernel(AlignLossArgs a)
 #pragma unroll
         for (int c = 0; c < 3; ++c) v9[r * 3 + c] += (double)(sc[r] * tw[c]);
     }
-    block_sum_d<9>(v9, sh);
+    block_sum<AL_WAVES>(v9, sh);
     if (tid == 0) {
       IterState& q = st[it];
       double H[3][3], U[3][3], Sv[3], V[3][3];
       for (int r = 0; r < 3; ++r)
         for (int c = 0; c < 3; ++c) H[r][c] = (double)(float)v9[r * 3 + c];
       svd3(H, U, Sv, V);
-      double Rp[3][3];
-      for (int r = 0; r < 3; ++r)
-        for (int c = 0; c < 3; ++c) Rp[r][c] = V[r][0] * U[c][0] + V[r][1] * U[c][1] + V[r][2] * U[c][2];
-      const double d = det3(Rp) > 0 ? 1.0 : -1.0;
+      double R[3][3];
+      const double d = procrustes_rotation(U, V, R);
       for (int r = 0; r < 3; ++r) {
         for (int c = 0; c < 3; ++c) {
-          q.R[r][c] = (double)(float)(V[r][0] * U[c][0] + V[r][1] * U[c][1] + d * V[r][2] * U[c][2]);
+          q.R[r][c] = (double)(float)R[r][c];
           q.V[r][c] = V[r][c];
           q.U[r][c] = c == 2 ? d * U[r][c] : U[r][c];      // U D
         }
@@ -194,7 +171,7 @@ __global__ __launch_bounds__(AL_THREADS) void align_loss_kernel(AlignLossArgs a)
         }
       }
     }
-    block_sum_d<14>(v14, sh);
+    block_sum<AL_WAVES>(v14, sh);
     if (tid == 0) {
       for (int k = 0; k < 12; ++k) st[it].G[k] = v14[k];
       if (a.loss_part) {      // this pair's terms; align_loss_reduce_kernel adds the pairs in pair order (no atomics: same bits every run)
@@ -287,7 +264,7 @@ __global__ __launch_bounds__(AL_THREADS) void align_loss_kernel(AlignLossArgs a)
     };
     double v1[1] = {0.0};
     for (int j = tid; j < J; j += AL_THREADS) v1[0] += g_wn(j) * weight(it, j);
-    block_sum_d<1>(v1, sh);
+    block_sum<AL_WAVES>(v1, sh);
     const double dotw = v1[0], bce = (a.labels && a.wt_in > 0.f) ? disc * (double)a.wt_in * inv_rows : 0.0;
     for (int j = tid; j < J; j += AL_THREADS) {
       const double w = weight(it, j);

@@ -61,10 +61,38 @@ __device__ __forceinline__ double wave_sum(double v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
   return v;
 }
+// Sum of NV doubles over a workgroup of NW waves, the totals returned to every thread: the wave butterfly, then thread k < NV
+// adds the waves' sums of value k in ascending wave order (a fixed order: same bits every run).  sh: [NW][NV] + [NV] doubles.
+template <int NW, int NV>
+__device__ __forceinline__ void block_sum(double (&v)[NV], double* sh) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+  for (int i = 0; i < NV; ++i) v[i] = wave_sum(v[i]);
+  __syncthreads();
+  if (lane == 0) {
+#pragma unroll
+    for (int i = 0; i < NV; ++i) sh[w * NV + i] = v[i];
+  }
+  __syncthreads();
+  if (threadIdx.x < NV) {
+    double s = 0.0;
+    for (int ww = 0; ww < NW; ++ww) s += sh[ww * NV + threadIdx.x];
+    sh[NW * NV + threadIdx.x] = s;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < NV; ++i) v[i] = sh[NW * NV + i];
+}
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
   return v;
+}
+
+// Row r of p' = R p + t for a row-major 3x4 transform T, in the one rounding sequence every pose kernel moves points by
+// (kabsch.hip, icp.hip)
+__device__ __forceinline__ float se3_row(const float* T, int r, float x, float y, float z) {
+  return __fadd_rn(fmaf(z, T[r * 4 + 2], fmaf(y, T[r * 4 + 1], __fmul_rn(x, T[r * 4 + 0]))), T[r * 4 + 3]);
 }
 
 // exp(x) for x <= 0 (softmax numerators, x = score - max): 2^(x*log2e) with the hardware v_exp_f32 (1 ulp).

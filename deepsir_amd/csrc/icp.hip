@@ -31,8 +31,7 @@ __global__ void icp_apply_kernel(const float* __restrict__ src, int stride, int 
     const float x = p[0], y = p[1], z = p[2];
     float* o = cur + ((int64_t)pair * J + j) * 3;
 #pragma unroll
-    for (int r = 0; r < 3; ++r)
-      o[r] = __fadd_rn(fmaf(z, t[r * 4 + 2], fmaf(y, t[r * 4 + 1], __fmul_rn(x, t[r * 4 + 0]))), t[r * 4 + 3]);
+    for (int r = 0; r < 3; ++r) o[r] = se3_row(t, r, x, y, z);
   }
 }
 

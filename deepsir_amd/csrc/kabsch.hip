@@ -14,6 +14,17 @@
 // (model.py:53,57).  Non-finite H => identity + invalid flag (model.py:61-64).
 // The same launch applies the transform to the src points, gathers the matched
 // ref points and composes the cumulative transform.
+//
+// Each formula is written once: the per-point functions add_abs_weight /
+// add_centroid_terms / add_covariance_terms hold the roundings of the three
+// passes, PairView a pair's pointers, kabsch_solve the SVD and the bookkeeping,
+// kabsch_frozen the step of a converged pair; block_sum and se3_row (p' = R p + t)
+// live in device_utils.h, the Procrustes rotation in svd3.h.  The kernels differ
+// only in where a thread's points come from: kabsch_kernel streams them from
+// memory once per pass, kabsch_reg_kernel<TR> holds them in registers,
+// kabsch_part_kernel<PHASE> streams one chunk of a large cloud (then
+// kabsch_final_kernel, kabsch_apply_kernel).  A thread always adds its points
+// i = first + tid, + 1024, .. in ascending order, so all three give the same bits.
 #include <cstdlib>
 
 #include "kernels.h"
@@ -30,25 +41,21 @@ namespace {
 constexpr int NTHR = 1024;
 constexpr int NWAVE = NTHR / 64;
 
-template <int NV>
-__device__ __forceinline__ void block_sum(double (&v)[NV], double* sh /* [NWAVE][NV] + [NV] */) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-  for (int i = 0; i < NV; ++i) v[i] = wave_sum(v[i]);
-  __syncthreads();
-  if (lane == 0) {
-#pragma unroll
-    for (int i = 0; i < NV; ++i) sh[w * NV + i] = v[i];
+__device__ __forceinline__ void identity34(float (&T)[12]) {
+  const float I[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+  for (int k = 0; k < 12; ++k) T[k] = I[k];
+}
+
+// a frozen pair (ICP converged; one thread): identity step, cumulative transform carried over
+__device__ void kabsch_frozen(const KabschArgs& a, int pair) {
+  float I[12];
+  identity34(I);
+  for (int k = 0; k < 12; ++k) a.T[(int64_t)pair * 12 + k] = I[k];
+  if (a.T_cum) {
+    float* out = a.T_cum + pair * a.T_stride;
+    const float* P = a.T_prev ? a.T_prev + pair * a.T_stride : I;
+    for (int k = 0; k < 12; ++k) out[k] = P[k];
   }
-  __syncthreads();
-  if (threadIdx.x < NV) {
-    double s = 0.0;
-    for (int ww = 0; ww < NWAVE; ++ww) s += sh[ww * NV + threadIdx.x];
-    sh[NWAVE * NV + threadIdx.x] = s;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < NV; ++i) v[i] = sh[NWAVE * NV + i];
 }
 
 // thread 0 of a pair: H (fp32, as the reference forms it) -> SVD in fp64 -> R, t; the pair's transform, flag and cumulative
@@ -62,20 +69,18 @@ __device__ void kabsch_solve(const KabschArgs& a, int pair, const double (&v9)[9
       H[r][c] = (double)h;
       finite = finite && isfinite(h);
     }
-  float T[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+  float T[12];
+  identity34(T);
   int bad = 1;
   if (finite) {
-    double U[3][3], S[3], V[3][3];
+    double U[3][3], S[3], V[3][3], Rd[3][3];
     svd3(H, U, S, V);
-    double Rp[3][3];
-    for (int r = 0; r < 3; ++r)
-      for (int c = 0; c < 3; ++c) Rp[r][c] = V[r][0] * U[c][0] + V[r][1] * U[c][1] + V[r][2] * U[c][2];
-    const double d = det3(Rp) > 0 ? 1.0 : -1.0;
+    procrustes_rotation(U, V, Rd);
     float R[3][3];
     bool ok = true;
     for (int r = 0; r < 3; ++r)
       for (int c = 0; c < 3; ++c) {
-        R[r][c] = (float)(V[r][0] * U[c][0] + V[r][1] * U[c][1] + d * V[r][2] * U[c][2]);
+        R[r][c] = (float)Rd[r][c];
         ok = ok && isfinite(R[r][c]);
       }
     if (ok) {
@@ -109,134 +114,138 @@ __device__ void kabsch_solve(const KabschArgs& a, int pair, const double (&v9)[9
   }
 }
 
+// one pair's inputs: the src points, the ref points they are matched to (through idx, or row by row) and the weights
+struct PairView {
+  const float* src; const float* ref; const int32_t* idx; const float* w;
+  int ld, sigmoid;
+  __device__ PairView(const KabschArgs& a, int pair)
+      : src(a.src + pair * a.src_stride), ref(a.ref + pair * a.ref_stride), idx(a.idx ? a.idx + (int64_t)pair * a.m : nullptr),
+        w(a.w + (int64_t)pair * a.m), ld(a.ref_ld ? a.ref_ld : 3), sigmoid(a.sigmoid) {}
+  __device__ __forceinline__ float squash(float x) const { return sigmoid ? 1.f / (1.f + expf(-x)) : x; }
+  __device__ __forceinline__ float weight(int i) const { return squash(w[i]); }
+  __device__ __forceinline__ void source(int i, float (&s)[3]) const {
+    s[0] = src[(int64_t)i * 3]; s[1] = src[(int64_t)i * 3 + 1]; s[2] = src[(int64_t)i * 3 + 2];
+  }
+  __device__ __forceinline__ void target(int i, float (&t)[3]) const {
+    const int64_t j = idx ? idx[i] : i;
+    t[0] = ref[j * ld]; t[1] = ref[j * ld + 1]; t[2] = ref[j * ld + 2];
+  }
+};
+
+// ---- the three passes, one point at a time: THE statement of the fp32 roundings every kernel below shares
+// pass 1: S = sum |w|
+__device__ __forceinline__ void add_abs_weight(double (&v1)[1], float w) { v1[0] += (double)fabsf(w); }
+__device__ __forceinline__ float weight_den(double S) { return (float)S + 1e-16f; }   // model.py:35 (fp32 sum + _EPS)
+// pass 2: weighted centroids, wn = w / den
+__device__ __forceinline__ void add_centroid_terms(double (&v6)[6], const float (&s)[3], const float (&t)[3], float wn) {
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    v6[c] += (double)__fmul_rn(s[c], wn);
+    v6[3 + c] += (double)__fmul_rn(t[c], wn);
+  }
+}
+__device__ __forceinline__ void centroids(const double (&v6)[6], float (&cs)[3], float (&ct)[3]) {
+#pragma unroll
+  for (int c = 0; c < 3; ++c) { cs[c] = (float)v6[c]; ct[c] = (float)v6[3 + c]; }
+}
+// pass 3: covariance H[a][b] = sum (s_a - cs_a) * ((t_b - ct_b) * wn)
+__device__ __forceinline__ void add_covariance_terms(double (&v9)[9], const float (&s)[3], const float (&t)[3], float wn,
+                                                     const float (&cs)[3], const float (&ct)[3]) {
+  float sc[3], tw[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    sc[c] = __fsub_rn(s[c], cs[c]);
+    tw[c] = __fmul_rn(__fsub_rn(t[c], ct[c]), wn);
+  }
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v9[r * 3 + c] += (double)__fmul_rn(sc[r], tw[c]);
+}
+// ---- the passes STREAMED: point i comes from memory.  DSIR_KABSCH_FOR_POINTS walks a thread's points i = first + tid, + 1024, .. < last
+// in ascending order
+#define DSIR_KABSCH_FOR_POINTS(i, first, last) DSIR_KABSCH_UNROLL for (int i = (first) + threadIdx.x; i < (last); i += NTHR)
+__device__ __forceinline__ void stream_abs_weight(const PairView& p, int i, double (&v1)[1]) { add_abs_weight(v1, p.weight(i)); }
+__device__ __forceinline__ void stream_centroid_terms(const PairView& p, int i, float den, double (&v6)[6]) {
+  const float wn = p.weight(i) / den;
+  float s[3], t[3];
+  p.target(i, t);
+  p.source(i, s);
+  add_centroid_terms(v6, s, t, wn);
+}
+__device__ __forceinline__ void stream_covariance_terms(const PairView& p, int i, float den, const float (&cs)[3], const float (&ct)[3],
+                                                        double (&v9)[9]) {
+  const float wn = p.weight(i) / den;
+  float s[3], t[3];
+  p.target(i, t);
+  p.source(i, s);
+  add_covariance_terms(v9, s, t, wn, cs, ct);
+}
+// apply: p' = p R^T + t (se3_torch.py:60-77), and the matched ref point.  src_out may be the src array itself (ICP): a thread
+// has read its point before it writes it
+__device__ __forceinline__ void stream_apply(const PairView& p, float* so, float* mo, int i, const float* T) {
+  if (mo) {
+    float t[3];
+    p.target(i, t);
+    mo[(int64_t)i * 3] = t[0]; mo[(int64_t)i * 3 + 1] = t[1]; mo[(int64_t)i * 3 + 2] = t[2];
+  }
+  if (so) {
+    float s[3];
+    p.source(i, s);
+#pragma unroll
+    for (int r = 0; r < 3; ++r) so[(int64_t)i * 3 + r] = se3_row(T, r, s[0], s[1], s[2]);
+  }
+}
+
+// one 1024-thread workgroup per pair, the points streamed once per pass
 __global__ __launch_bounds__(NTHR) void kabsch_kernel(const KabschArgs a) {
   __shared__ double sh[NWAVE * 9 + 9];
   __shared__ float sT[12];
   const int pair = blockIdx.x;
   const int m = a.m;
-  if (a.skip && a.skip[pair]) {   // block-uniform: frozen pair (ICP converged): identity step, cumulative transform carried over
-    if (threadIdx.x == 0) {
-      const float I[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-      for (int k = 0; k < 12; ++k) a.T[(int64_t)pair * 12 + k] = I[k];
-      if (a.T_cum) {
-        float* out = a.T_cum + pair * a.T_stride;
-        const float* P = a.T_prev ? a.T_prev + pair * a.T_stride : I;
-        for (int k = 0; k < 12; ++k) out[k] = P[k];
-      }
-    }
+  if (a.skip && a.skip[pair]) {   // block-uniform
+    if (threadIdx.x == 0) kabsch_frozen(a, pair);
     return;
   }
-  const int ld = a.ref_ld ? a.ref_ld : 3;
-  const float* src = a.src + pair * a.src_stride;
-  const float* ref = a.ref + pair * a.ref_stride;
-  const int32_t* idx = a.idx ? a.idx + (int64_t)pair * m : nullptr;
-  const float* wl = a.w + (int64_t)pair * m;
-  auto weight = [&](int i) -> float {
-    const float x = wl[i];
-    return a.sigmoid ? 1.f / (1.f + expf(-x)) : x;
-  };
-  auto target = [&](int i, float& x, float& y, float& z) {
-    const int64_t j = idx ? idx[i] : i;
-    x = ref[j * ld]; y = ref[j * ld + 1]; z = ref[j * ld + 2];
-  };
-
-  // pass 1: S = sum |w|
+  const PairView p(a, pair);
   double v1[1] = {0.0};
-  DSIR_KABSCH_UNROLL
-  for (int i = threadIdx.x; i < m; i += NTHR) v1[0] += (double)fabsf(weight(i));
-  block_sum<1>(v1, sh);
-  const float den = (float)v1[0] + 1e-16f;   // model.py:35 (fp32 sum + _EPS)
-
-  // pass 2: weighted centroids
+  DSIR_KABSCH_FOR_POINTS(i, 0, m) stream_abs_weight(p, i, v1);
+  block_sum<NWAVE>(v1, sh);
+  const float den = weight_den(v1[0]);
   double v6[6] = {0, 0, 0, 0, 0, 0};
-  DSIR_KABSCH_UNROLL
-  for (int i = threadIdx.x; i < m; i += NTHR) {
-    const float wn = weight(i) / den;
-    float tx, ty, tz;
-    target(i, tx, ty, tz);
-    v6[0] += (double)__fmul_rn(src[(int64_t)i * 3], wn);
-    v6[1] += (double)__fmul_rn(src[(int64_t)i * 3 + 1], wn);
-    v6[2] += (double)__fmul_rn(src[(int64_t)i * 3 + 2], wn);
-    v6[3] += (double)__fmul_rn(tx, wn);
-    v6[4] += (double)__fmul_rn(ty, wn);
-    v6[5] += (double)__fmul_rn(tz, wn);
-  }
-  block_sum<6>(v6, sh);
-  const float cs[3] = {(float)v6[0], (float)v6[1], (float)v6[2]};
-  const float ct[3] = {(float)v6[3], (float)v6[4], (float)v6[5]};
-
-  // pass 3: covariance H[a][b] = sum (s_a - cs_a) * ((t_b - ct_b) * wn)
+  DSIR_KABSCH_FOR_POINTS(i, 0, m) stream_centroid_terms(p, i, den, v6);
+  block_sum<NWAVE>(v6, sh);
+  float cs[3], ct[3];
+  centroids(v6, cs, ct);
   double v9[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-  DSIR_KABSCH_UNROLL
-  for (int i = threadIdx.x; i < m; i += NTHR) {
-    const float wn = weight(i) / den;
-    float t[3];
-    target(i, t[0], t[1], t[2]);
-    float sc[3], tw[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      sc[k] = __fsub_rn(src[(int64_t)i * 3 + k], cs[k]);
-      tw[k] = __fmul_rn(__fsub_rn(t[k], ct[k]), wn);
-    }
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-      for (int c = 0; c < 3; ++c) v9[r * 3 + c] += (double)__fmul_rn(sc[r], tw[c]);
-  }
-  block_sum<9>(v9, sh);
+  DSIR_KABSCH_FOR_POINTS(i, 0, m) stream_covariance_terms(p, i, den, cs, ct, v9);
+  block_sum<NWAVE>(v9, sh);
 
   if (threadIdx.x == 0) kabsch_solve(a, pair, v9, cs, ct, sT);
   __syncthreads();
-  // apply: p' = p R^T + t (se3_torch.py:60-77); gather the matched ref points
   if (a.src_out || a.matched_out) {
     float* so = a.src_out ? a.src_out + pair * a.src_out_stride : nullptr;
     float* mo = a.matched_out ? a.matched_out + (int64_t)pair * m * 3 : nullptr;
-    for (int i = threadIdx.x; i < m; i += NTHR) {
-      if (mo) {
-        float tx, ty, tz;
-        target(i, tx, ty, tz);
-        mo[(int64_t)i * 3] = tx; mo[(int64_t)i * 3 + 1] = ty; mo[(int64_t)i * 3 + 2] = tz;
-      }
-      if (so) {
-        const float x = src[(int64_t)i * 3], y = src[(int64_t)i * 3 + 1], z = src[(int64_t)i * 3 + 2];
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-          const float d = fmaf(z, sT[r * 4 + 2], fmaf(y, sT[r * 4 + 1], __fmul_rn(x, sT[r * 4 + 0])));
-          so[(int64_t)i * 3 + r] = __fadd_rn(d, sT[r * 4 + 3]);
-        }
-      }
-    }
+    for (int i = threadIdx.x; i < m; i += NTHR) stream_apply(p, so, mo, i, sT);
   }
 }
 
-// ---- clouds of up to TR x 1024 points: the same kernel with the points HELD IN REGISTERS between the passes.  With one pair in
+// ---- clouds of up to TR x 1024 points: the same passes with the points HELD IN REGISTERS between them.  With one pair in
 // flight (the reference's evaluation mode) the solve sits in the dependent chain of every iteration, and each pass of kabsch_kernel
 // opens with its own weight -> index -> ref-point load chain (three round trips to L2 plus the apply step's fourth); here the chain
-// is paid once.  A thread owns the same points i = tid, tid + 1024, .. and adds them in the same order: same bits as kabsch_kernel.
+// is paid once.  A thread owns the same points i = tid, tid + 1024, .. and hands them to the same per-point functions in the same
+// order: same bits as kabsch_kernel.
 template <int TR>
 __global__ __launch_bounds__(NTHR) void kabsch_reg_kernel(const KabschArgs a) {
   __shared__ double sh[NWAVE * 9 + 9];
   __shared__ float sT[12];
   const int pair = blockIdx.x;
   const int m = a.m;
-  if (a.skip && a.skip[pair]) {   // block-uniform: frozen pair (ICP converged): identity step, cumulative transform carried over
-    if (threadIdx.x == 0) {
-      const float I[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-      for (int k = 0; k < 12; ++k) a.T[(int64_t)pair * 12 + k] = I[k];
-      if (a.T_cum) {
-        float* out = a.T_cum + pair * a.T_stride;
-        const float* P = a.T_prev ? a.T_prev + pair * a.T_stride : I;
-        for (int k = 0; k < 12; ++k) out[k] = P[k];
-      }
-    }
+  if (a.skip && a.skip[pair]) {   // block-uniform
+    if (threadIdx.x == 0) kabsch_frozen(a, pair);
     return;
   }
-  const int ld = a.ref_ld ? a.ref_ld : 3;
-  const float* src = a.src + pair * a.src_stride;
-  const float* ref = a.ref + pair * a.ref_stride;
-  const int32_t* idx = a.idx ? a.idx + (int64_t)pair * m : nullptr;
-  const float* wl = a.w + (int64_t)pair * m;
-
+  const PairView p(a, pair);
   float w[TR], s[TR][3], t[TR][3];
 #pragma unroll
   for (int k = 0; k < TR; ++k) {
@@ -244,78 +253,53 @@ __global__ __launch_bounds__(NTHR) void kabsch_reg_kernel(const KabschArgs a) {
     w[k] = 0.f;
     s[k][0] = s[k][1] = s[k][2] = t[k][0] = t[k][1] = t[k][2] = 0.f;
     if (i < m) {
-      const int64_t j = idx ? idx[i] : i;
-      w[k] = wl[i];
-      t[k][0] = ref[j * ld]; t[k][1] = ref[j * ld + 1]; t[k][2] = ref[j * ld + 2];
-      s[k][0] = src[(int64_t)i * 3]; s[k][1] = src[(int64_t)i * 3 + 1]; s[k][2] = src[(int64_t)i * 3 + 2];
+      w[k] = p.w[i];
+      p.target(i, t[k]);
+      p.source(i, s[k]);
     }
   }
-  if (a.sigmoid) {
 #pragma unroll
-    for (int k = 0; k < TR; ++k) w[k] = 1.f / (1.f + expf(-w[k]));
-  }
+  for (int k = 0; k < TR; ++k) w[k] = p.squash(w[k]);
 
-  // pass 1: S = sum |w|
   double v1[1] = {0.0};
 #pragma unroll
   for (int k = 0; k < TR; ++k)
-    if (threadIdx.x + k * NTHR < m) v1[0] += (double)fabsf(w[k]);
-  block_sum<1>(v1, sh);
-  const float den = (float)v1[0] + 1e-16f;   // model.py:35 (fp32 sum + _EPS)
+    if (threadIdx.x + k * NTHR < m) add_abs_weight(v1, w[k]);
+  block_sum<NWAVE>(v1, sh);
+  const float den = weight_den(v1[0]);
 
-  // pass 2: weighted centroids
   double v6[6] = {0, 0, 0, 0, 0, 0};
 #pragma unroll
   for (int k = 0; k < TR; ++k)
     if (threadIdx.x + k * NTHR < m) {
-      w[k] = w[k] / den;          // wn: the same quotient both passes of kabsch_kernel form
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        v6[c] += (double)__fmul_rn(s[k][c], w[k]);
-        v6[3 + c] += (double)__fmul_rn(t[k][c], w[k]);
-      }
+      w[k] = w[k] / den;          // wn, formed once: the quotient both streamed passes form
+      add_centroid_terms(v6, s[k], t[k], w[k]);
     }
-  block_sum<6>(v6, sh);
-  const float cs[3] = {(float)v6[0], (float)v6[1], (float)v6[2]};
-  const float ct[3] = {(float)v6[3], (float)v6[4], (float)v6[5]};
+  block_sum<NWAVE>(v6, sh);
+  float cs[3], ct[3];
+  centroids(v6, cs, ct);
 
-  // pass 3: covariance H[a][b] = sum (s_a - cs_a) * ((t_b - ct_b) * wn)
   double v9[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
   for (int k = 0; k < TR; ++k)
-    if (threadIdx.x + k * NTHR < m) {
-      float sc[3], tw[3];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        sc[c] = __fsub_rn(s[k][c], cs[c]);
-        tw[c] = __fmul_rn(__fsub_rn(t[k][c], ct[c]), w[k]);
-      }
-#pragma unroll
-      for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) v9[r * 3 + c] += (double)__fmul_rn(sc[r], tw[c]);
-    }
-  block_sum<9>(v9, sh);
+    if (threadIdx.x + k * NTHR < m) add_covariance_terms(v9, s[k], t[k], w[k], cs, ct);
+  block_sum<NWAVE>(v9, sh);
 
   if (threadIdx.x == 0) kabsch_solve(a, pair, v9, cs, ct, sT);
   __syncthreads();
-  // apply: p' = p R^T + t (se3_torch.py:60-77); the matched ref points
   if (a.src_out || a.matched_out) {
     float* so = a.src_out ? a.src_out + pair * a.src_out_stride : nullptr;
     float* mo = a.matched_out ? a.matched_out + (int64_t)pair * m * 3 : nullptr;
 #pragma unroll
-    for (int k = 0; k < TR; ++k) {
-      const int i = threadIdx.x + k * NTHR;
-      if (i >= m) continue;
-      if (mo) { mo[(int64_t)i * 3] = t[k][0]; mo[(int64_t)i * 3 + 1] = t[k][1]; mo[(int64_t)i * 3 + 2] = t[k][2]; }
-      if (so) {
+    for (int k = 0; k < TR; ++k)
+      if (threadIdx.x + k * NTHR < m) {
+        const int i = threadIdx.x + k * NTHR;
+        if (mo) { mo[(int64_t)i * 3] = t[k][0]; mo[(int64_t)i * 3 + 1] = t[k][1]; mo[(int64_t)i * 3 + 2] = t[k][2]; }
+        if (so) {
 #pragma unroll
-        for (int r = 0; r < 3; ++r) {
-          const float d = fmaf(s[k][2], sT[r * 4 + 2], fmaf(s[k][1], sT[r * 4 + 1], __fmul_rn(s[k][0], sT[r * 4 + 0])));
-          so[(int64_t)i * 3 + r] = __fadd_rn(d, sT[r * 4 + 3]);
+          for (int r = 0; r < 3; ++r) so[(int64_t)i * 3 + r] = se3_row(sT, r, s[k][0], s[k][1], s[k][2]);
         }
       }
-    }
   }
 }
 
@@ -325,82 +309,47 @@ __global__ __launch_bounds__(NTHR) void kabsch_reg_kernel(const KabschArgs a) {
 // 65536 points in 64 dependent trips per pass (218 us per solve with 2 pairs in flight); in chunks: five short launches.
 constexpr int CHUNK = 4096;
 
+// the chunks' partials of one pass, added in chunk order
+template <int NV>
+__device__ __forceinline__ void sum_chunks(const double* part, int nch, int at, double (&v)[NV]) {
+  for (int c = 0; c < nch; ++c)
+#pragma unroll
+    for (int k = 0; k < NV; ++k) v[k] += part[c * 16 + at + k];
+}
+
 template <int PHASE>
 __global__ __launch_bounds__(NTHR) void kabsch_part_kernel(const KabschArgs a, int nch) {
   __shared__ double sh[NWAVE * 9 + 9];
   const int pair = blockIdx.y, ch = blockIdx.x;
   if (a.skip && a.skip[pair]) return;                 // block-uniform (frozen pair): kabsch_final_kernel writes the identity
-  const int m = a.m;
   double* part = a.part + (int64_t)pair * nch * 16;
-  const int ld = a.ref_ld ? a.ref_ld : 3;
-  const float* src = a.src + pair * a.src_stride;
-  const float* ref = a.ref + pair * a.ref_stride;
-  const int32_t* idx = a.idx ? a.idx + (int64_t)pair * m : nullptr;
-  const float* wl = a.w + (int64_t)pair * m;
-  auto weight = [&](int i) -> float {
-    const float x = wl[i];
-    return a.sigmoid ? 1.f / (1.f + expf(-x)) : x;
-  };
-  auto target = [&](int i, float& x, float& y, float& z) {
-    const int64_t j = idx ? idx[i] : i;
-    x = ref[j * ld]; y = ref[j * ld + 1]; z = ref[j * ld + 2];
-  };
-  const int i1 = min(m, (ch + 1) * CHUNK);
+  const PairView p(a, pair);
+  const int first = ch * CHUNK, last = min(a.m, first + CHUNK);
   float den = 0.f, cs[3] = {0.f, 0.f, 0.f}, ct[3] = {0.f, 0.f, 0.f};
   if (PHASE >= 1) {
-    double S = 0.0;
-    for (int c = 0; c < nch; ++c) S += part[c * 16];
-    den = (float)S + 1e-16f;                          // model.py:35 (fp32 sum + _EPS)
+    double S[1] = {0.0};
+    sum_chunks(part, nch, 0, S);
+    den = weight_den(S[0]);
   }
   if (PHASE >= 2) {
     double v[6] = {0, 0, 0, 0, 0, 0};
-    for (int c = 0; c < nch; ++c)
-#pragma unroll
-      for (int k = 0; k < 6; ++k) v[k] += part[c * 16 + 1 + k];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { cs[k] = (float)v[k]; ct[k] = (float)v[3 + k]; }
+    sum_chunks(part, nch, 1, v);
+    centroids(v, cs, ct);
   }
   if (PHASE == 0) {
     double v1[1] = {0.0};
-    DSIR_KABSCH_UNROLL
-    for (int i = ch * CHUNK + threadIdx.x; i < i1; i += NTHR) v1[0] += (double)fabsf(weight(i));
-    block_sum<1>(v1, sh);
+    DSIR_KABSCH_FOR_POINTS(i, first, last) stream_abs_weight(p, i, v1);
+    block_sum<NWAVE>(v1, sh);
     if (threadIdx.x == 0) part[ch * 16] = v1[0];
   } else if (PHASE == 1) {
     double v6[6] = {0, 0, 0, 0, 0, 0};
-    DSIR_KABSCH_UNROLL
-    for (int i = ch * CHUNK + threadIdx.x; i < i1; i += NTHR) {
-      const float wn = weight(i) / den;
-      float tx, ty, tz;
-      target(i, tx, ty, tz);
-      v6[0] += (double)__fmul_rn(src[(int64_t)i * 3], wn);
-      v6[1] += (double)__fmul_rn(src[(int64_t)i * 3 + 1], wn);
-      v6[2] += (double)__fmul_rn(src[(int64_t)i * 3 + 2], wn);
-      v6[3] += (double)__fmul_rn(tx, wn);
-      v6[4] += (double)__fmul_rn(ty, wn);
-      v6[5] += (double)__fmul_rn(tz, wn);
-    }
-    block_sum<6>(v6, sh);
+    DSIR_KABSCH_FOR_POINTS(i, first, last) stream_centroid_terms(p, i, den, v6);
+    block_sum<NWAVE>(v6, sh);
     if (threadIdx.x < 6) part[ch * 16 + 1 + threadIdx.x] = v6[threadIdx.x];
   } else {
     double v9[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    DSIR_KABSCH_UNROLL
-    for (int i = ch * CHUNK + threadIdx.x; i < i1; i += NTHR) {
-      const float wn = weight(i) / den;
-      float t[3];
-      target(i, t[0], t[1], t[2]);
-      float sc[3], tw[3];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        sc[k] = __fsub_rn(src[(int64_t)i * 3 + k], cs[k]);
-        tw[k] = __fmul_rn(__fsub_rn(t[k], ct[k]), wn);
-      }
-#pragma unroll
-      for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) v9[r * 3 + c] += (double)__fmul_rn(sc[r], tw[c]);
-    }
-    block_sum<9>(v9, sh);
+    DSIR_KABSCH_FOR_POINTS(i, first, last) stream_covariance_terms(p, i, den, cs, ct, v9);
+    block_sum<NWAVE>(v9, sh);
     if (threadIdx.x < 9) part[ch * 16 + 7 + threadIdx.x] = v9[threadIdx.x];
   }
 }
@@ -409,52 +358,24 @@ __global__ __launch_bounds__(NTHR) void kabsch_part_kernel(const KabschArgs a, i
 __global__ __launch_bounds__(64) void kabsch_final_kernel(const KabschArgs a, int nch) {
   const int pair = blockIdx.x * 64 + threadIdx.x;
   if (pair >= a.pairs) return;
-  if (a.skip && a.skip[pair]) {
-    const float I[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-    for (int k = 0; k < 12; ++k) a.T[(int64_t)pair * 12 + k] = I[k];
-    if (a.T_cum) {
-      float* out = a.T_cum + pair * a.T_stride;
-      const float* P = a.T_prev ? a.T_prev + pair * a.T_stride : I;
-      for (int k = 0; k < 12; ++k) out[k] = P[k];
-    }
-    return;
-  }
+  if (a.skip && a.skip[pair]) { kabsch_frozen(a, pair); return; }
   const double* part = a.part + (int64_t)pair * nch * 16;
   double v6[6] = {0, 0, 0, 0, 0, 0}, v9[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-  for (int c = 0; c < nch; ++c) {
-    for (int k = 0; k < 6; ++k) v6[k] += part[c * 16 + 1 + k];
-    for (int k = 0; k < 9; ++k) v9[k] += part[c * 16 + 7 + k];
-  }
-  const float cs[3] = {(float)v6[0], (float)v6[1], (float)v6[2]};
-  const float ct[3] = {(float)v6[3], (float)v6[4], (float)v6[5]};
-  float sT[12];
+  sum_chunks(part, nch, 1, v6);
+  sum_chunks(part, nch, 7, v9);
+  float cs[3], ct[3], sT[12];
+  centroids(v6, cs, ct);
   kabsch_solve(a, pair, v9, cs, ct, sT);
 }
 
-// apply: p' = p R^T + t (se3_torch.py:60-77); gather the matched ref points; one thread per point
+// the apply step of the chunked path, one thread per point
 __global__ __launch_bounds__(256) void kabsch_apply_kernel(const KabschArgs a) {
   const int pair = blockIdx.y;
   if (a.skip && a.skip[pair]) return;
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= a.m) return;
-  const int ld = a.ref_ld ? a.ref_ld : 3;
-  const float* src = a.src + pair * a.src_stride;
-  if (a.matched_out) {
-    const float* ref = a.ref + pair * a.ref_stride;
-    const int64_t j = a.idx ? a.idx[(int64_t)pair * a.m + i] : i;
-    float* mo = a.matched_out + ((int64_t)pair * a.m + i) * 3;
-    mo[0] = ref[j * ld]; mo[1] = ref[j * ld + 1]; mo[2] = ref[j * ld + 2];
-  }
-  if (a.src_out) {
-    const float* T = a.T + (int64_t)pair * 12;
-    float* so = a.src_out + pair * a.src_out_stride;
-    const float x = src[(int64_t)i * 3], y = src[(int64_t)i * 3 + 1], z = src[(int64_t)i * 3 + 2];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-      const float d = fmaf(z, T[r * 4 + 2], fmaf(y, T[r * 4 + 1], __fmul_rn(x, T[r * 4 + 0])));
-      so[(int64_t)i * 3 + r] = __fadd_rn(d, T[r * 4 + 3]);
-    }
-  }
+  stream_apply(PairView(a, pair), a.src_out ? a.src_out + pair * a.src_out_stride : nullptr,
+               a.matched_out ? a.matched_out + (int64_t)pair * a.m * 3 : nullptr, i, a.T + (int64_t)pair * 12);
 }
 
 }  // namespace

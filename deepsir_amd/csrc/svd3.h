@@ -75,5 +75,15 @@ __device__ __forceinline__ double det3(const double M[3][3]) {
          M[0][2] * (M[1][0] * M[2][1] - M[1][1] * M[2][0]);
 }
 
+// The Procrustes rotation of H = U S V^T: R = V diag(1, 1, d) U^T with d = sign(det(V U^T)) (model.py:44-53); returns d
+__device__ inline double procrustes_rotation(const double U[3][3], const double V[3][3], double R[3][3]) {
+  double Rp[3][3];
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) Rp[r][c] = V[r][0] * U[c][0] + V[r][1] * U[c][1] + V[r][2] * U[c][2];
+  const double d = det3(Rp) > 0 ? 1.0 : -1.0;
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) R[r][c] = V[r][0] * U[c][0] + V[r][1] * U[c][1] + d * V[r][2] * U[c][2];
+  return d;
+}
 
 }  // namespace dsir

@@ -299,6 +299,42 @@ def test_kabsch_chunked_reduction_on_large_clouds(m):
     assert_pose_close(T_chunked.cpu().numpy(), ref, 5e-6, 5e-6, f"chunked vs oracle, m = {m}")
 
 
+def test_kabsch_kernels_agree_at_their_size_boundaries(tmp_path):
+    """The pose solve has three one-workgroup forms - kabsch_reg_kernel<5> up to 5 x 1024 points, kabsch_reg_kernel<8> up to
+    8 x 1024, kabsch_kernel beyond - that share their per-point functions and per-thread order (csrc/kabsch.hip): at
+    m in {1, 2, 63, 1024, 1025, 5120, 5121, 8192, 8193}, 3 pairs (one with a third of its weights zero, one with a NaN coordinate:
+    identity + invalid bit 0), T and invalid equal, bit for bit, those of a process that runs the streaming kernel for every size
+    (DSIR_KABSCH_STREAM=1, read once per process).  The chunked solve (threshold moved to 4096: 2 and 3 chunks, the last one
+    ragged) adds its fp64 partial sums in another order: within 1e-6 rad / 1e-6 m of the one-workgroup solve, as
+    test_kabsch_chunked_reduction_on_large_clouds."""
+    import importlib.util, subprocess, sys
+    from deepsir_amd.arch import NetConfig
+    from deepsir_amd.weights import generate_state_dict
+    tool = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools", "pose_dump.py")
+    spec = importlib.util.spec_from_file_location("pose_dump", tool)
+    pd = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(pd)
+    cfg = NetConfig(feat_len=3)
+    eng = engine_for(cfg, generate_state_dict(cfg, 0), "w0kab", max_points=65536, max_pairs=2)
+    here = pd.kabsch_outputs(eng)
+    out = str(tmp_path / "stream.npz")
+    r = subprocess.run([sys.executable, tool, out, "kabsch"], env=dict(os.environ, DSIR_TUNING="1", DSIR_KABSCH_STREAM="1"),
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    stream = np.load(out)
+    for m in pd.KABSCH_SIZES:
+        T, bad = here[f"kabsch_m{m}_T"], here[f"kabsch_m{m}_invalid"]
+        assert np.array_equal(T.view(np.uint32), stream[f"kabsch_m{m}_T"].view(np.uint32)), f"T differs at m = {m}"
+        assert np.array_equal(bad, stream[f"kabsch_m{m}_invalid"]), f"invalid differs at m = {m}"
+        assert bad.tolist() == [0, 0, 1], (m, bad)
+        assert np.array_equal(T[2], np.eye(4, dtype=np.float32)[:3]), m
+        assert np.isfinite(T).all(), m
+    for m in (4097, 8193):
+        T_single, bad = eng.kabsch(*map(cu, pd.kabsch_case(m)))
+        assert bad.cpu().tolist() == [0, 0, 1] and here[f"chunked_m{m}_invalid"].tolist() == [0, 0, 1], m
+        assert_pose_close(here[f"chunked_m{m}_T"], T_single.cpu().numpy(), 1e-6, 1e-6, f"chunked vs one workgroup, m = {m}")
+
+
 # --------------------------------------------------------------------------- whole path
 @pytest.mark.parametrize("name", ["stage_n1024_s1", "stage_n1024_s2_sep", "e2e_n2048_s3", "e2e_n2048_s4_sep",
                                   "e2e_n2048_s6_f4", "e2e_n5000_s5"])
