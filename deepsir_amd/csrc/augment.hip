@@ -19,6 +19,7 @@
 #include <stdint.h>
 
 #include "dsir_train.h"
+#include "device_utils.h"
 
 namespace dsir {
 namespace {
@@ -36,13 +37,6 @@ struct AugParams {
   int64_t rmode, scaled, pad[3];
 };
 static_assert(sizeof(AugParams) == 24 * 8, "AugParams is 24 slots");
-
-__device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
-  uint64_t z = x + 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
 
 inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 inline int grid1(int64_t total) { const int64_t g = (total + 255) / 256; return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g)); }

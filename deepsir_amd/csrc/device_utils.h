@@ -51,6 +51,14 @@ __device__ __forceinline__ int32_t packed_index(unsigned long long p) {
   return p == ~0ull ? 0 : (int32_t)(p & 0xffffffffull);
 }
 
+// splitmix64 (Vigna): the one generator behind every keyed draw of the engine (preprocess.hip, augment.hip, ransac.hip)
+__device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
+  uint64_t z = x + 0x9E3779B97F4A7C15ull;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);

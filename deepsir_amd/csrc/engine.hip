@@ -2013,6 +2013,54 @@ int dsir_icp_refine(dsir_ctx* c, const float* points_src, const float* points_re
   return post(c);
 }
 
+int dsir_ransac_correspondence(dsir_ctx* c, const float* points_src, const float* points_ref, int pairs, int J, int K, int stride,
+                               const int32_t* corr, const int32_t* counts, int M, float max_dist, int ransac_n, float edge_sim,
+                               int hypotheses, int refine_iters, uint64_t seed, const float* T_init, float* T_out, double* stats,
+                               int32_t* invalid, const dsir_ransac_diag* diag) {
+  if (!c) return 1;
+  if (!points_src || !points_ref || !corr || !T_out || !stats || !invalid || pairs < 1 || J < 1 || K < 1 || M < 1 || stride < 3 ||
+      !(max_dist > 0.f) || !std::isfinite(max_dist) || !std::isfinite(edge_sim))
+    return fail(c, "dsir_ransac_correspondence: bad arguments");
+  if (ransac_n != 3 && ransac_n != 4) return fail(c, "dsir_ransac_correspondence: ransac_n must be 3 or 4 (got %d)", ransac_n);
+  if (hypotheses < 1 || hypotheses > DSIR_RANSAC_MAX_HYPOTHESES)
+    return fail(c, "dsir_ransac_correspondence: hypotheses=%d outside [1,%d]", hypotheses, DSIR_RANSAC_MAX_HYPOTHESES);
+  if (refine_iters < 0 || refine_iters > DSIR_RANSAC_MAX_REFINE)
+    return fail(c, "dsir_ransac_correspondence: refine_iters=%d outside [0,%d]", refine_iters, DSIR_RANSAC_MAX_REFINE);
+  if (M > c->cfg.max_points || J > c->cfg.max_points || K > c->cfg.max_points)
+    return fail(c, "dsir_ransac_correspondence: M=%d, J=%d or K=%d beyond max_points=%d", M, J, K, c->cfg.max_points);
+  HIP_OK(c, hipSetDevice(c->device));
+  c->ws.top = 0; c->ws.overflow = false;
+  void* scratch = c->ws.raw(ransac_scratch_bytes(pairs, M, hypotheses, refine_iters));
+  if (c->ws.overflow) return fail(c, "workspace too small for dsir_ransac_correspondence (pairs x (M x 28 + hypotheses x 56) bytes: raise max_points / max_pairs)");
+  RansacArgs a{};
+  a.src = points_src; a.ref = points_ref; a.pairs = pairs; a.J = J; a.K = K; a.stride = stride; a.corr = corr; a.counts = counts;
+  a.M = M; a.max_dist = max_dist; a.n = ransac_n; a.edge_sim = edge_sim; a.hypotheses = hypotheses; a.refine_iters = refine_iters;
+  a.seed = seed; a.T_init = T_init; a.T_out = T_out; a.stats = stats; a.invalid = invalid;
+  if (diag) { a.diag_sample = diag->hyp_sample; a.diag_T = diag->hyp_T; a.diag_valid = diag->hyp_valid; a.diag_count = diag->hyp_count; }
+  launch_ransac(a, scratch, c->stream);
+  return post(c);
+}
+
+int dsir_feature_correspondences(dsir_ctx* c, const float* desc_src, const float* desc_ref, int pairs, int J, int K, int mutual,
+                                 int32_t* corr, int32_t* counts) {
+  if (!c) return 1;
+  if (!desc_src || !desc_ref || !corr || !counts || pairs < 1 || J < 1 || K < 1)
+    return fail(c, "dsir_feature_correspondences: bad arguments");
+  if (J > c->cfg.max_points || K > c->cfg.max_points)
+    return fail(c, "dsir_feature_correspondences: J=%d or K=%d beyond max_points=%d", J, K, c->cfg.max_points);
+  HIP_OK(c, hipSetDevice(c->device));
+  c->ws.top = 0; c->ws.overflow = false;
+  int32_t* ab = c->ws.get<int32_t>((size_t)pairs * J);
+  int32_t* ba = c->ws.get<int32_t>((size_t)pairs * K);
+  void* s_ab = c->ws.raw(nn_match_scratch_bytes(pairs, J, K));
+  void* s_ba = c->ws.raw(nn_match_scratch_bytes(pairs, K, J));
+  if (c->ws.overflow) return fail(c, "workspace too small for dsir_feature_correspondences (raise max_points / max_pairs)");
+  launch_nn_match_ws(desc_src, desc_ref, pairs, J, K, ab, s_ab, c->stream, nullptr, nullptr);
+  if (mutual) launch_nn_match_ws(desc_ref, desc_src, pairs, K, J, ba, s_ba, c->stream, nullptr, nullptr);
+  launch_corr_compact(ab, ba, pairs, J, K, mutual ? 1 : 0, corr, counts, c->stream);
+  return post(c);
+}
+
 int dsir_pose_finetune(dsir_ctx* c, const float* xyz_src, const float* xyz_ref, const float* weights, int weights_are_logits,
                        int pairs, int m, const float* T_init, float quantization_size, int max_iter, float break_threshold_ratio,
                        int max_break_count, float* T_out, double* stats) {

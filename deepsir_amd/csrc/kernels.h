@@ -475,6 +475,25 @@ void launch_icp_refine(const float* src, const float* ref, int pairs, int J, int
                        int max_iter, float rel_fitness, float rel_rmse, const float* T_init, float* T_out,
                        double* stats_out, void* scratch, hipStream_t st);
 
+// ransac.hip — RANSAC pose from correspondences (network/DGR.py:7-36, :249-306 / open3d registration_ransac_*; the rule is stated in
+// the file's header), all pairs at once; and the mutual-nearest-neighbour list of dsir_feature_correspondences
+struct RansacArgs {
+  const float* src; const float* ref;   // [pairs][J][stride], [pairs][K][stride]
+  int pairs, J, K, stride;
+  const int32_t* corr;                  // [pairs][M][2]
+  const int32_t* counts;                // [pairs] or nullptr
+  int M;
+  float max_dist; int n; float edge_sim; int hypotheses, refine_iters; uint64_t seed;
+  const float* T_init;                  // [pairs][3][4] or nullptr (identity)
+  float* T_out; double* stats; int32_t* invalid;
+  int32_t* diag_sample; float* diag_T; int32_t* diag_valid; int32_t* diag_count;   // optional
+};
+size_t ransac_scratch_bytes(int pairs, int M, int H, int refine_iters);
+void launch_ransac(const RansacArgs& a, void* scratch, hipStream_t st);
+// ab [pairs][J] (src -> ref arg-min), ba [pairs][K] (ref -> src; read with mutual != 0 only) -> corr [pairs][J][2], counts [pairs]
+void launch_corr_compact(const int32_t* ab, const int32_t* ba, int pairs, int J, int K, int mutual, int32_t* corr, int32_t* counts,
+                         hipStream_t st);
+
 // finetune.hip — Adam fine-tune of the pose on matched points (test.py:159-207), one workgroup per pair
 void launch_pose_finetune(const float* src, const float* ref, const float* w, int sigmoid, int pairs, int m, const float* T_init,
                           float quant, int max_iter, float break_ratio, int max_break, float* T_out, double* stats,

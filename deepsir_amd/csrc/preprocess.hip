@@ -23,13 +23,6 @@ namespace {
 
 constexpr uint64_t kInvalidKey = ~0ull;
 
-__device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
-  uint64_t z = x + 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
 __device__ __forceinline__ bool crop_ok(const float* p, const float4 crop, bool use_crop) {
   if (!use_crop) return true;
   const float r2 = __fadd_rn(__fadd_rn(__fmul_rn(p[0], p[0]), __fmul_rn(p[1], p[1])), __fmul_rn(p[2], p[2]));

@@ -467,6 +467,65 @@ class Engine:
         self.sync()
         return T, stats
 
+    RANSAC_CHUNK = 256                 # DSIR_RANSAC_CHUNK: correspondences a scoring workgroup stages per step
+    RANSAC_MAX_HYPOTHESES = 1 << 20    # DSIR_RANSAC_MAX_HYPOTHESES
+
+    def ransac_correspondence(self, points_src, points_ref, corr, max_dist: float, counts=None, ransac_n: int = 3,
+                              edge_sim: float = 0.9, hypotheses: int = 8192, refine_iters: int = 2, seed: int = 0, T_init=None,
+                              diag: bool = False):
+        """open3d registration_ransac_based_on_correspondence counterpart for P pairs (reference network/DGR.py:26-36, :249-306;
+        parity unpinned, the rule is stated in csrc/ransac.hip and restated in deepsir_amd/ransac.py).
+        points_* [P,N,>=3] CUDA fp32, corr [P,M,2] i32 (src index, ref index), counts [P] i32 or None, T_init [P,3,4] or None
+        -> (T [P,3,4], stats [P,5] f64: fitness, inlier_rmse, winning hypothesis or -1, valid hypotheses, inliers; invalid [P] i32)
+        and, with diag=True, a dict of hyp_sample [P,H,4], hyp_T [P,H,3,4], hyp_valid [P,H], hyp_count [P,H]."""
+        points_src, points_ref = _chk(points_src, torch.float32, "points_src"), _chk(points_ref, torch.float32, "points_ref")
+        corr = _chk(corr, torch.int32, "corr")
+        P, J, stride = points_src.shape
+        K, M = points_ref.shape[1], corr.shape[1]
+        if points_ref.shape[0] != P or points_ref.shape[2] != stride or tuple(corr.shape) != (P, M, 2):
+            raise EngineError("ransac_correspondence: points_* must be [P,N,stride] and corr [P,M,2]")
+        if counts is not None:
+            counts = _chk(counts, torch.int32, "counts")
+            if tuple(counts.shape) != (P,):
+                raise EngineError("ransac_correspondence: counts must be [P]")
+        if T_init is not None:
+            T_init = _chk(T_init, torch.float32, "T_init")
+            if tuple(T_init.shape) != (P, 3, 4):
+                raise EngineError("ransac_correspondence: T_init must be [P,3,4]")
+        T = self._empty((P, 3, 4))
+        stats = self._empty((P, 5), torch.float64)
+        invalid = self._empty((P,), torch.int32)
+        d, dref = None, None
+        if diag:
+            Hn = max(int(hypotheses), 1)
+            d = {"hyp_sample": self._empty((P, Hn, 4), torch.int32), "hyp_T": self._empty((P, Hn, 3, 4)),
+                 "hyp_valid": self._empty((P, Hn), torch.int32), "hyp_count": self._empty((P, Hn), torch.int32)}
+            dref = C.byref(_lib.dsir_ransac_diag(*[_ptr(d[k]) for k in ("hyp_sample", "hyp_T", "hyp_valid", "hyp_count")]))
+        self._pre()
+        self._call(self.lib.dsir_ransac_correspondence(self.h, _ptr(points_src), _ptr(points_ref), P, J, K, stride, _ptr(corr),
+                                                       _ptr(counts), M, float(max_dist), int(ransac_n), float(edge_sim),
+                                                       int(hypotheses), int(refine_iters), int(seed) & ((1 << 64) - 1),
+                                                       _ptr(T_init), _ptr(T), _ptr(stats), _ptr(invalid), dref))
+        self.sync()
+        return (T, stats, invalid, d) if diag else (T, stats, invalid)
+
+    def feature_correspondences(self, desc_src, desc_ref, mutual: bool = True):
+        """The correspondence set of open3d's registration_ransac_based_on_feature_matching (reference network/DGR.py:7-24),
+        made explicit: exact descriptor arg-min src -> ref (nn_match), kept where the ref -> src arg-min points back (mutual),
+        in ascending src index.  desc_* [P,N,64] -> (corr [P,J,2] i32 with -1 beyond counts[p], counts [P] i32)."""
+        desc_src, desc_ref = _chk(desc_src, torch.float32, "desc_src"), _chk(desc_ref, torch.float32, "desc_ref")
+        P, J, c = desc_src.shape
+        K = desc_ref.shape[1]
+        if c != 64 or desc_ref.shape[0] != P or desc_ref.shape[2] != 64:
+            raise EngineError("feature_correspondences: descriptors must be [P,N,64]")
+        corr = self._empty((P, J, 2), torch.int32)
+        counts = self._empty((P,), torch.int32)
+        self._pre()
+        self._call(self.lib.dsir_feature_correspondences(self.h, _ptr(desc_src), _ptr(desc_ref), P, J, K, 1 if mutual else 0,
+                                                         _ptr(corr), _ptr(counts)))
+        self.sync()
+        return corr, counts
+
     def pose_finetune(self, xyz_src, xyz_ref, T_init, weights=None, weights_are_logits: bool = False,
                       quantization_size: float = 1.0, max_iter: int = 1000, break_threshold_ratio: float = 1e-4,
                       max_break_count: int = 20):

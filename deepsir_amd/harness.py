@@ -25,12 +25,15 @@ from .metrics import THRESHOLDS, rte_rre
 @torch.no_grad()
 def inference_align(pairs: Sequence[Dict[str, np.ndarray]], model, num_reg_iter: int = 5, dataset_type: str = "3DMatch",
                     batch: int = 1, device: Optional[torch.device] = None, dist=None, pose_opt: Optional[str] = None,
-                    voxel_size: float = 0.3, in_flight: int = 1):
+                    voxel_size: float = 0.3, in_flight: int = 1, safeguard_wsum: Optional[float] = None,
+                    ransac_hypotheses: int = 80000, ransac_seed: int = 0):
     """pairs: sequence of dicts with ``points_src/points_ref [1,N,C]``, ``transform_gt [1,3,4]`` and optionally the
     pyramid tensors and ``others`` (as the reference's collate, data_base.py:196-219).
     ``in_flight`` > 1: the reference's one-pair-per-call loop fed AHEAD - the pairs go one by one to a
     ``deepsir_amd.serve.PairServer`` that keeps that many requests outstanding (same results bit for bit; the per-pair
     time is then the shard's wall time divided by its size).
+    ``pose_opt='ransac'``: DGR's safeguard (network/DGR.py:249-306) over the last iteration's correspondences, see below;
+    ``safeguard_wsum``: only pairs whose summed sigmoid inlier weight is below it take the RANSAC pose (DGR.py:273-304).
     Returns (pred_transforms_all [n_pairs, n_iter+1, 3, 4], stats [n_pairs, 5]) gathered over ranks."""
     device = device or torch.device("cuda", torch.cuda.current_device())
     rte_t, rre_t = THRESHOLDS[dataset_type]
@@ -90,10 +93,24 @@ def inference_align(pairs: Sequence[Dict[str, np.ndarray]], model, num_reg_iter:
                                                    transforms[-1].contiguous(), weights=endpoints["perm_matrices"][-1],
                                                    weights_are_logits=True, quantization_size=2.0 * voxel_size)
             transforms.append(T_opt)
+        elif pose_opt == "ransac":
+            # DGR.safeguard_registration (network/DGR.py:249-306): RANSAC over the last iteration's correspondences (row i of pt_src
+            # with row i of pt_ref_new), threshold 2 x voxel size, DGR's 80 000 hypotheses by default; with safeguard_wsum only the
+            # pairs whose inlier network assigned less total weight than that take it, the others keep the network's pose
+            xs, xr = endpoints["pt_src"].float().contiguous(), endpoints["pt_ref_new"].float().contiguous()
+            m = xs.shape[1]
+            corr = torch.arange(m, dtype=torch.int32, device=xs.device)[None, :, None].expand(xs.shape[0], m, 2).contiguous()
+            T_net = transforms[-1].contiguous()
+            T_opt, _, _ = _aux_engine(model, data).ransac_correspondence(xs, xr, corr, 2.0 * voxel_size, hypotheses=ransac_hypotheses,
+                                                                         seed=ransac_seed, T_init=T_net)
+            if safeguard_wsum is not None:
+                wsum = torch.sigmoid(endpoints["perm_matrices"][-1].float()).reshape(xs.shape[0], -1).sum(1)
+                T_opt = torch.where((wsum < safeguard_wsum)[:, None, None], T_opt, T_net)
+            transforms.append(T_opt)
         elif pose_opt is None:
             transforms.append(transforms[-1].detach())        # pose_optimization == identity (test.py:215-216, :406-408)
         else:
-            raise ValueError("pose_opt must be None, 'icp' or 'tune'")
+            raise ValueError("pose_opt must be None, 'icp', 'tune' or 'ransac'")
         T = torch.stack(transforms, dim=1).cpu().numpy()      # [B, n_iter+1, 3, 4]
         preds.append(T)
         gt = data["transform_gt"].cpu().numpy()
@@ -282,6 +299,43 @@ def inference_feat(pairs: Sequence[Dict[str, np.ndarray]], model, batch: int = 1
                 rec[f"score_{s}"] = ep[f"score_{s}"][j].cpu().numpy()
             out.append(rec)
     return out, total
+
+
+@torch.no_grad()
+def register_feat(pairs: Sequence[Dict[str, np.ndarray]], model, voxel_size: float = 0.3, hypotheses: int = 8192, mutual: bool = True,
+                  num_reg: int = 1, dataset_type: str = "3DMatch", batch: int = 1, device: Optional[torch.device] = None,
+                  ransac_n: int = 3, edge_sim: float = 0.9, refine_iters: int = 2, seed: int = 0):
+    """The 'feat' pipeline as a registration (what the reference reaches through open3d's
+    registration_ransac_based_on_feature_matching, network/DGR.py:7-24, test.py:259-263): forward_pair -> key points and
+    descriptors -> (mutual) nearest-neighbour correspondences -> RANSAC pose (threshold 2 x voxel size), all on the device.
+    Returns (pred_transforms [n_pairs, num_reg, 3, 4] - the one pose repeated ``num_reg`` times, so that the result has
+    ``inference_align``'s layout and ``evaluate_align`` works on it -, stats [n_pairs, 5] rows ``[succ, rte, rre, time, seq]``)."""
+    device = device or torch.device("cuda", torch.cuda.current_device())
+    rte_t, rre_t = THRESHOLDS[dataset_type]
+    preds, stats = [], np.zeros((len(pairs), 5))
+    for ids, data in _pair_batches(pairs, batch, device):
+        torch.cuda.synchronize(device)
+        t0 = time.time()
+        _, ep = model(data)
+        eng = _aux_engine(model, data)
+        xs, xr = ep["pt_src"].permute(0, 2, 1).contiguous(), ep["pt_ref"].permute(0, 2, 1).contiguous()
+        corr, counts = eng.feature_correspondences(ep["feat_src"].permute(0, 2, 1).contiguous(), ep["feat_ref"].permute(0, 2, 1).contiguous(),
+                                                   mutual=mutual)
+        T, _, _ = eng.ransac_correspondence(xs, xr, corr, 2.0 * voxel_size, counts=counts, ransac_n=ransac_n, edge_sim=edge_sim,
+                                            hypotheses=hypotheses, refine_iters=refine_iters, seed=seed)
+        torch.cuda.synchronize(device)
+        dt = (time.time() - t0) / len(ids)
+        T = T.cpu().numpy()
+        preds.append(np.repeat(T[:, None], num_reg, 1))
+        gt = data["transform_gt"].cpu().numpy() if "transform_gt" in data else None
+        for j, i in enumerate(ids):
+            if gt is not None:
+                stats[i, :3] = rte_rre(T[j], gt[j], rte_t, rre_t)
+            stats[i, 3] = dt
+            others = pairs[i].get("others")
+            stats[i, 4] = _seq_id(others[0]["seq"]) if others else -1
+    pred = np.concatenate(preds, 0) if preds else np.zeros((0, num_reg, 3, 4), np.float32)
+    return pred, stats
 
 
 @torch.no_grad()

@@ -16,7 +16,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from deepsir_amd import data as D  # noqa: E402
 from deepsir_amd.arch import NetConfig  # noqa: E402
-from deepsir_amd.harness import evaluate_align, inference_align, summarize  # noqa: E402
+from deepsir_amd.harness import evaluate_align, inference_align, register_feat, summarize  # noqa: E402
 from deepsir_amd.model import Network  # noqa: E402
 from deepsir_amd.weights import generate_state_dict, to_torch_state_dict  # noqa: E402
 
@@ -31,11 +31,20 @@ def main():
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--limit", type=int, default=0)
-    ap.add_argument("--pose-opt", choices=["none", "icp"], default="none")
+    ap.add_argument("--pose-opt", choices=["none", "icp", "tune", "ransac"], default="none")
+    ap.add_argument("--pipeline", choices=["align", "feat"], default="align")
+    ap.add_argument("--ransac", action="store_true", help="with --pipeline feat: descriptors -> mutual nearest neighbours -> RANSAC pose")
+    ap.add_argument("--num-sub", type=int, default=1024, help="key points per cloud of the feat pipeline")
+    ap.add_argument("--hypotheses", type=int, default=8192)
     a = ap.parse_args()
     kitti = a.dataset == "KITTI"
     cfg = NetConfig(feat_len=4 if kitti else 3)
-    args = argparse.Namespace(pipeline="align", num_sub=-1, num_knn=16, out_feat_dim=64, clip_weight_thresh=0.0,
+    if a.pipeline == "feat" and not a.ransac:
+        ap.error("--pipeline feat evaluates as a registration only with --ransac")
+    feat = a.pipeline == "feat"
+    if feat:
+        cfg = NetConfig(feat_len=cfg.feat_len, pipeline="feat", num_sub=a.num_sub)
+    args = argparse.Namespace(pipeline=a.pipeline, num_sub=a.num_sub if feat else -1, num_knn=16, out_feat_dim=64, clip_weight_thresh=0.0,
                               feat_len=cfg.feat_len, d_out=[16, 64, 128, 256], num_points=a.num_points,
                               sub_sampling_ratio=[4, 4, 4, 4], use_ppf=False)
     model = Network(args)
@@ -48,8 +57,11 @@ def main():
           else D.ThreeDMatchTest(a.root, eng, voxel_size=voxel, num_points=a.num_points))
     n = min(len(ds), a.limit) if a.limit else len(ds)
     pairs = [D.as_batch(ds[i]) for i in range(n)]
-    pred, stats = inference_align(pairs, model, a.iters, a.dataset, batch=a.batch,
-                                  pose_opt=None if a.pose_opt == "none" else "icp", voxel_size=voxel)
+    if feat:
+        pred, stats = register_feat(pairs, model, voxel_size=voxel, hypotheses=a.hypotheses, dataset_type=a.dataset, batch=a.batch)
+    else:
+        pred, stats = inference_align(pairs, model, a.iters, a.dataset, batch=a.batch,
+                                      pose_opt=None if a.pose_opt == "none" else a.pose_opt, voxel_size=voxel)
     print({k: round(float(v), 4) for k, v in summarize(stats).items()})
     _, summary = evaluate_align(pred, pairs, eng, a.dataset)
     print({k: round(float(v), 5) for k, v in summary.items()})

@@ -278,6 +278,44 @@ int dsir_pose_finetune(dsir_ctx* ctx, const float* xyz_src, const float* xyz_ref
                        int pairs, int m, const float* T_init, float quantization_size, int max_iter, float break_threshold_ratio,
                        int max_break_count, float* T_out, double* stats);
 
+/* Replaces open3d's registration_ransac_based_on_correspondence (network/DGR.py:26-36) as DGR.safeguard_registration uses it
+ * (network/DGR.py:249-306: 80 000 iterations, threshold 2 x voxel size), and - after dsir_feature_correspondences - the
+ * registration_ransac_based_on_feature_matching of network/DGR.py:7-24, for P pairs at once, entirely on device.
+ * open3d cannot be imported here: parity at this boundary is UNPINNED.  The engine owns the rule; it is stated once in the header of
+ * deepsir_amd/csrc/ransac.hip (and DESIGN.md section 8) and restated on the host in deepsir_amd/ransac.py, which the tests compare against.
+ * points_src [P][J][stride], points_ref [P][K][stride] (xyz first); corr [P][M][2] (src index, ref index); counts [P] (device) live
+ * rows per pair or NULL (all M).  Out-of-range indices of live rows are clamped and reported as bit 2 of invalid[p].
+ * max_dist: inlier threshold; ransac_n in {3, 4}; edge_sim: open3d's edge-length similarity (<= 0: no check; DGR uses 0.9);
+ * hypotheses in [1, DSIR_RANSAC_MAX_HYPOTHESES]; refine_iters in [0, DSIR_RANSAC_MAX_REFINE] refits on all inliers (default use: 2).
+ * seed: hypothesis h of pair p draws from splitmix64(splitmix64(seed ^ (p << 40)) ^ (h << 8) ^ k) alone, so the same hypothesis is the
+ * same sample for every P and H; pair p of a call is pair 0 of a call with seed ^ (p << 40).
+ * T_init [P][3][4] or NULL (identity): returned for a pair without a valid hypothesis (stats {0, 0, -1, 0, 0}; not an error).
+ * T_out [P][3][4]; stats [P][5] float64 {fitness = inliers / count, inlier RMSE, winning hypothesis or -1, valid hypotheses, inliers};
+ * invalid [P].  Non-finite coordinates are never inliers and never sampled.  Pairs are independent, bit for bit; two runs write the
+ * same bytes.  M, J, K <= max_points. */
+#define DSIR_RANSAC_CHUNK 256               /* correspondences a scoring workgroup stages per step (tests place M around it) */
+#define DSIR_RANSAC_MAX_HYPOTHESES (1 << 20)
+#define DSIR_RANSAC_MAX_REFINE 8
+/* test / measurement outputs of dsir_ransac_correspondence (all optional, device memory): the rows every hypothesis drew (-1 beyond
+ * ransac_n), its fitted transform (zeros when the sample was rejected before the fit), its verdict and its inlier count */
+typedef struct dsir_ransac_diag {
+  int32_t* hyp_sample;   /* [P][H][4] */
+  float* hyp_T;          /* [P][H][12] */
+  int32_t* hyp_valid;    /* [P][H] */
+  int32_t* hyp_count;    /* [P][H] */
+} dsir_ransac_diag;
+int dsir_ransac_correspondence(dsir_ctx* ctx, const float* points_src, const float* points_ref, int pairs, int J, int K,
+                               int stride, const int32_t* corr, const int32_t* counts, int M, float max_dist, int ransac_n,
+                               float edge_sim, int hypotheses, int refine_iters, uint64_t seed, const float* T_init, float* T_out,
+                               double* stats, int32_t* invalid, const dsir_ransac_diag* diag /* NULL in production */);
+
+/* The correspondence set open3d's registration_ransac_based_on_feature_matching (network/DGR.py:7-24; called at test.py:259-263)
+ * draws from, made explicit (parity unpinned, as above): the exact descriptor arg-min of dsir_nn_match src -> ref, with mutual != 0
+ * kept only where the ref -> src arg-min points back; survivors in ascending src index.  desc_src [P][J][64], desc_ref [P][K][64]
+ * -> corr [P][J][2] (rows beyond counts[p] are -1), counts [P].  Same bytes on every run. */
+int dsir_feature_correspondences(dsir_ctx* ctx, const float* desc_src, const float* desc_ref, int pairs, int J, int K, int mutual,
+                                 int32_t* corr, int32_t* counts);
+
 /* ---- the training slice (backward half) ------- */
 
 /* Replaces ScanAlignmentLoss.forward with reduction='mean' (network/loss.py:705-851; defaults of arguments.py:51-61:
