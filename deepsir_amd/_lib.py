@@ -33,6 +33,9 @@ class dsir_cfg(C.Structure):
     ]
 
 
+DSIR_FLAG_PPF = 1   # include/dsir.h: args.use_ppf
+
+
 class dsir_pair_batch(C.Structure):
     _fields_ = [
         ("pairs", C.c_int32), ("n_src", C.c_int32), ("n_ref", C.c_int32),
@@ -64,6 +67,7 @@ class dsir_cloud_out(C.Structure):
 # every symbol include/dsir.h declares: (restype, argtypes)
 SYMBOLS = {
     "dsir_create": (C.c_int, [C.c_int, C.POINTER(dsir_cfg), C.POINTER(C.c_void_p)]),
+    "dsir_create_ex": (C.c_int, [C.c_int, C.POINTER(dsir_cfg), C.c_int, C.POINTER(C.c_void_p)]),
     "dsir_destroy": (None, [C.c_void_p]),
     "dsir_last_error": (C.c_char_p, [C.c_void_p]),
     "dsir_stream": (C.c_void_p, [C.c_void_p]),
@@ -78,6 +82,9 @@ SYMBOLS = {
                                    C.c_void_p, C.c_void_p]),
     "dsir_randla_forward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dsir_ppf_pre": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
+    "dsir_estimate_normals": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int, c_float_p, C.c_void_p,
+                                        C.c_void_p]),
     "dsir_score": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                              C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "dsir_aggregate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
@@ -124,6 +131,8 @@ SYMBOLS = {
     "dsir_gn_contributions": (C.c_int, [C.POINTER(dsir_cfg), C.c_int]),
     "dsir_gn_contribution_limit": (C.c_int, []),
     "dsir_max_points_limit": (C.c_int, [C.POINTER(dsir_cfg)]),
+    "dsir_gn_contributions_ex": (C.c_int, [C.POINTER(dsir_cfg), C.c_int, C.c_int]),
+    "dsir_max_points_limit_ex": (C.c_int, [C.POINTER(dsir_cfg), C.c_int]),
     "dsir_screen_bounds": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dsir_screen_cap": (C.c_int, []),

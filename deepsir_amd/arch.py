@@ -109,10 +109,10 @@ def _mlp1d(prefix: str, channels: Sequence[int]) -> List[ParamSpec]:
 
 
 def randla_specs(prefix: str, feat_in: int, num_classes: int, cfg: NetConfig) -> List[ParamSpec]:
-    """RandLANet.py:233-285."""
+    """RandLANet.py:233-285; use_ppf (:251-254): mlp_pre reads feat_grouping's 10 channels and level 0 takes 12."""
     out: List[ParamSpec] = []
-    dim = 8
-    out += _mlp2d(prefix + ".mlp_pre", feat_in, dim)
+    dim = 12 if cfg.use_ppf else 8
+    out += _mlp2d(prefix + ".mlp_pre", 10 if cfg.use_ppf else feat_in, dim)
     for i, d in enumerate(cfg.d_out):
         p = f"{prefix}.dilated_res_blocks.{i}"
         out += _mlp2d(p + ".mlp1", dim, d // 2)

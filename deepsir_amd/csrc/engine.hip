@@ -50,6 +50,7 @@ struct BlockW { Mlp2dW mlp1, lfa1, lfa2, mlp2, skip; AttW att1, att2; int d_in =
                 const float *pair_W = nullptr, *pair_b = nullptr; };   // mlp1's rows followed by mlp_skip's (and the biases likewise): up_pair
 struct LinW { const float *W = nullptr, *b = nullptr; int cin = 0, cout = 0; };
 struct RandlaW { Mlp2dW pre; BlockW blk[4]; Mlp2dW mid; Mlp2dW dec[4]; const float* out_w = nullptr; int dec_out = 0; LinW fc[3]; int cin = 0, ncls = 0;
+                 bool ppf = false;   // DSIR_FLAG_PPF: mlp_pre is the point-pair-feature layer (ppf.hip), level 0 takes 12 channels
                  const void* head_wh[4] = {}; const void* head_wl[4] = {}; };   // fp16 split of mlp_out + fc_label (head_mlp_h.hip)
 struct NetW { RandlaW feat, inl; LinW mlp_feat[3], mlp_att[5], mlp_proj; };
 
@@ -99,6 +100,7 @@ struct Act {
 struct dsir_ctx {
   int device = 0;
   dsir_cfg cfg{};
+  int flags = 0;                       // DSIR_FLAG_* of dsir_create_ex
   hipStream_t stream = nullptr;        // where every launch of this context goes: own_stream, or a caller's (dsir_set_stream)
   hipStream_t own_stream = nullptr;
   std::string err;
@@ -217,7 +219,12 @@ void fill_pyramid_layout(const dsir_cfg& cfg, int clouds, int n, Pyramid& p) {
 // (Cin <= 64 and the relative-position layers: pw_stream.hip or - d / 2 = 8, 32 - lse_uv.hip; wider: pw_tile.hip, whose count also
 // bounds the generic pw_gemm.hip kernel's 64-row blocks).  The exactness proof of the statistics' atomics (device_utils.h) needs
 // this number <= kGnMaxContrib: dsir_create refuses a max_points beyond it.
-int gn_max_contributions(const dsir_cfg& g, int n) {
+// Under DSIR_FLAG_PPF the schedule gains the point-pair-feature layer (ppf.hip: one contribution per 64 points) and level 0's
+// mlp1 / mlp_skip take 12 input channels, which no tuned family serves: the general kernel's 64-row blocks (pw_gemm.hip).  Both
+// count n / 64 per statistic, half of lfa.mlp1's n / 32 at level 0 (16 n rows in units of 512), which stays the largest: the
+// bound on max_points is the same with and without the flag, and it is re-derived here, not assumed.
+int gn_max_contributions(const dsir_cfg& g, int n, int flags = 0) {
+  const bool ppf = (flags & DSIR_FLAG_PPF) != 0;
   int worst = 0;
   auto layer = [&](int M, int cin, int cout) {
     const int groups = cout >= 64 ? 8 : 4;
@@ -227,11 +234,13 @@ int gn_max_contributions(const dsir_cfg& g, int n) {
   int nl[DSIR_MAX_LEVELS + 1];
   level_sizes(g, n, nl);
   const int L = g.num_layers;
-  layer(nl[0], 6 > g.feat_len ? 6 : g.feat_len, 8);
-  int dim = 8;
+  if (ppf) { const int c = ppf_gn_contributions(nl[0]); if (c > worst) worst = c; }
+  else layer(nl[0], 6 > g.feat_len ? 6 : g.feat_len, 8);
+  int dim = ppf ? 12 : 8;
   for (int l = 0; l < L; ++l) {
     const int d = g.d_out[l], m = nl[l], mk = nl[l] * kKnn;
-    layer(m, dim, d / 2); layer(m, dim, 2 * d);                  // mlp1, mlp_skip
+    if (ppf && l == 0) { const int c = pw_gemm_gn_contributions(m); if (c > worst) worst = c; }   // Cin = 12: the general kernel
+    else { layer(m, dim, d / 2); layer(m, dim, 2 * d); }         // mlp1, mlp_skip
     if (d / 2 == 8 || d / 2 == 32) { const int c = lse_uv_gn_contributions(m, d / 2); if (c > worst) worst = c; }
     layer(mk, 10, d / 2);                                        // lfa.mlp1 (also when the tables are switched off)
     layer(mk, d / 2, d / 2);                                     // lfa.mlp2
@@ -287,8 +296,9 @@ void add_mlp1d(dsir_ctx* c, const std::string& pre, const std::vector<int>& ch) 
 }
 void add_randla(dsir_ctx* c, const std::string& pre, int cin, int ncls) {
   const dsir_cfg& g = c->cfg;
-  int dim = 8;
-  add_mlp2d(c, pre + ".mlp_pre", cin, dim);
+  const bool ppf = (c->flags & DSIR_FLAG_PPF) != 0;       // RandLANet.py:251-254: d_feat_in = 10, dim_temp = 12
+  int dim = ppf ? 12 : 8;
+  add_mlp2d(c, pre + ".mlp_pre", ppf ? 10 : cin, dim);
   for (int i = 0; i < g.num_layers; ++i) {
     const int d = g.d_out[i];
     const std::string p = pre + ".dilated_res_blocks." + std::to_string(i);
@@ -606,6 +616,25 @@ struct Sched {
     gemm(a);
     return y;
   }
+  // use_ppf: feat_grouping + mlp_pre + the mean over the neighbours (ppf.hip; RandLANet.py:324-332).  pts: the rows' xyz columns,
+  // nrm: their "normals" (optionally gathered: the inlier model's matched ref points, model.py:574-577), nb: level-0 neighbour rows.
+  // The result is a finished activation (normalised, activated, averaged): no lazy GroupNorm rides on it.
+  Act ppf_pre(const Mlp2dW& w, const Seg& pts, const Seg& nrm, const int32_t* nb, int64_t nb_cs, int n, float* out_buf = nullptr) {
+    Act y;
+    y.p = out_buf ? out_buf : c->ws.get<float>((size_t)clouds * n * 12);
+    y.C = 12; y.rows = n; y.act = 0;
+    PpfArgs a;
+    a.xyz = pts.x; a.xyz_cs = pts.cloud_stride; a.xyz_ld = pts.ld;
+    a.nrm = nrm.x; a.nrm_cs = nrm.cloud_stride; a.nrm_ld = nrm.ld; a.nrm_idx = nrm.idx; a.nrm_idx_cs = nrm.idx_cloud_stride;
+    a.neigh = nb; a.neigh_cs = nb_cs;
+    a.W = w.W; a.b = w.b; a.gamma = w.gamma; a.beta = w.beta;
+    a.stats = stats_slot(4);
+    a.out = y.p; a.out_cs = (int64_t)n * 12; a.n = n; a.clouds = clouds;
+    rec_flush();
+    if (w.cin != 10 || w.cout != 12 || w.groups != 4) { refuse("mlp_pre: the point-pair-feature layer is 10 -> 12 channels in 4 groups"); return y; }
+    if (!c->ws.overflow && !launch_ppf_pre(a, st)) refuse("mlp_pre: the point-pair-feature layer refused the launch");
+    return y;
+  }
   // mlp1 and mlp_skip of a block in ONE launch (same input; the weights one after the other, BlockW::pair_W): two outputs, two
   // sets of statistics - each element the chain the separate launch gives it.  False: not served (the caller launches them apart).
   bool mlp2d_pair(const BlockW& b, const Seg& s0, int M, Act& y1, Act& y2) {
@@ -848,7 +877,8 @@ int randla_forward(dsir_ctx* c, const RandlaW& w, const Seg& in0, const Seg* in1
                            cache ? cache->enc2_buf[l] : nullptr, cache ? cache->enc2_stats[l] : nullptr);
   };
   Act enc_pre[DSIR_MAX_LEVELS], enc2_pre[DSIR_MAX_LEVELS];
-  Act x = s.mlp2d(w.pre, in0, in1, py.nl[0], true);
+  if (w.ppf && !in1) return fail(c, "randla_forward: the point-pair-feature layer needs normals");
+  Act x = w.ppf ? s.ppf_pre(w.pre, in0, *in1, py.neigh, neigh_cs, py.nl[0]) : s.mlp2d(w.pre, in0, in1, py.nl[0], true);
   std::vector<Act> skips;
   for (int l = 0; l < L; ++l) {
     const BlockW& b = w.blk[l];
@@ -1109,8 +1139,12 @@ dsir_ctx::MatchEvents* match_event_slot(dsir_ctx* c) {
 // =================================================================== C ABI
 extern "C" {
 
-int dsir_create(int device, const dsir_cfg* cfg, dsir_ctx** out) {
+int dsir_create(int device, const dsir_cfg* cfg, dsir_ctx** out) { return dsir_create_ex(device, cfg, 0, out); }
+
+int dsir_create_ex(int device, const dsir_cfg* cfg, int flags, dsir_ctx** out) {
   if (!cfg || !out) return fail(nullptr, "dsir_create: null argument");
+  if (flags & ~DSIR_FLAG_PPF) return fail(nullptr, "dsir_create_ex: unknown flags 0x%x", flags);
+  const bool ppf = (flags & DSIR_FLAG_PPF) != 0;
   if (cfg->num_knn != kKnn) return fail(nullptr, "num_knn must be %d (got %d)", kKnn, cfg->num_knn);
   if (cfg->num_layers != 4) return fail(nullptr, "num_layers must be 4 (got %d)", cfg->num_layers);
   if (cfg->out_feat_dim != 64) return fail(nullptr, "out_feat_dim must be 64 (got %d)", cfg->out_feat_dim);
@@ -1120,21 +1154,24 @@ int dsir_create(int device, const dsir_cfg* cfg, dsir_ctx** out) {
     if (cfg->sub_sampling_ratio[l] < 1) return fail(nullptr, "bad sub_sampling_ratio");
   }
   if (cfg->feat_len < 3 || cfg->feat_len > 16) return fail(nullptr, "feat_len must be in [3,16]");
+  // use_ppf: a point row is xyz + normal (+ more); the reference asserts it in RandLA.forward (RandLANet.py:325)
+  if (ppf && cfg->feat_len < 6)
+    return fail(nullptr, "use_ppf: feat_len=%d, but a point row needs xyz and a normal, at least 6 columns (reference RandLANet.py:325: \"feature dimension error\")", cfg->feat_len);
   if (cfg->max_points < kKnn * 64 || cfg->max_pairs < 1) return fail(nullptr, "max_points must be >= %d and max_pairs >= 1", kKnn * 64);
   // several kernels address a cloud's rows with 32-bit byte offsets from a per-cloud base (n * 16 * d * 4 < 2^32 at d = 64: knn_grid.hip,
   // att_pool.hip, lse_uv.hip check their own products); 2^20 points per cloud is far beyond what the 2.5 kB-per-point workspace admits
   if (cfg->max_points > (1 << 20)) return fail(nullptr, "max_points must be <= %d", 1 << 20);
   // the GroupNorm statistics' atomics are exact - order independent - for at most kGnMaxContrib contributions per statistic
   // (device_utils.h); the largest layer of a cloud of max_points points must stay within that
-  if (const int gc = gn_max_contributions(*cfg, cfg->max_points); gc > kGnMaxContrib)
+  if (const int gc = gn_max_contributions(*cfg, cfg->max_points, flags); gc > kGnMaxContrib)
     return fail(nullptr, "max_points=%d: %d workgroup contributions per GroupNorm statistic exceed the exactness bound %d of the statistics' atomics (max_points <= %d)",
-                cfg->max_points, gc, kGnMaxContrib, dsir_max_points_limit(cfg));
+                cfg->max_points, gc, kGnMaxContrib, dsir_max_points_limit_ex(cfg, flags));
   if (cfg->pipeline < DSIR_PIPELINE_ALIGN || cfg->pipeline > DSIR_PIPELINE_LABEL) return fail(nullptr, "unknown pipeline %d", cfg->pipeline);
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(nullptr, "no HIP device available");
   if (device < 0 || device >= ndev) return fail(nullptr, "device %d out of range (%d devices)", device, ndev);
   dsir_ctx* c = new dsir_ctx();
-  c->device = device; c->cfg = *cfg;
+  c->device = device; c->cfg = *cfg; c->flags = flags;
   c->screen_mode = tuning_flag("DSIR_NO_SCREEN") ? 0 : 1;
   if (const char* e = tuning_env("DSIR_PRUNE_MIN_K")) c->prune_min_points = atoi(e) > 0 ? atoi(e) : 0;   // A/B hook; 0 = off
   if (const char* e = tuning_env("DSIR_PRUNE_MIN_ROWS")) c->prune_min_rows = atoll(e) > 0 ? atoll(e) : 0;   // tuning hook
@@ -1233,22 +1270,24 @@ void dsir_destroy(dsir_ctx* c) {
   delete c;
 }
 
-int dsir_gn_contributions(const dsir_cfg* cfg, int n_points) {
-  if (!cfg || cfg->num_layers != 4 || n_points < 1) return -1;
+int dsir_gn_contributions_ex(const dsir_cfg* cfg, int flags, int n_points) {
+  if (!cfg || cfg->num_layers != 4 || n_points < 1 || (flags & ~DSIR_FLAG_PPF)) return -1;
   for (int l = 0; l < 4; ++l) if (cfg->sub_sampling_ratio[l] < 1) return -1;
-  return gn_max_contributions(*cfg, n_points);
+  return gn_max_contributions(*cfg, n_points, flags);
 }
+int dsir_gn_contributions(const dsir_cfg* cfg, int n_points) { return dsir_gn_contributions_ex(cfg, 0, n_points); }
 int dsir_gn_contribution_limit(void) { return kGnMaxContrib; }
-int dsir_max_points_limit(const dsir_cfg* cfg) {
-  if (dsir_gn_contributions(cfg, 1024) < 0) return -1;
+int dsir_max_points_limit_ex(const dsir_cfg* cfg, int flags) {
+  if (dsir_gn_contributions_ex(cfg, flags, 1024) < 0) return -1;
   int lo = 1024, hi = 1 << 20;                       // the count grows with n: bisect the largest n within the bound
-  if (gn_max_contributions(*cfg, hi) <= kGnMaxContrib) return hi;
+  if (gn_max_contributions(*cfg, hi, flags) <= kGnMaxContrib) return hi;
   while (hi - lo > 1) {
     const int mid = lo + (hi - lo) / 2;
-    if (gn_max_contributions(*cfg, mid) <= kGnMaxContrib) lo = mid; else hi = mid;
+    if (gn_max_contributions(*cfg, mid, flags) <= kGnMaxContrib) lo = mid; else hi = mid;
   }
   return lo;
 }
+int dsir_max_points_limit(const dsir_cfg* cfg) { return dsir_max_points_limit_ex(cfg, 0); }
 
 void dsir_set_tuning(int on) { g_tuning = on ? 1 : 0; }
 int dsir_tuning(void) { tuning_env("DSIR_TUNING"); return g_tuning == 1; }
@@ -1334,6 +1373,7 @@ int dsir_finalize_weights(dsir_ctx* c) {
   const float* b = c->dweights;
   c->net.feat = bind_randla(b, fo, c->cfg);
   if (has_inl) c->net.inl = bind_randla(b, io, c->cfg);
+  c->net.feat.ppf = c->net.inl.ppf = (c->flags & DSIR_FLAG_PPF) != 0;
   if (c->dweights16) { hipFree(c->dweights16); c->dweights16 = nullptr; }
   for (int k = 0; k < 5; ++k) c->agg_wh[k] = c->agg_wl[k] = nullptr;
   if (has_agg) {
@@ -1392,17 +1432,52 @@ int dsir_randla_forward(dsir_ctx* c, int which, const float* features, int cin, 
   HIP_OK(c, hipSetDevice(c->device));
   if (which != 0 && c->cfg.pipeline != DSIR_PIPELINE_ALIGN) return fail(c, "randla_forward: this context has no inlier_model (pipeline != align)");
   const RandlaW& w = which == 0 ? c->net.feat : c->net.inl;
-  if (cin != w.cin) return fail(c, "randla_forward: expected %d input channels, got %d", w.cin, cin);
+  if (w.ppf ? cin < 6 : cin != w.cin)
+    return w.ppf ? fail(c, "randla_forward: use_ppf needs rows of xyz + normal, at least 6 columns, got %d (reference RandLANet.py:325)", cin)
+                 : fail(c, "randla_forward: expected %d input channels, got %d", w.cin, cin);
   if (clouds > 2 * c->cfg.max_pairs || n > c->cfg.max_points) return fail(c, "randla_forward: batch exceeds max_pairs/max_points");
   Pyramid py;
   fill_pyramid_layout(c->cfg, clouds, n, py);
   if (py.nl[3] < kKnn) return fail(c, "cloud too small (n=%d)", n);
   py.xyz = xyz; py.neigh = neigh; py.sub = sub; py.interp = interp;
-  const Seg in0 = plain_seg(features, (int64_t)n * cin, cin, cin);
+  // use_ppf: the row's first three columns are the point, the next three its normal (RandLANet.py:326)
+  const Seg in0 = plain_seg(features, (int64_t)n * cin, w.ppf ? 3 : cin, cin);
+  const Seg in1 = plain_seg(features + 3, (int64_t)n * cin, 3, cin);
   if (int r = walk_begin_call(c)) return r;
-  if (int r = randla_forward(c, w, in0, nullptr, py, feat, logits)) return r;
+  if (int r = randla_forward(c, w, in0, w.ppf ? &in1 : nullptr, py, feat, logits)) return r;
   if (int r = walk_end_call(c)) return r;
   return post(c);
+}
+
+int dsir_ppf_pre(dsir_ctx* c, int which, const float* rows, int stride, const int32_t* neigh, int64_t neigh_cs, int clouds, int n,
+                 float* out) {
+  if (check_ready(c)) return 1;
+  HIP_OK(c, hipSetDevice(c->device));
+  if (!(c->flags & DSIR_FLAG_PPF)) return fail(c, "dsir_ppf_pre: the context was not created with DSIR_FLAG_PPF");
+  if (which != 0 && c->cfg.pipeline != DSIR_PIPELINE_ALIGN) return fail(c, "dsir_ppf_pre: this context has no inlier_model (pipeline != align)");
+  if (!rows || !neigh || !out || clouds < 1 || n < kKnn) return fail(c, "dsir_ppf_pre: bad arguments");
+  if (stride < 6) return fail(c, "dsir_ppf_pre: rows of xyz + normal need at least 6 columns, got %d (reference RandLANet.py:325)", stride);
+  if (clouds > 2 * c->cfg.max_pairs || n > c->cfg.max_points) return fail(c, "dsir_ppf_pre: batch exceeds max_pairs/max_points");
+  const RandlaW& w = which == 0 ? c->net.feat : c->net.inl;
+  const size_t stats_need = (size_t)clouds * 4 * kGnWords;
+  if (stats_need > c->stats_cap) return fail(c, "stats arena too small (%zu > %zu)", stats_need, c->stats_cap);
+  c->stats_top = 0;
+  HIP_OK(c, hipMemsetAsync(c->stats, 0, stats_need * sizeof(double), c->stream));
+  Sched s{c, c->stream, clouds};
+  s.ppf_pre(w.pre, plain_seg(rows, (int64_t)n * stride, 3, stride), plain_seg(rows + 3, (int64_t)n * stride, 3, stride), neigh, neigh_cs, n, out);
+  return post(c);
+}
+
+int dsir_estimate_normals(dsir_ctx* c, const float* points, int stride, const int32_t* neigh, int64_t neigh_cs, int clouds, int n,
+                          const float* viewpoint, float* normals, int32_t* flags) {
+  if (!c) return 1;
+  HIP_OK(c, hipSetDevice(c->device));
+  if (!points || !neigh || !normals || clouds < 1 || clouds > 65535 || n < 1 || stride < 3) return fail(c, "dsir_estimate_normals: bad arguments");
+  const float v[3] = {viewpoint ? viewpoint[0] : 0.f, viewpoint ? viewpoint[1] : 0.f, viewpoint ? viewpoint[2] : 0.f};
+  launch_estimate_normals(points, (int64_t)n * stride, stride, neigh, neigh_cs, n, clouds, v[0], v[1], v[2], normals, flags, c->stream);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(c, "HIP launch error: %s", hipGetErrorString(e));
+  return 0;
 }
 
 int dsir_score(dsir_ctx* c, const float* feat, const float* logits, const float* xyz, int64_t xyz_cs,
@@ -1613,19 +1688,25 @@ static int forward_pair_stage(dsir_ctx* c, const dsir_pair_batch* in, bool want_
   // ---- forward_pair (model.py:609-648): feature RandLA + score on src and ref
   const size_t mark0 = ws.mark();
   ScoreScratch sc;
+  // the extractor's input rows; use_ppf: columns 0 - 2 the point, 3 - 5 its normal (RandLANet.py:326)
+  const bool ppf = c->net.feat.ppf;
+  auto extract = [&](const float* rows, int n, const Pyramid& py, float* feat, float* logit) {
+    const Seg pts = plain_seg(rows, (int64_t)n * cin, ppf ? 3 : cin, cin), nrm = plain_seg(rows + 3, (int64_t)n * cin, 3, cin);
+    return randla_forward(c, c->net.feat, pts, ppf ? &nrm : nullptr, py, feat, logit);
+  };
   if (joint) {
     Pyramid pa = ps;
     pa.clouds = 2 * P;
-    if (int r = randla_forward(c, c->net.feat, plain_seg(feats_in, (int64_t)J * cin, cin, cin), nullptr, pa, feat_all, logit_all)) return r;
+    if (int r = extract(feats_in, J, pa, feat_all, logit_all)) return r;
     if (want_score) {
       sc.red = score_red; sc.prob = ws.get<float>((size_t)2 * P * J); sc.label = ws.get<int32_t>((size_t)2 * P * J);
       launch_score(feat_all, logit_all, g.num_classes, pxyz, (int64_t)ps.S * 3, pneigh, (int64_t)ps.S * kKnn, 2 * P, J, sc,
                    score_all, label_all, st, /*red_preset=*/true);
     }
   } else {
-    if (int r = randla_forward(c, c->net.feat, plain_seg(feats_in, (int64_t)J * cin, cin, cin), nullptr, ps, feat_s, logit_s)) return r;
+    if (int r = extract(feats_in, J, ps, feat_s, logit_s)) return r;
     ws.release(mark0);
-    if (int r = randla_forward(c, c->net.feat, plain_seg(feats_in + (size_t)P * J * cin, (int64_t)K * cin, cin, cin), nullptr, pr, feat_r, logit_r)) return r;
+    if (int r = extract(feats_in + (size_t)P * J * cin, K, pr, feat_r, logit_r)) return r;
     ws.release(mark0);
     if (want_score) {
       const int nmax = J > K ? J : K;

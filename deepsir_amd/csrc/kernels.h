@@ -115,6 +115,9 @@ int pw_stream_gn_contributions(int M, int Cout);        // pw_stream.hip: the VI
 int pw_tile_gn_contributions(int M, int Cout, int groups);   // pw_tile.hip: row blocks x column blocks a group spans
 int lse_uv_gn_contributions(int n, int KH);             // lse_uv.hip: virtual workgroups per cloud
 
+int pw_gemm_gn_contributions(int M);                     // pw_gemm.hip: the general kernel's 64-row blocks
+int ppf_gn_contributions(int n);                        // ppf.hip: workgroups per cloud of the statistics pass
+
 // false: no kernel took the layer (the caller reports it; nothing was launched)
 bool launch_pw_gemm(const GemmArgs& a, hipStream_t st);
 bool pw_gemm_serves_pair(const GemmArgs& a);   // would launch_pw_gemm serve this launch with GemmArgs::c_split set? (ask before fusing two layers)
@@ -168,6 +171,26 @@ struct LseUvArgs {
   int vgrid = 0;                                         // virtual workgroups per cloud (filled by the launcher; a function of n alone)
 };
 bool launch_lse_uv_stats(const LseUvArgs& a, hipStream_t st);   // KH = 8 or 32; false => outside the envelope
+
+// ppf.hip - the point-pair-feature input layer (use_ppf; RandLANet.py:110-137, :324-332): feat_grouping + mlp_pre (conv 10 -> 12,
+// GroupNorm, LeakyReLU) + the mean over the 16 neighbours, in two launches (statistics, consumer) that both rebuild the ten
+// channels of a (point, neighbour) row from the points, the normals and the neighbour list: neither the [n,16,10] code nor the
+// [n,16,12] activations are ever in memory.  The arithmetic rule is stated in the file's header.
+struct PpfArgs {
+  const float* xyz = nullptr; int64_t xyz_cs = 0; int xyz_ld = 3;      // centre points [clouds][n][xyz_ld], 3 columns used
+  const float* nrm = nullptr; int64_t nrm_cs = 0; int nrm_ld = 3;      // "normals" rows, 3 columns used: the normal of point i is row
+  const int32_t* nrm_idx = nullptr; int64_t nrm_idx_cs = 0;           //   nrm_idx ? nrm_idx[i] : i   (the inlier model's matched ref points)
+  const int32_t* neigh = nullptr; int64_t neigh_cs = 0;               // level-0 neighbour rows [clouds][n][16]
+  const float *W = nullptr, *b = nullptr, *gamma = nullptr, *beta = nullptr;   // mlp_pre: [12][10], [12], [12], [12]
+  double* stats = nullptr;                                            // [clouds][4][kGnWords], zero before the launch
+  float* out = nullptr; int64_t out_cs = 0;                           // [clouds][n][12]
+  int n = 0, clouds = 0;
+};
+bool launch_ppf_pre(const PpfArgs& a, hipStream_t st);                // false: outside the envelope (nothing launched)
+// normals from the level-0 neighbour lists (the rule: ppf.hip's header): points [clouds][n][stride] -> normals [clouds][n][3],
+// flags [clouds][n] (1: degenerate neighbourhood, normal (0,0,0))
+void launch_estimate_normals(const float* pts, int64_t pts_cs, int stride, const int32_t* neigh, int64_t neigh_cs, int n, int clouds,
+                             float vx, float vy, float vz, float* normals, int32_t* flags, hipStream_t st);
 
 // mlp_out + fc_label fused (head_mlp.hip): x[32] -> feat[64] -> 64 -> 32 -> ncls   (RandLANet.py:363-367)
 struct HeadArgs {

@@ -294,6 +294,10 @@ void launch_bn(const GemmArgs& a, hipStream_t st) {
 
 }  // namespace
 
+// workgroups of one cloud that add into one GroupNorm statistic of a layer served by the general kernel: its 64-row blocks (a
+// group never spans two column blocks: its width divides Cout / 4 <= BN)
+int pw_gemm_gn_contributions(int M) { return (M + BM - 1) / BM; }
+
 // may the caller hand this (two-layer, GemmArgs::c_split) launch to launch_pw_gemm?  Only pw_tile_small_kernel writes two outputs.
 bool pw_gemm_serves_pair(const GemmArgs& a) {
   static const bool no_tile = tuning_flag("DSIR_NO_TILE");

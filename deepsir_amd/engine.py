@@ -36,8 +36,6 @@ def _chk(t: torch.Tensor, dtype, name: str) -> torch.Tensor:
 
 class Engine:
     def __init__(self, cfg: NetConfig, device: int = 0, max_points: int = 8192, max_pairs: int = 1):
-        if cfg.use_ppf:
-            raise EngineError("use_ppf=True is outside the hot path (reference default is False)")
         self.lib = _lib.load()
         self.cfg = cfg
         self.device = torch.device("cuda", device)
@@ -51,7 +49,9 @@ class Engine:
         c.max_points, c.max_pairs = self.max_points, self.max_pairs
         c.pipeline = PIPELINES.index(cfg.pipeline)
         h = C.c_void_p()
-        if self.lib.dsir_create(device, C.byref(c), C.byref(h)) != 0:
+        # use_ppf (reference RandLANet.py:251-254): feat_len is then the width of a point row, xyz + normal (+ ignored columns)
+        flags = _lib.DSIR_FLAG_PPF if cfg.use_ppf else 0
+        if self.lib.dsir_create_ex(device, C.byref(c), flags, C.byref(h)) != 0:
             raise EngineError("dsir_create: " + self.lib.dsir_last_error(None).decode())
         self.h = h
         self.weights_loaded = False
@@ -183,6 +183,32 @@ class Engine:
                                                 _ptr(interp), _ptr(feat), _ptr(logits)))
         self.sync()
         return feat, logits
+
+    def ppf_pre(self, which: str, rows, neigh_multi):
+        """The use_ppf front end of RandLA.forward (RandLANet.py:324-332; csrc/ppf.hip): rows [c,n,>=6] = xyz + normal,
+        neigh_multi the pyramid's neigh_idx [c,S,16] (its level-0 rows are read) -> [c,n,12], the input of level 0."""
+        rows, neigh_multi = _chk(rows, torch.float32, "rows"), _chk(neigh_multi, torch.int32, "neigh_idx")
+        c, n, stride = rows.shape
+        out = self._empty((c, n, 12))
+        self._pre()
+        self._call(self.lib.dsir_ppf_pre(self.h, {"feat_extractor": 0, "inlier_model": 1}[which], _ptr(rows), stride, _ptr(neigh_multi),
+                                         neigh_multi.shape[1] * 16, c, n, _ptr(out)))
+        self.sync()
+        return out
+
+    def estimate_normals(self, points, neigh_multi, viewpoint=(0.0, 0.0, 0.0)):
+        """Normals from the level-0 neighbour lists (include/dsir.h, dsir_estimate_normals; the rule: deepsir_amd/ppf.py):
+        points [c,n,>=3], neigh_multi [c,S,16] -> (normals [c,n,3], flags [c,n] i32: 1 = degenerate, normal (0,0,0))."""
+        points, neigh_multi = _chk(points, torch.float32, "points"), _chk(neigh_multi, torch.int32, "neigh_idx")
+        c, n, stride = points.shape
+        normals = self._empty((c, n, 3))
+        flags = self._empty((c, n), torch.int32)
+        v = (C.c_float * 3)(*[float(x) for x in viewpoint])
+        self._pre()
+        self._call(self.lib.dsir_estimate_normals(self.h, _ptr(points), stride, _ptr(neigh_multi), neigh_multi.shape[1] * 16, c, n, v,
+                                                  _ptr(normals), _ptr(flags)))
+        self.sync()
+        return normals, flags
 
     def score(self, feat, logits, xyz_multi, neigh_multi):
         """torch.max(logits) + score_fun counterpart -> (score [c,n], label [c,n] i32)."""

@@ -17,6 +17,7 @@ raises.
 """
 from __future__ import annotations
 
+import dataclasses
 from typing import Dict, List, Optional
 
 import torch
@@ -136,6 +137,12 @@ class Network(nn.Module):
             raise NotImplementedError("num_sub > 0 with pipeline='align' is not runnable in the reference either")
         self.num_sub, self.num_knn, self.d_out = self.cfg.num_sub, self.cfg.num_knn, self.cfg.out_feat_dim
         self.clip_weight_thresh = getattr(args, "clip_weight_thresh", 0.0)
+        # use_ppf (RandLANet.py:251-254, :324-332): inference in all three pipelines.  Two fields the reference lacks: clouds
+        # without normals (3DMatch, KITTI rows) get them from the engine's own rule (deepsir_amd/ppf.py) when asked to.
+        self.ppf_estimate_normals = bool(getattr(args, "ppf_estimate_normals", False))
+        self.ppf_viewpoint = tuple(float(x) for x in getattr(args, "ppf_viewpoint", (0.0, 0.0, 0.0)))
+        # the engines read rows of exactly xyz + normal under use_ppf (_ppf_rows); no state-dict shape depends on feat_len there
+        self._engine_cfg = dataclasses.replace(self.cfg, feat_len=6) if self.cfg.use_ppf else self.cfg
         for spec in network_specs(self.cfg):
             dtype = torch.int64 if spec.kind == "bn_count" else torch.float32
             trainable = spec.kind not in ("bn_mean", "bn_var", "bn_count")
@@ -191,7 +198,7 @@ class Network(nn.Module):
                 self._pool.close()
             self._pool_points = max(self._pool_points, n_points, 1024)
             self._pool_pairs = max(self._pool_pairs, pairs)
-            self._pool = EnginePool(self.cfg, dev, self._pool_points, self._pool_pairs, streams=2)
+            self._pool = EnginePool(self._engine_cfg, dev, self._pool_points, self._pool_pairs, streams=2)
             self._pool_dirty = True
         if self._pool_dirty:
             self._pool.load_state_dict({k: v for k, v in self.state_dict().items()})
@@ -206,7 +213,7 @@ class Network(nn.Module):
         if srv is None or n_points > srv.max_points or srv.n_iter != n_iter:
             if srv is not None:
                 srv.close()
-            self._server = srv = PairServer(self.cfg, {k: v for k, v in self.state_dict().items()}, dev, max(n_points, 1024),
+            self._server = srv = PairServer(self._engine_cfg, {k: v for k, v in self.state_dict().items()}, dev, max(n_points, 1024),
                                             2 * self.SERVE_MAX_PAIRS, 2, n_iter, True)
             self._server_dirty = False
         if self._server_dirty:       # new weights (load_state_dict, an optimiser step): reloaded into the running engines
@@ -218,7 +225,7 @@ class Network(nn.Module):
         """A ``deepsir_amd.serve.PairServer`` on this network's weights: K single-pair registrations in flight
         (the reference's batch-1 evaluation mode, test.py:56, fed ahead)."""
         from .serve import PairServer
-        return PairServer(self.cfg, {k: v for k, v in self.state_dict().items()}, self._device_index(), max_points, max_in_flight,
+        return PairServer(self._engine_cfg, {k: v for k, v in self.state_dict().items()}, self._device_index(), max_points, max_in_flight,
                           engines, self.cfg.num_reg_iter if n_iter is None else n_iter, want_aux)
 
     def _ensure_engine(self, n_points: int, pairs: int) -> Engine:
@@ -229,7 +236,7 @@ class Network(nn.Module):
                 self._engine.close()
             self._max_points = max(self._max_points, n_points, 1024)
             self._max_pairs = max(self._max_pairs, pairs)
-            self._engine = Engine(self.cfg, dev, self._max_points, self._max_pairs)
+            self._engine = Engine(self._engine_cfg, dev, self._max_points, self._max_pairs)
             self._dirty = True
         if self._dirty:
             self._engine.load_state_dict({k: v for k, v in self.state_dict().items()})
@@ -255,6 +262,7 @@ class Network(nn.Module):
         ``nn.Parameter`` (and every BatchNorm running statistic) is a view of its trainer's flat device buffer, so what
         ``optimizer.step()`` or ``train_step`` writes is what the next training forward computes with - no copies either way."""
         from . import train as T
+        self._no_ppf_training()
         st = self._tstate
         named = dict(self.named_parameters())
         named.update(dict(self.named_buffers()))
@@ -277,6 +285,13 @@ class Network(nn.Module):
         names = [k for k in main.params if named[k].requires_grad]
         self._tstate = st = _TrainState(dev, main, frozen, names, [named[k] for k in names])
         return st
+
+    def _no_ppf_training(self):
+        """Out of scope, said so: the training operators (deepsir_amd/train.py, include/dsir_train.h) know the 8-channel input layer
+        only - no taped forward, no backward of feat_grouping - so nothing may run them on a use_ppf network."""
+        if self.cfg.use_ppf:
+            raise NotImplementedError("training with use_ppf=True is not built (train_step, the training-mode forward, RandlaTrainer): "
+                                      "the point-pair-feature input layer is inference only")
 
     def _train_engine(self, st: _TrainState, n_points: int, pairs: int) -> Engine:
         """The weight-free operators of the training forward (score, arg-min, Kabsch, loss)."""
@@ -324,6 +339,7 @@ class Network(nn.Module):
         from . import se3
         from . import train as T
         from .autograd import run_taped
+        self._no_ppf_training()
         src, ref = data["points_src"].float().contiguous(), data["points_ref"].float().contiguous()
         if not src.is_cuda:
             raise EngineError("Network is on the CPU: this engine has no CPU path; call .to('cuda') / .cuda() first")
@@ -444,6 +460,8 @@ class Network(nn.Module):
         K = ref.shape[1]
         have = all(f"points_{s}_{k}" in data for s in ("src", "ref") for k in _PYR_KEYS)
         pyr = {f"points_{s}_{k}": data[f"points_{s}_{k}"] for s in ("src", "ref") for k in _PYR_KEYS} if have else None
+        if self.cfg.use_ppf:
+            src, ref, pyr = self._ppf_rows(src, ref, pyr)
         if self.pipeline != "align":
             return self._forward_pair(self._ensure_engine(max(J, K), B), src, ref, pyr)
         num_reg_iter, _clip_weight = opt  # clip_weight is ignored by the reference too (model.py:581-582)
@@ -458,6 +476,29 @@ class Network(nn.Module):
             pyr = {k: (v if v.dtype != torch.int64 else v.to(torch.int32)) for k, v in pyr.items()}
         out = eng.register(src.float(), ref.float(), int(num_reg_iter), pyramids=pyr)
         return self._align_outputs(out, src, ref, int(num_reg_iter))
+
+    def _ppf_rows(self, src, ref, pyr):
+        """use_ppf: rows of xyz + normal for the engine (RandLANet.py:325-326).  Clouds that carry them pass through (columns
+        beyond 6 are not read by the reference either); clouds that do not get normals from ``Engine.estimate_normals`` on the
+        pyramid the registration needs anyway - handed on, not built twice - when ``args.ppf_estimate_normals`` says so; else the
+        reference's assertion."""
+        if src.shape[2] >= 6 and ref.shape[2] >= 6:
+            return src[:, :, :6].float().contiguous(), ref[:, :, :6].float().contiguous(), pyr
+        if not self.ppf_estimate_normals:
+            raise AssertionError("feature dimension error")       # RandLANet.py:325
+        eng = self._ensure_engine(max(src.shape[1], ref.shape[1]), src.shape[0])
+        out, rows = {}, []
+        for s_, pts in (("src", src), ("ref", ref)):
+            pts = pts.float().contiguous()
+            if pyr is not None:
+                py = [pyr[f"points_{s_}_xyz"].float().contiguous()] + [eng.narrow(pyr[f"points_{s_}_{k}"]) for k in _PYR_KEYS[1:]]
+            else:
+                py = list(eng.knn_pyramid(pts))
+            normals, _ = eng.estimate_normals(pts, py[1].reshape(pts.shape[0], -1, 16), self.ppf_viewpoint)
+            rows.append(torch.cat([pts[:, :, :3], normals], dim=2).contiguous())
+            for k, t in zip(_PYR_KEYS, py):
+                out[f"points_{s_}_{k}"] = t
+        return rows[0], rows[1], out
 
     @staticmethod
     def _align_outputs(out, src, ref, num_reg_iter: int):
@@ -494,6 +535,7 @@ class Network(nn.Module):
         the training-mode forward - so ``state_dict()`` is the trained checkpoint and the next ``forward`` serves it.  Adam state lives
         in that state's main trainer; ``load_state_dict`` resets it.  Returns the step's dict (loss ...)."""
         from . import train as T
+        self._no_ppf_training()
         src, ref = data["points_src"].float(), data["points_ref"].float()
         B, J, _ = src.shape
         K = ref.shape[1]

@@ -1,0 +1,132 @@
+"""Host restatement (numpy) of the two rules csrc/ppf.hip owns: the point-pair-feature input layer of ``use_ppf`` (reference
+network/RandLANet.py:110-137, :324-332; network/matchnet.py:11-30) in the kernel's written arithmetic, and the normal
+estimation (open3d's ``estimate_normals`` is unpinned: the rule is the engine's own).  What the tests compare the kernels with,
+as ``deepsir_amd/ransac.py`` and ``augment.py`` are for theirs.  Nothing here runs on the hot path.
+
+Front end, all fp32, every operation rounded once (numpy's float32 arithmetic does that), j = neigh[i, k]:
+    d = p_j - p_i;  cross(a, b) = (a1 b2 - a2 b1, a2 b0 - a0 b2, a0 b1 - a1 b0);  dot(a, b) = ((+0 + a0 b0) + a1 b1) + a2 b2
+    (the sum starts from +0 as torch.sum's does: products of a zero vector with negative numbers are -0, and atan2(0, -0) is pi)
+    norm(a) = sqrt((a0 a0 + a1 a1) + a2 a2);  angle(a, b) = atan2(norm(cross(a, b)), dot(a, b))     (atan2(0, 0) = 0)
+    x = [p_i, d, angle(n_i, d), angle(n_j, d), angle(n_i, n_j), norm(d)]
+    y[c] = fma chain over the input channels in ascending order, starting from the bias
+    GroupNorm(4 groups of 3 channels, statistics over the cloud's n x 16 rows, fp64 sums, scale / shift rounded to fp32, applied
+    as one fma), LeakyReLU(0.2), mean over k as a butterfly (partners 1, 2, 4, 8) times 1/16.
+The fma is restated as round32(float64(w) * float64(x) + float64(acc)): the product is exact in fp64, the sum is rounded twice -
+to fp64, then to fp32 - where the kernel rounds once; the two differ by one fp32 ulp in about one sum in 2^29.  atan2 is the host
+library's, the device's atan2f is its own (both within a few ulp): the comparison is a tolerance, not bits.
+
+Normals, one point at a time: the 16 level-0 neighbours in list order (self included); mean and covariance as fp64 sums of the
+fp32 coordinates in that order; the eigenvector of the smallest eigenvalue (``numpy.linalg.eigh`` here, the Jacobi SVD of svd3.h
+on the device); normalised in fp64; flipped so that n . (v - p) >= 0 for the viewpoint v (at exactly 0: the component of largest
+magnitude positive, ties to the lower axis); rounded to fp32 once.  Largest eigenvalue 0 or anything non-finite: normal (0,0,0),
+flag 1.
+"""
+from __future__ import annotations
+
+from typing import Tuple
+
+import numpy as np
+
+F = np.float32
+
+
+def _norm3(a: np.ndarray) -> np.ndarray:
+    return np.sqrt((a[..., 0] * a[..., 0] + a[..., 1] * a[..., 1]) + a[..., 2] * a[..., 2])
+
+
+def angle(a: np.ndarray, b: np.ndarray) -> np.ndarray:
+    """matchnet.py:11-30 in the kernel's written order; a, b float32 [..., 3]."""
+    a, b = np.asarray(a, F), np.asarray(b, F)
+    c = np.stack([a[..., 1] * b[..., 2] - a[..., 2] * b[..., 1],
+                  a[..., 2] * b[..., 0] - a[..., 0] * b[..., 2],
+                  a[..., 0] * b[..., 1] - a[..., 1] * b[..., 0]], -1)
+    dot = ((F(0.0) + a[..., 0] * b[..., 0]) + a[..., 1] * b[..., 1]) + a[..., 2] * b[..., 2]    # from +0: never -0 (atan2(0, -0) = pi)
+    return np.arctan2(_norm3(c), dot).astype(F)
+
+
+def feat_grouping(xyz: np.ndarray, normals: np.ndarray, neigh: np.ndarray) -> np.ndarray:
+    """RandLANet.py:110-137: xyz, normals [B, N, 3], neigh [B, N, 16] -> the ten channels [B, N, 16, 10] (float32)."""
+    xyz, normals = np.asarray(xyz, F), np.asarray(normals, F)
+    B = xyz.shape[0]
+    bi = np.arange(B)[:, None, None]
+    pj, nj = xyz[bi, neigh], normals[bi, neigh]                    # [B, N, 16, 3]
+    pi = np.broadcast_to(xyz[:, :, None, :], pj.shape)
+    ni = np.broadcast_to(normals[:, :, None, :], pj.shape)
+    d = pj - pi
+    return np.concatenate([pi, d, angle(ni, d)[..., None], angle(nj, d)[..., None], angle(ni, nj)[..., None], _norm3(d)[..., None]],
+                          -1).astype(F)
+
+
+def _fma(a: np.ndarray, b: np.ndarray, c: np.ndarray) -> np.ndarray:
+    return (a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)).astype(F)
+
+
+def ppf_pre(rows: np.ndarray, neigh: np.ndarray, W: np.ndarray, b: np.ndarray, gamma: np.ndarray, beta: np.ndarray) -> np.ndarray:
+    """The whole front end (RandLANet.py:324-332): rows [B, N, >= 6] = xyz + normal, neigh [B, N, 16] (level 0), mlp_pre's
+    conv weight [12, 10(,1,1)], bias, GroupNorm weight, bias -> [B, N, 12], the input of level 0 (point-major)."""
+    rows = np.asarray(rows, F)
+    x = feat_grouping(rows[..., :3], rows[..., 3:6], neigh)            # [B, N, 16, 10]
+    W = np.asarray(W, F).reshape(12, 10)
+    y = np.broadcast_to(np.asarray(b, F), x.shape[:-1] + (12,)).copy()
+    for q in range(10):
+        y = _fma(np.broadcast_to(W[:, q], y.shape), np.broadcast_to(x[..., q:q + 1], y.shape), y)
+    B, N = y.shape[:2]
+    g = y.reshape(B, N * 16, 4, 3)
+    s1 = g.astype(np.float64).sum((1, 3))                              # [B, 4]
+    s2 = (g * g).astype(np.float64).sum((1, 3))                        # the square is an fp32 product
+    inv = 1.0 / (3.0 * N * 16.0)
+    mean = s1 * inv
+    var = np.maximum(s2 * inv - mean * mean, 0.0)
+    rstd = 1.0 / np.sqrt(var + 1e-5)
+    sc = np.asarray(gamma, np.float64)[None, :] * np.repeat(rstd, 3, 1)                # [B, 12]
+    sh = np.asarray(beta, np.float64)[None, :] - np.repeat(mean, 3, 1) * sc
+    z = _fma(y, np.broadcast_to(sc.astype(F)[:, None, None, :], y.shape), np.broadcast_to(sh.astype(F)[:, None, None, :], y.shape))
+    z = np.where(z < 0, F(0.2) * z, z).astype(F)
+    k = np.arange(16)
+    for o in (1, 2, 4, 8):
+        z = z + z[:, :, k ^ o, :]
+    return (z[:, :, 0, :] * F(0.0625)).astype(F)
+
+
+def estimate_normals(points: np.ndarray, neigh: np.ndarray, viewpoint=(0.0, 0.0, 0.0)) -> Tuple[np.ndarray, np.ndarray]:
+    """points [B, N, >= 3] float32, neigh [B, N, 16] (level 0) -> (normals [B, N, 3] float32, flags [B, N] int32)."""
+    pts = np.asarray(points, F)[..., :3].astype(np.float64)
+    v = np.asarray(viewpoint, F).astype(np.float64)
+    B, N = pts.shape[:2]
+    out = np.zeros((B, N, 3), F)
+    flags = np.ones((B, N), np.int32)
+    for bi in range(B):
+        q = pts[bi][neigh[bi]]                                         # [N, 16, 3]
+        m = np.zeros((N, 3))
+        for k in range(16):
+            m = m + q[:, k]
+        m = m / 16.0
+        C = np.zeros((N, 3, 3))
+        for k in range(16):
+            e = q[:, k] - m
+            C = C + e[:, :, None] * e[:, None, :]
+        ok = np.isfinite(C).all((1, 2))
+        w, V = np.linalg.eigh(np.where(ok[:, None, None], C, 0.0))     # ascending eigenvalues
+        nv = V[:, :, 0]
+        nv = nv / np.sqrt((nv * nv).sum(1, keepdims=True))
+        t = (nv * (v[None] - pts[bi])).sum(1)
+        mx = np.argmax(np.abs(nv), 1)                                  # first maximum = the lower axis
+        flip = np.where(t == 0.0, nv[np.arange(N), mx] < 0.0, t < 0.0)
+        nv = np.where(flip[:, None], -nv, nv)
+        good = ok & (w[:, 2] > 0.0) & np.isfinite(t)
+        out[bi] = np.where(good[:, None], nv, 0.0).astype(F)
+        flags[bi] = np.where(good, 0, 1)
+    return out, flags
+
+
+def analytic_normals_cloud(n: int, seed: int) -> np.ndarray:
+    """The cloud the normal rule is tested on: half the points on the unit sphere centred (0, 0, 3), half on the plane z = 5 with
+    x, y in [-1, 1]; Gaussian jitter of sigma 0.002 clipped at 0.01; rows permuted; float32 [n, 3]."""
+    rng = np.random.Generator(np.random.Philox(key=int(seed)))
+    h = n // 2
+    u = rng.standard_normal((h, 3))
+    sphere = u / np.linalg.norm(u, axis=1, keepdims=True) + np.array([0.0, 0.0, 3.0])
+    plane = np.concatenate([rng.uniform(-1.0, 1.0, (n - h, 2)), np.full((n - h, 1), 5.0)], 1)
+    pts = np.concatenate([sphere, plane], 0)
+    pts = pts + np.clip(rng.standard_normal(pts.shape) * 0.002, -0.01, 0.01)
+    return np.ascontiguousarray(pts[rng.permutation(n)], dtype=F)

@@ -541,6 +541,8 @@ class RandlaTrainer(_ParamStore):
 
     def __init__(self, cfg: NetConfig, state_dict: Dict[str, "np.ndarray | torch.Tensor"], prefix: str = "inlier_model", feat_in: int = 6,
                  num_classes: int = 1, device: "str | torch.device" = "cuda:0"):
+        if cfg.use_ppf:      # the taped forward below is the 8-channel input layer: never run it on a 12-channel checkpoint
+            raise NotImplementedError("RandlaTrainer: training with use_ppf=True is not built (the point-pair-feature input layer is inference only)")
         self.cfg, self.prefix, self.feat_in, self.num_classes = cfg, prefix, feat_in, num_classes
         self.device = torch.device(device)
         self.ops = _Ops(self.device)

@@ -62,6 +62,14 @@ typedef struct dsir_cfg {
 
 /* Replaces Network.__init__ + .to(device) (network/model.py:119-195, test.py:609-611). */
 int dsir_create(int device, const dsir_cfg* cfg, dsir_ctx** out);
+/* The same with option flags (dsir_create is flags = 0; dsir_cfg itself does not grow).
+ * DSIR_FLAG_PPF = args.use_ppf (network/RandLANet.py:251-254): both RandLA networks take the point-pair-feature input layer -
+ * mlp_pre is conv 10 -> 12 on feat_grouping's code (:110-137) and level 0 takes 12 channels (the state dict's shapes follow:
+ * mlp_pre.conv.weight [12,10,1,1], dilated_res_blocks.0.mlp1 / .mlp_skip 12 inputs).  cfg.feat_len is then the number of
+ * columns of a point row: xyz, the normal, anything more is ignored; fewer than 6 is an error (the reference's assertion,
+ * RandLANet.py:325 "feature dimension error").  Inference only: the training operators (dsir_train.h) know no such layer. */
+#define DSIR_FLAG_PPF 1
+int dsir_create_ex(int device, const dsir_cfg* cfg, int flags, dsir_ctx** out);
 void dsir_destroy(dsir_ctx* ctx);
 const char* dsir_last_error(const dsir_ctx* ctx);   /* ctx may be NULL: creation errors */
 /* The HIP stream (hipStream_t) every call is ordered on. */
@@ -112,6 +120,28 @@ int dsir_knn_pyramid(dsir_ctx* ctx, const float* points, int stride, int clouds,
 int dsir_randla_forward(dsir_ctx* ctx, int which, const float* features, int cin, int clouds, int n,
                         const float* xyz_multi, const int32_t* neigh_idx, const int32_t* sub_idx,
                         const int32_t* interp_idx, float* feat, float* logits);
+
+/* Under DSIR_FLAG_PPF dsir_randla_forward takes rows of cin >= 6 columns (xyz, normal) for either network (the reference's
+ * inlier model is handed [moved src xyz ; matched ref xyz] there, model.py:574-577: its "normals" are the matched points),
+ * and dsir_forward_pair / dsir_register read points_src / points_ref as rows of feat_len columns with the normal in 3 .. 5.
+ *
+ * dsir_ppf_pre replaces the use_ppf front end of RandLA.forward alone (network/RandLANet.py:324-332: feat_grouping :110-137 with
+ * matchnet.py:11-30 angle, mlp_pre, mean over the neighbours).  which as above; rows [clouds][n][stride] (stride >= 6: xyz,
+ * normal); neigh_idx = the level-0 rows of the pyramid, neigh_cloud_stride ints between clouds -> out [clouds][n][12], the
+ * input of dilated_res_blocks[0].  Needs a DSIR_FLAG_PPF context.  Same bytes on every run; clouds are independent, bit for bit. */
+int dsir_ppf_pre(dsir_ctx* ctx, int which, const float* rows, int stride, const int32_t* neigh_idx, int64_t neigh_cloud_stride,
+                 int clouds, int n, float* out);
+
+/* Normals for the rows above where the data has none (the reference's 3DMatch / KITTI loaders; it would call open3d's
+ * estimate_normals, which is unpinned here: the rule is this engine's own, stated in csrc/ppf.hip and restated in
+ * deepsir_amd/ppf.py).  Per point: the 16 level-0 neighbours (self included), fp64 mean and covariance in list order, the
+ * eigenvector of the smallest eigenvalue, normalised in fp64, oriented towards the viewpoint (n . (v - p) >= 0; exactly 0: largest
+ * component positive, ties to the lower axis), rounded to fp32 once.  points [clouds][n][stride] (xyz first); neigh_idx /
+ * neigh_cloud_stride as for dsir_ppf_pre; viewpoint = HOST float[3] or NULL (the origin) -> normals [clouds][n][3], flags
+ * [clouds][n] i32 or NULL (1: degenerate - all neighbours coincide or a value is not finite - normal (0,0,0); not an error:
+ * angle() of a zero vector is 0, matchnet.py:16).  Any context serves. */
+int dsir_estimate_normals(dsir_ctx* ctx, const float* points, int stride, const int32_t* neigh_idx, int64_t neigh_cloud_stride,
+                          int clouds, int n, const float* viewpoint, float* normals, int32_t* flags);
 
 /* Replaces torch.max(logits,1) + Network.feat_score/score_fun with num_sub<=0
  * (network/model.py:638-644, :668-757).
@@ -432,6 +462,11 @@ int dsir_tuning(void);
 int dsir_gn_contributions(const dsir_cfg* cfg, int n_points);
 int dsir_gn_contribution_limit(void);
 int dsir_max_points_limit(const dsir_cfg* cfg);
+/* The same under dsir_create_ex's flags.  DSIR_FLAG_PPF adds the point-pair-feature layer (one contribution per 64 points) and moves
+ * level 0's mlp1 / mlp_skip to the general kernel (one per 64 rows); level 0's lfa.mlp1 (one per 32 points) remains the largest, so
+ * the limit is the same number - computed, not assumed. */
+int dsir_gn_contributions_ex(const dsir_cfg* cfg, int flags, int n_points);
+int dsir_max_points_limit_ex(const dsir_cfg* cfg, int flags);
 
 /* Diagnostics of the fp16 screening (csrc/nn_screen.hip) on ONE pair, all pointers DEVICE memory: for every (row, column)
  * the screening's lower bound L, its upper bound U = L + 2 d and the exact fp32 distance D of dsir_nn_match
