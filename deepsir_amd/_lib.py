@@ -169,6 +169,12 @@ SYMBOLS = {
                                      C.c_void_p]),
     "dsir_t_maxpool_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                      C.c_void_p, C.c_int]),
+    "dsir_t_ppf_fwd_scratch": (C.c_size_t, [C.c_int, C.c_int]),
+    "dsir_t_ppf_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dsir_t_ppf_bwd_scratch": (C.c_size_t, [C.c_int, C.c_int]),
+    "dsir_t_ppf_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dsir_t_weighted_ce_scratch": (C.c_size_t, [C.c_int64]),
     "dsir_t_weighted_ce": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_float, C.c_void_p,
                                      C.c_void_p, C.c_void_p]),

@@ -184,6 +184,8 @@ struct PpfArgs {
   const float *W = nullptr, *b = nullptr, *gamma = nullptr, *beta = nullptr;   // mlp_pre: [12][10], [12], [12], [12]
   double* stats = nullptr;                                            // [clouds][4][kGnWords], zero before the launch
   float* out = nullptr; int64_t out_cs = 0;                           // [clouds][n][12]
+  float* saved = nullptr;                                             // the taped forward (dsir_t_ppf_fwd): [clouds][32] = scale[12], shift[12],
+                                                                      //   {mean, rstd}[4] as applied; nullptr: inference, nothing kept
   int n = 0, clouds = 0;
 };
 bool launch_ppf_pre(const PpfArgs& a, hipStream_t st);                // false: outside the envelope (nothing launched)

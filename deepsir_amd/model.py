@@ -137,7 +137,7 @@ class Network(nn.Module):
             raise NotImplementedError("num_sub > 0 with pipeline='align' is not runnable in the reference either")
         self.num_sub, self.num_knn, self.d_out = self.cfg.num_sub, self.cfg.num_knn, self.cfg.out_feat_dim
         self.clip_weight_thresh = getattr(args, "clip_weight_thresh", 0.0)
-        # use_ppf (RandLANet.py:251-254, :324-332): inference in all three pipelines.  Two fields the reference lacks: clouds
+        # use_ppf (RandLANet.py:251-254, :324-332): inference and the training-mode forward in all three pipelines.  Two fields the reference lacks: clouds
         # without normals (3DMatch, KITTI rows) get them from the engine's own rule (deepsir_amd/ppf.py) when asked to.
         self.ppf_estimate_normals = bool(getattr(args, "ppf_estimate_normals", False))
         self.ppf_viewpoint = tuple(float(x) for x in getattr(args, "ppf_viewpoint", (0.0, 0.0, 0.0)))
@@ -262,7 +262,6 @@ class Network(nn.Module):
         ``nn.Parameter`` (and every BatchNorm running statistic) is a view of its trainer's flat device buffer, so what
         ``optimizer.step()`` or ``train_step`` writes is what the next training forward computes with - no copies either way."""
         from . import train as T
-        self._no_ppf_training()
         st = self._tstate
         named = dict(self.named_parameters())
         named.update(dict(self.named_buffers()))
@@ -286,12 +285,12 @@ class Network(nn.Module):
         self._tstate = st = _TrainState(dev, main, frozen, names, [named[k] for k in names])
         return st
 
-    def _no_ppf_training(self):
-        """Out of scope, said so: the training operators (deepsir_amd/train.py, include/dsir_train.h) know the 8-channel input layer
-        only - no taped forward, no backward of feat_grouping - so nothing may run them on a use_ppf network."""
+    def _no_ppf_train_step(self):
+        """``train_step`` alone still refuses a use_ppf network: its callers hand it raw loader rows, and the normals hand-over of
+        ``_ppf_rows`` is not wired into it.  The trainers and the training-mode forward do train under use_ppf."""
         if self.cfg.use_ppf:
-            raise NotImplementedError("training with use_ppf=True is not built (train_step, the training-mode forward, RandlaTrainer): "
-                                      "the point-pair-feature input layer is inference only")
+            raise NotImplementedError("train_step with use_ppf=True is not built: train a use_ppf network through the training-mode forward "
+                                      "(net.train(); net(data, opt); loss.backward(); optimizer.step()) or the trainers of deepsir_amd.train")
 
     def _train_engine(self, st: _TrainState, n_points: int, pairs: int) -> Engine:
         """The weight-free operators of the training forward (score, arg-min, Kabsch, loss)."""
@@ -300,7 +299,7 @@ class Network(nn.Module):
         if eng is None or n_points > have[0] or pairs > have[1]:
             # an outgrown engine is not closed: the endpoints of an earlier forward may still hold it for their loss (_AlignLoss);
             # Engine.__del__ frees it once the last of them is gone
-            st.engine = eng = Engine(self.cfg, st.dev.index or 0, max(n_points, have[0]), max(pairs, have[1]))
+            st.engine = eng = Engine(self._engine_cfg, st.dev.index or 0, max(n_points, have[0]), max(pairs, have[1]))
             eng.load_state_dict({k: v for k, v in self.state_dict().items()})
         return eng
 
@@ -339,7 +338,6 @@ class Network(nn.Module):
         from . import se3
         from . import train as T
         from .autograd import run_taped
-        self._no_ppf_training()
         src, ref = data["points_src"].float().contiguous(), data["points_ref"].float().contiguous()
         if not src.is_cuda:
             raise EngineError("Network is on the CPU: this engine has no CPU path; call .to('cuda') / .cuda() first")
@@ -348,6 +346,13 @@ class Network(nn.Module):
         K = ref.shape[1]
         st = self._training_state(dev)
         eng = self._train_engine(st, max(J, K), B)
+        if self.cfg.use_ppf:
+            # rows of xyz + normal for the point-pair-feature layer (RandLANet.py:325-326); normals that have to be estimated come from
+            # the training engine itself (weight-free operators), and the pyramid built for them is handed on
+            have = all(f"points_{s}_{k}" in data for s in ("src", "ref") for k in _PYR_KEYS)
+            src, ref, pyr = self._ppf_rows(src, ref, {f"points_{s}_{k}": data[f"points_{s}_{k}"] for s in ("src", "ref") for k in _PYR_KEYS} if have else None, eng)
+            if pyr is not None:
+                data = {**data, **pyr}
         main, frozen, params, names = st.main, st.frozen, st.params, st.names
         batch = self._pyramids(eng, data, src, ref)
         self._dirty = self._pool_dirty = self._server_dirty = True      # running statistics move now, the weights at optimizer.step()
@@ -477,16 +482,17 @@ class Network(nn.Module):
         out = eng.register(src.float(), ref.float(), int(num_reg_iter), pyramids=pyr)
         return self._align_outputs(out, src, ref, int(num_reg_iter))
 
-    def _ppf_rows(self, src, ref, pyr):
+    def _ppf_rows(self, src, ref, pyr, eng: Optional[Engine] = None):
         """use_ppf: rows of xyz + normal for the engine (RandLANet.py:325-326).  Clouds that carry them pass through (columns
         beyond 6 are not read by the reference either); clouds that do not get normals from ``Engine.estimate_normals`` on the
         pyramid the registration needs anyway - handed on, not built twice - when ``args.ppf_estimate_normals`` says so; else the
-        reference's assertion."""
+        reference's assertion.  eng: the engine to estimate with (the training forward hands its own; default: the inference engine)."""
         if src.shape[2] >= 6 and ref.shape[2] >= 6:
             return src[:, :, :6].float().contiguous(), ref[:, :, :6].float().contiguous(), pyr
         if not self.ppf_estimate_normals:
             raise AssertionError("feature dimension error")       # RandLANet.py:325
-        eng = self._ensure_engine(max(src.shape[1], ref.shape[1]), src.shape[0])
+        if eng is None:
+            eng = self._ensure_engine(max(src.shape[1], ref.shape[1]), src.shape[0])
         out, rows = {}, []
         for s_, pts in (("src", src), ("ref", ref)):
             pts = pts.float().contiguous()
@@ -535,7 +541,7 @@ class Network(nn.Module):
         the training-mode forward - so ``state_dict()`` is the trained checkpoint and the next ``forward`` serves it.  Adam state lives
         in that state's main trainer; ``load_state_dict`` resets it.  Returns the step's dict (loss ...)."""
         from . import train as T
-        self._no_ppf_training()
+        self._no_ppf_train_step()
         src, ref = data["points_src"].float(), data["points_ref"].float()
         B, J, _ = src.shape
         K = ref.shape[1]

@@ -15,6 +15,9 @@ The fma is restated as round32(float64(w) * float64(x) + float64(acc)): the prod
 to fp64, then to fp32 - where the kernel rounds once; the two differ by one fp32 ulp in about one sum in 2^29.  atan2 is the host
 library's, the device's atan2f is its own (both within a few ulp): the comparison is a tolerance, not bits.
 
+Training: ``ppf_pre_backward`` restates the backward of the front end's four parameter tensors (dsir_t_ppf_bwd) - fp32 element-wise
+as the kernel writes it, every sum in fp64; what the GPU tests compare against where no golden exists.
+
 Normals, one point at a time: the 16 level-0 neighbours in list order (self included); mean and covariance as fp64 sums of the
 fp32 coordinates in that order; the eigenvector of the smallest eigenvalue (``numpy.linalg.eigh`` here, the Jacobi SVD of svd3.h
 on the device); normalised in fp64; flipped so that n . (v - p) >= 0 for the viewpoint v (at exactly 0: the component of largest
@@ -61,10 +64,11 @@ def _fma(a: np.ndarray, b: np.ndarray, c: np.ndarray) -> np.ndarray:
     return (a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)).astype(F)
 
 
-def ppf_pre(rows: np.ndarray, neigh: np.ndarray, W: np.ndarray, b: np.ndarray, gamma: np.ndarray, beta: np.ndarray) -> np.ndarray:
-    """The whole front end (RandLANet.py:324-332): rows [B, N, >= 6] = xyz + normal, neigh [B, N, 16] (level 0), mlp_pre's
-    conv weight [12, 10(,1,1)], bias, GroupNorm weight, bias -> [B, N, 12], the input of level 0 (point-major)."""
+def _pre_rows(rows, neigh, W, b, gamma, beta):
+    """What the forward and the backward rebuild of every (point, neighbour) row: x [B, N, 16, 10], the raw conv outputs y
+    [B, N, 16, 12], the fp32 scale / shift [B, 12] the layer applies and the groups' fp64 mean / rstd [B, 4]."""
     rows = np.asarray(rows, F)
+    neigh = np.clip(np.asarray(neigh), 0, rows.shape[1] - 1)           # the kernel's clamp: a bad neighbour index never leaves the cloud
     x = feat_grouping(rows[..., :3], rows[..., 3:6], neigh)            # [B, N, 16, 10]
     W = np.asarray(W, F).reshape(12, 10)
     y = np.broadcast_to(np.asarray(b, F), x.shape[:-1] + (12,)).copy()
@@ -80,12 +84,51 @@ def ppf_pre(rows: np.ndarray, neigh: np.ndarray, W: np.ndarray, b: np.ndarray, g
     rstd = 1.0 / np.sqrt(var + 1e-5)
     sc = np.asarray(gamma, np.float64)[None, :] * np.repeat(rstd, 3, 1)                # [B, 12]
     sh = np.asarray(beta, np.float64)[None, :] - np.repeat(mean, 3, 1) * sc
-    z = _fma(y, np.broadcast_to(sc.astype(F)[:, None, None, :], y.shape), np.broadcast_to(sh.astype(F)[:, None, None, :], y.shape))
+    return x, y, sc.astype(F), sh.astype(F), mean, rstd
+
+
+def ppf_pre(rows: np.ndarray, neigh: np.ndarray, W: np.ndarray, b: np.ndarray, gamma: np.ndarray, beta: np.ndarray) -> np.ndarray:
+    """The whole front end (RandLANet.py:324-332): rows [B, N, >= 6] = xyz + normal, neigh [B, N, 16] (level 0), mlp_pre's
+    conv weight [12, 10(,1,1)], bias, GroupNorm weight, bias -> [B, N, 12], the input of level 0 (point-major)."""
+    _, y, sc, sh, _, _ = _pre_rows(rows, neigh, W, b, gamma, beta)
+    z = _fma(y, np.broadcast_to(sc[:, None, None, :], y.shape), np.broadcast_to(sh[:, None, None, :], y.shape))
     z = np.where(z < 0, F(0.2) * z, z).astype(F)
     k = np.arange(16)
     for o in (1, 2, 4, 8):
         z = z + z[:, :, k ^ o, :]
     return (z[:, :, 0, :] * F(0.0625)).astype(F)
+
+
+def ppf_pre_backward(rows: np.ndarray, neigh: np.ndarray, W: np.ndarray, b: np.ndarray, gamma: np.ndarray, beta: np.ndarray,
+                     dout: np.ndarray, per_cloud: bool = False):
+    """The backward of ``ppf_pre`` w.r.t. its four parameter tensors (the rows are data), the rule of csrc/ppf.hip's training
+    paragraph: dout [B, N, 12] = d loss / d output -> (dW [12, 10], db, dgamma, dbeta [12]) as float64.  Element-wise steps in fp32
+    as the kernel writes them, every sum in fp64 (the kernel: fp64 per lane and across workgroups; fp32 inside pass B's MFMA tile).
+        z  = fma(y, scale, shift) from the forward's fp32 scale / shift;  g = dout / 16 * (z < 0 ? 0.2 : 1);  yh = (y - mean) rstd
+        pass A, per cloud:  dbeta_c = sum g,  dgamma_c = sum g yh;  per group  S1 = sum_c gamma_c dbeta_c,  S2 = sum_c gamma_c dgamma_c
+        pass B:             dy = rstd (g gamma_c - S1 / m - yh S2 / m),  m = 3 N 16;  dW[c][q] = sum dy x[q],  db[c] = sum dy
+    per_cloud: also return every cloud's own (dbeta, dgamma) [B, 12] each - what the parameter gradients add up in cloud order."""
+    x, y, sc, sh, mean, rstd = _pre_rows(rows, neigh, W, b, gamma, beta)
+    B, N = y.shape[:2]
+    gamma32 = np.asarray(gamma, F)
+    z = _fma(y, np.broadcast_to(sc[:, None, None, :], y.shape), np.broadcast_to(sh[:, None, None, :], y.shape))
+    gd = (np.asarray(dout, F) * F(0.0625))[:, :, None, :]
+    g = np.where(z < 0, F(0.2) * gd, gd).astype(F)                                    # [B, N, 16, 12]
+    mean32 = np.repeat(mean.astype(F), 3, 1)[:, None, None, :]
+    rstd32 = np.repeat(rstd.astype(F), 3, 1)[:, None, None, :]
+    yh = ((y - mean32) * rstd32).astype(F)
+    dbeta_c = g.astype(np.float64).sum((1, 2))                                        # [B, 12]
+    dgamma_c = (g.astype(np.float64) * yh.astype(np.float64)).sum((1, 2))
+    m = 3.0 * N * 16.0
+    S1 = (gamma32.astype(np.float64)[None] * dbeta_c).reshape(B, 4, 3).sum(2) / m     # [B, 4]
+    S2 = (gamma32.astype(np.float64)[None] * dgamma_c).reshape(B, 4, 3).sum(2) / m
+    gm1 = np.repeat(S1.astype(F), 3, 1)[:, None, None, :]
+    gm2 = np.repeat(S2.astype(F), 3, 1)[:, None, None, :]
+    dy = (rstd32 * (((g * gamma32) - gm1) - yh * gm2)).astype(F)
+    dW = np.einsum("bnkc,bnkq->cq", dy.astype(np.float64), x.astype(np.float64))
+    db = dy.astype(np.float64).sum((0, 1, 2))
+    out = (dW, db, dgamma_c.sum(0), dbeta_c.sum(0))
+    return out + (dbeta_c, dgamma_c) if per_cloud else out
 
 
 def estimate_normals(points: np.ndarray, neigh: np.ndarray, viewpoint=(0.0, 0.0, 0.0)) -> Tuple[np.ndarray, np.ndarray]:

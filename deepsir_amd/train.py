@@ -125,6 +125,42 @@ class _Ops:
                      int(act), _ptr(dy), _ptr(dgamma), _ptr(dbeta), _ptr(sc))
         return dy
 
+    # ---- the point-pair-feature input layer of use_ppf (csrc/ppf.hip)
+    def _ppf_check(self, op: str, rows: torch.Tensor, neigh: torch.Tensor, nbytes: int) -> None:
+        """The shapes both front-end operators take; nbytes: the library's scratch size for them, 0 when it refuses the shape."""
+        if rows.dim() != 3 or rows.shape[2] < 6 or tuple(neigh.shape) != (rows.shape[0], rows.shape[1], K_NN):
+            raise ValueError(f"{op}: rows {tuple(rows.shape)} / neigh {tuple(neigh.shape)}: [clouds,n,>=6] and [clouds,n,{K_NN}] expected")
+        if rows.dtype != torch.float32 or neigh.dtype != torch.int32 or not rows.is_contiguous() or not neigh.is_contiguous():
+            raise ValueError(f"{op}: rows must be contiguous float32 and neigh contiguous int32")
+        if nbytes == 0:
+            raise ValueError(f"{op}: the library refuses {rows.shape[0]} clouds of {rows.shape[1]} points (dsir_t_ppf_*_scratch returned 0: too many points per cloud)")
+
+    def ppf_fwd(self, rows: torch.Tensor, neigh: torch.Tensor, w, bias, gamma, beta):
+        """rows [clouds][n][>= 6] = xyz + normal, neigh [clouds][n][16] (level 0), both contiguous -> (out [clouds][n][12] - the bits of
+        ``Engine.ppf_pre`` -, saved [clouds][32]: what ``ppf_bwd`` rebuilds the rows' normalised values from)."""
+        nb = int(self.lib.dsir_t_ppf_fwd_scratch(rows.shape[0], rows.shape[1])) if rows.dim() == 3 else 0
+        self._ppf_check("ppf_fwd", rows, neigh, nb)
+        clouds, n, stride = rows.shape
+        out, saved = self.empty(clouds, n, 12), self.empty(clouds, 32)
+        self._launch("dsir_t_ppf_fwd", _ptr(rows), stride, _ptr(neigh), clouds, n, _ptr(w), _ptr(bias), _ptr(gamma), _ptr(beta), _ptr(out),
+                     _ptr(saved), _ptr(self.scratch(nb)))
+        return out, saved
+
+    def ppf_bwd(self, rows, neigh, w, bias, gamma, beta, saved, dout, dw, db, dgamma, dbeta) -> torch.Tensor:
+        """Accumulates the four parameter gradients of the layer from dout [clouds][n][12] (contiguous).  -> every cloud's own
+        {d beta[12], d gamma[12]} as float64 [clouds][24]: a view of the scratch buffer, valid until the next operator that takes scratch."""
+        nb = int(self.lib.dsir_t_ppf_bwd_scratch(rows.shape[0], rows.shape[1])) if rows.dim() == 3 else 0
+        self._ppf_check("ppf_bwd", rows, neigh, nb)
+        clouds, n, stride = rows.shape
+        if tuple(dout.shape) != (clouds, n, 12) or dout.dtype != torch.float32 or not dout.is_contiguous():
+            raise ValueError(f"ppf_bwd: dout {tuple(dout.shape)}: contiguous float32 [{clouds},{n},12] expected")
+        if tuple(saved.shape) != (clouds, 32):
+            raise ValueError(f"ppf_bwd: saved {tuple(saved.shape)}: the forward's [{clouds},32] expected")
+        sc = self.scratch(nb)                                 # doubles: the buffer is a torch allocation, aligned far beyond 8 bytes
+        self._launch("dsir_t_ppf_bwd", _ptr(rows), stride, _ptr(neigh), clouds, n, _ptr(w), _ptr(bias), _ptr(gamma), _ptr(beta), _ptr(saved),
+                     _ptr(dout), _ptr(dw), _ptr(db), _ptr(dgamma), _ptr(dbeta), _ptr(sc))
+        return sc[:clouds * 48].view(torch.float64).view(clouds, 24)
+
     def bn_running(self, stats: torch.Tensor, channels: int, rows: int, mean: torch.Tensor, var: torch.Tensor) -> None:
         """BatchNorm1d's running statistics from the batch statistics of ``gn_fwd`` (one cloud, one group per channel), momentum 0.1."""
         self._launch("dsir_t_bn_running", _ptr(stats), channels, rows, 0.1, _ptr(mean), _ptr(var))
@@ -541,8 +577,6 @@ class RandlaTrainer(_ParamStore):
 
     def __init__(self, cfg: NetConfig, state_dict: Dict[str, "np.ndarray | torch.Tensor"], prefix: str = "inlier_model", feat_in: int = 6,
                  num_classes: int = 1, device: "str | torch.device" = "cuda:0"):
-        if cfg.use_ppf:      # the taped forward below is the 8-channel input layer: never run it on a 12-channel checkpoint
-            raise NotImplementedError("RandlaTrainer: training with use_ppf=True is not built (the point-pair-feature input layer is inference only)")
         self.cfg, self.prefix, self.feat_in, self.num_classes = cfg, prefix, feat_in, num_classes
         self.device = torch.device(device)
         self.ops = _Ops(self.device)
@@ -568,6 +602,21 @@ class RandlaTrainer(_ParamStore):
                              L.act, self.grads[name + ".norm.weight"], self.grads[name + ".norm.bias"])
         self.ops.conv_dw(dy, L.x, self.grads[name + ".conv.weight"], self.grads[name + ".conv.bias"])
         return self.ops.conv_dx(dy, w) if need_dx else None
+
+    def _ppf(self, tape: RandlaTape, name: str, rows: torch.Tensor, neigh: torch.Tensor) -> torch.Tensor:
+        """use_ppf's input layer (RandLANet.py:324-332): feat_grouping + mlp_pre + the mean over the neighbours, nothing of n x 16 kept."""
+        rows = rows.contiguous()
+        out, saved = self.ops.ppf_fwd(rows, neigh, self.params[name + ".conv.weight"], self.params[name + ".conv.bias"],
+                                      self.params[name + ".norm.weight"], self.params[name + ".norm.bias"])
+        tape.misc[name] = (rows, neigh, saved)
+        return out
+
+    def _ppf_bwd(self, tape: RandlaTape, name: str, dout: torch.Tensor) -> None:
+        """The rows are data (the loader's, or [moved src ; matched ref] under R_t.detach()): four parameter gradients, nothing further."""
+        rows, neigh, saved = tape.misc[name]
+        self.ops.ppf_bwd(rows, neigh, self.params[name + ".conv.weight"], self.params[name + ".conv.bias"], self.params[name + ".norm.weight"],
+                         self.params[name + ".norm.bias"], saved, dout.contiguous(), self.grads[name + ".conv.weight"],
+                         self.grads[name + ".conv.bias"], self.grads[name + ".norm.weight"], self.grads[name + ".norm.bias"])
 
     def _att(self, tape: RandlaTape, name: str, cat: torch.Tensor, clouds: int, n: int) -> torch.Tensor:
         """Att_pooling (RandLANet.py:140-157); cat [clouds * n * 16][d]."""
@@ -668,7 +717,9 @@ class RandlaTrainer(_ParamStore):
         """RandLA.forward in TRAINING mode (RandLANet.py:311-372; train.py:379 ``my_model.train()``): GroupNorm as always,
         the two BatchNorm1d of ``fc_label`` on batch statistics (running statistics updated with momentum 0.1), Dropout(0.5)
         with ``dropout_mask`` ([clouds][N][64] uint8 keep flags; None = keep everything, i.e. dropout off).
-        features [clouds][N][feat_in]; pyramids as ``Engine.knn_pyramid`` returns them (int32).
+        features [clouds][N][feat_in] - with ``cfg.use_ppf`` rows of xyz + normal, [clouds][N][>= 6], for the point-pair-feature layer
+        (which runs anew in every pass, also under ``shared``: its rows move with the pose); pyramids as ``Engine.knn_pyramid``
+        returns them (int32).
         shared: a dict the caller keeps across SEVERAL forward passes on the SAME pyramid with the SAME weights (the
         registration iterations of one `align` step, model.py:575: the inlier model always runs on the src pyramid): the
         position-encoding branch of every level - lfa.mlp1 on the relative position code and lfa.mlp2 on top, the two
@@ -694,7 +745,10 @@ class RandlaTrainer(_ParamStore):
                    "interp": [interp_idx[:, off[l]:off[l + 1], 0].contiguous() for l in range(L)]}
             if shared is not None:
                 shared["_pyr"] = pyr
-        x = self._mlp2d(tape, pf + ".mlp_pre", features.reshape(clouds * N, cin).contiguous(), clouds).reshape(clouds, N, -1)
+        if self.cfg.use_ppf:
+            x = self._ppf(tape, pf + ".mlp_pre", features, pyr["neigh"][0])
+        else:
+            x = self._mlp2d(tape, pf + ".mlp_pre", features.reshape(clouds * N, cin).contiguous(), clouds).reshape(clouds, N, -1)
         skips: List[torch.Tensor] = []
         args: List[torch.Tensor] = []
         for l in range(L):
@@ -762,6 +816,8 @@ class RandlaTrainer(_ParamStore):
             dfeat = self._res_block_bwd(tape, f"{pf}.dilated_res_blocks.{l}", denc, need_dx=True, shared=shared)
             if l > 0:
                 dskips[l] = o.acc(dskips[l], dfeat).reshape(shapes[l])
+            elif self.cfg.use_ppf:
+                self._ppf_bwd(tape, pf + ".mlp_pre", dfeat)
             else:
                 self._mlp2d_bwd(tape, pf + ".mlp_pre", dfeat.reshape(clouds * N, -1), need_dx=False)
 

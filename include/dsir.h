@@ -67,7 +67,8 @@ int dsir_create(int device, const dsir_cfg* cfg, dsir_ctx** out);
  * mlp_pre is conv 10 -> 12 on feat_grouping's code (:110-137) and level 0 takes 12 channels (the state dict's shapes follow:
  * mlp_pre.conv.weight [12,10,1,1], dilated_res_blocks.0.mlp1 / .mlp_skip 12 inputs).  cfg.feat_len is then the number of
  * columns of a point row: xyz, the normal, anything more is ignored; fewer than 6 is an error (the reference's assertion,
- * RandLANet.py:325 "feature dimension error").  Inference only: the training operators (dsir_train.h) know no such layer. */
+ * RandLANet.py:325 "feature dimension error").  Training: dsir_t_ppf_fwd / dsir_t_ppf_bwd (dsir_train.h) are the layer's taped
+ * forward - the same bits as dsir_ppf_pre - and the backward of its four parameter tensors. */
 #define DSIR_FLAG_PPF 1
 int dsir_create_ex(int device, const dsir_cfg* cfg, int flags, dsir_ctx** out);
 void dsir_destroy(dsir_ctx* ctx);

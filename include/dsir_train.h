@@ -114,6 +114,29 @@ int dsir_t_det_des_loss(void* stream, const float* feat_ref, const float* feat_s
                         const float* score_ref, const float* transform_gt, int pairs, int M, int C, float thres_radius, float det_loss_weight,
                         double* out, float* d_feat_ref, float* d_feat_src, void* scratch);
 
+/* The point-pair-feature input layer of args.use_ppf in training mode (RandLANet.py:110-137 feat_grouping, :324-332: mlp_pre =
+ * Conv2d 10 -> 12 + bias, GroupNorm(4, 12), LeakyReLU(0.2), then the mean over the 16 neighbours; network/matchnet.py:11-30 angle).
+ * rows [clouds][n][stride >= 6]: columns 0 - 2 the point, 3 - 5 its normal (the inlier model: the matched reference point,
+ * network/model.py:574-590); neigh [clouds][n][16] the level-0 neighbour lists; W [12][10], b, gamma, beta [12]: mlp_pre.conv.weight /
+ * .bias, mlp_pre.norm.weight / .bias.  out [clouds][n][12]: the same bits as dsir_ppf_pre (include/dsir.h) on the same inputs - the
+ * two launches are the same (csrc/ppf.hip states the arithmetic).  saved [clouds][32] is kept for the backward: the fp32 scale[12] /
+ * shift[12] the layer applied and {mean, rstd} of the 4 groups; nothing of size n x 16 is stored.
+ * scratch: dsir_t_ppf_fwd_scratch(clouds, n) bytes (0: the shape is refused - more than 4096 x 64 points per cloud). */
+size_t dsir_t_ppf_fwd_scratch(int clouds, int n);
+int dsir_t_ppf_fwd(void* stream, const float* rows, int stride, const int32_t* neigh, int clouds, int n, const float* W, const float* b,
+                   const float* gamma, const float* beta, float* out, float* saved, void* scratch);
+/* Its backward (what autograd does for the four parameters of RandLANet.py:251-254's mlp_pre; the rows are data in every pipeline -
+ * the loader's points and normals, or [moved src ; matched ref] under R_t.detach() - so nothing flows to them).  The SAME rows, neigh
+ * and parameters as the forward, its `saved`, dOut [clouds][n][12] = d loss / d out.  dW [12][10], db, dgamma, dbeta [12] ACCUMULATE.
+ * Every row is rebuilt twice (pass A: d gamma, d beta and the group sums; pass B: dW, db) with the forward's bits; the sums take a
+ * fixed partition (64 points per workgroup) and order, fp64 partials, no float atomics: the same bytes on every run.
+ * scratch: dsir_t_ppf_bwd_scratch(clouds, n) bytes; after the call it begins with [clouds][24] doubles, every cloud's own
+ * {d beta[12], d gamma[12]} - the same bytes for a cloud alone or inside a batch; the parameter gradients add them in cloud order. */
+size_t dsir_t_ppf_bwd_scratch(int clouds, int n);
+int dsir_t_ppf_bwd(void* stream, const float* rows, int stride, const int32_t* neigh, int clouds, int n, const float* W, const float* b,
+                   const float* gamma, const float* beta, const float* saved, const float* dOut, float* dW, float* db, float* dgamma,
+                   float* dbeta, void* scratch);
+
 /* F.leaky_relu(a + b, 0.2) (RandLANet.py:230) and its backward (d a = d b = dOut * slope(out)). */
 int dsir_t_add_leaky_fwd(void* stream, const float* a, const float* b, int64_t n, float* out);
 int dsir_t_add_leaky_bwd(void* stream, const float* dOut, const float* out, int64_t n, float* d);

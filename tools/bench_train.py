@@ -1,4 +1,4 @@
-"""tools/bench_train.py [--pairs P] [--points N] [--iters I] [--steps K]: time of one `align` training step of the inlier model
+"""tools/bench_train.py [--pairs P] [--points N] [--iters I] [--steps K] [--use-ppf]: time of one `align` training step of the inlier model
 (deepsir_amd.train.train_step_align: 5 training-mode forwards, loss + gradient, 5 backwards, Adam) on one GPU; the
 inference half (Engine.register) is timed separately.  Prints one JSON line.
 
@@ -6,7 +6,9 @@ inference half (Engine.register) is timed separately.  Prints one JSON line.
 already on the device - the step with no target work at all; host: find_correct_correspondence on the host against the batch's
 match lists (copy of idx down, np.isin per pair and iteration, copy up); matches: the same lists hashed, sorted and searched on
 the device (deepsir_amd.train.inlier_targets); radius: no list, the distance test on the device.  The lists themselves come from
-Engine.radius_matches with --radius (default 0.09 for --shape 3dmatch, 0.9 for kitti), once, outside the timed steps."""
+Engine.radius_matches with --radius (default 0.09 for --shape 3dmatch, 0.9 for kitti), once, outside the timed steps.
+
+--use-ppf: the networks of args.use_ppf (point rows of xyz + seeded unit normals; the taped point-pair-feature front end, csrc/ppf.hip)."""
 import argparse
 import json
 import os
@@ -34,13 +36,20 @@ ap.add_argument("--eager", action="store_true", help="launch every operator from
 ap.add_argument("--targets", choices=("random", "host", "matches", "radius"), default="random", help="source of the confidence targets in the timed step")
 ap.add_argument("--shape", choices=("3dmatch", "kitti"), default="3dmatch", help="extent of the synthetic clouds")
 ap.add_argument("--radius", type=float, default=None, help="match radius (default 0.09 for 3dmatch, 0.9 for kitti)")
+ap.add_argument("--use-ppf", action="store_true", help="train the use_ppf networks (rows of xyz + normal)")
 a = ap.parse_args()
-cfg = NetConfig(feat_len=3)
+cfg = NetConfig(feat_len=6, use_ppf=True) if a.use_ppf else NetConfig(feat_len=3)
 sd = generate_state_dict(cfg, 3, "plain")
 dev = torch.device("cuda:0")
 eng = Engine(cfg, max_points=a.points, max_pairs=a.pairs)
 eng.load_state_dict(sd)
 raws = [make_pair(a.points, 100 + b, 3, a.shape) for b in range(a.pairs)]
+if a.use_ppf:
+    rng = np.random.Generator(np.random.Philox(key=0x99F))
+    for r in raws:
+        for k in ("points_src", "points_ref"):
+            nrm = rng.standard_normal(r[k].shape)
+            r[k] = np.concatenate([r[k], nrm / np.linalg.norm(nrm, axis=2, keepdims=True)], 2).astype(np.float32)
 src = torch.from_numpy(np.concatenate([r["points_src"] for r in raws])).to(dev)
 ref = torch.from_numpy(np.concatenate([r["points_ref"] for r in raws])).to(dev)
 gt = torch.from_numpy(np.concatenate([r["transform_gt"] for r in raws]).astype(np.float32)).to(dev)
@@ -90,6 +99,8 @@ for s in range(a.steps + 2):
 extra = {} if a.targets == "random" else {"targets": a.targets, "shape": a.shape, "radius": radius}
 if matches is not None:
     extra["matches_per_point"] = round(sum(len(m) for m in matches) / (a.pairs * a.points), 2)
+if a.use_ppf:
+    extra["use_ppf"] = True
 print(json.dumps({"mode": "whole network in training mode (eager)" if a.full else "eager" if a.eager else "hipGraph replay", "pairs": a.pairs, "points": a.points, "iters": a.iters, "inference_ms": round(1e3 * float(np.median(t_inf)), 2),
                   "train_step_ms": round(1e3 * float(np.median(t_train)), 2),
                   "train_pairs_per_s": round(a.pairs / float(np.median(t_train)), 2), "losses": [round(l, 5) for l in losses],
