@@ -45,7 +45,7 @@ struct Seg {
   int64_t uv_cloud_stride = 0;
   const float* dist = nullptr;      // [clouds][n * 16]
   int64_t dist_cloud_stride = 0;
-  const float* w8 = nullptr;        // [C][8] folded weights {a, ux, uy, uz, vx, vy, vz, b} (engine.hip, up_lse_uv)
+  const float* w8 = nullptr;        // [C][8] folded weights {a, ux, uy, uz, vx, vy, vz, b} (weights.hip, up_lse_uv)
 };
 
 enum AMode { A_SEGS = 0, A_LSE = 1 };
@@ -109,7 +109,7 @@ struct GemmArgs {
 // GroupNorm statistics meet across workgroups in exact atomics (device_utils.h, gn_block_commit): the proof that every partial
 // total stays an integer below 2^53 holds for at most kGnMaxContrib contributions per (cloud, group) statistic.  Every launcher
 // that commits statistics states how many workgroups of ONE cloud add into one statistic (a function of the layer's shape alone);
-// dsir_create bounds max_points by the largest of them over the schedule (engine.hip, gn_max_contributions).
+// dsir_create bounds max_points by the largest of them over the schedule (schedule.hip, gn_max_contributions).
 constexpr int kGnMaxContrib = 1 << 12;
 int pw_stream_gn_contributions(int M, int Cout);        // pw_stream.hip: the VIRTUAL workgroups of a column block
 int pw_tile_gn_contributions(int M, int Cout, int groups);   // pw_tile.hip: row blocks x column blocks a group spans

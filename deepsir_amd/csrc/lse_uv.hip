@@ -5,7 +5,7 @@
 // pair.  Nine of the ten inputs are linear in the two points, so the raw output splits by linearity into per-POINT parts:
 //     enc_raw[i, k][c] = a[c] dist(i, j) + U[j][c] + V[i][c],      j = neigh[i][k],
 //     a = W[:, 0],   U[j] = (W[:, 1:4] + W[:, 7:10]) p_j,   V[i] = (W[:, 4:7] - W[:, 1:4]) p_i + bias
-// (the folded weights are made once at weight load, engine.hip::up_lse_uv).  Up to round 3 the layer's output - 16 rows per
+// (the folded weights are made once at weight load, weights.hip::up_lse_uv).  Up to round 3 the layer's output - 16 rows per
 // point, 2.56 MB per cloud at each of the two levels - was written once and re-read by the attentive pooling and by lfa.mlp2 in
 // every pass: ~90 MB of the 432 MB a registration moved through HBM.  Now the consumers rebuild a row from dist (4 bytes) and
 // two gathered per-point rows that live in L2 (att_pool.hip, pw_stream.hip loader S_UV): two instructions per channel.

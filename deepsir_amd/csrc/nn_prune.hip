@@ -127,7 +127,7 @@ __global__ __launch_bounds__(256) void tile_stats_kernel(const float* __restrict
 
 // DOMAIN of the margins below (2e-5 (1 + |a|^2 + |b_prev|^2) on T, 1e-5 (1 + |a|^2 + |c|^2) on L): they cover the fp32 evaluation error
 // of a SKIPPED column only while that column's own |b|^2 is of the order of the norms they are built from.  The pruned search is
-// reachable from dsir_register alone (engine.hip: `prune` requires the registration's own descriptors), and those are L2-normalised by
+// reachable from dsir_register alone (search_plan.h: the pruned mode requires the registration's own descriptors), and those are L2-normalised by
 // the aggregation chain (model.py:232-233: |a| = |b| = 1 up to rounding); it is not offered to caller-supplied descriptors
 // (dsir_nn_match searches exhaustively or through the unpruned screening, whose bound carries every column's own norm).
 // per src row: the sort key of the row order (its nearest-centroid tile) and the upper bound from the previous iteration's match,

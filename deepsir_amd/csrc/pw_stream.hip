@@ -337,7 +337,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(pw_stream_m
         for (int r = 0; r < 4; ++r) {
           const float* gp = p.g + cloud * p.g_cloud_stride;                 // wave-uniform bases
           const float* fp = p.fseg.x + cloud * p.fseg.cloud_stride;
-          // G is stored in this kernel's order (engine.hip, up_fc_g): the block's column of lane fr in tiles 0..3 is one float4
+          // G is stored in this kernel's order (weights.hip, up_fc_g): the block's column of lane fr in tiles 0..3 is one float4
           const uint32_t go = 4u * ((uint32_t)gi_all[d][r] * (uint32_t)p.Cout + (uint32_t)(n0 + 4 * fr));
           const uint32_t fo = 4u * ((uint32_t)gi_all[d][r] * (uint32_t)p.fseg.ld + (uint32_t)fr);
           static_assert(EPI != EPI_ATT2 || NT == 4, "one float4 of G per gathered row");

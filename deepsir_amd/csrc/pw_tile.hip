@@ -88,7 +88,7 @@ bool seg_ok(const Seg& s) {
 
 }  // namespace
 
-// does launch_pw_tile hand this layer to pw_tile_small_kernel?  (engine.hip asks before it fuses two layers into one launch)
+// does launch_pw_tile hand this layer to pw_tile_small_kernel?  (schedule.hip asks before it fuses two layers into one launch)
 bool pw_tile_small_serves(const GemmArgs& a) {
   static const int min_cout_h = (int)tuning_int("DSIR_TILE_MIN_COUT", 32);
   static const int small_m = (int)tuning_int("DSIR_TILE_SMALL_M", 320);

@@ -1,5 +1,5 @@
 // Training operators (include/dsir_train.h): forward-with-saved-activations and backward of the ATen calls RandLA.forward
-// makes (reference network/RandLANet.py:140-230, :311-408), point-major fp32.  The inference engine (engine.hip) fuses and
+// makes (reference network/RandLANet.py:140-230, :311-408), point-major fp32.  The inference engine (schedule.hip) fuses and
 // never materialises most of these tensors; a training step needs them all, so this path is layer by layer: one
 // exact-fp32 MFMA GEMM for every 1x1 convolution (forward, d input, d weight), and row-streaming kernels around it.
 #include <hip/hip_runtime.h>

@@ -165,3 +165,17 @@ def test_groupnorm_exactness_bound_limits_max_points():
     csrc = os.path.join(ROOT, "deepsir_amd", "csrc")
     assert "stream_blocks(a.M, gy, big)" in open(os.path.join(csrc, "pw_stream.hip")).read()
     assert "b.vgrid = lse_uv_gn_contributions(a.n, a.KH);" in open(os.path.join(csrc, "lse_uv.hip")).read()
+
+
+@pytest.mark.parametrize("name", ["search_plan_check", "ppf_plan_check"])
+def test_host_only_plan_checks(name, tmp_path):
+    """csrc/search_plan.h (which arg-min path a registration takes, the operand sizes) and csrc/ppf_plan.h hold no device code: their
+    stand-alone checks (tools/*_plan_check.cpp; the sanitizer command is in each file's header) build as plain host C++ and pass."""
+    import subprocess
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    exe = str(tmp_path / name)
+    r = subprocess.run([hipcc, "-x", "c++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "deepsir_amd", "csrc"),
+                        os.path.join(ROOT, "tools", name + ".cpp"), "-o", exe], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and "_plan: " in r.stdout, r.stdout + r.stderr

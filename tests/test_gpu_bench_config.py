@@ -1,5 +1,5 @@
 """GPU parity on the configuration bench.py measures: many 5000-point pairs per call through
-``EnginePool`` on 4 HIP streams, large enough per engine (P*J*K >= 2e8, csrc/engine.hip) for the fp16-screened
+``EnginePool`` on 4 HIP streams, large enough per engine (P*J*K >= 2e8, csrc/search_plan.h) for the fp16-screened
 arg-min (csrc/nn_screen.hip) to run - the path every golden / oracle test of tests/test_gpu_parity.py misses
 because one or two pairs take the exhaustive kernel.  Checked directly against the CPU oracle, not against
 another HIP kernel.  Robustness of the same path to non-finite input, bad caller indices and weight reloads
@@ -206,7 +206,7 @@ def test_graph_replay_after_weight_reload():
 
 def test_hoisted_loop_invariants_are_bit_identical(tmp_path):
     """The loop invariants hoisted out of the registration iterations - the inlier model's position-encoding layers and the
-    enc half of its attention scores (EncCache, csrc/engine.hip) - change nothing: recomputing them every iteration
+    enc half of its attention scores (EncCache, csrc/schedule.hip) - change nothing: recomputing them every iteration
     (DSIR_NO_HOIST), or only the score halves (DSIR_NO_S2), gives the same bits.  Switches are read once per process."""
     import os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

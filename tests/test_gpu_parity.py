@@ -768,7 +768,7 @@ def test_screened_argmin_equals_exhaustive(kind):
 
 
 def test_register_screened_equals_exhaustive(tmp_path):
-    """A whole registration large enough for the screened arg-min (P*J*K >= 2e8, csrc/engine.hip) must produce the same
+    """A whole registration large enough for the screened arg-min (P*J*K >= 2e8, csrc/search_plan.h) must produce the same
     bits - correspondences, inlier logits, transforms - as the same registration with the exhaustive exact-fp32 kernel
     (DSIR_NO_SCREEN=1; the switch is read once per process, hence two child processes)."""
     import subprocess, sys
