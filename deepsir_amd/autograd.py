@@ -58,7 +58,7 @@ def run_taped(params: Sequence[torch.nn.Parameter], run: Callable, n_out: int):
 
 # ----------------------------------------------------------------------------------------------------------- align
 class _AlignLoss(torch.autograd.Function):
-    """total = sum_i discount^(n - 1 - i) (dist_i + outlier_i) of ScanAlignmentLoss (reduction='mean'), with d total / d logits."""
+    """total = sum_i discount^(n - 1 - i) (dist_i + outlier_i + poseError_i) of ScanAlignmentLoss (reduction='mean'), with d total / d logits."""
 
     @staticmethod
     def forward(ctx, logits, engine, pt_src, pt_ref, idx, labels, transform_gt, kw):
@@ -75,7 +75,8 @@ class _AlignLoss(torch.autograd.Function):
 
 
 class ScanAlignmentLoss:
-    """``my_model.loss_align_fun`` (reference network/loss.py:705-851; wt_pose_loss = 0, its default).  data: the endpoints of an
+    """``my_model.loss_align_fun`` (reference network/loss.py:705-851; all three terms: wt_pose_loss > 0 adds the keys poseError_i, as
+    in the reference, whose default is 0).  data: the endpoints of an
     `align` forward plus 'transform_gt' [B,3,4] and optionally 'matches' (per pair an int [n',2] array, as the reference's loader
     gives, or a ``train.MatchKeys``) for the correspondence-confidence term; without a list, 'match_radius' in data or ``match_radius=``
     here (or ``args.match_radius``) gives the same 0/1 targets from the geometry: |T_gt src_j - ref_idx[j]| < radius.  Either way
@@ -94,8 +95,6 @@ class ScanAlignmentLoss:
         self.discount_factor = float(getattr(args, "loss_discount_factor", 0.5))
         if self.loss_type not in ("mae", "mse"):
             raise AssertionError("loss_type must be 'mae' or 'mse' (reference loss.py:721)")
-        if self.wt_pose_loss > 0:
-            raise NotImplementedError("wt_pose_loss > 0 (off by default, arguments.py:57) is outside the accelerated path")
 
     def __call__(self, data: Dict, reduction=None):
         from .train import _Ops, inlier_targets
@@ -123,7 +122,7 @@ class ScanAlignmentLoss:
             labels = inlier_targets(self._ops, idx, J, data.get("matches"), radius, pt_src, pt_ref, T_gt)
         eng = tr["engine"] if tr is not None else self._net._ensure_engine(max(J, pt_ref.shape[1]), B)
         kw = dict(loss_type=self.loss_type, wt_ptDist_loss=self.wt_ptDist_loss, wt_inlier_loss=self.wt_inlier_loss,
-                  loss_discount_factor=self.discount_factor)
+                  loss_discount_factor=self.discount_factor, wt_pose_loss=self.wt_pose_loss)
         if reduction == "none":
             out = eng.align_loss_backward(pt_src, pt_ref, idx, logits.detach().contiguous(), labels, T_gt, per_pair=True, **kw)
             return {k: torch.from_numpy(np.asarray(v, np.float32)).to(dev) for k, v in out["losses_per_pair"].items()}

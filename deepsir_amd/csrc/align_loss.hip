@@ -18,6 +18,14 @@
 //   weights    dL/dwn_j = (s_j - c_s)^T (dL/dH) (t_j - c_t) + dL/dc_s . s_j + dL/dc_t . t_j,  then the normalisation and
 //              sigmoid' = w (1 - w);  BCE: discount_i wt (w - y) / (P J)
 // Pinned by tests/golden/align_loss_cases.npz (the imported reference's autograd, oracle/gen_golden_align_loss.py).
+//
+// The pose-error term (loss.py:830-842, wt_pose_loss > 0; off by default) reads the same Tc_i and T_gt:
+//   s_i = (<R_gt, Rc_i>_F - 1) / 2,  err_r = acos(clamp(s_i, -1, 1)),  err_t = |t_gt - tc_i|,  poseError_i = wt (mean err_r + mean err_t)
+//   dL/dRc_i += c_i (-1 / (2 sqrt(1 - s_i^2))) R_gt,   dL/dtc_i += c_i (tc_i - t_gt) / |tc_i - t_gt|,   c_i = discount_i wt / P,
+// added to dL/dTc_i before the concatenate step.  Corner rules (include/dsir.h): err_t == 0 gives no translation addend (torch.norm's
+// subgradient); 1 - s_i^2 <= 0 gives no rotation addend (the reference's fp32 autograd is inf / NaN there).  One lane, fp64, behind
+// a branch on the argument that every lane takes alike: with wt_pose == 0 the first two terms run exactly as without the term.
+// Pinned by tests/golden/align_pose_loss_cases.npz (tools/gen_golden_align_pose_loss.py).
 #include "kernels.h"
 #include "device_utils.h"
 #include "svd3.h"
@@ -36,10 +44,10 @@ struct AlignLossArgs {
   const float* logits; const float* labels;   // [n_iter][P][J]; labels may be nullptr (no confidence term)
   const float* T_gt;                          // [P][3][4]
   int P, J, K, n_iter, mse;
-  float wt_pt, wt_in, discount;
+  float wt_pt, wt_in, discount, wt_pose;
   float* T_out;                               // [P][n_iter][3][4] or nullptr
-  double* losses;                             // [n_iter][2] (point-distance term, confidence term), summed over the pairs by align_loss_reduce_kernel
-  double* loss_part;                          // [P][n_iter][2] every pair's terms (nullptr: no losses wanted)
+  double* losses;                             // [n_iter][3] (point-distance term, confidence term, pose-error term), summed over the pairs by align_loss_reduce_kernel
+  double* loss_part;                          // [P][n_iter][3] every pair's terms (nullptr: no losses wanted)
   float* grad;                                // [n_iter][P][J]
 };
 
@@ -51,6 +59,21 @@ struct IterState {
   double den, sw;              // sum |w| + 1e-16, sum wn
   double G[12];                // sum_j dl/dpred_j [p_j; 1]^T (row major 3x4), unscaled
 };
+
+// err_r, err_t of one pair and iteration, and the two addends' factors: dL/dRc += c gr R_gt, dL/dtc += c gt[] (see the header).
+__device__ inline void pose_error(const IterState& q, const float* Tg, double& err_r, double& err_t, double& gr, double (&gt)[3]) {
+  double tr = 0.0, d2 = 0.0;
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) tr += (double)Tg[r * 4 + c] * q.Rc[r][c];
+    gt[r] = q.tc[r] - (double)Tg[r * 4 + 3];
+    d2 += gt[r] * gt[r];
+  }
+  const double s = 0.5 * (tr - 1.0), om = 1.0 - s * s;
+  err_r = acos(fmin(fmax(s, -1.0), 1.0));
+  gr = om > 0.0 ? -0.5 / sqrt(om) : 0.0;
+  err_t = sqrt(d2);
+  for (int r = 0; r < 3; ++r) gt[r] = err_t > 0.0 ? gt[r] / err_t : 0.0;
+}
 
 __global__ __launch_bounds__(AL_THREADS) void align_loss_kernel(AlignLossArgs a) {
   __shared__ double sh[AL_WAVES * 14 + 14];
@@ -175,8 +198,16 @@ __global__ __launch_bounds__(AL_THREADS) void align_loss_kernel(AlignLossArgs a)
     if (tid == 0) {
       for (int k = 0; k < 12; ++k) st[it].G[k] = v14[k];
       if (a.loss_part) {      // this pair's terms; align_loss_reduce_kernel adds the pairs in pair order (no atomics: same bits every run)
-        a.loss_part[((int64_t)pair * a.n_iter + it) * 2] = a.wt_pt > 0.f ? v14[12] * inv_pts : 0.0;
-        a.loss_part[((int64_t)pair * a.n_iter + it) * 2 + 1] = (a.labels && a.wt_in > 0.f) ? v14[13] * inv_rows * (double)a.wt_in : 0.0;
+        double* lp = a.loss_part + ((int64_t)pair * a.n_iter + it) * 3;
+        lp[0] = a.wt_pt > 0.f ? v14[12] * inv_pts : 0.0;
+        lp[1] = (a.labels && a.wt_in > 0.f) ? v14[13] * inv_rows * (double)a.wt_in : 0.0;
+        double pose = 0.0;
+        if (a.wt_pose > 0.f) {      // this pair's share of wt (mean err_r + mean err_t)
+          double er, et, gr, gt[3];
+          pose_error(st[it], Tg, er, et, gr, gt);
+          pose = (er + et) * (double)a.wt_pose / (double)a.P;
+        }
+        lp[2] = pose;
       }
     }
     __syncthreads();
@@ -193,6 +224,15 @@ __global__ __launch_bounds__(AL_THREADS) void align_loss_kernel(AlignLossArgs a)
       const double sc = a.wt_pt > 0.f ? disc * inv_pts : 0.0;
       for (int r = 0; r < 3; ++r)
         for (int c = 0; c < 4; ++c) G[r][c] = sc * q.G[r * 4 + c] + carry[r * 4 + c];
+      if (a.wt_pose > 0.f) {
+        double er, et, gr, gt[3];
+        pose_error(q, Tg, er, et, gr, gt);
+        const double ci = disc * (double)a.wt_pose / (double)a.P;
+        for (int r = 0; r < 3; ++r) {
+          for (int c = 0; c < 3; ++c) G[r][c] += ci * gr * (double)Tg[r * 4 + c];
+          G[r][3] += ci * gt[r];
+        }
+      }
       double gR[3][3], gt[3];
       if (it == 0) {
         for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) gR[r][c] = G[r][c]; gt[r] = G[r][3]; }
@@ -279,11 +319,11 @@ __global__ __launch_bounds__(AL_THREADS) void align_loss_kernel(AlignLossArgs a)
 }
 
 // losses[it][term] = sum over the pairs, in pair order
-__global__ void align_loss_reduce_kernel(const double* __restrict__ part, int P, int n2, double* __restrict__ losses) {
+__global__ void align_loss_reduce_kernel(const double* __restrict__ part, int P, int n3, double* __restrict__ losses) {
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= n2) return;
+  if (k >= n3) return;
   double s = 0.0;
-  for (int p = 0; p < P; ++p) s += part[(int64_t)p * n2 + k];
+  for (int p = 0; p < P; ++p) s += part[(int64_t)p * n3 + k];
   losses[k] = s;
 }
 
@@ -291,16 +331,16 @@ __global__ void align_loss_reduce_kernel(const double* __restrict__ part, int P,
 
 int launch_align_loss(const float* src, const float* ref, const int32_t* idx, const float* logits, const float* labels,
                       const float* T_gt, int P, int J, int K, int n_iter, int mse, float wt_pt, float wt_in, float discount,
-                      float* T_out, double* losses, float* grad, hipStream_t st, double* loss_part) {
+                      float wt_pose, float* T_out, double* losses, float* grad, hipStream_t st, double* loss_part) {
   if (n_iter < 1 || n_iter > AL_MAX_ITER) return 1;
   AlignLossArgs a;
   a.src = src; a.ref = ref; a.idx = idx; a.logits = logits; a.labels = labels; a.T_gt = T_gt; a.P = P; a.J = J; a.K = K;
-  a.n_iter = n_iter; a.mse = mse; a.wt_pt = wt_pt; a.wt_in = wt_in; a.discount = discount; a.T_out = T_out; a.losses = losses;
+  a.n_iter = n_iter; a.mse = mse; a.wt_pt = wt_pt; a.wt_in = wt_in; a.discount = discount; a.wt_pose = wt_pose; a.T_out = T_out; a.losses = losses;
   a.grad = grad;
   if (losses && !loss_part) return 2;
   a.loss_part = losses ? loss_part : nullptr;
   hipLaunchKernelGGL(align_loss_kernel, dim3(P), dim3(AL_THREADS), 0, st, a);
-  if (losses) hipLaunchKernelGGL(align_loss_reduce_kernel, dim3(1), dim3(64), 0, st, loss_part, P, 2 * n_iter, losses);
+  if (losses) hipLaunchKernelGGL(align_loss_reduce_kernel, dim3(1), dim3(64), 0, st, loss_part, P, 3 * n_iter, losses);
   return 0;
 }
 

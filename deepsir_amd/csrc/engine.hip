@@ -802,43 +802,70 @@ int dsir_pose_finetune(dsir_ctx* c, const float* xyz_src, const float* xyz_ref, 
   return post(c);
 }
 
-int dsir_align_loss_backward2(dsir_ctx* c, const float* pt_src, const float* pt_ref, const int32_t* idx, const float* logits,
-                             const float* labels, const float* transform_gt, int pairs, int J, int K, int n_iter, int loss_type,
-                             float wt_ptDist_loss, float wt_inlier_loss, float loss_discount_factor, float* transforms,
-                             double* losses, float* grad_logits, double* losses_per_pair) {
+// One body behind the three entries: the kernel always writes three columns (point distance, confidence, pose error); the
+// two older entries run it with weight 0 and hand their callers the first two.
+static int align_loss_body(dsir_ctx* c, const float* pt_src, const float* pt_ref, const int32_t* idx, const float* logits,
+                           const float* labels, const float* transform_gt, int pairs, int J, int K, int n_iter, int loss_type,
+                           float wt_ptDist_loss, float wt_inlier_loss, float loss_discount_factor, float wt_pose_loss, float* transforms,
+                           double* losses, float* grad_logits, double* losses_per_pair, int cols) {
   if (!c) return 1;
   if (!pt_src || !pt_ref || !idx || !logits || !transform_gt || !grad_logits || pairs < 1 || J < 1 || K < 1 || n_iter < 1 ||
       n_iter > 8 || (loss_type != 0 && loss_type != 1))
     return fail(c, "dsir_align_loss_backward: bad arguments (n_iter in [1,8], loss_type 0 = mae / 1 = mse)");
+  if (!(wt_pose_loss >= 0.f) || !std::isfinite(wt_pose_loss))
+    return fail(c, "dsir_align_loss_backward3: wt_pose_loss must be finite and >= 0");
   HIP_OK(c, hipSetDevice(c->device));
   c->ws.top = 0; c->ws.overflow = false;
   // correspondences come from the caller: clamped into [0, K) before any gather
   int32_t* idx_ok = c->ws.get<int32_t>((size_t)n_iter * pairs * J);
-  double* dloss = c->ws.get<double>((size_t)2 * n_iter);
-  double* dpart = c->ws.get<double>((size_t)2 * n_iter * pairs);       // every pair's loss terms, added in pair order (align_loss.hip)
+  double* dloss = c->ws.get<double>((size_t)3 * n_iter);
+  double* dpart = c->ws.get<double>((size_t)3 * n_iter * pairs);       // every pair's loss terms, added in pair order (align_loss.hip)
   if (c->ws.overflow) return fail(c, "workspace too small for dsir_align_loss_backward");
   launch_copy_idx_clamped(idx, (int64_t)pairs * J, pairs * J, K, n_iter, idx_ok, (int64_t)pairs * J, nullptr, 1, c->stream);
   if (launch_align_loss(pt_src, pt_ref, idx_ok, logits, labels, transform_gt, pairs, J, K, n_iter, loss_type, wt_ptDist_loss,
-                        wt_inlier_loss, loss_discount_factor, transforms, dloss, grad_logits, c->stream, dpart))
+                        wt_inlier_loss, loss_discount_factor, wt_pose_loss, transforms, dloss, grad_logits, c->stream, dpart))
     return fail(c, "dsir_align_loss_backward: launch failed");
   if (losses || losses_per_pair) {
     HIP_OK(c, hipStreamSynchronize(c->stream));
-    if (losses) HIP_OK(c, hipMemcpy(losses, dloss, sizeof(double) * 2 * n_iter, hipMemcpyDeviceToHost));
+    const size_t rows = (size_t)n_iter * pairs;
+    std::vector<double> h(3 * rows);
+    if (losses) {
+      HIP_OK(c, hipMemcpy(h.data(), dloss, sizeof(double) * 3 * n_iter, hipMemcpyDeviceToHost));
+      for (int i = 0; i < n_iter; ++i)
+        for (int k = 0; k < cols; ++k) losses[(size_t)i * cols + k] = h[(size_t)i * 3 + k];
+    }
     if (losses_per_pair) {
       // the kernel's per-pair partials carry the batch mean's 1 / pairs: a pair's own mean is pairs x its share
-      HIP_OK(c, hipMemcpy(losses_per_pair, dpart, sizeof(double) * 2 * n_iter * pairs, hipMemcpyDeviceToHost));
-      for (size_t k = 0; k < (size_t)2 * n_iter * pairs; ++k) losses_per_pair[k] *= (double)pairs;
+      HIP_OK(c, hipMemcpy(h.data(), dpart, sizeof(double) * 3 * rows, hipMemcpyDeviceToHost));
+      for (size_t r = 0; r < rows; ++r)
+        for (int k = 0; k < cols; ++k) losses_per_pair[r * cols + k] = h[r * 3 + k] * (double)pairs;
     }
   }
   return post(c);
+}
+
+int dsir_align_loss_backward3(dsir_ctx* c, const float* pt_src, const float* pt_ref, const int32_t* idx, const float* logits,
+                              const float* labels, const float* transform_gt, int pairs, int J, int K, int n_iter, int loss_type,
+                              float wt_ptDist_loss, float wt_inlier_loss, float loss_discount_factor, float wt_pose_loss,
+                              float* transforms, double* losses, float* grad_logits, double* losses_per_pair) {
+  return align_loss_body(c, pt_src, pt_ref, idx, logits, labels, transform_gt, pairs, J, K, n_iter, loss_type, wt_ptDist_loss,
+                         wt_inlier_loss, loss_discount_factor, wt_pose_loss, transforms, losses, grad_logits, losses_per_pair, 3);
+}
+
+int dsir_align_loss_backward2(dsir_ctx* c, const float* pt_src, const float* pt_ref, const int32_t* idx, const float* logits,
+                              const float* labels, const float* transform_gt, int pairs, int J, int K, int n_iter, int loss_type,
+                              float wt_ptDist_loss, float wt_inlier_loss, float loss_discount_factor, float* transforms,
+                              double* losses, float* grad_logits, double* losses_per_pair) {
+  return align_loss_body(c, pt_src, pt_ref, idx, logits, labels, transform_gt, pairs, J, K, n_iter, loss_type, wt_ptDist_loss,
+                         wt_inlier_loss, loss_discount_factor, 0.f, transforms, losses, grad_logits, losses_per_pair, 2);
 }
 
 int dsir_align_loss_backward(dsir_ctx* c, const float* pt_src, const float* pt_ref, const int32_t* idx, const float* logits,
                              const float* labels, const float* transform_gt, int pairs, int J, int K, int n_iter, int loss_type,
                              float wt_ptDist_loss, float wt_inlier_loss, float loss_discount_factor, float* transforms,
                              double* losses, float* grad_logits) {
-  return dsir_align_loss_backward2(c, pt_src, pt_ref, idx, logits, labels, transform_gt, pairs, J, K, n_iter, loss_type, wt_ptDist_loss,
-                                   wt_inlier_loss, loss_discount_factor, transforms, losses, grad_logits, nullptr);
+  return align_loss_body(c, pt_src, pt_ref, idx, logits, labels, transform_gt, pairs, J, K, n_iter, loss_type, wt_ptDist_loss,
+                         wt_inlier_loss, loss_discount_factor, 0.f, transforms, losses, grad_logits, nullptr, 2);
 }
 
 int dsir_graph_stats(dsir_ctx* c, int64_t* out) {

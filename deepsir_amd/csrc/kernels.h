@@ -525,10 +525,10 @@ void launch_pose_finetune(const float* src, const float* ref, const float* w, in
                           hipStream_t st);
 
 // align_loss.hip — ScanAlignmentLoss and its gradient down to the inlier logits (loss.py:705-851, model.py:22-66, :571-595);
-// losses [n_iter][2] float64 on device (point-distance term, confidence term), summed over pairs; returns 0 on success
+// losses [n_iter][3] float64 on device (point-distance, confidence, pose-error term), summed over pairs; returns 0 on success
 int launch_align_loss(const float* src, const float* ref, const int32_t* idx, const float* logits, const float* labels,
                       const float* T_gt, int P, int J, int K, int n_iter, int mse, float wt_pt, float wt_in, float discount,
-                      float* T_out, double* losses, float* grad, hipStream_t st, double* loss_part);   // loss_part: [P][n_iter][2] scratch (with losses)
+                      float wt_pose, float* T_out, double* losses, float* grad, hipStream_t st, double* loss_part);   // loss_part: [P][n_iter][3] scratch (with losses)
 
 // pre-processing on ragged batches (preprocess.hip); return 0 on success
 size_t voxel_downsample_scratch_bytes(int64_t total, int clouds);

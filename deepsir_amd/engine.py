@@ -22,6 +22,14 @@ class EngineError(RuntimeError):
     pass
 
 
+def check_pose_weight(w) -> float:
+    """wt_pose_loss as the loss entries take it: finite and >= 0 (dsir_align_loss_backward3 rejects anything else, too)."""
+    w = float(w)
+    if not (w >= 0.0) or w == float("inf"):
+        raise EngineError(f"align_loss_backward: wt_pose_loss must be finite and >= 0, got {w}")
+    return w
+
+
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
@@ -578,10 +586,13 @@ class Engine:
 
     def align_loss_backward(self, pt_src, pt_ref, idx, logits, labels, transform_gt, loss_type: str = "mae",
                             wt_ptDist_loss: float = 1.0, wt_inlier_loss: float = 1.0, loss_discount_factor: float = 0.5,
-                            per_pair: bool = False):
+                            per_pair: bool = False, wt_pose_loss: float = 0.0):
         """ScanAlignmentLoss (reduction='mean') + its gradient down to the inlier logits (include/dsir.h).
         pt_src [P,J,3], pt_ref [P,K,3], idx [n,P,J] i32, logits [n,P,J], labels [n,P,J] or None, transform_gt [P,3,4]
-        -> dict(losses {mae_i|mse_i, outlier_i, total}, grad_logits [n,P,J], transforms [P,n,3,4])."""
+        -> dict(losses {mae_i|mse_i, outlier_i, total}, grad_logits [n,P,J], transforms [P,n,3,4]).
+        wt_pose_loss > 0 adds the rotation + translation error term (loss.py:830-842): keys poseError_i, as the reference's dict has
+        them only then (dsir_align_loss_backward3; 0 runs dsir_align_loss_backward2 as before).  With wt_ptDist_loss == 0 the
+        keys mae_i | mse_i stay, at 0, as in the reference (loss.py:793-798)."""
         pt_src, pt_ref = _chk(pt_src, torch.float32, "pt_src"), _chk(pt_ref, torch.float32, "pt_ref")
         idx, logits = _chk(idx, torch.int32, "idx"), _chk(logits, torch.float32, "logits")
         transform_gt = _chk(transform_gt, torch.float32, "transform_gt")
@@ -593,35 +604,44 @@ class Engine:
                 (labels is not None and tuple(labels.shape) != (n, P, J)):
             raise EngineError("align_loss_backward: inconsistent shapes")
         lt = {"mae": 0, "mse": 1}[loss_type]
+        wt_pose_loss = check_pose_weight(wt_pose_loss)
+        pose = wt_pose_loss > 0.0
+        nc = 3 if pose else 2
         T = self._empty((P, n, 3, 4))
         grad = self._empty((n, P, J))
-        losses = (C.c_double * (2 * n))()
-        pp = (C.c_double * (2 * n * P))() if per_pair else None
+        losses = (C.c_double * (nc * n))()
+        pp = (C.c_double * (nc * n * P))() if per_pair else None
         self._pre()
-        self._call(self.lib.dsir_align_loss_backward2(self.h, _ptr(pt_src), _ptr(pt_ref), _ptr(idx), _ptr(logits), _ptr(labels),
-                                                      _ptr(transform_gt), P, J, K, n, lt, float(wt_ptDist_loss), float(wt_inlier_loss),
-                                                      float(loss_discount_factor), _ptr(T), losses, _ptr(grad), pp))
+        if pose:
+            self._call(self.lib.dsir_align_loss_backward3(self.h, _ptr(pt_src), _ptr(pt_ref), _ptr(idx), _ptr(logits), _ptr(labels),
+                                                          _ptr(transform_gt), P, J, K, n, lt, float(wt_ptDist_loss), float(wt_inlier_loss),
+                                                          float(loss_discount_factor), wt_pose_loss, _ptr(T), losses, _ptr(grad), pp))
+        else:
+            self._call(self.lib.dsir_align_loss_backward2(self.h, _ptr(pt_src), _ptr(pt_ref), _ptr(idx), _ptr(logits), _ptr(labels),
+                                                          _ptr(transform_gt), P, J, K, n, lt, float(wt_ptDist_loss), float(wt_inlier_loss),
+                                                          float(loss_discount_factor), _ptr(T), losses, _ptr(grad), pp))
         self.sync()
-        d, total = {}, 0.0
-        for i in range(n):
-            disc = loss_discount_factor ** (n - i - 1)
-            if wt_ptDist_loss > 0:
-                d[f"{loss_type}_{i}"] = losses[2 * i]; total += disc * losses[2 * i]
-            if wt_inlier_loss > 0 and labels is not None:
-                d[f"outlier_{i}"] = losses[2 * i + 1]; total += disc * losses[2 * i + 1]
-        d["total"] = total
-        out = {"losses": d, "grad_logits": grad, "transforms": T}
-        if per_pair:      # reduction='none' (loss.py:779, :836): every pair's own terms, [P] each
-            a = np.frombuffer(pp, dtype=np.float64).reshape(P, n, 2)
-            dd, tot = {}, np.zeros(P)
+
+        def terms(col, zero):
+            """The reference's dict for one reduction: col(i, k) = term k of iteration i, zero = 0.0 or zeros [P]."""
+            d, total = {}, zero
             for i in range(n):
                 disc = loss_discount_factor ** (n - i - 1)
                 if wt_ptDist_loss > 0:
-                    dd[f"{loss_type}_{i}"] = a[:, i, 0].copy(); tot += disc * a[:, i, 0]
+                    d[f"{loss_type}_{i}"] = col(i, 0); total = total + disc * d[f"{loss_type}_{i}"]
+                else:      # loss.py:793-798: the key stays, at 0
+                    d[f"{loss_type}_{i}"] = zero * 0.0
                 if wt_inlier_loss > 0 and labels is not None:
-                    dd[f"outlier_{i}"] = a[:, i, 1].copy(); tot += disc * a[:, i, 1]
-            dd["total"] = tot
-            out["losses_per_pair"] = dd
+                    d[f"outlier_{i}"] = col(i, 1); total = total + disc * d[f"outlier_{i}"]
+                if pose:
+                    d[f"poseError_{i}"] = col(i, 2); total = total + disc * d[f"poseError_{i}"]
+            d["total"] = total
+            return d
+
+        out = {"losses": terms(lambda i, k: losses[nc * i + k], 0.0), "grad_logits": grad, "transforms": T}
+        if per_pair:      # reduction='none' (loss.py:779, :836): every pair's own terms, [P] each
+            a = np.frombuffer(pp, dtype=np.float64).reshape(P, n, nc)
+            out["losses_per_pair"] = terms(lambda i, k: a[:, i, k].copy(), np.zeros(P))
         return out
 
     # ------------------------------------------------------------------ ground-truth matches / inlier targets (include/dsir_train.h)

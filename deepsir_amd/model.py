@@ -522,7 +522,7 @@ class Network(nn.Module):
     # ---- one optimisation step of the pipeline: train.py:396-448 without autograd (deepsir_amd/train.py)
     def train_step(self, data: Dict[str, torch.Tensor], opt=None, lr: float = 1e-3, dropout_seed: Optional[int] = None,
                    thres_radius: float = 0.1, det_loss_weight: float = 1.0, loss_kwargs: Optional[dict] = None, dist=None,
-                   frozen_mode: str = "train", match_radius: Optional[float] = None) -> dict:
+                   frozen_mode: str = "train", match_radius: Optional[float] = None, wt_pose_loss: Optional[float] = None) -> dict:
         """What the reference's loop does per batch - ``my_model(train_data, opt)``, ``loss_*_fun``, ``loss.backward()``,
         ``optimizer.step()`` (train.py:396-448) - for this network's pipeline, on the device:
           align: trains ``inlier_model`` (the only sub-network ScanAlignmentLoss reaches; data: transform_gt [B,3,4] and,
@@ -530,6 +530,7 @@ class Network(nn.Module):
                  ``train.MatchKeys``; without a list, ``match_radius`` - the argument or data['match_radius'] - gives the same
                  targets from the geometry: (j, idx[j]) is a match iff |T_gt src_j - ref_idx[j]| < radius.  The targets are
                  made on the device, ``deepsir_amd.train.inlier_targets``).
+                 wt_pose_loss: the weight of the loss's pose-error term (loss.py:830-842); None reads ``args.wt_pose_loss`` (0 = off).
                  frozen_mode 'train' (default): the whole network in training mode as ``my_model.train()`` leaves it - the
                  frozen sub-networks' BatchNorm on batch statistics, their running statistics moving, Dropout on
                  (``train_step_align_full``); 'eval': the frozen half from ONE inference pass of the engine (faster; the
@@ -553,6 +554,11 @@ class Network(nn.Module):
         # the confidence term's 0/1 targets, on the device (deepsir_amd/train.py::inlier_targets): from the caller's match list - its
         # keys are built ONCE per step, not per iteration -, else from the radius and the geometry, else no term
         targets = None
+        if wt_pose_loss is None:
+            wt_pose_loss = (loss_kwargs or {}).get("wt_pose_loss", getattr(getattr(self, "loss_align_fun", None), "wt_pose_loss", 0.0))
+        wt_pose = float(wt_pose_loss)
+        if loss_kwargs and "wt_pose_loss" in loss_kwargs:
+            loss_kwargs = {k: v for k, v in loss_kwargs.items() if k != "wt_pose_loss"}
         if self.pipeline == "align":
             radius = data.get("match_radius", match_radius)
             if "matches" in data:
@@ -568,15 +574,15 @@ class Network(nn.Module):
             if targets is not None:
                 fn = lambda idx: T.inlier_targets(tr.ops, idx, J, **targets)
             out = T.train_step_align_full(eng, tr, fe, ag, batch, data["transform_gt"].float().to(dev), n_iter, fn, lr,
-                                          self._seeded_masks(dropout_seed, B, J, K, dev, n_iter), loss_kwargs, dist=dist)
+                                          self._seeded_masks(dropout_seed, B, J, K, dev, n_iter), loss_kwargs, dist=dist, wt_pose_loss=wt_pose)
             out["loss"] = out["losses"]["total"]
         elif self.pipeline == "align":
             n_iter = int(opt[0]) if opt is not None else self.cfg.num_reg_iter
             res = eng.register(src, ref, n_iter)
             labels = None if targets is None else T.inlier_targets(tr.ops, res["idx"], J, **targets)
-            key = (id(eng), B, J, K, n_iter)
-            if st.stepper_key != key:                                           # hipGraph-replayed halves, fixed batch geometry
-                st.stepper, st.stepper_key = T.AlignTrainStep(eng, tr, B, J, K, n_iter), key
+            key = (id(eng), B, J, K, n_iter, wt_pose)
+            if st.stepper_key != key:                                           # hipGraph-replayed halves, fixed batch geometry and loss weight
+                st.stepper, st.stepper_key = T.AlignTrainStep(eng, tr, B, J, K, n_iter, wt_pose_loss=wt_pose), key
             out = st.stepper.step(batch, res, data["transform_gt"].float().to(dev), labels, lr, dropout_seed, loss_kwargs, dist=dist)
             out["loss"] = out["losses"]["total"]
         elif self.pipeline == "label":

@@ -928,17 +928,25 @@ def forward_align_train(engine, inlier: RandlaTrainer, extractor: RandlaTrainer,
             "xyz_ref": xyz_r, "invalid": invalid, "shared": shared, "T": Ts, "pt_ref_new": pt_ref_new}
 
 
+def _loss_kw(loss_kwargs: Optional[dict], wt_pose_loss: float) -> dict:
+    """The keyword arguments of ``Engine.align_loss_backward``: the caller's, with the pose-error weight when one is given."""
+    kw = dict(loss_kwargs or {})
+    if wt_pose_loss:
+        kw["wt_pose_loss"] = float(wt_pose_loss)
+    return kw
+
+
 def train_step_align_full(engine, inlier: RandlaTrainer, extractor: RandlaTrainer, aggregation: "AggregationTrainer", batch: dict,
                           transform_gt, n_iter: int, labels_fn=None, lr: float = 1e-3, masks: Optional[dict] = None,
-                          loss_kwargs: Optional[dict] = None, apply: bool = True, dist=None) -> dict:
+                          loss_kwargs: Optional[dict] = None, apply: bool = True, dist=None, wt_pose_loss: float = 0.0) -> dict:
     """One optimisation step of the `align` pipeline with the WHOLE network in training mode, as train.py:379-448 runs it
     (``forward_align_train``): only the inlier model receives gradients and is updated (model.py:136, :182), but the frozen
     sub-networks' BatchNorm running statistics move, as they do in the reference.  labels_fn(idx) -> [n_iter][P][J] float 0/1
-    (``find_correct_correspondence``) or None: no confidence term."""
+    (``find_correct_correspondence``) or None: no confidence term.  wt_pose_loss > 0: the loss's pose-error term (loss.py:830-842)."""
     inlier.zero_grad()
     fw = forward_align_train(engine, inlier, extractor, aggregation, batch, n_iter, masks)
     labels = None if labels_fn is None else labels_fn(fw["idx"])
-    out = engine.align_loss_backward(fw["xyz_src"], fw["xyz_ref"], fw["idx"], fw["logits"], labels, transform_gt, **(loss_kwargs or {}))
+    out = engine.align_loss_backward(fw["xyz_src"], fw["xyz_ref"], fw["idx"], fw["logits"], labels, transform_gt, **_loss_kw(loss_kwargs, wt_pose_loss))
     inlier_backwards(inlier, fw["tapes"], out["grad_logits"], fw["shared"])
     bad = inlier.finish_step(lr, apply, dist, fw["invalid"])
     out.update(logits=fw["logits"], idx=fw["idx"], skipped=bad)
@@ -947,7 +955,7 @@ def train_step_align_full(engine, inlier: RandlaTrainer, extractor: RandlaTraine
 
 def train_step_align(engine, trainer: RandlaTrainer, batch: dict, result: dict, transform_gt: np.ndarray,
                      labels: Optional[np.ndarray] = None, lr: float = 1e-3, dropout_seed: Optional[int] = None,
-                     loss_kwargs: Optional[dict] = None, apply: bool = True, dist=None) -> dict:
+                     loss_kwargs: Optional[dict] = None, apply: bool = True, dist=None, wt_pose_loss: float = 0.0) -> dict:
     """One optimisation step of the `align` pipeline on the inlier model (train.py:396-448).
 
     ``batch``: the device tensors of one ``Engine.register`` call (points_src [P][N][C], the src pyramid
@@ -956,7 +964,8 @@ def train_step_align(engine, trainer: RandlaTrainer, batch: dict, result: dict, 
     inference engine.  Per iteration the inlier model's input cat(xyz_src_i, xyz_ref[idx_i]) (model.py:571-573) is rebuilt
     from them, run forward in training mode, the alignment loss and its gradient w.r.t. the logits come from
     ``Engine.align_loss_backward``, and the gradients of all iterations are accumulated before ONE Adam step - skipped,
-    like the reference's (train.py:437-446), when a gradient is NaN or a pose was degenerate."""
+    like the reference's (train.py:437-446), when a gradient is NaN or a pose was degenerate.  wt_pose_loss > 0 turns the loss's
+    pose-error term on (loss.py:830-842; ``Engine.align_loss_backward``)."""
     xyz_s = batch["points_src"][:, :, :3].contiguous()
     xyz_r = batch["points_ref"][:, :, :3].contiguous()
     idx = result["idx"]
@@ -966,7 +975,7 @@ def train_step_align(engine, trainer: RandlaTrainer, batch: dict, result: dict, 
     logits, tapes, shared = inlier_forwards(trainer, xyz_s, xyz_r, idx, result["transforms"],
                                             (batch["src_xyz"], batch["src_neigh"], batch["src_sub"], batch["src_interp"]), masks)
     lg_all = torch.stack(logits).contiguous()
-    out = engine.align_loss_backward(xyz_s, xyz_r, idx, lg_all, labels, transform_gt, **(loss_kwargs or {}))
+    out = engine.align_loss_backward(xyz_s, xyz_r, idx, lg_all, labels, transform_gt, **_loss_kw(loss_kwargs, wt_pose_loss))
     inlier_backwards(trainer, tapes, out["grad_logits"], shared)
     out["logits"] = lg_all
     out["skipped"] = trainer.finish_step(lr, apply, dist, [result.get("invalid")])
@@ -1138,10 +1147,14 @@ class AlignTrainStep:
     The first call runs eagerly (it IS a training step), the second captures, later ones replay.  Inputs are copied into
     static device buffers; with the same ``dropout_seed`` the masks are those of ``train_step_align`` (``dropout_keep_masks``) and the
     results are those of ``train_step_align``: both run ``inlier_forwards`` / ``inlier_backwards``, and the scatter-adds sum over a sorted
-    plan, not with float atomics (tests/test_train.py::test_graph_replayed_step_equals_the_eager_step compares the two)."""
+    plan, not with float atomics (tests/test_train.py::test_graph_replayed_step_equals_the_eager_step compares the two).
+    ``wt_pose_loss`` (the loss's pose-error term) belongs to the step's signature like its geometry: a stepper is built for one
+    weight and ``step`` raises when its loss_kwargs ask for another - it never runs with a stale scalar."""
 
     def __init__(self, engine, trainer: RandlaTrainer, pairs: int, n_src: int, n_ref: int, n_iter: int, dropout: bool = True,
-                 use_graph: bool = True):
+                 use_graph: bool = True, wt_pose_loss: float = 0.0):
+        from .engine import check_pose_weight
+        self.wt_pose_loss = check_pose_weight(wt_pose_loss)
         self.engine, self.tr = engine, trainer
         self.P, self.N, self.K, self.n_iter, self.dropout, self.use_graph = pairs, n_src, n_ref, n_iter, dropout, use_graph
         dev = trainer.device
@@ -1173,6 +1186,9 @@ class AlignTrainStep:
     def step(self, batch: dict, result: dict, transform_gt, labels=None, lr: float = 1e-3, dropout_seed: Optional[int] = None,
              loss_kwargs: Optional[dict] = None, apply: bool = True, dist=None) -> dict:
         tr = self.tr
+        kw = dict(loss_kwargs or {})
+        if float(kw.setdefault("wt_pose_loss", self.wt_pose_loss)) != self.wt_pose_loss:
+            raise ValueError(f"this AlignTrainStep was built for wt_pose_loss = {self.wt_pose_loss}, not {kw['wt_pose_loss']}: build another")
         self.xyz_s.copy_(batch["points_src"][:, :, :3]); self.xyz_r.copy_(batch["points_ref"][:, :, :3])
         self.src_xyz.copy_(batch["src_xyz"]); self.neigh.copy_(batch["src_neigh"])
         self.sub.copy_(batch["src_sub"]); self.interp.copy_(batch["src_interp"])
@@ -1193,7 +1209,7 @@ class AlignTrainStep:
             self.gf.replay()
         else:
             self._forward_all()
-        out = self.engine.align_loss_backward(self.xyz_s, self.xyz_r, self.idx, self.logits, labels, transform_gt, **(loss_kwargs or {}))
+        out = self.engine.align_loss_backward(self.xyz_s, self.xyz_r, self.idx, self.logits, labels, transform_gt, **kw)
         self.grad.copy_(out["grad_logits"])
         if graphs and self.gb is None:
             torch.cuda.synchronize()

@@ -66,6 +66,7 @@ def main():
     ap.add_argument("--batch", type=int, default=2)
     ap.add_argument("--iters", type=int, default=3, help="num_train_reg_iter")
     ap.add_argument("--lr", type=float, default=1e-3)
+    ap.add_argument("--wt_pose_loss", type=float, default=0.0, help="weight of the rotation + translation error term (0 = off, the reference's default)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--epochs", type=int, default=1000000)
     ap.add_argument("--steps", type=int, default=100, help="stop after this many optimisation steps (counted across resumes)")
@@ -83,7 +84,7 @@ def main():
     kitti = a.dataset == "kitti"
     args = SimpleNamespace(pipeline="align", feat_len=4 if kitti else 3, num_sub=-1, num_knn=16, out_feat_dim=64, clip_weight_thresh=0.0,
                            d_out=[16, 64, 128, 256], sub_sampling_ratio=[4, 4, 4, 4], use_ppf=False, num_reg_iter=a.iters, loss_type="mae",
-                           wt_ptDist_loss=1.0, wt_inlier_loss=1.0, wt_pose_loss=0.0, loss_discount_factor=0.5, lr=a.lr)
+                           wt_ptDist_loss=1.0, wt_inlier_loss=1.0, wt_pose_loss=a.wt_pose_loss, loss_discount_factor=0.5, lr=a.lr)
     model = Network(args)
     os.makedirs(a.out, exist_ok=True)
     ckpt, step = os.path.join(a.out, "ckpt.pth"), 0
@@ -126,8 +127,11 @@ def main():
                 continue
             out = model.train_step(data, (a.iters, True), lr=a.lr, dropout_seed=a.seed * 1000003 + step)
             step += 1
-            emit({"event": "train", "step": step, "epoch": epoch, "loss": float(out["loss"]),
-                  "invalid_clouds": int((data["invalid"] != 0).sum().item())})
+            rec = {"event": "train", "step": step, "epoch": epoch, "loss": float(out["loss"]),
+                   "invalid_clouds": int((data["invalid"] != 0).sum().item())}
+            if a.wt_pose_loss > 0:      # the term of the last iteration, when it is on
+                rec["pose_error"] = float(out["losses"][f"poseError_{a.iters - 1}"])
+            emit(rec)
             if step % a.val_every == 0 or step == a.steps:
                 rec = {"event": "val", "step": step}
                 rec.update(validate(model, val_batches, a.iters, "KITTI" if kitti else "3DMatch"))

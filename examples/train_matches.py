@@ -30,12 +30,13 @@ def main():
     ap.add_argument("--radius", type=float, default=0.09, help="voxel_size * positive_pair_radius_multiplier")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--lr", type=float, default=1e-3)
+    ap.add_argument("--wt_pose_loss", type=float, default=0.0, help="weight of the rotation + translation error term (0 = off, the reference's default)")
     ap.add_argument("--no-list", action="store_true", help="no match list: the targets from endpoints['match_radius']")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     _args = SimpleNamespace(pipeline="align", feat_len=3, num_sub=-1, num_knn=16, out_feat_dim=64, clip_weight_thresh=0.0, d_out=[16, 64, 128, 256],
                             sub_sampling_ratio=[4, 4, 4, 4], use_ppf=False, num_reg_iter=a.iters, loss_type="mae", wt_ptDist_loss=1.0,
-                            wt_inlier_loss=1.0, wt_pose_loss=0.0, loss_discount_factor=0.5, lr=a.lr)
+                            wt_inlier_loss=1.0, wt_pose_loss=a.wt_pose_loss, loss_discount_factor=0.5, lr=a.lr)
     my_model = Network(_args)
     my_model.load_state_dict(to_torch_state_dict(generate_state_dict(my_model.cfg, 1, "separated")))
     my_model.to(dev)
@@ -72,7 +73,8 @@ def main():
         if not (backprop_flag or endpoints['invalid_gradient']):
             optimizer.step()
         last = a.iters - 1
-        print(f"step {step:3d}  total {loss.item():.5f}  mae_{last} {losses[f'mae_{last}'].item():.5f}  outlier_{last} {losses[f'outlier_{last}'].item():.5f}",
+        pose = f"  poseError_{last} {losses[f'poseError_{last}'].item():.5f}" if f"poseError_{last}" in losses else ""
+        print(f"step {step:3d}  total {loss.item():.5f}  mae_{last} {losses[f'mae_{last}'].item():.5f}  outlier_{last} {losses[f'outlier_{last}'].item():.5f}{pose}",
               flush=True)
 
 

@@ -350,7 +350,8 @@ int dsir_feature_correspondences(dsir_ctx* ctx, const float* desc_src, const flo
 /* ---- the training slice (backward half) ------- */
 
 /* Replaces ScanAlignmentLoss.forward with reduction='mean' (network/loss.py:705-851; defaults of arguments.py:51-61:
- * loss_type mae, wt_ptDist_loss 1, wt_inlier_loss 1, wt_pose_loss 0, loss_discount_factor 0.5; called at train.py:401)
+ * loss_type mae, wt_ptDist_loss 1, wt_inlier_loss 1, wt_pose_loss 0, loss_discount_factor 0.5; called at train.py:401;
+ * wt_pose_loss > 0, the rotation + translation error term of loss.py:830-842: dsir_align_loss_backward3 below)
  * AND torch autograd's backward of it down to the inlier logits: through se3_torch.concatenate (model.py:595) and the
  * SVD of compute_rigid_transform_2 (model.py:22-66).  In forward_align_4 the matching runs under no_grad and the src
  * cloud is moved by R_t.detach(), so d total / d logits is the whole gradient the network receives from this loss: the
@@ -372,6 +373,25 @@ int dsir_align_loss_backward2(dsir_ctx* ctx, const float* pt_src, const float* p
                               const float* labels, const float* transform_gt, int pairs, int J, int K, int n_iter, int loss_type,
                               float wt_ptDist_loss, float wt_inlier_loss, float loss_discount_factor, float* transforms,
                               double* losses, float* grad_logits, double* losses_per_pair);
+/* dsir_align_loss_backward2 plus the pose-error term, float wt_pose_loss (finite, >= 0; 0 = the call above, same bits).  Per pair
+ * and iteration, from the cumulative pose [Rc_i | tc_i] and the ground truth:
+ *     s_i = (<R_gt, Rc_i>_F - 1) / 2,   err_r = acos(clamp(s_i, -1, 1)),   err_t = |t_gt - tc_i|_2
+ *     poseError_i = (mean_pairs err_r + mean_pairs err_t) wt_pose_loss       (losses_per_pair: (err_r + err_t) wt_pose_loss)
+ * losses = HOST float64 [n_iter][3], losses_per_pair = HOST float64 [P][n_iter][3]: {mae_i | mse_i, outlier_i, poseError_i}, the
+ * third already multiplied by wt_pose_loss and, like the other two, not yet discounted; total adds discount^(n_iter-1-i) x it.
+ * grad_logits carries the term's gradient through the same chain (concatenate, Kabsch / SVD adjoint, weight normalisation, sigmoid'):
+ *     dL/dRc_i += c_i (-1 / (2 sqrt(1 - s_i^2))) R_gt,   dL/dtc_i += c_i (tc_i - t_gt) / |tc_i - t_gt|,   c_i = discount_i wt_pose_loss / P.
+ * Corner rules:
+ *   |tc_i - t_gt| == 0: zero translation gradient (torch.norm's own subgradient).
+ *   1 - s_i^2 <= 0 (s_i in fp64 from the fp32 matrices): the value is acos of s_i clamped to [-1, 1]; the rotation gradient is ZERO.
+ *     A deliberate departure: in fp32 the reference's clamp bounds -1 + 1e-16, 1 - 1e-16 round to -1, 1 and its autograd yields inf
+ *     or NaN there, after which its loop skips the step (train.py:436-441); this entry returns a finite gradient instead.
+ * A pair whose pose solve is degenerate gets no special treatment from this term, as it gets none from the point-distance term: the
+ * kernel replays the chain as it is; the trainer's step is skipped on the engine's `invalid` flag, as before. */
+int dsir_align_loss_backward3(dsir_ctx* ctx, const float* pt_src, const float* pt_ref, const int32_t* idx, const float* logits,
+                              const float* labels, const float* transform_gt, int pairs, int J, int K, int n_iter, int loss_type,
+                              float wt_ptDist_loss, float wt_inlier_loss, float loss_discount_factor, float wt_pose_loss,
+                              float* transforms, double* losses, float* grad_logits, double* losses_per_pair);
 
 /* Launch-bound small batches: capture the whole dsir_register launch sequence into a hipGraph once per
  * call signature (sizes and buffer addresses) and replay it; the context keeps the graphs of its 16 most recent signatures

@@ -187,7 +187,11 @@ int dsir_t_radius_matches_fill(void* stream, const float* src, const float* ref,
 
 /* Targets from geometry: labels[i][p][j] = rule(T_gt[p], src[p][j], ref[p][idx[i][p][j]]) ? 1 : 0; idx [n_iter][pairs][J] (clamped
  * into [0, K)), labels [n_iter][pairs][J] fp32 - what dsir_align_loss_backward2 takes as `labels`.  With the reference's K = None
- * list this IS "(j, idx[j]) is among the matches": no list is needed. */
+ * list this IS "(j, idx[j]) is among the matches": no list is needed.
+ * The loss entries themselves live in dsir.h; dsir_align_loss_backward3 there adds the pose-error term (wt_pose_loss > 0) with two
+ * corner rules, stated in full next to it: |tc_i - t_gt| == 0 gives a zero translation gradient (torch.norm's subgradient), and
+ * 1 - s_i^2 <= 0 gives acos of the clamped s_i as the value and a ZERO rotation gradient, where the reference's fp32 autograd
+ * yields inf or NaN and its loop skips the step. */
 int dsir_t_inlier_targets_radius(void* stream, const float* src, const float* ref, int stride, const int32_t* idx, const float* transform_gt,
                                  int n_iter, int pairs, int J, int K, float radius, float* labels);
 

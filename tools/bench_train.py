@@ -1,4 +1,4 @@
-"""tools/bench_train.py [--pairs P] [--points N] [--iters I] [--steps K] [--use-ppf]: time of one `align` training step of the inlier model
+"""tools/bench_train.py [--pairs P] [--points N] [--iters I] [--steps K] [--use-ppf] [--wt-pose-loss W]: time of one `align` training step of the inlier model
 (deepsir_amd.train.train_step_align: 5 training-mode forwards, loss + gradient, 5 backwards, Adam) on one GPU; the
 inference half (Engine.register) is timed separately.  Prints one JSON line.
 
@@ -7,6 +7,8 @@ already on the device - the step with no target work at all; host: find_correct_
 match lists (copy of idx down, np.isin per pair and iteration, copy up); matches: the same lists hashed, sorted and searched on
 the device (deepsir_amd.train.inlier_targets); radius: no list, the distance test on the device.  The lists themselves come from
 Engine.radius_matches with --radius (default 0.09 for --shape 3dmatch, 0.9 for kitti), once, outside the timed steps.
+
+--wt-pose-loss W: the loss with its pose-error term at weight W (default 0: off).
 
 --use-ppf: the networks of args.use_ppf (point rows of xyz + seeded unit normals; the taped point-pair-feature front end, csrc/ppf.hip)."""
 import argparse
@@ -37,6 +39,7 @@ ap.add_argument("--targets", choices=("random", "host", "matches", "radius"), de
 ap.add_argument("--shape", choices=("3dmatch", "kitti"), default="3dmatch", help="extent of the synthetic clouds")
 ap.add_argument("--radius", type=float, default=None, help="match radius (default 0.09 for 3dmatch, 0.9 for kitti)")
 ap.add_argument("--use-ppf", action="store_true", help="train the use_ppf networks (rows of xyz + normal)")
+ap.add_argument("--wt-pose-loss", type=float, default=0.0, help="weight of the loss's pose-error term (0 = off)")
 a = ap.parse_args()
 cfg = NetConfig(feat_len=6, use_ppf=True) if a.use_ppf else NetConfig(feat_len=3)
 sd = generate_state_dict(cfg, 3, "plain")
@@ -78,7 +81,7 @@ if a.full:
     fe, ag = RandlaTrainer(cfg, sd, "feat_extractor", cfg.feat_len, cfg.num_classes, dev), AggregationTrainer(cfg, sd, dev)
     rx, rn, rs, ri = eng.knn_pyramid(ref)
     batch.update({"ref_xyz": rx, "ref_neigh": rn, "ref_sub": rs, "ref_interp": ri})
-stepper = AlignTrainStep(eng, tr, a.pairs, a.points, a.points, a.iters, dropout=True, use_graph=not a.eager)
+stepper = AlignTrainStep(eng, tr, a.pairs, a.points, a.points, a.iters, dropout=True, use_graph=not a.eager, wt_pose_loss=a.wt_pose_loss)
 t_inf, t_train, losses = [], [], []
 for s in range(a.steps + 2):
     torch.cuda.synchronize(); t0 = time.perf_counter()
@@ -88,7 +91,7 @@ for s in range(a.steps + 2):
         g_ = torch.Generator(device=dev).manual_seed(s)
         keep = lambda *sh: (torch.rand(*sh, generator=g_, device=dev) >= 0.5).to(torch.uint8)
         masks = {"fe_src": keep(a.pairs, a.points, 64), "fe_ref": keep(a.pairs, a.points, 64), "inlier": keep(a.iters, a.pairs, a.points, 64)}
-        out = train_step_align_full(eng, tr, fe, ag, batch, gt, a.iters, targets, lr=1e-3, masks=masks)
+        out = train_step_align_full(eng, tr, fe, ag, batch, gt, a.iters, targets, lr=1e-3, masks=masks, wt_pose_loss=a.wt_pose_loss)
     else:
         out = stepper.step(batch, res, gt, labels=targets(res["idx"]), lr=1e-3, dropout_seed=s)
     torch.cuda.synchronize(); t2 = time.perf_counter()
@@ -101,6 +104,8 @@ if matches is not None:
     extra["matches_per_point"] = round(sum(len(m) for m in matches) / (a.pairs * a.points), 2)
 if a.use_ppf:
     extra["use_ppf"] = True
+if a.wt_pose_loss:
+    extra["wt_pose_loss"] = a.wt_pose_loss
 print(json.dumps({"mode": "whole network in training mode (eager)" if a.full else "eager" if a.eager else "hipGraph replay", "pairs": a.pairs, "points": a.points, "iters": a.iters, "inference_ms": round(1e3 * float(np.median(t_inf)), 2),
                   "train_step_ms": round(1e3 * float(np.median(t_train)), 2),
                   "train_pairs_per_s": round(a.pairs / float(np.median(t_train)), 2), "losses": [round(l, 5) for l in losses],
