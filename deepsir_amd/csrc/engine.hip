@@ -761,6 +761,27 @@ int dsir_icp_refine(dsir_ctx* c, const float* points_src, const float* points_re
   return post(c);
 }
 
+int dsir_icp_refine_ex(dsir_ctx* c, const float* points_src, const float* points_ref, int pairs, int J, int K, int stride,
+                       float max_corr_dist, int max_iter, float rel_fitness, float rel_rmse, const float* T_init, float* T_out,
+                       int estimator, const float* normals_ref, double* stats) {
+  if (!c) return 1;
+  if (!points_src || !points_ref || !T_init || !T_out || pairs < 1 || J < 1 || K < 1 || stride < 3 || max_iter < 0 ||
+      !(max_corr_dist > 0.f) || (estimator != 0 && estimator != 1))
+    return fail(c, "dsir_icp_refine_ex: bad arguments");
+  if (estimator == 1 && !normals_ref && stride < 6)
+    return fail(c, "dsir_icp_refine_ex: bad arguments (the plane estimator without normals_ref reads the normals from columns 3..5 "
+                   "of the points_ref rows: stride=%d, needs >= 6)", stride);
+  HIP_OK(c, hipSetDevice(c->device));
+  c->ws.top = 0; c->ws.overflow = false;
+  void* scratch = c->ws.raw(icp_scratch_bytes_ex(pairs, J, estimator));
+  if (c->ws.overflow) return fail(c, "workspace too small for dsir_icp_refine_ex (raise max_points / max_pairs)");
+  const float* normals = normals_ref ? normals_ref : points_ref + 3;
+  launch_icp_refine_ex(points_src, points_ref, pairs, J, K, stride, max_corr_dist, max_iter, rel_fitness, rel_rmse, T_init, T_out,
+                       nullptr, stats, estimator, normals, normals_ref ? (int64_t)K * 3 : (int64_t)K * stride, normals_ref ? 3 : stride,
+                       scratch, c->stream);
+  return post(c);
+}
+
 int dsir_ransac_correspondence(dsir_ctx* c, const float* points_src, const float* points_ref, int pairs, int J, int K, int stride,
                                const int32_t* corr, const int32_t* counts, int M, float max_dist, int ransac_n, float edge_sim,
                                int hypotheses, int refine_iters, uint64_t seed, const float* T_init, float* T_out, double* stats,

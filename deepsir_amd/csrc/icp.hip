@@ -10,8 +10,29 @@
 // run for all pairs of a batch at once, entirely on device (no host round trip per iteration): a per-pair `done` flag
 // turns the remaining iterations into no-ops.  Nearest neighbours: exact brute force in fp32 (squared distance
 // (dx*dx + dy*dy) + dz*dz without FMA contraction, ties to the lower index), support staged through LDS.
+//
+// ---- Point-to-plane estimator (dsir_icp_refine_ex, estimator 1): open3d's TransformationEstimationPointToPlane in the same loop.
+// open3d is not installable here: parity is unpinned, THE RULE IS OWNED HERE and restated in tests/icp_plane_host.py.  The first
+// search, fitness, inlier RMSE (from point distances), the convergence test, the `done` flag and max_iter are the loop above;
+// only the update differs.  Over the correspondences (s = moved source point, t = its target point, n = the target's normal,
+// all fp32 values taken to fp64):
+//   r = ((s-t).x n.x + (s-t).y n.y) + (s-t).z n.z,   J = [s x n ; n]  (6),   A = sum J J^T (21 distinct sums),   b = sum J r (6)
+//   solve A x = -b in fp64;  update R = Rz(x2) Ry(x1) Rx(x0), t = (x3, x4, x5)  (open3d's TransformVector6dToMatrix4d),
+//   rounded to fp32 once, applied to the moved points and composed onto T exactly as the Kabsch step's transform is.
+// A correspondence whose normal is (0,0,0) (dsir_estimate_normals' degenerate output), or whose normal or target coordinates are
+// not finite, contributes nothing and is not counted as a row.  The update is the IDENTITY - the moved points and T keep their
+// bits, and the pair's fifth statistic counts it - when fewer than 6 rows entered the sums, when the system is singular
+// (icp_plane.h: LDL^T without pivoting of the matrix scaled to unit diagonal, a pivot below kIcpPlanePivotMin; a diagonal entry
+// that is zero or not finite is singular), or when any of the pair's moved source points is not finite.
+// Kernels: icp_plane_accum_kernel, one workgroup per (chunk of kIcpPlaneChunk source points, pair), writes the chunk's 29 fp64 sums
+// (wave butterflies, then the waves in order: no atomics) to its own slot; icp_plane_step_kernel, one workgroup per 256 source
+// points and pair, adds the pair's slots in chunk order (every workgroup for itself: the same bits in each), solves, and moves its
+// points; its first workgroup composes T and hands the pair's `done` flag to the next search.  The partition depends on J alone,
+// so a pair's result depends neither on the run nor on the other pairs of the call.  An iteration is four launches, as in the
+// point-to-point loop (flags, Kabsch, search, statistics there; sums, step, search, statistics here).
 #include "kernels.h"
 #include "device_utils.h"
+#include "icp_plane.h"
 
 namespace dsir {
 
@@ -127,6 +148,123 @@ __global__ void icp_done_flags_kernel(const double* __restrict__ state, int pair
   if (p < pairs) skip[p] = state[(int64_t)p * 4 + 2] != 0.0 ? 1 : 0;
 }
 
+// ---- point-to-plane update (the rule: this file's header)
+constexpr int PT = 256;    // threads of both plane kernels (kIcpPlaneChunk / PT points per thread in the sums)
+
+// C = T o P for row-major 3x4 transforms, (R_T R_P, R_T t_P + t_T), in the rounding sequence kabsch_solve composes the cumulative pose by
+__device__ __forceinline__ void se3_compose(const float* T, const float* P, float* C) {
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c)
+      C[r * 4 + c] = fmaf(T[r * 4 + 2], P[2 * 4 + c], fmaf(T[r * 4 + 1], P[1 * 4 + c], __fmul_rn(T[r * 4 + 0], P[c])));
+    const float rt = fmaf(T[r * 4 + 2], P[2 * 4 + 3], fmaf(T[r * 4 + 1], P[1 * 4 + 3], __fmul_rn(T[r * 4 + 0], P[3])));
+    C[r * 4 + 3] = __fadd_rn(rt, T[r * 4 + 3]);
+  }
+}
+
+// normals of pair `pair`: N + pair * cs, `ld` floats between points ([P][K][3], or columns 3..5 of the reference rows)
+struct PlaneNormals { const float* N; int64_t cs; int ld; };
+
+__global__ __launch_bounds__(PT) void icp_plane_accum_kernel(const float* __restrict__ cur, const float* __restrict__ ref, int ref_stride,
+                                                             PlaneNormals nrm, const int32_t* __restrict__ idx,
+                                                             const float* __restrict__ w, int J, int K,
+                                                             const double* __restrict__ state, double* __restrict__ part) {
+  __shared__ double sh[(PT / 64 + 1) * kIcpPlaneSums];
+  const int pair = blockIdx.y, ch = blockIdx.x;
+  if (state[(int64_t)pair * 4 + 2] != 0.0) return;   // converged: the step is the identity (block-uniform)
+  const float* S = ref + (int64_t)pair * K * ref_stride;
+  const float* N = nrm.N + pair * nrm.cs;
+  const int first = ch * kIcpPlaneChunk, last = min(J, first + kIcpPlaneChunk);
+  double v[kIcpPlaneSums];
+#pragma unroll
+  for (int k = 0; k < kIcpPlaneSums; ++k) v[k] = 0.0;
+  for (int j = first + threadIdx.x; j < last; j += PT) {
+    const int64_t o = (int64_t)pair * J + j;
+    const float sx = cur[o * 3], sy = cur[o * 3 + 1], sz = cur[o * 3 + 2];
+    if (!(isfinite(sx) && isfinite(sy) && isfinite(sz))) v[28] += 1.0;
+    if (w[o] == 0.f) continue;                        // no correspondence (icp_stats_kernel: weight 0, index clamped)
+    const int64_t i = idx[o];
+    const float tx = S[i * ref_stride], ty = S[i * ref_stride + 1], tz = S[i * ref_stride + 2];
+    const float nx = N[i * nrm.ld], ny = N[i * nrm.ld + 1], nz = N[i * nrm.ld + 2];
+    if (!(isfinite(tx) && isfinite(ty) && isfinite(tz) && isfinite(nx) && isfinite(ny) && isfinite(nz))) continue;
+    if (nx == 0.f && ny == 0.f && nz == 0.f) continue;
+    const double s[3] = {(double)sx, (double)sy, (double)sz}, n[3] = {(double)nx, (double)ny, (double)nz};
+    const double r = ((s[0] - (double)tx) * n[0] + (s[1] - (double)ty) * n[1]) + (s[2] - (double)tz) * n[2];
+    const double Jr[6] = {s[1] * n[2] - s[2] * n[1], s[2] * n[0] - s[0] * n[2], s[0] * n[1] - s[1] * n[0], n[0], n[1], n[2]};
+    int k = 0;
+#pragma unroll
+    for (int a = 0; a < 6; ++a)
+#pragma unroll
+      for (int b = a; b < 6; ++b) v[k++] += Jr[a] * Jr[b];
+#pragma unroll
+    for (int a = 0; a < 6; ++a) v[21 + a] += Jr[a] * r;
+    v[27] += 1.0;
+  }
+  block_sum<PT / 64>(v, sh);
+  if (threadIdx.x < kIcpPlaneSums)
+    part[((int64_t)pair * gridDim.x + ch) * kIcpPlaneSlots + threadIdx.x] = sh[(PT / 64) * kIcpPlaneSums + threadIdx.x];
+}
+
+__global__ __launch_bounds__(PT) void icp_plane_step_kernel(float* __restrict__ cur, int J, int nch, const double* __restrict__ part,
+                                                            const double* __restrict__ state, const float* __restrict__ T_prev,
+                                                            float* __restrict__ T_cum, double* __restrict__ nsing,
+                                                            int32_t* __restrict__ skip) {
+  __shared__ double tot[kIcpPlaneSlots];
+  __shared__ float sT[12];
+  __shared__ int s_move;
+  const int pair = blockIdx.y;
+  const bool lead = blockIdx.x == 0 && threadIdx.x == 0;   // the one thread that writes the pair's transform, counter and flag
+  const bool done = state[(int64_t)pair * 4 + 2] != 0.0;   // block-uniform
+  if (lead) skip[pair] = done ? 1 : 0;                      // the search after this step leaves a converged pair alone
+  if (done) {
+    if (lead)
+      for (int k = 0; k < 12; ++k) T_cum[pair * 12 + k] = T_prev[pair * 12 + k];
+    return;
+  }
+  if (threadIdx.x < kIcpPlaneSums) {
+    double s = 0.0;
+    for (int c = 0; c < nch; ++c) s += part[((int64_t)pair * nch + c) * kIcpPlaneSlots + threadIdx.x];   // chunk order
+    tot[threadIdx.x] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double x[6], Td[12];
+    const bool ok = tot[28] == 0.0 && icp_plane_solve(tot, tot + 21, tot[27], x);
+    bool move = ok;
+    if (ok) {
+      icp_plane_transform(x, Td);
+      for (int k = 0; k < 12; ++k) {
+        sT[k] = (float)Td[k];
+        move = move && isfinite(sT[k]);
+      }
+    }
+    s_move = move ? 1 : 0;
+    if (lead) {
+      const float* P = T_prev + pair * 12;
+      float C[12];
+      if (move) se3_compose(sT, P, C);
+      for (int k = 0; k < 12; ++k) T_cum[pair * 12 + k] = move ? C[k] : P[k];
+      if (!move) nsing[pair] += 1.0;
+    }
+  }
+  __syncthreads();
+  if (!s_move) return;                                      // identity update: the points keep their bits (block-uniform)
+  const int j = blockIdx.x * PT + threadIdx.x;
+  if (j < J) {
+    float* p = cur + ((int64_t)pair * J + j) * 3;
+    const float x = p[0], y = p[1], z = p[2];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) p[r] = se3_row(sT, r, x, y, z);
+  }
+}
+
+// stats [pairs][5] = the four values of the loop's state, then the identity updates taken for a singular system (0 without counters)
+__global__ void icp_stats5_kernel(const double* __restrict__ state, const double* __restrict__ nsing, int pairs, double* __restrict__ out) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= pairs) return;
+  for (int k = 0; k < 4; ++k) out[(int64_t)p * 5 + k] = state[(int64_t)p * 4 + k];
+  out[(int64_t)p * 5 + 4] = nsing ? nsing[p] : 0.0;
+}
+
 }  // namespace
 
 size_t icp_scratch_bytes(int pairs, int J) {
@@ -135,10 +273,24 @@ size_t icp_scratch_bytes(int pairs, int J) {
          al((size_t)pairs * 4) + al((size_t)pairs * 48);
 }
 
+size_t icp_scratch_bytes_ex(int pairs, int J, int estimator) {
+  return icp_scratch_bytes(pairs, J) + (estimator == 1 ? icp_plane_extra_bytes(pairs, J) : 0);
+}
+
 // T_init / T_out [pairs][3][4]; stats_out [pairs][4] doubles {fitness, inlier_rmse, converged, iterations} or nullptr
 void launch_icp_refine(const float* src, const float* ref, int pairs, int J, int K, int stride, float max_corr_dist,
                        int max_iter, float rel_fitness, float rel_rmse, const float* T_init, float* T_out,
                        double* stats_out, void* scratch, hipStream_t st) {
+  launch_icp_refine_ex(src, ref, pairs, J, K, stride, max_corr_dist, max_iter, rel_fitness, rel_rmse, T_init, T_out, stats_out, nullptr,
+                       0, nullptr, 0, 0, scratch, st);
+}
+
+// estimator 0: the point-to-point loop (scratch: icp_scratch_bytes); 1: point-to-plane with the normal of reference point i of a
+// pair at normals + pair * normals_cs + i * normals_ld (scratch: icp_scratch_bytes_ex).  stats5_out [pairs][5] doubles or nullptr.
+void launch_icp_refine_ex(const float* src, const float* ref, int pairs, int J, int K, int stride, float max_corr_dist,
+                          int max_iter, float rel_fitness, float rel_rmse, const float* T_init, float* T_out,
+                          double* stats_out, double* stats5_out, int estimator, const float* normals, int64_t normals_cs,
+                          int normals_ld, void* scratch, hipStream_t st) {
   char* p = reinterpret_cast<char*>(scratch);
   auto take = [&](size_t bytes) { char* r = p; p += (bytes + 255) & ~(size_t)255; return r; };
   float* cur = reinterpret_cast<float*>(take((size_t)pairs * J * 12));
@@ -150,6 +302,11 @@ void launch_icp_refine(const float* src, const float* ref, int pairs, int J, int
   double* state = reinterpret_cast<double*>(take((size_t)pairs * 32));
   int32_t* skip = reinterpret_cast<int32_t*>(take((size_t)pairs * 4));
   float* Tstep = reinterpret_cast<float*>(take((size_t)pairs * 48));
+  const bool plane = estimator == 1;
+  const int nch = icp_plane_chunks(J);
+  double* part = plane ? reinterpret_cast<double*>(take(icp_plane_part_bytes(pairs, J))) : nullptr;
+  double* nsing = plane ? reinterpret_cast<double*>(take((size_t)pairs * 8)) : nullptr;
+  if (plane) hipMemsetAsync(nsing, 0, (size_t)pairs * 8, st);
   const float r2 = max_corr_dist * max_corr_dist;
   hipMemsetAsync(state, 0, (size_t)pairs * 32, st);
   hipMemcpyAsync(Ta, T_init, (size_t)pairs * 48, hipMemcpyDeviceToDevice, st);
@@ -159,6 +316,17 @@ void launch_icp_refine(const float* src, const float* ref, int pairs, int J, int
   hipLaunchKernelGGL(icp_stats_kernel, dim3(pairs), dim3(256), 0, st, idx, d2, w, J, 0, rel_fitness, rel_rmse, state);
   float *Tp = Ta, *Tn = Tb;
   for (int it = 0; it < max_iter; ++it) {
+    if (plane) {
+      hipLaunchKernelGGL(icp_plane_accum_kernel, dim3(nch, pairs), dim3(PT), 0, st, (const float*)cur, ref, stride,
+                         PlaneNormals{normals, normals_cs, normals_ld}, (const int32_t*)idx, (const float*)w, J, K,
+                         (const double*)state, part);
+      hipLaunchKernelGGL(icp_plane_step_kernel, dim3((J + PT - 1) / PT, pairs), dim3(PT), 0, st, cur, J, nch, (const double*)part,
+                         (const double*)state, (const float*)Tp, Tn, nsing, skip);
+      hipLaunchKernelGGL(icp_nn_kernel, gq, dim3(QB * NW), 0, st, cur, ref, stride, J, K, r2, idx, d2, (const int32_t*)skip);
+      hipLaunchKernelGGL(icp_stats_kernel, dim3(pairs), dim3(256), 0, st, idx, d2, w, J, 1, rel_fitness, rel_rmse, state);
+      float* t = Tp; Tp = Tn; Tn = t;
+      continue;
+    }
     hipLaunchKernelGGL(icp_done_flags_kernel, dim3((pairs + 255) / 256), dim3(256), 0, st, state, pairs, skip);
     KabschArgs a{};
     a.src = cur; a.ref = ref; a.idx = idx; a.w = w; a.src_stride = (int64_t)J * 3; a.ref_stride = (int64_t)K * stride;
@@ -171,6 +339,7 @@ void launch_icp_refine(const float* src, const float* ref, int pairs, int J, int
   }
   hipMemcpyAsync(T_out, Tp, (size_t)pairs * 48, hipMemcpyDeviceToDevice, st);
   if (stats_out) hipMemcpyAsync(stats_out, state, (size_t)pairs * 32, hipMemcpyDeviceToDevice, st);
+  if (stats5_out) hipLaunchKernelGGL(icp_stats5_kernel, dim3((pairs + 255) / 256), dim3(256), 0, st, (const double*)state, (const double*)nsing, pairs, stats5_out);
 }
 
 }  // namespace dsir

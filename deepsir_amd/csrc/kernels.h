@@ -499,6 +499,13 @@ size_t icp_scratch_bytes(int pairs, int J);
 void launch_icp_refine(const float* src, const float* ref, int pairs, int J, int K, int stride, float max_corr_dist,
                        int max_iter, float rel_fitness, float rel_rmse, const float* T_init, float* T_out,
                        double* stats_out, void* scratch, hipStream_t st);
+// the same loop with the estimator chosen (0 point-to-point, 1 point-to-plane: the rule is stated in icp.hip's header) and stats of
+// five columns; icp_scratch_bytes_ex(.., 0) == icp_scratch_bytes(..)
+size_t icp_scratch_bytes_ex(int pairs, int J, int estimator);
+void launch_icp_refine_ex(const float* src, const float* ref, int pairs, int J, int K, int stride, float max_corr_dist,
+                          int max_iter, float rel_fitness, float rel_rmse, const float* T_init, float* T_out,
+                          double* stats_out, double* stats5_out, int estimator, const float* normals, int64_t normals_cs,
+                          int normals_ld, void* scratch, hipStream_t st);
 
 // ransac.hip — RANSAC pose from correspondences (network/DGR.py:7-36, :249-306 / open3d registration_ransac_*; the rule is stated in
 // the file's header), all pairs at once; and the mutual-nearest-neighbour list of dsir_feature_correspondences

@@ -484,22 +484,56 @@ class Engine:
         return {k: out[:, i] for i, k in enumerate(self.METRIC_NAMES)}
 
     # ------------------------------------------------------------------ measurement hooks
+    ICP_ESTIMATORS = {"point": 0, "plane": 1}
+
     def icp_refine(self, points_src, points_ref, T_init, max_corr_dist: float, max_iter: int = 30,
-                   rel_fitness: float = 1e-6, rel_rmse: float = 1e-6):
-        """open3d registration_icp (point-to-point) counterpart for P pairs (reference test.py:241-258, disabled there).
-        points_* [P,N,>=3] CUDA fp32, T_init [P,3,4] -> (T [P,3,4], stats [P,4] f64: fitness, inlier_rmse, converged, iters)."""
+                   rel_fitness: float = 1e-6, rel_rmse: float = 1e-6, estimator: str = "point", normals_ref=None,
+                   viewpoint=(0.0, 0.0, 0.0)):
+        """open3d registration_icp counterpart for P pairs (reference test.py:241-258, disabled there).
+        points_* [P,N,>=3] CUDA fp32, T_init [P,3,4] -> (T [P,3,4], stats [P,4] f64: fitness, inlier_rmse, converged, iters).
+        estimator="plane": the point-to-plane update (include/dsir.h, dsir_icp_refine_ex) and a fifth stats column, the identity
+        updates taken for a singular system.  Its normals of points_ref: ``normals_ref`` [P,K,3] if given, else columns 3..5 of
+        rows of 6 columns and more (the use_ppf layout), else estimated here - knn_pyramid on points_ref, estimate_normals on its
+        level-0 lists towards ``viewpoint`` - which needs a cloud the pyramid accepts (ValueError otherwise)."""
+        if estimator not in self.ICP_ESTIMATORS:
+            raise ValueError("estimator must be 'point' or 'plane'")
         points_src, points_ref = _chk(points_src, torch.float32, "points_src"), _chk(points_ref, torch.float32, "points_ref")
         T_init = _chk(T_init, torch.float32, "T_init")
         P, J, stride = points_src.shape
         K = points_ref.shape[1]
         assert points_ref.shape[0] == P and points_ref.shape[2] == stride and tuple(T_init.shape) == (P, 3, 4)
         T = self._empty((P, 3, 4))
-        stats = self._empty((P, 4), torch.float64)
+        if estimator == "point":
+            stats = self._empty((P, 4), torch.float64)
+            self._pre()
+            self._call(self.lib.dsir_icp_refine(self.h, _ptr(points_src), _ptr(points_ref), P, J, K, stride, float(max_corr_dist),
+                                                int(max_iter), float(rel_fitness), float(rel_rmse), _ptr(T_init), _ptr(T), _ptr(stats)))
+            self.sync()
+            return T, stats
+        if normals_ref is not None:
+            normals_ref = _chk(normals_ref, torch.float32, "normals_ref")
+            if tuple(normals_ref.shape) != (P, K, 3):
+                raise ValueError(f"normals_ref must be [{P}, {K}, 3], got {tuple(normals_ref.shape)}")
+        elif stride < 6:
+            normals_ref = self.icp_normals(points_ref, viewpoint)
+        stats = self._empty((P, 5), torch.float64)
         self._pre()
-        self._call(self.lib.dsir_icp_refine(self.h, _ptr(points_src), _ptr(points_ref), P, J, K, stride, float(max_corr_dist),
-                                            int(max_iter), float(rel_fitness), float(rel_rmse), _ptr(T_init), _ptr(T), _ptr(stats)))
+        self._call(self.lib.dsir_icp_refine_ex(self.h, _ptr(points_src), _ptr(points_ref), P, J, K, stride, float(max_corr_dist),
+                                               int(max_iter), float(rel_fitness), float(rel_rmse), _ptr(T_init), _ptr(T), 1,
+                                               _ptr(normals_ref), _ptr(stats)))
         self.sync()
         return T, stats
+
+    def icp_normals(self, points_ref, viewpoint=(0.0, 0.0, 0.0)):
+        """The normals icp_refine(estimator="plane") estimates when it is given none: knn_pyramid on points_ref [P,K,>=3], then
+        estimate_normals on the level-0 lists -> [P,K,3].  ValueError for a cloud the pyramid does not accept."""
+        K = points_ref.shape[1]
+        if K > self.max_points or level_sizes(K, self.cfg.sub_sampling_ratio)[len(self.cfg.d_out) - 1] < self.cfg.num_knn:
+            raise ValueError(f"estimator='plane' cannot estimate normals for a reference cloud of {K} points (the KNN pyramid takes "
+                             f"{64 * self.cfg.num_knn} .. max_points={self.max_points}): pass normals_ref, or rows that carry the "
+                             "normals in columns 3..5")
+        _, neigh, _, _ = self.knn_pyramid(points_ref)
+        return self.estimate_normals(points_ref, neigh, viewpoint)[0]
 
     RANSAC_CHUNK = 256                 # DSIR_RANSAC_CHUNK: correspondences a scoring workgroup stages per step
     RANSAC_MAX_HYPOTHESES = 1 << 20    # DSIR_RANSAC_MAX_HYPOTHESES

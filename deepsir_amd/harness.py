@@ -32,6 +32,7 @@ def inference_align(pairs: Sequence[Dict[str, np.ndarray]], model, num_reg_iter:
     ``in_flight`` > 1: the reference's one-pair-per-call loop fed AHEAD - the pairs go one by one to a
     ``deepsir_amd.serve.PairServer`` that keeps that many requests outstanding (same results bit for bit; the per-pair
     time is then the shard's wall time divided by its size).
+    ``pose_opt='icp'`` / ``'icp_plane'``: ICP on the raw clouds from the last pose, point-to-point / point-to-plane.
     ``pose_opt='ransac'``: DGR's safeguard (network/DGR.py:249-306) over the last iteration's correspondences, see below;
     ``safeguard_wsum``: only pairs whose summed sigmoid inlier weight is below it take the RANSAC pose (DGR.py:273-304).
     Returns (pred_transforms_all [n_pairs, n_iter+1, 3, 4], stats [n_pairs, 5]) gathered over ranks."""
@@ -85,6 +86,13 @@ def inference_align(pairs: Sequence[Dict[str, np.ndarray]], model, num_reg_iter:
             T_opt, _ = _aux_engine(model, data).icp_refine(data["points_src"].float(), data["points_ref"].float(),
                                                 transforms[-1].contiguous(), 2.0 * voxel_size)
             transforms.append(T_opt)
+        elif pose_opt == "icp_plane":
+            # the same refinement with the point-to-plane estimator (open3d's TransformationEstimationPointToPlane; include/dsir.h,
+            # dsir_icp_refine_ex), same radius; the normals are those of use_ppf rows where the data has them, else estimated from
+            # the reference cloud's level-0 neighbour lists
+            T_opt, _ = _aux_engine(model, data).icp_refine(data["points_src"].float(), data["points_ref"].float(),
+                                                           transforms[-1].contiguous(), 2.0 * voxel_size, estimator="plane")
+            transforms.append(T_opt)
         elif pose_opt == "tune":
             # pose_optimization with use_tune (test.py:218-239; off in the reference): Adam fine-tune of the 6-D-rotation
             # pose on the last iteration's correspondences, weights = sigmoid of its inlier logits, distances in units
@@ -110,7 +118,7 @@ def inference_align(pairs: Sequence[Dict[str, np.ndarray]], model, num_reg_iter:
         elif pose_opt is None:
             transforms.append(transforms[-1].detach())        # pose_optimization == identity (test.py:215-216, :406-408)
         else:
-            raise ValueError("pose_opt must be None, 'icp', 'tune' or 'ransac'")
+            raise ValueError("pose_opt must be None, 'icp', 'icp_plane', 'tune' or 'ransac'")
         T = torch.stack(transforms, dim=1).cpu().numpy()      # [B, n_iter+1, 3, 4]
         preds.append(T)
         gt = data["transform_gt"].cpu().numpy()

@@ -31,7 +31,7 @@ def main():
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--limit", type=int, default=0)
-    ap.add_argument("--pose-opt", choices=["none", "icp", "tune", "ransac"], default="none")
+    ap.add_argument("--pose-opt", choices=["none", "icp", "icp_plane", "tune", "ransac"], default="none")
     ap.add_argument("--pipeline", choices=["align", "feat"], default="align")
     ap.add_argument("--ransac", action="store_true", help="with --pipeline feat: descriptors -> mutual nearest neighbours -> RANSAC pose")
     ap.add_argument("--num-sub", type=int, default=1024, help="key points per cloud of the feat pipeline")

@@ -290,6 +290,32 @@ int dsir_icp_refine(dsir_ctx* ctx, const float* points_src, const float* points_
                     float max_corr_dist, int max_iter, float rel_fitness, float rel_rmse, const float* T_init,
                     float* T_out, double* stats);
 
+/* dsir_icp_refine with the transformation estimator chosen: estimator 0 = point-to-point (open3d's
+ * TransformationEstimationPointToPoint: byte for byte what dsir_icp_refine writes), 1 = point-to-plane (open3d's
+ * TransformationEstimationPointToPlane; open3d is not pinned, so parity is unpinned: the rule is this engine's own, stated in the
+ * header of csrc/icp.hip and restated in tests/icp_plane_host.py).  Arguments as for dsir_icp_refine, plus
+ *   normals_ref [P][K][3] (device) or NULL.  Estimator 1 with NULL reads the normals from columns 3..5 of the points_ref rows
+ *               (the use_ppf row layout), which requires stride >= 6: NULL with stride < 6 is "bad arguments".  Estimator 0
+ *               does not read them.
+ *   stats       [P][5] float64 or NULL: the four values of dsir_icp_refine, then the number of identity updates taken for a
+ *               singular system (always 0 with estimator 0).
+ * The loop - first search, fitness, inlier RMSE from point distances, convergence test, max_iter - is dsir_icp_refine's; only
+ * the update differs: with r = (s - t) . n and J = [s x n ; n] over the correspondences (s moved source point, t target point,
+ * n target normal), A = sum J J^T and b = sum J r in fp64, A x = -b solved in fp64, update R = Rz(x2) Ry(x1) Rx(x0),
+ * t = (x3, x4, x5), applied and composed onto T as the Kabsch step's transform is.  Corner cases of estimator 1 (none is an error):
+ *   singular system   with fewer than 6 contributing correspondences, or a singular system, the update is the identity and
+ *                     is counted in stats[4].  Singular = LDL^T without pivoting of A scaled to unit diagonal meets a pivot
+ *                     below 1e-10 (csrc/icp_plane.h gives the reason for the value); a zero diagonal entry is singular.  A
+ *                     planar target (all normals parallel) is the plain example: T_out = T_init.
+ *   zero normal       (dsir_estimate_normals' degenerate output) the correspondence contributes nothing.
+ *   non-finite        a non-finite normal or reference coordinate takes that correspondence out of the update (fitness and
+ *                     RMSE are the search's, as ever).  A pair with a non-finite source point takes identity updates from
+ *                     then on (counted in stats[4]), so its T_out stays a finite rigid transform; other pairs are untouched.
+ * Same bytes on every run (fixed partition of the sums, no floating-point atomics); pairs are independent, bit for bit. */
+int dsir_icp_refine_ex(dsir_ctx* ctx, const float* points_src, const float* points_ref, int pairs, int J, int K, int stride,
+                       float max_corr_dist, int max_iter, float rel_fitness, float rel_rmse, const float* T_init,
+                       float* T_out, int estimator, const float* normals_ref, double* stats);
+
 /* Replaces the `use_tune` branch of pose_optimization (test.py:209-239): transformation_finetune (test.py:159-207) with
  * HighDimSmoothL1Loss (test.py:103-131) over the network's last correspondences, the pose re-parametrised as
  * network/DGR.py's Transformation (6-D rotation + translation, :60-132) and fitted by Adam (lr 0.1, ExponentialLR 0.999)
