@@ -567,3 +567,86 @@ class TrainBatches:
         items = self.voxels(indices)
         vox, counts, poses = self.assemble(items)
         return self.finish(vox, counts, poses, indices, [it[3] for it in items])
+
+
+# ================================================================================================== 3DMatch train tables
+def list_3dmatch_fragments(root: str, split: str) -> Dict[str, List[str]]:
+    """The fragments of a 3DMatch download as the reference's preprocessing lists them (dataloader/3DMatch_preprocess.py:32-47):
+    scenes in the order of `<root>/scene_list_{split}.txt`, their `seq*` folders sorted, the `*.ply` of a sequence sorted by the
+    integer after the last '_' -> {scene: [ids]}, an id being `scene/seq/name` (no extension)."""
+    from .overlap import fragment_sort_key
+    with open(os.path.join(root, f"scene_list_{split}.txt")) as f:
+        scenes = [ln.strip() for ln in f.read().splitlines() if ln.strip()]
+    out: Dict[str, List[str]] = {}
+    for scene in scenes:
+        out[scene] = []
+        for seq in sorted(os.listdir(os.path.join(root, scene))):
+            if not seq.startswith("seq"):
+                continue
+            names = [fn.split(".")[0] for fn in os.listdir(os.path.join(root, scene, seq)) if fn.endswith("ply")]
+            out[scene] += sorted([f"{scene}/{seq}/{n}" for n in names], key=fragment_sort_key)
+    return out
+
+
+class _EngineSearch:
+    """The `overlap.Search` of an engine: one cell index per fragment list (a scene), kept between the count and the fill pass; job
+    lists are cut so that no call's job table and neighbour lists exceed `max_jobs_bytes`."""
+
+    def __init__(self, engine, max_jobs_bytes: int):
+        self.engine, self.max_jobs_bytes = engine, int(max_jobs_bytes)
+        self._frags, self._index = None, None
+
+    def chunks(self, jobs: np.ndarray, sizes: np.ndarray, fill: bool) -> List[Tuple[int, int]]:
+        cost = 16 + (4 * sizes[jobs[:, 0]] if fill else np.zeros(len(jobs), np.int64))
+        out, start, used = [], 0, 0
+        for k, c in enumerate(cost.tolist()):
+            if k > start and used + c > self.max_jobs_bytes:
+                out.append((start, k))
+                start, used = k, 0
+            used += c
+        if len(jobs) > start:
+            out.append((start, len(jobs)))
+        return out
+
+    def __call__(self, fragments: List[np.ndarray], jobs: np.ndarray, radius: float, fill: bool):
+        if self._frags is not fragments:
+            sizes = np.array([len(f) for f in fragments], np.int64)
+            host = np.concatenate([np.asarray(f, np.float32).reshape(-1, 3) for f in fragments])
+            ok = np.isfinite(host).all(1)
+            bounds = np.concatenate([host[ok].min(0), host[ok].max(0)]) if ok.any() else np.zeros(6, np.float32)
+            self._index = self.engine.nn_index(_to_device(self.engine, host), np.concatenate([[0], np.cumsum(sizes)]), radius, bounds)
+            self._frags, self._sizes = fragments, sizes
+        jobs = np.asarray(jobs, np.int32).reshape(-1, 2)
+        counts, lists = [], []
+        for a, b in self.chunks(jobs, self._sizes, fill):
+            c, flat = self._index.search(jobs[a:b], fill=fill)
+            counts.append(c.cpu().numpy())
+            if fill:
+                rows, flat = self._index.rows(jobs[a:b]), flat.cpu().numpy()
+                lists += [flat[rows[k]:rows[k + 1]] for k in range(b - a)]
+        return (np.concatenate(counts) if counts else np.zeros(0, np.int32)), (lists if fill else None)
+
+
+def preprocess_3dmatch(root: str, savepath: str, split: str, engine, downsample: float = 0.03, overlap_thres: float = 0.30,
+                       max_jobs_bytes: int = 1 << 28, batch: int = 16):
+    """dataloader/3DMatch_preprocess.py on the device: writes `3DMatch_{split}_{downsample:.3f}_points.pkl` ({id: float64 [n, 3]}:
+    every fragment read with `read_ply_xyz`, thinned by `Engine.voxel_downsample` - the engine's voxel rule -, then moved by
+    `<id>.pose.npy` in float64 on the host), `_overlap.pkl` ({"src@ref": ratio}) and `_keypts.pkl` ({"src@ref": int32 [m, 2]}) under
+    `savepath`, the last two for the pairs i < j of a scene whose share of src points with a ref point closer than `downsample`
+    (`Engine.nn_index` on the float32 cast: csrc/overlap.hip) exceeds `overlap_thres`.  Existing files are reloaded, not recomputed.
+    `ThreeDMatchTrain(root_of(savepath), engine)` and the reference's loader read what it wrote when `savepath` is
+    `<root>/3dmatch_train_val`.  -> (points, overlap, keypts)."""
+    from .overlap import write_3dmatch_tables
+
+    def load_points(ids: List[str]) -> Dict[str, np.ndarray]:
+        pts: Dict[str, np.ndarray] = {}
+        for s in range(0, len(ids), batch):
+            part = ids[s:s + batch]
+            vox = _voxelize(engine, [read_ply_xyz(os.path.join(root, i + ".ply")) for i in part], float(downsample))
+            for i, v in zip(part, vox):
+                M = np.load(os.path.join(root, i + ".pose.npy")).astype(np.float64)
+                pts[i] = v[:, :3].cpu().numpy().astype(np.float64) @ M[:3, :3].T + M[:3, 3]
+        return pts
+
+    return write_3dmatch_tables(savepath, split, float(downsample), list_3dmatch_fragments(root, split), load_points,
+                                _EngineSearch(engine, max_jobs_bytes), overlap_thres)

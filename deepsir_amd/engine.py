@@ -708,6 +708,53 @@ class Engine:
         return self._train_ops().inlier_targets_radius(src, ref, _chk(idx, torch.int32, "idx"), _chk(transform_gt, torch.float32, "transform_gt"),
                                                        radius)
 
+    # ------------------------------------------------------------------ fragment overlap (csrc/overlap.hip; the rule: deepsir_amd/overlap.py)
+    def nn_index(self, points, offsets, radius: float, bounds=None):
+        """The sparse cell index of F ragged fragments (points [total, C] fp32, offsets [F + 1] on the host), built once; its
+        ``search(jobs, poses=None, fill=False)`` runs job lists against it (``train.NNIndex``)."""
+        return self._train_ops().nn_index(_chk(points, torch.float32, "points"), offsets, radius, bounds)
+
+    def nn_within(self, points, offsets, jobs, radius: float, poses=None, fill=None, bounds=None):
+        """Radius-bounded nearest neighbour of one fragment in another, for a list of jobs: points [total, C] fp32 holding F ragged
+        fragments (offsets [F + 1], host), jobs [n, 2] (host) of (query fragment, target fragment), poses None or [n, 3, 4] fp32
+        (the query is moved first) -> (counts [n] i32: matched queries per job, nn).  fill: None, or the positions in ``jobs``
+        whose neighbour lists are wanted; nn is then a list with one i32 [n_query] tensor per such job (original index in the
+        target, or -1).  Raises ValueError with the library's reason, launching nothing, where the call is refused (radius <= 0,
+        a job index out of range, an extent of more than 2^21 - 2 cells; the last needs the bounds, which are reduced on the
+        device first unless ``bounds`` gives them)."""
+        ops = self._train_ops()
+        off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64).reshape(-1))
+        jobs = np.ascontiguousarray(np.asarray(jobs, dtype=np.int32).reshape(-1, 2))
+        why = ops.nn_refusal(off, jobs, radius) if off.size >= 2 else "nn_within: offsets [F + 1] expected"
+        if why is not None:
+            raise ValueError(why)
+        if poses is not None:
+            poses = _chk(poses, torch.float32, "poses")
+        index = self.nn_index(points, off, radius, bounds)
+        counts, _ = index.search(jobs, poses)
+        if fill is None:
+            return counts, None
+        sel = np.asarray(fill, dtype=np.int64).reshape(-1)
+        sub = jobs[sel]
+        sub_poses = None if poses is None else poses[torch.as_tensor(sel, device=poses.device)].contiguous()
+        _, flat = index.search(sub, sub_poses, fill=True)
+        rows = index.rows(sub)
+        return counts, [flat[rows[k]:rows[k + 1]] for k in range(len(sub))]
+
+    def overlap_ratio(self, src, ref, T, radius: float) -> np.ndarray:
+        """The share of every pair's source points that have a reference point within ``radius`` under the pose: src [P, J, C],
+        ref [P, K, C], T [P, 3, 4] fp32 -> float64 [P].  The kernels of ``nn_within`` with one job per pair."""
+        src, ref, T = _chk(src, torch.float32, "src"), _chk(ref, torch.float32, "ref"), _chk(T, torch.float32, "T")
+        P, J, stride = src.shape
+        K = ref.shape[1]
+        if ref.shape[0] != P or ref.shape[2] != stride or tuple(T.shape) != (P, 3, 4):
+            raise ValueError("overlap_ratio: src [P,J,C], ref [P,K,C] and T [P,3,4] expected")
+        points = torch.cat([src.reshape(P * J, stride), ref.reshape(P * K, stride)], 0)
+        offsets = np.concatenate([np.arange(P + 1, dtype=np.int64) * J, P * J + np.arange(1, P + 1, dtype=np.int64) * K])
+        jobs = np.stack([np.arange(P), P + np.arange(P)], 1)
+        counts, _ = self.nn_within(points, offsets, jobs, radius, poses=T)
+        return counts.cpu().numpy().astype(np.float64) / max(J, 1)
+
     def enable_graph(self, on=True):
         """Replay dsir_register through a captured hipGraph (same buffers on every call; one graph per call signature)."""
         if on:

@@ -391,6 +391,80 @@ class _Ops:
         return labels
 
 
+    # ---- fragment overlap: radius-bounded nearest neighbour over a sparse cell index (csrc/overlap.hip; the rule: deepsir_amd/overlap.py)
+    def finite_bounds(self, points: torch.Tensor) -> np.ndarray:
+        """min xyz, max xyz over the finite rows of points [n][C] (zeros when there is none): one reduction, one 24-byte read."""
+        out = self.empty(6)
+        self._launch("dsir_t_finite_bounds", _ptr(points) if points.shape[0] else None, points.shape[1], points.shape[0], _ptr(out))
+        return out.cpu().numpy()
+
+    def nn_index(self, points: torch.Tensor, offsets, radius: float, bounds=None) -> "NNIndex":
+        """The cell index of F ragged fragments (points [total][C] fp32 on the device, offsets [F + 1] on the host) for searches
+        within `radius`, built once.  bounds: min xyz, max xyz of the finite points when the caller knows them (host), else they are
+        reduced on the device.  Raises ValueError, before any launch of the build, where the library refuses the call."""
+        off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64).reshape(-1))
+        if points.dim() != 2 or points.shape[1] < 3 or off.size < 2 or int(off[-1]) != points.shape[0]:
+            raise ValueError("nn_index: points [total, C >= 3] and offsets [F + 1] ending at total expected")
+        why = self.nn_refusal(off, None, radius)            # everything but the extent: before the reduction is launched
+        if why is not None:
+            raise ValueError(why)
+        if bounds is None:
+            bounds = self.finite_bounds(points)
+        bounds = np.ascontiguousarray(np.asarray(bounds, dtype=np.float32).reshape(6))
+        return NNIndex(self, points, off, float(radius), bounds)
+
+    def nn_refusal(self, offsets: np.ndarray, jobs: Optional[np.ndarray], radius: float, bounds: Optional[np.ndarray] = None) -> Optional[str]:
+        """dsir_t_nn_within_check: why the library would refuse the call (host only, nothing is launched), or None.  offsets int64
+        [F + 1], jobs int32 [n][2] or None, both contiguous; bounds None: checked with an empty extent."""
+        b = np.zeros(6, np.float32) if bounds is None else bounds
+        why = self.lib.dsir_t_nn_within_check(offsets.ctypes.data, int(offsets.size - 1), None if jobs is None else jobs.ctypes.data,
+                                              0 if jobs is None else len(jobs), float(radius), b.ctypes.data)
+        return None if why is None else why.decode()
+
+
+class NNIndex:
+    """What ``_Ops.nn_index`` built: ``search`` runs job lists against it (count mode, or fill mode with the neighbour lists)."""
+
+    def __init__(self, ops: "_Ops", points: torch.Tensor, offsets: np.ndarray, radius: float, bounds: np.ndarray):
+        self.ops, self.points, self.offsets, self.radius, self.bounds = ops, points, offsets, radius, bounds
+        self.fragments = int(offsets.size - 1)
+        self._refuse(None)
+        nb = int(ops.lib.dsir_t_nn_index_scratch(int(offsets[-1]), self.fragments))
+        if nb == 0:
+            raise ValueError("nn_index: shape refused")
+        self.index = torch.empty(nb, dtype=torch.uint8, device=ops.device)
+        ops._launch("dsir_t_nn_index_build", _ptr(points) if points.shape[0] else None, points.shape[1], self.offsets.ctypes.data,
+                    self.fragments, self.radius, self.bounds.ctypes.data, _ptr(self.index))
+
+    def _refuse(self, jobs: Optional[np.ndarray]) -> None:
+        why = self.ops.nn_refusal(self.offsets, jobs, self.radius, self.bounds)
+        if why is not None:
+            raise ValueError(why)
+
+    def search(self, jobs, poses: Optional[torch.Tensor] = None, fill: bool = False):
+        """jobs [n][2] (host) of (query fragment, target fragment), poses None or [n][3][4] fp32 on the device ->
+        (counts [n] i32 on the device, nn): nn is None in count mode, else the jobs' query rows concatenated in job order
+        (i32, original index in the target or -1; ``rows`` below gives each job's slice)."""
+        ops = self.ops
+        jobs = np.ascontiguousarray(np.asarray(jobs, dtype=np.int32).reshape(-1, 2))
+        self._refuse(jobs)
+        n = len(jobs)
+        if poses is not None and (tuple(poses.shape) != (n, 3, 4) or poses.dtype != torch.float32 or not poses.is_contiguous()):
+            raise ValueError("nn_within: poses [n_jobs, 3, 4] fp32 contiguous expected")
+        counts = ops.empty(n, dtype=torch.int32)
+        nn = ops.empty(int(self.rows(jobs)[-1]), dtype=torch.int32) if fill else None
+        if n:
+            scratch = torch.empty(int(ops.lib.dsir_t_nn_within_scratch(n)), dtype=torch.uint8, device=ops.device)
+            ops._launch("dsir_t_nn_within", _ptr(self.index), self.offsets.ctypes.data, self.fragments, jobs.ctypes.data, n, _ptr(poses),
+                        self.radius, self.bounds.ctypes.data, _ptr(counts), _ptr(nn) if fill and nn.numel() else None, _ptr(scratch))
+        return counts, nn
+
+    def rows(self, jobs) -> np.ndarray:
+        """[n + 1]: where each job's query rows start in the ``nn`` of a fill-mode search."""
+        jobs = np.asarray(jobs, dtype=np.int64).reshape(-1, 2)
+        return np.concatenate([[0], np.cumsum(np.diff(self.offsets)[jobs[:, 0]])]).astype(np.int64)
+
+
 class MatchKeys:
     """A batch's ground-truth matches as ``_Ops.match_keys`` leaves them: keys int64 [n'] sorted within each pair, offsets [P + 1] i32.
     May be handed over as ``data['matches']`` in place of the lists, so that a loader builds it once per batch."""

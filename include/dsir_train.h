@@ -240,6 +240,42 @@ int dsir_t_augment(void* stream, const float* in, const int32_t* counts, int clo
 int dsir_t_augment_gt(void* stream, const double* M, const void* params_src, const void* params_ref, const double* centroids_src,
                       const double* centroids_ref, int pairs, int reference_gt, float* transform_gt);
 
+/* ---- fragment overlap: radius-bounded nearest neighbour of one ragged cloud in another (csrc/overlap.hip) ------------------------
+ * The core of the reference's offline dataloader/3DMatch_preprocess.py:82-89 (cv2.BFMatcher.match + distance < voxel size) for every
+ * fragment pair of a scene; cv2 is not installable here: parity is unpinned, the engine owns the rule (deepsir_amd/overlap.py,
+ * nn_within_host, restates it in numpy float32; the full statement and the lattice argument head csrc/overlap.hip) -
+ *   d2 = (dx dx + dy dy) + dz dz, d = b - a, fp32, every operation rounded on its own (the rule of the match lists above);
+ *   the neighbour of a is the b of smallest d2, ties to the lower original index of b; a match is d2 < r r, strict, r r one fp32
+ *   product; a non-finite a matches nothing, a non-finite b is never a neighbour, an empty side gives count 0; with a pose per
+ *   job the query is moved first by the match lists' expression ((T0 x + T1 y) + T2 z) + T3.
+ * points [total][stride] (device) holds `fragments` ragged clouds, offsets [fragments + 1] (HOST, int64) their rows; jobs [n_jobs][2]
+ * (HOST, int32) = (query fragment, target fragment); bounds [6] (HOST) = min xyz, max xyz over all finite points, which
+ * dsir_t_finite_bounds computes on the device (bounds_dev [6] fp32; zeros when no point is finite).
+ *
+ * dsir_t_nn_within_check (host only, no device call): NULL when the call is acceptable, else the reason - radius <= 0 or not finite,
+ * bounds not finite or inverted, an axis that needs more than 2^21 - 2 cells of edge radius (1 + 2^-10), offsets not ascending from 0,
+ * more than 2^30 points or 2^20 fragments, a job index outside [0, fragments) (jobs may be NULL to check the index alone), a job
+ * list of more than 2^31 - 1 query rows.  Both operators below run it first and return an error WITHOUT a launch when it objects.
+ *
+ * _index_build: the sparse cell index of every fragment on one lattice, once per call - per fragment its points sorted by a 64-bit
+ *   cell key (hipCUB segmented radix sort), xyz + original index as float4, and the fragment's cell box.  index:
+ *   dsir_t_nn_index_scratch(total, fragments) bytes (0: shape refused), linear in total, never in the box's cell count.
+ * _within: per job, one lane per query point in the query fragment's cell order; 9 key-interval lookups in the target fragment.
+ *   counts [n_jobs] (device, required) = matched queries per job (integer adds only); nn (device, may be NULL = count mode):
+ *   the jobs' query rows concatenated in job order, nn[row] = original index in the target fragment or -1.  poses (device, may be
+ *   NULL) [n_jobs][3][4].  job_scratch: dsir_t_nn_within_scratch(n_jobs) bytes.  The same index, offsets, bounds and radius as _build.
+ * No floating-point atomics, no allocation, no host synchronisation between the launches; two runs write the same bytes, and a
+ * job's result does not depend on the rest of the list. */
+const char* dsir_t_nn_within_check(const int64_t* offsets, int fragments, const int32_t* jobs, int64_t n_jobs, float radius,
+                                   const float* bounds);
+int dsir_t_finite_bounds(void* stream, const float* points, int stride, int64_t n, float* bounds_dev);
+size_t dsir_t_nn_index_scratch(int64_t total, int fragments);
+int dsir_t_nn_index_build(void* stream, const float* points, int stride, const int64_t* offsets, int fragments, float radius,
+                          const float* bounds, void* index);
+size_t dsir_t_nn_within_scratch(int64_t n_jobs);
+int dsir_t_nn_within(void* stream, const void* index, const int64_t* offsets, int fragments, const int32_t* jobs, int64_t n_jobs,
+                     const float* poses, float radius, const float* bounds, int32_t* counts, int32_t* nn, void* job_scratch);
+
 #ifdef __cplusplus
 }
 #endif
