@@ -704,9 +704,8 @@ int build_pyramid(dsir_ctx* c, const float* points, int stride, int clouds, int 
       if (ngrid) launch_knn16_grid_levels(points, (int64_t)n * stride, stride, ngrid, gn, clouds, gout, neigh_cs, gscr, st);
       launch_knn_small_levels(points, (int64_t)n * stride, stride, clouds, jobs, st);
       for (int l = 0; l + 1 < g.num_layers; ++l)
-        if (nn1_by_grid(l))      // level l + 1 has a grid (nn1_by_grid): the search walks it, its queries in level l's cell order when that has one
-          launch_nn1_grid(points, (int64_t)n * stride, stride, p.nl[l], p.nl[l + 1], clouds, interp + p.off[l], p.S, gscr[grid_of[l + 1]], st,
-                          grid_of[l] >= 0 ? gscr[grid_of[l]] : nullptr);
+        if (nn1_by_grid(l))      // level l + 1 has a grid, hence the larger level l too: the search walks the one, its queries in the cell order of the other
+          launch_nn1_grid(p.nl[l], p.nl[l + 1], clouds, interp + p.off[l], p.S, gscr[grid_of[l + 1]], gscr[grid_of[l]], st);
       c->ws.release(mark);
       launch_copy_sub_levels(neigh, neigh_cs, lv, clouds, sub, sub_cs, st);
       return 0;
@@ -719,10 +718,10 @@ int build_pyramid(dsir_ctx* c, const float* points, int stride, int clouds, int 
       if (c->ws.overflow) return fail(c, "workspace exhausted in the KNN pyramid");
       launch_knn16_grid(points, (int64_t)n * stride, stride, p.nl[l], clouds, neigh + (int64_t)p.off[l] * kKnn, neigh_cs,
                         scratch, st);
-      // this level's points are the support of the level above's interpolation search: it walks the grid just built
+      // this level's points are the support of the level above's interpolation search: it walks the grid just built (the level above
+      // is no smaller, so it took this branch too and prev_scratch is its grid)
       if (l > 0 && nn1_by_grid(l - 1))
-        launch_nn1_grid(points, (int64_t)n * stride, stride, p.nl[l - 1], p.nl[l], clouds, interp + p.off[l - 1], p.S, scratch, st,
-                        prev_scratch);
+        launch_nn1_grid(p.nl[l - 1], p.nl[l], clouds, interp + p.off[l - 1], p.S, scratch, prev_scratch, st);
       prev_scratch = scratch;
     } else {
       prev_scratch = nullptr;
