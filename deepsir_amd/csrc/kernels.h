@@ -430,16 +430,9 @@ struct ScreenOrder {
   long long cand_rs = 0;             // filled by launch_nn_screen: rows of the launch (pairs x J) = the stride between the slots of the entry lists
 };
 int nn_screen_rows_per_block(int J);   // rows a workgroup of the screening owns for this J (what tile lists are built for)
-int nn_screen_max_bound_tiles();
-void launch_centroid_argmin(const void* ah, const void* al, const void* ch, const void* cl, const float* cn2, int pairs, int J, int nt,
-                            int32_t* tstar, hipStream_t st);
-void launch_tile_T(const void* ah, const void* al, const float* sa, const int32_t* rows, const int32_t* tstar, const void* bh, const void* bl,
-                   const float* sbp, int pairs, int J, int K, int nt, float* T, hipStream_t st);
-void launch_tile_bound(const void* ah, const void* al, const float* sa, const int32_t* rows, const float* T, const void* ch, const void* cl,
-                       const float* cn2, const float* rad, int pairs, int J, int nt, int32_t* tlist, int32_t* tcount, int tl_stride,
-                       int32_t* rborder, hipStream_t st);
 // nn_prune.hip: column order (Morton order of the ref points) + tile bounds once per registration; row order, upper bounds and
-// tile lists per iteration (acc, optional: device 2 x u64 running totals {tile products kept, tile products in all})
+// tile lists per iteration, from a bound pass of its own on the screening's arithmetic (screen_bound.h) (acc, optional: device
+// 2 x u64 running totals {tile products kept, tile products in all})
 bool nn_prune_supported(int pairs, int J, int K);
 size_t nn_prune_scratch_bytes(int pairs, int J, int K);
 int launch_prune_ref(const float* ref_xyz, int64_t xyz_cloud_stride, const float* desc_ref, const void* bh, const void* bl, const float* sb,

@@ -20,16 +20,18 @@
 // visited at 16 384 points, 35 - 61 % at 65 536, ~all at 5 000 (79 tiles: the search is not worth pruning there and is not).
 // All arithmetic of the bounds is fp32 with explicit safety margins (the exact distances they are compared with are fp32
 // evaluations, too): margins of 2e-5 (1 + |a|^2 + |b|^2) against evaluation errors below 4e-6 (1 + ...) - see the kernels.
+// The bound pass (centroid_argmin_kernel, tile_T_kernel, tile_bound_kernel) runs the screening's own MFMA chain and bound
+// arithmetic: screen_bound.h, the one definition tests/test_gpu_screen_bound.py proves the inequality for.
 #include <hipcub/hipcub.hpp>
 
+#include <type_traits>
+
 #include "kernels.h"
-#include "device_utils.h"
+#include "screen_bound.h"
 
 namespace dsir {
 
 namespace {
-
-constexpr int TILE = 64;            // = the screening's column tile (DSIR_SCREEN_BC)
 
 inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 inline int grid_for(int64_t n) { const int64_t g = (n + 255) / 256; return (int)(g < 1 ? 1 : (g > 65535 ? 65535 : g)); }
@@ -108,13 +110,13 @@ __global__ __launch_bounds__(256) void tile_stats_kernel(const float* __restrict
   const int pair = (int)(tg / nt), t = (int)(tg % nt);
   const float* D = desc + (int64_t)pair * K * 64;
   const int32_t* C = cols + (int64_t)pair * K;
-  const int n = min(TILE, K - t * TILE);
+  const int n = min(SBC, K - t * SBC);
   float s = 0.f;
-  for (int i = 0; i < n; ++i) s += D[(int64_t)C[t * TILE + i] * 64 + lane];
+  for (int i = 0; i < n; ++i) s += D[(int64_t)C[t * SBC + i] * 64 + lane];
   const float c = s / (float)n;
   float r2 = 0.f;
   for (int i = 0; i < n; ++i) {
-    const float d = D[(int64_t)C[t * TILE + i] * 64 + lane] - c;
+    const float d = D[(int64_t)C[t * SBC + i] * 64 + lane] - c;
     r2 = fmaxf(r2, wave_sum(d * d));
   }
   const float c2 = wave_sum(c * c);
@@ -131,7 +133,7 @@ __global__ __launch_bounds__(256) void tile_stats_kernel(const float* __restrict
 // the aggregation chain (model.py:232-233: |a| = |b| = 1 up to rounding); it is not offered to caller-supplied descriptors
 // (dsir_nn_match searches exhaustively or through the unpruned screening, whose bound carries every column's own norm).
 // per src row: the sort key of the row order (its nearest-centroid tile) and the upper bound from the previous iteration's match,
-// T = D(a, b_prev) + margin, D evaluated as nn_match.hip evaluates it (fmaf chain over the channels, the reference's roundings);
+// T = D(a, b_prev) + margin, D evaluated as nn_match.hip evaluates it (exact_dist);
 // iteration 0 (idx_prev == nullptr): +inf (tile_T_kernel supplies the bound)
 __global__ __launch_bounds__(256) void row_prep_kernel(const float* __restrict__ a, const float* __restrict__ b,
                                                        const float* __restrict__ sa, const float* __restrict__ sb,
@@ -144,18 +146,10 @@ __global__ __launch_bounds__(256) void row_prep_kernel(const float* __restrict__
     if (idx_prev && !keep_all) {
       int k = idx_prev[i];
       k = k < 0 ? 0 : (k >= K ? K - 1 : k);
-      const float4* ap = reinterpret_cast<const float4*>(a + i * 64);
-      const float4* bp = reinterpret_cast<const float4*>(b + ((int64_t)pair * K + k) * 64);
-      float acc = 0.f;
-#pragma unroll
-      for (int q = 0; q < 16; ++q) {
-        const float4 u = ap[q], v = bp[q];
-        acc = fmaf(u.x, v.x, acc); acc = fmaf(u.y, v.y, acc); acc = fmaf(u.z, v.z, acc); acc = fmaf(u.w, v.w, acc);
-      }
       const float san = sa[i], sbn = sb[(int64_t)pair * K + k];
-      const float d = __fadd_rn(__fmaf_rn(acc, -2.f, san), sbn);
+      const float d = exact_dist(reinterpret_cast<const float4*>(a + i * 64), b + ((int64_t)pair * K + k) * 64, san, sbn);
       // non-finite rows get an infinite bound (they visit every tile)
-      if (d == d) bound = d + 2e-5f * (1.f + san + sbn);
+      if (d == d) bound = d + kMarginExact * (1.f + san + sbn);
     }
     T[i] = bound;
     key[i] = ((uint32_t)pair << tbits) | (uint32_t)tstar[i];
@@ -185,11 +179,233 @@ __global__ void prune_account_kernel(const int32_t* __restrict__ tcount, int n, 
   if (threadIdx.x == 0) atomicAdd(acc + 1, (unsigned long long)n * (unsigned long long)nt);
 }
 
+// ---- the bound pass on the matrix core: which column tiles must a row block visit?
+// A tile t (SBC ref columns, centroid c_t, radius r_t) can be skipped by a row whose minimum is known to be <= T iff
+// (|a - c_t| - r_t)_+^2 > T.  |a - c_t|^2 is bounded from BELOW by the screening's own bound (screen_bound.h): the centroids are split
+// like descriptors and L(a, c_t) <= D(a, c_t) comes out of the same six-MFMA chain (rows x nt centroids: 1/64 of a search).
+// Block = 8 waves x RT row tiles = one row block of the screening (rows in the given order); per 16-centroid step every lane
+// tests its column against its 4 RT rows, the wave folds the answers into a 16-bit column mask, and the tiles some row needs
+// are compacted into the block's list.
+template <int RT>
+__global__ __launch_bounds__(512) void tile_bound_kernel(const _Float16* __restrict__ Ah, const _Float16* __restrict__ Al,
+                                                         const float* __restrict__ sa, const int32_t* __restrict__ rows,
+                                                         const float* __restrict__ T, const _Float16* __restrict__ Ch,
+                                                         const _Float16* __restrict__ Cl, const float* __restrict__ cn2,
+                                                         const float* __restrict__ rad, int J, int nt, int32_t* __restrict__ tlist,
+                                                         int32_t* __restrict__ tcount, int tl_stride) {
+  __shared__ unsigned int flags[kMaxBoundTiles / 16];
+  const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int fr = lane & 15, fq = lane >> 4;
+  const int rb = blockIdx.x, pair = blockIdx.y, nrb = gridDim.x;
+  const int64_t arow = (int64_t)pair * J;
+  const int row0 = (rb * 8 + w) * (16 * RT);
+  const int nsteps = (nt + 15) >> 4;
+  for (int i = tid; i < nsteps; i += 512) flags[i] = 0u;
+  ScreenFrag af[RT];
+  // skip iff (sqrt(lo) 0.99999 - r)_+^2 > T, tested without a square root per element as lo > ((sqrt(T) + r) k)^2, k = kMarginRoot:
+  // slo2 = |a|^2 - d_a - margin per row (+inf for rows past the end: they need nothing), sT = sqrt(T) k per row, r k per column
+  float slo2[RT][4], sT[RT][4];
+#pragma unroll
+  for (int rt = 0; rt < RT; ++rt) {
+    af[rt] = screen_frag(Ah, Al, arow + rows[arow + min(row0 + rt * 16 + fr, J - 1)], fq);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int pos = row0 + rt * 16 + 4 * fq + r;
+      const int re = rows[arow + min(pos, J - 1)];
+      const float san = sa[arow + re];
+      slo2[rt][r] = pos < J ? screen_slo(san) - kMarginCentroid * (1.f + san) : INFINITY;
+      sT[rt][r] = pos < J ? sqrtf(T[arow + re]) * kMarginRoot : 0.f;      // T < 0 or NaN: NaN - the row visits every tile
+    }
+  }
+  __syncthreads();
+  const _Float16* ch = Ch + (int64_t)pair * nt * 64;
+  const _Float16* cl = Cl + (int64_t)pair * nt * 64;
+  // the next step's centroid fragments travel while the current step's MFMAs run (a step's own loads were exposed: 24 MFMAs
+  // cannot start before four 16-byte loads and two scalars have come back)
+  struct CFrag { ScreenFrag b; float c2, rad; };
+  auto cload = [&](int s) {
+    const int tc = min(16 * s + fr, nt - 1);
+    return CFrag{screen_frag(ch, cl, tc, fq), cn2[(int64_t)pair * nt + tc], rad[(int64_t)pair * nt + tc]};
+  };
+  CFrag nxt = cload(0);
+  for (int s = 0; s < nsteps; ++s) {
+    const CFrag cur = nxt;
+    if (s + 1 < nsteps) nxt = cload(s + 1);
+    const float rk = cur.rad * kMarginRoot;
+    const float cterm = kMarginCentroid * cur.c2;
+    const float seed = 16 * s + fr < nt ? screen_seed(cur.c2) : -INFINITY;      // tiles past the end: L = +inf (their flags are not read)
+    bool need = false;
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) {
+      const f32x4 z = screen_chain(af[rt], cur.b, seed);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        // L <= D(a, c) (the screening bound), D(a, c) within kMarginCentroid (1 + |a|^2 + |c|^2) of the true |a - c|^2: a lower bound of that
+        const float lo = screen_lower(z[r], slo2[rt][r]) - cterm;
+        const float thr = sT[rt][r] + rk;
+        need = need || !(lo > thr * thr);                                        // NaN anywhere: visit
+      }
+    }
+    const unsigned long long m = __ballot(need);
+    const unsigned int m16 = (unsigned int)((m | (m >> 16) | (m >> 32) | (m >> 48)) & 0xffffull);
+    if (lane == 0 && m16) atomicOr(&flags[s], m16);
+  }
+  __syncthreads();
+  if (tid < 64) {
+    int32_t* out = tlist + ((int64_t)pair * nrb + rb) * tl_stride;
+    int cnt = 0;
+    for (int base = 0; base < nt; base += 64) {
+      const int t = base + tid;
+      const bool f = t < nt && ((flags[t >> 4] >> (t & 15)) & 1u);
+      const unsigned long long m = __ballot(f);
+      if (f) out[cnt + __popcll(m & ((1ull << tid) - 1ull))] = t;
+      cnt += __popcll(m);
+    }
+    if (tid == 0) tcount[pair * nrb + rb] = cnt;
+  }
+}
+
+// ---- where does a row look first?  The tile whose CENTROID is nearest (smallest screening lower bound L(a, c_t)), per src row, rows
+// in their natural order.  That tile orders the rows (rows that start in the same tile sit in the same row block and agree on
+// which tiles matter) and supplies an upper bound of the row's minimum that does not need a previous iteration (tile_T_kernel).
+// Same MFMA chain and operands as tile_bound_kernel; L = slo_row - 2^-21 z', so the arg-min of L over t is the arg-max of z'.
+template <int RT>
+__global__ __launch_bounds__(512) void centroid_argmin_kernel(const _Float16* __restrict__ Ah, const _Float16* __restrict__ Al,
+                                                              const _Float16* __restrict__ Ch, const _Float16* __restrict__ Cl,
+                                                              const float* __restrict__ cn2, int J, int nt, int32_t* __restrict__ tstar) {
+  const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int fr = lane & 15, fq = lane >> 4;
+  const int rb = blockIdx.x, pair = blockIdx.y;
+  const int64_t arow = (int64_t)pair * J;
+  const int row0 = (rb * 8 + w) * (16 * RT);
+  if (row0 >= J) return;                                 // wave-uniform; no barrier in this kernel
+  ScreenFrag af[RT];
+  float bz[RT][4];
+  int bt[RT][4];
+#pragma unroll
+  for (int rt = 0; rt < RT; ++rt) {
+    af[rt] = screen_frag(Ah, Al, arow + min(row0 + rt * 16 + fr, J - 1), fq);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { bz[rt][r] = -INFINITY; bt[rt][r] = 0; }
+  }
+  const _Float16* ch = Ch + (int64_t)pair * nt * 64;
+  const _Float16* cl = Cl + (int64_t)pair * nt * 64;
+  const int nsteps = (nt + 15) >> 4;
+  for (int s = 0; s < nsteps; ++s) {
+    const int t = 16 * s + fr;
+    const int tc = min(t, nt - 1);
+    const ScreenFrag b = screen_frag(ch, cl, tc, fq);
+    const float seed = t < nt ? screen_seed(cn2[(int64_t)pair * nt + tc]) : -INFINITY;
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt) {
+      const f32x4 z = screen_chain(af[rt], b, seed);
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        if (z[r] > bz[rt][r]) { bz[rt][r] = z[r]; bt[rt][r] = t; }        // NaN never wins; first (lowest) tile on ties within a lane
+    }
+  }
+  // the 16 lanes of a row group hold its column classes: larger z' wins, the lower tile on ties (any tile is a valid choice)
+#pragma unroll
+  for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      float z = bz[rt][r];
+      int t = bt[rt][r];
+#pragma unroll
+      for (int o = 1; o < 16; o <<= 1) {
+        const float zo = __shfl_xor(z, o);
+        const int to = __shfl_xor(t, o);
+        if (zo > z || (zo == z && to < t)) { z = zo; t = to; }
+      }
+      const int row = row0 + rt * 16 + 4 * fq + r;
+      if (fr == 0 && row < J) tstar[arow + row] = t;
+    }
+}
+
+// ---- an upper bound of every row's minimum from the tiles its 16-row group points at.  One wave per 16 consecutive rows of the row
+// ORDER (rows sorted by their nearest-centroid tile: a group points at one or two tiles): for every distinct tile among the
+// group's rows the screening chain on (16 rows x SBC columns of the ref operands in column order), U = L + 2 d >= D(row, column)
+// for every (row, column) - the screening's proven upper bound of the exact fp32 distance -, so min U over ANY columns bounds the
+// row minimum from above.  T[row] = min(T[row], min U + margin): T arrives holding the bound from the previous iteration's match
+// (or +inf in iteration 0) and leaves as what tile_bound_kernel prunes against.  (64-row groups - a tile's operands read once per
+// 64 rows - measured twice as slow: 4 x fewer waves with 3 x longer dependent chains; the kernel is latency-, not bandwidth-bound.)
+__global__ __launch_bounds__(256) void tile_T_kernel(const _Float16* __restrict__ Ah, const _Float16* __restrict__ Al,
+                                                     const float* __restrict__ sa, const int32_t* __restrict__ rows,
+                                                     const int32_t* __restrict__ tstar, const _Float16* __restrict__ Bh,
+                                                     const _Float16* __restrict__ Bl, const float* __restrict__ sbp, int J, int K, int nt,
+                                                     float* __restrict__ T) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int fr = lane & 15, fq = lane >> 4;
+  const int pair = blockIdx.y;
+  const int g0 = (blockIdx.x * 4 + w) * 16;              // first position of the wave's group in the row order
+  if (g0 >= J) return;                                   // wave-uniform; no barrier in this kernel
+  const int64_t arow = (int64_t)pair * J, brow = (int64_t)pair * K;
+  const int ra = rows[arow + min(g0 + fr, J - 1)];        // the row whose A fragment this lane holds
+  const ScreenFrag af = screen_frag(Ah, Al, arow + ra, fq);
+  int rowe[4];
+  float san[4], slo[4], best[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    rowe[r] = rows[arow + min(g0 + 4 * fq + r, J - 1)];
+    san[r] = sa[arow + rowe[r]];
+    slo[r] = screen_slo(san[r]);
+    best[r] = INFINITY;
+  }
+  int mine = tstar[arow + ra];                            // the tile this lane's row points at (lanes fr, all four fq copies)
+  mine = mine < 0 ? 0 : (mine >= nt ? nt - 1 : mine);
+  bool pending = g0 + fr < J;
+  for (int guard = 0; guard < 16; ++guard) {              // at most 16 distinct tiles per group
+    // the lowest tile some lane still waits for
+    int t = pending ? mine : 0x7fffffff;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) t = min(t, __shfl_xor(t, o));
+    if (t == 0x7fffffff) break;                           // wave-uniform
+    if (mine == t) pending = false;
+#pragma unroll
+    for (int s = 0; s < SBC / 16; ++s) {
+      const int pos = min(SBC * t + 16 * s + fr, K - 1);
+      const bool live = SBC * t + 16 * s + fr < K;
+      const float sbk = sbp[brow + pos];
+      const f32x4 z = screen_chain(af, screen_frag(Bh, Bl, brow + pos, fq), screen_seed(sbk));
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        // U = L + 2 d + the margin row_prep_kernel puts on an exact distance
+        const float u = screen_upper(screen_lower(z[r], slo[r]), san[r], sbk) + kMarginExact * (1.f + san[r] + sbk);
+        if (live) best[r] = fminf(best[r], u);           // NaN: ignored (a row without finite bound keeps +inf: it visits every tile)
+      }
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    float b = best[r];
+#pragma unroll
+    for (int o = 1; o < 16; o <<= 1) b = fminf(b, __shfl_xor(b, o));
+    if (fr == 0 && g0 + 4 * fq + r < J) {
+      const float old = T[arow + rowe[r]];
+      T[arow + rowe[r]] = fminf(old, b);                   // one writer per row
+    }
+  }
+}
+
+// the row blocks of every pair by descending tile count (ties: by index): the persistent search takes the long items first, so
+// that its last round is made of short ones (longest-processing-time-first; the tail of a launch was up to one full-length item,
+// 18 % of the kernel at 65536 points).  One workgroup per pair, rank by counting - a pair has at most a few hundred row blocks
+__global__ __launch_bounds__(256) void rank_blocks_kernel(const int32_t* __restrict__ tcount, int nrb, int32_t* __restrict__ rborder) {
+  const int32_t* c = tcount + (int64_t)blockIdx.x * nrb;
+  int32_t* out = rborder + (int64_t)blockIdx.x * nrb;
+  for (int i = threadIdx.x; i < nrb; i += 256) {
+    const int ci = c[i];
+    int rank = 0;
+    for (int j = 0; j < nrb; ++j) { const int cj = c[j]; rank += (cj > ci || (cj == ci && j < i)) ? 1 : 0; }
+    out[rank] = i;
+  }
+}
+
 struct Layout {
   int32_t *cols, *rows, *tlist, *tcount, *queue, *rborder, *tstar;
   float *cen, *cn2, *rad, *T, *box;
-  void *ch, *cl;                       // the centroids as the screening's fp16 pairs
-  void *pbh, *pbl;                     // the ref side's fp16 pairs in column order
+  _Float16 *ch, *cl;                   // the centroids as the screening's fp16 pairs
+  _Float16 *pbh, *pbl;                 // the ref side's fp16 pairs in column order
   float* psb;
   uint32_t *k0, *k1, *v0, *v1;
   void* cub;
@@ -197,7 +413,7 @@ struct Layout {
 };
 
 Layout carve(void* scratch, int pairs, int J, int K) {
-  const int nt = (K + TILE - 1) / TILE;
+  const int nt = (K + SBC - 1) / SBC;
   const int rpb = nn_screen_rows_per_block(J);
   const int nrb = (J + rpb - 1) / rpb;
   const size_t nmax = (size_t)pairs * (size_t)(J > K ? J : K);
@@ -212,8 +428,8 @@ Layout carve(void* scratch, int pairs, int J, int K) {
   L.queue = reinterpret_cast<int32_t*>(take(8 * 4));
   L.rborder = reinterpret_cast<int32_t*>(take((size_t)pairs * nrb * 4));
   L.cen = reinterpret_cast<float*>(take((size_t)pairs * nt * 64 * 4));
-  L.ch = take((size_t)pairs * nt * 64 * 2);
-  L.cl = take((size_t)pairs * nt * 64 * 2);
+  L.ch = reinterpret_cast<_Float16*>(take((size_t)pairs * nt * 64 * 2));
+  L.cl = reinterpret_cast<_Float16*>(take((size_t)pairs * nt * 64 * 2));
   L.cn2 = reinterpret_cast<float*>(take((size_t)pairs * nt * 4));
   L.rad = reinterpret_cast<float*>(take((size_t)pairs * nt * 4));
   L.T = reinterpret_cast<float*>(take((size_t)pairs * J * 4));
@@ -222,8 +438,8 @@ Layout carve(void* scratch, int pairs, int J, int K) {
   L.k1 = reinterpret_cast<uint32_t*>(take(nmax * 4));
   L.v0 = reinterpret_cast<uint32_t*>(take(nmax * 4));
   L.v1 = reinterpret_cast<uint32_t*>(take(nmax * 4));
-  L.pbh = take((size_t)pairs * K * 64 * 2);
-  L.pbl = take((size_t)pairs * K * 64 * 2);
+  L.pbh = reinterpret_cast<_Float16*>(take((size_t)pairs * K * 64 * 2));
+  L.pbl = reinterpret_cast<_Float16*>(take((size_t)pairs * K * 64 * 2));
   L.psb = reinterpret_cast<float*>(take((size_t)pairs * K * 4));
   // temporary storage of the two radix sorts: sized for the largest sort over all 32 key bits; every sort asks again for its own
   // size and bit range and refuses to run if the answer exceeds this (sort_pairs)
@@ -249,11 +465,40 @@ int sort_pairs(const Layout& L, int64_t total, int end_bit, hipStream_t st) {
 
 inline int bits_for(int n) { int b = 0; while ((1ll << b) < n) ++b; return b; }   // smallest b with 2^b >= n
 
+// the bound pass works on the screening's row blocks: f(its row tiles per wave for this J, as an integral constant)
+template <typename F>
+void with_row_tiles(int J, F&& f) {
+  if (nn_screen_rows_per_block(J) == 512) f(std::integral_constant<int, 4>{});
+  else                                    f(std::integral_constant<int, 2>{});
+}
+
+// nearest-centroid tile of every src row (natural row order)
+void launch_centroid_argmin(const Layout& L, const _Float16* Ah, const _Float16* Al, int pairs, int J, int nrb, int nt, hipStream_t st) {
+  with_row_tiles(J, [&](auto rt) {
+    hipLaunchKernelGGL(centroid_argmin_kernel<decltype(rt)::value>, dim3(nrb, pairs), dim3(512), 0, st, Ah, Al, L.ch, L.cl, L.cn2, J, nt, L.tstar);
+  });
+}
+
+// T[row] = min(T[row], upper bound from the tiles the row's 16-row group (in the row order) points at)
+void launch_tile_T(const Layout& L, const _Float16* Ah, const _Float16* Al, const float* sa, int pairs, int J, int K, int nt, hipStream_t st) {
+  hipLaunchKernelGGL(tile_T_kernel, dim3((J + 63) / 64, pairs), dim3(256), 0, st, Ah, Al, sa, L.rows, L.tstar, L.pbh, L.pbl, L.psb, J, K, nt, L.T);
+}
+
+// tile lists of every (pair, row block) for the row order L.rows and the per-row upper bounds L.T; rborder (optional): their ranking
+void launch_tile_bound(const Layout& L, const _Float16* Ah, const _Float16* Al, const float* sa, int pairs, int J, int nrb, int nt,
+                       int32_t* rborder, hipStream_t st) {
+  with_row_tiles(J, [&](auto rt) {
+    hipLaunchKernelGGL(tile_bound_kernel<decltype(rt)::value>, dim3(nrb, pairs), dim3(512), 0, st, Ah, Al, sa, L.rows, L.T, L.ch, L.cl, L.cn2,
+                       L.rad, J, nt, L.tlist, L.tcount, nt);
+  });
+  if (rborder) hipLaunchKernelGGL(rank_blocks_kernel, dim3(pairs), dim3(256), 0, st, L.tcount, nrb, rborder);
+}
+
 }  // namespace
 
 bool nn_prune_supported(int pairs, int J, int K) {
   if (bits_for(pairs) + bits_for(K) > 32 || bits_for(pairs) > 12) return false;     // the sorts' composite 32-bit keys
-  return (K + TILE - 1) / TILE <= nn_screen_max_bound_tiles() && (int64_t)pairs * (J > K ? J : K) <= 0x7fffffffll && nn_screen_rows_per_block(J) <= 512;
+  return (K + SBC - 1) / SBC <= kMaxBoundTiles && (int64_t)pairs * (J > K ? J : K) <= 0x7fffffffll && nn_screen_rows_per_block(J) <= 512;
 }
 
 size_t nn_prune_scratch_bytes(int pairs, int J, int K) { return carve(nullptr, pairs, J, K).total; }
@@ -262,7 +507,7 @@ size_t nn_prune_scratch_bytes(int pairs, int J, int K) { return carve(nullptr, p
 int launch_prune_ref(const float* ref_xyz, int64_t xyz_cs, const float* desc_r, const void* bh, const void* bl, const float* sb, int pairs, int J,
                      int K, void* scratch, hipStream_t st) {
   const Layout L = carve(scratch, pairs, J, K);
-  const int nt = (K + TILE - 1) / TILE;
+  const int nt = (K + SBC - 1) / SBC;
   const int64_t total = (int64_t)pairs * K;
   const int pbits = bits_for(pairs);
   const int mbits = 32 - pbits < 30 ? 32 - pbits : 30;
@@ -284,7 +529,7 @@ int launch_prune_ref(const float* ref_xyz, int64_t xyz_cs, const float* desc_r, 
 int launch_prune_rows(const float* desc_s, const float* desc_r, const void* ah, const void* al, const float* sa, const float* sb,
                       const int32_t* idx_prev, int pairs, int J, int K, void* scratch, hipStream_t st, ScreenOrder* ord, unsigned long long* acc) {
   const Layout L = carve(scratch, pairs, J, K);
-  const int nt = (K + TILE - 1) / TILE;
+  const int nt = (K + SBC - 1) / SBC;
   const int rpb = nn_screen_rows_per_block(J);
   const int nrb = (J + rpb - 1) / rpb;
   const int64_t total = (int64_t)pairs * J;
@@ -293,13 +538,14 @@ int launch_prune_rows(const float* desc_s, const float* desc_r, const void* ah, 
   static const bool no_lpt = tuning_flag("DSIR_PRUNE_NO_LPT");       // A/B hook: items in row-block order
   static const bool keep_all = tuning_flag("DSIR_PRUNE_KEEP_ALL");   // measurement hook: every tile on every list (the mechanism's own cost)
   static const bool no_tile_T = tuning_flag("DSIR_PRUNE_NO_TILE_T"); // A/B hook: upper bounds from the previous match only
-  launch_centroid_argmin(ah, al, L.ch, L.cl, L.cn2, pairs, J, nt, L.tstar, st);
+  const _Float16 *Ah = reinterpret_cast<const _Float16*>(ah), *Al = reinterpret_cast<const _Float16*>(al);
+  launch_centroid_argmin(L, Ah, Al, pairs, J, nrb, nt, st);
   hipLaunchKernelGGL(row_prep_kernel, dim3(grid_for(total)), dim3(256), 0, st, desc_s, desc_r, sa, sb, idx_prev, L.tstar, J, K, tbits, total,
                      keep_all, L.k0, L.v0, L.T);
   if (sort_pairs(L, total, tbits + bits_for(pairs), st)) return 1;
   hipLaunchKernelGGL(order_kernel, dim3(grid_for(total)), dim3(256), 0, st, L.v1, J, total, id_rows, L.rows, (int32_t*)nullptr);
-  if (!keep_all && !no_tile_T) launch_tile_T(ah, al, sa, L.rows, L.tstar, L.pbh, L.pbl, L.psb, pairs, J, K, nt, L.T, st);
-  launch_tile_bound(ah, al, sa, L.rows, L.T, L.ch, L.cl, L.cn2, L.rad, pairs, J, nt, L.tlist, L.tcount, nt, no_lpt ? nullptr : L.rborder, st);
+  if (!keep_all && !no_tile_T) launch_tile_T(L, Ah, Al, sa, pairs, J, K, nt, st);
+  launch_tile_bound(L, Ah, Al, sa, pairs, J, nrb, nt, no_lpt ? nullptr : L.rborder, st);
   if (acc) hipLaunchKernelGGL(prune_account_kernel, dim3(1), dim3(256), 0, st, L.tcount, pairs * nrb, nt, acc);
   ord->rows = L.rows;
   ord->cols = L.cols;

@@ -23,45 +23,22 @@
 //           as a whole and skips the screening for the rest of the registration.  Nothing is ever decided by an
 //           approximate value.
 //
-// Error budget, in units of M = |a|^2 + |b|^2 (|a||b| <= M/2): representation 2^-22 per element (3 2^-22 M with the
-// dropped al.bl term); fp32 accumulation: both high parts are stored pre-scaled by 2^11 (exact) and the kernel forms
-// z' = 2^22 (c + ah.bh) + 2^11 (ah.bl + al.bh) = 2^22 z in ONE chain of six MFMAs (192 exact fp16 products + the seed;
-// a pure power-of-two scaling: the roundings are those of the unscaled sum), pessimistically one fp32 rounding per
-// addition relative to the sum of the magnitudes (|a||b| + |b|^2 / 2) <= M: 198 2^-24 M on z, 2^-15.4 M after the factor 2; the reference's own
-// fmaf chain 64 * 2^-24 * 2 |a||b| <= 2^-18 M; final roundings 2^-22 M: 2.8e-5 M against 2^-15 M = 3.05e-5 M (measured on
-// unit descriptors: < 1e-6 against 6e-5).  Elements below 2^-25 lose their low part
-// (fp16 underflow): <= 2^-25 per element, 2^-21 (|a| + |b|) <= 2^-21 (1 + M/2) on the distance: the constant term 2^-20.
-// MEASURED on the matrix core (round 3; tests/test_gpu_screen_bound.py through dsir_screen_bounds, which runs this file's MFMA
-// chain on this file's operands and returns L, U and the exact D of EVERY (row, column)): 19 input regimes chosen against the
-// bound - same-sign components (no cancellation in the accumulator), constant vectors / 64 identical products, components on
-// fp16 rounding ties, |x| = 16, norms 1e-3 .. 30, one-hot, sparse, below the fp16 normal range, near-duplicates, geometric
-// decay - x three shapes, 4.4 M entries: no entry outside [L, U]; worst |D - (L + U) / 2| = 0.066 of the half width (a margin
-// of 15 on d); the accumulation error of the six chained MFMAs against an fp64 sum of the same fp16 products never exceeded
-// 11.9 fp32 roundings of the magnitude sum, against the 198 budgeted above: the v_mfma_f32_16x16x32_f16 adder of gfx950 rounds
-// far less often than once per product (and not by truncation: same-sign inputs err LESS than signed ones).  The bound is
-// kept at its pessimistic width; the test asserts a margin of 2 so that a different stepping would be noticed.
-// Elements with |x| > 16 (the 2^11 pre-scaling of the high part must stay inside fp16: 2^15 < 65504) or not finite: split16_kernel
-// raises a flag and every pair is searched exhaustively (the engine's descriptors are L2-normalised, model.py:232-233,
-// and never take that path).
+// The error budget of d, its measurement on the matrix core and the bound's arithmetic itself: screen_bound.h, shared with
+// the bound pass of the pruned search (nn_prune.hip).
 #include <hip/hip_fp16.h>
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
 
 #include "kernels.h"
-#include "device_utils.h"
+#include "screen_bound.h"
 
 namespace dsir {
 
 namespace {
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef _Float16 h4 __attribute__((ext_vector_type(4)));
 
-#ifndef DSIR_SCREEN_BC
-#define DSIR_SCREEN_BC 64
-#endif
-constexpr int SBC = DSIR_SCREEN_BC;   // ref columns per LDS tile
 #ifndef DSIR_SCREEN_SRS
 #define DSIR_SCREEN_SRS 80
 #endif
@@ -73,18 +50,6 @@ constexpr int SBC = DSIR_SCREEN_BC;   // ref columns per LDS tile
 #endif
 constexpr int SRS = DSIR_SCREEN_SRS;     // halfs per LDS row: 64 + 16 pad (160 B; measured 1 % faster than the 144 B of a minimal pad)
 constexpr int CAP = 16;     // entries kept per row; more => the row goes to the exhaustive kernel
-constexpr float kC1 = 1.0f / 32768.0f;      // bound width: d = kC1 (|a|^2 + |b|^2) + kC0 (see the header)
-constexpr float kC0 = 1.0f / 1048576.0f;
-constexpr float kW = 2.0f * 1.015625f;       // upper - lower bound = 2 d, with slack for the rounding of its own evaluation
-
-__device__ __forceinline__ unsigned int order_bits(float f) {
-  const unsigned int u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float unorder_bits(unsigned int b) {
-  return __uint_as_float((b & 0x80000000u) ? (b & 0x7fffffffu) : ~b);
-}
-
 // four channels fp32 -> fp16 high / low parts (see the header): device_utils.h, screen_split4 (shared with agg_chain_h.hip's epilogue)
 __device__ __forceinline__ void split4(const float4 v, h4& h, h4& l, int32_t* __restrict__ bad) { screen_split4(v, h, l, bad); }
 
@@ -152,7 +117,6 @@ __global__ __launch_bounds__(256) void split_norm_kernel(const float* __restrict
 #else
 #define DSIR_MORE(x) (x)
 #endif
-constexpr int kMaxBoundTiles = 4096;   // tiles of a pruned search's column order (LDS: tile flags of the bound pass, an item's tile list)
 // ORD = false: the dense search (every tile of the item's column range, natural row / column order) - the `ord` fields are not
 // touched and the code is the round-2 kernel's; ORD = true: the pruned search of nn_prune.hip (row / column orders, tile lists)
 template <int RT, int NWV, bool ORD>
@@ -187,17 +151,13 @@ __device__ __forceinline__ void screen_item(const int wi, const _Float16* __rest
   __syncthreads();                                   // the next item of a persistent workgroup rewrites s_skip
   if (skip) return;
 
-  // A fragments: lane holds row fr, channels 32 c + 8 fq .. +7; ah = 2^11 x (high part), al = 2^11 x (low part)
-  h8 ah[RT][2], al[RT][2];
+  // A fragments: lane holds row fr; h = 2^11 x (high part), l = 2^11 x (low part)
+  ScreenFrag af[RT];
 #pragma unroll
   for (int rt = 0; rt < RT; ++rt) {
     int row = min(row0 + rt * 16 + fr, J - 1);
     if (ORD && ord.rows) row = ord.rows[arow + row];   // pruned search: the block's rows are rows [row0, ..) of the given ORDER
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-      ah[rt][c] = *reinterpret_cast<const h8*>(Ah + (arow + row) * 64 + 32 * c + 8 * fq);
-      al[rt][c] = *reinterpret_cast<const h8*>(Al + (arow + row) * 64 + 32 * c + 8 * fq);
-    }
+    af[rt] = screen_frag(Ah, Al, arow + row, fq);
   }
   // per C element (row 4 fq + r of tile rt, column class fr): the two largest z' and the column of the largest
   float z1[RT][4], z2[RT][4];
@@ -261,7 +221,7 @@ __device__ __forceinline__ void screen_item(const int wi, const _Float16* __rest
       const int r = min(col, K - 1);
       const bool ok = live && col < c_lim && f < SBC * 4;                 // columns past the range never win
       if (ORD) { pre.sb[i] = ord.sbp[brow + r]; pre.ok |= ok ? 1u << i : 0u; }
-      else { const float s = sb[brow + r]; pre.sb[i] = ok ? -2097152.f * (s - kC1 * s) : -INFINITY; }
+      else { const float s = sb[brow + r]; pre.sb[i] = ok ? screen_seed(s) : -INFINITY; }
     }
   };
   auto lstore = [&](const Pre& pre, int buf) {
@@ -274,9 +234,8 @@ __device__ __forceinline__ void screen_item(const int wi, const _Float16* __rest
 #pragma unroll
     for (int i = 0; i < NSB; ++i) {
       const int f = tid + NWV * 64 * i;
-      // the accumulator seed 2^22 c, c = -(|b|^2 - d_b) / 2; columns past the range never win
-      if (f < SBC * 4)
-        reinterpret_cast<float*>(sbs[buf])[f] = !ORD ? pre.sb[i] : ((pre.ok >> i) & 1u) ? -2097152.f * (pre.sb[i] - kC1 * pre.sb[i]) : -INFINITY;
+      // columns past the range never win
+      if (f < SBC * 4) reinterpret_cast<float*>(sbs[buf])[f] = !ORD ? pre.sb[i] : ((pre.ok >> i) & 1u) ? screen_seed(pre.sb[i]) : -INFINITY;
     }
   };
   // fragments of one 16-column step: lane holds column fr of the step, channels 8 fq .. (+32)
@@ -287,7 +246,9 @@ __device__ __forceinline__ void screen_item(const int wi, const _Float16* __rest
   for (int rt = 0; rt < RT; ++rt) zP[rt] = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
 #define DSIR_MFMA(acc, a, b, c) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0)
   // one step: the six MFMAs per row tile on `cur`, between them the ranking of the previous step's accumulators (zP) and
-  // the fragment reads of the next step (`nxt`; skipped when !more)
+  // the fragment reads of the next step (`nxt`; skipped when !more).  screen_chain (screen_bound.h) DEFINES the operand order;
+  // it is written out here because the schedule is pinned between the MFMAs (tests/test_gpu_screen_bound.py, mism == 0, holds
+  // the two together)
   auto step = [&](const Frag& cur, Frag& nxt, const _Float16* bhp, const _Float16* blp, const float4* cp, bool more, int col) {
     f32x4 zN[RT];
 #define DSIR_RANK_ALL(r)                                                                          \
@@ -295,25 +256,25 @@ __device__ __forceinline__ void screen_item(const int wi, const _Float16* __rest
     _Pragma("unroll") for (int rt = 0; rt < RT; ++rt) DSIR_RANK(z1[rt][r], z2[rt][r], k1[rt][r], zP[rt][r], colP); \
     DSIR_FENCE()
 #pragma unroll
-    for (int rt = 0; rt < RT; ++rt) DSIR_MFMA(zN[rt], ah[rt][0], cur.bh0, cur.cin);
+    for (int rt = 0; rt < RT; ++rt) DSIR_MFMA(zN[rt], af[rt].h[0], cur.bh0, cur.cin);
     if (more) { nxt.bh0 = *reinterpret_cast<const h8*>(bhp); const float4 v = *cp; nxt.cin = f32x4{v.x, v.y, v.z, v.w}; }
     DSIR_RANK_ALL(0);
 #pragma unroll
-    for (int rt = 0; rt < RT; ++rt) DSIR_MFMA(zN[rt], ah[rt][1], cur.bh1, zN[rt]);
+    for (int rt = 0; rt < RT; ++rt) DSIR_MFMA(zN[rt], af[rt].h[1], cur.bh1, zN[rt]);
     if (more) nxt.bl0 = *reinterpret_cast<const h8*>(blp);
     DSIR_RANK_ALL(1);
 #pragma unroll
-    for (int rt = 0; rt < RT; ++rt) DSIR_MFMA(zN[rt], ah[rt][0], cur.bl0, zN[rt]);
+    for (int rt = 0; rt < RT; ++rt) DSIR_MFMA(zN[rt], af[rt].h[0], cur.bl0, zN[rt]);
     if (more) nxt.bh1 = *reinterpret_cast<const h8*>(bhp + 32);
     DSIR_RANK_ALL(2);
 #pragma unroll
-    for (int rt = 0; rt < RT; ++rt) DSIR_MFMA(zN[rt], al[rt][0], cur.bh0, zN[rt]);
+    for (int rt = 0; rt < RT; ++rt) DSIR_MFMA(zN[rt], af[rt].l[0], cur.bh0, zN[rt]);
     if (more) nxt.bl1 = *reinterpret_cast<const h8*>(blp + 32);
     DSIR_RANK_ALL(3);
 #pragma unroll
-    for (int rt = 0; rt < RT; ++rt) DSIR_MFMA(zN[rt], ah[rt][1], cur.bl1, zN[rt]);
+    for (int rt = 0; rt < RT; ++rt) DSIR_MFMA(zN[rt], af[rt].h[1], cur.bl1, zN[rt]);
 #pragma unroll
-    for (int rt = 0; rt < RT; ++rt) DSIR_MFMA(zN[rt], al[rt][1], cur.bh1, zN[rt]);
+    for (int rt = 0; rt < RT; ++rt) DSIR_MFMA(zN[rt], af[rt].l[1], cur.bh1, zN[rt]);
 #undef DSIR_RANK_ALL
     DSIR_FENCE();
 #pragma unroll
@@ -403,12 +364,11 @@ __device__ __forceinline__ void screen_item(const int wi, const _Float16* __rest
     for (int r = 0; r < 4; ++r) {
       const bool live_row = row0 + rt * 16 + 4 * fq + r < J;
       const float san = sanv[rt][r];
-      const float slo = san - kC1 * san - kC0;       // |a|^2 - d_a
-      // z' = 2^22 z: L = slo - 2 z = slo - 2^-21 z'
-      const float l1 = fmaf(z1[rt][r], -4.76837158203125e-7f, slo), l2 = fmaf(z2[rt][r], -4.76837158203125e-7f, slo);
+      const float slo = screen_slo(san);
+      const float l1 = screen_lower(z1[rt][r], slo), l2 = screen_lower(z2[rt][r], slo);
       const int k = k1[rt][r];
       float u = INFINITY;
-      if (k >= 0) u = l1 + kW * (kC1 * (san + sbkv[rt][r]) + kC0);
+      if (k >= 0) u = screen_upper(l1, san, sbkv[rt][r]);
       float T = u;
 #pragma unroll
       for (int o = 1; o < 16; o <<= 1) T = fminf(T, __shfl_xor(T, o));
@@ -479,18 +439,6 @@ __global__ __launch_bounds__(NWV * 64) __attribute__((amdgpu_waves_per_eu(DSIR_S
   const int first = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (id >> 3);
   for (int wi = first; wi < total; wi += nwg)
     screen_item<RT, NWV, ORD>(wi, Ah, Al, Bh, Bl, sa, sb, J, K, cols_per_split, rb_count, splits, umin, cnt, cand, ovf, rowlist, ovf_min, ord);
-}
-
-// exact D(row, k) exactly as nn_match.hip evaluates it: the k-ordered fmaf chain of v_mfma_f32_16x16x4_f32 from a zero
-// accumulator, then fl(fl(-2 dot + |a|^2) + |b|^2)
-__device__ __forceinline__ float exact_dist(const float4 (&a)[16], const float* __restrict__ b, float san, float sbn) {
-  float acc = 0.f;
-#pragma unroll
-  for (int q = 0; q < 16; ++q) {
-    const float4 v = reinterpret_cast<const float4*>(b)[q];
-    acc = fmaf(a[q].x, v.x, acc); acc = fmaf(a[q].y, v.y, acc); acc = fmaf(a[q].z, v.z, acc); acc = fmaf(a[q].w, v.w, acc);
-  }
-  return __fadd_rn(__fmaf_rn(acc, -2.f, san), sbn);
 }
 
 // One thread per src row.  Entries whose lower bound exceeds the row's final threshold (the min over all blocks) are
@@ -631,8 +579,8 @@ __global__ void screen_reset_kernel(int32_t* __restrict__ ovf, int pairs, int ov
 }
 
 // ---- diagnostics (dsir_screen_bounds): the screening's arithmetic laid bare for EVERY (row, column) of one small pair.
-// One wave per 16 x 16 tile runs the SAME chain of six v_mfma_f32_16x16x32_f16 as screen_item (same operands, same
-// order, same seed 2^22 c) and the epilogue's arithmetic for the lower bound L and the upper bound U = L + 2 d, and evaluates the exact
+// One wave per 16 x 16 tile runs screen_chain on screen_item's operands and seed and screen_bound.h's arithmetic for the lower
+// bound L and the upper bound U = L + 2 d (what screen_item's epilogue and the pruned search's bound pass call), and evaluates the exact
 // distance D beside them, so that a test can assert L <= D <= U entry by entry on adversarial inputs - the
 // property the whole screened path rests on, checked on the matrix core itself rather than derived from an assumed
 // rounding model.  tests/test_gpu_screen_bound.py also ties this kernel to the product: every candidate entry
@@ -646,33 +594,16 @@ __global__ __launch_bounds__(64) void screen_bounds_kernel(const _Float16* __res
   const int lane = threadIdx.x & 63, fr = lane & 15, fq = lane >> 4;
   const int row0 = blockIdx.y * 16, col0 = blockIdx.x * 16;
   const int arow = min(row0 + fr, J - 1), bcol = min(col0 + fr, K - 1);
-  h8 ah[2], al[2], bh[2], bl[2];
-#pragma unroll
-  for (int c = 0; c < 2; ++c) {
-    ah[c] = *reinterpret_cast<const h8*>(Ah + (int64_t)arow * 64 + 32 * c + 8 * fq);
-    al[c] = *reinterpret_cast<const h8*>(Al + (int64_t)arow * 64 + 32 * c + 8 * fq);
-    bh[c] = *reinterpret_cast<const h8*>(Bh + (int64_t)bcol * 64 + 32 * c + 8 * fq);
-    bl[c] = *reinterpret_cast<const h8*>(Bl + (int64_t)bcol * 64 + 32 * c + 8 * fq);
-  }
   const float sbk = sb[bcol];
-  const float seed = -2097152.f * (sbk - kC1 * sbk);          // screen_item's gload: 2^22 c, c = -(|b|^2 - d_b) / 2
-  f32x4 z = f32x4{seed, seed, seed, seed};
-  // screen_item's step(), one row tile: (ah0,bh0) (ah1,bh1) (ah0,bl0) (al0,bh0) (ah1,bl1) (al1,bh1)
-  z = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[0], bh[0], z, 0, 0, 0);
-  z = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[1], bh[1], z, 0, 0, 0);
-  z = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[0], bl[0], z, 0, 0, 0);
-  z = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[0], bh[0], z, 0, 0, 0);
-  z = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[1], bl[1], z, 0, 0, 0);
-  z = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[1], bh[1], z, 0, 0, 0);
+  const f32x4 z = screen_chain(screen_frag(Ah, Al, arow, fq), screen_frag(Bh, Bl, bcol, fq), screen_seed(sbk));
   const int col = col0 + fr;
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int row = row0 + 4 * fq + r;
     if (row >= J || col >= K) continue;
     const float san = sa[row];
-    const float slo = san - kC1 * san - kC0;                                  // the epilogue of screen_item, verbatim
-    const float l1 = fmaf(z[r], -4.76837158203125e-7f, slo);
-    const float u = l1 + kW * (kC1 * (san + sbk) + kC0);
+    const float l1 = screen_lower(z[r], screen_slo(san));
+    const float u = screen_upper(l1, san, sbk);
     float4 a[16];
 #pragma unroll
     for (int q = 0; q < 16; ++q) a[q] = reinterpret_cast<const float4*>(A + (int64_t)row * 64)[q];
@@ -700,318 +631,26 @@ __global__ void screen_export_kernel(const unsigned int* __restrict__ umin, cons
   }
 }
 
-// ---- the bound pass of the pruned search (nn_prune.hip) on the matrix core: which column tiles must a row block visit?
-// A tile t (64 ref columns, centroid c_t, radius r_t) can be skipped by a row whose minimum is known to be <= T iff
-// (|a - c_t| - r_t)_+^2 > T.  |a - c_t|^2 is bounded from BELOW by this file's own screening bound: the centroids are split like
-// descriptors and L(a, c_t) <= D(a, c_t) comes out of the same six-MFMA chain (rows x nt centroids: 1/64 of a search).
-// Block = 8 waves x RT row tiles = one row block of the screening (rows in the given order); per 16-centroid step every lane
-// tests its column against its 4 RT rows, the wave folds the answers into a 16-bit column mask, and the tiles some row needs
-// are compacted into the block's list.
-template <int RT>
-__global__ __launch_bounds__(512) void tile_bound_kernel(const _Float16* __restrict__ Ah, const _Float16* __restrict__ Al,
-                                                         const float* __restrict__ sa, const int32_t* __restrict__ rows,
-                                                         const float* __restrict__ T, const _Float16* __restrict__ Ch,
-                                                         const _Float16* __restrict__ Cl, const float* __restrict__ cn2,
-                                                         const float* __restrict__ rad, int J, int nt, int32_t* __restrict__ tlist,
-                                                         int32_t* __restrict__ tcount, int tl_stride) {
-  __shared__ unsigned int flags[kMaxBoundTiles / 16];
-  const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int fr = lane & 15, fq = lane >> 4;
-  const int rb = blockIdx.x, pair = blockIdx.y, nrb = gridDim.x;
-  const int64_t arow = (int64_t)pair * J;
-  const int row0 = (rb * 8 + w) * (16 * RT);
-  const int nsteps = (nt + 15) >> 4;
-  for (int i = tid; i < nsteps; i += 512) flags[i] = 0u;
-  h8 ah[RT][2], al[RT][2];
-  // skip iff (sqrt(lo) 0.99999 - r)_+^2 > T, tested without a square root per element as lo > ((sqrt(T) + r) k)^2, k = 1.00002 (the
-  // factor 1 / 0.99999 and the rounding of sqrtf): slo2 = |a|^2 - d_a - margin per row (+inf for rows past the end: they need
-  // nothing), sT = sqrt(T) k per row, r k per column
-  float slo2[RT][4], sT[RT][4];
-#pragma unroll
-  for (int rt = 0; rt < RT; ++rt) {
-    const int ra = rows[arow + min(row0 + rt * 16 + fr, J - 1)];
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-      ah[rt][c] = *reinterpret_cast<const h8*>(Ah + (arow + ra) * 64 + 32 * c + 8 * fq);
-      al[rt][c] = *reinterpret_cast<const h8*>(Al + (arow + ra) * 64 + 32 * c + 8 * fq);
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int pos = row0 + rt * 16 + 4 * fq + r;
-      const int re = rows[arow + min(pos, J - 1)];
-      const float san = sa[arow + re];
-      slo2[rt][r] = pos < J ? (san - kC1 * san - kC0) - 1e-5f * (1.f + san) : INFINITY;
-      sT[rt][r] = pos < J ? sqrtf(T[arow + re]) * 1.00002f : 0.f;      // T < 0 or NaN: NaN - the row visits every tile
-    }
+// the scratch of launch_nn_screen as byte offsets, every piece 256-byte aligned
+struct ScreenScratch {
+  size_t umin, cnt, cand, ovf, packed, rowlist, total;
+  ScreenScratch(int pairs, int J) {
+    const size_t rows = (size_t)pairs * J;
+    size_t p = 0;
+    auto take = [&](size_t bytes) { const size_t r = p; p += (bytes + 255) & ~(size_t)255; return r; };
+    umin = take(rows * 4);              // row thresholds u32 [rows]
+    cnt = take(rows * 4);               // entry counts i32 [rows]
+    cand = take(rows * CAP * 8);        // entries {col, lower bound} [CAP][rows]
+    ovf = take((size_t)pairs * 4);      // undecidable rows per pair i32 [pairs]
+    packed = take(rows * 8);            // packed results of the exhaustive fallback u64 [rows]
+    rowlist = take(rows * 4);           // list of the undecidable rows i32 [rows]
+    total = p;
   }
-  __syncthreads();
-  const _Float16* ch = Ch + (int64_t)pair * nt * 64;
-  const _Float16* cl = Cl + (int64_t)pair * nt * 64;
-  // the next step's centroid fragments travel while the current step's MFMAs run (a step's own loads were exposed: 24 MFMAs
-  // cannot start before four 16-byte loads and two scalars have come back)
-  struct CFrag { h8 bh0, bh1, bl0, bl1; float c2, rad; };
-  auto cload = [&](int s) {
-    const int tc = min(16 * s + fr, nt - 1);
-    CFrag f;
-    f.bh0 = *reinterpret_cast<const h8*>(ch + (int64_t)tc * 64 + 8 * fq); f.bh1 = *reinterpret_cast<const h8*>(ch + (int64_t)tc * 64 + 32 + 8 * fq);
-    f.bl0 = *reinterpret_cast<const h8*>(cl + (int64_t)tc * 64 + 8 * fq); f.bl1 = *reinterpret_cast<const h8*>(cl + (int64_t)tc * 64 + 32 + 8 * fq);
-    f.c2 = cn2[(int64_t)pair * nt + tc];
-    f.rad = rad[(int64_t)pair * nt + tc];
-    return f;
-  };
-  CFrag nxt = cload(0);
-  for (int s = 0; s < nsteps; ++s) {
-    const CFrag cur = nxt;
-    if (s + 1 < nsteps) nxt = cload(s + 1);
-    const int t = 16 * s + fr;
-    const h8 bh0 = cur.bh0, bh1 = cur.bh1, bl0 = cur.bl0, bl1 = cur.bl1;
-    const float c2 = cur.c2;
-    const float rk = cur.rad * 1.00002f;
-    const float cterm = 1e-5f * c2;
-    const float seed = t < nt ? -2097152.f * (c2 - kC1 * c2) : -INFINITY;      // tiles past the end: L = +inf (their flags are not read)
-    bool need = false;
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt) {
-      f32x4 z = f32x4{seed, seed, seed, seed};
-      z = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[rt][0], bh0, z, 0, 0, 0);      // screen_item's chain
-      z = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[rt][1], bh1, z, 0, 0, 0);
-      z = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[rt][0], bl0, z, 0, 0, 0);
-      z = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[rt][0], bh0, z, 0, 0, 0);
-      z = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[rt][1], bl1, z, 0, 0, 0);
-      z = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[rt][1], bh1, z, 0, 0, 0);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        // L <= D(a, c) (the screening bound), D(a, c) within 1e-5 (1 + |a|^2 + |c|^2) of the true |a - c|^2: a lower bound of that
-        const float lo = fmaf(z[r], -4.76837158203125e-7f, slo2[rt][r]) - cterm;
-        const float thr = sT[rt][r] + rk;
-        need = need || !(lo > thr * thr);                                        // NaN anywhere: visit
-      }
-    }
-    const unsigned long long m = __ballot(need);
-    const unsigned int m16 = (unsigned int)((m | (m >> 16) | (m >> 32) | (m >> 48)) & 0xffffull);
-    if (lane == 0 && m16) atomicOr(&flags[s], m16);
-  }
-  __syncthreads();
-  if (tid < 64) {
-    int32_t* out = tlist + ((int64_t)pair * nrb + rb) * tl_stride;
-    int cnt = 0;
-    for (int base = 0; base < nt; base += 64) {
-      const int t = base + tid;
-      const bool f = t < nt && ((flags[t >> 4] >> (t & 15)) & 1u);
-      const unsigned long long m = __ballot(f);
-      if (f) out[cnt + __popcll(m & ((1ull << tid) - 1ull))] = t;
-      cnt += __popcll(m);
-    }
-    if (tid == 0) tcount[pair * nrb + rb] = cnt;
-  }
-}
-
-// ---- where does a row look first?  The tile whose CENTROID is nearest (smallest screening lower bound L(a, c_t)), per src row, rows
-// in their natural order.  That tile orders the rows (rows that start in the same tile sit in the same row block and agree on
-// which tiles matter) and supplies an upper bound of the row's minimum that does not need a previous iteration (tile_T_kernel).
-// Same MFMA chain and operands as tile_bound_kernel; L = slo_row - 2^-21 z', so the arg-min of L over t is the arg-max of z'.
-template <int RT>
-__global__ __launch_bounds__(512) void centroid_argmin_kernel(const _Float16* __restrict__ Ah, const _Float16* __restrict__ Al,
-                                                              const _Float16* __restrict__ Ch, const _Float16* __restrict__ Cl,
-                                                              const float* __restrict__ cn2, int J, int nt, int32_t* __restrict__ tstar) {
-  const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int fr = lane & 15, fq = lane >> 4;
-  const int rb = blockIdx.x, pair = blockIdx.y;
-  const int64_t arow = (int64_t)pair * J;
-  const int row0 = (rb * 8 + w) * (16 * RT);
-  if (row0 >= J) return;                                 // wave-uniform; no barrier in this kernel
-  h8 ah[RT][2], al[RT][2];
-#pragma unroll
-  for (int rt = 0; rt < RT; ++rt) {
-    const int ra = min(row0 + rt * 16 + fr, J - 1);
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-      ah[rt][c] = *reinterpret_cast<const h8*>(Ah + (arow + ra) * 64 + 32 * c + 8 * fq);
-      al[rt][c] = *reinterpret_cast<const h8*>(Al + (arow + ra) * 64 + 32 * c + 8 * fq);
-    }
-  }
-  float bz[RT][4];
-  int bt[RT][4];
-#pragma unroll
-  for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) { bz[rt][r] = -INFINITY; bt[rt][r] = 0; }
-  const _Float16* ch = Ch + (int64_t)pair * nt * 64;
-  const _Float16* cl = Cl + (int64_t)pair * nt * 64;
-  const int nsteps = (nt + 15) >> 4;
-  for (int s = 0; s < nsteps; ++s) {
-    const int t = 16 * s + fr;
-    const int tc = min(t, nt - 1);
-    const h8 bh0 = *reinterpret_cast<const h8*>(ch + (int64_t)tc * 64 + 8 * fq), bh1 = *reinterpret_cast<const h8*>(ch + (int64_t)tc * 64 + 32 + 8 * fq);
-    const h8 bl0 = *reinterpret_cast<const h8*>(cl + (int64_t)tc * 64 + 8 * fq), bl1 = *reinterpret_cast<const h8*>(cl + (int64_t)tc * 64 + 32 + 8 * fq);
-    const float c2 = cn2[(int64_t)pair * nt + tc];
-    const float seed = t < nt ? -2097152.f * (c2 - kC1 * c2) : -INFINITY;
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt) {
-      f32x4 z = f32x4{seed, seed, seed, seed};
-      z = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[rt][0], bh0, z, 0, 0, 0);
-      z = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[rt][1], bh1, z, 0, 0, 0);
-      z = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[rt][0], bl0, z, 0, 0, 0);
-      z = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[rt][0], bh0, z, 0, 0, 0);
-      z = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[rt][1], bl1, z, 0, 0, 0);
-      z = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[rt][1], bh1, z, 0, 0, 0);
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        if (z[r] > bz[rt][r]) { bz[rt][r] = z[r]; bt[rt][r] = t; }        // NaN never wins; first (lowest) tile on ties within a lane
-    }
-  }
-  // the 16 lanes of a row group hold its column classes: larger z' wins, the lower tile on ties (any tile is a valid choice)
-#pragma unroll
-  for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      float z = bz[rt][r];
-      int t = bt[rt][r];
-#pragma unroll
-      for (int o = 1; o < 16; o <<= 1) {
-        const float zo = __shfl_xor(z, o);
-        const int to = __shfl_xor(t, o);
-        if (zo > z || (zo == z && to < t)) { z = zo; t = to; }
-      }
-      const int row = row0 + rt * 16 + 4 * fq + r;
-      if (fr == 0 && row < J) tstar[arow + row] = t;
-    }
-}
-
-// ---- an upper bound of every row's minimum from the tiles its 16-row group points at.  One wave per 16 consecutive rows of the row
-// ORDER (rows sorted by their nearest-centroid tile: a group points at one or two tiles): for every distinct tile among the
-// group's rows the screening chain on (16 rows x 64 columns of the ref operands in column order), U = L + 2 d >= D(row, column)
-// for every (row, column) - the screening's proven upper bound of the exact fp32 distance -, so min U over ANY columns bounds the
-// row minimum from above.  T[row] = min(T[row], min U + margin): T arrives holding the bound from the previous iteration's match
-// (or +inf in iteration 0) and leaves as what tile_bound_kernel prunes against.  (64-row groups - a tile's operands read once per
-// 64 rows - measured twice as slow: 4 x fewer waves with 3 x longer dependent chains; the kernel is latency-, not bandwidth-bound.)
-__global__ __launch_bounds__(256) void tile_T_kernel(const _Float16* __restrict__ Ah, const _Float16* __restrict__ Al,
-                                                     const float* __restrict__ sa, const int32_t* __restrict__ rows,
-                                                     const int32_t* __restrict__ tstar, const _Float16* __restrict__ Bh,
-                                                     const _Float16* __restrict__ Bl, const float* __restrict__ sbp, int J, int K, int nt,
-                                                     float* __restrict__ T) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int fr = lane & 15, fq = lane >> 4;
-  const int pair = blockIdx.y;
-  const int g0 = (blockIdx.x * 4 + w) * 16;              // first position of the wave's group in the row order
-  if (g0 >= J) return;                                   // wave-uniform; no barrier in this kernel
-  const int64_t arow = (int64_t)pair * J, brow = (int64_t)pair * K;
-  const int ra = rows[arow + min(g0 + fr, J - 1)];        // the row whose A fragment this lane holds
-  h8 ah[2], al[2];
-#pragma unroll
-  for (int c = 0; c < 2; ++c) {
-    ah[c] = *reinterpret_cast<const h8*>(Ah + (arow + ra) * 64 + 32 * c + 8 * fq);
-    al[c] = *reinterpret_cast<const h8*>(Al + (arow + ra) * 64 + 32 * c + 8 * fq);
-  }
-  int rowe[4];
-  float san[4], slo[4], best[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    rowe[r] = rows[arow + min(g0 + 4 * fq + r, J - 1)];
-    san[r] = sa[arow + rowe[r]];
-    slo[r] = san[r] - kC1 * san[r] - kC0;
-    best[r] = INFINITY;
-  }
-  int mine = tstar[arow + ra];                            // the tile this lane's row points at (lanes fr, all four fq copies)
-  mine = mine < 0 ? 0 : (mine >= nt ? nt - 1 : mine);
-  bool pending = g0 + fr < J;
-  for (int guard = 0; guard < 16; ++guard) {              // at most 16 distinct tiles per group
-    // the lowest tile some lane still waits for
-    int t = pending ? mine : 0x7fffffff;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) t = min(t, __shfl_xor(t, o));
-    if (t == 0x7fffffff) break;                           // wave-uniform
-    if (mine == t) pending = false;
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      const int pos = min(64 * t + 16 * s + fr, K - 1);
-      const bool live = 64 * t + 16 * s + fr < K;
-      const _Float16* bh = Bh + (brow + pos) * 64;
-      const _Float16* bl = Bl + (brow + pos) * 64;
-      const h8 bh0 = *reinterpret_cast<const h8*>(bh + 8 * fq), bh1 = *reinterpret_cast<const h8*>(bh + 32 + 8 * fq);
-      const h8 bl0 = *reinterpret_cast<const h8*>(bl + 8 * fq), bl1 = *reinterpret_cast<const h8*>(bl + 32 + 8 * fq);
-      const float sbk = sbp[brow + pos];
-      const float seed = -2097152.f * (sbk - kC1 * sbk);
-      f32x4 z = f32x4{seed, seed, seed, seed};
-      z = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[0], bh0, z, 0, 0, 0);         // screen_item's chain
-      z = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[1], bh1, z, 0, 0, 0);
-      z = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[0], bl0, z, 0, 0, 0);
-      z = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[0], bh0, z, 0, 0, 0);
-      z = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[1], bl1, z, 0, 0, 0);
-      z = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[1], bh1, z, 0, 0, 0);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float l = fmaf(z[r], -4.76837158203125e-7f, slo[r]);
-        // U = L + 2 d (the epilogue of screen_item) + the margin row_prep_kernel puts on an exact distance
-        const float u = l + kW * (kC1 * (san[r] + sbk) + kC0) + 2e-5f * (1.f + san[r] + sbk);
-        if (live) best[r] = fminf(best[r], u);           // NaN: ignored (a row without finite bound keeps +inf: it visits every tile)
-      }
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    float b = best[r];
-#pragma unroll
-    for (int o = 1; o < 16; o <<= 1) b = fminf(b, __shfl_xor(b, o));
-    if (fr == 0 && g0 + 4 * fq + r < J) {
-      const float old = T[arow + rowe[r]];
-      T[arow + rowe[r]] = fminf(old, b);                   // one writer per row
-    }
-  }
-}
-
-// the row blocks of every pair by descending tile count (ties: by index): the persistent search takes the long items first, so
-// that its last round is made of short ones (longest-processing-time-first; the tail of a launch was up to one full-length item,
-// 18 % of the kernel at 65536 points).  One workgroup per pair, rank by counting - a pair has at most a few hundred row blocks
-__global__ __launch_bounds__(256) void rank_blocks_kernel(const int32_t* __restrict__ tcount, int nrb, int32_t* __restrict__ rborder) {
-  const int32_t* c = tcount + (int64_t)blockIdx.x * nrb;
-  int32_t* out = rborder + (int64_t)blockIdx.x * nrb;
-  for (int i = threadIdx.x; i < nrb; i += 256) {
-    const int ci = c[i];
-    int rank = 0;
-    for (int j = 0; j < nrb; ++j) { const int cj = c[j]; rank += (cj > ci || (cj == ci && j < i)) ? 1 : 0; }
-    out[rank] = i;
-  }
-}
+};
 
 inline int grid_for(int64_t n) { const int64_t g = (n + 255) / 256; return (int)(g < 1 ? 1 : (g > 65535 ? 65535 : g)); }
 
 }  // namespace
-
-int nn_screen_max_bound_tiles() { return kMaxBoundTiles; }
-
-// nearest-centroid tile of every src row (natural row order)
-void launch_centroid_argmin(const void* ah, const void* al, const void* ch, const void* cl, const float* cn2, int pairs, int J, int nt,
-                            int32_t* tstar, hipStream_t st) {
-  const int rpb = nn_screen_rows_per_block(J);
-  const dim3 grid((J + rpb - 1) / rpb, pairs);
-  const _Float16 *Ah = reinterpret_cast<const _Float16*>(ah), *Al = reinterpret_cast<const _Float16*>(al);
-  const _Float16 *Ch = reinterpret_cast<const _Float16*>(ch), *Cl = reinterpret_cast<const _Float16*>(cl);
-  if (rpb == 512) hipLaunchKernelGGL(centroid_argmin_kernel<4>, grid, dim3(512), 0, st, Ah, Al, Ch, Cl, cn2, J, nt, tstar);
-  else            hipLaunchKernelGGL(centroid_argmin_kernel<2>, grid, dim3(512), 0, st, Ah, Al, Ch, Cl, cn2, J, nt, tstar);
-}
-
-// T[row] = min(T[row], upper bound from the tiles the row's 16-row group (in the row order) points at); bh / bl / sbp: the ref
-// operands in column order
-void launch_tile_T(const void* ah, const void* al, const float* sa, const int32_t* rows, const int32_t* tstar, const void* bh, const void* bl,
-                   const float* sbp, int pairs, int J, int K, int nt, float* T, hipStream_t st) {
-  hipLaunchKernelGGL(tile_T_kernel, dim3((J + 63) / 64, pairs), dim3(256), 0, st, reinterpret_cast<const _Float16*>(ah),
-                     reinterpret_cast<const _Float16*>(al), sa, rows, tstar, reinterpret_cast<const _Float16*>(bh),
-                     reinterpret_cast<const _Float16*>(bl), sbp, J, K, nt, T);
-}
-
-// tile lists of every (pair, row block) for the row order `rows` and the per-row upper bounds T (nn_prune.hip)
-void launch_tile_bound(const void* ah, const void* al, const float* sa, const int32_t* rows, const float* T, const void* ch, const void* cl,
-                       const float* cn2, const float* rad, int pairs, int J, int nt, int32_t* tlist, int32_t* tcount, int tl_stride,
-                       int32_t* rborder, hipStream_t st) {
-  const int rpb = nn_screen_rows_per_block(J);
-  const dim3 grid((J + rpb - 1) / rpb, pairs);
-  const _Float16 *Ah = reinterpret_cast<const _Float16*>(ah), *Al = reinterpret_cast<const _Float16*>(al);
-  const _Float16 *Ch = reinterpret_cast<const _Float16*>(ch), *Cl = reinterpret_cast<const _Float16*>(cl);
-  if (rpb == 512) hipLaunchKernelGGL(tile_bound_kernel<4>, grid, dim3(512), 0, st, Ah, Al, sa, rows, T, Ch, Cl, cn2, rad, J, nt, tlist, tcount, tl_stride);
-  else            hipLaunchKernelGGL(tile_bound_kernel<2>, grid, dim3(512), 0, st, Ah, Al, sa, rows, T, Ch, Cl, cn2, rad, J, nt, tlist, tcount, tl_stride);
-  if (rborder) hipLaunchKernelGGL(rank_blocks_kernel, dim3(pairs), dim3(256), 0, st, tcount, (int)grid.x, rborder);
-}
 
 int nn_screen_cap() { return CAP; }
 
@@ -1034,24 +673,17 @@ void launch_screen_bounds(const float* a, const float* b, const void* ah, const 
                      exact, zacc);
 }
 
-// scratch = what launch_nn_screen ran on with pairs = 1 (layout: see nn_screen_scratch_bytes)
+// scratch = what launch_nn_screen ran on with pairs = 1
 void launch_screen_export(const void* scratch, int J, float* thresh, int32_t* count, int32_t* code, float* lower, hipStream_t st) {
-  const size_t rows = (size_t)J;
+  const ScreenScratch L(1, J);
   const char* p = reinterpret_cast<const char*>(scratch);
-  auto take = [&](size_t bytes) { const char* r = p; p += (bytes + 255) & ~(size_t)255; return r; };
-  const unsigned int* umin = reinterpret_cast<const unsigned int*>(take(rows * 4));
-  const int32_t* cnt = reinterpret_cast<const int32_t*>(take(rows * 4));
-  const int2* cand = reinterpret_cast<const int2*>(take(rows * CAP * 8));
+  const unsigned int* umin = reinterpret_cast<const unsigned int*>(p + L.umin);
+  const int32_t* cnt = reinterpret_cast<const int32_t*>(p + L.cnt);
+  const int2* cand = reinterpret_cast<const int2*>(p + L.cand);
   hipLaunchKernelGGL(screen_export_kernel, dim3((J + 255) / 256), dim3(256), 0, st, umin, cnt, cand, J, thresh, count, code, lower);
 }
 
-// scratch: Umin u32 [rows] | cnt i32 [rows] | cand {col, lower bound} [rows][CAP] | undecidable rows per pair i32 [pairs] |
-//          packed results of the exhaustive fallback u64 [rows] | list of the undecidable rows i32 [rows]
-size_t nn_screen_scratch_bytes(int pairs, int J) {
-  const size_t rows = (size_t)pairs * J;
-  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  return al(rows * 4) * 3 + al(rows * CAP * 8) + al((size_t)pairs * 4) + al(rows * 8);
-}
+size_t nn_screen_scratch_bytes(int pairs, int J) { return ScreenScratch(pairs, J).total; }
 
 void launch_split16(const float* x, int64_t rows, void* hi, void* lo, hipStream_t st, int32_t* bad) {
   const int64_t n4 = rows * 16;
@@ -1072,14 +704,14 @@ void launch_nn_screen(const float* a, const float* b, const void* ah, const void
   ScreenOrder ord = ord_in;
   ord.cand_rs = (long long)pairs * J;
   const size_t rows = (size_t)pairs * J;
+  const ScreenScratch L(pairs, J);
   char* p = reinterpret_cast<char*>(scratch);
-  auto take = [&](size_t bytes) { char* r = p; p += (bytes + 255) & ~(size_t)255; return r; };
-  unsigned int* umin = reinterpret_cast<unsigned int*>(take(rows * 4));
-  int32_t* cnt = reinterpret_cast<int32_t*>(take(rows * 4));
-  int2* cand = reinterpret_cast<int2*>(take(rows * CAP * 8));
-  int32_t* ovf = reinterpret_cast<int32_t*>(take((size_t)pairs * 4));
-  unsigned long long* packed = reinterpret_cast<unsigned long long*>(take(rows * 8));
-  int32_t* rowlist = reinterpret_cast<int32_t*>(take(rows * 4));
+  unsigned int* umin = reinterpret_cast<unsigned int*>(p + L.umin);
+  int32_t* cnt = reinterpret_cast<int32_t*>(p + L.cnt);
+  int2* cand = reinterpret_cast<int2*>(p + L.cand);
+  int32_t* ovf = reinterpret_cast<int32_t*>(p + L.ovf);
+  unsigned long long* packed = reinterpret_cast<unsigned long long*>(p + L.packed);
+  int32_t* rowlist = reinterpret_cast<int32_t*>(p + L.rowlist);
   // Screening that is not selective (descriptors closer to each other than the bound width) leaves rows undecided: they
   // are searched by the exhaustive fp32 MFMA kernel - row by row through a list, or the whole pair once a quarter of its
   // rows is affected (then the pair also skips the screening in the remaining iterations of the registration).
@@ -1093,8 +725,6 @@ void launch_nn_screen(const float* a, const float* b, const void* ah, const void
                        packed, (int64_t)rows);
   }
   constexpr int NWV = DSIR_SCREEN_NWV;   // waves per block: they share one staged ref tile (the L2 -> LDS fill is the scarce resource)
-  // row tiles per wave: four (512-row blocks: every ref fragment read from LDS feeds four MFMA chains, -12 % kernel time
-  // at J = 5000) unless the padding of J to whole blocks costs more than that
   const int rows_per_block = nn_screen_rows_per_block(J);
   const int RT = rows_per_block / (NWV * 16);
   const int rb_count = (J + rows_per_block - 1) / rows_per_block;
