@@ -218,6 +218,10 @@ SYMBOLS = {
                                         C.c_void_p, C.c_void_p, C.c_void_p]),
     "dsir_t_augment": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dsir_t_augment_gt": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    # half-space crop (csrc/crop.hip)
+    "dsir_t_halfspace_crop_scratch": (C.c_size_t, [C.c_int, C.c_int]),
+    "dsir_t_halfspace_crop": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     # fragment overlap: radius-bounded nearest neighbour over a sparse cell index (csrc/overlap.hip)
     "dsir_t_nn_within_check": (C.c_char_p, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_float, C.c_void_p]),
     "dsir_t_finite_bounds": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p]),

@@ -111,6 +111,7 @@ class AugmentConfig:
     xy_rot_scale: float = 1.0
     normals: bool = False               # columns 3:6 are normals: rotate them
     reference_gt: bool = False          # keep the reference's unscaled ground-truth translation
+    permute: bool = True                # v2: permute before FixedResampler (the Oxford loader's val / test: False)
 
 
 def rodrigues(axis: np.ndarray, theta: float) -> np.ndarray:
@@ -178,7 +179,7 @@ def pair_params(cfg: AugmentConfig, seed: int, epoch: int, index: int) -> Tuple[
             mode = RESAMPLE_FIXED if cfg.fixed else RESAMPLE_RANDOM
             jm, js, jc = (JITTER_UNIFORM, cfg.jitter_scale, 0.0) if jitter_on else (JITTER_NONE, 0.0, 0.0)
         else:
-            mode = RESAMPLE_PERMUTED_FIXED
+            mode = RESAMPLE_PERMUTED_FIXED if cfg.permute else RESAMPLE_FIXED
             jm, js, jc = (JITTER_NORMAL, cfg.jitter_sigma, cfg.jitter_clip) if jitter_on else (JITTER_NONE, 0.0, 0.0)
         out.append(CloudParams(R, t, float(scale), bool(scale_on), jm, js, jc, centered, cfg.normals, k, mode))
     return out[0], out[1]

@@ -23,16 +23,20 @@ The train / val branches (bottom of this file): `ThreeDMatchTrain` (pickled frag
 threeDMatch_loader.py:39-115, :139-159), `KittiOdometryTrain` (prepare_kitti, kitti_loader.py:80-96, :299-346, :384-406) and
 `TrainBatches`, which turns either into device-resident training batches: host parsing, then voxel grid -> augmentation
 (`Engine.augment`, csrc/augment.hip; the rule is deepsir_amd/augment.py) -> ground-truth matches (`Engine.radius_matches`), all
-on the device."""
+on the device.  `OxfordTrain` / `OxfordTest` (oxford_loader.py): the train split has one scan per sample and no pose - the pair is the
+scan cropped twice by random half-spaces (`Engine.halfspace_crop`, csrc/crop.hip; the rule is deepsir_amd/crop.py) under the identity."""
 from __future__ import annotations
 
 import glob
+import logging
 import os
 import pickle
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
+
+_logger = logging.getLogger(__name__)
 
 # the reference's split files (dataloader/split/test_3dmatch.txt, test_kitti.txt): the standard public test splits
 THREEDMATCH_TEST_SCENES = (
@@ -473,6 +477,121 @@ class KittiOdometryTrain(KittiOdometryTest):
         return scans[0], scans[1], M, {"seq": drive, "id_src": t0, "id_ref": t1}
 
 
+OXFORD_CROP = (0.0, 50.0, -3.0, 20.0)            # process_point_cloud(r_min, r_max, z_min, z_max) of oxford_loader.py:168-169
+
+
+def read_oxford_train_list(path: str) -> List[Dict[str, object]]:
+    """`train_relative.txt` (oxford_loader.py:62-86): lines `file | positives | non-negatives` -> [{'file', 'pos_list', 'nonneg_list'}];
+    a line that does not have three fields is skipped with a log message, as in the reference."""
+    out = []
+    with open(path, "r") as f:
+        for i, line in enumerate(f.readlines()):
+            parts = line.split("|")
+            if len(parts) != 3:
+                _logger.info("Invalid line %d: %s", i, parts)
+                continue
+            out.append({"file": parts[0].strip(), "pos_list": [int(x) for x in parts[1].split()],
+                        "nonneg_list": [int(x) for x in parts[2].split()]})
+    return out
+
+
+class OxfordTrain:
+    """The Oxford train split (oxford_loader.py:16-86, :137-153): every line of `<root>/train_np_nofilter/train_relative.txt` is one
+    sample, ONE scan `[n, 7]` = [x y z nx ny nz curvature] of which the first `feat_len` columns are kept.  There is no second scan and
+    no pose: the pair is the scan cropped twice by random half-spaces keeping `p_crop` of its rows (`self_pair_crop`, which
+    `TrainBatches` runs on the device per batch), ground truth the identity, and the augmentation supplies the motion
+    (apply_augment_V2 with rotation, jitter and scale 0.8 to 1.2 on, :33-41).  Range crop and voxel grid as :168-175."""
+
+    TRAIN_DIR = "train_np_nofilter"
+
+    def __init__(self, root: str, engine, num_points: int, p_crop: float = 0.6, voxel_size: float = 0.3, feat_len: int = 3,
+                 positive_pair_radius_multiplier: float = 3.0, rot_mag: float = 45.0, trans_mag: float = 2.0, xy_rot_scale: float = 0.1,
+                 reference_gt: bool = False):
+        from .augment import AugmentConfig
+        self.root_path = os.path.join(root, self.TRAIN_DIR)
+        fn = os.path.join(self.root_path, "train_relative.txt")
+        if not os.path.exists(fn):
+            raise FileNotFoundError(fn)
+        if not (0.0 < float(p_crop) <= 1.0):
+            raise ValueError("OxfordTrain: p_crop is a share of the scan, in (0, 1]")
+        self.engine, self.split, self.voxel_size, self.crop = engine, "train", float(voxel_size), OXFORD_CROP
+        self.files = read_oxford_train_list(fn)
+        self.feat_len, self.label_col = max(3, min(int(feat_len), 7)), None
+        self.self_pair_crop = float(p_crop)
+        self.match_radius = self.voxel_size * float(positive_pair_radius_multiplier)
+        self.augment_cfg = AugmentConfig(variant="v2", num_points=int(num_points), random_rotation=True, random_jitter=True,
+                                         random_scale=True, min_scale=0.8, max_scale=1.2, rot_mag=rot_mag, trans_mag=trans_mag,
+                                         xy_rot_scale=xy_rot_scale, reference_gt=reference_gt)
+
+    def __len__(self):
+        return len(self.files)
+
+    def raw(self, index: int) -> np.ndarray:
+        """The one scan of a sample, [n, feat_len] float32 (:142-144)."""
+        a = np.load(os.path.join(self.root_path, self.files[index]["file"]))
+        return np.ascontiguousarray(a[:, :self.feat_len], dtype=np.float32)
+
+    def others(self, index: int) -> Dict[str, object]:
+        name = self.files[index]["file"]
+        return {"seq": None, "id_src": name, "id_ref": name}
+
+
+class OxfordTest:
+    """The Oxford val / test split (oxford_loader.py:88-94, :155-183): `<root>/test_models_20k_np_nofilter/groundtruths.pkl` is a list
+    of dicts with `anc_idx`, `pos_idx`, `t` and `q` = [qw qx qy qz]; src = `<pos_idx>.npy`, ref = `<anc_idx>.npy`, the pose
+    `se3.xyzquat2mat`.  No half-space crop; the range crop and voxel grid of the train split; augmentation off and no permutation
+    (apply_augment_V2 with fixed=True: the cloud with fewer voxels is tiled to the size of the other, in voxel order), or
+    `num_points` rows of each.  `num_val` > 0 truncates the val split.  Yields the dicts `harness.inference_align` takes; with
+    `num_points` it is also a dataset `TrainBatches` accepts (`raw`, the validation batches of the training loop)."""
+
+    TEST_DIR = "test_models_20k_np_nofilter"
+
+    def __init__(self, root: str, engine, split: str = "test", num_val: int = -1, voxel_size: float = 0.3, feat_len: int = 3,
+                 num_points: Optional[int] = None, positive_pair_radius_multiplier: float = 3.0):
+        from .augment import AugmentConfig
+        if split not in ("val", "test"):
+            raise ValueError("OxfordTest: split is 'val' or 'test' (the train split is OxfordTrain)")
+        self.root_path = os.path.join(root, self.TEST_DIR)
+        fn = os.path.join(self.root_path, "groundtruths.pkl")
+        if not os.path.exists(fn):
+            raise FileNotFoundError(fn)
+        with open(fn, "rb") as f:
+            self.files = list(pickle.load(f))
+        if num_val > 0 and split == "val":
+            self.files = self.files[:num_val]
+        self.engine, self.split, self.voxel_size, self.crop = engine, split, float(voxel_size), OXFORD_CROP
+        self.feat_len, self.num_points, self.label_col = max(3, min(int(feat_len), 7)), num_points, None
+        self.match_radius = self.voxel_size * float(positive_pair_radius_multiplier)
+        self.augment_cfg = AugmentConfig(variant="v2", num_points=int(num_points or 0), random_rotation=False, random_jitter=False,
+                                         random_scale=False, permute=False)
+
+    def __len__(self):
+        return len(self.files)
+
+    def pose(self, index: int) -> np.ndarray:
+        """[4, 4] float64: ref = R src + t (:163-166)."""
+        from .se3 import xyzquat2mat
+        rec = self.files[index]
+        return xyzquat2mat(np.concatenate([np.asarray(rec["t"], np.float64).reshape(3), np.asarray(rec["q"], np.float64).reshape(4)]))
+
+    def raw(self, index: int):
+        """Host part of get_data (:155-166): (src [n, feat_len], ref [n', feat_len] float32, pose [4, 4], others)."""
+        rec = self.files[index]
+        pos, anc = int(rec["pos_idx"]), int(rec["anc_idx"])
+        src, ref = (np.ascontiguousarray(np.load(os.path.join(self.root_path, "%d.npy" % i))[:, :self.feat_len], dtype=np.float32)
+                    for i in (pos, anc))
+        return src, ref, self.pose(index), {"seq": None, "id_src": pos, "id_ref": anc}
+
+    def __getitem__(self, index: int) -> Dict[str, object]:
+        src, ref, pose, others = self.raw(index)
+        raw = [src, ref]
+        vox, counts = self.engine.voxel_downsample([_to_device(self.engine, c) for c in raw], self.voxel_size, self.crop)
+        k = int(self.num_points) if self.num_points else int(counts.max().item())
+        pts = self.engine.resample(vox, counts, max(k, 1), 0, "fixed")
+        return {"points_src": pts[0].contiguous(), "points_ref": pts[1].contiguous(), "transform_gt": pose[:3, :].astype(np.float32),
+                "others": others}
+
+
 class TrainBatches:
     """Device-resident training batches of a train / val dataset above: an iterable with `set_epoch(e)`.
 
@@ -486,6 +605,10 @@ class TrainBatches:
     Yields the reference's collate dict (data_base.py:196-219): points_src / points_ref [B, N, feat_len] fp32 and transform_gt
     [B, 3, 4] fp32 on the device, labels_src / labels_ref [B, N] int64 when the dataset has labels, matches (list of B int64
     arrays [n', 2]) or match_radius, others (list of B dicts), plus `invalid` [2, B] int32 (`Engine.augment`).
+
+    A dataset that declares `self_pair_crop = p_keep` (`OxfordTrain`) has ONE scan per sample: the cache then holds the raw scan on
+    the device, once per index, and every batch crops it twice by random half-spaces (`Engine.halfspace_crop`, sides src and ref
+    keyed by (seed, epoch, index)) in front of the same voxel grid, augmentation and matches; the pose is the identity.
 
     Every random number comes from (seed, epoch, dataset index): a sample is the same bytes whatever batch it lands in, and the
     epoch's order is a permutation drawn from the same counter RNG (`augment.epoch_order`)."""
@@ -563,7 +686,41 @@ class TrainBatches:
                 out["matches"] = as_reference_matches(off, cols, src.shape[0], src.shape[1])
         return out
 
+    def scans(self, indices: Sequence[int]) -> List[tuple]:
+        """self_pair_crop datasets: (scan [n, C] on the device, others) of every index, from the cache where present."""
+        ds, fresh = self.dataset, {}
+        for i in dict.fromkeys(indices):
+            if i not in self.cache:
+                fresh[i] = (_to_device(self.engine, ds.raw(i)), ds.others(i))
+                if len(self.cache) < self.cache_size:
+                    self.cache[i] = fresh[i]
+        return [self.cache[i] if i in self.cache else fresh[i] for i in indices]
+
+    def self_pairs(self, indices: Sequence[int]):
+        """One scan per sample -> (voxels [2, B, cap, C], counts [2, B] i32, identity poses, others): both half-space crops of every scan
+        in ONE call (clouds 0..B-1 the src side, B..2B-1 the ref side), then the ragged voxel grid over the 2 B crops."""
+        from .augment import SIDE_REF, SIDE_SRC
+        ds, B = self.dataset, len(indices)
+        items = self.scans(indices)
+        n = [int(it[0].shape[0]) for it in items]
+        cap = max(1, max(n))
+        raw = torch.zeros((2 * B, cap, items[0][0].shape[1]), dtype=torch.float32, device=self.engine.device)
+        for b, it in enumerate(items):
+            raw[b, :n[b]] = it[0]
+            raw[B + b, :n[b]] = it[0]
+        counts = torch.from_numpy(np.asarray(n + n, np.int32)).to(self.engine.device)
+        out, kept, _ = self.engine.halfspace_crop(raw, counts, ds.self_pair_crop, self.seed, self.epoch, list(indices) + list(indices),
+                                                  [SIDE_SRC] * B + [SIDE_REF] * B)
+        m = kept.cpu().tolist()
+        vox, vcounts = self.engine.voxel_downsample([out[c, :m[c]] for c in range(2 * B)], ds.voxel_size, ds.crop)
+        capv = max(1, int(vcounts.max().item()))
+        vox = vox[:, :capv].contiguous().view(2, B, capv, vox.shape[2])
+        return vox, vcounts.view(2, B), np.tile(np.identity(4), (B, 1, 1)), [it[1] for it in items]
+
     def batch(self, indices: Sequence[int]) -> Dict[str, object]:
+        if getattr(self.dataset, "self_pair_crop", None) is not None:
+            vox, counts, poses, others = self.self_pairs(indices)
+            return self.finish(vox, counts, poses, indices, others)
         items = self.voxels(indices)
         vox, counts, poses = self.assemble(items)
         return self.finish(vox, counts, poses, indices, [it[3] for it in items])

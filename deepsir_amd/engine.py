@@ -464,6 +464,45 @@ class Engine:
             return out[0], out[1], gt, invalid, rows[0], rows[1]
         return out[0], out[1], gt, invalid
 
+    def halfspace_crop(self, points: torch.Tensor, counts: torch.Tensor, p_keep, seed: int, epoch: int, indices: Sequence[int], sides,
+                       out_cap: Optional[int] = None, directions=None):
+        """Transforms.RandomCrop.crop for a ragged batch on the device (csrc/crop.hip; the rule: deepsir_amd/crop.py).  points
+        [clouds, cap, C] + counts [clouds] i32, p_keep a float or one per cloud, indices the clouds' DATASET indices and sides their
+        sides (an int or one per cloud): the direction of a cloud comes from (seed, epoch, index, side), never from its position in
+        the call -> (out [clouds, out_cap, C]: the kept rows in input order, zeros behind them; out_counts [clouds] i32, which may
+        exceed out_cap - then the first out_cap rows are written; invalid [clouds] i32: bit 0 nothing came in or is kept, bit 1
+        non-finite centroid or threshold).  ``directions`` [clouds, 3] replaces the drawn ones.  Host work: the directions, uploaded
+        as one tensor; no synchronisation."""
+        from . import crop as K
+        ops = self._train_ops()
+        points, counts = _chk(points, torch.float32, "points"), _chk(counts, torch.int32, "counts")
+        if points.dim() != 3 or points.shape[2] < 3 or counts.numel() != points.shape[0] or points.shape[0] < 1 or points.shape[1] < 1:
+            raise EngineError("halfspace_crop: points [clouds >= 1, cap >= 1, C >= 3] and counts [clouds] expected")
+        clouds, cap, stride = points.shape
+        pk = np.ascontiguousarray(np.broadcast_to(np.asarray(p_keep, np.float64), (clouds,)))
+        if not (np.isfinite(pk) & (pk > 0.0)).all():
+            raise EngineError("halfspace_crop: every p_keep must be finite and > 0")
+        sides = np.broadcast_to(np.asarray(sides, np.int64), (clouds,))
+        if len(indices) != clouds:
+            raise EngineError("halfspace_crop: one dataset index per cloud expected")
+        dirs = K.crop_directions(seed, epoch, indices, sides) if directions is None else np.asarray(directions, np.float32)
+        if dirs.shape != (clouds, 3):
+            raise EngineError("halfspace_crop: directions [clouds, 3] expected")
+        out_cap = int(out_cap or cap)
+        dev = torch.from_numpy(np.ascontiguousarray(dirs)).to(self.device, non_blocking=True)
+        cen = self._empty((clouds, 3), torch.float64)
+        inv = self._empty((clouds,), torch.int32)
+        out = torch.zeros((clouds, out_cap, stride), dtype=torch.float32, device=self.device)
+        out_counts = self._empty((clouds,), torch.int32)
+        nbytes = int(self.lib.dsir_t_halfspace_crop_scratch(clouds, cap))
+        if nbytes == 0 or out_cap < 1:
+            raise EngineError("halfspace_crop: shape refused (clouds * cap and clouds * out_cap must stay below 2^31, clouds <= 65535)")
+        sc = ops.scratch(max(int(self.lib.dsir_t_cloud_centroids_scratch(clouds)), nbytes))
+        ops._launch("dsir_t_cloud_centroids", _ptr(points), _ptr(counts), clouds, cap, stride, _ptr(cen), _ptr(inv), _ptr(sc))
+        ops._launch("dsir_t_halfspace_crop", _ptr(points), _ptr(counts), clouds, cap, stride, _ptr(dev), pk.ctypes.data, _ptr(cen), out_cap,
+                    _ptr(out), _ptr(out_counts), _ptr(inv), _ptr(sc))
+        return out, out_counts, inv
+
     # ------------------------------------------------------------------ after the path: metrics
     METRIC_NAMES = ("r_mse", "r_mae", "t_mse", "t_mae", "err_r_deg", "err_t", "succ", "chamfer_dist")
 

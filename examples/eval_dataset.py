@@ -3,6 +3,7 @@
 
     python examples/eval_dataset.py --dataset 3DMatch --root /data/3DMatch --num-points 5000 [--ckpt model.pth] [--limit 50]
     python examples/eval_dataset.py --dataset KITTI   --root /data/kitti   --num-points 16384 --voxel-size 0.3
+    python examples/eval_dataset.py --dataset Oxford  --root /data/oxford  --num-points 10000
 
 Directory layouts are the reference's (dataloader/threeDMatch_loader.py, kitti_loader.py); see deepsir_amd/data.py.
 Without --ckpt a seeded random state-dict is used (plumbing check only)."""
@@ -23,7 +24,7 @@ from deepsir_amd.weights import generate_state_dict, to_torch_state_dict  # noqa
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--dataset", choices=["3DMatch", "KITTI"], required=True)
+    ap.add_argument("--dataset", choices=["3DMatch", "KITTI", "Oxford"], required=True)
     ap.add_argument("--root", required=True)
     ap.add_argument("--ckpt", default="")
     ap.add_argument("--num-points", type=int, default=5000)
@@ -52,8 +53,10 @@ def main():
     model.load_state_dict(sd["state_dict"] if "state_dict" in sd else sd)
     model = model.cuda().eval()
     eng = model._ensure_engine(max(a.num_points, 1024), a.batch)   # the engine also runs the datasets' device steps
-    voxel = a.voxel_size or (0.3 if kitti else 0.03)
+    oxford = a.dataset == "Oxford"
+    voxel = a.voxel_size or (0.3 if kitti or oxford else 0.03)
     ds = (D.KittiOdometryTest(a.root, eng, voxel_size=voxel, feat_len=cfg.feat_len, num_points=a.num_points) if kitti
+          else D.OxfordTest(a.root, eng, "test", voxel_size=voxel, feat_len=cfg.feat_len, num_points=a.num_points) if oxford
           else D.ThreeDMatchTest(a.root, eng, voxel_size=voxel, num_points=a.num_points))
     n = min(len(ds), a.limit) if a.limit else len(ds)
     pairs = [D.as_batch(ds[i]) for i in range(n)]

@@ -3,6 +3,7 @@ over ``deepsir_amd.data.TrainBatches`` (no open3d, no reference code):
 
     python examples/train_dataset.py --dataset 3dmatch --root /data/3dmatch --points 2048 --batch 2 --steps 100 --out runs/a
     python examples/train_dataset.py --dataset kitti --root /data/kitti --points 18000 --batch 8 --epochs 2 --out runs/k
+    python examples/train_dataset.py --dataset Oxford --root /data/oxford --points 10000 --batch 8 --epochs 2 --out runs/o
 
 Per epoch: device-resident batches (voxel grid, augmentation, ground-truth matches: all HIP) -> ``Network.train_step`` (Adam on the
 device).  Every --val-every steps: the val split through the evaluation-mode network, ``loss_align_fun(..., reduction='none')``
@@ -59,7 +60,7 @@ def save_checkpoint(path, model, lr, step):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--dataset", choices=["3dmatch", "kitti"], default="3dmatch")
+    ap.add_argument("--dataset", choices=["3dmatch", "kitti", "Oxford"], default="3dmatch")
     ap.add_argument("--root", required=True)
     ap.add_argument("--out", required=True)
     ap.add_argument("--points", type=int, default=2048)
@@ -103,6 +104,9 @@ def main():
                   with_labels=os.path.isdir(os.path.join(a.root, "dataset", "sequences", "%02d" % (a.sequences or [0])[0], "labels")))
         train = D.KittiOdometryTrain(a.root, eng, "train", sequences=a.sequences, **kw)
         val = D.KittiOdometryTrain(a.root, eng, "val", sequences=a.val_sequences, num_val=a.num_val, **kw)
+    elif a.dataset == "Oxford":        # one scan per sample, cropped twice on the device; validation on the ground-truth pairs
+        train = D.OxfordTrain(a.root, eng, num_points=a.points, voxel_size=a.voxel_size or 0.3)
+        val = D.OxfordTest(a.root, eng, "val", num_val=a.num_val, voxel_size=a.voxel_size or 0.3, num_points=a.points)
     else:
         kw = dict(voxel_size=a.voxel_size or 0.03, num_points=a.points)
         train = D.ThreeDMatchTrain(a.root, eng, "train", **kw)
@@ -134,7 +138,7 @@ def main():
             emit(rec)
             if step % a.val_every == 0 or step == a.steps:
                 rec = {"event": "val", "step": step}
-                rec.update(validate(model, val_batches, a.iters, "KITTI" if kitti else "3DMatch"))
+                rec.update(validate(model, val_batches, a.iters, "KITTI" if kitti else ("Oxford" if a.dataset == "Oxford" else "3DMatch")))
                 save_checkpoint(ckpt, model, a.lr, step)
                 emit(rec)
             if step >= a.steps:

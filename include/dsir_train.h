@@ -240,6 +240,33 @@ int dsir_t_augment(void* stream, const float* in, const int32_t* counts, int clo
 int dsir_t_augment_gt(void* stream, const double* M, const void* params_src, const void* params_ref, const double* centroids_src,
                       const double* centroids_ref, int pairs, int reference_gt, float* transform_gt);
 
+/* ---- half-space crop (csrc/crop.hip) ---------------------------------------------------------------------------------------------
+ * Transforms.RandomCrop.crop (dataloader/transformation.py:121-145) as the Oxford loader applies it twice to one scan
+ * (dataloader/oxford_loader.py:141-153, p_crop = 0.6): the rows of a cloud beyond a plane normal to a random
+ * direction, placed at the (1 - p_keep) quantile of the rows' projections onto that direction.  The reference's RNG and np.percentile's interpolation
+ * cannot be pinned; the rule is this engine's and is written down in deepsir_amd/crop.py (the host restatement the tests compare
+ * against bit for bit):
+ *   d_j = ((px - mx) ux + (py - my) uy) + (pz - mz) uz, fp32, every operation rounded, no fused multiply-add, m = the centroid of
+ *   dsir_t_cloud_centroids rounded to fp32; with n = min(counts[c], cap) rows, v = (n - 1) * (((1 - p_keep) * 100) / 100) in float64
+ *   and lo = floor(v): row j is kept iff d_j > d_(lo), the lo-th smallest projection (0-based; -0 equals +0).  p_keep == 0.5 keeps
+ *   d_j > 0, p_keep >= 1 every row.  A row with a non-finite d_j is dropped, counts in n and sorts last.  In exact arithmetic this is
+ *   dist > np.percentile(dist, q); numpy keeps one row fewer only where v is within rounding of an integer from below.
+ * Per cloud, never an error - invalid [clouds] int32: bit 0 = no rows came in or none is kept (count 0), bit 1 = non-finite centroid,
+ * or d_(lo) itself not finite (count 0).
+ * in [clouds][cap][stride] + counts (device) -> out [clouds][out_cap][stride]: the kept rows in input order, every column copied;
+ * out_counts [clouds] = kept rows, which may exceed out_cap - then the first out_cap are written and the check is the caller's, as
+ * with dsir_voxel_downsample.  dirs [clouds][3] fp32 (device): the unit directions, per-cloud numbers the host draws like the
+ * rotations; p_keep [clouds] float64 (HOST; each > 0 and finite, else an error before any launch); centroids [clouds][3] float64
+ * (device) from dsir_t_cloud_centroids on the same input.
+ * Radix select of one rank per cloud (four 8-bit digit histograms, integer LDS atomics), then a stable compaction by per-workgroup
+ * counts prefixed in workgroup order: no sort, no floating-point atomics, no atomic that decides a position, no host round trip
+ * between the launches.  Two runs write the same bytes and a cloud's output does not depend on the rest of the call.
+ * scratch: dsir_t_halfspace_crop_scratch(clouds, cap) bytes (0: shape refused). */
+size_t dsir_t_halfspace_crop_scratch(int clouds, int cap);
+int dsir_t_halfspace_crop(void* stream, const float* in, const int32_t* counts, int clouds, int cap, int stride, const float* dirs,
+                          const double* p_keep, const double* centroids, int out_cap, float* out, int32_t* out_counts, int32_t* invalid,
+                          void* scratch);
+
 /* ---- fragment overlap: radius-bounded nearest neighbour of one ragged cloud in another (csrc/overlap.hip) ------------------------
  * The core of the reference's offline dataloader/3DMatch_preprocess.py:82-89 (cv2.BFMatcher.match + distance < voxel size) for every
  * fragment pair of a scene; cv2 is not installable here: parity is unpinned, the engine owns the rule (deepsir_amd/overlap.py,
