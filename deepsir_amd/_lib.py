@@ -85,6 +85,8 @@ SYMBOLS = {
     "dsir_ppf_pre": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
     "dsir_estimate_normals": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int, c_float_p, C.c_void_p,
                                         C.c_void_p]),
+    "dsir_fpfh": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                            C.c_void_p, C.c_int, C.c_void_p]),
     "dsir_score": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                              C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "dsir_aggregate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int,

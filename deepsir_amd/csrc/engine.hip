@@ -311,6 +311,28 @@ int dsir_estimate_normals(dsir_ctx* c, const float* points, int stride, const in
   return 0;
 }
 
+int dsir_fpfh(dsir_ctx* c, const float* points, int stride, const float* normals, const int32_t* neigh, int64_t neigh_cs,
+              const int32_t* csr_offsets, const int32_t* csr_cols, int clouds, int n, float* desc, int out_ld, int32_t* flags) {
+  if (!c) return 1;
+  if (!points || !desc || clouds < 1 || clouds > 65535 || n < 1 || stride < 3 || out_ld < kFpfhDim) return fail(c, "dsir_fpfh: bad arguments");
+  if (!normals && stride < 6) return fail(c, "dsir_fpfh: without normals the rows need xyz + normal, at least 6 columns, got %d", stride);
+  const bool fixed = neigh != nullptr, csr = csr_offsets != nullptr || csr_cols != nullptr;
+  if (fixed == csr) return fail(c, "dsir_fpfh: exactly one of neigh_idx and (csr_offsets, csr_cols) expected");
+  if (csr && (!csr_offsets || !csr_cols)) return fail(c, "dsir_fpfh: a CSR list needs both csr_offsets and csr_cols");
+  if ((int64_t)clouds * n > 0x7fffffffll / kFpfhRow) return fail(c, "dsir_fpfh: clouds x n = %lld rows beyond the int32 range of the SPFH table", (long long)clouds * n);
+  HIP_OK(c, hipSetDevice(c->device));
+  c->ws.top = 0; c->ws.overflow = false;
+  FpfhArgs a;
+  a.table = reinterpret_cast<int32_t*>(c->ws.raw(fpfh_scratch_bytes(clouds, n)));
+  if (c->ws.overflow) return fail(c, "workspace too small for dsir_fpfh (clouds x n x 136 bytes: raise max_points / max_pairs)");
+  a.pts = points; a.pts_cs = (int64_t)n * stride; a.pts_ld = stride;
+  a.nrm = normals ? normals : points + 3; a.nrm_ld = normals ? 3 : stride; a.nrm_cs = (int64_t)n * a.nrm_ld;
+  a.cols = fixed ? neigh : csr_cols; a.neigh_cs = neigh_cs; a.offsets = csr_offsets;
+  a.desc = desc; a.out_ld = out_ld; a.flags = flags; a.n = n; a.clouds = clouds;
+  if (!launch_fpfh(a, c->stream)) return fail(c, "dsir_fpfh: shape refused");
+  return post(c);
+}
+
 int dsir_score(dsir_ctx* c, const float* feat, const float* logits, const float* xyz, int64_t xyz_cs,
                const int32_t* neigh, int64_t neigh_cs, int clouds, int n, float* score, int32_t* label) {
   if (check_ready(c)) return 1;

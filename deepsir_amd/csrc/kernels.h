@@ -194,6 +194,23 @@ bool launch_ppf_pre(const PpfArgs& a, hipStream_t st);                // false: 
 void launch_estimate_normals(const float* pts, int64_t pts_cs, int stride, const int32_t* neigh, int64_t neigh_cs, int n, int clouds,
                              float vx, float vy, float vz, float* normals, int32_t* flags, hipStream_t st);
 
+// fpfh.hip - FPFH descriptors from points, normals and neighbour lists (the rule: the file's header).  One body serves both list
+// forms: a row is cols[start(i) .. start(i) + deg(i)); offsets == nullptr: the fixed form, start = cloud * neigh_cs + 16 i, deg = 16.
+constexpr int kFpfhDim = 33;                // 3 blocks of 11 bins
+constexpr int kFpfhRow = kFpfhDim + 1;      // the SPFH table's row: 33 integer counts and valid(i)
+struct FpfhArgs {
+  const float* pts = nullptr; int64_t pts_cs = 0; int pts_ld = 3;     // [clouds][n][pts_ld], 3 columns used
+  const float* nrm = nullptr; int64_t nrm_cs = 0; int nrm_ld = 3;     // [clouds][n][nrm_ld], 3 columns used
+  const int32_t* cols = nullptr; int64_t neigh_cs = 0;                // fixed: [clouds][..][16], neigh_cs ints between clouds; CSR: the columns
+  const int32_t* offsets = nullptr;                                   // CSR: [clouds * n + 1], else nullptr
+  int32_t* table = nullptr;                                           // scratch [clouds][n][kFpfhRow] (fpfh_scratch_bytes)
+  float* desc = nullptr; int out_ld = 64;                             // [clouds][n][out_ld], out_ld >= kFpfhDim
+  int32_t* flags = nullptr;                                           // [clouds][n] or nullptr
+  int n = 0, clouds = 0;
+};
+size_t fpfh_scratch_bytes(int clouds, int n);
+bool launch_fpfh(const FpfhArgs& a, hipStream_t st);                  // false: outside the envelope (nothing launched)
+
 // mlp_out + fc_label fused (head_mlp.hip): x[32] -> feat[64] -> 64 -> 32 -> ncls   (RandLANet.py:363-367)
 struct HeadArgs {
   Seg in = {};                  // last decoder block, [clouds][M][32], lazy GroupNorm + LeakyReLU

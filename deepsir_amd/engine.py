@@ -218,6 +218,47 @@ class Engine:
         self.sync()
         return normals, flags
 
+    def fpfh(self, points, normals=None, neigh_multi=None, csr=None, pad_to: int = 64):
+        """FPFH descriptors (include/dsir.h, dsir_fpfh; the rule: csrc/fpfh.hip, restated in deepsir_amd/fpfh.py): points [c,n,>=3],
+        normals [c,n,3] (None: columns 3..5 of the rows) and exactly one of neigh_multi [c,S,16] (the pyramid's neigh_idx, its
+        level-0 rows are read) and csr = (offsets [c n + 1] i32, cols i32 with cloud-local columns: what ``radius_matches(x, x,
+        identity, r)`` returns) -> (desc [c,n,pad_to]: 33 values and zeros, pad_to = 64 feeds ``feature_correspondences``;
+        flags [c,n] i32: 1 = no valid pair, the row is all zeros).  Needs no weights."""
+        points = _chk(points, torch.float32, "points")
+        if points.dim() != 3 or points.shape[2] < 3 or points.shape[0] < 1 or points.shape[1] < 1:
+            raise EngineError("fpfh: points [clouds >= 1, n >= 1, C >= 3] expected")
+        c, n, stride = points.shape
+        if normals is not None:
+            normals = _chk(normals, torch.float32, "normals")
+            if tuple(normals.shape) != (c, n, 3):
+                raise EngineError(f"fpfh: normals must be [{c}, {n}, 3], got {tuple(normals.shape)}")
+        if (neigh_multi is None) == (csr is None):
+            raise EngineError("fpfh: exactly one of neigh_multi and csr expected")
+        if pad_to < 33:
+            raise EngineError("fpfh: pad_to >= 33 (the descriptor has 33 values)")
+        neigh_cs, off, cols = 0, None, None
+        if neigh_multi is not None:
+            neigh_multi = _chk(neigh_multi, torch.int32, "neigh_idx")
+            if neigh_multi.dim() != 3 or neigh_multi.shape[0] != c or neigh_multi.shape[1] < n or neigh_multi.shape[2] != 16:
+                raise EngineError(f"fpfh: neigh_multi must be [{c}, >= {n}, 16], got {tuple(neigh_multi.shape)}")
+            neigh_cs = neigh_multi.shape[1] * 16
+        else:
+            off, cols = _chk(csr[0], torch.int32, "csr offsets"), _chk(csr[1], torch.int32, "csr cols")
+            if off.numel() != c * n + 1:
+                raise EngineError(f"fpfh: csr offsets must have clouds * n + 1 = {c * n + 1} entries, got {off.numel()}")
+            # the kernels trust the offsets: refuse a list that would leave cols (two reductions and one read-back, no descriptor work)
+            if int(off[0]) != 0 or int(off[-1]) != cols.numel() or bool((off[1:] < off[:-1]).any()):
+                raise EngineError("fpfh: csr offsets must start at 0, be non-decreasing and end at len(cols)")
+            if cols.numel() == 0:                                   # every row empty: the kernels still want a pointer
+                cols = torch.zeros((1,), dtype=torch.int32, device=self.device)
+        desc = self._empty((c, n, int(pad_to)))
+        flags = self._empty((c, n), torch.int32)
+        self._pre()
+        self._call(self.lib.dsir_fpfh(self.h, _ptr(points), stride, _ptr(normals), _ptr(neigh_multi), neigh_cs, _ptr(off), _ptr(cols),
+                                      c, n, _ptr(desc), int(pad_to), _ptr(flags)))
+        self.sync()
+        return desc, flags
+
     def score(self, feat, logits, xyz_multi, neigh_multi):
         """torch.max(logits) + score_fun counterpart -> (score [c,n], label [c,n] i32)."""
         feat, logits = _chk(feat, torch.float32, "feat"), _chk(logits, torch.float32, "logits")

@@ -346,6 +346,75 @@ def register_feat(pairs: Sequence[Dict[str, np.ndarray]], model, voxel_size: flo
     return pred, stats
 
 
+def _fpfh_side(engine, pts, viewpoints, radius):
+    """One side of a batch for ``register_fpfh``: pts [B, N, C] -> (desc [B, N, 64], flags [B, N], normals [B, N, 3])."""
+    _, neigh, _, _ = engine.knn_pyramid(pts)
+    if all(v == viewpoints[0] for v in viewpoints):
+        normals, _ = engine.estimate_normals(pts, neigh, viewpoints[0])
+    else:                                    # one viewpoint per call; clouds are independent bit for bit, so per-cloud calls change nothing
+        normals = torch.cat([engine.estimate_normals(pts[b:b + 1], neigh[b:b + 1], viewpoints[b])[0] for b in range(pts.shape[0])], 0)
+    if radius is None:
+        desc, flags = engine.fpfh(pts, normals, neigh_multi=neigh)
+    else:
+        eye = torch.eye(3, 4, device=pts.device).repeat(pts.shape[0], 1, 1).contiguous()
+        desc, flags = engine.fpfh(pts, normals, csr=engine.radius_matches(pts, pts, eye, float(radius)))
+    return desc, flags, normals
+
+
+@torch.no_grad()
+def register_fpfh(pairs: Sequence[Dict[str, np.ndarray]], engine, voxel_size: float = 0.3, radius: Optional[float] = None,
+                  hypotheses: int = 8192, mutual: bool = True, num_reg: int = 1, dataset_type: str = "3DMatch", batch: int = 1,
+                  device: Optional[torch.device] = None, ransac_n: int = 3, edge_sim: float = 0.9, refine_iters: int = 2, seed: int = 0,
+                  want_corr: bool = False):
+    """The weight-independent baseline of ``register_feat``: FPFH + feature-matching RANSAC (open3d compute_fpfh_feature ->
+    registration_ransac_based_on_feature_matching; parity unpinned, the rules are the engine's own), all on the device.  Per batch
+    and side: ``knn_pyramid`` -> ``estimate_normals`` on its level-0 lists (towards the pair's optional ``viewpoint_src`` /
+    ``viewpoint_ref`` entry, 3 floats; default the origin) -> ``fpfh`` over those 16-NN lists, or with ``radius`` set over the CSR of
+    ``radius_matches(x, x, identity, radius)`` -> ``feature_correspondences(mutual)`` -> ``ransac_correspondence`` (threshold
+    2 x voxel size).  Returns what ``register_feat`` returns - (pred_transforms [n_pairs, num_reg, 3, 4], stats [n_pairs, 5] rows
+    ``[succ, rte, rre, time, seq]``) - so ``evaluate_align`` and ``Engine.icp_refine`` take it the same way; with ``want_corr`` a
+    third value, per pair the (corr [count, 2], flags_src [J], flags_ref [K]) numpy arrays.
+
+    ``engine`` is a ``deepsir_amd.engine.Engine`` THE CALLER PREPARED: the descriptor itself needs no weights, but the pyramid and
+    the other existing entries this calls refuse a context whose weights are not loaded (``check_ready``, csrc/engine_ctx.h), so
+    load a state dict first - any, e.g. ``weights.generate_state_dict(cfg, 0)``; its values are never read here.  Its max_points /
+    max_pairs must cover the clouds and ``batch``; the clouds must be ones the pyramid takes (>= 1024 points with the default
+    ratios)."""
+    device = device or torch.device("cuda", torch.cuda.current_device())
+    rte_t, rre_t = THRESHOLDS[dataset_type]
+    preds, corrs, stats = [], [], np.zeros((len(pairs), 5))
+
+    def view(i, side):
+        v = pairs[i].get("viewpoint_" + side)
+        return (0.0, 0.0, 0.0) if v is None else tuple(float(x) for x in np.asarray(v.cpu() if isinstance(v, torch.Tensor) else v).reshape(-1)[:3])
+
+    for ids, data in _pair_batches(pairs, batch, device):
+        torch.cuda.synchronize(device)
+        t0 = time.time()
+        xs, xr = data["points_src"].float().contiguous(), data["points_ref"].float().contiguous()
+        ds, fs, _ = _fpfh_side(engine, xs, [view(i, "src") for i in ids], radius)
+        dr, fr, _ = _fpfh_side(engine, xr, [view(i, "ref") for i in ids], radius)
+        corr, counts = engine.feature_correspondences(ds, dr, mutual=mutual)
+        T, _, _ = engine.ransac_correspondence(xs, xr, corr, 2.0 * voxel_size, counts=counts, ransac_n=ransac_n, edge_sim=edge_sim,
+                                               hypotheses=hypotheses, refine_iters=refine_iters, seed=seed)
+        torch.cuda.synchronize(device)
+        dt = (time.time() - t0) / len(ids)
+        T = T.cpu().numpy()
+        preds.append(np.repeat(T[:, None], num_reg, 1))
+        gt = data["transform_gt"].cpu().numpy() if "transform_gt" in data else None
+        if want_corr:
+            cn, cc = counts.cpu().numpy(), corr.cpu().numpy()
+            corrs += [(cc[j, :cn[j]], fs[j].cpu().numpy(), fr[j].cpu().numpy()) for j in range(len(ids))]
+        for j, i in enumerate(ids):
+            if gt is not None:
+                stats[i, :3] = rte_rre(T[j], gt[j], rte_t, rre_t)
+            stats[i, 3] = dt
+            others = pairs[i].get("others")
+            stats[i, 4] = _seq_id(others[0]["seq"]) if others else -1
+    pred = np.concatenate(preds, 0) if preds else np.zeros((0, num_reg, 3, 4), np.float32)
+    return (pred, stats, corrs) if want_corr else (pred, stats)
+
+
 @torch.no_grad()
 def inference_label(pairs: Sequence[Dict[str, np.ndarray]], model, batch: int = 1, device: Optional[torch.device] = None):
     """test.py::inference_label (:508-567): semantic head over every pair; ``labels_src`` / ``labels_ref`` [1,N]

@@ -6,7 +6,9 @@
     python examples/eval_dataset.py --dataset Oxford  --root /data/oxford  --num-points 10000
 
 Directory layouts are the reference's (dataloader/threeDMatch_loader.py, kitti_loader.py); see deepsir_amd/data.py.
-Without --ckpt a seeded random state-dict is used (plumbing check only)."""
+Without --ckpt a seeded random state-dict is used (plumbing check only).  `--method fpfh` needs no checkpoint at all: the
+weight-independent baseline, FPFH descriptors + feature-matching RANSAC on the device (`harness.register_fpfh`; `--fpfh-radius R`
+takes the descriptors over radius lists instead of the pyramid's 16-NN lists)."""
 import argparse
 import os
 import sys
@@ -17,7 +19,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from deepsir_amd import data as D  # noqa: E402
 from deepsir_amd.arch import NetConfig  # noqa: E402
-from deepsir_amd.harness import evaluate_align, inference_align, register_feat, summarize  # noqa: E402
+from deepsir_amd.harness import evaluate_align, inference_align, register_feat, register_fpfh, summarize  # noqa: E402
 from deepsir_amd.model import Network  # noqa: E402
 from deepsir_amd.weights import generate_state_dict, to_torch_state_dict  # noqa: E402
 
@@ -37,6 +39,8 @@ def main():
     ap.add_argument("--ransac", action="store_true", help="with --pipeline feat: descriptors -> mutual nearest neighbours -> RANSAC pose")
     ap.add_argument("--num-sub", type=int, default=1024, help="key points per cloud of the feat pipeline")
     ap.add_argument("--hypotheses", type=int, default=8192)
+    ap.add_argument("--method", choices=["network", "fpfh"], default="network", help="fpfh: FPFH + RANSAC instead of the network")
+    ap.add_argument("--fpfh-radius", type=float, default=None, help="with --method fpfh: radius lists instead of the 16-NN lists")
     a = ap.parse_args()
     kitti = a.dataset == "KITTI"
     cfg = NetConfig(feat_len=4 if kitti else 3)
@@ -60,7 +64,10 @@ def main():
           else D.ThreeDMatchTest(a.root, eng, voxel_size=voxel, num_points=a.num_points))
     n = min(len(ds), a.limit) if a.limit else len(ds)
     pairs = [D.as_batch(ds[i]) for i in range(n)]
-    if feat:
+    if a.method == "fpfh":
+        pred, stats = register_fpfh(pairs, eng, voxel_size=voxel, radius=a.fpfh_radius, hypotheses=a.hypotheses, dataset_type=a.dataset,
+                                    batch=a.batch)
+    elif feat:
         pred, stats = register_feat(pairs, model, voxel_size=voxel, hypotheses=a.hypotheses, dataset_type=a.dataset, batch=a.batch)
     else:
         pred, stats = inference_align(pairs, model, a.iters, a.dataset, batch=a.batch,

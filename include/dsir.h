@@ -144,6 +144,22 @@ int dsir_ppf_pre(dsir_ctx* ctx, int which, const float* rows, int stride, const 
 int dsir_estimate_normals(dsir_ctx* ctx, const float* points, int stride, const int32_t* neigh_idx, int64_t neigh_cloud_stride,
                           int clouds, int n, const float* viewpoint, float* normals, int32_t* flags);
 
+/* FPFH descriptors (the classical feature of open3d's compute_fpfh_feature -> registration_ransac_based_on_feature_matching
+ * baseline, unpinned here: the rule is this engine's own, stated in csrc/fpfh.hip and restated in deepsir_amd/fpfh.py) from
+ * points, normals and neighbour lists, all float64 on the fp32 inputs.  points [clouds][n][stride] (xyz first); normals
+ * [clouds][n][3], or NULL: columns 3..5 of the rows, which needs stride >= 6.  Exactly one list form:
+ *   neigh_idx / neigh_cloud_stride  the fixed 16 entries per point of dsir_estimate_normals (the pyramid's level-0 rows), or
+ *   csr_offsets [clouds * n + 1] / csr_cols  a CSR list with cloud-local columns, the layout of dsir_t_radius_matches_fill for
+ *                                            src == ref; offsets must be non-decreasing and stay inside csr_cols.
+ * Neighbour indices are clamped into the cloud.  -> desc [clouds][n][out_ld] (out_ld >= 33: 33 values, then +0; out_ld = 64 feeds
+ * dsir_feature_correspondences, whose squared distances the zero columns leave unchanged), flags [clouds][n] i32 or NULL (1: the
+ * point has no valid pair, its row is all zeros; not an error).  Scratch: 34 ints per point from the context's workspace; a cloud
+ * set that does not fit is refused before any launch.  Same bytes on every run; clouds are independent, bit for bit.  Any
+ * context serves (no weights needed). */
+int dsir_fpfh(dsir_ctx* ctx, const float* points, int stride, const float* normals, const int32_t* neigh_idx,
+              int64_t neigh_cloud_stride, const int32_t* csr_offsets, const int32_t* csr_cols, int clouds, int n, float* desc,
+              int out_ld, int32_t* flags);
+
 /* Replaces torch.max(logits,1) + Network.feat_score/score_fun with num_sub<=0
  * (network/model.py:638-644, :668-757).
  * feat [clouds][n][64], logits [clouds][n][ncls], xyz [clouds][n][3],
