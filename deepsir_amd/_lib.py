@@ -57,6 +57,11 @@ class dsir_ransac_diag(C.Structure):
     _fields_ = [("hyp_sample", C.c_void_p), ("hyp_T", C.c_void_p), ("hyp_valid", C.c_void_p), ("hyp_count", C.c_void_p)]
 
 
+class dsir_consensus_diag(C.Structure):
+    _fields_ = [("bits", C.c_void_p), ("score", C.c_void_p), ("seed", C.c_void_p), ("seed_members", C.c_void_p), ("seed_T", C.c_void_p),
+                ("seed_valid", C.c_void_p), ("seed_count", C.c_void_p)]
+
+
 class dsir_cloud_out(C.Structure):
     _fields_ = [
         ("xyz", C.c_void_p), ("feat", C.c_void_p), ("logits", C.c_void_p), ("score", C.c_void_p), ("label", C.c_void_p),
@@ -105,6 +110,9 @@ SYMBOLS = {
     "dsir_ransac_correspondence": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                              C.c_int, C.c_float, C.c_int, C.c_float, C.c_int, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_void_p, C.POINTER(dsir_ransac_diag)]),
+    "dsir_consensus_correspondence": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.POINTER(dsir_consensus_diag)]),
     "dsir_feature_correspondences": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                                C.c_void_p]),
     "dsir_pose_finetune": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float,

@@ -832,6 +832,46 @@ int dsir_ransac_correspondence(dsir_ctx* c, const float* points_src, const float
   return post(c);
 }
 
+int dsir_consensus_correspondence(dsir_ctx* c, const float* points_src, const float* points_ref, int pairs, int J, int K, int stride,
+                                  const int32_t* corr, const int32_t* counts, int M, float max_dist, float compat_dist, int seeds,
+                                  int members, int refine_iters, const float* T_init, float* T_out, double* stats, int32_t* invalid,
+                                  const dsir_consensus_diag* diag) {
+  if (!c) return 1;
+  if (!points_src || !points_ref || !corr || !T_out || !stats || !invalid || pairs < 1 || J < 1 || K < 1 || M < 1 || stride < 3 ||
+      !(max_dist > 0.f) || !std::isfinite(max_dist) || !std::isfinite(compat_dist))
+    return fail(c, "dsir_consensus_correspondence: bad arguments");
+  if (seeds < 1 || seeds > DSIR_CONSENSUS_MAX_SEEDS)
+    return fail(c, "dsir_consensus_correspondence: seeds=%d outside [1,%d]", seeds, DSIR_CONSENSUS_MAX_SEEDS);
+  if (members < 3 || members > DSIR_CONSENSUS_MAX_MEMBERS)
+    return fail(c, "dsir_consensus_correspondence: members=%d outside [3,%d]", members, DSIR_CONSENSUS_MAX_MEMBERS);
+  if (refine_iters < 0 || refine_iters > DSIR_RANSAC_MAX_REFINE)
+    return fail(c, "dsir_consensus_correspondence: refine_iters=%d outside [0,%d]", refine_iters, DSIR_RANSAC_MAX_REFINE);
+  if (M > c->cfg.max_points || J > c->cfg.max_points || K > c->cfg.max_points)
+    return fail(c, "dsir_consensus_correspondence: M=%d, J=%d or K=%d beyond max_points=%d", M, J, K, c->cfg.max_points);
+  if (M > DSIR_CONSENSUS_MAX_M) return fail(c, "dsir_consensus_correspondence: M=%d beyond DSIR_CONSENSUS_MAX_M=%d", M, DSIR_CONSENSUS_MAX_M);
+  if ((int64_t)pairs * M > 0x7fffffffll) return fail(c, "dsir_consensus_correspondence: pairs x M = %lld unsupported", (long long)pairs * M);
+  HIP_OK(c, hipSetDevice(c->device));
+  // the whole workspace, validated before the first launch
+  const size_t need = consensus_scratch_bytes(pairs, M, seeds, refine_iters);
+  if (need > c->ws.cap)
+    return fail(c, "workspace too small for dsir_consensus_correspondence: needs %zu bytes (the bit matrix alone: pairs x M x ceil(M / 64) x 8 = "
+                   "%zu), the arena holds %zu (raise max_points / max_pairs, or pass fewer pairs)", need,
+                (size_t)pairs * M * ((size_t)(M + 63) / 64) * 8, c->ws.cap);
+  c->ws.top = 0; c->ws.overflow = false;
+  void* scratch = c->ws.raw(need);
+  if (c->ws.overflow) return fail(c, "workspace too small for dsir_consensus_correspondence");
+  ConsensusArgs a{};
+  a.src = points_src; a.ref = points_ref; a.pairs = pairs; a.J = J; a.K = K; a.stride = stride; a.corr = corr; a.counts = counts;
+  a.M = M; a.max_dist = max_dist; a.compat_dist = compat_dist; a.seeds = seeds; a.members = members; a.refine_iters = refine_iters;
+  a.T_init = T_init; a.T_out = T_out; a.stats = stats; a.invalid = invalid;
+  if (diag) {
+    a.diag_bits = diag->bits; a.diag_score = diag->score; a.diag_seed = diag->seed; a.diag_members = diag->seed_members;
+    a.diag_T = diag->seed_T; a.diag_valid = diag->seed_valid; a.diag_count = diag->seed_count;
+  }
+  if (int r = launch_consensus(a, scratch, c->stream)) return fail(c, "dsir_consensus_correspondence: launch failed (%d)", r);
+  return post(c);
+}
+
 int dsir_pose_finetune(dsir_ctx* c, const float* xyz_src, const float* xyz_ref, const float* weights, int weights_are_logits,
                        int pairs, int m, const float* T_init, float quantization_size, int max_iter, float break_threshold_ratio,
                        int max_break_count, float* T_out, double* stats) {

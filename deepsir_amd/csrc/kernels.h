@@ -537,6 +537,23 @@ void launch_ransac(const RansacArgs& a, void* scratch, hipStream_t st);
 void launch_corr_compact(const int32_t* ab, const int32_t* ba, int pairs, int J, int K, int mutual, int32_t* corr, int32_t* counts,
                          hipStream_t st);
 
+// consensus.hip — spatial-consensus pose from correspondences (second-order compatibility; the rule is stated in the file's header),
+// all pairs at once; returns 0 on success
+struct ConsensusArgs {
+  const float* src; const float* ref;   // [pairs][J][stride], [pairs][K][stride]
+  int pairs, J, K, stride;
+  const int32_t* corr;                  // [pairs][M][2]
+  const int32_t* counts;                // [pairs] or nullptr
+  int M;
+  float max_dist, compat_dist; int seeds, members, refine_iters;
+  const float* T_init;                  // [pairs][3][4] or nullptr (identity)
+  float* T_out; double* stats; int32_t* invalid;
+  uint64_t* diag_bits; int32_t* diag_score; int32_t* diag_seed; int32_t* diag_members;   // optional
+  float* diag_T; int32_t* diag_valid; int32_t* diag_count;
+};
+size_t consensus_scratch_bytes(int pairs, int M, int seeds, int refine_iters);
+int launch_consensus(const ConsensusArgs& a, void* scratch, hipStream_t st);
+
 // finetune.hip — Adam fine-tune of the pose on matched points (test.py:159-207), one workgroup per pair
 void launch_pose_finetune(const float* src, const float* ref, const float* w, int sigmoid, int pairs, int m, const float* T_init,
                           float quant, int max_iter, float break_ratio, int max_break, float* T_out, double* stats,

@@ -41,6 +41,7 @@
 // before the current chunk is consumed; per-lane integer counters end in one integer atomicAdd per hypothesis and slice: exact, so
 // order cannot matter) -> ransac_pick_kernel (max of count << 32 | (0xFFFFFFFF - h)) -> per round ransac_weights_kernel, launch_kabsch,
 // the scoring kernel with H = 1 -> ransac_finish_kernel.  No host synchronisation between them, nothing allocated.
+// The gather, the float64 fit and everything from the scoring on are also the stages of consensus.hip: ransac_stages.h declares them.
 // No MFMA form of the scoring: d2 as a bilinear form <phi(h), psi(i)> cancels terms of 1e2..1e4 m^2 against thresholds of
 // 1e-3..1e-1 m^2 in fp32 and would give up the exact counts.
 //
@@ -51,6 +52,7 @@
 #include "kernels.h"
 #include "device_utils.h"
 #include "svd3.h"
+#include "ransac_stages.h"
 #include "dsir.h"
 
 namespace dsir {
@@ -62,20 +64,12 @@ constexpr int SB = 256;                 // hypotheses per scoring workgroup (one
 static_assert(CH == SB, "a scoring workgroup stages one correspondence per thread and chunk");
 constexpr int HB = 128;                 // hypotheses per fitting workgroup
 
-__device__ __forceinline__ int live_count(const int32_t* counts, int pair, int M) {
-  return counts ? max(0, min(counts[pair], M)) : M;
-}
-
 // squared residual of one correspondence under T: THE fp32 rounding sequence of the rule (checks, scores, weights and stats share it)
 __device__ __forceinline__ float ransac_d2(const float* T, float sx, float sy, float sz, float qx, float qy, float qz) {
   const float dx = __fsub_rn(se3_row(T, 0, sx, sy, sz), qx);
   const float dy = __fsub_rn(se3_row(T, 1, sx, sy, sz), qy);
   const float dz = __fsub_rn(se3_row(T, 2, sx, sy, sz), qz);
   return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
-}
-
-__device__ __forceinline__ bool parked(const float* s, const float* q) {
-  return q[0] == FLT_MAX && q[1] == FLT_MAX && q[2] == FLT_MAX && s[0] == 0.f && s[1] == 0.f && s[2] == 0.f;
 }
 
 // cs / cq [P][M][3]: the matched points, gathered once; dead rows (>= count) and rows with a non-finite coordinate are parked
@@ -137,21 +131,7 @@ __global__ __launch_bounds__(HB) void ransac_hyp_kernel(const float* __restrict_
       ok = ok && !parked(s[k], q[k]);
     }
     if (ok) {
-      double ms[3] = {0, 0, 0}, mq[3] = {0, 0, 0};
-      for (int k = 0; k < n; ++k)
-        for (int c = 0; c < 3; ++c) { ms[c] += (double)s[k][c]; mq[c] += (double)q[k][c]; }
-      for (int c = 0; c < 3; ++c) { ms[c] /= (double)n; mq[c] /= (double)n; }
-      double Hm[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
-      for (int k = 0; k < n; ++k)
-        for (int a = 0; a < 3; ++a)
-          for (int b = 0; b < 3; ++b) Hm[a][b] += ((double)s[k][a] - ms[a]) * ((double)q[k][b] - mq[b]);
-      double U[3][3], S[3], V[3][3], R[3][3];
-      svd3(Hm, U, S, V);
-      procrustes_rotation(U, V, R);
-      for (int r = 0; r < 3; ++r) {
-        for (int c = 0; c < 3; ++c) T[r * 4 + c] = (float)R[r][c];
-        T[r * 4 + 3] = (float)(mq[r] - ((R[r][0] * ms[0] + R[r][1] * ms[1]) + R[r][2] * ms[2]));
-      }
+      fit_rows64(n, [&](int k) { return s[k]; }, [&](int k) { return q[k]; }, T);
       for (int k = 0; k < 12; ++k) ok = ok && isfinite(T[k]);
       if (edge_sim > 0.f) {
         for (int a = 0; a < n; ++a)
@@ -367,49 +347,74 @@ void launch_score(const float* cs, const float* cq, const int32_t* counts, int p
 
 }  // namespace
 
+size_t pose_scratch_bytes(int pairs, int M, int refine_iters) {
+  const size_t P = (size_t)pairs;
+  return 2 * al256(P * M * 12) + al256(P * M * 4) + al256(P * (refine_iters + 1) * 48) + al256(P * (refine_iters + 1) * 4) + al256(P * 16);
+}
+
+PoseScratch pose_scratch_take(char*& p, int pairs, int M, int refine_iters) {
+  const size_t P = (size_t)pairs;
+  auto take = [&](size_t bytes) { char* r = p; p += al256(bytes); return r; };
+  PoseScratch s;
+  s.cs = reinterpret_cast<float*>(take(P * M * 12));
+  s.cq = reinterpret_cast<float*>(take(P * M * 12));
+  s.w = reinterpret_cast<float*>(take(P * M * 4));
+  s.Tcand = reinterpret_cast<float*>(take(P * (refine_iters + 1) * 48));
+  s.cnt = reinterpret_cast<int32_t*>(take(P * (refine_iters + 1) * 4));
+  s.info = reinterpret_cast<int32_t*>(take(P * 16));
+  return s;
+}
+
+void launch_ransac_gather(const float* src, const float* ref, int pairs, int J, int K, int stride, const int32_t* corr,
+                          const int32_t* counts, int M, const PoseScratch& s, int32_t* invalid, hipStream_t st) {
+  hipMemsetAsync(invalid, 0, (size_t)pairs * 4, st);
+  hipLaunchKernelGGL(ransac_gather_kernel, dim3((M + 255) / 256, pairs), dim3(256), 0, st, src, ref, J, K, stride, corr, counts, M, s.cs,
+                     s.cq, invalid);
+}
+
+void launch_ransac_tail(const PoseScratch& s, const int32_t* counts, int pairs, int M, const float* hyp_T, const int32_t* hyp_valid,
+                        int32_t* hyp_count, int H, int R, float thr2, const float* T_init, float* T_out, double* stats, hipStream_t st) {
+  const int P = pairs;
+  const dim3 gm((M + 255) / 256, P);
+  hipMemsetAsync(hyp_count, 0, (size_t)P * H * 4, st);
+  hipMemsetAsync(s.cnt, 0, (size_t)P * (R + 1) * 4, st);
+  launch_score(s.cs, s.cq, counts, P, M, hyp_T, hyp_valid, H, thr2, hyp_count, st);
+  hipLaunchKernelGGL(ransac_pick_kernel, dim3(P), dim3(256), 0, st, hyp_T, hyp_valid, hyp_count, H, T_init, s.Tcand, P, s.cnt, s.info);
+  for (int r = 0; r < R; ++r) {
+    float* Tr = s.Tcand + (size_t)r * P * 12;
+    float* Tn = s.Tcand + (size_t)(r + 1) * P * 12;
+    hipLaunchKernelGGL(ransac_weights_kernel, gm, dim3(256), 0, st, s.cs, s.cq, counts, M, Tr, thr2, s.w);
+    KabschArgs k{};
+    k.src = s.cs; k.ref = s.cq; k.idx = nullptr; k.w = s.w; k.src_stride = (int64_t)M * 3; k.ref_stride = (int64_t)M * 3;
+    k.sigmoid = 0; k.pairs = P; k.m = M; k.T = Tn; k.invalid = nullptr;
+    k.skip = s.info + 3 * P;   // a pair without a valid hypothesis: identity step, and its recount is gated by `found`
+    launch_kabsch(k, st);
+    launch_score(s.cs, s.cq, counts, P, M, Tn, s.info + 2 * P, 1, thr2, s.cnt + (size_t)(r + 1) * P, st);
+  }
+  hipLaunchKernelGGL(ransac_finish_kernel, dim3(P), dim3(256), 0, st, s.cs, s.cq, counts, M, P, R, s.Tcand, s.cnt, s.info, thr2, T_out,
+                     stats);
+}
+
 // P (M 28 + H 56) bytes for the matched points, weights and hypotheses, plus a few hundred bytes per pair of round state
 size_t ransac_scratch_bytes(int pairs, int M, int H, int refine_iters) {
   const size_t P = (size_t)pairs;
-  return 2 * al256(P * M * 12) + al256(P * M * 4) + al256(P * H * 48) + 2 * al256(P * H * 4) +
-         al256(P * (refine_iters + 1) * 48) + al256(P * (refine_iters + 1) * 4) + al256(P * 16);
+  return pose_scratch_bytes(pairs, M, refine_iters) + al256(P * H * 48) + 2 * al256(P * H * 4);
 }
 
 void launch_ransac(const RansacArgs& a, void* scratch, hipStream_t st) {
   const int P = a.pairs, M = a.M, H = a.hypotheses, R = a.refine_iters;
   char* p = reinterpret_cast<char*>(scratch);
   auto take = [&](size_t bytes) { char* r = p; p += al256(bytes); return r; };
-  float* cs = reinterpret_cast<float*>(take((size_t)P * M * 12));
-  float* cq = reinterpret_cast<float*>(take((size_t)P * M * 12));
-  float* w = reinterpret_cast<float*>(take((size_t)P * M * 4));
+  const PoseScratch s = pose_scratch_take(p, P, M, R);
   float* hyp_T = reinterpret_cast<float*>(take((size_t)P * H * 48));
   int32_t* hyp_valid = reinterpret_cast<int32_t*>(take((size_t)P * H * 4));
   int32_t* hyp_count = reinterpret_cast<int32_t*>(take((size_t)P * H * 4));
-  float* Tcand = reinterpret_cast<float*>(take((size_t)P * (R + 1) * 48));
-  int32_t* cnt = reinterpret_cast<int32_t*>(take((size_t)P * (R + 1) * 4));
-  int32_t* info = reinterpret_cast<int32_t*>(take((size_t)P * 16));
   const float thr2 = a.max_dist * a.max_dist;   // fp32 product (the build keeps contraction off)
 
-  hipMemsetAsync(a.invalid, 0, (size_t)P * 4, st);
-  hipMemsetAsync(hyp_count, 0, (size_t)P * H * 4, st);
-  hipMemsetAsync(cnt, 0, (size_t)P * (R + 1) * 4, st);
-  const dim3 gm((M + 255) / 256, P);
-  hipLaunchKernelGGL(ransac_gather_kernel, gm, dim3(256), 0, st, a.src, a.ref, a.J, a.K, a.stride, a.corr, a.counts, M, cs, cq, a.invalid);
-  hipLaunchKernelGGL(ransac_hyp_kernel, dim3((H + HB - 1) / HB, P), dim3(HB), 0, st, cs, cq, a.counts, M, H, a.n, a.seed, thr2, a.edge_sim,
-                     hyp_T, hyp_valid, a.diag_sample);
-  launch_score(cs, cq, a.counts, P, M, hyp_T, hyp_valid, H, thr2, hyp_count, st);
-  hipLaunchKernelGGL(ransac_pick_kernel, dim3(P), dim3(256), 0, st, hyp_T, hyp_valid, hyp_count, H, a.T_init, Tcand, P, cnt, info);
-  for (int r = 0; r < R; ++r) {
-    float* Tr = Tcand + (size_t)r * P * 12;
-    float* Tn = Tcand + (size_t)(r + 1) * P * 12;
-    hipLaunchKernelGGL(ransac_weights_kernel, gm, dim3(256), 0, st, cs, cq, a.counts, M, Tr, thr2, w);
-    KabschArgs k{};
-    k.src = cs; k.ref = cq; k.idx = nullptr; k.w = w; k.src_stride = (int64_t)M * 3; k.ref_stride = (int64_t)M * 3;
-    k.sigmoid = 0; k.pairs = P; k.m = M; k.T = Tn; k.invalid = nullptr;
-    k.skip = info + 3 * P;   // a pair without a valid hypothesis: identity step, and its recount is gated by `found`
-    launch_kabsch(k, st);
-    launch_score(cs, cq, a.counts, P, M, Tn, info + 2 * P, 1, thr2, cnt + (size_t)(r + 1) * P, st);
-  }
-  hipLaunchKernelGGL(ransac_finish_kernel, dim3(P), dim3(256), 0, st, cs, cq, a.counts, M, P, R, Tcand, cnt, info, thr2, a.T_out, a.stats);
+  launch_ransac_gather(a.src, a.ref, P, a.J, a.K, a.stride, a.corr, a.counts, M, s, a.invalid, st);
+  hipLaunchKernelGGL(ransac_hyp_kernel, dim3((H + HB - 1) / HB, P), dim3(HB), 0, st, s.cs, s.cq, a.counts, M, H, a.n, a.seed, thr2,
+                     a.edge_sim, hyp_T, hyp_valid, a.diag_sample);
+  launch_ransac_tail(s, a.counts, P, M, hyp_T, hyp_valid, hyp_count, H, R, thr2, a.T_init, a.T_out, a.stats, st);
   if (a.diag_T) hipMemcpyAsync(a.diag_T, hyp_T, (size_t)P * H * 48, hipMemcpyDeviceToDevice, st);
   if (a.diag_valid) hipMemcpyAsync(a.diag_valid, hyp_valid, (size_t)P * H * 4, hipMemcpyDeviceToDevice, st);
   if (a.diag_count) hipMemcpyAsync(a.diag_count, hyp_count, (size_t)P * H * 4, hipMemcpyDeviceToDevice, st);

@@ -657,6 +657,52 @@ class Engine:
         self.sync()
         return (T, stats, invalid, d) if diag else (T, stats, invalid)
 
+    CONSENSUS_MAX_SEEDS = 256          # DSIR_CONSENSUS_MAX_SEEDS
+    CONSENSUS_MAX_MEMBERS = 128        # DSIR_CONSENSUS_MAX_MEMBERS
+    CONSENSUS_MAX_M = 24576            # DSIR_CONSENSUS_MAX_M
+
+    def consensus_correspondence(self, points_src, points_ref, corr, max_dist: float, counts=None, compat_dist=None, seeds: int = 64,
+                                 members: int = 32, refine_iters: int = 2, T_init=None, diag: bool = False):
+        """Spatial-consensus pose for P pairs: the deterministic alternative to ransac_correspondence for correspondence sets that are
+        mostly wrong (parity unpinned, the rule is stated in csrc/consensus.hip and restated in deepsir_amd/consensus.py).
+        Arguments and results as ransac_correspondence; compat_dist None / <= 0: max_dist.
+        -> (T [P,3,4], stats [P,5] f64: fitness, inlier_rmse, winning seed rank or -1, valid seeds, inliers; invalid [P] i32) and, with
+        diag=True, a dict of bits [P,M,W] i64 (the words of the compatibility matrix), score [P,M] i32, seed [P,seeds],
+        seed_members [P,seeds,members], seed_T [P,seeds,3,4], seed_valid [P,seeds], seed_count [P,seeds]."""
+        points_src, points_ref = _chk(points_src, torch.float32, "points_src"), _chk(points_ref, torch.float32, "points_ref")
+        corr = _chk(corr, torch.int32, "corr")
+        P, J, stride = points_src.shape
+        K, M = points_ref.shape[1], corr.shape[1]
+        if points_ref.shape[0] != P or points_ref.shape[2] != stride or tuple(corr.shape) != (P, M, 2):
+            raise EngineError("consensus_correspondence: points_* must be [P,N,stride] and corr [P,M,2]")
+        if counts is not None:
+            counts = _chk(counts, torch.int32, "counts")
+            if tuple(counts.shape) != (P,):
+                raise EngineError("consensus_correspondence: counts must be [P]")
+        if T_init is not None:
+            T_init = _chk(T_init, torch.float32, "T_init")
+            if tuple(T_init.shape) != (P, 3, 4):
+                raise EngineError("consensus_correspondence: T_init must be [P,3,4]")
+        T = self._empty((P, 3, 4))
+        stats = self._empty((P, 5), torch.float64)
+        invalid = self._empty((P,), torch.int32)
+        d, dref = None, None
+        if diag:
+            Hn, Mn, W = min(max(int(seeds), 1), self.CONSENSUS_MAX_SEEDS), min(max(int(members), 1), self.CONSENSUS_MAX_MEMBERS), (M + 63) // 64
+            d = {"bits": self._empty((P, M, W), torch.int64), "score": self._empty((P, M), torch.int32),
+                 "seed": self._empty((P, Hn), torch.int32), "seed_members": self._empty((P, Hn, Mn), torch.int32),
+                 "seed_T": self._empty((P, Hn, 3, 4)), "seed_valid": self._empty((P, Hn), torch.int32),
+                 "seed_count": self._empty((P, Hn), torch.int32)}
+            dref = C.byref(_lib.dsir_consensus_diag(*[_ptr(d[k]) for k in ("bits", "score", "seed", "seed_members", "seed_T", "seed_valid",
+                                                                            "seed_count")]))
+        self._pre()
+        self._call(self.lib.dsir_consensus_correspondence(self.h, _ptr(points_src), _ptr(points_ref), P, J, K, stride, _ptr(corr),
+                                                          _ptr(counts), M, float(max_dist), float(compat_dist or 0.0), int(seeds),
+                                                          int(members), int(refine_iters), _ptr(T_init), _ptr(T), _ptr(stats),
+                                                          _ptr(invalid), dref))
+        self.sync()
+        return (T, stats, invalid, d) if diag else (T, stats, invalid)
+
     def feature_correspondences(self, desc_src, desc_ref, mutual: bool = True):
         """The correspondence set of open3d's registration_ransac_based_on_feature_matching (reference network/DGR.py:7-24),
         made explicit: exact descriptor arg-min src -> ref (nn_match), kept where the ref -> src arg-min points back (mutual),

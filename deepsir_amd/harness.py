@@ -34,6 +34,7 @@ def inference_align(pairs: Sequence[Dict[str, np.ndarray]], model, num_reg_iter:
     time is then the shard's wall time divided by its size).
     ``pose_opt='icp'`` / ``'icp_plane'``: ICP on the raw clouds from the last pose, point-to-point / point-to-plane.
     ``pose_opt='ransac'``: DGR's safeguard (network/DGR.py:249-306) over the last iteration's correspondences, see below;
+    ``pose_opt='consensus'``: the same correspondences through ``consensus_correspondence`` instead of the seeded sampling;
     ``safeguard_wsum``: only pairs whose summed sigmoid inlier weight is below it take the RANSAC pose (DGR.py:273-304).
     Returns (pred_transforms_all [n_pairs, n_iter+1, 3, 4], stats [n_pairs, 5]) gathered over ranks."""
     device = device or torch.device("cuda", torch.cuda.current_device())
@@ -101,7 +102,7 @@ def inference_align(pairs: Sequence[Dict[str, np.ndarray]], model, num_reg_iter:
                                                    transforms[-1].contiguous(), weights=endpoints["perm_matrices"][-1],
                                                    weights_are_logits=True, quantization_size=2.0 * voxel_size)
             transforms.append(T_opt)
-        elif pose_opt == "ransac":
+        elif pose_opt in ("ransac", "consensus"):
             # DGR.safeguard_registration (network/DGR.py:249-306): RANSAC over the last iteration's correspondences (row i of pt_src
             # with row i of pt_ref_new), threshold 2 x voxel size, DGR's 80 000 hypotheses by default; with safeguard_wsum only the
             # pairs whose inlier network assigned less total weight than that take it, the others keep the network's pose
@@ -109,8 +110,11 @@ def inference_align(pairs: Sequence[Dict[str, np.ndarray]], model, num_reg_iter:
             m = xs.shape[1]
             corr = torch.arange(m, dtype=torch.int32, device=xs.device)[None, :, None].expand(xs.shape[0], m, 2).contiguous()
             T_net = transforms[-1].contiguous()
-            T_opt, _, _ = _aux_engine(model, data).ransac_correspondence(xs, xr, corr, 2.0 * voxel_size, hypotheses=ransac_hypotheses,
-                                                                         seed=ransac_seed, T_init=T_net)
+            if pose_opt == "ransac":
+                T_opt, _, _ = _aux_engine(model, data).ransac_correspondence(xs, xr, corr, 2.0 * voxel_size, hypotheses=ransac_hypotheses,
+                                                                             seed=ransac_seed, T_init=T_net)
+            else:             # the same correspondences through the spatial-consensus stage (csrc/consensus.hip): no sampling, no seed
+                T_opt, _, _ = _aux_engine(model, data).consensus_correspondence(xs, xr, corr, 2.0 * voxel_size, T_init=T_net)
             if safeguard_wsum is not None:
                 wsum = torch.sigmoid(endpoints["perm_matrices"][-1].float()).reshape(xs.shape[0], -1).sum(1)
                 T_opt = torch.where((wsum < safeguard_wsum)[:, None, None], T_opt, T_net)
@@ -118,7 +122,7 @@ def inference_align(pairs: Sequence[Dict[str, np.ndarray]], model, num_reg_iter:
         elif pose_opt is None:
             transforms.append(transforms[-1].detach())        # pose_optimization == identity (test.py:215-216, :406-408)
         else:
-            raise ValueError("pose_opt must be None, 'icp', 'icp_plane', 'tune' or 'ransac'")
+            raise ValueError("pose_opt must be None, 'icp', 'icp_plane', 'tune', 'ransac' or 'consensus'")
         T = torch.stack(transforms, dim=1).cpu().numpy()      # [B, n_iter+1, 3, 4]
         preds.append(T)
         gt = data["transform_gt"].cpu().numpy()
@@ -309,13 +313,26 @@ def inference_feat(pairs: Sequence[Dict[str, np.ndarray]], model, batch: int = 1
     return out, total
 
 
+def _pose_from_corr(eng, pose, xs, xr, corr, counts, max_dist, ransac_n, edge_sim, hypotheses, refine_iters, seed, seeds, members):
+    """The pose stage of ``register_feat`` / ``register_fpfh``: 'ransac' (seeded sampling) or 'consensus' (spatial compatibility)."""
+    if pose == "ransac":
+        return eng.ransac_correspondence(xs, xr, corr, max_dist, counts=counts, ransac_n=ransac_n, edge_sim=edge_sim,
+                                         hypotheses=hypotheses, refine_iters=refine_iters, seed=seed)[0]
+    if pose == "consensus":
+        return eng.consensus_correspondence(xs, xr, corr, max_dist, counts=counts, seeds=seeds, members=members,
+                                            refine_iters=refine_iters)[0]
+    raise ValueError("pose must be 'ransac' or 'consensus'")
+
+
 @torch.no_grad()
 def register_feat(pairs: Sequence[Dict[str, np.ndarray]], model, voxel_size: float = 0.3, hypotheses: int = 8192, mutual: bool = True,
                   num_reg: int = 1, dataset_type: str = "3DMatch", batch: int = 1, device: Optional[torch.device] = None,
-                  ransac_n: int = 3, edge_sim: float = 0.9, refine_iters: int = 2, seed: int = 0):
+                  ransac_n: int = 3, edge_sim: float = 0.9, refine_iters: int = 2, seed: int = 0, pose: str = "ransac",
+                  seeds: int = 64, members: int = 32):
     """The 'feat' pipeline as a registration (what the reference reaches through open3d's
     registration_ransac_based_on_feature_matching, network/DGR.py:7-24, test.py:259-263): forward_pair -> key points and
     descriptors -> (mutual) nearest-neighbour correspondences -> RANSAC pose (threshold 2 x voxel size), all on the device.
+    ``pose='consensus'``: the pose from ``consensus_correspondence`` (``seeds``, ``members``; no sampling, no seed) instead.
     Returns (pred_transforms [n_pairs, num_reg, 3, 4] - the one pose repeated ``num_reg`` times, so that the result has
     ``inference_align``'s layout and ``evaluate_align`` works on it -, stats [n_pairs, 5] rows ``[succ, rte, rre, time, seq]``)."""
     device = device or torch.device("cuda", torch.cuda.current_device())
@@ -329,8 +346,8 @@ def register_feat(pairs: Sequence[Dict[str, np.ndarray]], model, voxel_size: flo
         xs, xr = ep["pt_src"].permute(0, 2, 1).contiguous(), ep["pt_ref"].permute(0, 2, 1).contiguous()
         corr, counts = eng.feature_correspondences(ep["feat_src"].permute(0, 2, 1).contiguous(), ep["feat_ref"].permute(0, 2, 1).contiguous(),
                                                    mutual=mutual)
-        T, _, _ = eng.ransac_correspondence(xs, xr, corr, 2.0 * voxel_size, counts=counts, ransac_n=ransac_n, edge_sim=edge_sim,
-                                            hypotheses=hypotheses, refine_iters=refine_iters, seed=seed)
+        T = _pose_from_corr(eng, pose, xs, xr, corr, counts, 2.0 * voxel_size, ransac_n, edge_sim, hypotheses, refine_iters, seed, seeds,
+                            members)
         torch.cuda.synchronize(device)
         dt = (time.time() - t0) / len(ids)
         T = T.cpu().numpy()
@@ -365,13 +382,13 @@ def _fpfh_side(engine, pts, viewpoints, radius):
 def register_fpfh(pairs: Sequence[Dict[str, np.ndarray]], engine, voxel_size: float = 0.3, radius: Optional[float] = None,
                   hypotheses: int = 8192, mutual: bool = True, num_reg: int = 1, dataset_type: str = "3DMatch", batch: int = 1,
                   device: Optional[torch.device] = None, ransac_n: int = 3, edge_sim: float = 0.9, refine_iters: int = 2, seed: int = 0,
-                  want_corr: bool = False):
+                  want_corr: bool = False, pose: str = "ransac", seeds: int = 64, members: int = 32):
     """The weight-independent baseline of ``register_feat``: FPFH + feature-matching RANSAC (open3d compute_fpfh_feature ->
     registration_ransac_based_on_feature_matching; parity unpinned, the rules are the engine's own), all on the device.  Per batch
     and side: ``knn_pyramid`` -> ``estimate_normals`` on its level-0 lists (towards the pair's optional ``viewpoint_src`` /
     ``viewpoint_ref`` entry, 3 floats; default the origin) -> ``fpfh`` over those 16-NN lists, or with ``radius`` set over the CSR of
     ``radius_matches(x, x, identity, radius)`` -> ``feature_correspondences(mutual)`` -> ``ransac_correspondence`` (threshold
-    2 x voxel size).  Returns what ``register_feat`` returns - (pred_transforms [n_pairs, num_reg, 3, 4], stats [n_pairs, 5] rows
+    2 x voxel size), or with ``pose='consensus'`` -> ``consensus_correspondence`` (``seeds``, ``members``).  Returns what ``register_feat`` returns - (pred_transforms [n_pairs, num_reg, 3, 4], stats [n_pairs, 5] rows
     ``[succ, rte, rre, time, seq]``) - so ``evaluate_align`` and ``Engine.icp_refine`` take it the same way; with ``want_corr`` a
     third value, per pair the (corr [count, 2], flags_src [J], flags_ref [K]) numpy arrays.
 
@@ -395,8 +412,8 @@ def register_fpfh(pairs: Sequence[Dict[str, np.ndarray]], engine, voxel_size: fl
         ds, fs, _ = _fpfh_side(engine, xs, [view(i, "src") for i in ids], radius)
         dr, fr, _ = _fpfh_side(engine, xr, [view(i, "ref") for i in ids], radius)
         corr, counts = engine.feature_correspondences(ds, dr, mutual=mutual)
-        T, _, _ = engine.ransac_correspondence(xs, xr, corr, 2.0 * voxel_size, counts=counts, ransac_n=ransac_n, edge_sim=edge_sim,
-                                               hypotheses=hypotheses, refine_iters=refine_iters, seed=seed)
+        T = _pose_from_corr(engine, pose, xs, xr, corr, counts, 2.0 * voxel_size, ransac_n, edge_sim, hypotheses, refine_iters, seed,
+                            seeds, members)
         torch.cuda.synchronize(device)
         dt = (time.time() - t0) / len(ids)
         T = T.cpu().numpy()

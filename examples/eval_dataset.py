@@ -34,11 +34,13 @@ def main():
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--limit", type=int, default=0)
-    ap.add_argument("--pose-opt", choices=["none", "icp", "icp_plane", "tune", "ransac"], default="none")
+    ap.add_argument("--pose-opt", choices=["none", "icp", "icp_plane", "tune", "ransac", "consensus"], default="none")
     ap.add_argument("--pipeline", choices=["align", "feat"], default="align")
     ap.add_argument("--ransac", action="store_true", help="with --pipeline feat: descriptors -> mutual nearest neighbours -> RANSAC pose")
     ap.add_argument("--num-sub", type=int, default=1024, help="key points per cloud of the feat pipeline")
     ap.add_argument("--hypotheses", type=int, default=8192)
+    ap.add_argument("--pose", choices=["ransac", "consensus"], default="ransac",
+                    help="pose stage of --method fpfh and --pipeline feat: seeded RANSAC or the spatial-consensus stage (no sampling)")
     ap.add_argument("--method", choices=["network", "fpfh"], default="network", help="fpfh: FPFH + RANSAC instead of the network")
     ap.add_argument("--fpfh-radius", type=float, default=None, help="with --method fpfh: radius lists instead of the 16-NN lists")
     a = ap.parse_args()
@@ -66,9 +68,10 @@ def main():
     pairs = [D.as_batch(ds[i]) for i in range(n)]
     if a.method == "fpfh":
         pred, stats = register_fpfh(pairs, eng, voxel_size=voxel, radius=a.fpfh_radius, hypotheses=a.hypotheses, dataset_type=a.dataset,
-                                    batch=a.batch)
+                                    batch=a.batch, pose=a.pose)
     elif feat:
-        pred, stats = register_feat(pairs, model, voxel_size=voxel, hypotheses=a.hypotheses, dataset_type=a.dataset, batch=a.batch)
+        pred, stats = register_feat(pairs, model, voxel_size=voxel, hypotheses=a.hypotheses, dataset_type=a.dataset, batch=a.batch,
+                                    pose=a.pose)
     else:
         pred, stats = inference_align(pairs, model, a.iters, a.dataset, batch=a.batch,
                                       pose_opt=None if a.pose_opt == "none" else a.pose_opt, voxel_size=voxel)

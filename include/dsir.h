@@ -382,6 +382,38 @@ int dsir_ransac_correspondence(dsir_ctx* ctx, const float* points_src, const flo
                                float edge_sim, int hypotheses, int refine_iters, uint64_t seed, const float* T_init, float* T_out,
                                double* stats, int32_t* invalid, const dsir_ransac_diag* diag /* NULL in production */);
 
+/* Spatial-consensus pose from correspondences: the deterministic alternative to dsir_ransac_correspondence for correspondence sets
+ * that are mostly wrong (hand-crafted descriptors: 90 % outliers and more), after the second-order spatial compatibility of SC2-PCR.
+ * Neither the reference nor open3d has the stage: parity is UNPINNED, the engine owns the rule, stated once in the header of
+ * deepsir_amd/csrc/consensus.hip (and DESIGN.md section 8) and restated on the host in deepsir_amd/consensus.py.
+ * Same boundary as dsir_ransac_correspondence: points_src, points_ref, corr, counts, M, max_dist, T_init in; T_out, invalid and
+ * stats [P][5] float64 {fitness, inlier RMSE, winning seed rank or -1, valid seeds, inliers} out; P pairs at once, no host round
+ * trip, pairs independent bit for bit, two runs write the same bytes.  No seed and no random number anywhere.
+ * compat_dist: two matches are compatible when the lengths |s_i - s_j| and |q_i - q_j| differ by less than it (<= 0: max_dist);
+ * seeds in [1, DSIR_CONSENSUS_MAX_SEEDS] (default use: 64): candidate poses, from the rows of the largest second-order score;
+ * members in [3, DSIR_CONSENSUS_MAX_MEMBERS] (default use: 32): rows each seed's pose is fitted to;
+ * refine_iters in [0, DSIR_RANSAC_MAX_REFINE]: as for RANSAC.
+ * M <= DSIR_CONSENSUS_MAX_M (the scores are int32: M^2 < 2^31; a row of second-order counts is held in LDS as uint16) and
+ * M, J, K <= max_points.  The workspace holds the compatibility bit matrix, P x M x ceil(M / 64) x 8 bytes (M = 5000: 3.2 MB a pair),
+ * plus P x (M x 48 + seeds x 56)-order scratch; a call that does not fit is refused, naming the needed and the available bytes. */
+#define DSIR_CONSENSUS_MAX_SEEDS 256
+#define DSIR_CONSENSUS_MAX_MEMBERS 128
+#define DSIR_CONSENSUS_MAX_M 24576
+/* test / measurement outputs of dsir_consensus_correspondence (all optional, device memory), W = ceil(M / 64) */
+typedef struct dsir_consensus_diag {
+  uint64_t* bits;        /* [P][M][W]: bit j % 64 of word j / 64 of row i is C[i][j] */
+  int32_t* score;        /* [P][M] */
+  int32_t* seed;         /* [P][seeds]: the row of seed rank r, or -1 */
+  int32_t* seed_members; /* [P][seeds][members]: ascending rows, -1 padded */
+  float* seed_T;         /* [P][seeds][12]: zeros for an invalid seed */
+  int32_t* seed_valid;   /* [P][seeds] */
+  int32_t* seed_count;   /* [P][seeds]: inliers of seed_T under max_dist */
+} dsir_consensus_diag;
+int dsir_consensus_correspondence(dsir_ctx* ctx, const float* points_src, const float* points_ref, int pairs, int J, int K,
+                                  int stride, const int32_t* corr, const int32_t* counts, int M, float max_dist, float compat_dist,
+                                  int seeds, int members, int refine_iters, const float* T_init, float* T_out, double* stats,
+                                  int32_t* invalid, const dsir_consensus_diag* diag /* NULL in production */);
+
 /* The correspondence set open3d's registration_ransac_based_on_feature_matching (network/DGR.py:7-24; called at test.py:259-263)
  * draws from, made explicit (parity unpinned, as above): the exact descriptor arg-min of dsir_nn_match src -> ref, with mutual != 0
  * kept only where the ref -> src arg-min points back; survivors in ascending src index.  desc_src [P][J][64], desc_ref [P][K][64]
