@@ -240,6 +240,11 @@ SYMBOLS = {
     "dsir_t_nn_within_scratch": (C.c_size_t, [C.c_int64]),
     "dsir_t_nn_within": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_float, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p]),
+    # top-k descriptor search and the correspondences built on it (csrc/nn_topk.hip)
+    "dsir_nn_match_topk": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "dsir_nn_match_topk_splits": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "dsir_feature_correspondences_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                  C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

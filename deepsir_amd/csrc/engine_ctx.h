@@ -283,6 +283,12 @@ struct DescSearch {
     bool want_stats = false;               // fill `stats`
   };
   int run(const float* desc_s, const float* desc_r, int32_t* idx_out, const Iter& i);
+  // the k nearest per row with distances (nn_topk.hip), exhaustive mode only: bytes alloc_topk takes from the arena, the
+  // allocation (the caller checks ws.overflow, or compares topk_bytes against the arena first), the run
+  void* topk_scratch = nullptr;
+  size_t topk_bytes(int k) const { return nn_topk_scratch_bytes(P, J, K, k); }
+  void alloc_topk(int k) { topk_scratch = c->ws.raw(topk_bytes(k)); }
+  int run_topk(const float* desc_s, const float* desc_r, int k, int32_t* idx_out, float* dist_out);
 };
 constexpr size_t kMatchSlots = 4096;
 

@@ -577,4 +577,16 @@ int launch_resample(const float* in, const int32_t* counts, int clouds, int cap,
 void launch_eval_metrics(const float* pred, int64_t pred_stride, const float* gt, const float* src, const float* ref,
                          int pairs, int n, int stride, float rte_thresh, float rre_thresh, double* out, hipStream_t st);
 
+// nn_topk.hip — the k nearest ref descriptors of every src descriptor (the rule is stated in the file's header), k in [1, 8]:
+// idx [pairs][J][k], dist [pairs][J][k] or nullptr; scratch of nn_topk_scratch_bytes(); nn_topk_splits: the column splits taken
+size_t nn_topk_scratch_bytes(int pairs, int J, int K, int k);
+int nn_topk_splits(int pairs, int J, int K, int k);
+void launch_nn_topk(const float* a, const float* b, int pairs, int J, int K, int k, int32_t* idx, float* dist, void* scratch,
+                    hipStream_t st);
+// correspondences from such lists: iab / dab [pairs][J][stride_ab] (src -> ref), iba [pairs][K][stride_ba] (ref -> src, mutual only;
+// nullptr: no mutual test); k candidates per row; r2 > 0: the ratio test on ranks 0 / 1 (k == 1, stride_ab >= 2);
+// corr [pairs][J k][2], counts [pairs], corr_dist [pairs][J k] or nullptr
+void launch_corr_topk_compact(const int32_t* iab, const float* dab, int stride_ab, const int32_t* iba, int stride_ba, int pairs, int J,
+                              int K, int mutual, int k, float r2, int32_t* corr, int32_t* counts, float* corr_dist, hipStream_t st);
+
 }  // namespace dsir

@@ -273,3 +273,93 @@ int dsir_match_timer2(dsir_ctx* c, int reset, double* op_ms, double* kernel_ms, 
 int dsir_match_timer(dsir_ctx* c, int reset, double* total_ms, int64_t* launches) { return dsir_match_timer2(c, reset, total_ms, nullptr, launches); }
 
 }  // extern "C"
+
+// =================================================================== top-k search (nn_topk.hip) and the correspondences built on it
+namespace dsir {
+
+int DescSearch::run_topk(const float* desc_s, const float* desc_r, int k, int32_t* idx_out, float* dist_out) {
+  if (mode != SearchMode::exhaustive || !topk_scratch) return fail(c, "top-k search: exhaustive mode with alloc_topk() only");
+  launch_nn_topk(desc_s, desc_r, P, J, K, k, idx_out, dist_out, topk_scratch, c->stream);
+  return 0;
+}
+
+namespace {
+
+inline size_t arena_pad(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// J, K and k of a top-k call against the context's limits
+int topk_check_shape(dsir_ctx* c, const char* who, int pairs, int J, int K, int k) {
+  if (pairs < 1 || J < 1 || K < 1) return fail(c, "%s: bad arguments", who);
+  if (k < 1 || k > DSIR_TOPK_MAX) return fail(c, "%s: k=%d outside [1, %d]", who, k, DSIR_TOPK_MAX);
+  if (J > c->cfg.max_points || K > c->cfg.max_points)
+    return fail(c, "%s: J=%d or K=%d beyond max_points=%d", who, J, K, c->cfg.max_points);
+  if ((int64_t)pairs * J * k > 0x7fffffffll || (int64_t)pairs * K * k > 0x7fffffffll)
+    return fail(c, "%s: pairs x points x k beyond 2^31", who);
+  return 0;
+}
+
+}  // namespace
+}  // namespace dsir
+
+extern "C" {
+
+int dsir_nn_match_topk(dsir_ctx* c, const float* a, const float* b, int pairs, int J, int K, int k, int32_t* idx, float* dist) {
+  if (!c) return 1;
+  if (!a || !b || !idx) return fail(c, "dsir_nn_match_topk: bad arguments");
+  if (int r = topk_check_shape(c, "dsir_nn_match_topk", pairs, J, K, k)) return r;
+  HIP_OK(c, hipSetDevice(c->device));
+  DescSearch s{c, SearchMode::exhaustive, pairs, J, K};
+  // the whole scratch, checked before the first launch
+  const size_t need = arena_pad(s.topk_bytes(k));
+  if (need > c->ws.cap)
+    return fail(c, "workspace too small for dsir_nn_match_topk: needs %zu bytes, the arena holds %zu (raise max_points / max_pairs, or pass "
+                   "fewer pairs)", need, c->ws.cap);
+  c->ws.top = 0; c->ws.overflow = false;
+  s.alloc_topk(k);
+  if (c->ws.overflow) return fail(c, "workspace exhausted in dsir_nn_match_topk");
+  if (int r = s.run_topk(a, b, k, idx, dist)) return r;
+  return post(c);
+}
+
+int dsir_nn_match_topk_splits(dsir_ctx* c, int pairs, int J, int K, int k) {
+  if (!c || pairs < 1 || J < 1 || K < 1 || k < 1 || k > DSIR_TOPK_MAX) return -1;
+  return nn_topk_splits(pairs, J, K, k);
+}
+
+int dsir_feature_correspondences_ex(dsir_ctx* c, const float* desc_src, const float* desc_ref, int pairs, int J, int K, int mutual,
+                                    int k, float ratio, int32_t* corr, int32_t* counts, float* corr_dist) {
+  if (!c) return 1;
+  if (!desc_src || !desc_ref || !corr || !counts) return fail(c, "dsir_feature_correspondences_ex: bad arguments");
+  if (int r = topk_check_shape(c, "dsir_feature_correspondences_ex", pairs, J, K, k)) return r;
+  if ((int64_t)J * k > c->cfg.max_points)
+    return fail(c, "dsir_feature_correspondences_ex: J x k = %lld beyond max_points=%d (the pose stages take M <= max_points)",
+                (long long)J * k, c->cfg.max_points);
+  if (ratio != ratio || ratio - ratio != 0.f || ratio >= 1.f)
+    return fail(c, "dsir_feature_correspondences_ex: ratio=%g must be finite and below 1 (<= 0: no test)", (double)ratio);
+  if (ratio > 0.f && k > 1)
+    return fail(c, "dsir_feature_correspondences_ex: the ratio test is defined on the 1-NN set (ratio=%g with k=%d)", (double)ratio, k);
+  // today's rule on today's launches
+  if (k == 1 && !(ratio > 0.f) && !corr_dist) return dsir_feature_correspondences(c, desc_src, desc_ref, pairs, J, K, mutual, corr, counts);
+  HIP_OK(c, hipSetDevice(c->device));
+  const int ks = ratio > 0.f ? 2 : k;                 // ranks searched src -> ref: the ratio test reads rank 1
+  const float r2 = ratio > 0.f ? ratio * ratio : 0.f;   // fp32, rounded once
+  DescSearch s_ab{c, SearchMode::exhaustive, pairs, J, K}, s_ba{c, SearchMode::exhaustive, pairs, K, J};
+  const size_t n_ab = (size_t)pairs * J * ks, n_ba = mutual ? (size_t)pairs * K * k : 0;
+  const size_t need = 2 * arena_pad(n_ab * 4) + arena_pad(n_ba * 4) + arena_pad(s_ab.topk_bytes(ks)) + (mutual ? arena_pad(s_ba.topk_bytes(k)) : 0);
+  if (need > c->ws.cap)
+    return fail(c, "workspace too small for dsir_feature_correspondences_ex: needs %zu bytes, the arena holds %zu (raise max_points / "
+                   "max_pairs, or pass fewer pairs)", need, c->ws.cap);
+  c->ws.top = 0; c->ws.overflow = false;
+  int32_t* iab = c->ws.get<int32_t>(n_ab);
+  float* dab = c->ws.get<float>(n_ab);
+  int32_t* iba = mutual ? c->ws.get<int32_t>(n_ba) : nullptr;
+  s_ab.alloc_topk(ks);
+  if (mutual) s_ba.alloc_topk(k);
+  if (c->ws.overflow) return fail(c, "workspace exhausted in dsir_feature_correspondences_ex");
+  if (int r = s_ab.run_topk(desc_src, desc_ref, ks, iab, dab)) return r;
+  if (mutual) if (int r = s_ba.run_topk(desc_ref, desc_src, k, iba, nullptr)) return r;
+  launch_corr_topk_compact(iab, dab, ks, iba, k, pairs, J, K, mutual ? 1 : 0, k, r2, corr, counts, corr_dist, c->stream);
+  return post(c);
+}
+
+}  // extern "C"

@@ -46,4 +46,26 @@ inline SearchOperandBytes search_operand_bytes(SearchMode m, int P, int J, int K
   return {(size_t)P * J * 64 * 2, (size_t)P * K * 64 * 2, (size_t)P * J * sizeof(float), (size_t)P * K * sizeof(float)};
 }
 
+// Geometry of the top-k search (nn_topk.hip) for lists of kk = 2, 4 or 8 keys per row.  Row tiles per wave: 2 (128-row blocks) once
+// that still leaves a workgroup per CU and the lists fit beside two sets of A fragments (kk <= 4), else 1.  Column splits: at least
+// two workgroups per CU (512 in all) where the problem allows it, every split 8 tiles of 64 columns or longer so that the A-fragment
+// preload and the 16-lane merge stay amortised, 16 splits at the most (the merge kernel reads them all per row).
+struct TopkPlan { int rt, rb_count, splits, cols_per_split; };
+inline TopkPlan nn_topk_plan(int P, int J, int K, int kk) {
+  TopkPlan p;
+  p.rt = (kk <= 4 && (int64_t)P * ((J + 127) / 128) >= 256) ? 2 : 1;
+  const int rows_per_block = 64 * p.rt;
+  p.rb_count = (J + rows_per_block - 1) / rows_per_block;
+  const int64_t base = (int64_t)P * p.rb_count;
+  const int tiles = (K + 63) / 64;
+  int64_t want = (512 + base - 1) / base;
+  if (want > tiles / 8) want = tiles / 8;
+  if (want > 16) want = 16;
+  if (want < 1) want = 1;
+  const int tiles_per = (tiles + (int)want - 1) / (int)want;
+  p.cols_per_split = tiles_per * 64;
+  p.splits = (tiles + tiles_per - 1) / tiles_per;
+  return p;
+}
+
 }  // namespace dsir

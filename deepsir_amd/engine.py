@@ -703,22 +703,56 @@ class Engine:
         self.sync()
         return (T, stats, invalid, d) if diag else (T, stats, invalid)
 
-    def feature_correspondences(self, desc_src, desc_ref, mutual: bool = True):
+    def feature_correspondences(self, desc_src, desc_ref, mutual: bool = True, k: int = 1, ratio: float = 0.0, with_dist: bool = False):
         """The correspondence set of open3d's registration_ransac_based_on_feature_matching (reference network/DGR.py:7-24),
         made explicit: exact descriptor arg-min src -> ref (nn_match), kept where the ref -> src arg-min points back (mutual),
-        in ascending src index.  desc_* [P,N,64] -> (corr [P,J,2] i32 with -1 beyond counts[p], counts [P] i32)."""
+        in ascending src index.  desc_* [P,N,64] -> (corr [P,J,2] i32 with -1 beyond counts[p], counts [P] i32).
+        k > 1: the k nearest ref descriptors of every src row as candidates (corr [P,J*k,2], ascending j then rank; mutual: j
+        among the k nearest of the candidate's column).  ratio in (0, 1): Lowe's ratio test on the 1-NN set (k must be 1).  with_dist:
+        also the kept distances [P,J*k] f32 (+inf beyond counts[p]).  The rule: include/dsir.h, dsir_feature_correspondences_ex."""
         desc_src, desc_ref = _chk(desc_src, torch.float32, "desc_src"), _chk(desc_ref, torch.float32, "desc_ref")
         P, J, c = desc_src.shape
         K = desc_ref.shape[1]
         if c != 64 or desc_ref.shape[0] != P or desc_ref.shape[2] != 64:
             raise EngineError("feature_correspondences: descriptors must be [P,N,64]")
-        corr = self._empty((P, J, 2), torch.int32)
+        k, ratio = int(k), float(ratio)
+        if k == 1 and ratio == 0.0 and not with_dist:
+            corr = self._empty((P, J, 2), torch.int32)
+            counts = self._empty((P,), torch.int32)
+            self._pre()
+            self._call(self.lib.dsir_feature_correspondences(self.h, _ptr(desc_src), _ptr(desc_ref), P, J, K, 1 if mutual else 0,
+                                                             _ptr(corr), _ptr(counts)))
+            self.sync()
+            return corr, counts
+        M = J * max(k, 1)
+        corr = self._empty((P, M, 2), torch.int32)
         counts = self._empty((P,), torch.int32)
+        dist = self._empty((P, M)) if with_dist else None
         self._pre()
-        self._call(self.lib.dsir_feature_correspondences(self.h, _ptr(desc_src), _ptr(desc_ref), P, J, K, 1 if mutual else 0,
-                                                         _ptr(corr), _ptr(counts)))
+        self._call(self.lib.dsir_feature_correspondences_ex(self.h, _ptr(desc_src), _ptr(desc_ref), P, J, K, 1 if mutual else 0, k, ratio,
+                                                            _ptr(corr), _ptr(counts), _ptr(dist)))
         self.sync()
-        return corr, counts
+        return (corr, counts, dist) if with_dist else (corr, counts)
+
+    def nn_match_topk(self, desc_src, desc_ref, k: int, with_dist: bool = True):
+        """The k nearest ref descriptors of every src descriptor, ascending by (fp32 distance, column); rank 0 is nn_match's result.
+        desc_* [P,N,64] -> (idx [P,J,k] i32, dist [P,J,k] f32 or None); ranks beyond K are -1 / +inf (include/dsir.h)."""
+        desc_src, desc_ref = _chk(desc_src, torch.float32, "desc_src"), _chk(desc_ref, torch.float32, "desc_ref")
+        P, J, c = desc_src.shape
+        K = desc_ref.shape[1]
+        if c != 64 or desc_ref.shape[0] != P or desc_ref.shape[2] != 64:
+            raise EngineError("nn_match_topk: descriptors must be [P,N,64]")
+        k = int(k)
+        idx = self._empty((P, J, max(k, 1)), torch.int32)
+        dist = self._empty((P, J, max(k, 1))) if with_dist else None
+        self._pre()
+        self._call(self.lib.dsir_nn_match_topk(self.h, _ptr(desc_src), _ptr(desc_ref), P, J, K, k, _ptr(idx), _ptr(dist)))
+        self.sync()
+        return idx, dist
+
+    def nn_match_topk_splits(self, pairs: int, J: int, K: int, k: int) -> int:
+        """Column splits the top-k launcher takes for this shape (host arithmetic)."""
+        return int(self.lib.dsir_nn_match_topk_splits(self.h, int(pairs), int(J), int(K), int(k)))
 
     def pose_finetune(self, xyz_src, xyz_ref, T_init, weights=None, weights_are_logits: bool = False,
                       quantization_size: float = 1.0, max_iter: int = 1000, break_threshold_ratio: float = 1e-4,

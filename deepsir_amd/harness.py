@@ -328,11 +328,13 @@ def _pose_from_corr(eng, pose, xs, xr, corr, counts, max_dist, ransac_n, edge_si
 def register_feat(pairs: Sequence[Dict[str, np.ndarray]], model, voxel_size: float = 0.3, hypotheses: int = 8192, mutual: bool = True,
                   num_reg: int = 1, dataset_type: str = "3DMatch", batch: int = 1, device: Optional[torch.device] = None,
                   ransac_n: int = 3, edge_sim: float = 0.9, refine_iters: int = 2, seed: int = 0, pose: str = "ransac",
-                  seeds: int = 64, members: int = 32):
+                  seeds: int = 64, members: int = 32, match_k: int = 1, match_ratio: float = 0.0):
     """The 'feat' pipeline as a registration (what the reference reaches through open3d's
     registration_ransac_based_on_feature_matching, network/DGR.py:7-24, test.py:259-263): forward_pair -> key points and
     descriptors -> (mutual) nearest-neighbour correspondences -> RANSAC pose (threshold 2 x voxel size), all on the device.
     ``pose='consensus'``: the pose from ``consensus_correspondence`` (``seeds``, ``members``; no sampling, no seed) instead.
+    ``match_k`` > 1: the k nearest descriptors of every src point as candidates (M = J x match_k rows for the pose stage);
+    ``match_ratio`` in (0, 1): Lowe's ratio test on the 1-NN set (``Engine.feature_correspondences``).
     Returns (pred_transforms [n_pairs, num_reg, 3, 4] - the one pose repeated ``num_reg`` times, so that the result has
     ``inference_align``'s layout and ``evaluate_align`` works on it -, stats [n_pairs, 5] rows ``[succ, rte, rre, time, seq]``)."""
     device = device or torch.device("cuda", torch.cuda.current_device())
@@ -345,7 +347,7 @@ def register_feat(pairs: Sequence[Dict[str, np.ndarray]], model, voxel_size: flo
         eng = _aux_engine(model, data)
         xs, xr = ep["pt_src"].permute(0, 2, 1).contiguous(), ep["pt_ref"].permute(0, 2, 1).contiguous()
         corr, counts = eng.feature_correspondences(ep["feat_src"].permute(0, 2, 1).contiguous(), ep["feat_ref"].permute(0, 2, 1).contiguous(),
-                                                   mutual=mutual)
+                                                   mutual=mutual, k=match_k, ratio=match_ratio)
         T = _pose_from_corr(eng, pose, xs, xr, corr, counts, 2.0 * voxel_size, ransac_n, edge_sim, hypotheses, refine_iters, seed, seeds,
                             members)
         torch.cuda.synchronize(device)
@@ -382,7 +384,8 @@ def _fpfh_side(engine, pts, viewpoints, radius):
 def register_fpfh(pairs: Sequence[Dict[str, np.ndarray]], engine, voxel_size: float = 0.3, radius: Optional[float] = None,
                   hypotheses: int = 8192, mutual: bool = True, num_reg: int = 1, dataset_type: str = "3DMatch", batch: int = 1,
                   device: Optional[torch.device] = None, ransac_n: int = 3, edge_sim: float = 0.9, refine_iters: int = 2, seed: int = 0,
-                  want_corr: bool = False, pose: str = "ransac", seeds: int = 64, members: int = 32):
+                  want_corr: bool = False, pose: str = "ransac", seeds: int = 64, members: int = 32, match_k: int = 1,
+                  match_ratio: float = 0.0):
     """The weight-independent baseline of ``register_feat``: FPFH + feature-matching RANSAC (open3d compute_fpfh_feature ->
     registration_ransac_based_on_feature_matching; parity unpinned, the rules are the engine's own), all on the device.  Per batch
     and side: ``knn_pyramid`` -> ``estimate_normals`` on its level-0 lists (towards the pair's optional ``viewpoint_src`` /
@@ -390,7 +393,8 @@ def register_fpfh(pairs: Sequence[Dict[str, np.ndarray]], engine, voxel_size: fl
     ``radius_matches(x, x, identity, radius)`` -> ``feature_correspondences(mutual)`` -> ``ransac_correspondence`` (threshold
     2 x voxel size), or with ``pose='consensus'`` -> ``consensus_correspondence`` (``seeds``, ``members``).  Returns what ``register_feat`` returns - (pred_transforms [n_pairs, num_reg, 3, 4], stats [n_pairs, 5] rows
     ``[succ, rte, rre, time, seq]``) - so ``evaluate_align`` and ``Engine.icp_refine`` take it the same way; with ``want_corr`` a
-    third value, per pair the (corr [count, 2], flags_src [J], flags_ref [K]) numpy arrays.
+    third value, per pair the (corr [count, 2], flags_src [J], flags_ref [K]) numpy arrays.  ``match_k`` / ``match_ratio``: k candidate
+    matches per src point (M = J x match_k) or Lowe's ratio test, as in ``register_feat``.
 
     ``engine`` is a ``deepsir_amd.engine.Engine`` THE CALLER PREPARED: the descriptor itself needs no weights, but the pyramid and
     the other existing entries this calls refuse a context whose weights are not loaded (``check_ready``, csrc/engine_ctx.h), so
@@ -411,7 +415,7 @@ def register_fpfh(pairs: Sequence[Dict[str, np.ndarray]], engine, voxel_size: fl
         xs, xr = data["points_src"].float().contiguous(), data["points_ref"].float().contiguous()
         ds, fs, _ = _fpfh_side(engine, xs, [view(i, "src") for i in ids], radius)
         dr, fr, _ = _fpfh_side(engine, xr, [view(i, "ref") for i in ids], radius)
-        corr, counts = engine.feature_correspondences(ds, dr, mutual=mutual)
+        corr, counts = engine.feature_correspondences(ds, dr, mutual=mutual, k=match_k, ratio=match_ratio)
         T = _pose_from_corr(engine, pose, xs, xr, corr, counts, 2.0 * voxel_size, ransac_n, edge_sim, hypotheses, refine_iters, seed,
                             seeds, members)
         torch.cuda.synchronize(device)

@@ -43,6 +43,10 @@ def main():
                     help="pose stage of --method fpfh and --pipeline feat: seeded RANSAC or the spatial-consensus stage (no sampling)")
     ap.add_argument("--method", choices=["network", "fpfh"], default="network", help="fpfh: FPFH + RANSAC instead of the network")
     ap.add_argument("--fpfh-radius", type=float, default=None, help="with --method fpfh: radius lists instead of the 16-NN lists")
+    ap.add_argument("--match-k", type=int, default=1,
+                    help="--method fpfh / --pipeline feat: the k nearest descriptors of every src point as candidate matches (1 .. 8)")
+    ap.add_argument("--match-ratio", type=float, default=0.0,
+                    help="--method fpfh / --pipeline feat: Lowe's ratio test on the 1-NN matches (0 < ratio < 1; 0 = off; needs --match-k 1)")
     a = ap.parse_args()
     kitti = a.dataset == "KITTI"
     cfg = NetConfig(feat_len=4 if kitti else 3)
@@ -58,7 +62,8 @@ def main():
     sd = torch.load(a.ckpt, map_location="cpu") if a.ckpt else to_torch_state_dict(generate_state_dict(cfg, 0))
     model.load_state_dict(sd["state_dict"] if "state_dict" in sd else sd)
     model = model.cuda().eval()
-    eng = model._ensure_engine(max(a.num_points, 1024), a.batch)   # the engine also runs the datasets' device steps
+    # the engine also runs the datasets' device steps; the pose stages take J x match_k <= max_points rows
+    eng = model._ensure_engine(max(a.num_points * (a.match_k if a.method == "fpfh" else 1), 1024), a.batch)
     oxford = a.dataset == "Oxford"
     voxel = a.voxel_size or (0.3 if kitti or oxford else 0.03)
     ds = (D.KittiOdometryTest(a.root, eng, voxel_size=voxel, feat_len=cfg.feat_len, num_points=a.num_points) if kitti
@@ -68,10 +73,10 @@ def main():
     pairs = [D.as_batch(ds[i]) for i in range(n)]
     if a.method == "fpfh":
         pred, stats = register_fpfh(pairs, eng, voxel_size=voxel, radius=a.fpfh_radius, hypotheses=a.hypotheses, dataset_type=a.dataset,
-                                    batch=a.batch, pose=a.pose)
+                                    batch=a.batch, pose=a.pose, match_k=a.match_k, match_ratio=a.match_ratio)
     elif feat:
         pred, stats = register_feat(pairs, model, voxel_size=voxel, hypotheses=a.hypotheses, dataset_type=a.dataset, batch=a.batch,
-                                    pose=a.pose)
+                                    pose=a.pose, match_k=a.match_k, match_ratio=a.match_ratio)
     else:
         pred, stats = inference_align(pairs, model, a.iters, a.dataset, batch=a.batch,
                                       pose_opt=None if a.pose_opt == "none" else a.pose_opt, voxel_size=voxel)

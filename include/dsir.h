@@ -579,6 +579,27 @@ int dsir_screen_bounds(dsir_ctx* ctx, const float* desc_src, const float* desc_r
                        int32_t* out_of_domain);
 int dsir_screen_cap(void);
 
+/* Top-k descriptor search (csrc/nn_topk.hip, whose header states the rule): a row's k smallest keys order_bits(d) << 32 | column in
+ * ascending order, d dsir_nn_match's fp32 distance - rank 0 IS dsir_nn_match's result, ties go to the lower column, nothing depends
+ * on the arrival order of workgroups.  A rank without an entry (k > K, non-finite distances) is index -1, distance +inf.  DEVICE
+ * pointers; bad arguments (k outside [1, DSIR_TOPK_MAX], J or K beyond max_points, a workspace that does not fit) are errors and
+ * leave the context usable. */
+#define DSIR_TOPK_MAX 8
+/* k nearest ref descriptors of every src descriptor: idx [P][J][k] i32, dist [P][J][k] f32 (dist may be NULL) */
+int dsir_nn_match_topk(dsir_ctx* ctx, const float* desc_src, const float* desc_ref, int pairs, int J, int K, int k,
+                       int32_t* idx, float* dist);
+/* host only: the column splits the launcher takes for this shape (tests use it to place K across a split boundary); -1: bad arguments */
+int dsir_nn_match_topk_splits(dsir_ctx* ctx, int pairs, int J, int K, int k);
+/* dsir_feature_correspondences with k candidates per src row or a ratio test: corr [P][J*k][2], counts [P],
+ * corr_dist [P][J*k] f32 or NULL.  k = 1, ratio = 0 gives dsir_feature_correspondences' bytes.
+ * Candidates: (j, c) for every rank < k of row j that has an entry; under `mutual` kept iff j is among the k nearest of column c in
+ * the ref -> src search; ascending j, then ascending rank; rows beyond counts[p] are -1 (corr_dist: +inf).
+ * Ratio test (Lowe): with r2 = fp32(ratio * ratio), row j keeps its rank-0 match iff rank 1 is missing or
+ * max(d0, 0) < r2 * max(d1, 0).  ratio <= 0: no test; ratio >= 1, a non-finite ratio, ratio > 0 with k > 1 (the test is defined on
+ * the 1-NN set) and J * k > max_points (the pose stages take M <= max_points) are refused. */
+int dsir_feature_correspondences_ex(dsir_ctx* ctx, const float* desc_src, const float* desc_ref, int pairs, int J, int K,
+                                    int mutual, int k, float ratio, int32_t* corr, int32_t* counts, float* corr_dist);
+
 #ifdef __cplusplus
 }
 #endif
