@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "engine_ctx.h"
+#include "icp_grid.h"
 
 using namespace dsir;
 
@@ -801,6 +802,53 @@ int dsir_icp_refine_ex(dsir_ctx* c, const float* points_src, const float* points
   launch_icp_refine_ex(points_src, points_ref, pairs, J, K, stride, max_corr_dist, max_iter, rel_fitness, rel_rmse, T_init, T_out,
                        nullptr, stats, estimator, normals, normals_ref ? (int64_t)K * 3 : (int64_t)K * stride, normals_ref ? 3 : stride,
                        scratch, c->stream);
+  return post(c);
+}
+
+// search 1 -> 2 (the grid without its query order) under the measurement switch DSIR_ICP_GRID_NO_ORDER: same bytes, other speed
+static int icp_search_mode(int search) { return search == 1 && tuning_flag("DSIR_ICP_GRID_NO_ORDER") ? 2 : search; }
+
+int dsir_icp_refine_ex2(dsir_ctx* c, const float* points_src, const float* points_ref, int pairs, int J, int K, int stride,
+                        float max_corr_dist, int max_iter, float rel_fitness, float rel_rmse, const float* T_init, float* T_out,
+                        int estimator, const float* normals_ref, int search, double* stats) {
+  if (!c) return 1;
+  if (!points_src || !points_ref || !T_init || !T_out || pairs < 1 || J < 1 || K < 1 || stride < 3 || max_iter < 0 ||
+      !(max_corr_dist > 0.f) || (estimator != 0 && estimator != 1) || (search != 0 && search != 1))
+    return fail(c, "dsir_icp_refine_ex2: bad arguments");
+  if (estimator == 1 && !normals_ref && stride < 6)
+    return fail(c, "dsir_icp_refine_ex2: bad arguments (the plane estimator without normals_ref reads the normals from columns 3..5 "
+                   "of the points_ref rows: stride=%d, needs >= 6)", stride);
+  if (search == 1 && (!icp_grid_radius_ok(max_corr_dist) || !icp_grid_shape_ok(pairs, J, K)))
+    return fail(c, "dsir_icp_refine_ex2: bad arguments (the grid search needs a max_corr_dist whose fp32 square is finite, and pairs x J "
+                   "and pairs x K below 2^31)");
+  HIP_OK(c, hipSetDevice(c->device));
+  c->ws.top = 0; c->ws.overflow = false;
+  void* scratch = c->ws.raw(icp_scratch_bytes_ex2(pairs, J, K, estimator, search));
+  if (c->ws.overflow) return fail(c, "workspace too small for dsir_icp_refine_ex2 (raise max_points / max_pairs)");
+  const float* normals = normals_ref ? normals_ref : points_ref + 3;
+  if (const int e = launch_icp_refine_ex2(points_src, points_ref, pairs, J, K, stride, max_corr_dist, max_iter, rel_fitness, rel_rmse, T_init,
+                                          T_out, nullptr, stats, estimator, normals, normals_ref ? (int64_t)K * 3 : (int64_t)K * stride,
+                                          normals_ref ? 3 : stride, icp_search_mode(search), scratch, c->stream))
+    return fail(c, "dsir_icp_refine_ex2: the index build failed (HIP error %d)", e);
+  return post(c);
+}
+
+int dsir_icp_correspondences(dsir_ctx* c, const float* points_src, const float* points_ref, int pairs, int J, int K, int stride,
+                             float max_corr_dist, const float* T, int search, int32_t* idx_out, float* d2_out, double* stats_out) {
+  if (!c) return 1;
+  if (!points_src || !points_ref || !T || !idx_out || !d2_out || pairs < 1 || J < 1 || K < 1 || stride < 3 || !(max_corr_dist > 0.f) ||
+      (search != 0 && search != 1))
+    return fail(c, "dsir_icp_correspondences: bad arguments");
+  if (search == 1 && (!icp_grid_radius_ok(max_corr_dist) || !icp_grid_shape_ok(pairs, J, K)))
+    return fail(c, "dsir_icp_correspondences: bad arguments (the grid search needs a max_corr_dist whose fp32 square is finite, and "
+                   "pairs x J and pairs x K below 2^31)");
+  HIP_OK(c, hipSetDevice(c->device));
+  c->ws.top = 0; c->ws.overflow = false;
+  void* scratch = c->ws.raw(icp_corr_scratch_bytes(pairs, J, K, search));
+  if (c->ws.overflow) return fail(c, "workspace too small for dsir_icp_correspondences (raise max_points / max_pairs)");
+  if (const int e = launch_icp_correspondences(points_src, points_ref, pairs, J, K, stride, max_corr_dist, T, icp_search_mode(search), idx_out,
+                                               d2_out, stats_out, scratch, c->stream))
+    return fail(c, "dsir_icp_correspondences: the index build failed (HIP error %d)", e);
   return post(c);
 }
 

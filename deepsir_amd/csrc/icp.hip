@@ -10,6 +10,8 @@
 // run for all pairs of a batch at once, entirely on device (no host round trip per iteration): a per-pair `done` flag
 // turns the remaining iterations into no-ops.  Nearest neighbours: exact brute force in fp32 (squared distance
 // (dx*dx + dy*dy) + dz*dz without FMA contraction, ties to the lower index), support staged through LDS.
+// launch_icp_refine_ex2(search = 1) runs the same loop with the cell index of icp_grid.hip at the three search sites: the same
+// neighbour and the same d2 bits, so the same pose and statistics byte for byte, without the J x K product per iteration.
 //
 // ---- Point-to-plane estimator (dsir_icp_refine_ex, estimator 1): open3d's TransformationEstimationPointToPlane in the same loop.
 // open3d is not installable here: parity is unpinned, THE RULE IS OWNED HERE and restated in tests/icp_plane_host.py.  The first
@@ -140,6 +142,29 @@ __global__ __launch_bounds__(256) void icp_stats_kernel(int32_t* __restrict__ id
       if (fabs(st[0] - fitness) < (double)rel_fitness && fabs(st[1] - rmse) < (double)rel_rmse) st[2] = 1.0;
     }
     st[0] = fitness; st[1] = rmse;
+  }
+}
+
+// one search step's {fitness, inlier RMSE} in icp_stats_kernel's summation order, the correspondences left as the search wrote them
+__global__ __launch_bounds__(256) void icp_corr_stats_kernel(const int32_t* __restrict__ idx, const float* __restrict__ d2, int J,
+                                                             double* __restrict__ out) {
+  __shared__ double s_cnt[4], s_sse[4];
+  const int pair = blockIdx.x;
+  double cnt = 0.0, sse = 0.0;
+  for (int j = threadIdx.x; j < J; j += 256) {
+    const int64_t o = (int64_t)pair * J + j;
+    const bool in = idx[o] >= 0;
+    cnt += in ? 1.0 : 0.0;
+    sse += in ? (double)d2[o] : 0.0;
+  }
+  cnt = wave_sum(cnt); sse = wave_sum(sse);
+  if ((threadIdx.x & 63) == 0) { s_cnt[threadIdx.x >> 6] = cnt; s_sse[threadIdx.x >> 6] = sse; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    cnt = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+    sse = s_sse[0] + s_sse[1] + s_sse[2] + s_sse[3];
+    out[(int64_t)pair * 2] = cnt / (double)J;
+    out[(int64_t)pair * 2 + 1] = cnt > 0.0 ? sqrt(sse / cnt) : 0.0;
   }
 }
 
@@ -291,6 +316,20 @@ void launch_icp_refine_ex(const float* src, const float* ref, int pairs, int J, 
                           int max_iter, float rel_fitness, float rel_rmse, const float* T_init, float* T_out,
                           double* stats_out, double* stats5_out, int estimator, const float* normals, int64_t normals_cs,
                           int normals_ld, void* scratch, hipStream_t st) {
+  launch_icp_refine_ex2(src, ref, pairs, J, K, stride, max_corr_dist, max_iter, rel_fitness, rel_rmse, T_init, T_out, stats_out, stats5_out,
+                        estimator, normals, normals_cs, normals_ld, 0, scratch, st);
+}
+
+size_t icp_scratch_bytes_ex2(int pairs, int J, int K, int estimator, int search) {
+  return icp_scratch_bytes_ex(pairs, J, estimator) + (search != 0 ? icp_grid_scratch_bytes(pairs, J, K) : 0);
+}
+
+// search 0: every launch below is launch_icp_refine_ex's, in its order.  search 1 (2: without the query order): the index of
+// icp_grid.hip is built once after the points are moved by T_init, and the three search sites launch its kernel instead.
+int launch_icp_refine_ex2(const float* src, const float* ref, int pairs, int J, int K, int stride, float max_corr_dist,
+                          int max_iter, float rel_fitness, float rel_rmse, const float* T_init, float* T_out,
+                          double* stats_out, double* stats5_out, int estimator, const float* normals, int64_t normals_cs,
+                          int normals_ld, int search, void* scratch, hipStream_t st) {
   char* p = reinterpret_cast<char*>(scratch);
   auto take = [&](size_t bytes) { char* r = p; p += (bytes + 255) & ~(size_t)255; return r; };
   float* cur = reinterpret_cast<float*>(take((size_t)pairs * J * 12));
@@ -306,13 +345,21 @@ void launch_icp_refine_ex(const float* src, const float* ref, int pairs, int J, 
   const int nch = icp_plane_chunks(J);
   double* part = plane ? reinterpret_cast<double*>(take(icp_plane_part_bytes(pairs, J))) : nullptr;
   double* nsing = plane ? reinterpret_cast<double*>(take((size_t)pairs * 8)) : nullptr;
+  void* grid_scratch = search != 0 ? take(icp_grid_scratch_bytes(pairs, J, K)) : nullptr;
   if (plane) hipMemsetAsync(nsing, 0, (size_t)pairs * 8, st);
   const float r2 = max_corr_dist * max_corr_dist;
   hipMemsetAsync(state, 0, (size_t)pairs * 32, st);
   hipMemcpyAsync(Ta, T_init, (size_t)pairs * 48, hipMemcpyDeviceToDevice, st);
   const dim3 gj((J + 255) / 256, pairs), gq((J + QB - 1) / QB, pairs);
   hipLaunchKernelGGL(icp_apply_kernel, gj, dim3(256), 0, st, src, stride, J, Ta, cur);
-  hipLaunchKernelGGL(icp_nn_kernel, gq, dim3(QB * NW), 0, st, cur, ref, stride, J, K, r2, idx, d2, (const int32_t*)nullptr);
+  IcpGrid grid{};
+  if (search != 0)
+    if (const int e = icp_grid_build(ref, stride, cur, pairs, J, K, max_corr_dist, search == 1, grid_scratch, st, &grid)) return e;
+  auto nn = [&](const int32_t* skip_flags) {
+    if (search != 0) { launch_icp_nn_grid(grid, cur, pairs, J, K, r2, idx, d2, skip_flags, st); return; }
+    hipLaunchKernelGGL(icp_nn_kernel, gq, dim3(QB * NW), 0, st, cur, ref, stride, J, K, r2, idx, d2, skip_flags);
+  };
+  nn(nullptr);
   hipLaunchKernelGGL(icp_stats_kernel, dim3(pairs), dim3(256), 0, st, idx, d2, w, J, 0, rel_fitness, rel_rmse, state);
   float *Tp = Ta, *Tn = Tb;
   for (int it = 0; it < max_iter; ++it) {
@@ -322,7 +369,7 @@ void launch_icp_refine_ex(const float* src, const float* ref, int pairs, int J, 
                          (const double*)state, part);
       hipLaunchKernelGGL(icp_plane_step_kernel, dim3((J + PT - 1) / PT, pairs), dim3(PT), 0, st, cur, J, nch, (const double*)part,
                          (const double*)state, (const float*)Tp, Tn, nsing, skip);
-      hipLaunchKernelGGL(icp_nn_kernel, gq, dim3(QB * NW), 0, st, cur, ref, stride, J, K, r2, idx, d2, (const int32_t*)skip);
+      nn(skip);
       hipLaunchKernelGGL(icp_stats_kernel, dim3(pairs), dim3(256), 0, st, idx, d2, w, J, 1, rel_fitness, rel_rmse, state);
       float* t = Tp; Tp = Tn; Tn = t;
       continue;
@@ -333,13 +380,37 @@ void launch_icp_refine_ex(const float* src, const float* ref, int pairs, int J, 
     a.ref_ld = stride; a.sigmoid = 0; a.pairs = pairs; a.m = J; a.T = Tstep; a.invalid = nullptr;
     a.src_out = cur; a.src_out_stride = (int64_t)J * 3; a.T_prev = Tp; a.T_cum = Tn; a.T_stride = 12; a.skip = skip;
     launch_kabsch(a, st);
-    hipLaunchKernelGGL(icp_nn_kernel, gq, dim3(QB * NW), 0, st, cur, ref, stride, J, K, r2, idx, d2, (const int32_t*)skip);
+    nn(skip);
     hipLaunchKernelGGL(icp_stats_kernel, dim3(pairs), dim3(256), 0, st, idx, d2, w, J, 1, rel_fitness, rel_rmse, state);
     float* t = Tp; Tp = Tn; Tn = t;
   }
   hipMemcpyAsync(T_out, Tp, (size_t)pairs * 48, hipMemcpyDeviceToDevice, st);
   if (stats_out) hipMemcpyAsync(stats_out, state, (size_t)pairs * 32, hipMemcpyDeviceToDevice, st);
   if (stats5_out) hipLaunchKernelGGL(icp_stats5_kernel, dim3((pairs + 255) / 256), dim3(256), 0, st, (const double*)state, (const double*)nsing, pairs, stats5_out);
+  return 0;
+}
+
+size_t icp_corr_scratch_bytes(int pairs, int J, int K, int search) {
+  return (((size_t)pairs * J * 12 + 255) & ~(size_t)255) + (search != 0 ? icp_grid_scratch_bytes(pairs, J, K) : 0);
+}
+
+// one search step under T: the apply and the search of the loop's first three launches, and their statistics
+int launch_icp_correspondences(const float* src, const float* ref, int pairs, int J, int K, int stride, float max_corr_dist, const float* T,
+                               int search, int32_t* idx_out, float* d2_out, double* stats_out, void* scratch, hipStream_t st) {
+  float* cur = reinterpret_cast<float*>(scratch);
+  void* grid_scratch = reinterpret_cast<char*>(scratch) + (((size_t)pairs * J * 12 + 255) & ~(size_t)255);
+  const float r2 = max_corr_dist * max_corr_dist;
+  hipLaunchKernelGGL(icp_apply_kernel, dim3((J + 255) / 256, pairs), dim3(256), 0, st, src, stride, J, T, cur);
+  if (search != 0) {
+    IcpGrid grid{};
+    if (const int e = icp_grid_build(ref, stride, cur, pairs, J, K, max_corr_dist, search == 1, grid_scratch, st, &grid)) return e;
+    launch_icp_nn_grid(grid, cur, pairs, J, K, r2, idx_out, d2_out, nullptr, st);
+  } else {
+    hipLaunchKernelGGL(icp_nn_kernel, dim3((J + QB - 1) / QB, pairs), dim3(QB * NW), 0, st, (const float*)cur, ref, stride, J, K, r2, idx_out,
+                       d2_out, (const int32_t*)nullptr);
+  }
+  if (stats_out) hipLaunchKernelGGL(icp_corr_stats_kernel, dim3(pairs), dim3(256), 0, st, (const int32_t*)idx_out, (const float*)d2_out, J, stats_out);
+  return 0;
 }
 
 }  // namespace dsir

@@ -517,6 +517,26 @@ void launch_icp_refine_ex(const float* src, const float* ref, int pairs, int J, 
                           int max_iter, float rel_fitness, float rel_rmse, const float* T_init, float* T_out,
                           double* stats_out, double* stats5_out, int estimator, const float* normals, int64_t normals_cs,
                           int normals_ld, void* scratch, hipStream_t st);
+// the same loop with the search chosen: 0 = the brute force of icp_nn_kernel (launch_icp_refine_ex's sequence, untouched), 1 = the cell
+// index of icp_grid.hip (same neighbour, same d2 bits: the whole loop is byte for byte the brute-force loop's), 2 = 1 without the
+// query order (a measurement hook, not reachable through the C ABI's argument).  Returns 0 or a HIP error of the index build.
+size_t icp_scratch_bytes_ex2(int pairs, int J, int K, int estimator, int search);
+int launch_icp_refine_ex2(const float* src, const float* ref, int pairs, int J, int K, int stride, float max_corr_dist,
+                          int max_iter, float rel_fitness, float rel_rmse, const float* T_init, float* T_out,
+                          double* stats_out, double* stats5_out, int estimator, const float* normals, int64_t normals_cs,
+                          int normals_ld, int search, void* scratch, hipStream_t st);
+// one search step under pose T [pairs][3][4]: idx_out [pairs][J] (-1: none), d2_out [pairs][J], stats_out [pairs][2] {fitness, inlier_rmse}
+size_t icp_corr_scratch_bytes(int pairs, int J, int K, int search);
+int launch_icp_correspondences(const float* src, const float* ref, int pairs, int J, int K, int stride, float max_corr_dist, const float* T,
+                               int search, int32_t* idx_out, float* d2_out, double* stats_out, void* scratch, hipStream_t st);
+
+// icp_grid.hip - the cell index of the ICP search (the rule, the lattice and the containment argument: the file's header)
+struct IcpGrid { const void* keys; const void* sorted; const int32_t* perm; const void* lat; };
+size_t icp_grid_scratch_bytes(int pairs, int J, int K);   // 0 for a shape the index does not take
+int icp_grid_build(const float* ref, int stride, const float* cur, int pairs, int J, int K, float r, bool order, void* scratch,
+                   hipStream_t st, IcpGrid* out);
+void launch_icp_nn_grid(const IcpGrid& g, const float* cur, int pairs, int J, int K, float r2, int32_t* idx, float* d2, const int32_t* skip,
+                        hipStream_t st);
 
 // ransac.hip — RANSAC pose from correspondences (network/DGR.py:7-36, :249-306 / open3d registration_ransac_*; the rule is stated in
 // the file's header), all pairs at once; and the mutual-nearest-neighbour list of dsir_feature_correspondences

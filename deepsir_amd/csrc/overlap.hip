@@ -44,6 +44,7 @@
 
 #include <vector>
 
+#include "cell_index.h"
 #include "dsir_train.h"
 
 namespace dsir {
@@ -51,27 +52,12 @@ namespace {
 
 constexpr int NN_BLOCK = 256;                       // queries per block: one per lane, 4 waves
 constexpr int64_t MAX_CELLS = (1ll << 21) - 2;      // per axis
-constexpr int MAXC = (1 << 21) - 1;                 // largest coordinate a key holds
 constexpr int64_t MAX_POINTS = 1ll << 30;
 constexpr int MAX_FRAGMENTS = 1 << 20;
-constexpr uint64_t KEY_NONE = ~0ull;
 
 struct Lattice { double ox, oy, oz, h; };
 
 inline double cell_edge(float r) { return (double)r * (1.0 + 1.0 / 1024.0); }
-
-// the cell coordinate of a finite fp32 value, clamped so that a moved query far outside the lattice stays a valid int
-__device__ __forceinline__ int cell_of(float a, double o, double h) {
-  double u = floor(((double)a - o) / h);
-  u = u < -2.0 ? -2.0 : (u > (double)(MAXC + 2) ? (double)(MAXC + 2) : u);
-  return (int)u;
-}
-__device__ __forceinline__ uint64_t cell_key(int x, int y, int z) { return (uint64_t)x | ((uint64_t)y << 21) | ((uint64_t)z << 42); }
-__device__ __forceinline__ bool finite3(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
-
-// order-preserving map fp32 -> uint32, for integer min / max
-__device__ __forceinline__ uint32_t f2ord(float f) { const uint32_t u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
-__device__ __forceinline__ float ord2f(uint32_t o) { return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o); }
 
 // enc [6]: min xyz, max xyz of the finite rows, as ordered integers (integer atomics: order-independent)
 __global__ void finite_bounds_kernel(const float* __restrict__ pts, int stride, int64_t n, uint32_t* __restrict__ enc) {
@@ -123,7 +109,7 @@ __global__ void nn_gather_kernel(const float* __restrict__ pts, int stride, cons
     while (hi - lo > 1) { const int mid = lo + ((hi - lo) >> 1); if ((int64_t)off[mid] <= i) lo = mid; else hi = mid; }
     const uint32_t v = vals[i];
     const float* p = pts + ((int64_t)off[lo] + v) * stride;
-    sorted[i] = make_float4(p[0], p[1], p[2], __uint_as_float(v));
+    sorted[i] = gather_xyzi(p, v);
   }
 }
 

@@ -316,7 +316,7 @@ class KittiOdometryTest:
         Md = torch.from_numpy(M.astype(np.float32)).to(self.engine.device)
         v0 = (v0 @ Md[:3, :3].T + Md[:3, 3]).contiguous()
         eye = torch.eye(4, device=self.engine.device)[None, :3, :].contiguous()
-        T, _ = self.engine.icp_refine(v0[None].contiguous(), v1[None].contiguous(), eye, 0.2, max_iter=200)
+        T, _ = self.engine.icp_refine(v0[None].contiguous(), v1[None].contiguous(), eye, 0.2, max_iter=200, search="auto")
         Tp = np.eye(4)
         Tp[:3, :] = T[0].double().cpu().numpy()
         M2 = M @ Tp

@@ -566,23 +566,45 @@ class Engine:
     # ------------------------------------------------------------------ measurement hooks
     ICP_ESTIMATORS = {"point": 0, "plane": 1}
 
+    ICP_SEARCHES = ("brute", "grid", "auto")
+    # search="auto" takes the cell index from this many reference points on: the measured crossover of tools/bench_icp.py's
+    # single-pair sweep, rounded up to a power of two (profiles/README.md, "ICP: cell-indexed search")
+    ICP_GRID_MIN_REF = 4096
+
+    def _icp_search(self, search: str, K: int) -> int:
+        """0 = brute force, 1 = cell index: a host-only decision on shapes, like the ones in csrc/search_plan.h"""
+        if search not in self.ICP_SEARCHES:
+            raise ValueError("search must be 'brute', 'grid' or 'auto'")
+        return int(search == "grid" or (search == "auto" and K >= self.ICP_GRID_MIN_REF))
+
     def icp_refine(self, points_src, points_ref, T_init, max_corr_dist: float, max_iter: int = 30,
                    rel_fitness: float = 1e-6, rel_rmse: float = 1e-6, estimator: str = "point", normals_ref=None,
-                   viewpoint=(0.0, 0.0, 0.0)):
+                   viewpoint=(0.0, 0.0, 0.0), search: str = "brute"):
         """open3d registration_icp counterpart for P pairs (reference test.py:241-258, disabled there).
         points_* [P,N,>=3] CUDA fp32, T_init [P,3,4] -> (T [P,3,4], stats [P,4] f64: fitness, inlier_rmse, converged, iters).
         estimator="plane": the point-to-plane update (include/dsir.h, dsir_icp_refine_ex) and a fifth stats column, the identity
         updates taken for a singular system.  Its normals of points_ref: ``normals_ref`` [P,K,3] if given, else columns 3..5 of
         rows of 6 columns and more (the use_ppf layout), else estimated here - knn_pyramid on points_ref, estimate_normals on its
-        level-0 lists towards ``viewpoint`` - which needs a cloud the pyramid accepts (ValueError otherwise)."""
+        level-0 lists towards ``viewpoint`` - which needs a cloud the pyramid accepts (ValueError otherwise).
+        search: "brute" (J x K distance tests per iteration), "grid" (a cell index of points_ref built once per call,
+        csrc/icp_grid.hip) or "auto" (the grid from ICP_GRID_MIN_REF reference points on).  Same bytes out, whichever is taken."""
         if estimator not in self.ICP_ESTIMATORS:
             raise ValueError("estimator must be 'point' or 'plane'")
+        grid = self._icp_search(search, points_ref.shape[1])
         points_src, points_ref = _chk(points_src, torch.float32, "points_src"), _chk(points_ref, torch.float32, "points_ref")
         T_init = _chk(T_init, torch.float32, "T_init")
         P, J, stride = points_src.shape
         K = points_ref.shape[1]
         assert points_ref.shape[0] == P and points_ref.shape[2] == stride and tuple(T_init.shape) == (P, 3, 4)
         T = self._empty((P, 3, 4))
+        if grid and estimator == "point":
+            stats = self._empty((P, 5), torch.float64)
+            self._pre()
+            self._call(self.lib.dsir_icp_refine_ex2(self.h, _ptr(points_src), _ptr(points_ref), P, J, K, stride, float(max_corr_dist),
+                                                    int(max_iter), float(rel_fitness), float(rel_rmse), _ptr(T_init), _ptr(T), 0,
+                                                    None, 1, _ptr(stats)))
+            self.sync()
+            return T, stats[:, :4].contiguous()
         if estimator == "point":
             stats = self._empty((P, 4), torch.float64)
             self._pre()
@@ -598,11 +620,34 @@ class Engine:
             normals_ref = self.icp_normals(points_ref, viewpoint)
         stats = self._empty((P, 5), torch.float64)
         self._pre()
-        self._call(self.lib.dsir_icp_refine_ex(self.h, _ptr(points_src), _ptr(points_ref), P, J, K, stride, float(max_corr_dist),
-                                               int(max_iter), float(rel_fitness), float(rel_rmse), _ptr(T_init), _ptr(T), 1,
-                                               _ptr(normals_ref), _ptr(stats)))
+        if grid:
+            self._call(self.lib.dsir_icp_refine_ex2(self.h, _ptr(points_src), _ptr(points_ref), P, J, K, stride, float(max_corr_dist),
+                                                    int(max_iter), float(rel_fitness), float(rel_rmse), _ptr(T_init), _ptr(T), 1,
+                                                    _ptr(normals_ref), 1, _ptr(stats)))
+        else:
+            self._call(self.lib.dsir_icp_refine_ex(self.h, _ptr(points_src), _ptr(points_ref), P, J, K, stride, float(max_corr_dist),
+                                                   int(max_iter), float(rel_fitness), float(rel_rmse), _ptr(T_init), _ptr(T), 1,
+                                                   _ptr(normals_ref), _ptr(stats)))
         self.sync()
         return T, stats
+
+    def icp_correspondences(self, points_src, points_ref, T, max_corr_dist: float, search: str = "brute"):
+        """open3d evaluate_registration counterpart for P pairs: one search step of icp_refine under the pose T.
+        points_* [P,N,>=3] CUDA fp32, T [P,3,4] -> (idx [P,J] i32: the reference point of each source point moved by T, or -1;
+        d2 [P,J] fp32: its squared distance, 0 where idx is -1; stats [P,2] f64: fitness, inlier_rmse).  search as for icp_refine."""
+        grid = self._icp_search(search, points_ref.shape[1])
+        points_src, points_ref = _chk(points_src, torch.float32, "points_src"), _chk(points_ref, torch.float32, "points_ref")
+        T = _chk(T, torch.float32, "T")
+        P, J, stride = points_src.shape
+        K = points_ref.shape[1]
+        assert points_ref.shape[0] == P and points_ref.shape[2] == stride and tuple(T.shape) == (P, 3, 4)
+        idx, d2 = self._empty((P, J), torch.int32), self._empty((P, J))
+        stats = self._empty((P, 2), torch.float64)
+        self._pre()
+        self._call(self.lib.dsir_icp_correspondences(self.h, _ptr(points_src), _ptr(points_ref), P, J, K, stride, float(max_corr_dist),
+                                                     _ptr(T), grid, _ptr(idx), _ptr(d2), _ptr(stats)))
+        self.sync()
+        return idx, d2, stats
 
     def icp_normals(self, points_ref, viewpoint=(0.0, 0.0, 0.0)):
         """The normals icp_refine(estimator="plane") estimates when it is given none: knn_pyramid on points_ref [P,K,>=3], then

@@ -26,13 +26,14 @@ from .metrics import THRESHOLDS, rte_rre
 def inference_align(pairs: Sequence[Dict[str, np.ndarray]], model, num_reg_iter: int = 5, dataset_type: str = "3DMatch",
                     batch: int = 1, device: Optional[torch.device] = None, dist=None, pose_opt: Optional[str] = None,
                     voxel_size: float = 0.3, in_flight: int = 1, safeguard_wsum: Optional[float] = None,
-                    ransac_hypotheses: int = 80000, ransac_seed: int = 0):
+                    ransac_hypotheses: int = 80000, ransac_seed: int = 0, icp_search: str = "auto"):
     """pairs: sequence of dicts with ``points_src/points_ref [1,N,C]``, ``transform_gt [1,3,4]`` and optionally the
     pyramid tensors and ``others`` (as the reference's collate, data_base.py:196-219).
     ``in_flight`` > 1: the reference's one-pair-per-call loop fed AHEAD - the pairs go one by one to a
     ``deepsir_amd.serve.PairServer`` that keeps that many requests outstanding (same results bit for bit; the per-pair
     time is then the shard's wall time divided by its size).
-    ``pose_opt='icp'`` / ``'icp_plane'``: ICP on the raw clouds from the last pose, point-to-point / point-to-plane.
+    ``pose_opt='icp'`` / ``'icp_plane'``: ICP on the raw clouds from the last pose, point-to-point / point-to-plane;
+    ``icp_search`` is ``Engine.icp_refine``'s ``search`` ("auto": the cell index on large clouds; the poses are the same bytes).
     ``pose_opt='ransac'``: DGR's safeguard (network/DGR.py:249-306) over the last iteration's correspondences, see below;
     ``pose_opt='consensus'``: the same correspondences through ``consensus_correspondence`` instead of the seeded sampling;
     ``safeguard_wsum``: only pairs whose summed sigmoid inlier weight is below it take the RANSAC pose (DGR.py:273-304).
@@ -85,14 +86,15 @@ def inference_align(pairs: Sequence[Dict[str, np.ndarray]], model, num_reg_iter:
             # pose_optimization with use_icp (test.py:241-258; off in the reference): point-to-point ICP on the raw clouds,
             # correspondence radius 2 x voxel size (test.py:219), open3d's default criteria
             T_opt, _ = _aux_engine(model, data).icp_refine(data["points_src"].float(), data["points_ref"].float(),
-                                                transforms[-1].contiguous(), 2.0 * voxel_size)
+                                                transforms[-1].contiguous(), 2.0 * voxel_size, search=icp_search)
             transforms.append(T_opt)
         elif pose_opt == "icp_plane":
             # the same refinement with the point-to-plane estimator (open3d's TransformationEstimationPointToPlane; include/dsir.h,
             # dsir_icp_refine_ex), same radius; the normals are those of use_ppf rows where the data has them, else estimated from
             # the reference cloud's level-0 neighbour lists
             T_opt, _ = _aux_engine(model, data).icp_refine(data["points_src"].float(), data["points_ref"].float(),
-                                                           transforms[-1].contiguous(), 2.0 * voxel_size, estimator="plane")
+                                                           transforms[-1].contiguous(), 2.0 * voxel_size, estimator="plane",
+                                                           search=icp_search)
             transforms.append(T_opt)
         elif pose_opt == "tune":
             # pose_optimization with use_tune (test.py:218-239; off in the reference): Adam fine-tune of the 6-D-rotation

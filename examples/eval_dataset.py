@@ -35,6 +35,8 @@ def main():
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--limit", type=int, default=0)
     ap.add_argument("--pose-opt", choices=["none", "icp", "icp_plane", "tune", "ransac", "consensus"], default="none")
+    ap.add_argument("--icp-search", choices=["brute", "grid", "auto"], default="auto",
+                    help="with --pose-opt icp / icp_plane: the nearest-neighbour search of the refinement (same poses, other time)")
     ap.add_argument("--pipeline", choices=["align", "feat"], default="align")
     ap.add_argument("--ransac", action="store_true", help="with --pipeline feat: descriptors -> mutual nearest neighbours -> RANSAC pose")
     ap.add_argument("--num-sub", type=int, default=1024, help="key points per cloud of the feat pipeline")
@@ -79,7 +81,8 @@ def main():
                                     pose=a.pose, match_k=a.match_k, match_ratio=a.match_ratio)
     else:
         pred, stats = inference_align(pairs, model, a.iters, a.dataset, batch=a.batch,
-                                      pose_opt=None if a.pose_opt == "none" else a.pose_opt, voxel_size=voxel)
+                                      pose_opt=None if a.pose_opt == "none" else a.pose_opt, voxel_size=voxel,
+                                      icp_search=a.icp_search)
     print({k: round(float(v), 4) for k, v in summarize(stats).items()})
     _, summary = evaluate_align(pred, pairs, eng, a.dataset)
     print({k: round(float(v), 5) for k, v in summary.items()})

@@ -332,6 +332,26 @@ int dsir_icp_refine_ex(dsir_ctx* ctx, const float* points_src, const float* poin
                        float max_corr_dist, int max_iter, float rel_fitness, float rel_rmse, const float* T_init,
                        float* T_out, int estimator, const float* normals_ref, double* stats);
 
+/* dsir_icp_refine_ex with the nearest-neighbour search chosen: search 0 = exact brute force (byte for byte what
+ * dsir_icp_refine_ex writes), 1 = a sparse cell index of the reference cloud, built once per call on the device and searched by
+ * every iteration (csrc/icp_grid.hip).  The rule is the same - d2 = (dx dx + dy dy) + dz dz in fp32, the smallest d2 with ties to
+ * the lower index, accepted iff d2 <= fl(r r) - and both searches return the same index and the same d2 bits, so T_out and stats
+ * are byte for byte those of search 0: the choice changes time only (J x K distance evaluations per search against a few hundred
+ * per query).  Arguments as for dsir_icp_refine_ex, `search` before `stats`.  No extent is refused: a pair whose reference box is
+ * more than 2^20 cells of the radius wide gets coarser cells.  search 1 with a max_corr_dist whose fp32 square is not finite, or with
+ * P x J or P x K of 2^31 and more, is "bad arguments".  The index, the query order and the sort's temporary storage come from the
+ * context workspace: "workspace too small" says to raise max_points / max_pairs. */
+int dsir_icp_refine_ex2(dsir_ctx* ctx, const float* points_src, const float* points_ref, int pairs, int J, int K, int stride,
+                        float max_corr_dist, int max_iter, float rel_fitness, float rel_rmse, const float* T_init,
+                        float* T_out, int estimator, const float* normals_ref, int search, double* stats);
+
+/* One search step of the loop under pose T [P][3][4]: open3d's evaluate_registration(src, tgt, max_correspondence_distance, T).
+ * idx_out [P][J] int32: the reference point of source point j moved by T, or -1 where none lies within max_corr_dist;
+ * d2_out [P][J] fp32: its squared distance, 0 where idx is -1; stats_out [P][2] float64 {fitness = matched / J, inlier_rmse =
+ * sqrt(sum d2 / matched), 0 without a match} or NULL.  search as for dsir_icp_refine_ex2: both values write the same bytes. */
+int dsir_icp_correspondences(dsir_ctx* ctx, const float* points_src, const float* points_ref, int pairs, int J, int K, int stride,
+                             float max_corr_dist, const float* T, int search, int32_t* idx_out, float* d2_out, double* stats_out);
+
 /* Replaces the `use_tune` branch of pose_optimization (test.py:209-239): transformation_finetune (test.py:159-207) with
  * HighDimSmoothL1Loss (test.py:103-131) over the network's last correspondences, the pose re-parametrised as
  * network/DGR.py's Transformation (6-D rotation + translation, :60-132) and fitted by Adam (lr 0.1, ExponentialLR 0.999)
