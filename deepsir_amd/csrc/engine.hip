@@ -768,88 +768,79 @@ int dsir_forward_pair(dsir_ctx* c, const dsir_pair_batch* in, int num_sub, const
   return post(c);
 }
 
+// search 1 -> the grid without its query order under the measurement switch DSIR_ICP_GRID_NO_ORDER: same bytes, other speed
+static IcpSearch icp_search_mode(int search) {
+  if (search != 1) return IcpSearch::Brute;
+  return tuning_flag("DSIR_ICP_GRID_NO_ORDER") ? IcpSearch::GridUnordered : IcpSearch::Grid;
+}
+
+struct IcpCorrOut { int32_t* idx; float* d2; double* stats; };
+
+// What the four ICP entries share: the checks under the entry's own `name`, the workspace reset, the scratch, the normals
+// (normals_ref [pairs][K][3], or columns 3..5 of the points_ref rows) and the launch; corr != nullptr: one search step, not the loop.
+static int icp_entry(dsir_ctx* c, const char* name, IcpArgs a, const float* normals_ref, int search, const IcpCorrOut* corr) {
+  if (!c) return 1;
+  const bool outs = corr ? corr->idx && corr->d2 : a.T_out != nullptr;
+  if (!a.src || !a.ref || !a.T_init || !outs || a.pairs < 1 || a.J < 1 || a.K < 1 || a.stride < 3 || a.max_iter < 0 ||
+      !(a.max_corr_dist > 0.f) || (a.estimator != 0 && a.estimator != 1) || (search != 0 && search != 1))
+    return fail(c, "%s: bad arguments", name);
+  if (a.estimator == 1 && !normals_ref && a.stride < 6)
+    return fail(c, "%s: bad arguments (the plane estimator without normals_ref reads the normals from columns 3..5 "
+                   "of the points_ref rows: stride=%d, needs >= 6)", name, a.stride);
+  if (search == 1 && (!icp_grid_radius_ok(a.max_corr_dist) || !icp_grid_shape_ok(a.pairs, a.J, a.K)))
+    return fail(c, "%s: bad arguments (the grid search needs a max_corr_dist whose fp32 square is finite, and pairs x J "
+                   "and pairs x K below 2^31)", name);
+  a.search = icp_search_mode(search);
+  a.normals = normals_ref ? normals_ref : a.ref + 3;
+  a.normals_cs = normals_ref ? (int64_t)a.K * 3 : (int64_t)a.K * a.stride;
+  a.normals_ld = normals_ref ? 3 : a.stride;
+  HIP_OK(c, hipSetDevice(c->device));
+  c->ws.top = 0; c->ws.overflow = false;
+  void* scratch = c->ws.raw(corr ? icp_corr_scratch_bytes(a) : icp_scratch_bytes(a));
+  if (c->ws.overflow) return fail(c, "workspace too small for %s (raise max_points / max_pairs)", name);
+  if (const int e = corr ? launch_icp_correspondences(a, corr->idx, corr->d2, corr->stats, scratch, c->stream)
+                         : launch_icp_refine(a, scratch, c->stream))
+    return fail(c, "%s: the index build failed (HIP error %d)", name, e);
+  return post(c);
+}
+
+static IcpArgs icp_args(const float* points_src, const float* points_ref, int pairs, int J, int K, int stride, float max_corr_dist,
+                        int max_iter, float rel_fitness, float rel_rmse, const float* T_init, float* T_out, int estimator) {
+  IcpArgs a{};
+  a.src = points_src; a.ref = points_ref; a.pairs = pairs; a.J = J; a.K = K; a.stride = stride; a.max_corr_dist = max_corr_dist;
+  a.max_iter = max_iter; a.rel_fitness = rel_fitness; a.rel_rmse = rel_rmse; a.T_init = T_init; a.T_out = T_out; a.estimator = estimator;
+  return a;
+}
+
 int dsir_icp_refine(dsir_ctx* c, const float* points_src, const float* points_ref, int pairs, int J, int K, int stride,
                     float max_corr_dist, int max_iter, float rel_fitness, float rel_rmse, const float* T_init,
                     float* T_out, double* stats) {
-  if (!c) return 1;
-  if (!points_src || !points_ref || !T_init || !T_out || pairs < 1 || J < 1 || K < 1 || stride < 3 || max_iter < 0 ||
-      !(max_corr_dist > 0.f))
-    return fail(c, "dsir_icp_refine: bad arguments");
-  HIP_OK(c, hipSetDevice(c->device));
-  c->ws.top = 0; c->ws.overflow = false;
-  void* scratch = c->ws.raw(icp_scratch_bytes(pairs, J));
-  if (c->ws.overflow) return fail(c, "workspace too small for dsir_icp_refine (raise max_points / max_pairs)");
-  launch_icp_refine(points_src, points_ref, pairs, J, K, stride, max_corr_dist, max_iter, rel_fitness, rel_rmse, T_init,
-                    T_out, stats, scratch, c->stream);
-  return post(c);
+  IcpArgs a = icp_args(points_src, points_ref, pairs, J, K, stride, max_corr_dist, max_iter, rel_fitness, rel_rmse, T_init, T_out, 0);
+  a.stats_out = stats;                                            // [pairs][4]
+  return icp_entry(c, "dsir_icp_refine", a, nullptr, 0, nullptr);
 }
 
 int dsir_icp_refine_ex(dsir_ctx* c, const float* points_src, const float* points_ref, int pairs, int J, int K, int stride,
                        float max_corr_dist, int max_iter, float rel_fitness, float rel_rmse, const float* T_init, float* T_out,
                        int estimator, const float* normals_ref, double* stats) {
-  if (!c) return 1;
-  if (!points_src || !points_ref || !T_init || !T_out || pairs < 1 || J < 1 || K < 1 || stride < 3 || max_iter < 0 ||
-      !(max_corr_dist > 0.f) || (estimator != 0 && estimator != 1))
-    return fail(c, "dsir_icp_refine_ex: bad arguments");
-  if (estimator == 1 && !normals_ref && stride < 6)
-    return fail(c, "dsir_icp_refine_ex: bad arguments (the plane estimator without normals_ref reads the normals from columns 3..5 "
-                   "of the points_ref rows: stride=%d, needs >= 6)", stride);
-  HIP_OK(c, hipSetDevice(c->device));
-  c->ws.top = 0; c->ws.overflow = false;
-  void* scratch = c->ws.raw(icp_scratch_bytes_ex(pairs, J, estimator));
-  if (c->ws.overflow) return fail(c, "workspace too small for dsir_icp_refine_ex (raise max_points / max_pairs)");
-  const float* normals = normals_ref ? normals_ref : points_ref + 3;
-  launch_icp_refine_ex(points_src, points_ref, pairs, J, K, stride, max_corr_dist, max_iter, rel_fitness, rel_rmse, T_init, T_out,
-                       nullptr, stats, estimator, normals, normals_ref ? (int64_t)K * 3 : (int64_t)K * stride, normals_ref ? 3 : stride,
-                       scratch, c->stream);
-  return post(c);
+  IcpArgs a = icp_args(points_src, points_ref, pairs, J, K, stride, max_corr_dist, max_iter, rel_fitness, rel_rmse, T_init, T_out, estimator);
+  a.stats5_out = stats;                                           // [pairs][5]
+  return icp_entry(c, "dsir_icp_refine_ex", a, normals_ref, 0, nullptr);
 }
-
-// search 1 -> 2 (the grid without its query order) under the measurement switch DSIR_ICP_GRID_NO_ORDER: same bytes, other speed
-static int icp_search_mode(int search) { return search == 1 && tuning_flag("DSIR_ICP_GRID_NO_ORDER") ? 2 : search; }
 
 int dsir_icp_refine_ex2(dsir_ctx* c, const float* points_src, const float* points_ref, int pairs, int J, int K, int stride,
                         float max_corr_dist, int max_iter, float rel_fitness, float rel_rmse, const float* T_init, float* T_out,
                         int estimator, const float* normals_ref, int search, double* stats) {
-  if (!c) return 1;
-  if (!points_src || !points_ref || !T_init || !T_out || pairs < 1 || J < 1 || K < 1 || stride < 3 || max_iter < 0 ||
-      !(max_corr_dist > 0.f) || (estimator != 0 && estimator != 1) || (search != 0 && search != 1))
-    return fail(c, "dsir_icp_refine_ex2: bad arguments");
-  if (estimator == 1 && !normals_ref && stride < 6)
-    return fail(c, "dsir_icp_refine_ex2: bad arguments (the plane estimator without normals_ref reads the normals from columns 3..5 "
-                   "of the points_ref rows: stride=%d, needs >= 6)", stride);
-  if (search == 1 && (!icp_grid_radius_ok(max_corr_dist) || !icp_grid_shape_ok(pairs, J, K)))
-    return fail(c, "dsir_icp_refine_ex2: bad arguments (the grid search needs a max_corr_dist whose fp32 square is finite, and pairs x J "
-                   "and pairs x K below 2^31)");
-  HIP_OK(c, hipSetDevice(c->device));
-  c->ws.top = 0; c->ws.overflow = false;
-  void* scratch = c->ws.raw(icp_scratch_bytes_ex2(pairs, J, K, estimator, search));
-  if (c->ws.overflow) return fail(c, "workspace too small for dsir_icp_refine_ex2 (raise max_points / max_pairs)");
-  const float* normals = normals_ref ? normals_ref : points_ref + 3;
-  if (const int e = launch_icp_refine_ex2(points_src, points_ref, pairs, J, K, stride, max_corr_dist, max_iter, rel_fitness, rel_rmse, T_init,
-                                          T_out, nullptr, stats, estimator, normals, normals_ref ? (int64_t)K * 3 : (int64_t)K * stride,
-                                          normals_ref ? 3 : stride, icp_search_mode(search), scratch, c->stream))
-    return fail(c, "dsir_icp_refine_ex2: the index build failed (HIP error %d)", e);
-  return post(c);
+  IcpArgs a = icp_args(points_src, points_ref, pairs, J, K, stride, max_corr_dist, max_iter, rel_fitness, rel_rmse, T_init, T_out, estimator);
+  a.stats5_out = stats;
+  return icp_entry(c, "dsir_icp_refine_ex2", a, normals_ref, search, nullptr);
 }
 
 int dsir_icp_correspondences(dsir_ctx* c, const float* points_src, const float* points_ref, int pairs, int J, int K, int stride,
                              float max_corr_dist, const float* T, int search, int32_t* idx_out, float* d2_out, double* stats_out) {
-  if (!c) return 1;
-  if (!points_src || !points_ref || !T || !idx_out || !d2_out || pairs < 1 || J < 1 || K < 1 || stride < 3 || !(max_corr_dist > 0.f) ||
-      (search != 0 && search != 1))
-    return fail(c, "dsir_icp_correspondences: bad arguments");
-  if (search == 1 && (!icp_grid_radius_ok(max_corr_dist) || !icp_grid_shape_ok(pairs, J, K)))
-    return fail(c, "dsir_icp_correspondences: bad arguments (the grid search needs a max_corr_dist whose fp32 square is finite, and "
-                   "pairs x J and pairs x K below 2^31)");
-  HIP_OK(c, hipSetDevice(c->device));
-  c->ws.top = 0; c->ws.overflow = false;
-  void* scratch = c->ws.raw(icp_corr_scratch_bytes(pairs, J, K, search));
-  if (c->ws.overflow) return fail(c, "workspace too small for dsir_icp_correspondences (raise max_points / max_pairs)");
-  if (const int e = launch_icp_correspondences(points_src, points_ref, pairs, J, K, stride, max_corr_dist, T, icp_search_mode(search), idx_out,
-                                               d2_out, stats_out, scratch, c->stream))
-    return fail(c, "dsir_icp_correspondences: the index build failed (HIP error %d)", e);
-  return post(c);
+  const IcpArgs a = icp_args(points_src, points_ref, pairs, J, K, stride, max_corr_dist, 0, 0.f, 0.f, T, nullptr, 0);
+  const IcpCorrOut out{idx_out, d2_out, stats_out};
+  return icp_entry(c, "dsir_icp_correspondences", a, nullptr, search, &out);
 }
 
 int dsir_ransac_correspondence(dsir_ctx* c, const float* points_src, const float* points_ref, int pairs, int J, int K, int stride,

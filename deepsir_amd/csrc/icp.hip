@@ -10,8 +10,9 @@
 // run for all pairs of a batch at once, entirely on device (no host round trip per iteration): a per-pair `done` flag
 // turns the remaining iterations into no-ops.  Nearest neighbours: exact brute force in fp32 (squared distance
 // (dx*dx + dy*dy) + dz*dz without FMA contraction, ties to the lower index), support staged through LDS.
-// launch_icp_refine_ex2(search = 1) runs the same loop with the cell index of icp_grid.hip at the three search sites: the same
-// neighbour and the same d2 bits, so the same pose and statistics byte for byte, without the J x K product per iteration.
+// IcpSearch::Grid runs the same loop with the cell index of icp_grid.hip at the search sites: the same neighbour and the same d2
+// bits, so the same pose and statistics byte for byte, without the J x K product per iteration.  One call path: IcpArgs (kernels.h)
+// in, IcpLayout (icp_layout.h) for the scratch, the estimator as a step (step_point / step_plane) of one loop body.
 //
 // ---- Point-to-plane estimator (dsir_icp_refine_ex, estimator 1): open3d's TransformationEstimationPointToPlane in the same loop.
 // open3d is not installable here: parity is unpinned, THE RULE IS OWNED HERE and restated in tests/icp_plane_host.py.  The first
@@ -34,7 +35,7 @@
 // point-to-point loop (flags, Kabsch, search, statistics there; sums, step, search, statistics here).
 #include "kernels.h"
 #include "device_utils.h"
-#include "icp_plane.h"
+#include "icp_layout.h"
 
 namespace dsir {
 
@@ -89,9 +90,7 @@ __global__ __launch_bounds__(QB * NW) void icp_nn_kernel(const float* __restrict
     __syncthreads();
     const int cnt = max(0, min(TILE, s_end - (s_begin + t0)));
     for (int j = 0; j < cnt; ++j) {
-      const float4 s = tile[w][j];
-      const float dx = __fsub_rn(s.x, qx), dy = __fsub_rn(s.y, qy), dz = __fsub_rn(s.z, qz);
-      const float d = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+      const float d = dist2_rn(tile[w][j], qx, qy, qz);
       if (d < bd) { bd = d; bi = s_begin + t0 + j; }
     }
     __syncthreads();
@@ -290,126 +289,103 @@ __global__ void icp_stats5_kernel(const double* __restrict__ state, const double
   out[(int64_t)p * 5 + 4] = nsing ? nsing[p] : 0.0;
 }
 
+// the loop's scratch as pointers: IcpLayout's parts
+struct IcpParts {
+  float* cur; int32_t* idx; float* d2; float* w; float* Ta; float* Tb; double* state; int32_t* skip; float* Tstep;
+  double* part; double* nsing; void* grid;
+  IcpParts(const IcpLayout& l, void* scratch, bool plane) {
+    char* b = reinterpret_cast<char*>(scratch);
+    cur = reinterpret_cast<float*>(b + l.cur); idx = reinterpret_cast<int32_t*>(b + l.idx); d2 = reinterpret_cast<float*>(b + l.d2);
+    w = reinterpret_cast<float*>(b + l.w); Ta = reinterpret_cast<float*>(b + l.Ta); Tb = reinterpret_cast<float*>(b + l.Tb);
+    state = reinterpret_cast<double*>(b + l.state); skip = reinterpret_cast<int32_t*>(b + l.skip);
+    Tstep = reinterpret_cast<float*>(b + l.Tstep);
+    part = plane ? reinterpret_cast<double*>(b + l.part) : nullptr;
+    nsing = plane ? reinterpret_cast<double*>(b + l.nsing) : nullptr;
+    grid = b + l.grid;
+  }
+};
+
+size_t grid_bytes(const IcpArgs& a) { return a.search != IcpSearch::Brute ? icp_grid_scratch_bytes(a.pairs, a.J, a.K) : 0; }
+IcpLayout layout(const IcpArgs& a) { return IcpLayout(a.pairs, a.J, a.estimator == 1, grid_bytes(a)); }
+
+// the point-to-point update: the pairs' done flags, then Kabsch on the correspondences (moves cur, composes Tn = step o Tp)
+void step_point(const IcpArgs& a, const IcpParts& s, const float* Tp, float* Tn, hipStream_t st) {
+  hipLaunchKernelGGL(icp_done_flags_kernel, dim3((a.pairs + 255) / 256), dim3(256), 0, st, s.state, a.pairs, s.skip);
+  KabschArgs k{};
+  k.src = s.cur; k.ref = a.ref; k.idx = s.idx; k.w = s.w; k.src_stride = (int64_t)a.J * 3; k.ref_stride = (int64_t)a.K * a.stride;
+  k.ref_ld = a.stride; k.sigmoid = 0; k.pairs = a.pairs; k.m = a.J; k.T = s.Tstep; k.invalid = nullptr;
+  k.src_out = s.cur; k.src_out_stride = (int64_t)a.J * 3; k.T_prev = Tp; k.T_cum = Tn; k.T_stride = 12; k.skip = s.skip;
+  launch_kabsch(k, st);
+}
+
+// the point-to-plane update: the chunks' sums, then the solve and the move (its first workgroup composes Tn and writes the flags)
+void step_plane(const IcpArgs& a, const IcpParts& s, const float* Tp, float* Tn, hipStream_t st) {
+  const int nch = icp_plane_chunks(a.J);
+  hipLaunchKernelGGL(icp_plane_accum_kernel, dim3(nch, a.pairs), dim3(PT), 0, st, (const float*)s.cur, a.ref, a.stride,
+                     PlaneNormals{a.normals, a.normals_cs, a.normals_ld}, (const int32_t*)s.idx, (const float*)s.w, a.J, a.K,
+                     (const double*)s.state, s.part);
+  hipLaunchKernelGGL(icp_plane_step_kernel, dim3((a.J + PT - 1) / PT, a.pairs), dim3(PT), 0, st, s.cur, a.J, nch, (const double*)s.part,
+                     (const double*)s.state, Tp, Tn, s.nsing, s.skip);
+}
+
+// the search of cur [pairs][J][3]: the grid's kernel with an index (built by the caller), else the brute force
+void search(const IcpArgs& a, const IcpGrid* grid, const float* cur, float r2, int32_t* idx, float* d2, const int32_t* skip, hipStream_t st) {
+  if (grid) { launch_icp_nn_grid(*grid, cur, a.pairs, a.J, a.K, r2, idx, d2, skip, st); return; }
+  hipLaunchKernelGGL(icp_nn_kernel, dim3((a.J + QB - 1) / QB, a.pairs), dim3(QB * NW), 0, st, cur, a.ref, a.stride, a.J, a.K, r2, idx, d2, skip);
+}
+
 }  // namespace
 
-size_t icp_scratch_bytes(int pairs, int J) {
-  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  return al((size_t)pairs * J * 12) + 3 * al((size_t)pairs * J * 4) + 2 * al((size_t)pairs * 48) + al((size_t)pairs * 32) +
-         al((size_t)pairs * 4) + al((size_t)pairs * 48);
-}
+size_t icp_scratch_bytes(const IcpArgs& a) { return layout(a).bytes; }
 
-size_t icp_scratch_bytes_ex(int pairs, int J, int estimator) {
-  return icp_scratch_bytes(pairs, J) + (estimator == 1 ? icp_plane_extra_bytes(pairs, J) : 0);
-}
-
-// T_init / T_out [pairs][3][4]; stats_out [pairs][4] doubles {fitness, inlier_rmse, converged, iterations} or nullptr
-void launch_icp_refine(const float* src, const float* ref, int pairs, int J, int K, int stride, float max_corr_dist,
-                       int max_iter, float rel_fitness, float rel_rmse, const float* T_init, float* T_out,
-                       double* stats_out, void* scratch, hipStream_t st) {
-  launch_icp_refine_ex(src, ref, pairs, J, K, stride, max_corr_dist, max_iter, rel_fitness, rel_rmse, T_init, T_out, stats_out, nullptr,
-                       0, nullptr, 0, 0, scratch, st);
-}
-
-// estimator 0: the point-to-point loop (scratch: icp_scratch_bytes); 1: point-to-plane with the normal of reference point i of a
-// pair at normals + pair * normals_cs + i * normals_ld (scratch: icp_scratch_bytes_ex).  stats5_out [pairs][5] doubles or nullptr.
-void launch_icp_refine_ex(const float* src, const float* ref, int pairs, int J, int K, int stride, float max_corr_dist,
-                          int max_iter, float rel_fitness, float rel_rmse, const float* T_init, float* T_out,
-                          double* stats_out, double* stats5_out, int estimator, const float* normals, int64_t normals_cs,
-                          int normals_ld, void* scratch, hipStream_t st) {
-  launch_icp_refine_ex2(src, ref, pairs, J, K, stride, max_corr_dist, max_iter, rel_fitness, rel_rmse, T_init, T_out, stats_out, stats5_out,
-                        estimator, normals, normals_cs, normals_ld, 0, scratch, st);
-}
-
-size_t icp_scratch_bytes_ex2(int pairs, int J, int K, int estimator, int search) {
-  return icp_scratch_bytes_ex(pairs, J, estimator) + (search != 0 ? icp_grid_scratch_bytes(pairs, J, K) : 0);
-}
-
-// search 0: every launch below is launch_icp_refine_ex's, in its order.  search 1 (2: without the query order): the index of
-// icp_grid.hip is built once after the points are moved by T_init, and the three search sites launch its kernel instead.
-int launch_icp_refine_ex2(const float* src, const float* ref, int pairs, int J, int K, int stride, float max_corr_dist,
-                          int max_iter, float rel_fitness, float rel_rmse, const float* T_init, float* T_out,
-                          double* stats_out, double* stats5_out, int estimator, const float* normals, int64_t normals_cs,
-                          int normals_ld, int search, void* scratch, hipStream_t st) {
-  char* p = reinterpret_cast<char*>(scratch);
-  auto take = [&](size_t bytes) { char* r = p; p += (bytes + 255) & ~(size_t)255; return r; };
-  float* cur = reinterpret_cast<float*>(take((size_t)pairs * J * 12));
-  int32_t* idx = reinterpret_cast<int32_t*>(take((size_t)pairs * J * 4));
-  float* d2 = reinterpret_cast<float*>(take((size_t)pairs * J * 4));
-  float* w = reinterpret_cast<float*>(take((size_t)pairs * J * 4));
-  float* Ta = reinterpret_cast<float*>(take((size_t)pairs * 48));
-  float* Tb = reinterpret_cast<float*>(take((size_t)pairs * 48));
-  double* state = reinterpret_cast<double*>(take((size_t)pairs * 32));
-  int32_t* skip = reinterpret_cast<int32_t*>(take((size_t)pairs * 4));
-  float* Tstep = reinterpret_cast<float*>(take((size_t)pairs * 48));
-  const bool plane = estimator == 1;
-  const int nch = icp_plane_chunks(J);
-  double* part = plane ? reinterpret_cast<double*>(take(icp_plane_part_bytes(pairs, J))) : nullptr;
-  double* nsing = plane ? reinterpret_cast<double*>(take((size_t)pairs * 8)) : nullptr;
-  void* grid_scratch = search != 0 ? take(icp_grid_scratch_bytes(pairs, J, K)) : nullptr;
-  if (plane) hipMemsetAsync(nsing, 0, (size_t)pairs * 8, st);
-  const float r2 = max_corr_dist * max_corr_dist;
-  hipMemsetAsync(state, 0, (size_t)pairs * 32, st);
-  hipMemcpyAsync(Ta, T_init, (size_t)pairs * 48, hipMemcpyDeviceToDevice, st);
-  const dim3 gj((J + 255) / 256, pairs), gq((J + QB - 1) / QB, pairs);
-  hipLaunchKernelGGL(icp_apply_kernel, gj, dim3(256), 0, st, src, stride, J, Ta, cur);
+// The first search under T_init, then max_iter times: the estimator's step, the search, the statistics with the convergence test.
+// With a cell index (search != Brute) it is built once after the points are moved by T_init and serves every search.
+int launch_icp_refine(const IcpArgs& a, void* scratch, hipStream_t st) {
+  const bool plane = a.estimator == 1;
+  const IcpParts s(layout(a), scratch, plane);
+  const int pairs = a.pairs, J = a.J;
+  if (plane) hipMemsetAsync(s.nsing, 0, (size_t)pairs * 8, st);
+  const float r2 = a.max_corr_dist * a.max_corr_dist;
+  hipMemsetAsync(s.state, 0, (size_t)pairs * 32, st);
+  hipMemcpyAsync(s.Ta, a.T_init, (size_t)pairs * 48, hipMemcpyDeviceToDevice, st);
+  hipLaunchKernelGGL(icp_apply_kernel, dim3((J + 255) / 256, pairs), dim3(256), 0, st, a.src, a.stride, J, s.Ta, s.cur);
   IcpGrid grid{};
-  if (search != 0)
-    if (const int e = icp_grid_build(ref, stride, cur, pairs, J, K, max_corr_dist, search == 1, grid_scratch, st, &grid)) return e;
-  auto nn = [&](const int32_t* skip_flags) {
-    if (search != 0) { launch_icp_nn_grid(grid, cur, pairs, J, K, r2, idx, d2, skip_flags, st); return; }
-    hipLaunchKernelGGL(icp_nn_kernel, gq, dim3(QB * NW), 0, st, cur, ref, stride, J, K, r2, idx, d2, skip_flags);
-  };
-  nn(nullptr);
-  hipLaunchKernelGGL(icp_stats_kernel, dim3(pairs), dim3(256), 0, st, idx, d2, w, J, 0, rel_fitness, rel_rmse, state);
-  float *Tp = Ta, *Tn = Tb;
-  for (int it = 0; it < max_iter; ++it) {
-    if (plane) {
-      hipLaunchKernelGGL(icp_plane_accum_kernel, dim3(nch, pairs), dim3(PT), 0, st, (const float*)cur, ref, stride,
-                         PlaneNormals{normals, normals_cs, normals_ld}, (const int32_t*)idx, (const float*)w, J, K,
-                         (const double*)state, part);
-      hipLaunchKernelGGL(icp_plane_step_kernel, dim3((J + PT - 1) / PT, pairs), dim3(PT), 0, st, cur, J, nch, (const double*)part,
-                         (const double*)state, (const float*)Tp, Tn, nsing, skip);
-      nn(skip);
-      hipLaunchKernelGGL(icp_stats_kernel, dim3(pairs), dim3(256), 0, st, idx, d2, w, J, 1, rel_fitness, rel_rmse, state);
-      float* t = Tp; Tp = Tn; Tn = t;
-      continue;
-    }
-    hipLaunchKernelGGL(icp_done_flags_kernel, dim3((pairs + 255) / 256), dim3(256), 0, st, state, pairs, skip);
-    KabschArgs a{};
-    a.src = cur; a.ref = ref; a.idx = idx; a.w = w; a.src_stride = (int64_t)J * 3; a.ref_stride = (int64_t)K * stride;
-    a.ref_ld = stride; a.sigmoid = 0; a.pairs = pairs; a.m = J; a.T = Tstep; a.invalid = nullptr;
-    a.src_out = cur; a.src_out_stride = (int64_t)J * 3; a.T_prev = Tp; a.T_cum = Tn; a.T_stride = 12; a.skip = skip;
-    launch_kabsch(a, st);
-    nn(skip);
-    hipLaunchKernelGGL(icp_stats_kernel, dim3(pairs), dim3(256), 0, st, idx, d2, w, J, 1, rel_fitness, rel_rmse, state);
+  const IcpGrid* g = a.search != IcpSearch::Brute ? &grid : nullptr;
+  if (g)
+    if (const int e = icp_grid_build(a.ref, a.stride, s.cur, pairs, J, a.K, a.max_corr_dist, a.search == IcpSearch::Grid, s.grid, st, &grid)) return e;
+  search(a, g, s.cur, r2, s.idx, s.d2, nullptr, st);
+  hipLaunchKernelGGL(icp_stats_kernel, dim3(pairs), dim3(256), 0, st, s.idx, s.d2, s.w, J, 0, a.rel_fitness, a.rel_rmse, s.state);
+  float *Tp = s.Ta, *Tn = s.Tb;
+  for (int it = 0; it < a.max_iter; ++it) {
+    if (plane) step_plane(a, s, Tp, Tn, st);
+    else step_point(a, s, Tp, Tn, st);
+    search(a, g, s.cur, r2, s.idx, s.d2, s.skip, st);
+    hipLaunchKernelGGL(icp_stats_kernel, dim3(pairs), dim3(256), 0, st, s.idx, s.d2, s.w, J, 1, a.rel_fitness, a.rel_rmse, s.state);
     float* t = Tp; Tp = Tn; Tn = t;
   }
-  hipMemcpyAsync(T_out, Tp, (size_t)pairs * 48, hipMemcpyDeviceToDevice, st);
-  if (stats_out) hipMemcpyAsync(stats_out, state, (size_t)pairs * 32, hipMemcpyDeviceToDevice, st);
-  if (stats5_out) hipLaunchKernelGGL(icp_stats5_kernel, dim3((pairs + 255) / 256), dim3(256), 0, st, (const double*)state, (const double*)nsing, pairs, stats5_out);
+  hipMemcpyAsync(a.T_out, Tp, (size_t)pairs * 48, hipMemcpyDeviceToDevice, st);
+  if (a.stats_out) hipMemcpyAsync(a.stats_out, s.state, (size_t)pairs * 32, hipMemcpyDeviceToDevice, st);
+  if (a.stats5_out)
+    hipLaunchKernelGGL(icp_stats5_kernel, dim3((pairs + 255) / 256), dim3(256), 0, st, (const double*)s.state, (const double*)s.nsing, pairs,
+                       a.stats5_out);
   return 0;
 }
 
-size_t icp_corr_scratch_bytes(int pairs, int J, int K, int search) {
-  return (((size_t)pairs * J * 12 + 255) & ~(size_t)255) + (search != 0 ? icp_grid_scratch_bytes(pairs, J, K) : 0);
-}
+size_t icp_corr_scratch_bytes(const IcpArgs& a) { return IcpCorrLayout(a.pairs, a.J, grid_bytes(a)).bytes; }
 
-// one search step under T: the apply and the search of the loop's first three launches, and their statistics
-int launch_icp_correspondences(const float* src, const float* ref, int pairs, int J, int K, int stride, float max_corr_dist, const float* T,
-                               int search, int32_t* idx_out, float* d2_out, double* stats_out, void* scratch, hipStream_t st) {
-  float* cur = reinterpret_cast<float*>(scratch);
-  void* grid_scratch = reinterpret_cast<char*>(scratch) + (((size_t)pairs * J * 12 + 255) & ~(size_t)255);
-  const float r2 = max_corr_dist * max_corr_dist;
-  hipLaunchKernelGGL(icp_apply_kernel, dim3((J + 255) / 256, pairs), dim3(256), 0, st, src, stride, J, T, cur);
-  if (search != 0) {
-    IcpGrid grid{};
-    if (const int e = icp_grid_build(ref, stride, cur, pairs, J, K, max_corr_dist, search == 1, grid_scratch, st, &grid)) return e;
-    launch_icp_nn_grid(grid, cur, pairs, J, K, r2, idx_out, d2_out, nullptr, st);
-  } else {
-    hipLaunchKernelGGL(icp_nn_kernel, dim3((J + QB - 1) / QB, pairs), dim3(QB * NW), 0, st, (const float*)cur, ref, stride, J, K, r2, idx_out,
-                       d2_out, (const int32_t*)nullptr);
-  }
-  if (stats_out) hipLaunchKernelGGL(icp_corr_stats_kernel, dim3(pairs), dim3(256), 0, st, (const int32_t*)idx_out, (const float*)d2_out, J, stats_out);
+// one search step under a.T_init: the apply and the search of the loop's first three launches, and their statistics
+int launch_icp_correspondences(const IcpArgs& a, int32_t* idx_out, float* d2_out, double* stats_out, void* scratch, hipStream_t st) {
+  const IcpCorrLayout l(a.pairs, a.J, grid_bytes(a));
+  float* cur = reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) + l.cur);
+  hipLaunchKernelGGL(icp_apply_kernel, dim3((a.J + 255) / 256, a.pairs), dim3(256), 0, st, a.src, a.stride, a.J, a.T_init, cur);
+  IcpGrid grid{};
+  const IcpGrid* g = a.search != IcpSearch::Brute ? &grid : nullptr;
+  if (g)
+    if (const int e = icp_grid_build(a.ref, a.stride, cur, a.pairs, a.J, a.K, a.max_corr_dist, a.search == IcpSearch::Grid,
+                                     reinterpret_cast<char*>(scratch) + l.grid, st, &grid))
+      return e;
+  search(a, g, cur, a.max_corr_dist * a.max_corr_dist, idx_out, d2_out, nullptr, st);
+  if (stats_out) hipLaunchKernelGGL(icp_corr_stats_kernel, dim3(a.pairs), dim3(256), 0, st, (const int32_t*)idx_out, (const float*)d2_out, a.J, stats_out);
   return 0;
 }
 

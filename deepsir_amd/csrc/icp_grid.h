@@ -14,7 +14,7 @@ constexpr double kIcpGridMargin = 1.0 + 1.0 / 1024.0;   // cell edge over radius
 constexpr double kIcpGridMinEdge = 0x1p-60;              // floor of the edge: covers a radius whose fp32 square underflows
 constexpr double kIcpGridMaxCells = 1048576.0;           // 2^20: cells the longest axis may span, so c + 1 fits a key's 21 bits
 
-struct IcpLattice { double ox, oy, oz, h; };             // one per pair, in device memory
+using IcpLattice = CellLattice;                          // one per pair, in device memory
 
 // h = max(r (1 + 2^-10), 2^-60, longest axis extent / 2^20) in fp64
 DSIR_CELL_HD double icp_grid_cell_edge(float r, double extent) {
@@ -52,22 +52,21 @@ struct IcpGridLayout {
   size_t lat, enc, off_ref, off_qry, keys, sorted, perm, keys_raw, vals_raw, vals, keys_qry, tmp, tmp_bytes, bytes;
   IcpGridLayout(int pairs, int J, int K, size_t sort_tmp_bytes) {
     const size_t P = (size_t)pairs, nj = P * (size_t)J, nk = P * (size_t)K, nm = nj > nk ? nj : nk;
-    size_t p = 0;
-    auto take = [&](size_t b) { const size_t at = p; p += (b + 255) & ~(size_t)255; return at; };
-    lat = take(P * sizeof(IcpLattice));
-    enc = take(P * 6 * sizeof(uint32_t));          // [3 P] minima, then [3 P] maxima, as ordered integers
-    off_ref = take((P + 1) * sizeof(int32_t));     // p K
-    off_qry = take((P + 1) * sizeof(int32_t));     // p J
-    keys = take(nk * sizeof(uint64_t));            // the reference keys, sorted per pair
-    sorted = take(nk * 16);                        // (x, y, z, original index) in key order
-    perm = take(nj * sizeof(int32_t));             // the queries in cell order
-    keys_raw = take(nm * sizeof(uint64_t));
-    vals_raw = take(nm * sizeof(uint32_t));
-    vals = take(nk * sizeof(uint32_t));
-    keys_qry = take(nj * sizeof(uint64_t));
+    Carve c;
+    lat = c.take(P * sizeof(IcpLattice));
+    enc = c.take(P * 6 * sizeof(uint32_t));          // [3 P] minima, then [3 P] maxima, as ordered integers
+    off_ref = c.take((P + 1) * sizeof(int32_t));     // p K
+    off_qry = c.take((P + 1) * sizeof(int32_t));     // p J
+    keys = c.take(nk * sizeof(uint64_t));            // the reference keys, sorted per pair
+    sorted = c.take(nk * 16);                        // (x, y, z, original index) in key order
+    perm = c.take(nj * sizeof(int32_t));             // the queries in cell order
+    keys_raw = c.take(nm * sizeof(uint64_t));
+    vals_raw = c.take(nm * sizeof(uint32_t));
+    vals = c.take(nk * sizeof(uint32_t));
+    keys_qry = c.take(nj * sizeof(uint64_t));
     tmp_bytes = sort_tmp_bytes;
-    tmp = take(tmp_bytes < 256 ? 256 : tmp_bytes);
-    bytes = p;
+    tmp = c.take(tmp_bytes < 256 ? 256 : tmp_bytes);
+    bytes = c.p;
   }
 };
 

@@ -1,7 +1,8 @@
 // Cell-indexed nearest neighbour for the ICP loop (icp.hip, search = 1): the same neighbour index and the same d2 bits as the brute
 // force of icp_nn_kernel, from a sparse cell index of the reference cloud that is built once per call and searched up to
 // max_iter + 1 times.  The index is overlap.hip's (points sorted by a 64-bit cell key, 27 cells around the query; csrc/cell_index.h
-// holds what both files share); what differs is the rule's `<=` and a lattice that is made per pair on the device.
+// holds what both files share: CellLattice, point_key, the bounds accumulation, key_lower_bound, walk_key_intervals, dist2_rn);
+// what differs is the rule's `<=` and a lattice that is made per pair on the device.
 //
 // The rule (header of icp.hip, unchanged):
 //     d = ref - cur,  d2 = (dx dx + dy dy) + dz dz        fp32, every operation rounded on its own
@@ -14,14 +15,12 @@
 // (integer atomics on the order-preserving map of cell_index.h: order-independent), cell edge
 //     h = max(r (1 + 2^-10), 2^-60, longest axis extent / 2^20)      in fp64 (csrc/icp_grid.h, restated in deepsir_amd/icp.py)
 // cell coordinate c(a) = floor(((double)a - (double)o) / h) per axis.  Why no reference point b that the rule accepts for a query a
-// can lie outside the 27 cells around c(a), restated for `<=`: every term of d2 is non-negative and rounding is monotone, so
-// fl(dx dx) <= d2 <= fl(r r), hence dx^2 <= r^2 (1 + 2^-24) / (1 - 2^-24) and, dx = fl(b - a) being within 2^-24 of b - a,
-// |b - a| <= r (1 + 2^-21) per axis in exact arithmetic - the bound of the strict rule with <= in place of <.  The margin takes it up:
-// |b - a| / h <= (1 + 2^-21) / (1 + 2^-10) < 1 - 2^-11, strictly, for every h >= r (1 + 2^-10); a coarser h only lowers the quotient.
+// can lie outside the 27 cells around c(a): the argument of csrc/cell_index.h with `<=` - fl(dx dx) <= d2 <= fl(r r) gives
+// |b - a| <= r (1 + 2^-21) per axis, and |b - a| / h <= (1 + 2^-21) / (1 + 2^-10) < 1 - 2^-11 stays strict for every h >= r (1 + 2^-10);
+// a coarser h only lowers the quotient.
 // Where products underflow (fl(r r) or fl(dx dx) below 2^-126) the relative bounds do not hold; then dx^2 < 2^-126 + 2^-149 + r2,
 // so for r < 2^-61 |dx| < 2^-60 = the floor of h, and for r >= 2^-61 r r is a normal number and an underflowing dx dx has
-// |dx| < 2^-63 < r.  The fp64 subtraction and division carry a relative error of 2^-52 on quotients below 2^21 + 2 (the clamp of
-// cell_of), less than 2^-29 absolute: the two computed quotients differ by less than 1 and their floors by at most 1.  The third term
+// |dx| < 2^-63 < r.  The coarsened edge in place of a refused extent: the third term
 // of h bounds a reference coordinate by 2^20 (extent / h <= 2^20 (1 + 2^-52)), so c + 1 fits the 21 bits an axis has in the key
 // x | y << 21 | z << 42 and NO EXTENT IS REFUSED: a far-flung cloud gets coarser cells, a slower and still exact search.  A query that
 // T has moved out of the lattice is clamped to -2 or 2^21 + 1 cells: more than one cell from every reference cell, and h >= the
@@ -67,20 +66,8 @@ constexpr int SEG_MAX = 4095;   // longer segments are sorted pair by pair with 
 __global__ __launch_bounds__(256) void icp_grid_bounds_kernel(const float* __restrict__ ref, int stride, int K, int pairs,
                                                               uint32_t* __restrict__ enc) {
   const int pair = blockIdx.y;
-  const float* S = ref + (int64_t)pair * K * stride;
-  uint32_t lo[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, hi[3] = {0u, 0u, 0u};
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < K; i += gridDim.x * blockDim.x) {
-    const float* p = S + (int64_t)i * stride;
-    const float v[3] = {p[0], p[1], p[2]};
-    if (!finite3(v[0], v[1], v[2])) continue;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) { const uint32_t o = f2ord(v[a]); lo[a] = min(lo[a], o); hi[a] = max(hi[a], o); }
-  }
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    for (int s = 32; s > 0; s >>= 1) { lo[a] = min(lo[a], (uint32_t)__shfl_xor((int)lo[a], s)); hi[a] = max(hi[a], (uint32_t)__shfl_xor((int)hi[a], s)); }
-    if ((threadIdx.x & 63) == 0) { atomicMin(enc + pair * 3 + a, lo[a]); atomicMax(enc + (pairs + pair) * 3 + a, hi[a]); }
-  }
+  finite_bounds_accumulate(ref + (int64_t)pair * K * stride, stride, K, (int64_t)blockIdx.x * blockDim.x + threadIdx.x,
+                           (int64_t)gridDim.x * blockDim.x, enc + pair * 3, enc + (pairs + pair) * 3);
 }
 
 // the pair's lattice (icp_grid.h) and both offset tables of the segmented sorts
@@ -109,14 +96,7 @@ __global__ __launch_bounds__(256) void icp_grid_key_kernel(const float* __restri
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
     const int64_t o = (int64_t)pair * n + i;
     const float* p = pts + o * stride;
-    const float x = p[0], y = p[1], z = p[2];
-    uint64_t k = KEY_NONE;
-    if (finite3(x, y, z)) {
-      const int cx = min(max(cell_of(x, L.ox, L.h), 0), MAXC), cy = min(max(cell_of(y, L.oy, L.h), 0), MAXC),
-                cz = min(max(cell_of(z, L.oz, L.h), 0), MAXC);
-      k = cell_key(cx, cy, cz);
-    }
-    keys[o] = k;
+    keys[o] = point_key(p[0], p[1], p[2], L);
     vals[o] = (uint32_t)i;
   }
 }
@@ -153,39 +133,28 @@ __global__ __launch_bounds__(GB) void icp_nn_grid_kernel(const float* __restrict
     const int cx = cell_of(x, L.ox, L.h), cy = cell_of(y, L.oy, L.h), cz = cell_of(z, L.oz, L.h);
     const uint64_t* Kk = keys + (int64_t)pair * K;
     const float4* S = sorted + (int64_t)pair * K;
-    const int x0 = max(cx - 1, 0), x1 = min(cx + 1, MAXC);
-    for (int dz = -1; dz <= 1; ++dz) {
-      const int zz = cz + dz;
-      if (zz < 0 || zz > MAXC || x1 < x0) continue;
-      for (int dy = -1; dy <= 1; ++dy) {
-        const int yy = cy + dy;
-        if (yy < 0 || yy > MAXC) continue;
-        const uint64_t klo = cell_key(x0, yy, zz), khi = cell_key(x1, yy, zz);
-        int lo = 0, hi = K;                                        // the first position whose key is >= klo
-        while (lo < hi) { const int mid = lo + ((hi - lo) >> 1); if (Kk[mid] < klo) lo = mid + 1; else hi = mid; }
-        // lane `sub` of the group takes positions lo + sub, lo + sub + SUB, ..: the group's loads are SUB neighbouring rows
-        for (int64_t i = (int64_t)lo + sub; i < K; i += UNROLL * SUB) {
-          uint64_t k[UNROLL];
-          float4 s[UNROLL];
+    walk_key_intervals(cx, cy, cz, -1, MAXC + 1, -1, MAXC + 1, [&](uint64_t klo, uint64_t khi) {
+      // lane `sub` of the group takes positions lo + sub, lo + sub + SUB, ..: the group's loads are SUB neighbouring rows
+      for (int64_t i = (int64_t)key_lower_bound(Kk, K, klo) + sub; i < K; i += UNROLL * SUB) {
+        uint64_t k[UNROLL];
+        float4 s[UNROLL];
 #pragma unroll
-          for (int u = 0; u < UNROLL; ++u) {
-            const int64_t ii = min(i + (int64_t)u * SUB, (int64_t)K - 1);                              // never past the pair's K
-            k[u] = Kk[ii]; s[u] = S[ii];
-          }
-          bool more = true;
-#pragma unroll
-          for (int u = 0; u < UNROLL; ++u) {
-            const bool in = i + (int64_t)u * SUB < K && k[u] <= khi;   // keys ascend: the first position outside ends the lane's run
-            more = more && in;
-            const float ex = __fsub_rn(s[u].x, x), ey = __fsub_rn(s[u].y, y), ez = __fsub_rn(s[u].z, z);
-            const float e2 = __fadd_rn(__fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey)), __fmul_rn(ez, ez));
-            const int ti = (int)__float_as_uint(s[u].w);
-            if (more && e2 <= r2 && (e2 < bd || (e2 == bd && ti < bi))) { bd = e2; bi = ti; }
-          }
-          if (!more) break;
+        for (int u = 0; u < UNROLL; ++u) {
+          const int64_t ii = min(i + (int64_t)u * SUB, (int64_t)K - 1);                              // never past the pair's K
+          k[u] = Kk[ii]; s[u] = S[ii];
         }
+        bool more = true;
+#pragma unroll
+        for (int u = 0; u < UNROLL; ++u) {
+          const bool in = i + (int64_t)u * SUB < K && k[u] <= khi;   // keys ascend: the first position outside ends the lane's run
+          more = more && in;
+          const float e2 = dist2_rn(s[u], x, y, z);
+          const int ti = (int)__float_as_uint(s[u].w);
+          if (more && e2 <= r2 && (e2 < bd || (e2 == bd && ti < bi))) { bd = e2; bi = ti; }
+        }
+        if (!more) break;
       }
-    }
+    });
   }
   // the group's best by (d2, original index): a minimum, so the order of the exchange does not matter
 #pragma unroll
@@ -201,13 +170,6 @@ __global__ __launch_bounds__(GB) void icp_nn_grid_kernel(const float* __restrict
 }
 
 inline unsigned blocks_for(int n) { const int g = (n + 255) / 256; return (unsigned)(g < 1 ? 1 : (g > 1024 ? 1024 : g)); }
-
-size_t seg_sort_tmp_bytes(int64_t total, int segments) {
-  size_t b = 0;
-  hipcub::DeviceSegmentedRadixSort::SortPairs(nullptr, b, (const uint64_t*)nullptr, (uint64_t*)nullptr, (const uint32_t*)nullptr,
-                                              (uint32_t*)nullptr, (int)total, segments, (const int32_t*)nullptr, (const int32_t*)nullptr);
-  return b;
-}
 
 size_t dev_sort_tmp_bytes(int n) {
   size_t b = 0;
@@ -239,6 +201,13 @@ bool sort_pairs(void* tmp, size_t tmp_bytes, const uint64_t* kin, uint64_t* kout
 }
 
 }  // namespace
+
+size_t seg_sort_tmp_bytes(int64_t total, int segments) {
+  size_t b = 0;
+  hipcub::DeviceSegmentedRadixSort::SortPairs(nullptr, b, (const uint64_t*)nullptr, (uint64_t*)nullptr, (const uint32_t*)nullptr,
+                                              (uint32_t*)nullptr, (int)total, segments, (const int32_t*)nullptr, (const int32_t*)nullptr);
+  return b;
+}
 
 size_t icp_grid_scratch_bytes(int pairs, int J, int K) {
   if (!icp_grid_shape_ok(pairs, J, K)) return 0;

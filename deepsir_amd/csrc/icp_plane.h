@@ -30,7 +30,7 @@ constexpr double kIcpPlanePivotMin = 1e-10;
 
 DSIR_HD inline int icp_plane_chunks(int J) { return J <= 0 ? 0 : (int)(((int64_t)J + kIcpPlaneChunk - 1) / kIcpPlaneChunk); }
 
-// scratch the plane estimator needs beyond icp_scratch_bytes(pairs, J): partials [pairs][chunks][kIcpPlaneSlots] doubles, then the
+// scratch the plane estimator needs beyond the point-to-point loop's parts (IcpLayout, icp_layout.h): partials [pairs][chunks][kIcpPlaneSlots] doubles, then the
 // identity-update counters [pairs] doubles; both pieces padded to 256 bytes.  0 for shapes that are not positive.
 inline size_t icp_plane_part_bytes(int pairs, int J) {
   if (pairs < 1 || J < 1) return 0;

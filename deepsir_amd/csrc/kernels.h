@@ -505,30 +505,30 @@ constexpr int kKabschChunkedMin = 16384;
 size_t kabsch_part_bytes(int pairs, int m, int chunk_min = 0);   // 0 below the threshold
 void launch_kabsch(const KabschArgs& a, hipStream_t st);
 
-// icp.hip — point-to-point ICP refinement (test.py:241-258 / open3d registration_icp), all pairs at once
-size_t icp_scratch_bytes(int pairs, int J);
-void launch_icp_refine(const float* src, const float* ref, int pairs, int J, int K, int stride, float max_corr_dist,
-                       int max_iter, float rel_fitness, float rel_rmse, const float* T_init, float* T_out,
-                       double* stats_out, void* scratch, hipStream_t st);
-// the same loop with the estimator chosen (0 point-to-point, 1 point-to-plane: the rule is stated in icp.hip's header) and stats of
-// five columns; icp_scratch_bytes_ex(.., 0) == icp_scratch_bytes(..)
-size_t icp_scratch_bytes_ex(int pairs, int J, int estimator);
-void launch_icp_refine_ex(const float* src, const float* ref, int pairs, int J, int K, int stride, float max_corr_dist,
-                          int max_iter, float rel_fitness, float rel_rmse, const float* T_init, float* T_out,
-                          double* stats_out, double* stats5_out, int estimator, const float* normals, int64_t normals_cs,
-                          int normals_ld, void* scratch, hipStream_t st);
-// the same loop with the search chosen: 0 = the brute force of icp_nn_kernel (launch_icp_refine_ex's sequence, untouched), 1 = the cell
-// index of icp_grid.hip (same neighbour, same d2 bits: the whole loop is byte for byte the brute-force loop's), 2 = 1 without the
-// query order (a measurement hook, not reachable through the C ABI's argument).  Returns 0 or a HIP error of the index build.
-size_t icp_scratch_bytes_ex2(int pairs, int J, int K, int estimator, int search);
-int launch_icp_refine_ex2(const float* src, const float* ref, int pairs, int J, int K, int stride, float max_corr_dist,
-                          int max_iter, float rel_fitness, float rel_rmse, const float* T_init, float* T_out,
-                          double* stats_out, double* stats5_out, int estimator, const float* normals, int64_t normals_cs,
-                          int normals_ld, int search, void* scratch, hipStream_t st);
-// one search step under pose T [pairs][3][4]: idx_out [pairs][J] (-1: none), d2_out [pairs][J], stats_out [pairs][2] {fitness, inlier_rmse}
-size_t icp_corr_scratch_bytes(int pairs, int J, int K, int search);
-int launch_icp_correspondences(const float* src, const float* ref, int pairs, int J, int K, int stride, float max_corr_dist, const float* T,
-                               int search, int32_t* idx_out, float* d2_out, double* stats_out, void* scratch, hipStream_t st);
+// icp.hip — ICP refinement (test.py:241-258 / open3d registration_icp), all pairs at once; the rules are stated in the file's header
+enum class IcpSearch : int {
+  Brute = 0,           // the exact fp32 brute force of icp_nn_kernel
+  Grid = 1,            // the cell index of icp_grid.hip: same neighbour, same d2 bits, so the whole loop is byte for byte the brute one's
+  GridUnordered = 2,   // Grid without the query order: a measurement hook, not reachable through the C ABI's argument
+};
+struct IcpArgs {
+  const float* src; const float* ref;   // [pairs][J][stride], [pairs][K][stride]
+  int pairs, J, K, stride;
+  float max_corr_dist; int max_iter; float rel_fitness, rel_rmse;
+  const float* T_init; float* T_out;    // [pairs][3][4]
+  int estimator;                        // 0 point-to-point, 1 point-to-plane
+  const float* normals;                 // estimator 1: the normal of reference point i of a pair at normals + pair * normals_cs + i * normals_ld
+  int64_t normals_cs; int normals_ld;
+  IcpSearch search;
+  double* stats_out;                    // [pairs][4] {fitness, inlier_rmse, converged, iterations} or nullptr
+  double* stats5_out;                   // [pairs][5]: the same, then the identity updates taken for a singular system; or nullptr
+};
+size_t icp_scratch_bytes(const IcpArgs& a);
+int launch_icp_refine(const IcpArgs& a, void* scratch, hipStream_t st);   // 0, or a HIP error of the index build
+// one search step under the pose a.T_init (reads the clouds, the shapes, max_corr_dist and search of `a`): idx_out [pairs][J]
+// (-1: none), d2_out [pairs][J], stats_out [pairs][2] {fitness, inlier_rmse} or nullptr
+size_t icp_corr_scratch_bytes(const IcpArgs& a);
+int launch_icp_correspondences(const IcpArgs& a, int32_t* idx_out, float* d2_out, double* stats_out, void* scratch, hipStream_t st);
 
 // icp_grid.hip - the cell index of the ICP search (the rule, the lattice and the containment argument: the file's header)
 struct IcpGrid { const void* keys; const void* sorted; const int32_t* perm; const void* lat; };

@@ -15,12 +15,10 @@
 //
 // The lattice, one per call: origin o = the minimum over all finite points (the caller's bounds), cell edge h = r (1 + 2^-10) in fp64,
 // cell coordinate c(a) = floor(((double)a - (double)o) / h) per axis, in fp64 from the fp32 values.  Why no b that satisfies the rule
-// can lie outside the 27 cells around c(a): every term of d2 is non-negative and rounding is monotone, so fl(dx dx) <= d2 < fl(r r),
-// hence dx^2 < r^2 (1 + 2^-24) / (1 - 2^-24) and, dx = fl(b - a) being within 2^-24 of b - a, |b - a| < r (1 + 2^-21) per axis in
-// exact arithmetic (a dx dx that underflows has |dx| < 2^-63: smaller still).  So |b - a| / h < (1 + 2^-21) / (1 + 2^-10) < 1 - 2^-11;
-// the fp64 subtraction and division carry a relative error of 2^-52 on coordinates below 2^21, i.e. less than 2^-30 absolute: the two
-// computed quotients differ by less than 1 and their floors by at most 1.  An extent of more than 2^21 - 2 cells on an axis is
-// refused before any launch, so c + 1 still fits the 21 bits an axis has in the key  x | y << 21 | z << 42.
+// can lie outside the 27 cells around c(a): the argument of csrc/cell_index.h with the strict `<` - fl(dx dx) <= d2 < fl(r r) gives
+// |b - a| < r (1 + 2^-21) per axis (a dx dx that underflows has |dx| < 2^-63: smaller still), so |b - a| / h < 1 - 2^-11.  An extent
+// of more than 2^21 - 2 cells on an axis is refused before any launch, so c + 1 still fits the 21 bits an axis has in the key
+// x | y << 21 | z << 42.
 //
 // The index is sparse - workspace linear in the point count, never in the box's cells (a 5 m fragment at 0.03 m spans 5 10^6 cells,
 // a scene has hundreds of fragments): per fragment the points sorted by key (hipCUB segmented radix sort, a library step), xyz and the
@@ -33,7 +31,7 @@
 // or adjacent parts of the target's keys), results written in original numbering.  Per query 9 lookups (dy, dz) in {-1, 0, 1}^2,
 // each the key interval [key(cx - 1), key(cx + 1)]: a binary search (up to 15 dependent global loads at 16384 target points) and a
 // scan of the run.  What bounds it is that latency, about 9 x 15 dependent probes per lane, hidden by occupancy: the build reports
-// 27 VGPRs, 70 SGPRs, no LDS, no scratch, 8 waves per SIMD.  A query whose cell is outside the target's cell box grown by one, and a block
+// 29 VGPRs, 70 SGPRs, no LDS, no scratch, 8 waves per SIMD.  A query whose cell is outside the target's cell box grown by one, and a block
 // whose whole job has disjoint boxes, end without a search.  Jobs are ragged: block -> (job, query block) through a prefix over
 // the jobs' block counts, made on the host with the validation.  Counts meet in integer atomics (order-independent); nothing else
 // is shared, so two runs write the same bytes and a job's bytes do not depend on the rest of the list.
@@ -55,25 +53,11 @@ constexpr int64_t MAX_CELLS = (1ll << 21) - 2;      // per axis
 constexpr int64_t MAX_POINTS = 1ll << 30;
 constexpr int MAX_FRAGMENTS = 1 << 20;
 
-struct Lattice { double ox, oy, oz, h; };
-
 inline double cell_edge(float r) { return (double)r * (1.0 + 1.0 / 1024.0); }
 
 // enc [6]: min xyz, max xyz of the finite rows, as ordered integers (integer atomics: order-independent)
 __global__ void finite_bounds_kernel(const float* __restrict__ pts, int stride, int64_t n, uint32_t* __restrict__ enc) {
-  uint32_t lo[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, hi[3] = {0u, 0u, 0u};
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const float* p = pts + i * stride;
-    const float v[3] = {p[0], p[1], p[2]};
-    if (!finite3(v[0], v[1], v[2])) continue;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) { const uint32_t o = f2ord(v[a]); lo[a] = min(lo[a], o); hi[a] = max(hi[a], o); }
-  }
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    for (int s = 32; s > 0; s >>= 1) { lo[a] = min(lo[a], (uint32_t)__shfl_xor((int)lo[a], s)); hi[a] = max(hi[a], (uint32_t)__shfl_xor((int)hi[a], s)); }
-    if ((threadIdx.x & 63) == 0) { atomicMin(enc + a, lo[a]); atomicMax(enc + 3 + a, hi[a]); }
-  }
+  finite_bounds_accumulate(pts, stride, n, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x, enc, enc + 3);
 }
 __global__ void finite_bounds_decode_kernel(const uint32_t* enc, float* out) {
   const int a = threadIdx.x < 6 ? threadIdx.x : 0;                // enc and out may be the same 24 bytes: read all, then write
@@ -83,20 +67,13 @@ __global__ void finite_bounds_decode_kernel(const uint32_t* enc, float* out) {
 }
 
 // keys [total], vals [total] = the row's index inside its fragment; frag found by binary search over off [F + 1]
-__global__ void nn_key_kernel(const float* __restrict__ pts, int stride, const int32_t* __restrict__ off, int F, int64_t total, Lattice L,
+__global__ void nn_key_kernel(const float* __restrict__ pts, int stride, const int32_t* __restrict__ off, int F, int64_t total, CellLattice L,
                               uint64_t* __restrict__ keys, uint32_t* __restrict__ vals) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     int lo = 0, hi = F;                                            // the last f with off[f] <= i
     while (hi - lo > 1) { const int mid = lo + ((hi - lo) >> 1); if ((int64_t)off[mid] <= i) lo = mid; else hi = mid; }
     const float* p = pts + i * stride;
-    const float x = p[0], y = p[1], z = p[2];
-    uint64_t k = KEY_NONE;
-    if (finite3(x, y, z)) {
-      const int cx = min(max(cell_of(x, L.ox, L.h), 0), MAXC), cy = min(max(cell_of(y, L.oy, L.h), 0), MAXC),
-                cz = min(max(cell_of(z, L.oz, L.h), 0), MAXC);
-      k = cell_key(cx, cy, cz);
-    }
-    keys[i] = k;
+    keys[i] = point_key(p[0], p[1], p[2], L);
     vals[i] = (uint32_t)(i - off[lo]);
   }
 }
@@ -144,7 +121,7 @@ __global__ __launch_bounds__(NN_BLOCK) void nn_within_kernel(const uint64_t* __r
                                                              const int32_t* __restrict__ box, const int32_t* __restrict__ off,
                                                              const int32_t* __restrict__ jobs, const int32_t* __restrict__ blk,
                                                              const int32_t* __restrict__ row, int n_jobs, const float* __restrict__ poses,
-                                                             float r2, Lattice L, int32_t* __restrict__ counts, int32_t* __restrict__ nn) {
+                                                             float r2, CellLattice L, int32_t* __restrict__ counts, int32_t* __restrict__ nn) {
   int jlo = 0, jhi = n_jobs;                                       // the last job with blk[job] <= blockIdx.x: block-uniform
   while (jhi - jlo > 1) { const int mid = jlo + ((jhi - jlo) >> 1); if (blk[mid] <= (int)blockIdx.x) jlo = mid; else jhi = mid; }
   const int job = jlo;
@@ -177,26 +154,15 @@ __global__ __launch_bounds__(NN_BLOCK) void nn_within_kernel(const uint64_t* __r
       if (cx >= tlo[0] && cx <= thi[0] && cy >= tlo[1] && cy <= thi[1] && cz >= tlo[2] && cz <= thi[2]) {
         const uint64_t* K = keys + tb;
         const float4* S = sorted + tb;
-        const int x0 = max(cx - 1, 0), x1 = min(cx + 1, MAXC);
         float best = INFINITY;
-        for (int dz = -1; dz <= 1; ++dz) {
-          const int zz = cz + dz;
-          if (zz < 0 || zz > MAXC || zz <= tlo[2] || zz >= thi[2]) continue;      // tlo / thi are the box grown by one
-          for (int dy = -1; dy <= 1; ++dy) {
-            const int yy = cy + dy;
-            if (yy < 0 || yy > MAXC || yy <= tlo[1] || yy >= thi[1] || x1 < x0) continue;
-            const uint64_t klo = cell_key(x0, yy, zz), khi = cell_key(x1, yy, zz);
-            int lo = 0, hi = nt;                                   // the first position whose key is >= klo
-            while (lo < hi) { const int mid = lo + ((hi - lo) >> 1); if (K[mid] < klo) lo = mid + 1; else hi = mid; }
-            for (int i = lo; i < nt && K[i] <= khi; ++i) {
-              const float4 t = S[i];
-              const float ex = __fsub_rn(t.x, x), ey = __fsub_rn(t.y, y), ez = __fsub_rn(t.z, z);
-              const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey)), __fmul_rn(ez, ez));
-              const int ti = (int)__float_as_uint(t.w);
-              if (d2 < r2 && (d2 < best || (d2 == best && ti < best_i))) { best = d2; best_i = ti; }
-            }
+        walk_key_intervals(cx, cy, cz, tlo[1], thi[1], tlo[2], thi[2], [&](uint64_t klo, uint64_t khi) {   // tlo / thi: the box grown by one
+          for (int i = key_lower_bound(K, nt, klo); i < nt && K[i] <= khi; ++i) {
+            const float4 t = S[i];
+            const float d2 = dist2_rn(t, x, y, z);
+            const int ti = (int)__float_as_uint(t.w);
+            if (d2 < r2 && (d2 < best || (d2 == best && ti < best_i))) { best = d2; best_i = ti; }
           }
-        }
+        });
       }
     }
     if (nn) nn[(int64_t)row[job] + orig] = best_i;
@@ -206,34 +172,7 @@ __global__ __launch_bounds__(NN_BLOCK) void nn_within_kernel(const uint64_t* __r
 }
 
 inline unsigned grid1(int64_t n) { const int64_t g = (n + 255) / 256; return (unsigned)(g < 1 ? 1 : (g > 8192 ? 8192 : g)); }
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-size_t seg_sort_tmp_bytes(int64_t total, int F) {
-  size_t b = 0;
-  hipcub::DeviceSegmentedRadixSort::SortPairs(nullptr, b, (const uint64_t*)nullptr, (uint64_t*)nullptr, (const uint32_t*)nullptr,
-                                              (uint32_t*)nullptr, (int)total, F, (const int32_t*)nullptr, (const int32_t*)nullptr);
-  return b;
-}
-
-// the index's parts inside its one allocation: a function of (total, fragments) alone, shared by _scratch, _build and _within
-struct IndexLayout {
-  size_t keys, sorted, box, off, keys_raw, vals_raw, vals, tmp, tmp_bytes, bytes;
-  IndexLayout(int64_t total, int F) {
-    const size_t n = (size_t)(total < 1 ? 1 : total);
-    size_t p = 0;
-    auto take = [&](size_t b) { const size_t at = p; p += align256(b); return at; };
-    keys = take(n * sizeof(uint64_t));
-    sorted = take(n * sizeof(float4));
-    box = take((size_t)F * 6 * sizeof(int32_t));
-    off = take((size_t)(F + 1) * sizeof(int32_t));
-    keys_raw = take(n * sizeof(uint64_t));
-    vals_raw = take(n * sizeof(uint32_t));
-    vals = take(n * sizeof(uint32_t));
-    tmp_bytes = seg_sort_tmp_bytes(total, F);
-    tmp = take(tmp_bytes < 256 ? 256 : tmp_bytes);
-    bytes = p;
-  }
-};
+inline IndexLayout layout(int64_t total, int F) { return IndexLayout(total, F, seg_sort_tmp_bytes(total, F)); }
 
 inline bool index_shape_ok(int64_t total, int F) { return total >= 0 && total <= MAX_POINTS && F >= 1 && F <= MAX_FRAGMENTS; }
 
@@ -267,7 +206,7 @@ const char* check(const int64_t* offsets, int F, const int32_t* jobs, int64_t n_
   return nullptr;
 }
 
-inline Lattice lattice(const float* bounds, float radius) { return Lattice{(double)bounds[0], (double)bounds[1], (double)bounds[2], cell_edge(radius)}; }
+inline CellLattice lattice(const float* bounds, float radius) { return CellLattice{(double)bounds[0], (double)bounds[1], (double)bounds[2], cell_edge(radius)}; }
 
 }  // namespace
 }  // namespace dsir
@@ -295,7 +234,7 @@ int dsir_t_finite_bounds(void* stream, const float* points, int stride, int64_t 
 
 size_t dsir_t_nn_index_scratch(int64_t total, int fragments) {
   if (!index_shape_ok(total, fragments)) return 0;
-  return IndexLayout(total, fragments).bytes;
+  return layout(total, fragments).bytes;
 }
 
 int dsir_t_nn_index_build(void* stream, const float* points, int stride, const int64_t* offsets, int fragments, float radius,
@@ -304,7 +243,7 @@ int dsir_t_nn_index_build(void* stream, const float* points, int stride, const i
   const int64_t total = offsets[fragments];
   if (total > 0 && !points) return (int)hipErrorInvalidValue;
   hipStream_t st = (hipStream_t)stream;
-  const IndexLayout lay(total, fragments);
+  const IndexLayout lay = layout(total, fragments);
   char* base = reinterpret_cast<char*>(index);
   uint64_t* keys = reinterpret_cast<uint64_t*>(base + lay.keys);
   float4* sorted = reinterpret_cast<float4*>(base + lay.sorted);
@@ -331,7 +270,9 @@ int dsir_t_nn_index_build(void* stream, const float* points, int stride, const i
 
 size_t dsir_t_nn_within_scratch(int64_t n_jobs) {
   if (n_jobs < 0 || n_jobs > 0x3fffffffll) return 0;
-  return align256((size_t)(4 * n_jobs + 2) * sizeof(int32_t));
+  Carve c;
+  c.take((size_t)(4 * n_jobs + 2) * sizeof(int32_t));
+  return c.p;
 }
 
 int dsir_t_nn_within(void* stream, const void* index, const int64_t* offsets, int fragments, const int32_t* jobs, int64_t n_jobs,
@@ -341,7 +282,7 @@ int dsir_t_nn_within(void* stream, const void* index, const int64_t* offsets, in
   if (n_jobs == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
   const int64_t total = offsets[fragments];
-  const IndexLayout lay(total, fragments);
+  const IndexLayout lay = layout(total, fragments);
   const char* base = reinterpret_cast<const char*>(index);
   // jobs [n][2] | blk [n + 1] | row [n + 1]
   std::vector<int32_t> tab((size_t)(4 * n_jobs + 2));

@@ -596,40 +596,23 @@ class Engine:
         P, J, stride = points_src.shape
         K = points_ref.shape[1]
         assert points_ref.shape[0] == P and points_ref.shape[2] == stride and tuple(T_init.shape) == (P, 3, 4)
-        T = self._empty((P, 3, 4))
-        if grid and estimator == "point":
-            stats = self._empty((P, 5), torch.float64)
-            self._pre()
-            self._call(self.lib.dsir_icp_refine_ex2(self.h, _ptr(points_src), _ptr(points_ref), P, J, K, stride, float(max_corr_dist),
-                                                    int(max_iter), float(rel_fitness), float(rel_rmse), _ptr(T_init), _ptr(T), 0,
-                                                    None, 1, _ptr(stats)))
-            self.sync()
-            return T, stats[:, :4].contiguous()
-        if estimator == "point":
-            stats = self._empty((P, 4), torch.float64)
-            self._pre()
-            self._call(self.lib.dsir_icp_refine(self.h, _ptr(points_src), _ptr(points_ref), P, J, K, stride, float(max_corr_dist),
-                                                int(max_iter), float(rel_fitness), float(rel_rmse), _ptr(T_init), _ptr(T), _ptr(stats)))
-            self.sync()
-            return T, stats
-        if normals_ref is not None:
+        plane = self.ICP_ESTIMATORS[estimator]
+        if not plane:
+            normals_ref = None
+        elif normals_ref is not None:
             normals_ref = _chk(normals_ref, torch.float32, "normals_ref")
             if tuple(normals_ref.shape) != (P, K, 3):
                 raise ValueError(f"normals_ref must be [{P}, {K}, 3], got {tuple(normals_ref.shape)}")
         elif stride < 6:
             normals_ref = self.icp_normals(points_ref, viewpoint)
+        T = self._empty((P, 3, 4))
         stats = self._empty((P, 5), torch.float64)
         self._pre()
-        if grid:
-            self._call(self.lib.dsir_icp_refine_ex2(self.h, _ptr(points_src), _ptr(points_ref), P, J, K, stride, float(max_corr_dist),
-                                                    int(max_iter), float(rel_fitness), float(rel_rmse), _ptr(T_init), _ptr(T), 1,
-                                                    _ptr(normals_ref), 1, _ptr(stats)))
-        else:
-            self._call(self.lib.dsir_icp_refine_ex(self.h, _ptr(points_src), _ptr(points_ref), P, J, K, stride, float(max_corr_dist),
-                                                   int(max_iter), float(rel_fitness), float(rel_rmse), _ptr(T_init), _ptr(T), 1,
-                                                   _ptr(normals_ref), _ptr(stats)))
+        self._call(self.lib.dsir_icp_refine_ex2(self.h, _ptr(points_src), _ptr(points_ref), P, J, K, stride, float(max_corr_dist),
+                                                int(max_iter), float(rel_fitness), float(rel_rmse), _ptr(T_init), _ptr(T), plane,
+                                                _ptr(normals_ref), grid, _ptr(stats)))
         self.sync()
-        return T, stats
+        return T, (stats if plane else stats[:, :4].contiguous())
 
     def icp_correspondences(self, points_src, points_ref, T, max_corr_dist: float, search: str = "brute"):
         """open3d evaluate_registration counterpart for P pairs: one search step of icp_refine under the pose T.

@@ -209,6 +209,58 @@ def test_gpu_grid_loop_equals_brute_loop(eng, estimator, max_iter):
         assert st_g[0, 2] == 1.0 and 2 <= st_g[0, 3] < 30                                                # converged early
 
 
+def test_gpu_four_c_entries_agree(eng):
+    """dsir_icp_refine, dsir_icp_refine_ex, dsir_icp_refine_ex2 (search 0 and 1) and dsir_icp_correspondences (search 0 and 1), called
+    through the C ABI on the same input, write the same bytes: P = 2, J = 300 (no multiple of 64 or 256), K = 257 (no multiple of
+    the brute kernel's four support slices), rows of 6 columns whose columns 3..5 carry the normals, max_iter 5."""
+    import torch
+    P, J, K, max_iter = 2, 300, 257, 5
+    cases = [surface_case(J, K, seed) for seed in (7, 9)]
+    src = _dev(np.stack([np.c_[c["src"], np.zeros((J, 3), np.float32)] for c in cases]))
+    ref = _dev(np.stack([np.c_[c["ref"], c["normals"]] for c in cases]))
+    T0 = _dev(np.stack([c["T0"] for c in cases]))
+    assert tuple(src.shape) == (P, J, 6) and tuple(ref.shape) == (P, K, 6)
+
+    def refine(name, cols, *tail):
+        T = torch.zeros((P, 3, 4), dtype=torch.float32, device="cuda")
+        st = torch.full((P, cols), -1.0, dtype=torch.float64, device="cuda")
+        torch.cuda.synchronize()
+        rc = getattr(eng.lib, name)(eng.h, src.data_ptr(), ref.data_ptr(), P, J, K, 6, float(RADIUS), max_iter, 1e-6, 1e-6, T0.data_ptr(),
+                                    T.data_ptr(), *tail, st.data_ptr())
+        eng.sync()
+        assert rc == 0, (name, tail, eng.lib.dsir_last_error(eng.h))
+        return T, T.cpu().numpy(), st.cpu().numpy()
+
+    T_dev, T_ref, st_ref = refine("dsir_icp_refine", 4)
+    print(f"ENTRIES point: stats {st_ref.tolist()}")
+    assert (st_ref[:, 0] > 0).all() and np.isfinite(T_ref).all()                                # not a comparison of empty sets
+    for name, tail in (("dsir_icp_refine_ex", (0, None)), ("dsir_icp_refine_ex2", (0, None, 0)), ("dsir_icp_refine_ex2", (0, None, 1))):
+        _, T, st = refine(name, 5, *tail)
+        assert T.tobytes() == T_ref.tobytes() and st[:, :4].tobytes() == st_ref.tobytes(), (name, tail)
+    _, T_pl, st_pl = refine("dsir_icp_refine_ex", 5, 1, None)
+    print(f"ENTRIES plane: stats {st_pl.tolist()}")
+    assert (st_pl[:, 0] > 0).all() and np.isfinite(T_pl).all()
+    for search in (0, 1):
+        _, T, st = refine("dsir_icp_refine_ex2", 5, 1, None, search)
+        assert T.tobytes() == T_pl.tobytes() and st.tobytes() == st_pl.tobytes(), search
+
+    def corr(search):
+        idx = torch.full((P, J), -7, dtype=torch.int32, device="cuda")
+        d2 = torch.full((P, J), -1.0, dtype=torch.float32, device="cuda")
+        st = torch.full((P, 2), -1.0, dtype=torch.float64, device="cuda")
+        torch.cuda.synchronize()
+        rc = eng.lib.dsir_icp_correspondences(eng.h, src.data_ptr(), ref.data_ptr(), P, J, K, 6, float(RADIUS), T_dev.data_ptr(), search,
+                                              idx.data_ptr(), d2.data_ptr(), st.data_ptr())
+        eng.sync()
+        assert rc == 0, (search, eng.lib.dsir_last_error(eng.h))
+        return idx.cpu().numpy(), d2.cpu().numpy(), st.cpu().numpy()
+
+    b, g = corr(0), corr(1)
+    print(f"ENTRIES correspondences: stats {b[2].tolist()}")
+    assert (b[2][:, 0] > 0).all() and (b[0] >= 0).any(axis=1).all()
+    assert all(x.tobytes() == y.tobytes() for x, y in zip(b, g))
+
+
 # ------------------------------------------------------------------ 3. determinism
 def test_gpu_grid_two_runs_and_batch_independence(eng):
     src, ref, T0, normals = _loop_batch()

@@ -147,9 +147,18 @@ def _refine_ex(eng, src, ref, T0, estimator, normals, r=RADIUS, max_iter=30):
 def test_gpu_estimator_point_equals_icp_refine(J, K, noise, seeds):
     src, ref, T0, normals = _batch(J, K, noise, seeds)
     eng = _engine(max(J, K), 3)
-    T_old, st_old = eng.icp_refine(_dev(src), _dev(ref), _dev(T0), RADIUS)        # the default call: dsir_icp_refine
-    assert tuple(st_old.shape) == (3, 4)
+    import torch
+    s, t, t0 = _dev(src), _dev(ref), _dev(T0)                                     # the old entry itself: dsir_icp_refine
+    T_old = torch.zeros((3, 3, 4), dtype=torch.float32, device="cuda")
+    st_old = torch.full((3, 4), -1.0, dtype=torch.float64, device="cuda")
+    torch.cuda.synchronize()
+    assert eng.lib.dsir_icp_refine(eng.h, s.data_ptr(), t.data_ptr(), 3, J, K, s.shape[2], float(RADIUS), 30, 1e-6, 1e-6, t0.data_ptr(),
+                                   T_old.data_ptr(), st_old.data_ptr()) == 0
+    eng.sync()
     T_old, st_old = T_old.cpu().numpy(), st_old.cpu().numpy()
+    T_def, st_def = eng.icp_refine(s, t, t0, RADIUS)                              # and the default Python call
+    assert tuple(st_def.shape) == (3, 4)
+    assert T_def.cpu().numpy().tobytes() == T_old.tobytes() and st_def.cpu().numpy().tobytes() == st_old.tobytes()
     for nrm in (None, normals):                                                   # estimator 0 does not read the normals
         rc, T, st = _refine_ex(eng, src, ref, T0, 0, nrm)
         assert rc == 0

@@ -1,6 +1,7 @@
-// Stand-alone host check of deepsir_amd/csrc/icp_grid.h and csrc/cell_index.h (the per-pair lattice rule of the cell-indexed ICP
-// search, the cell coordinate and key, and the scratch layout that icp_scratch_bytes_ex2 adds and icp_grid_build takes its
-// offsets from) under AddressSanitizer + UndefinedBehaviorSanitizer: host code only, runs on the CPU, no GPU and no Python loader.
+// Stand-alone host check of deepsir_amd/csrc/icp_grid.h, csrc/icp_layout.h and csrc/cell_index.h (the per-pair lattice rule of the
+// cell-indexed ICP search, the cell coordinate and key, and the scratch layouts: IcpGridLayout that icp_grid_build takes its offsets
+// from, IcpLayout / IcpCorrLayout of the ICP loop and the search step, IndexLayout of overlap.hip) under AddressSanitizer +
+// UndefinedBehaviorSanitizer: host code only, runs on the CPU, no GPU and no Python loader.
 //   hipcc -x c++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -Ideepsir_amd/csrc \
 //         tools/icp_grid_check.cpp -o /tmp/icp_grid_check && /tmp/icp_grid_check
 // (any host C++17 compiler with -fsanitize=address,undefined does as well.  The sanitizer run is this manual command;
@@ -14,6 +15,7 @@
 #include <cstring>
 #include <vector>
 #include "icp_grid.h"
+#include "icp_layout.h"
 using namespace dsir;
 
 static long checks = 0;
@@ -31,6 +33,18 @@ static float d2_rule(const float* a, const float* b) {
   volatile float xx = dx * dx, yy = dy * dy, zz = dz * dz;
   volatile float s = xx + yy;
   return s + zz;
+}
+
+// parts at[0 .. n - 1] with at[n] = the total: in order, on 256 bytes, each as large as need[k], less than 256 bytes of padding, so
+// none overlaps and the total is the sum of the padded parts
+static void check_parts(const size_t* at, const size_t* need, int n) {
+  CHECK(at[0] == 0);
+  size_t sum = 0;
+  for (int k = 0; k < n; ++k) {
+    CHECK(at[k] % 256 == 0 && at[k + 1] >= at[k] + need[k] && at[k + 1] < at[k] + need[k] + 256);
+    sum += (need[k] + 255) / 256 * 256;
+  }
+  CHECK(at[n] == sum);
 }
 
 // n points in a box, every accepted pair (d2 <= fl(r r)) must be in adjacent cells; returns the accepted pairs seen
@@ -134,9 +148,43 @@ int main() {
     const size_t at[] = {l.lat, l.enc, l.off_ref, l.off_qry, l.keys, l.sorted, l.perm, l.keys_raw, l.vals_raw, l.vals, l.keys_qry, l.tmp, l.bytes};
     const size_t need[] = {(size_t)P * 32, (size_t)P * 24, (size_t)(P + 1) * 4, (size_t)(P + 1) * 4, nk * 8, nk * 16, nj * 4, nm * 8, nm * 4,
                            nk * 4, nj * 8, tmp < 256 ? 256 : tmp};
-    CHECK(l.lat == 0 && sizeof(IcpLattice) == 32 && l.tmp_bytes == tmp);
-    for (int k = 0; k < 12; ++k) CHECK(at[k] % 256 == 0 && at[k + 1] >= at[k] + need[k] && at[k + 1] < at[k] + need[k] + 256);
-    CHECK(l.bytes % 256 == 0);
+    CHECK(sizeof(IcpLattice) == 32 && sizeof(CellLattice) == 32 && l.tmp_bytes == tmp);
+    check_parts(at, need, 12);
+    // ---- the loop's scratch for estimator 0 / 1 and search 0 / 1: the parts, and the total against the formulas the loop grew by -
+    // the point-to-point loop's sum, plus icp_plane_extra_bytes, plus the grid's piece
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    for (int estimator = 0; estimator < 2; ++estimator) for (int search = 0; search < 2; ++search) {
+      const size_t grid = search ? l.bytes : 0, n = nj;
+      const IcpLayout i(P, J, estimator == 1, grid);
+      const size_t iat[] = {i.cur, i.idx, i.d2, i.w, i.Ta, i.Tb, i.state, i.skip, i.Tstep, i.part, i.nsing, i.grid, i.bytes};
+      const size_t ineed[] = {n * 12, n * 4, n * 4, n * 4, (size_t)P * 48, (size_t)P * 48, (size_t)P * 32, (size_t)P * 4, (size_t)P * 48,
+                              estimator ? (size_t)P * icp_plane_chunks(J) * kIcpPlaneSlots * 8 : 0, estimator ? (size_t)P * 8 : 0, grid};
+      check_parts(iat, ineed, 12);
+      const size_t point = al((size_t)P * J * 12) + 3 * al((size_t)P * J * 4) + 2 * al((size_t)P * 48) + al((size_t)P * 32) +
+                           al((size_t)P * 4) + al((size_t)P * 48);
+      CHECK(i.bytes == point + (estimator == 1 ? icp_plane_extra_bytes(P, J) : 0) + grid);
+      const IcpCorrLayout c(P, J, grid);
+      CHECK(c.cur == 0 && c.grid == al((size_t)P * J * 12) && c.bytes == al((size_t)P * J * 12) + grid);
+    }
+  }
+  // ---- overlap.hip's index over the same table (total points, fragments)
+  for (int F : ps) for (int n : ns) for (size_t tmp : tmps) {
+    const int64_t total = (int64_t)n - 1;                          // 0 included: laid out as one point
+    const IndexLayout l(total, F, tmp);
+    const size_t m = (size_t)(total < 1 ? 1 : total);
+    const size_t at[] = {l.keys, l.sorted, l.box, l.off, l.keys_raw, l.vals_raw, l.vals, l.tmp, l.bytes};
+    const size_t need[] = {m * 8, m * 16, (size_t)F * 24, (size_t)(F + 1) * 4, m * 8, m * 4, m * 4, tmp < 256 ? 256 : tmp};
+    CHECK(l.tmp_bytes == tmp);
+    check_parts(at, need, 8);
+    ++shapes;
+  }
+  // ---- Carve and point_key
+  {
+    Carve c;
+    CHECK(c.take(0) == 0 && c.p == 0 && c.take(1) == 0 && c.p == 256 && c.take(256) == 256 && c.take(257) == 512 && c.p == 1024);
+    const CellLattice L{0.0, 0.0, 0.0, 1.0};
+    CHECK(point_key(1.5f, 2.5f, 3.5f, L) == cell_key(1, 2, 3) && point_key(-5.f, 0.f, 1e30f, L) == cell_key(0, 0, MAXC));
+    CHECK(point_key(NAN, 0.f, 0.f, L) == KEY_NONE && point_key(0.f, INFINITY, 0.f, L) == KEY_NONE && point_key(0.f, 0.f, -INFINITY, L) == KEY_NONE);
   }
   std::printf("icp_grid: %ld checks passed, %ld shapes laid out, %ld accepted pairs contained\n", checks, shapes, hits);
   return 0;
