@@ -1006,9 +1006,9 @@ int dsir_enable_graph(dsir_ctx* c, int enable) {
 int dsir_voxel_downsample(dsir_ctx* c, const float* points, const int64_t* offsets, int clouds, int stride, float voxel_size,
                           const float* crop, int cap, float* out, int32_t* counts) {
   if (!c) return 1;
-  if (!points || !offsets || !out || !counts || clouds < 1 || clouds > 1000 || stride < 3 || stride > 16 || cap < 1 ||
-      !(voxel_size > 0.f))
+  if (!points || !offsets || !out || !counts || stride < 3 || stride > 16 || cap < 1 || !(voxel_size > 0.f))
     return fail(c, "dsir_voxel_downsample: bad arguments");
+  if (clouds < 1 || clouds > 1000) return fail(c, "dsir_voxel_downsample: %d clouds in one call (1 to 1000 supported)", clouds);
   HIP_OK(c, hipSetDevice(c->device));
   const int64_t total = offsets[clouds];
   if (total <= 0 || total > 0x7fffffffll) return fail(c, "dsir_voxel_downsample: %lld points unsupported", (long long)total);
@@ -1017,9 +1017,19 @@ int dsir_voxel_downsample(dsir_ctx* c, const float* points, const int64_t* offse
   if (c->ws.overflow) return fail(c, "workspace too small for %lld raw points (raise max_points / max_pairs)", (long long)total);
   // the host offsets are consumed by an async copy: make the call self-contained
   HIP_OK(c, hipStreamSynchronize(c->stream));
-  if (int r = launch_voxel_downsample(points, offsets, clouds, stride, voxel_size, crop, cap, out, counts, scratch, c->stream))
+  const int32_t* bad_dev = nullptr;
+  if (int r = launch_voxel_downsample(points, offsets, clouds, stride, voxel_size, crop, cap, out, counts, scratch, c->stream,
+                                      &bad_dev))
     return fail(c, "dsir_voxel_downsample: launch failed (%d)", r);
   HIP_OK(c, hipStreamSynchronize(c->stream));
+  int32_t bad = kVoxelNoBadRow;
+  HIP_OK(c, hipMemcpy(&bad, bad_dev, sizeof(bad), hipMemcpyDeviceToHost));
+  if (bad != kVoxelNoBadRow) {                       // never dropped, never aliased into a neighbouring key field
+    int cloud = 0;
+    while (cloud + 1 < clouds && offsets[cloud + 1] <= bad) ++cloud;
+    return fail(c, "dsir_voxel_downsample: cloud %d row %lld survives the crop with a voxel index outside [0, 2^18) or a "
+                   "coordinate that is not finite (counts / out are unspecified)", cloud, (long long)(bad - offsets[cloud]));
+  }
   return post(c);
 }
 

@@ -588,7 +588,11 @@ int launch_align_loss(const float* src, const float* ref, const int32_t* idx, co
 // pre-processing on ragged batches (preprocess.hip); return 0 on success
 size_t voxel_downsample_scratch_bytes(int64_t total, int clouds);
 int launch_voxel_downsample(const float* pts, const int64_t* offsets_host, int clouds, int stride, float voxel,
-                            const float* crop_host, int cap, float* out, int32_t* counts, void* scratch, hipStream_t st);
+                            const float* crop_host, int cap, float* out, int32_t* counts, void* scratch, hipStream_t st,
+                            const int32_t** bad_row_dev);
+// *bad_row_dev (in scratch, valid once the stream has drained): the smallest row of the batch that survives the crop and has a voxel
+// index outside [0, 2^18) on some axis or a coordinate that is not finite; kVoxelNoBadRow when every row could be keyed
+constexpr int32_t kVoxelNoBadRow = 0x7fffffff;
 size_t resample_scratch_bytes(int clouds, int cap);
 int launch_resample(const float* in, const int32_t* counts, int clouds, int cap, int stride, int k, int mode, uint64_t seed,
                     float* out, void* scratch, hipStream_t st);

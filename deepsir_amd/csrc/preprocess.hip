@@ -11,6 +11,10 @@
 // (ix, iy, iz) order; a voxel's points are summed in float64 in ascending input order; the random resampling draws
 // its keys from splitmix64(seed, cloud, index) and breaks ties by index.  Everything is deterministic.
 //
+// A voxel index has 18 bits per axis in the packed sort key.  A point that survives the crop and whose index on some
+// axis is outside [0, 2^18), or whose coordinate is not finite, is never dropped or aliased: voxel_key_kernel records
+// the smallest such row and the call is refused (dsir_voxel_downsample names the cloud and the row).
+//
 // Sorting and scanning are library calls (hipCUB device radix sort / scan): plain library ops, not the hot path.
 #include <hipcub/hipcub.hpp>
 
@@ -57,7 +61,8 @@ __global__ __launch_bounds__(1024) void bounds_kernel(const float* __restrict__ 
 
 __global__ void voxel_key_kernel(const float* __restrict__ pts, const int64_t* __restrict__ off, int clouds, int stride,
                                  double voxel, float4 crop, int use_crop, const float* __restrict__ minb,
-                                 uint64_t* __restrict__ keys, uint32_t* __restrict__ vals, int64_t total) {
+                                 uint64_t* __restrict__ keys, uint32_t* __restrict__ vals, int64_t total,
+                                 int32_t* __restrict__ bad_row) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     int lo = 0, hi = clouds;                       // cloud of point i: offsets are sorted
     while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (off[mid] <= i) lo = mid; else hi = mid; }
@@ -72,6 +77,7 @@ __global__ void voxel_key_kernel(const float* __restrict__ pts, const int64_t* _
         q[k] = (uint64_t)c;
       }
       if (ok) key = ((uint64_t)lo << 54) | (q[0] << 36) | (q[1] << 18) | q[2];
+      else atomicMin(bad_row, (int32_t)i);         // NaN / inf fail both comparisons; total <= 2^31 - 1
     }
     keys[i] = key;
     vals[i] = (uint32_t)(i - off[lo]);
@@ -174,12 +180,14 @@ size_t voxel_downsample_scratch_bytes(int64_t total, int clouds) {
   b += 2 * align256((size_t)total * sizeof(uint32_t));       // vals in / out
   b += 2 * align256((size_t)total * sizeof(int32_t));        // head, ordinal
   b += align256((size_t)clouds * sizeof(int32_t));           // first ordinal
+  b += align256(sizeof(int32_t));                            // first row with an unrepresentable voxel index
   b += align256(sort_tmp > scan_tmp ? sort_tmp : scan_tmp);
   return b;
 }
 
 int launch_voxel_downsample(const float* pts, const int64_t* offsets_host, int clouds, int stride, float voxel,
-                            const float* crop_host, int cap, float* out, int32_t* counts, void* scratch, hipStream_t st) {
+                            const float* crop_host, int cap, float* out, int32_t* counts, void* scratch, hipStream_t st,
+                            const int32_t** bad_row_dev) {
   const int64_t total = offsets_host[clouds];
   if (total <= 0 || total > 0x7fffffffll || stride < 3 || stride > 16 || clouds < 1 || clouds > 1023 || !(voxel > 0.f)) return 1;
   char* p = reinterpret_cast<char*>(scratch);
@@ -193,6 +201,8 @@ int launch_voxel_downsample(const float* pts, const int64_t* offsets_host, int c
   int32_t* head = reinterpret_cast<int32_t*>(take((size_t)total * sizeof(int32_t)));
   int32_t* ordinal = reinterpret_cast<int32_t*>(take((size_t)total * sizeof(int32_t)));
   int32_t* first = reinterpret_cast<int32_t*>(take((size_t)clouds * sizeof(int32_t)));
+  int32_t* bad_row = reinterpret_cast<int32_t*>(take(sizeof(int32_t)));
+  *bad_row_dev = bad_row;
   size_t sort_tmp = 0, scan_tmp = 0;
   hipcub::DeviceRadixSort::SortPairs(nullptr, sort_tmp, k0, k1, v0, v1, (int)total);
   hipcub::DeviceScan::ExclusiveSum(nullptr, scan_tmp, head, ordinal, (int)total);
@@ -203,8 +213,9 @@ int launch_voxel_downsample(const float* pts, const int64_t* offsets_host, int c
   const float4 crop = use_crop ? make_float4(crop_host[0], crop_host[1], crop_host[2], crop_host[3]) : make_float4(0, 0, 0, 0);
   if (hipMemcpyAsync(off, offsets_host, (size_t)(clouds + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st) != hipSuccess) return 2;
   hipLaunchKernelGGL(bounds_kernel, dim3(clouds), dim3(1024), 0, st, pts, off, stride, crop, use_crop ? 1 : 0, minb);
+  hipLaunchKernelGGL(fill_i32_kernel, dim3(1), dim3(256), 0, st, bad_row, 1, kVoxelNoBadRow);
   hipLaunchKernelGGL(voxel_key_kernel, dim3(grid_for(total)), dim3(256), 0, st, pts, off, clouds, stride, (double)voxel, crop,
-                     use_crop ? 1 : 0, minb, k0, v0, total);
+                     use_crop ? 1 : 0, minb, k0, v0, total, bad_row);
   size_t tb = tmp_bytes;
   if (hipcub::DeviceRadixSort::SortPairs(tmp, tb, k0, k1, v0, v1, (int)total, 0, 64, st) != hipSuccess) return 3;
   hipLaunchKernelGGL(voxel_head_kernel, dim3(grid_for(total)), dim3(256), 0, st, k1, total, head);

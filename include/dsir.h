@@ -265,6 +265,11 @@ int dsir_forward_pair(dsir_ctx* ctx, const dsir_pair_batch* in, int num_sub, con
  * [clouds+1] of row offsets, crop = HOST [r_min, r_max, z_min, z_max] or NULL.
  * out [clouds][cap][stride] (voxels in ascending (ix,iy,iz) order; rows beyond cap are dropped),
  * counts [clouds] i32 on device = number of voxels of every cloud (may exceed cap: caller's overflow check).
+ * 1 to 1000 clouds per call; a cloud may be empty, and a cloud the crop empties has count 0.  A voxel index has 18 bits
+ * per axis: a point that survives the crop with an index outside [0, 2^18) on some axis (an extent of 2^18 voxels or
+ * more, one stray far point) or with a coordinate that is not finite is neither dropped nor aliased - the call fails,
+ * the error names the cloud and the cloud-local row, and counts / out are unspecified.  (With a crop such a coordinate
+ * never survives: NaN and inf fail the crop's comparisons.)
  * The output order / arithmetic rule is this engine's own (open3d is unpinned): oracle/preprocess.py. */
 int dsir_voxel_downsample(dsir_ctx* ctx, const float* points, const int64_t* offsets, int clouds, int stride,
                           float voxel_size, const float* crop, int cap, float* out, int32_t* counts);

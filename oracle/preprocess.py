@@ -15,6 +15,9 @@ This module DEFINES the rule the engine owns (deepsir_amd/csrc/preprocess.hip mu
   min_bound over the points that survive the crop;
 * voxels are emitted in ascending (ix, iy, iz); a voxel's channels are summed in float64 in ascending input
   order and divided by the count, then rounded to float32;
+* a point that survives the crop with an index outside [0, 2^18) on some axis, or with a coordinate that is not finite,
+  is an error (ValueError naming the first such cloud-local row and its first such axis): never dropped, never aliased
+  into a neighbouring axis's field of the packed key;
 * random resampling: key_i = splitmix64(seed ^ (cloud << 40) ^ i) >> 1, points taken in ascending (key, i);
   if the cloud has fewer than k points the rest are drawn as splitmix64(~seed ^ (cloud << 40) ^ j) % n.
 """
@@ -25,6 +28,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 _M64 = (1 << 64) - 1
+_INDEX_LIMIT = 1 << 18               # a voxel index has 18 bits per axis in the packed key
 
 
 def splitmix64(x: int) -> int:
@@ -51,9 +55,16 @@ def voxel_downsample(points: np.ndarray, voxel: float, crop: Optional[Sequence[f
     if len(idx) == 0:
         return np.zeros((0, pts.shape[1]), np.float32)
     p = pts[idx]
-    minb = p[:, :3].min(0).astype(np.float64)
+    minb = np.fmin.reduce(p[:, :3], 0).astype(np.float64)     # fmin: a NaN row is the row reported below, not row 0
     v = float(np.float32(voxel))
-    q = np.floor((p[:, :3].astype(np.float64) - (minb - 0.5 * v)) / v).astype(np.int64)
+    with np.errstate(invalid="ignore"):
+        qf = np.floor((p[:, :3].astype(np.float64) - (minb - 0.5 * v)) / v)
+    bad = ~((qf >= 0.0) & (qf < float(_INDEX_LIMIT)))          # NaN / inf fail both comparisons
+    if bad.any():
+        r = int(np.nonzero(bad.any(1))[0][0])
+        raise ValueError(f"voxel_downsample: row {int(idx[r])} axis {int(np.nonzero(bad[r])[0][0])} survives the crop with a voxel "
+                         f"index outside [0, 2^18) or a coordinate that is not finite")
+    q = qf.astype(np.int64)
     key = (q[:, 0] << 36) | (q[:, 1] << 18) | q[:, 2]
     order = np.argsort(key, kind="stable")
     ks = key[order]
