@@ -13,33 +13,20 @@
 //
 // No atomics anywhere: the centroid is a two-stage sum in a fixed order (thread-strided partials, an LDS tree, the blocks' partials in
 // block order), so two runs write the same bytes.  Every cloud is handled by its own blocks / lanes from its own key: a cloud's rows do
-// not depend on what else is in the call.  The segmented sort is a library call (hipCUB).
-#include <hipcub/hipcub.hpp>
+// not depend on what else is in the call.  The resampling step (dsir_t_resample_keyed) is resample.hip's, shared with the engine.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "dsir_train.h"
 #include "device_utils.h"
+#include "augment_params.h"
+#include "scratch.h"
 
 namespace dsir {
 namespace {
 
 constexpr int CB = 16;                 // centroid: blocks per cloud (stage 1)
 constexpr int CT = 256;                // centroid: threads per block
-constexpr uint64_t kPadKey = ~0ull;
-constexpr uint64_t STREAM_PERM = 1ull << 40, STREAM_TOPUP = 2ull << 40, STREAM_JITTER = 3ull << 40;
-
-// one cloud's parameter block: 24 eight-byte slots (deepsir_amd/augment.py::pack_params)
-struct AugParams {
-  double R[9], t[3], s, jscale, jclip;
-  int64_t jmode, centered, normals;
-  uint64_t key;
-  int64_t rmode, scaled, pad[3];
-};
-static_assert(sizeof(AugParams) == 24 * 8, "AugParams is 24 slots");
-
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-inline int grid1(int64_t total) { const int64_t g = (total + 255) / 256; return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g)); }
 inline int done() { return (int)hipGetLastError(); }
 
 // ---- centroids: stage 1, block (b, cloud) sums rows [b chunk, (b + 1) chunk) of the cloud's first n rows
@@ -80,44 +67,6 @@ __global__ void centroid_final_kernel(const double* __restrict__ partial, const 
     centroids[cloud * 3 + k] = m;
   }
   invalid[cloud] = bits;
-}
-
-// ---- resampling with a key per cloud: dsir_resample's rule with the cloud's key in place of (seed, position in the call)
-__global__ void aug_sort_key_kernel(const int32_t* __restrict__ counts, const AugParams* __restrict__ prm, int clouds, int cap,
-                                    uint64_t* __restrict__ keys, uint32_t* __restrict__ vals, int* __restrict__ seg) {
-  const int64_t total = (int64_t)clouds * cap;
-  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e <= total; e += (int64_t)gridDim.x * blockDim.x) {
-    if (e <= clouds) seg[e] = (int)(e * cap);                                                  // total >= clouds: every offset is visited
-    if (e == total) break;
-    const int c = (int)(e / cap), i = (int)(e % cap);
-    const int n = min(counts[c], cap);
-    keys[e] = i < n ? (splitmix64(prm[c].key ^ STREAM_PERM ^ (uint64_t)i) >> 1) : kPadKey;   // padding sorts last
-    vals[e] = (uint32_t)i;
-  }
-}
-
-__global__ void aug_gather_kernel(const float* __restrict__ in, const int32_t* __restrict__ counts, const AugParams* __restrict__ prm,
-                                  const uint32_t* __restrict__ perm, int cap, int stride, int k, float* __restrict__ out,
-                                  int32_t* __restrict__ rows) {
-  const int c = blockIdx.y;
-  const int j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= k) return;
-  const int n = min(counts[c], cap);
-  float* o = out + ((int64_t)c * k + j) * stride;
-  if (n <= 0) {
-    for (int ch = 0; ch < stride; ++ch) o[ch] = 0.f;
-    if (rows) rows[(int64_t)c * k + j] = 0;
-    return;
-  }
-  const int mode = (int)prm[c].rmode;
-  int srow;
-  if (mode == 1) srow = j % n;                                                   // FixedResampler: tile / prefix
-  else if (mode == 2) srow = (int)perm[(int64_t)c * cap + j % n];                // the loader's permutation, then FixedResampler
-  else if (j < n) srow = (int)perm[(int64_t)c * cap + j];                        // Resampler: random order, no repeats
-  else srow = (int)(splitmix64(prm[c].key ^ STREAM_TOPUP ^ (uint64_t)j) % (uint64_t)n);   // top-up with replacement
-  const float* s = in + ((int64_t)c * cap + srow) * stride;
-  for (int ch = 0; ch < stride; ++ch) o[ch] = s[ch];
-  if (rows) rows[(int64_t)c * k + j] = srow;
 }
 
 // ---- the per-point pass: one row per lane, a cloud's rows contiguous; in place is fine (a lane reads its row, then writes it)
@@ -209,17 +158,6 @@ __global__ void augment_gt_kernel(const double* __restrict__ M, const AugParams*
   }
 }
 
-inline bool shape_ok(int clouds, int cap, int stride) {
-  return clouds >= 1 && cap >= 1 && stride >= 3 && (int64_t)clouds * cap <= 0x7fffffffll && clouds <= 65535;
-}
-
-inline size_t seg_sort_bytes(int64_t total, int clouds) {
-  size_t b = 0;
-  hipcub::DeviceSegmentedRadixSort::SortPairs(nullptr, b, (const uint64_t*)nullptr, (uint64_t*)nullptr, (const uint32_t*)nullptr,
-                                              (uint32_t*)nullptr, (int)total, clouds, (const int*)nullptr, (const int*)nullptr);
-  return b;
-}
-
 }  // namespace
 }  // namespace dsir
 
@@ -231,7 +169,7 @@ size_t dsir_t_cloud_centroids_scratch(int clouds) { return clouds < 1 ? 0 : alig
 
 int dsir_t_cloud_centroids(void* stream, const float* points, const int32_t* counts, int clouds, int cap, int stride, double* centroids,
                            int32_t* invalid, void* scratch) {
-  if (!points || !counts || !centroids || !invalid || !scratch || !shape_ok(clouds, cap, stride)) return (int)hipErrorInvalidValue;
+  if (!points || !counts || !centroids || !invalid || !scratch || !aug_shape_ok(clouds, cap, stride)) return (int)hipErrorInvalidValue;
   hipStream_t st = (hipStream_t)stream;
   double* partial = reinterpret_cast<double*>(scratch);
   hipLaunchKernelGGL(centroid_partial_kernel, dim3(CB, clouds), dim3(CT), 0, st, points, counts, cap, stride, partial);
@@ -239,41 +177,9 @@ int dsir_t_cloud_centroids(void* stream, const float* points, const int32_t* cou
   return done();
 }
 
-size_t dsir_t_resample_keyed_scratch(int clouds, int cap) {
-  if (!shape_ok(clouds, cap, 3)) return 0;
-  const int64_t total = (int64_t)clouds * cap;
-  return 2 * align256((size_t)total * 8) + 2 * align256((size_t)total * 4) + align256((size_t)(clouds + 1) * 4) +
-         align256(seg_sort_bytes(total, clouds));
-}
-
-int dsir_t_resample_keyed(void* stream, const float* in, const int32_t* counts, int clouds, int cap, int stride, int k, const void* params,
-                          int need_perm, float* out, int32_t* rows, void* scratch) {
-  if (!in || !counts || !params || !out || !scratch || !shape_ok(clouds, cap, stride) || k < 1 || (int64_t)clouds * k > 0x7fffffffll)
-    return (int)hipErrorInvalidValue;
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t total = (int64_t)clouds * cap;
-  const AugParams* prm = reinterpret_cast<const AugParams*>(params);
-  char* p = reinterpret_cast<char*>(scratch);
-  auto take = [&](size_t bytes) { char* r = p; p += align256(bytes); return r; };
-  uint64_t* k0 = reinterpret_cast<uint64_t*>(take((size_t)total * 8));
-  uint64_t* k1 = reinterpret_cast<uint64_t*>(take((size_t)total * 8));
-  uint32_t* v0 = reinterpret_cast<uint32_t*>(take((size_t)total * 4));
-  uint32_t* v1 = reinterpret_cast<uint32_t*>(take((size_t)total * 4));
-  int* seg = reinterpret_cast<int*>(take((size_t)(clouds + 1) * 4));
-  if (need_perm) {
-    size_t tb = seg_sort_bytes(total, clouds);
-    hipLaunchKernelGGL(aug_sort_key_kernel, dim3(grid1(total + 1)), dim3(256), 0, st, counts, prm, clouds, cap, k0, v0, seg);
-    if (hipcub::DeviceSegmentedRadixSort::SortPairs(p, tb, k0, k1, v0, v1, (int)total, clouds, seg, seg + 1, 0, 64, st) != hipSuccess)
-      return (int)hipErrorUnknown;
-  }
-  hipLaunchKernelGGL(aug_gather_kernel, dim3((k + 255) / 256, clouds), dim3(256), 0, st, in, counts, prm, (const uint32_t*)v1, cap, stride, k,
-                     out, rows);
-  return done();
-}
-
 int dsir_t_augment(void* stream, const float* in, const int32_t* counts, int clouds, int k, int stride, const void* params,
                    const double* centroids, float* out) {
-  if (!in || !counts || !params || !centroids || !out || !shape_ok(clouds, k, stride)) return (int)hipErrorInvalidValue;
+  if (!in || !counts || !params || !centroids || !out || !aug_shape_ok(clouds, k, stride)) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(augment_kernel, dim3((k + 255) / 256, clouds), dim3(256), 0, (hipStream_t)stream, in, counts,
                      reinterpret_cast<const AugParams*>(params), centroids, k, stride, out);
   return done();

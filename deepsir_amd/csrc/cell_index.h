@@ -1,5 +1,5 @@
 // The sparse cell index, stated once for overlap.hip (one lattice per call, one lane per query) and icp_grid.hip (one lattice per pair
-// made on the device, eight lanes per query): lattice, cell coordinate, key, scratch carving and overlap.hip's layout as plain C++ that
+// made on the device, eight lanes per query): lattice, cell coordinate, key and overlap.hip's layout (carved with scratch.h) as plain C++ that
 // compiles for the host too (tools/icp_grid_check.cpp); for the device the bounds accumulation, gather, distance rule and key walk.
 //
 // Why the 27 cells around c(a) hold every b the rule accepts for a query a - the part both users share.  The rule is
@@ -17,6 +17,8 @@
 #include <math.h>
 #include <stddef.h>
 #include <stdint.h>
+
+#include "scratch.h"
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
 #define DSIR_CELL_HD __host__ __device__ __forceinline__
@@ -47,12 +49,6 @@ DSIR_CELL_HD uint64_t point_key(float x, float y, float z, const CellLattice& L)
   return cell_key(cx < 0 ? 0 : (cx > MAXC ? MAXC : cx), cy < 0 ? 0 : (cy > MAXC ? MAXC : cy), cz < 0 ? 0 : (cz > MAXC ? MAXC : cz));
 }
 
-// parts of one piece of scratch, each starting on 256 bytes: take() returns the part's offset
-struct Carve {
-  size_t p = 0;
-  size_t take(size_t bytes) { const size_t at = p; p += (bytes + 255) & ~(size_t)255; return at; }
-};
-
 // overlap.hip's index inside its one allocation, from (total, fragments) and the sort's temporary size: _scratch, _build, _within
 struct IndexLayout {
   size_t keys, sorted, box, off, keys_raw, vals_raw, vals, tmp, tmp_bytes, bytes;
@@ -71,9 +67,6 @@ struct IndexLayout {
     bytes = c.p;
   }
 };
-
-// temporary bytes of hipCUB's segmented radix sort of `total` (uint64 key, uint32 value) pairs in `segments` segments (icp_grid.hip)
-size_t seg_sort_tmp_bytes(int64_t total, int segments);
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
 // order-preserving map fp32 -> uint32, for integer min / max

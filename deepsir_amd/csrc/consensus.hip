@@ -40,6 +40,7 @@
 #include "kernels.h"
 #include "device_utils.h"
 #include "ransac_stages.h"
+#include "seg_sort.h"
 #include "dsir.h"
 
 namespace dsir {
@@ -50,8 +51,6 @@ constexpr int CT = 64;    // rows per compat workgroup
 constexpr int SI = 256;   // rows i per scoring workgroup (one per lane)
 constexpr int CW = 8;     // words of a row per scoring workgroup
 constexpr int SJ = 64;    // rows j per LDS block: one word of C
-
-inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 __device__ __forceinline__ double len64(float ax, float ay, float az, float bx, float by, float bz) {
   const double dx = (double)ax - (double)bx, dy = (double)ay - (double)by, dz = (double)az - (double)bz;
@@ -149,10 +148,6 @@ __global__ __launch_bounds__(SI) void consensus_score_kernel(const unsigned long
 __global__ void consensus_key_kernel(const int32_t* __restrict__ score, int64_t total, int M, unsigned long long* __restrict__ key) {
   for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x)
     key[e] = ((unsigned long long)(uint32_t)score[e] << 32) | (0xFFFFFFFFu - (uint32_t)(e % M));
-}
-
-__global__ void consensus_seg_kernel(int* seg, int pairs, int M) {
-  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e <= pairs; e += gridDim.x * blockDim.x) seg[e] = e * M;
 }
 
 // seed [P][seeds]: row index of seed rank r, or -1
@@ -259,39 +254,24 @@ __global__ __launch_bounds__(256) void consensus_members_kernel(const float* __r
   }
 }
 
-size_t sort_tmp_bytes(int pairs, int M) {
-  size_t tmp = 0;
-  hipcub::DeviceSegmentedRadixSort::SortKeysDescending(nullptr, tmp, (const unsigned long long*)nullptr, (unsigned long long*)nullptr,
-                                                       pairs * M, pairs, (const int*)nullptr, (const int*)nullptr);
-  return tmp;
-}
-
 }  // namespace
 
-// P M W 8 bytes of bit matrix, P (M 48 + seeds 56)-order scratch, the sort's own
-size_t consensus_scratch_bytes(int pairs, int M, int seeds, int refine_iters) {
-  const size_t P = (size_t)pairs, W = (size_t)(M + 63) / 64;
-  return pose_scratch_bytes(pairs, M, refine_iters) + al256(P * M * W * 8) + al256(P * M * 4) + 2 * al256(P * M * 8) +
-         al256((P + 1) * 4) + al256(sort_tmp_bytes(pairs, M)) + al256(P * seeds * 4) + al256(P * seeds * 48) + 2 * al256(P * seeds * 4);
+size_t consensus_scratch_bytes(int pairs, int M, int seeds, int refine_iters) { 
+  return ConsensusLayout(pairs, M, seeds, refine_iters, seg_sort_keys_desc_tmp_bytes((int64_t)pairs * M, pairs)).bytes;
 }
 
 int launch_consensus(const ConsensusArgs& a, void* scratch, hipStream_t st) {
   const int P = a.pairs, M = a.M, H = a.seeds, R = a.refine_iters, W = (M + 63) / 64;
   if ((int64_t)P * M > 0x7fffffffll) return 1;
-  char* p = reinterpret_cast<char*>(scratch);
-  auto take = [&](size_t bytes) { char* r = p; p += al256(bytes); return r; };
-  const PoseScratch s = pose_scratch_take(p, P, M, R);
-  unsigned long long* bits = reinterpret_cast<unsigned long long*>(take((size_t)P * M * W * 8));
-  int32_t* score = reinterpret_cast<int32_t*>(take((size_t)P * M * 4));
-  unsigned long long* k0 = reinterpret_cast<unsigned long long*>(take((size_t)P * M * 8));
-  unsigned long long* k1 = reinterpret_cast<unsigned long long*>(take((size_t)P * M * 8));
-  int* seg = reinterpret_cast<int*>(take((size_t)(P + 1) * 4));
-  size_t tmp = sort_tmp_bytes(P, M);
-  void* sort_tmp = take(tmp);
-  int32_t* seed = reinterpret_cast<int32_t*>(take((size_t)P * H * 4));
-  float* hyp_T = reinterpret_cast<float*>(take((size_t)P * H * 48));
-  int32_t* hyp_valid = reinterpret_cast<int32_t*>(take((size_t)P * H * 4));
-  int32_t* hyp_count = reinterpret_cast<int32_t*>(take((size_t)P * H * 4));
+  size_t tmp = seg_sort_keys_desc_tmp_bytes((int64_t)P * M, P);
+  const ConsensusLayout lay(P, M, H, R, tmp);
+  const PoseParts s(scratch, lay.pose);
+  unsigned long long *bits = at<unsigned long long>(scratch, lay.bits), *k0 = at<unsigned long long>(scratch, lay.k0),
+                     *k1 = at<unsigned long long>(scratch, lay.k1);
+  int32_t *score = at<int32_t>(scratch, lay.score), *seed = at<int32_t>(scratch, lay.seed);
+  int* seg = at<int>(scratch, lay.seg);
+  float* hyp_T = at<float>(scratch, lay.hyp_T);
+  int32_t *hyp_valid = at<int32_t>(scratch, lay.hyp_valid), *hyp_count = at<int32_t>(scratch, lay.hyp_count);
   const float thr2 = a.max_dist * a.max_dist;   // fp32 product, as in ransac.hip
   const float cd = a.compat_dist > 0.f ? a.compat_dist : a.max_dist;
 
@@ -308,8 +288,9 @@ int launch_consensus(const ConsensusArgs& a, void* scratch, hipStream_t st) {
   const int64_t total = (int64_t)P * M;
   const int kg = (int)((total + 255) / 256 > 65535 ? 65535 : (total + 255) / 256);
   hipLaunchKernelGGL(consensus_key_kernel, dim3(kg), dim3(256), 0, st, score, total, M, k0);
-  hipLaunchKernelGGL(consensus_seg_kernel, dim3(1), dim3(256), 0, st, seg, P, M);
-  if (hipcub::DeviceSegmentedRadixSort::SortKeysDescending(sort_tmp, tmp, k0, k1, (int)total, P, seg, seg + 1, 0, 64, st) != hipSuccess)
+  launch_seg_offsets(seg, P, M, st);
+  if (hipcub::DeviceSegmentedRadixSort::SortKeysDescending(at<char>(scratch, lay.tmp), tmp, k0, k1, (int)total, P, seg, seg + 1, 0, 64, st) !=
+      hipSuccess)
     return 2;
   hipLaunchKernelGGL(consensus_seed_kernel, dim3((P * H + 255) / 256), dim3(256), 0, st, k1, P, M, H, seed);
   const size_t lds = (size_t)W * 8 + (size_t)M * 2;

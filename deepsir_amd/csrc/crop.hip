@@ -33,6 +33,7 @@
 
 #include "dsir_train.h"
 #include "device_utils.h"
+#include "scratch.h"
 
 namespace dsir {
 namespace {
@@ -50,7 +51,6 @@ struct CropState {
   int32_t mode, bits;
 };
 
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 inline int slices_of(int cap) { return (cap + ROWS - 1) / ROWS; }
 inline int done() { return (int)hipGetLastError(); }
 
@@ -60,13 +60,13 @@ struct Layout {
 inline Layout layout(int clouds, int cap) {
   Layout l;
   const size_t nb = (size_t)slices_of(cap);
-  size_t p = 0;
-  l.keys = p; p += align256((size_t)clouds * cap * 4);
-  l.hist = p; p += align256((size_t)clouds * nb * 256 * 4);
-  l.state = p; p += align256((size_t)clouds * sizeof(CropState));
-  l.q = p; p += align256((size_t)clouds * 2 * sizeof(double));
-  l.block_counts = p; p += align256((size_t)clouds * nb * 4);
-  l.total = p;
+  Carve c;
+  l.keys = c.take((size_t)clouds * cap * 4);
+  l.hist = c.take((size_t)clouds * nb * 256 * 4);
+  l.state = c.take((size_t)clouds * sizeof(CropState));
+  l.q = c.take((size_t)clouds * 2 * sizeof(double));
+  l.block_counts = c.take((size_t)clouds * nb * 4);
+  l.total = c.p;
   return l;
 }
 

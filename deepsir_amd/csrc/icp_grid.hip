@@ -50,6 +50,7 @@
 
 #include "kernels.h"
 #include "icp_grid.h"
+#include "seg_sort.h"
 
 namespace dsir {
 
@@ -202,13 +203,6 @@ bool sort_pairs(void* tmp, size_t tmp_bytes, const uint64_t* kin, uint64_t* kout
 
 }  // namespace
 
-size_t seg_sort_tmp_bytes(int64_t total, int segments) {
-  size_t b = 0;
-  hipcub::DeviceSegmentedRadixSort::SortPairs(nullptr, b, (const uint64_t*)nullptr, (uint64_t*)nullptr, (const uint32_t*)nullptr,
-                                              (uint32_t*)nullptr, (int)total, segments, (const int32_t*)nullptr, (const int32_t*)nullptr);
-  return b;
-}
-
 size_t icp_grid_scratch_bytes(int pairs, int J, int K) {
   if (!icp_grid_shape_ok(pairs, J, K)) return 0;
   return layout(pairs, J, K).bytes;
@@ -219,18 +213,17 @@ int icp_grid_build(const float* ref, int stride, const float* cur, int pairs, in
                    hipStream_t st, IcpGrid* out) {
   if (!icp_grid_shape_ok(pairs, J, K) || !icp_grid_radius_ok(r) || !scratch || !out) return (int)hipErrorInvalidValue;
   const IcpGridLayout lay = layout(pairs, J, K);
-  char* base = reinterpret_cast<char*>(scratch);
-  IcpLattice* lat = reinterpret_cast<IcpLattice*>(base + lay.lat);
-  uint32_t* enc = reinterpret_cast<uint32_t*>(base + lay.enc);
-  int32_t* off_ref = reinterpret_cast<int32_t*>(base + lay.off_ref);
-  int32_t* off_qry = reinterpret_cast<int32_t*>(base + lay.off_qry);
-  uint64_t* keys = reinterpret_cast<uint64_t*>(base + lay.keys);
-  float4* sorted = reinterpret_cast<float4*>(base + lay.sorted);
-  int32_t* perm = reinterpret_cast<int32_t*>(base + lay.perm);
-  uint64_t* keys_raw = reinterpret_cast<uint64_t*>(base + lay.keys_raw);
-  uint32_t* vals_raw = reinterpret_cast<uint32_t*>(base + lay.vals_raw);
-  uint32_t* vals = reinterpret_cast<uint32_t*>(base + lay.vals);
-  uint64_t* keys_qry = reinterpret_cast<uint64_t*>(base + lay.keys_qry);
+  IcpLattice* lat = at<IcpLattice>(scratch, lay.lat);
+  uint32_t* enc = at<uint32_t>(scratch, lay.enc);
+  int32_t* off_ref = at<int32_t>(scratch, lay.off_ref);
+  int32_t* off_qry = at<int32_t>(scratch, lay.off_qry);
+  uint64_t* keys = at<uint64_t>(scratch, lay.keys);
+  float4* sorted = at<float4>(scratch, lay.sorted);
+  int32_t* perm = at<int32_t>(scratch, lay.perm);
+  uint64_t* keys_raw = at<uint64_t>(scratch, lay.keys_raw);
+  uint32_t* vals_raw = at<uint32_t>(scratch, lay.vals_raw);
+  uint32_t* vals = at<uint32_t>(scratch, lay.vals);
+  uint64_t* keys_qry = at<uint64_t>(scratch, lay.keys_qry);
   if (hipMemsetAsync(enc, 0xff, (size_t)pairs * 3 * sizeof(uint32_t), st) != hipSuccess ||
       hipMemsetAsync(enc + (size_t)pairs * 3, 0, (size_t)pairs * 3 * sizeof(uint32_t), st) != hipSuccess)
     return (int)hipGetLastError();
@@ -238,11 +231,11 @@ int icp_grid_build(const float* ref, int stride, const float* cur, int pairs, in
   hipLaunchKernelGGL(icp_grid_lattice_kernel, dim3((pairs + 256) / 256), dim3(256), 0, st, (const uint32_t*)enc, pairs, J, K, r, lat, off_ref,
                      off_qry);
   hipLaunchKernelGGL(icp_grid_key_kernel, dim3(blocks_for(K), pairs), dim3(256), 0, st, ref, stride, K, (const IcpLattice*)lat, keys_raw, vals_raw);
-  if (!sort_pairs(base + lay.tmp, lay.tmp_bytes, keys_raw, keys, vals_raw, vals, pairs, K, off_ref, st)) return (int)hipErrorUnknown;
+  if (!sort_pairs(at<char>(scratch, lay.tmp), lay.tmp_bytes, keys_raw, keys, vals_raw, vals, pairs, K, off_ref, st)) return (int)hipErrorUnknown;
   hipLaunchKernelGGL(icp_grid_gather_kernel, dim3(blocks_for(K), pairs), dim3(256), 0, st, ref, stride, K, (const uint32_t*)vals, sorted);
   if (order) {
     hipLaunchKernelGGL(icp_grid_key_kernel, dim3(blocks_for(J), pairs), dim3(256), 0, st, cur, 3, J, (const IcpLattice*)lat, keys_raw, vals_raw);
-    if (!sort_pairs(base + lay.tmp, lay.tmp_bytes, keys_raw, keys_qry, vals_raw, reinterpret_cast<uint32_t*>(perm), pairs, J, off_qry, st))
+    if (!sort_pairs(at<char>(scratch, lay.tmp), lay.tmp_bytes, keys_raw, keys_qry, vals_raw, reinterpret_cast<uint32_t*>(perm), pairs, J, off_qry, st))
       return (int)hipErrorUnknown;
   }
   out->keys = keys; out->sorted = sorted; out->perm = order ? perm : nullptr; out->lat = lat;

@@ -13,6 +13,7 @@
 // Candidates arrive in arbitrary index order, hence the lexicographic insertion.
 #include "kernels.h"
 #include "device_utils.h"
+#include "scratch.h"
 
 namespace dsir {
 
@@ -35,18 +36,15 @@ struct GridScratch {
   static constexpr int cells_for(int n) { return n / 2 + 64; }
   GridScratch(int clouds, int n) : max_cells(cells_for(n)) {
     const size_t c = (size_t)clouds, mc = (size_t)max_cells;
-    size_t p = 0;
-    auto take = [&](size_t b) { const size_t at = p; p += (b + 255) & ~(size_t)255; return at; };
-    gp_at = take(c * sizeof(GridParams));
-    cell_of_at = take(c * n * sizeof(int));
-    counts_at = take(c * mc * sizeof(int));
-    starts_at = take(c * (mc + 1) * sizeof(int));
-    cursor_at = take(c * mc * sizeof(int));
-    sorted_at = take(c * n * sizeof(float4));
-    bytes = p;
+    Carve p;
+    gp_at = p.take(c * sizeof(GridParams));
+    cell_of_at = p.take(c * n * sizeof(int));
+    counts_at = p.take(c * mc * sizeof(int));
+    starts_at = p.take(c * (mc + 1) * sizeof(int));
+    cursor_at = p.take(c * mc * sizeof(int));
+    sorted_at = p.take(c * n * sizeof(float4));
+    bytes = p.p;
   }
-  template <class T> static T* at(void* base, size_t off) { return reinterpret_cast<T*>(static_cast<char*>(base) + off); }
-  template <class T> static const T* at(const void* base, size_t off) { return reinterpret_cast<const T*>(static_cast<const char*>(base) + off); }
   GridParams* gp(void* b) const { return at<GridParams>(b, gp_at); }
   int* cell_of(void* b) const { return at<int>(b, cell_of_at); }
   int* counts(void* b) const { return at<int>(b, counts_at); }

@@ -22,6 +22,8 @@
 #include <stdint.h>
 
 #include "dsir_train.h"
+#include "op_layouts.h"
+#include "seg_sort.h"
 
 namespace dsir {
 namespace {
@@ -152,7 +154,6 @@ __global__ void targets_matches_kernel(const int64_t* __restrict__ keys, const i
 
 inline unsigned grid1(int64_t n) { const int64_t g = (n + 255) / 256; return (unsigned)(g < 1 ? 1 : (g > 8192 ? 8192 : g)); }
 inline int done() { return (int)hipGetLastError(); }
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // reference slices across the grid: enough blocks to fill the chip (about 2048 of 4 waves), no part shorter than one tile
 inline int match_split(int pairs, int J, int K) {
@@ -172,6 +173,11 @@ size_t scan_tmp_bytes(int64_t rows) {
   hipcub::DeviceScan::InclusiveSum(nullptr, b, (const int32_t*)nullptr, (int32_t*)nullptr, (int)rows);
   return b;
 }
+inline BufferTmpLayout radius_layout(int pairs, int J, int K) {
+  const size_t rows = (size_t)pairs * J;
+  return BufferTmpLayout(rows * match_split(pairs, J, K) * NW * sizeof(int32_t), scan_tmp_bytes((int64_t)rows));
+}
+inline BufferTmpLayout keys_layout(int64_t n_matches, size_t sort_tmp) { return BufferTmpLayout((size_t)n_matches * sizeof(int64_t), sort_tmp); }
 
 }  // namespace
 }  // namespace dsir
@@ -181,9 +187,7 @@ using namespace dsir;
 extern "C" {
 
 size_t dsir_t_radius_matches_scratch(int pairs, int J, int K) {
-  if (!match_shape_ok(pairs, J, K, 3)) return 0;
-  const int64_t rows = (int64_t)pairs * J;
-  return align256((size_t)rows * match_split(pairs, J, K) * NW * sizeof(int32_t)) + align256(scan_tmp_bytes(rows));
+  return match_shape_ok(pairs, J, K, 3) ? radius_layout(pairs, J, K).bytes : 0;
 }
 
 int dsir_t_radius_matches_count(void* stream, const float* src, const float* ref, int stride, const float* transform_gt, int pairs, int J,
@@ -193,15 +197,16 @@ int dsir_t_radius_matches_count(void* stream, const float* src, const float* ref
   hipStream_t st = (hipStream_t)stream;
   const int64_t rows = (int64_t)pairs * J;
   const int split = match_split(pairs, J, K), parts = split * NW;
-  int32_t* part = reinterpret_cast<int32_t*>(scratch);
-  void* tmp = reinterpret_cast<char*>(scratch) + align256((size_t)rows * parts * sizeof(int32_t));
+  const BufferTmpLayout lay = radius_layout(pairs, J, K);
+  int32_t* part = at<int32_t>(scratch, lay.buf);
   const float r2 = radius * radius;
   hipLaunchKernelGGL(radius_matches_kernel<false>, dim3((J + QB - 1) / QB, split, pairs), dim3(QB * NW), 0, st, src, ref, stride, transform_gt, J,
                      K, r2, parts, part, (const int32_t*)nullptr, (int32_t*)nullptr, (int64_t)0);
   hipLaunchKernelGGL(row_prefix_kernel, dim3(grid1(rows)), dim3(256), 0, st, part, parts, rows, counts);
   if (hipMemsetAsync(offsets, 0, sizeof(int32_t), st) != hipSuccess) return (int)hipGetLastError();
   size_t tb = scan_tmp_bytes(rows);
-  if (hipcub::DeviceScan::InclusiveSum(tmp, tb, counts, offsets + 1, (int)rows, st) != hipSuccess) return (int)hipErrorUnknown;
+  if (hipcub::DeviceScan::InclusiveSum(at<char>(scratch, lay.tmp), tb, counts, offsets + 1, (int)rows, st) != hipSuccess)
+    return (int)hipErrorUnknown;
   return done();
 }
 
@@ -213,8 +218,9 @@ int dsir_t_radius_matches_fill(void* stream, const float* src, const float* ref,
   if (n_cols == 0) return 0;
   const int split = match_split(pairs, J, K), parts = split * NW;
   const float r2 = radius * radius;
+  int32_t* part = const_cast<int32_t*>(at<int32_t>(scratch, radius_layout(pairs, J, K).buf));
   hipLaunchKernelGGL(radius_matches_kernel<true>, dim3((J + QB - 1) / QB, split, pairs), dim3(QB * NW), 0, (hipStream_t)stream, src, ref, stride,
-                     transform_gt, J, K, r2, parts, const_cast<int32_t*>(reinterpret_cast<const int32_t*>(scratch)), offsets, cols, n_cols);
+                     transform_gt, J, K, r2, parts, part, offsets, cols, n_cols);
   return done();
 }
 
@@ -229,11 +235,7 @@ int dsir_t_inlier_targets_radius(void* stream, const float* src, const float* re
 }
 
 size_t dsir_t_match_keys_scratch(int64_t n_matches, int pairs) {
-  if (n_matches < 1 || n_matches > 0x7fffffffll || pairs < 1) return 0;
-  size_t sort_tmp = 0;
-  hipcub::DeviceSegmentedRadixSort::SortKeys(nullptr, sort_tmp, (const int64_t*)nullptr, (int64_t*)nullptr, (int)n_matches, pairs,
-                                             (const int32_t*)nullptr, (const int32_t*)nullptr);
-  return align256((size_t)n_matches * sizeof(int64_t)) + align256(sort_tmp);
+  return n_matches < 1 || n_matches > 0x7fffffffll || pairs < 1 ? 0 : keys_layout(n_matches, seg_sort_keys_i64_tmp_bytes(n_matches, pairs)).bytes;
 }
 
 int dsir_t_match_keys(void* stream, const int32_t* matches, const int32_t* pair_offsets, int64_t n_matches, int pairs, int64_t hash_seed,
@@ -242,13 +244,12 @@ int dsir_t_match_keys(void* stream, const int32_t* matches, const int32_t* pair_
   if (n_matches == 0) return 0;
   if (!matches || !keys || !scratch) return (int)hipErrorInvalidValue;
   hipStream_t st = (hipStream_t)stream;
-  int64_t* raw = reinterpret_cast<int64_t*>(scratch);
-  void* tmp = reinterpret_cast<char*>(scratch) + align256((size_t)n_matches * sizeof(int64_t));
-  size_t sort_tmp = 0;
-  hipcub::DeviceSegmentedRadixSort::SortKeys(nullptr, sort_tmp, (const int64_t*)raw, keys, (int)n_matches, pairs, pair_offsets, pair_offsets + 1);
+  size_t sort_tmp = seg_sort_keys_i64_tmp_bytes(n_matches, pairs);
+  const BufferTmpLayout lay = keys_layout(n_matches, sort_tmp);
+  int64_t* raw = at<int64_t>(scratch, lay.buf);
   hipLaunchKernelGGL(match_keys_kernel, dim3(grid1(n_matches)), dim3(256), 0, st, matches, n_matches, hash_seed, raw);
-  if (hipcub::DeviceSegmentedRadixSort::SortKeys(tmp, sort_tmp, (const int64_t*)raw, keys, (int)n_matches, pairs, pair_offsets, pair_offsets + 1,
-                                                 0, 64, st) != hipSuccess)
+  if (hipcub::DeviceSegmentedRadixSort::SortKeys(at<char>(scratch, lay.tmp), sort_tmp, (const int64_t*)raw, keys, (int)n_matches, pairs, pair_offsets,
+                                                 pair_offsets + 1, 0, 64, st) != hipSuccess)
     return (int)hipErrorUnknown;
   return done();
 }

@@ -28,12 +28,12 @@
 
 #include "kernels.h"
 #include "screen_bound.h"
+#include "scratch.h"
 
 namespace dsir {
 
 namespace {
 
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 inline int grid_for(int64_t n) { const int64_t g = (n + 255) / 256; return (int)(g < 1 ? 1 : (g > 65535 ? 65535 : g)); }
 
 // bounding box of every cloud's points: one 1024-thread block per cloud
@@ -417,39 +417,38 @@ Layout carve(void* scratch, int pairs, int J, int K) {
   const int rpb = nn_screen_rows_per_block(J);
   const int nrb = (J + rpb - 1) / rpb;
   const size_t nmax = (size_t)pairs * (size_t)(J > K ? J : K);
-  char* p = reinterpret_cast<char*>(scratch);
-  auto take = [&](size_t bytes) { char* r = p; p += align256(bytes); return r; };
+  Carve c;
   Layout L{};
-  L.cols = reinterpret_cast<int32_t*>(take((size_t)pairs * K * 4));
-  L.rows = reinterpret_cast<int32_t*>(take((size_t)pairs * J * 4));
-  L.tstar = reinterpret_cast<int32_t*>(take((size_t)pairs * J * 4));
-  L.tlist = reinterpret_cast<int32_t*>(take((size_t)pairs * nrb * nt * 4));
-  L.tcount = reinterpret_cast<int32_t*>(take((size_t)pairs * nrb * 4));
-  L.queue = reinterpret_cast<int32_t*>(take(8 * 4));
-  L.rborder = reinterpret_cast<int32_t*>(take((size_t)pairs * nrb * 4));
-  L.cen = reinterpret_cast<float*>(take((size_t)pairs * nt * 64 * 4));
-  L.ch = reinterpret_cast<_Float16*>(take((size_t)pairs * nt * 64 * 2));
-  L.cl = reinterpret_cast<_Float16*>(take((size_t)pairs * nt * 64 * 2));
-  L.cn2 = reinterpret_cast<float*>(take((size_t)pairs * nt * 4));
-  L.rad = reinterpret_cast<float*>(take((size_t)pairs * nt * 4));
-  L.T = reinterpret_cast<float*>(take((size_t)pairs * J * 4));
-  L.box = reinterpret_cast<float*>(take((size_t)pairs * 6 * 4));
-  L.k0 = reinterpret_cast<uint32_t*>(take(nmax * 4));
-  L.k1 = reinterpret_cast<uint32_t*>(take(nmax * 4));
-  L.v0 = reinterpret_cast<uint32_t*>(take(nmax * 4));
-  L.v1 = reinterpret_cast<uint32_t*>(take(nmax * 4));
-  L.pbh = reinterpret_cast<_Float16*>(take((size_t)pairs * K * 64 * 2));
-  L.pbl = reinterpret_cast<_Float16*>(take((size_t)pairs * K * 64 * 2));
-  L.psb = reinterpret_cast<float*>(take((size_t)pairs * K * 4));
+  L.cols = at<int32_t>(scratch, c.take((size_t)pairs * K * 4));
+  L.rows = at<int32_t>(scratch, c.take((size_t)pairs * J * 4));
+  L.tstar = at<int32_t>(scratch, c.take((size_t)pairs * J * 4));
+  L.tlist = at<int32_t>(scratch, c.take((size_t)pairs * nrb * nt * 4));
+  L.tcount = at<int32_t>(scratch, c.take((size_t)pairs * nrb * 4));
+  L.queue = at<int32_t>(scratch, c.take(8 * 4));
+  L.rborder = at<int32_t>(scratch, c.take((size_t)pairs * nrb * 4));
+  L.cen = at<float>(scratch, c.take((size_t)pairs * nt * 64 * 4));
+  L.ch = at<_Float16>(scratch, c.take((size_t)pairs * nt * 64 * 2));
+  L.cl = at<_Float16>(scratch, c.take((size_t)pairs * nt * 64 * 2));
+  L.cn2 = at<float>(scratch, c.take((size_t)pairs * nt * 4));
+  L.rad = at<float>(scratch, c.take((size_t)pairs * nt * 4));
+  L.T = at<float>(scratch, c.take((size_t)pairs * J * 4));
+  L.box = at<float>(scratch, c.take((size_t)pairs * 6 * 4));
+  L.k0 = at<uint32_t>(scratch, c.take(nmax * 4));
+  L.k1 = at<uint32_t>(scratch, c.take(nmax * 4));
+  L.v0 = at<uint32_t>(scratch, c.take(nmax * 4));
+  L.v1 = at<uint32_t>(scratch, c.take(nmax * 4));
+  L.pbh = at<_Float16>(scratch, c.take((size_t)pairs * K * 64 * 2));
+  L.pbl = at<_Float16>(scratch, c.take((size_t)pairs * K * 64 * 2));
+  L.psb = at<float>(scratch, c.take((size_t)pairs * K * 4));
   // temporary storage of the two radix sorts: sized for the largest sort over all 32 key bits; every sort asks again for its own
   // size and bit range and refuses to run if the answer exceeds this (sort_pairs)
   size_t tmp = 0;
   if (hipcub::DeviceRadixSort::SortPairs(nullptr, tmp, (const uint32_t*)nullptr, (uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr,
                                          (int)nmax, 0, 32) != hipSuccess)
     tmp = 0;                       // no storage: sort_pairs fails, the caller reports the error
-  L.cub = take(tmp);
+  L.cub = at<char>(scratch, c.take(tmp));
   L.cub_bytes = tmp;
-  L.total = (size_t)(p - reinterpret_cast<char*>(scratch));
+  L.total = c.p;
   return L;
 }
 

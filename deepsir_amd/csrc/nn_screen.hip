@@ -32,6 +32,7 @@
 
 #include "kernels.h"
 #include "screen_bound.h"
+#include "scratch.h"
 
 namespace dsir {
 
@@ -636,15 +637,14 @@ struct ScreenScratch {
   size_t umin, cnt, cand, ovf, packed, rowlist, total;
   ScreenScratch(int pairs, int J) {
     const size_t rows = (size_t)pairs * J;
-    size_t p = 0;
-    auto take = [&](size_t bytes) { const size_t r = p; p += (bytes + 255) & ~(size_t)255; return r; };
-    umin = take(rows * 4);              // row thresholds u32 [rows]
-    cnt = take(rows * 4);               // entry counts i32 [rows]
-    cand = take(rows * CAP * 8);        // entries {col, lower bound} [CAP][rows]
-    ovf = take((size_t)pairs * 4);      // undecidable rows per pair i32 [pairs]
-    packed = take(rows * 8);            // packed results of the exhaustive fallback u64 [rows]
-    rowlist = take(rows * 4);           // list of the undecidable rows i32 [rows]
-    total = p;
+    Carve c;
+    umin = c.take(rows * 4);             // row thresholds u32 [rows]
+    cnt = c.take(rows * 4);              // entry counts i32 [rows]
+    cand = c.take(rows * CAP * 8);       // entries {col, lower bound} [CAP][rows]
+    ovf = c.take((size_t)pairs * 4);     // undecidable rows per pair i32 [pairs]
+    packed = c.take(rows * 8);           // packed results of the exhaustive fallback u64 [rows]
+    rowlist = c.take(rows * 4);          // list of the undecidable rows i32 [rows]
+    total = c.p;
   }
 };
 

@@ -43,6 +43,7 @@
 #include <vector>
 
 #include "cell_index.h"
+#include "seg_sort.h"
 #include "dsir_train.h"
 
 namespace dsir {

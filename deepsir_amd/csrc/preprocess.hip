@@ -3,7 +3,7 @@
 //   * voxel-grid down-sample, voxel average   (open3d voxel_down_sample as called at threeDMatch_loader.py:168-175,
 //                                              kitti_loader.py:335-338; all channels are averaged, as open3d
 //                                              averages points and colours)
-//   * resample to exactly k points            (dataloader/transformation.py:72-93 Resampler / FixedResampler)
+//   * resample to exactly k points            (dataloader/transformation.py:72-93 Resampler / FixedResampler): resample.hip
 //
 // open3d is not installed and its output ORDER is the iteration order of a std::unordered_map, which nothing pins:
 // parity at this boundary is "unpinned" (DESIGN.md).  The rule owned here (and restated in oracle/preprocess.py):
@@ -20,6 +20,7 @@
 
 #include "kernels.h"
 #include "device_utils.h"
+#include "op_layouts.h"
 
 namespace dsir {
 
@@ -124,37 +125,6 @@ __global__ void voxel_average_kernel(const float* __restrict__ pts, const int64_
   }
 }
 
-// ---- resampling
-__global__ void resample_key_kernel(const int32_t* __restrict__ counts, int clouds, int cap, uint64_t seed,
-                                    uint64_t* __restrict__ keys, uint32_t* __restrict__ vals) {
-  const int64_t total = (int64_t)clouds * cap;
-  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
-    const int c = (int)(e / cap), i = (int)(e % cap);
-    const int n = min(counts[c], cap);
-    // 63-bit random key (top bit clear) for real rows, all-ones for padding: padding sorts last
-    keys[e] = i < n ? (splitmix64(seed ^ ((uint64_t)c << 40) ^ (uint64_t)i) >> 1) : kInvalidKey;
-    vals[e] = (uint32_t)i;
-  }
-}
-
-__global__ void resample_gather_kernel(const float* __restrict__ in, const int32_t* __restrict__ counts,
-                                       const uint32_t* __restrict__ perm, int clouds, int cap, int stride, int k, int mode,
-                                       uint64_t seed, float* __restrict__ out) {
-  const int64_t total = (int64_t)clouds * k;
-  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
-    const int c = (int)(e / k), j = (int)(e % k);
-    const int n = min(counts[c], cap);
-    float* o = out + e * stride;
-    if (n <= 0) { for (int ch = 0; ch < stride; ++ch) o[ch] = 0.f; continue; }
-    int srow;
-    if (mode == 1) srow = j % n;                                             // FixedResampler: tile / prefix
-    else if (j < n) srow = (int)perm[(int64_t)c * cap + j];                  // random order, no repeats
-    else srow = (int)(splitmix64(~seed ^ ((uint64_t)c << 40) ^ (uint64_t)j) % (uint64_t)n);   // top-up with replacement
-    const float* s = in + ((int64_t)c * cap + srow) * stride;
-    for (int ch = 0; ch < stride; ++ch) o[ch] = s[ch];
-  }
-}
-
 __global__ void fill_i32_kernel(int32_t* p, int n, int32_t v) {
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) p[i] = v;
 }
@@ -164,50 +134,33 @@ inline int grid_for(int64_t total) {
   return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
 }
 
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-}  // namespace
-
-size_t voxel_downsample_scratch_bytes(int64_t total, int clouds) {
+inline VoxelLayout layout(int64_t total, int clouds) {
   size_t sort_tmp = 0, scan_tmp = 0;
   hipcub::DeviceRadixSort::SortPairs(nullptr, sort_tmp, (const uint64_t*)nullptr, (uint64_t*)nullptr, (const uint32_t*)nullptr,
                                      (uint32_t*)nullptr, (int)total);
   hipcub::DeviceScan::ExclusiveSum(nullptr, scan_tmp, (const int32_t*)nullptr, (int32_t*)nullptr, (int)total);
-  size_t b = 0;
-  b += align256((size_t)(clouds + 1) * sizeof(int64_t));     // offsets (device copy)
-  b += align256((size_t)clouds * 3 * sizeof(float));         // min bounds
-  b += 2 * align256((size_t)total * sizeof(uint64_t));       // keys in / out
-  b += 2 * align256((size_t)total * sizeof(uint32_t));       // vals in / out
-  b += 2 * align256((size_t)total * sizeof(int32_t));        // head, ordinal
-  b += align256((size_t)clouds * sizeof(int32_t));           // first ordinal
-  b += align256(sizeof(int32_t));                            // first row with an unrepresentable voxel index
-  b += align256(sort_tmp > scan_tmp ? sort_tmp : scan_tmp);
-  return b;
+  return VoxelLayout(total, clouds, sort_tmp, scan_tmp);
 }
+
+}  // namespace
+
+size_t voxel_downsample_scratch_bytes(int64_t total, int clouds) { return layout(total, clouds).bytes; }
 
 int launch_voxel_downsample(const float* pts, const int64_t* offsets_host, int clouds, int stride, float voxel,
                             const float* crop_host, int cap, float* out, int32_t* counts, void* scratch, hipStream_t st,
                             const int32_t** bad_row_dev) {
   const int64_t total = offsets_host[clouds];
   if (total <= 0 || total > 0x7fffffffll || stride < 3 || stride > 16 || clouds < 1 || clouds > 1023 || !(voxel > 0.f)) return 1;
-  char* p = reinterpret_cast<char*>(scratch);
-  auto take = [&](size_t bytes) { char* r = p; p += align256(bytes); return r; };
-  int64_t* off = reinterpret_cast<int64_t*>(take((size_t)(clouds + 1) * sizeof(int64_t)));
-  float* minb = reinterpret_cast<float*>(take((size_t)clouds * 3 * sizeof(float)));
-  uint64_t* k0 = reinterpret_cast<uint64_t*>(take((size_t)total * sizeof(uint64_t)));
-  uint64_t* k1 = reinterpret_cast<uint64_t*>(take((size_t)total * sizeof(uint64_t)));
-  uint32_t* v0 = reinterpret_cast<uint32_t*>(take((size_t)total * sizeof(uint32_t)));
-  uint32_t* v1 = reinterpret_cast<uint32_t*>(take((size_t)total * sizeof(uint32_t)));
-  int32_t* head = reinterpret_cast<int32_t*>(take((size_t)total * sizeof(int32_t)));
-  int32_t* ordinal = reinterpret_cast<int32_t*>(take((size_t)total * sizeof(int32_t)));
-  int32_t* first = reinterpret_cast<int32_t*>(take((size_t)clouds * sizeof(int32_t)));
-  int32_t* bad_row = reinterpret_cast<int32_t*>(take(sizeof(int32_t)));
+  const VoxelLayout lay = layout(total, clouds);
+  int64_t* off = at<int64_t>(scratch, lay.off);
+  float* minb = at<float>(scratch, lay.minb);
+  uint64_t *k0 = at<uint64_t>(scratch, lay.k0), *k1 = at<uint64_t>(scratch, lay.k1);
+  uint32_t *v0 = at<uint32_t>(scratch, lay.v0), *v1 = at<uint32_t>(scratch, lay.v1);
+  int32_t *head = at<int32_t>(scratch, lay.head), *ordinal = at<int32_t>(scratch, lay.ordinal);
+  int32_t *first = at<int32_t>(scratch, lay.first), *bad_row = at<int32_t>(scratch, lay.bad_row);
   *bad_row_dev = bad_row;
-  size_t sort_tmp = 0, scan_tmp = 0;
-  hipcub::DeviceRadixSort::SortPairs(nullptr, sort_tmp, k0, k1, v0, v1, (int)total);
-  hipcub::DeviceScan::ExclusiveSum(nullptr, scan_tmp, head, ordinal, (int)total);
-  void* tmp = p;
-  size_t tmp_bytes = sort_tmp > scan_tmp ? sort_tmp : scan_tmp;
+  void* tmp = at<char>(scratch, lay.tmp);                      // the sort's, then the scan's
+  const size_t tmp_bytes = lay.tmp_bytes;
 
   const bool use_crop = crop_host != nullptr;
   const float4 crop = use_crop ? make_float4(crop_host[0], crop_host[1], crop_host[2], crop_host[3]) : make_float4(0, 0, 0, 0);
@@ -226,45 +179,6 @@ int launch_voxel_downsample(const float* pts, const int64_t* offsets_host, int c
   hipLaunchKernelGGL(voxel_cloud_kernel, dim3(grid_for(total)), dim3(256), 0, st, k1, head, ordinal, total, first, counts);
   hipLaunchKernelGGL(voxel_average_kernel, dim3(grid_for(total)), dim3(256), 0, st, pts, off, stride, k1, v1, head, ordinal,
                      first, total, cap, out);
-  return 0;
-}
-
-size_t resample_scratch_bytes(int clouds, int cap) {
-  const int64_t total = (int64_t)clouds * cap;
-  size_t sort_tmp = 0;
-  hipcub::DeviceSegmentedRadixSort::SortPairs(nullptr, sort_tmp, (const uint64_t*)nullptr, (uint64_t*)nullptr,
-                                              (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)total, clouds,
-                                              (const int*)nullptr, (const int*)nullptr);
-  return 2 * align256((size_t)total * 8) + 2 * align256((size_t)total * 4) + align256((size_t)(clouds + 1) * 4) + align256(sort_tmp);
-}
-
-__global__ void seg_offsets_kernel(int* seg, int clouds, int cap) {
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i <= clouds; i += gridDim.x * blockDim.x) seg[i] = i * cap;
-}
-
-int launch_resample(const float* in, const int32_t* counts, int clouds, int cap, int stride, int k, int mode, uint64_t seed,
-                    float* out, void* scratch, hipStream_t st) {
-  const int64_t total = (int64_t)clouds * cap;
-  if (total <= 0 || total > 0x7fffffffll || k < 1 || stride < 1) return 1;
-  char* p = reinterpret_cast<char*>(scratch);
-  auto take = [&](size_t bytes) { char* r = p; p += align256(bytes); return r; };
-  uint64_t* k0 = reinterpret_cast<uint64_t*>(take((size_t)total * 8));
-  uint64_t* k1 = reinterpret_cast<uint64_t*>(take((size_t)total * 8));
-  uint32_t* v0 = reinterpret_cast<uint32_t*>(take((size_t)total * 4));
-  uint32_t* v1 = reinterpret_cast<uint32_t*>(take((size_t)total * 4));
-  int* seg = reinterpret_cast<int*>(take((size_t)(clouds + 1) * 4));
-  const uint32_t* perm = v0;
-  if (mode == 0) {
-    size_t sort_tmp = 0;
-    hipcub::DeviceSegmentedRadixSort::SortPairs(nullptr, sort_tmp, k0, k1, v0, v1, (int)total, clouds, seg, seg + 1);
-    hipLaunchKernelGGL(seg_offsets_kernel, dim3(1), dim3(256), 0, st, seg, clouds, cap);
-    hipLaunchKernelGGL(resample_key_kernel, dim3(grid_for(total)), dim3(256), 0, st, counts, clouds, cap, seed, k0, v0);
-    if (hipcub::DeviceSegmentedRadixSort::SortPairs(p, sort_tmp, k0, k1, v0, v1, (int)total, clouds, seg, seg + 1, 0, 64, st) != hipSuccess)
-      return 2;
-    perm = v1;
-  }
-  hipLaunchKernelGGL(resample_gather_kernel, dim3(grid_for((int64_t)clouds * k)), dim3(256), 0, st, in, counts, perm, clouds, cap,
-                     stride, k, mode, seed, out);
   return 0;
 }
 

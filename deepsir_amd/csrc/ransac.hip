@@ -325,8 +325,6 @@ __global__ __launch_bounds__(256) void corr_compact_kernel(const int32_t* __rest
   if (tid == 0) counts[pair] = base;
 }
 
-inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // slices of a scoring launch: at least two workgroups per CU where the problem allows it, whole chunks per slice
 inline int chunks_per_slice(int M, int hyp_blocks, int pairs) {
   const int nch = (M + CH - 1) / CH;
@@ -347,32 +345,14 @@ void launch_score(const float* cs, const float* cq, const int32_t* counts, int p
 
 }  // namespace
 
-size_t pose_scratch_bytes(int pairs, int M, int refine_iters) {
-  const size_t P = (size_t)pairs;
-  return 2 * al256(P * M * 12) + al256(P * M * 4) + al256(P * (refine_iters + 1) * 48) + al256(P * (refine_iters + 1) * 4) + al256(P * 16);
-}
-
-PoseScratch pose_scratch_take(char*& p, int pairs, int M, int refine_iters) {
-  const size_t P = (size_t)pairs;
-  auto take = [&](size_t bytes) { char* r = p; p += al256(bytes); return r; };
-  PoseScratch s;
-  s.cs = reinterpret_cast<float*>(take(P * M * 12));
-  s.cq = reinterpret_cast<float*>(take(P * M * 12));
-  s.w = reinterpret_cast<float*>(take(P * M * 4));
-  s.Tcand = reinterpret_cast<float*>(take(P * (refine_iters + 1) * 48));
-  s.cnt = reinterpret_cast<int32_t*>(take(P * (refine_iters + 1) * 4));
-  s.info = reinterpret_cast<int32_t*>(take(P * 16));
-  return s;
-}
-
 void launch_ransac_gather(const float* src, const float* ref, int pairs, int J, int K, int stride, const int32_t* corr,
-                          const int32_t* counts, int M, const PoseScratch& s, int32_t* invalid, hipStream_t st) {
+                          const int32_t* counts, int M, const PoseParts& s, int32_t* invalid, hipStream_t st) {
   hipMemsetAsync(invalid, 0, (size_t)pairs * 4, st);
   hipLaunchKernelGGL(ransac_gather_kernel, dim3((M + 255) / 256, pairs), dim3(256), 0, st, src, ref, J, K, stride, corr, counts, M, s.cs,
                      s.cq, invalid);
 }
 
-void launch_ransac_tail(const PoseScratch& s, const int32_t* counts, int pairs, int M, const float* hyp_T, const int32_t* hyp_valid,
+void launch_ransac_tail(const PoseParts& s, const int32_t* counts, int pairs, int M, const float* hyp_T, const int32_t* hyp_valid,
                         int32_t* hyp_count, int H, int R, float thr2, const float* T_init, float* T_out, double* stats, hipStream_t st) {
   const int P = pairs;
   const dim3 gm((M + 255) / 256, P);
@@ -395,20 +375,14 @@ void launch_ransac_tail(const PoseScratch& s, const int32_t* counts, int pairs, 
                      stats);
 }
 
-// P (M 28 + H 56) bytes for the matched points, weights and hypotheses, plus a few hundred bytes per pair of round state
-size_t ransac_scratch_bytes(int pairs, int M, int H, int refine_iters) {
-  const size_t P = (size_t)pairs;
-  return pose_scratch_bytes(pairs, M, refine_iters) + al256(P * H * 48) + 2 * al256(P * H * 4);
-}
+size_t ransac_scratch_bytes(int pairs, int M, int H, int refine_iters) { return RansacLayout(pairs, M, H, refine_iters).bytes; }
 
 void launch_ransac(const RansacArgs& a, void* scratch, hipStream_t st) {
   const int P = a.pairs, M = a.M, H = a.hypotheses, R = a.refine_iters;
-  char* p = reinterpret_cast<char*>(scratch);
-  auto take = [&](size_t bytes) { char* r = p; p += al256(bytes); return r; };
-  const PoseScratch s = pose_scratch_take(p, P, M, R);
-  float* hyp_T = reinterpret_cast<float*>(take((size_t)P * H * 48));
-  int32_t* hyp_valid = reinterpret_cast<int32_t*>(take((size_t)P * H * 4));
-  int32_t* hyp_count = reinterpret_cast<int32_t*>(take((size_t)P * H * 4));
+  const RansacLayout lay(P, M, H, R);
+  const PoseParts s(scratch, lay.pose);
+  float* hyp_T = at<float>(scratch, lay.hyp_T);
+  int32_t *hyp_valid = at<int32_t>(scratch, lay.hyp_valid), *hyp_count = at<int32_t>(scratch, lay.hyp_count);
   const float thr2 = a.max_dist * a.max_dist;   // fp32 product (the build keeps contraction off)
 
   launch_ransac_gather(a.src, a.ref, P, a.J, a.K, a.stride, a.corr, a.counts, M, s, a.invalid, st);

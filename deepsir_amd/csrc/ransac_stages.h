@@ -8,6 +8,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "op_layouts.h"
 #include "svd3.h"
 
 namespace dsir {
@@ -41,23 +42,21 @@ __device__ inline void fit_rows64(int n, PS ps, PQ pq, float* T) {
   }
 }
 
-// the scratch both pose stages share: matched points, refit weights, round state
-struct PoseScratch {
-  float* cs; float* cq;   // [P][M][3]
-  float* w;               // [P][M]
-  float* Tcand;           // [R + 1][P][12]
-  int32_t* cnt;           // [R + 1][P]
-  int32_t* info;          // [4][P]
+// the parts of PoseLayout (op_layouts.h: the head of both pose stages' scratch) as the pointers the launchers below read
+struct PoseParts {
+  float *cs, *cq, *w, *Tcand;
+  int32_t *cnt, *info;
+  PoseParts(void* scratch, const PoseLayout& l)
+      : cs(at<float>(scratch, l.cs)), cq(at<float>(scratch, l.cq)), w(at<float>(scratch, l.w)), Tcand(at<float>(scratch, l.Tcand)),
+        cnt(at<int32_t>(scratch, l.cnt)), info(at<int32_t>(scratch, l.info)) {}
 };
-size_t pose_scratch_bytes(int pairs, int M, int refine_iters);
-PoseScratch pose_scratch_take(char*& p, int pairs, int M, int refine_iters);
 
 // clamp, flag (bit 2 of invalid, zeroed here), gather, park
 void launch_ransac_gather(const float* src, const float* ref, int pairs, int J, int K, int stride, const int32_t* corr,
-                          const int32_t* counts, int M, const PoseScratch& s, int32_t* invalid, hipStream_t st);
+                          const int32_t* counts, int M, const PoseParts& s, int32_t* invalid, hipStream_t st);
 // H candidate poses per pair (hyp_T [P][H][12], hyp_valid [P][H]) -> their inlier counts (hyp_count [P][H], zeroed here), the pick
 // (largest count, ties to the lower h), R refit rounds, T_out and stats
-void launch_ransac_tail(const PoseScratch& s, const int32_t* counts, int pairs, int M, const float* hyp_T, const int32_t* hyp_valid,
+void launch_ransac_tail(const PoseParts& s, const int32_t* counts, int pairs, int M, const float* hyp_T, const int32_t* hyp_valid,
                         int32_t* hyp_count, int H, int R, float thr2, const float* T_init, float* T_out, double* stats, hipStream_t st);
 
 }  // namespace dsir

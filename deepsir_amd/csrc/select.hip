@@ -9,12 +9,13 @@
 
 #include "kernels.h"
 #include "device_utils.h"
+#include "op_layouts.h"
+#include "seg_sort.h"
 
 namespace dsir {
 
 namespace {
 
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 inline int grid_for(int64_t n) { const int64_t g = (n + 255) / 256; return (int)(g < 1 ? 1 : (g > 65535 ? 65535 : g)); }
 
 // ascending key order == descending score order
@@ -26,10 +27,6 @@ __global__ void topk_key_kernel(const float* __restrict__ score, int64_t total, 
     key[i] = ~b;
     val[i] = (uint32_t)(i % n);
   }
-}
-
-__global__ void seg_offsets_kernel(int* seg, int clouds, int n) {
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i <= clouds; i += gridDim.x * blockDim.x) seg[i] = i * n;
 }
 
 __global__ void topk_take_kernel(const uint32_t* __restrict__ sorted_val, const float* __restrict__ score, int clouds, int n,
@@ -80,29 +77,21 @@ __global__ __launch_bounds__(256) void l2norm64_kernel(const float* __restrict__
 }  // namespace
 
 size_t topk_scratch_bytes(int clouds, int n) {
-  const int64_t total = (int64_t)clouds * n;
-  size_t sort_tmp = 0;
-  hipcub::DeviceSegmentedRadixSort::SortPairs(nullptr, sort_tmp, (const uint32_t*)nullptr, (uint32_t*)nullptr,
-                                              (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)total, clouds,
-                                              (const int*)nullptr, (const int*)nullptr);
-  return 4 * align256((size_t)total * 4) + align256((size_t)(clouds + 1) * 4) + align256(sort_tmp);
+  return SegSortLayout(clouds, n, 4, seg_sort_pairs_u32_tmp_bytes((int64_t)clouds * n, clouds)).bytes;
 }
 
 int launch_topk(const float* score, int clouds, int n, int k, int32_t* idx_out, float* score_out, void* scratch, hipStream_t st) {
   const int64_t total = (int64_t)clouds * n;
   if (total <= 0 || total > 0x7fffffffll || k < 1 || k > n) return 1;
-  char* p = reinterpret_cast<char*>(scratch);
-  auto take = [&](size_t bytes) { char* r = p; p += align256(bytes); return r; };
-  uint32_t* k0 = reinterpret_cast<uint32_t*>(take((size_t)total * 4));
-  uint32_t* k1 = reinterpret_cast<uint32_t*>(take((size_t)total * 4));
-  uint32_t* v0 = reinterpret_cast<uint32_t*>(take((size_t)total * 4));
-  uint32_t* v1 = reinterpret_cast<uint32_t*>(take((size_t)total * 4));
-  int* seg = reinterpret_cast<int*>(take((size_t)(clouds + 1) * 4));
-  size_t sort_tmp = 0;
-  hipcub::DeviceSegmentedRadixSort::SortPairs(nullptr, sort_tmp, k0, k1, v0, v1, (int)total, clouds, seg, seg + 1);
-  hipLaunchKernelGGL(seg_offsets_kernel, dim3(1), dim3(256), 0, st, seg, clouds, n);
+  size_t sort_tmp = seg_sort_pairs_u32_tmp_bytes(total, clouds);
+  const SegSortLayout lay(clouds, n, 4, sort_tmp);
+  uint32_t *k0 = at<uint32_t>(scratch, lay.k0), *k1 = at<uint32_t>(scratch, lay.k1);
+  uint32_t *v0 = at<uint32_t>(scratch, lay.v0), *v1 = at<uint32_t>(scratch, lay.v1);
+  int* seg = at<int>(scratch, lay.seg);
+  launch_seg_offsets(seg, clouds, n, st);
   hipLaunchKernelGGL(topk_key_kernel, dim3(grid_for(total)), dim3(256), 0, st, score, total, n, k0, v0);
-  if (hipcub::DeviceSegmentedRadixSort::SortPairs(p, sort_tmp, k0, k1, v0, v1, (int)total, clouds, seg, seg + 1, 0, 32, st) != hipSuccess)
+  if (hipcub::DeviceSegmentedRadixSort::SortPairs(at<char>(scratch, lay.tmp), sort_tmp, k0, k1, v0, v1, (int)total, clouds, seg, seg + 1, 0, 32,
+                                                  st) != hipSuccess)
     return 2;
   hipLaunchKernelGGL(topk_take_kernel, dim3(grid_for((int64_t)clouds * k)), dim3(256), 0, st, v1, score, clouds, n, k, idx_out,
                      score_out);
@@ -131,32 +120,31 @@ __global__ __launch_bounds__(256) void plan_offsets_kernel(const uint32_t* __res
     offsets[d] = (int32_t)lo;
   }
 }
+inline size_t plan_sort_tmp_bytes(int64_t total) {
+  size_t b = 0;
+  hipcub::DeviceRadixSort::SortPairs(nullptr, b, (const uint32_t*)nullptr, (uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr,
+                                     (int)total);
+  return b;
+}
 }  // namespace
 
 // The inverse of a gather index (train_ops.hip: the backward of gather_neighbour / nearest_interpolation / random_sample is a sum
 // over the SOURCES of every destination row): order = the sources grouped by destination, ascending source inside a group (one
 // stable radix sort of (destination, source) pairs - a library sort, not the hot path), offsets = the groups' bounds.  With it the
 // backward operators sum in a fixed order instead of racing float atomics.
-size_t scatter_plan_scratch_bytes(int64_t total) {
-  size_t sort_tmp = 0;
-  hipcub::DeviceRadixSort::SortPairs(nullptr, sort_tmp, (const uint32_t*)nullptr, (uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr,
-                                     (int)total);
-  return 3 * align256((size_t)total * 4) + align256(sort_tmp);
-}
+size_t scatter_plan_scratch_bytes(int64_t total) { return ScatterPlanLayout(total, plan_sort_tmp_bytes(total)).bytes; }
 int launch_scatter_plan(const int32_t* idx, int m, int clouds, int n, int32_t* order, int32_t* offsets, void* scratch, hipStream_t st) {
   const int64_t total = (int64_t)clouds * m, dests = (int64_t)clouds * n;
   if (total <= 0 || total > 0x7fffffffll || dests > 0x7fffffffll) return 1;
-  char* p = reinterpret_cast<char*>(scratch);
-  auto take = [&](size_t bytes) { char* r = p; p += align256(bytes); return r; };
-  uint32_t* k0 = reinterpret_cast<uint32_t*>(take((size_t)total * 4));
-  uint32_t* k1 = reinterpret_cast<uint32_t*>(take((size_t)total * 4));
-  uint32_t* v0 = reinterpret_cast<uint32_t*>(take((size_t)total * 4));
-  size_t sort_tmp = 0;
-  hipcub::DeviceRadixSort::SortPairs(nullptr, sort_tmp, k0, k1, v0, reinterpret_cast<uint32_t*>(order), (int)total);
+  size_t sort_tmp = plan_sort_tmp_bytes(total);
+  const ScatterPlanLayout lay(total, sort_tmp);
+  uint32_t *k0 = at<uint32_t>(scratch, lay.k0), *k1 = at<uint32_t>(scratch, lay.k1), *v0 = at<uint32_t>(scratch, lay.v0);
   int bits = 1;
   while (((int64_t)1 << bits) < dests) ++bits;
   hipLaunchKernelGGL(plan_key_kernel, dim3(grid_for(total)), dim3(256), 0, st, idx, total, m, n, k0, v0);
-  if (hipcub::DeviceRadixSort::SortPairs(p, sort_tmp, k0, k1, v0, reinterpret_cast<uint32_t*>(order), (int)total, 0, bits, st) != hipSuccess) return 2;
+  if (hipcub::DeviceRadixSort::SortPairs(at<char>(scratch, lay.tmp), sort_tmp, k0, k1, v0, reinterpret_cast<uint32_t*>(order), (int)total, 0, bits,
+                                         st) != hipSuccess)
+    return 2;
   hipLaunchKernelGGL(plan_offsets_kernel, dim3(grid_for(dests + 1)), dim3(256), 0, st, k1, total, dests, offsets);
   return 0;
 }

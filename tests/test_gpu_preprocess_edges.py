@@ -1,4 +1,4 @@
-"""csrc/preprocess.hip (crop, voxel average, resample) against oracle/preprocess.py, bit for bit, at the edges that
+"""csrc/preprocess.hip and csrc/resample.hip (crop, voxel average, resample) against oracle/preprocess.py, bit for bit, at the edges that
 tests/preprocess_cases.py builds: strides 3 to 16, clouds of 0 / 1 / 2 / 1025 points, one voxel holding a whole cloud, points on
 voxel faces and on the crop's thresholds, a crop that leaves nothing, cap below the voxel count, the last representable voxel index
 and the first unrepresentable one, non-finite coordinates, 1000 clouds in one call.  tests/test_preprocess_host.py holds the oracle
@@ -121,6 +121,40 @@ def test_resample_three_clouds(eng, k, stride):
 @pytest.mark.parametrize("k", P.RESAMPLE_KS)
 def test_resample_thousand_clouds(eng, k, stride):
     _check_resample(eng, 1000, 8, k, stride, _SEEDS)
+
+
+@pytest.mark.parametrize("counts", [(0, 1, 8), (5, 8, 9)])
+@pytest.mark.parametrize("stride", [3, 6])
+def test_both_resample_entries_share_one_body(eng, stride, counts):
+    """dsir_resample and dsir_t_resample_keyed run the same two kernels (csrc/resample.hip) with different draws: the engine's entry
+    in both modes against the oracle, the loader's entry in its three modes against augment.resample_rows, at 3 clouds of cap 8 with
+    an empty cloud, a single row, a full cloud and a count above cap, k below, at and above the counts."""
+    from deepsir_amd import augment as A
+    cap, seed, epoch, indices = 8, 11, 4, [5, 900, 10 ** 9]
+    table = np.random.default_rng(stride * 10 + counts[0]).uniform(-9, 9, (3, cap, stride)).astype(np.float32)
+    dv, dc = torch.from_numpy(table).to("cuda:0"), torch.tensor(counts, dtype=torch.int32, device="cuda:0")
+    live = [min(n, cap) for n in counts]
+    cfgs = {A.RESAMPLE_RANDOM: A.AugmentConfig(variant="v1", fixed=False), A.RESAMPLE_FIXED: A.AugmentConfig(variant="v1", fixed=True),
+            A.RESAMPLE_PERMUTED_FIXED: A.AugmentConfig(variant="v2", permute=True)}
+    assert sorted(cfgs) == [0, 1, 2]
+    for k in (1, 5, 8, 11):
+        for mode in ("random", "fixed"):
+            out = eng.resample(dv, dc, k, seed=seed, mode=mode).cpu().numpy()
+            for c in range(3):
+                assert np.array_equal(out[c], resample(table[c, :live[c]], k, c, seed, mode)), (k, mode, c)
+        for rmode, cfg in cfgs.items():
+            src, ref, _, _, rows_s, rows_r = eng.augment(dv, dc, dv, dc, None, cfg, seed, epoch, indices, k, return_rows=True)
+            for side, (pts, rows) in enumerate(((src, rows_s), (ref, rows_r))):
+                pts, rows = pts.cpu().numpy(), rows.cpu().numpy()
+                for c in range(3):
+                    prm = A.pair_params(cfg, seed, epoch, indices[c])[side]
+                    assert prm.resample_mode == rmode
+                    want = A.resample_rows(prm.key, live[c], k, rmode)
+                    assert np.array_equal(rows[c], want), (k, rmode, side, c)
+                    if live[c] == 0:
+                        assert not pts[c].any()
+                    else:
+                        assert np.array_equal(pts[c][:, 3:], table[c][want][:, 3:]), (k, rmode, side, c)    # untouched columns
 
 
 @pytest.mark.parametrize("name", ["empty_members", "crop_removes_all"])

@@ -198,3 +198,15 @@ def test_host_only_icp_grid_check(tmp_path):
     assert r.returncode == 0, r.stdout + r.stderr
     r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0 and "icp_grid: " in r.stdout, r.stdout + r.stderr
+
+
+def test_host_only_scratch_layout_check(tmp_path):
+    """csrc/scratch.h and csrc/op_layouts.h compile as plain host C++ and their stand-alone check passes (tools/scratch_layout_check.cpp:
+    every layout's parts in order, on 256 bytes, inside `bytes`, and `bytes` equal to the sums the size functions used to spell out)."""
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    exe = str(tmp_path / "scratch_layout_check")
+    r = subprocess.run([hipcc, "-x", "c++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "deepsir_amd", "csrc"),
+                        os.path.join(ROOT, "tools", "scratch_layout_check.cpp"), "-o", exe], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and "scratch_layout: " in r.stdout, r.stdout + r.stderr
