@@ -218,10 +218,12 @@ __device__ __forceinline__ float att_pool_tile(const f32x4& acc, const float (&f
   return o * __builtin_amdgcn_rcpf(se);   // se >= 1 (the max term contributes e^0): v_rcp_f32 is 1 ulp there
 }
 
-// Order-preserving float max through integer atomics (target initialised to -inf).
+// Order-preserving float max through integer atomics (target initialised to -inf).  The branch is taken on the SIGN BIT, not on
+// v >= 0: -0.0 compares >= 0 but its pattern is INT_MIN, which a signed max loses even to the -inf preset; as an unsigned min it
+// beats every negative number and yields to every value without a sign bit.
 __device__ __forceinline__ void atomic_max_float(float* addr, float v) {
-  if (v >= 0.f) atomicMax(reinterpret_cast<int*>(addr), __float_as_int(v));
-  else          atomicMin(reinterpret_cast<unsigned int*>(addr), __float_as_uint(v));
+  if (!(__float_as_uint(v) & 0x80000000u)) atomicMax(reinterpret_cast<int*>(addr), __float_as_int(v));
+  else                                     atomicMin(reinterpret_cast<unsigned int*>(addr), __float_as_uint(v));
 }
 
 

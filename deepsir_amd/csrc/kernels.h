@@ -262,7 +262,7 @@ void split_weights_f16(const float* w, size_t n, uint16_t* hi, uint16_t* lo);   
 
 // select.hip — feat / label pipelines (model.py:650-651, :682-697)
 size_t topk_scratch_bytes(int clouds, int n);
-// idx_out [clouds][k] = the k highest scores of every cloud, descending, ties in ascending index; score_out optional
+// idx_out [clouds][k] = the k highest scores of every cloud, descending, ties in ascending index, NaNs first; score_out optional
 int launch_topk(const float* score, int clouds, int n, int k, int32_t* idx_out, float* score_out, void* scratch, hipStream_t st);
 // inverse of a gather index [clouds][m] into [clouds][n]: order [clouds * m] (sources by destination, ascending inside), offsets [clouds * n + 1]
 size_t scatter_plan_scratch_bytes(int64_t total);

@@ -3,7 +3,8 @@
 //                                                     gather_neighbour_V3 of xyz / feat / label)
 //   * F.normalize(x, p=2, dim=channels)             (network/model.py:650-651)
 // torch.topk leaves the order of equal scores unspecified; the rule owned here (and restated in the oracle):
-// descending score, equal scores (+0 == -0) in ascending point index.  The sort itself is a library call
+// descending score, equal scores (+0 == -0) in ascending point index, a NaN of either sign before every number and NaNs among
+// themselves in ascending point index (what torch.sort(descending=True, stable=True) does).  The sort itself is a library call
 // (hipCUB segmented radix sort, stable), not the hot path.
 #include <hipcub/hipcub.hpp>
 
@@ -22,9 +23,10 @@ inline int grid_for(int64_t n) { const int64_t g = (n + 255) / 256; return (int)
 __global__ void topk_key_kernel(const float* __restrict__ score, int64_t total, int n, uint32_t* __restrict__ key,
                                 uint32_t* __restrict__ val) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    uint32_t b = __float_as_uint(score[i] + 0.0f);            // -0 -> +0
+    const float s = score[i];
+    uint32_t b = __float_as_uint(s + 0.0f);                   // -0 -> +0
     b = (b & 0x80000000u) ? ~b : (b | 0x80000000u);           // monotone float -> uint
-    key[i] = ~b;
+    key[i] = s != s ? 0u : ~b;                                // every NaN takes the one key no number has (+inf: 0x007fffff)
     val[i] = (uint32_t)(i % n);
   }
 }

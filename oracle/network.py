@@ -169,7 +169,8 @@ class OracleNet:
         """Network.forward of the 'feat' / 'label' pipelines = forward_pair without return_flag
         (model.py:173-179, :609-666) incl. feat_score's top-num_sub selection (:682-697).
         torch.topk's order among equal scores is unspecified; the rule here (and in select.hip) is
-        descending score, equal scores in ascending index (stable sort)."""
+        descending score, equal scores (+0 == -0) in ascending index, a NaN of either sign before every number and
+        NaNs among themselves in ascending index (torch's stable descending sort)."""
         ep: Dict[str, torch.Tensor] = {}
         sides = {}
         for s, k in (("src", "points_src"), ("ref", "points_ref")):
