@@ -90,6 +90,8 @@ SYMBOLS = {
     "dsir_ppf_pre": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
     "dsir_estimate_normals": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int, c_float_p, C.c_void_p,
                                         C.c_void_p]),
+    "dsir_estimate_normals_csr": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, c_float_p, C.c_void_p,
+                                            C.c_void_p]),
     "dsir_fpfh": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                             C.c_void_p, C.c_int, C.c_void_p]),
     "dsir_score": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
@@ -244,6 +246,12 @@ SYMBOLS = {
     "dsir_t_nn_within_scratch": (C.c_size_t, [C.c_int64]),
     "dsir_t_nn_within": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_float, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p]),
+    # neighbour lists over the same index (csrc/radius_nn.hip)
+    "dsir_t_nn_radius_scratch": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "dsir_t_nn_radius_count": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_float, C.c_void_p,
+                                         C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dsir_t_nn_radius_fill": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_float, C.c_void_p,
+                                        C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
     # top-k descriptor search and the correspondences built on it (csrc/nn_topk.hip)
     "dsir_nn_match_topk": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "dsir_nn_match_topk_splits": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),

@@ -49,6 +49,10 @@ DSIR_CELL_HD uint64_t point_key(float x, float y, float z, const CellLattice& L)
   return cell_key(cx < 0 ? 0 : (cx > MAXC ? MAXC : cx), cy < 0 ? 0 : (cy > MAXC ? MAXC : cy), cz < 0 ? 0 : (cz > MAXC ? MAXC : cz));
 }
 
+// the lattice of overlap.hip's index (searched by radius_nn.hip too): the cell edge r (1 + 2^-10) in fp64, the origin the bounds' minimum
+inline double nn_cell_edge(float r) { return (double)r * (1.0 + 1.0 / 1024.0); }
+inline CellLattice nn_lattice(const float* bounds, float r) { return CellLattice{(double)bounds[0], (double)bounds[1], (double)bounds[2], nn_cell_edge(r)}; }
+
 // overlap.hip's index inside its one allocation, from (total, fragments) and the sort's temporary size: _scratch, _build, _within
 struct IndexLayout {
   size_t keys, sorted, box, off, keys_raw, vals_raw, vals, tmp, tmp_bytes, bytes;

@@ -312,6 +312,19 @@ int dsir_estimate_normals(dsir_ctx* c, const float* points, int stride, const in
   return 0;
 }
 
+int dsir_estimate_normals_csr(dsir_ctx* c, const float* points, int stride, const int32_t* csr_offsets, const int32_t* csr_cols, int clouds,
+                              int n, const float* viewpoint, float* normals, int32_t* flags) {
+  if (!c) return 1;
+  HIP_OK(c, hipSetDevice(c->device));
+  if (!points || !csr_offsets || !csr_cols || !normals || clouds < 1 || clouds > 65535 || n < 1 || stride < 3)
+    return fail(c, "dsir_estimate_normals_csr: bad arguments");
+  const float v[3] = {viewpoint ? viewpoint[0] : 0.f, viewpoint ? viewpoint[1] : 0.f, viewpoint ? viewpoint[2] : 0.f};
+  launch_estimate_normals_csr(points, (int64_t)n * stride, stride, csr_offsets, csr_cols, n, clouds, v[0], v[1], v[2], normals, flags, c->stream);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(c, "HIP launch error: %s", hipGetErrorString(e));
+  return 0;
+}
+
 int dsir_fpfh(dsir_ctx* c, const float* points, int stride, const float* normals, const int32_t* neigh, int64_t neigh_cs,
               const int32_t* csr_offsets, const int32_t* csr_cols, int clouds, int n, float* desc, int out_ld, int32_t* flags) {
   if (!c) return 1;

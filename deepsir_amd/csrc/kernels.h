@@ -193,6 +193,9 @@ bool launch_ppf_pre(const PpfArgs& a, hipStream_t st);                // false: 
 // flags [clouds][n] (1: degenerate neighbourhood, normal (0,0,0))
 void launch_estimate_normals(const float* pts, int64_t pts_cs, int stride, const int32_t* neigh, int64_t neigh_cs, int n, int clouds,
                              float vx, float vy, float vz, float* normals, int32_t* flags, hipStream_t st);
+// the same from a CSR with cloud-local columns (offsets [clouds n + 1], the form launch_fpfh takes): a row's entries in row order
+void launch_estimate_normals_csr(const float* pts, int64_t pts_cs, int stride, const int32_t* offsets, const int32_t* cols, int n, int clouds,
+                                 float vx, float vy, float vz, float* normals, int32_t* flags, hipStream_t st);
 
 // fpfh.hip - FPFH descriptors from points, normals and neighbour lists (the rule: the file's header).  One body serves both list
 // forms: a row is cols[start(i) .. start(i) + deg(i)); offsets == nullptr: the fixed form, start = cloud * neigh_cs + 16 i, deg = 16.

@@ -54,8 +54,6 @@ constexpr int64_t MAX_CELLS = (1ll << 21) - 2;      // per axis
 constexpr int64_t MAX_POINTS = 1ll << 30;
 constexpr int MAX_FRAGMENTS = 1 << 20;
 
-inline double cell_edge(float r) { return (double)r * (1.0 + 1.0 / 1024.0); }
-
 // enc [6]: min xyz, max xyz of the finite rows, as ordered integers (integer atomics: order-independent)
 __global__ void finite_bounds_kernel(const float* __restrict__ pts, int stride, int64_t n, uint32_t* __restrict__ enc) {
   finite_bounds_accumulate(pts, stride, n, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x, enc, enc + 3);
@@ -186,7 +184,7 @@ const char* check(const int64_t* offsets, int F, const int32_t* jobs, int64_t n_
   for (int f = 0; f < F; ++f)
     if (offsets[f + 1] < offsets[f]) return "nn_within: offsets must ascend";
   if (offsets[F] > MAX_POINTS) return "nn_within: more than 2^30 points in one call";
-  const double h = cell_edge(radius);
+  const double h = nn_cell_edge(radius);
   for (int a = 0; a < 3; ++a) {
     if (!isfinite(bounds[a]) || !isfinite(bounds[3 + a]) || bounds[a] > bounds[3 + a]) return "nn_within: bounds must be finite, min <= max";
     if (floor(((double)bounds[3 + a] - (double)bounds[a]) / h) + 1.0 > (double)MAX_CELLS)
@@ -206,8 +204,6 @@ const char* check(const int64_t* offsets, int F, const int32_t* jobs, int64_t n_
   }
   return nullptr;
 }
-
-inline CellLattice lattice(const float* bounds, float radius) { return CellLattice{(double)bounds[0], (double)bounds[1], (double)bounds[2], cell_edge(radius)}; }
 
 }  // namespace
 }  // namespace dsir
@@ -257,7 +253,7 @@ int dsir_t_nn_index_build(void* stream, const float* points, int stride, const i
   for (int f = 0; f <= fragments; ++f) off32[f] = (int32_t)offsets[f];
   if (hipMemcpyAsync(off, off32.data(), off32.size() * sizeof(int32_t), hipMemcpyHostToDevice, st) != hipSuccess) return (int)hipGetLastError();
   if (total > 0) {
-    hipLaunchKernelGGL(nn_key_kernel, dim3(grid1(total)), dim3(256), 0, st, points, stride, off, fragments, total, lattice(bounds, radius),
+    hipLaunchKernelGGL(nn_key_kernel, dim3(grid1(total)), dim3(256), 0, st, points, stride, off, fragments, total, nn_lattice(bounds, radius),
                        keys_raw, vals_raw);
     size_t tb = lay.tmp_bytes;
     if (hipcub::DeviceSegmentedRadixSort::SortPairs(base + lay.tmp, tb, (const uint64_t*)keys_raw, keys, (const uint32_t*)vals_raw, vals,
@@ -304,7 +300,7 @@ int dsir_t_nn_within(void* stream, const void* index, const int64_t* offsets, in
     hipLaunchKernelGGL(nn_within_kernel, dim3(blocks), dim3(NN_BLOCK), 0, st, reinterpret_cast<const uint64_t*>(base + lay.keys),
                        reinterpret_cast<const float4*>(base + lay.sorted), reinterpret_cast<const int32_t*>(base + lay.box),
                        reinterpret_cast<const int32_t*>(base + lay.off), dtab, dtab + 2 * n_jobs, dtab + 3 * n_jobs + 1, (int)n_jobs, poses,
-                       radius * radius, lattice(bounds, radius), counts, nn);
+                       radius * radius, nn_lattice(bounds, radius), counts, nn);
   return (int)hipGetLastError();
 }
 

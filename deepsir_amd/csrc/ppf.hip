@@ -35,6 +35,8 @@
 //   orientation: t = n . (v - p) in fp64 (v: the viewpoint, default origin; p: the point itself); t < 0: n = -n; t == 0: the sign
 //   that makes the component of largest magnitude positive (ties: the lower axis)
 //   degenerate (S[0] == 0: all neighbours coincide; or anything non-finite): normal (0, 0, 0), flag 1 - angle() then yields 0
+//   dsir_estimate_normals_csr: the same arithmetic over the entries of a CSR row in row order (the divisor is the row's length); a row
+//   of fewer than 3 entries is degenerate too
 //
 // ---- Training (dsir_t_ppf_fwd / dsir_t_ppf_bwd, include/dsir_train.h).  The rows are data in every pipeline, so the front end has
 // four trainable tensors: W [12][10], b, gamma, beta.  The taped forward IS the two launches above (same bits); the consumer pass
@@ -333,23 +335,18 @@ __global__ __launch_bounds__(256) void ppf_bwd_b_final_kernel(const double* __re
   else db[o - 120] += (float)a;
 }
 
-__global__ __launch_bounds__(256) void estimate_normals_kernel(const float* __restrict__ pts, int64_t pts_cs, int stride,
-                                                               const int32_t* __restrict__ neigh, int64_t neigh_cs, int n, float vx,
-                                                               float vy, float vz, float* __restrict__ normals,
-                                                               int32_t* __restrict__ flags) {
-  const int cloud = blockIdx.y;
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const float* P = pts + cloud * pts_cs;
-  const int32_t* nb = neigh + cloud * neigh_cs + (int64_t)i * kKnn;
+// The normal of point i of cloud P [n][stride] from the `cnt` entries of its list nb, in list order; cnt < 3 (a CSR row too short to
+// span a plane): normal 0, flag 1.  One body for the fixed 16-entry lists and the CSR rows: the same bytes where the lists agree.
+__device__ __forceinline__ void normal_of_list(const float* __restrict__ P, int stride, int n, int i, const int32_t* __restrict__ nb, int cnt,
+                                               float vx, float vy, float vz, float* __restrict__ o, int32_t* __restrict__ flag_out) {
   double m[3] = {0.0, 0.0, 0.0};
-  for (int k = 0; k < kKnn; ++k) {
+  for (int k = 0; k < cnt; ++k) {
     const int j = min(max(nb[k], 0), n - 1);
     for (int a = 0; a < 3; ++a) m[a] += (double)P[(int64_t)j * stride + a];
   }
-  for (int a = 0; a < 3; ++a) m[a] = m[a] / 16.0;
+  for (int a = 0; a < 3; ++a) m[a] = m[a] / (double)cnt;
   double Cm[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
-  for (int k = 0; k < kKnn; ++k) {        // the neighbours are read a second time (cache hits) instead of held in 96 registers
+  for (int k = 0; k < cnt; ++k) {         // the neighbours are read a second time (cache hits) instead of held in 96 registers
     const int j = min(max(nb[k], 0), n - 1);
     double e[3];
     for (int a = 0; a < 3; ++a) e[a] = (double)P[(int64_t)j * stride + a] - m[a];
@@ -357,7 +354,7 @@ __global__ __launch_bounds__(256) void estimate_normals_kernel(const float* __re
       for (int b = a; b < 3; ++b) Cm[a][b] += e[a] * e[b];
   }
   Cm[1][0] = Cm[0][1]; Cm[2][0] = Cm[0][2]; Cm[2][1] = Cm[1][2];
-  bool finite = true;
+  bool finite = cnt >= 3;
   for (int a = 0; a < 3; ++a)
     for (int b = 0; b < 3; ++b) finite = finite && isfinite(Cm[a][b]);
   double nv[3] = {0.0, 0.0, 0.0};
@@ -384,9 +381,33 @@ __global__ __launch_bounds__(256) void estimate_normals_kernel(const float* __re
       }
     }
   }
-  float* o = normals + ((int64_t)cloud * n + i) * 3;
   o[0] = (float)nv[0]; o[1] = (float)nv[1]; o[2] = (float)nv[2];
-  if (flags) flags[(int64_t)cloud * n + i] = flag;
+  if (flag_out) *flag_out = flag;
+}
+
+__global__ __launch_bounds__(256) void estimate_normals_kernel(const float* __restrict__ pts, int64_t pts_cs, int stride,
+                                                               const int32_t* __restrict__ neigh, int64_t neigh_cs, int n, float vx,
+                                                               float vy, float vz, float* __restrict__ normals,
+                                                               int32_t* __restrict__ flags) {
+  const int cloud = blockIdx.y;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int64_t r = (int64_t)cloud * n + i;
+  normal_of_list(pts + cloud * pts_cs, stride, n, i, neigh + cloud * neigh_cs + (int64_t)i * kKnn, kKnn, vx, vy, vz, normals + r * 3,
+                 flags ? flags + r : nullptr);
+}
+
+// the same over a CSR with cloud-local columns (dsir_fpfh's csr form): row (cloud, i) = cols[offsets[cloud n + i] .. offsets[cloud n + i + 1])
+__global__ __launch_bounds__(256) void estimate_normals_csr_kernel(const float* __restrict__ pts, int64_t pts_cs, int stride,
+                                                                   const int32_t* __restrict__ offsets, const int32_t* __restrict__ cols, int n,
+                                                                   float vx, float vy, float vz, float* __restrict__ normals,
+                                                                   int32_t* __restrict__ flags) {
+  const int cloud = blockIdx.y;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int64_t r = (int64_t)cloud * n + i;
+  const int b = offsets[r], cnt = max(offsets[r + 1] - b, 0);
+  normal_of_list(pts + cloud * pts_cs, stride, n, i, cols + b, cnt, vx, vy, vz, normals + r * 3, flags ? flags + r : nullptr);
 }
 
 }  // namespace
@@ -410,6 +431,13 @@ void launch_estimate_normals(const float* pts, int64_t pts_cs, int stride, const
   if (n <= 0 || clouds <= 0) return;
   const dim3 grid((unsigned)((n + 255) / 256), (unsigned)clouds);
   hipLaunchKernelGGL(estimate_normals_kernel, grid, dim3(256), 0, st, pts, pts_cs, stride, neigh, neigh_cs, n, vx, vy, vz, normals, flags);
+}
+
+void launch_estimate_normals_csr(const float* pts, int64_t pts_cs, int stride, const int32_t* offsets, const int32_t* cols, int n, int clouds,
+                                 float vx, float vy, float vz, float* normals, int32_t* flags, hipStream_t st) {
+  if (n <= 0 || clouds <= 0) return;
+  const dim3 grid((unsigned)((n + 255) / 256), (unsigned)clouds);
+  hipLaunchKernelGGL(estimate_normals_csr_kernel, grid, dim3(256), 0, st, pts, pts_cs, stride, offsets, cols, n, vx, vy, vz, normals, flags);
 }
 
 }  // namespace dsir

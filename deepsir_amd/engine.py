@@ -204,19 +204,42 @@ class Engine:
         self.sync()
         return out
 
-    def estimate_normals(self, points, neigh_multi, viewpoint=(0.0, 0.0, 0.0)):
-        """Normals from the level-0 neighbour lists (include/dsir.h, dsir_estimate_normals; the rule: deepsir_amd/ppf.py):
-        points [c,n,>=3], neigh_multi [c,S,16] -> (normals [c,n,3], flags [c,n] i32: 1 = degenerate, normal (0,0,0))."""
-        points, neigh_multi = _chk(points, torch.float32, "points"), _chk(neigh_multi, torch.int32, "neigh_idx")
+    def estimate_normals(self, points, neigh_multi=None, viewpoint=(0.0, 0.0, 0.0), csr=None):
+        """Normals from neighbour lists (include/dsir.h, dsir_estimate_normals / dsir_estimate_normals_csr; the rule: deepsir_amd/ppf.py):
+        points [c,n,>=3] and exactly one of neigh_multi [c,S,16] (the pyramid's level-0 lists) and csr = (offsets [c n + 1] i32, cols
+        i32 with cloud-local columns: what ``radius_neighbors`` returns; a row of fewer than 3 entries is degenerate) ->
+        (normals [c,n,3], flags [c,n] i32: 1 = degenerate, normal (0,0,0))."""
+        points = _chk(points, torch.float32, "points")
+        if (neigh_multi is None) == (csr is None):
+            raise EngineError("estimate_normals: exactly one of neigh_multi and csr expected")
         c, n, stride = points.shape
         normals = self._empty((c, n, 3))
         flags = self._empty((c, n), torch.int32)
         v = (C.c_float * 3)(*[float(x) for x in viewpoint])
-        self._pre()
-        self._call(self.lib.dsir_estimate_normals(self.h, _ptr(points), stride, _ptr(neigh_multi), neigh_multi.shape[1] * 16, c, n, v,
-                                                  _ptr(normals), _ptr(flags)))
+        if csr is None:
+            neigh_multi = _chk(neigh_multi, torch.int32, "neigh_idx")
+            self._pre()
+            self._call(self.lib.dsir_estimate_normals(self.h, _ptr(points), stride, _ptr(neigh_multi), neigh_multi.shape[1] * 16, c, n, v,
+                                                      _ptr(normals), _ptr(flags)))
+        else:
+            off, cols = self._csr(csr, c * n, "estimate_normals")
+            self._pre()
+            self._call(self.lib.dsir_estimate_normals_csr(self.h, _ptr(points), stride, _ptr(off), _ptr(cols), c, n, v, _ptr(normals),
+                                                          _ptr(flags)))
         self.sync()
         return normals, flags
+
+    def _csr(self, csr, rows: int, who: str):
+        """(offsets, cols) of a caller's CSR over ``rows`` rows, checked: the kernels trust the offsets, so a list that would leave cols
+        is refused (two reductions and one read-back, no kernel work)."""
+        off, cols = _chk(csr[0], torch.int32, "csr offsets"), _chk(csr[1], torch.int32, "csr cols")
+        if off.numel() != rows + 1:
+            raise EngineError(f"{who}: csr offsets must have clouds * n + 1 = {rows + 1} entries, got {off.numel()}")
+        if int(off[0]) != 0 or int(off[-1]) != cols.numel() or bool((off[1:] < off[:-1]).any()):
+            raise EngineError(f"{who}: csr offsets must start at 0, be non-decreasing and end at len(cols)")
+        if cols.numel() == 0:                                       # every row empty: the kernels still want a pointer
+            cols = torch.zeros((1,), dtype=torch.int32, device=self.device)
+        return off, cols
 
     def fpfh(self, points, normals=None, neigh_multi=None, csr=None, pad_to: int = 64):
         """FPFH descriptors (include/dsir.h, dsir_fpfh; the rule: csrc/fpfh.hip, restated in deepsir_amd/fpfh.py): points [c,n,>=3],
@@ -243,14 +266,7 @@ class Engine:
                 raise EngineError(f"fpfh: neigh_multi must be [{c}, >= {n}, 16], got {tuple(neigh_multi.shape)}")
             neigh_cs = neigh_multi.shape[1] * 16
         else:
-            off, cols = _chk(csr[0], torch.int32, "csr offsets"), _chk(csr[1], torch.int32, "csr cols")
-            if off.numel() != c * n + 1:
-                raise EngineError(f"fpfh: csr offsets must have clouds * n + 1 = {c * n + 1} entries, got {off.numel()}")
-            # the kernels trust the offsets: refuse a list that would leave cols (two reductions and one read-back, no descriptor work)
-            if int(off[0]) != 0 or int(off[-1]) != cols.numel() or bool((off[1:] < off[:-1]).any()):
-                raise EngineError("fpfh: csr offsets must start at 0, be non-decreasing and end at len(cols)")
-            if cols.numel() == 0:                                   # every row empty: the kernels still want a pointer
-                cols = torch.zeros((1,), dtype=torch.int32, device=self.device)
+            off, cols = self._csr(csr, c * n, "fpfh")
         desc = self._empty((c, n, int(pad_to)))
         flags = self._empty((c, n), torch.int32)
         self._pre()
@@ -928,6 +944,25 @@ class Engine:
         _, flat = index.search(sub, sub_poses, fill=True)
         rows = index.rows(sub)
         return counts, [flat[rows[k]:rows[k + 1]] for k in range(len(sub))]
+
+    def radius_neighbors(self, points, radius: float, max_nn: int = 0, with_dist: bool = False):
+        """The self-neighbourhood of every cloud of a dense batch over the cell index (csrc/radius_nn.hip): points [c, n, C] fp32 ->
+        (offsets [c n + 1] i32, cols i32 with cloud-local columns, ascending per row[, d2 fp32 aligned with cols]) - exactly the
+        ``csr`` of ``fpfh`` and ``estimate_normals``.  ``max_nn`` = 0: every point within ``radius`` (the bytes of
+        ``radius_matches(x, x, identity, radius)``); > 0: the max_nn nearest of them, ties to the lower index (open3d's
+        KDTreeSearchParamHybrid).  One fragment and one job (i, i) per cloud.  Raises ValueError where the library refuses the
+        call: a bad ``max_nn``, radius, shape or row count before anything is launched, an extent of more than 2^21 - 2 cells after
+        the bounds reduction alone."""
+        points = _chk(points, torch.float32, "points")
+        if points.dim() != 3 or points.shape[2] < 3 or points.shape[0] < 1:
+            raise ValueError("radius_neighbors: points [clouds >= 1, n, C >= 3] expected")
+        c, n, stride = points.shape
+        if int(max_nn) != max_nn or max_nn < 0 or max_nn > 0x7fffffff:
+            raise ValueError("nn_radius: max_nn must be 0 (the whole ball) or a positive int32")
+        if c * n > (1 << 26) - 1:
+            raise ValueError("nn_radius: more than 2^26 - 1 query rows in one job list (one workgroup per row): split it")
+        index = self.nn_index(points.reshape(c * n, stride), np.arange(c + 1, dtype=np.int64) * n, radius)
+        return index.neighbors(np.repeat(np.arange(c, dtype=np.int32), 2).reshape(c, 2), None, max_nn, with_dist)
 
     def overlap_ratio(self, src, ref, T, radius: float) -> np.ndarray:
         """The share of every pair's source points that have a reference point within ``radius`` under the pose: src [P, J, C],

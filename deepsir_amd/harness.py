@@ -367,15 +367,38 @@ def register_feat(pairs: Sequence[Dict[str, np.ndarray]], model, voxel_size: flo
     return pred, stats
 
 
-def _fpfh_side(engine, pts, viewpoints, radius):
+def csr_of_cloud(csr, b: int, n: int, bounds=None):
+    """Cloud b's rows of a batch CSR (offsets [B n + 1], cloud-local cols) as a CSR of its own: (offsets [n + 1] from 0, cols).
+    ``bounds``: offsets[::n] on the host, when the caller has read them once for all clouds."""
+    off, cols = csr
+    lo, hi = (int(off[b * n]), int(off[(b + 1) * n])) if bounds is None else (int(bounds[b]), int(bounds[b + 1]))
+    return (off[b * n:(b + 1) * n + 1] - lo).contiguous(), cols[lo:hi].contiguous()
+
+
+def _fpfh_side(engine, pts, viewpoints, radius, search="brute", max_nn=0, normal_radius=None, normal_max_nn=0):
     """One side of a batch for ``register_fpfh``: pts [B, N, C] -> (desc [B, N, 64], flags [B, N], normals [B, N, 3])."""
-    _, neigh, _, _ = engine.knn_pyramid(pts)
-    if all(v == viewpoints[0] for v in viewpoints):
-        normals, _ = engine.estimate_normals(pts, neigh, viewpoints[0])
-    else:                                    # one viewpoint per call; clouds are independent bit for bit, so per-cloud calls change nothing
-        normals = torch.cat([engine.estimate_normals(pts[b:b + 1], neigh[b:b + 1], viewpoints[b])[0] for b in range(pts.shape[0])], 0)
+    def normals_of(neigh_multi=None, csr=None):
+        if all(v == viewpoints[0] for v in viewpoints):
+            return engine.estimate_normals(pts, neigh_multi, viewpoints[0], csr=csr)[0]
+        # one viewpoint per call; clouds are independent bit for bit, so per-cloud calls change nothing
+        B, n = pts.shape[:2]
+        if csr is None:
+            return torch.cat([engine.estimate_normals(pts[b:b + 1], neigh_multi[b:b + 1], viewpoints[b])[0] for b in range(B)], 0)
+        bounds = csr[0][::n].cpu().numpy()                          # one read for all clouds
+        return torch.cat([engine.estimate_normals(pts[b:b + 1], viewpoint=viewpoints[b], csr=csr_of_cloud(csr, b, n, bounds))[0]
+                          for b in range(B)], 0)
+
+    neigh = None
+    if normal_radius is None or radius is None:
+        _, neigh, _, _ = engine.knn_pyramid(pts)
+    if normal_radius is None:
+        normals = normals_of(neigh_multi=neigh)
+    else:
+        normals = normals_of(csr=engine.radius_neighbors(pts, float(normal_radius), int(normal_max_nn)))
     if radius is None:
         desc, flags = engine.fpfh(pts, normals, neigh_multi=neigh)
+    elif search == "grid":
+        desc, flags = engine.fpfh(pts, normals, csr=engine.radius_neighbors(pts, float(radius), int(max_nn)))
     else:
         eye = torch.eye(3, 4, device=pts.device).repeat(pts.shape[0], 1, 1).contiguous()
         desc, flags = engine.fpfh(pts, normals, csr=engine.radius_matches(pts, pts, eye, float(radius)))
@@ -387,7 +410,8 @@ def register_fpfh(pairs: Sequence[Dict[str, np.ndarray]], engine, voxel_size: fl
                   hypotheses: int = 8192, mutual: bool = True, num_reg: int = 1, dataset_type: str = "3DMatch", batch: int = 1,
                   device: Optional[torch.device] = None, ransac_n: int = 3, edge_sim: float = 0.9, refine_iters: int = 2, seed: int = 0,
                   want_corr: bool = False, pose: str = "ransac", seeds: int = 64, members: int = 32, match_k: int = 1,
-                  match_ratio: float = 0.0):
+                  match_ratio: float = 0.0, search: str = "brute", max_nn: int = 0, normal_radius: Optional[float] = None,
+                  normal_max_nn: int = 0):
     """The weight-independent baseline of ``register_feat``: FPFH + feature-matching RANSAC (open3d compute_fpfh_feature ->
     registration_ransac_based_on_feature_matching; parity unpinned, the rules are the engine's own), all on the device.  Per batch
     and side: ``knn_pyramid`` -> ``estimate_normals`` on its level-0 lists (towards the pair's optional ``viewpoint_src`` /
@@ -398,12 +422,28 @@ def register_fpfh(pairs: Sequence[Dict[str, np.ndarray]], engine, voxel_size: fl
     third value, per pair the (corr [count, 2], flags_src [J], flags_ref [K]) numpy arrays.  ``match_k`` / ``match_ratio``: k candidate
     matches per src point (M = J x match_k) or Lowe's ratio test, as in ``register_feat``.
 
+    ``search``: where the ``radius`` neighbourhoods come from - ``"brute"`` (the default: ``radius_matches``, J x K distance tests)
+    or ``"grid"`` (``radius_neighbors`` over the cell index; with ``max_nn`` = 0 the same CSR bytes, so the same poses).  ``max_nn``
+    > 0 keeps the max_nn nearest of a neighbourhood (grid only).  ``normal_radius`` (with ``normal_max_nn``) takes the normals from
+    radius neighbourhoods over the cell index instead of the 16-NN lists: open3d's recipe is ``normal_radius = 2 voxel,
+    normal_max_nn = 30, radius = 5 voxel, max_nn = 100, search = "grid"``.  With ``normal_radius`` and ``radius`` both set and
+    ``search="grid"`` no pyramid is built, so clouds under 1024 points work, up to what the FPFH, correspondence and pose entries take.
+
     ``engine`` is a ``deepsir_amd.engine.Engine`` THE CALLER PREPARED: the descriptor itself needs no weights, but the pyramid and
     the other existing entries this calls refuse a context whose weights are not loaded (``check_ready``, csrc/engine_ctx.h), so
     load a state dict first - any, e.g. ``weights.generate_state_dict(cfg, 0)``; its values are never read here.  Its max_points /
-    max_pairs must cover the clouds and ``batch``; the clouds must be ones the pyramid takes (>= 1024 points with the default
-    ratios)."""
+    max_pairs must cover the clouds and ``batch``; unless both radii are set with ``search="grid"`` (no pyramid, above), the clouds
+    must be ones the pyramid takes (>= 1024 points with the default ratios)."""
     device = device or torch.device("cuda", torch.cuda.current_device())
+    if search not in ("brute", "grid"):
+        raise ValueError(f"register_fpfh: search must be 'brute' or 'grid', got {search!r}")
+    if max_nn < 0 or normal_max_nn < 0:
+        raise ValueError("register_fpfh: max_nn and normal_max_nn must be 0 (no cap) or positive")
+    if max_nn > 0 and (radius is None or search != "grid"):
+        raise ValueError("register_fpfh: max_nn needs radius and search='grid' (the brute-force lists have no cap)")
+    if normal_max_nn > 0 and normal_radius is None:
+        raise ValueError("register_fpfh: normal_max_nn needs normal_radius")
+    nbr = (search, int(max_nn), normal_radius, int(normal_max_nn))
     rte_t, rre_t = THRESHOLDS[dataset_type]
     preds, corrs, stats = [], [], np.zeros((len(pairs), 5))
 
@@ -415,8 +455,8 @@ def register_fpfh(pairs: Sequence[Dict[str, np.ndarray]], engine, voxel_size: fl
         torch.cuda.synchronize(device)
         t0 = time.time()
         xs, xr = data["points_src"].float().contiguous(), data["points_ref"].float().contiguous()
-        ds, fs, _ = _fpfh_side(engine, xs, [view(i, "src") for i in ids], radius)
-        dr, fr, _ = _fpfh_side(engine, xr, [view(i, "ref") for i in ids], radius)
+        ds, fs, _ = _fpfh_side(engine, xs, [view(i, "src") for i in ids], radius, *nbr)
+        dr, fr, _ = _fpfh_side(engine, xr, [view(i, "ref") for i in ids], radius, *nbr)
         corr, counts = engine.feature_correspondences(ds, dr, mutual=mutual, k=match_k, ratio=match_ratio)
         T = _pose_from_corr(engine, pose, xs, xr, corr, counts, 2.0 * voxel_size, ransac_n, edge_sim, hypotheses, refine_iters, seed,
                             seeds, members)

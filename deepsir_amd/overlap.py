@@ -81,6 +81,60 @@ def nn_within_host(points: np.ndarray, offsets: Sequence[int], jobs: Sequence[Se
     return counts, nn
 
 
+def radius_pair_host(a: np.ndarray, b: np.ndarray, radius: float, max_nn: int = 0) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """The neighbour-list rule for one pair (csrc/radius_nn.hip): a [n, >=3], b [m, >=3] float32 -> (counts int32 [n], cols int32
+    [sum], d2 float32 [sum]): per row of a every b with d2 < r r, or with ``max_nn`` > 0 the max_nn smallest under (d2, index), each
+    row in ascending index."""
+    a = np.asarray(a, np.float32)[:, :3]
+    b = np.asarray(b, np.float32)[:, :3]
+    n, m = a.shape[0], b.shape[0]
+    counts = np.zeros(n, np.int32)
+    cols: List[np.ndarray] = []
+    dist: List[np.ndarray] = []
+    if n and m:
+        r = np.float32(radius)
+        r2 = np.float32(r * r)
+        bad_b = ~np.isfinite(b).all(1)
+        ok_a = np.isfinite(a).all(1)
+        step = max(1, _CHUNK // m)
+        with np.errstate(all="ignore"):
+            for s in range(0, n, step):
+                q = a[s:s + step]
+                dx = b[None, :, 0] - q[:, None, 0]
+                dy = b[None, :, 1] - q[:, None, 1]
+                dz = b[None, :, 2] - q[:, None, 2]
+                d2 = ((dx * dx + dy * dy) + dz * dz).astype(np.float32)
+                hit = (d2 < r2) & ~bad_b[None, :] & ok_a[s:s + step, None]
+                for i in range(len(q)):
+                    k = np.nonzero(hit[i])[0]                       # ascending index
+                    if max_nn > 0 and len(k) > max_nn:
+                        k = np.sort(k[np.lexsort((k, d2[i, k]))[:max_nn]])     # (d2, index) ascending, the first max_nn, back in index order
+                    counts[s + i] = len(k)
+                    cols.append(k.astype(np.int32))
+                    dist.append(d2[i, k])
+    cat = lambda parts, dt: np.concatenate(parts).astype(dt) if parts else np.zeros(0, dt)
+    return counts, cat(cols, np.int32), cat(dist, np.float32)
+
+
+def radius_neighbors_host(points: np.ndarray, offsets: Sequence[int], jobs: Sequence[Sequence[int]], radius: float,
+                          poses: Optional[np.ndarray] = None, max_nn: int = 0) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """``NNIndex.neighbors`` on the host, selection included: points [total, >=3] float32 holding ragged fragments (offsets [F + 1]),
+    jobs [n, 2] of (query fragment, target fragment), poses None or [n, 3, 4] (applied in float32 before the search) ->
+    (offsets int32 [rows + 1], cols int32 [total], d2 float32 [total]) over the jobs' query rows in job order."""
+    pts = np.asarray(points, np.float32)
+    off = np.asarray(offsets, np.int64)
+    jobs = np.asarray(jobs, np.int64).reshape(-1, 2)
+    counts, cols, dist = [np.zeros(0, np.int32)], [np.zeros(0, np.int32)], [np.zeros(0, np.float32)]
+    for j, (q, t) in enumerate(jobs):
+        a = pts[off[q]:off[q + 1], :3]
+        if poses is not None:
+            a = move_host(np.asarray(poses)[j], a)
+        c, k, d = radius_pair_host(a, pts[off[t]:off[t + 1], :3], radius, int(max_nn))
+        counts.append(c); cols.append(k); dist.append(d)
+    row_off = np.concatenate([[0], np.cumsum(np.concatenate(counts), dtype=np.int64)]).astype(np.int32)
+    return row_off, np.concatenate(cols), np.concatenate(dist)
+
+
 def keypoint_pairs(nn: np.ndarray) -> np.ndarray:
     """A job's neighbour list as the reference's key-point pairs (3DMatch_preprocess.py:82-89): int32 [m, 2] of (query, target) in
     ascending query index."""

@@ -26,7 +26,7 @@ flag 1.
 """
 from __future__ import annotations
 
-from typing import Tuple
+from typing import Optional, Tuple
 
 import numpy as np
 
@@ -131,34 +131,52 @@ def ppf_pre_backward(rows: np.ndarray, neigh: np.ndarray, W: np.ndarray, b: np.n
     return out + (dbeta_c, dgamma_c) if per_cloud else out
 
 
-def estimate_normals(points: np.ndarray, neigh: np.ndarray, viewpoint=(0.0, 0.0, 0.0)) -> Tuple[np.ndarray, np.ndarray]:
-    """points [B, N, >= 3] float32, neigh [B, N, 16] (level 0) -> (normals [B, N, 3] float32, flags [B, N] int32)."""
+def _normals_of(pts, q, cnt, v):
+    """pts [N, 3] float64, q [N, K, 3] float64 = the lists' points (entries at or past cnt [N] are ignored), v [3] -> (normals, flags)."""
+    N, K = q.shape[:2]
+    live = np.arange(K)[None, :] < cnt[:, None]
+    m = np.zeros((N, 3))
+    for k in range(K):
+        m = np.where(live[:, k, None], m + q[:, k], m)
+    with np.errstate(all="ignore"):
+        m = m / cnt[:, None].astype(np.float64)
+    C = np.zeros((N, 3, 3))
+    for k in range(K):
+        e = q[:, k] - m
+        C = np.where(live[:, k, None, None], C + e[:, :, None] * e[:, None, :], C)
+    ok = np.isfinite(C).all((1, 2)) & (cnt >= 3)
+    w, V = np.linalg.eigh(np.where(ok[:, None, None], C, 0.0))         # ascending eigenvalues
+    nv = V[:, :, 0]
+    nv = nv / np.sqrt((nv * nv).sum(1, keepdims=True))
+    t = (nv * (v[None] - pts)).sum(1)
+    mx = np.argmax(np.abs(nv), 1)                                      # first maximum = the lower axis
+    flip = np.where(t == 0.0, nv[np.arange(N), mx] < 0.0, t < 0.0)
+    nv = np.where(flip[:, None], -nv, nv)
+    good = ok & (w[:, 2] > 0.0) & np.isfinite(t)
+    return np.where(good[:, None], nv, 0.0).astype(F), np.where(good, 0, 1).astype(np.int32)
+
+
+def estimate_normals(points: np.ndarray, neigh: Optional[np.ndarray] = None, viewpoint=(0.0, 0.0, 0.0), csr=None) -> Tuple[np.ndarray, np.ndarray]:
+    """points [B, N, >= 3] float32 and exactly one of neigh [B, N, 16] (level 0) and csr = (offsets [B N + 1], cols, cloud-local: the
+    entries of a row in row order; fewer than 3: flag 1, normal 0) -> (normals [B, N, 3] float32, flags [B, N] int32)."""
+    if (neigh is None) == (csr is None):
+        raise ValueError("estimate_normals: exactly one of neigh and csr expected")
     pts = np.asarray(points, F)[..., :3].astype(np.float64)
     v = np.asarray(viewpoint, F).astype(np.float64)
     B, N = pts.shape[:2]
     out = np.zeros((B, N, 3), F)
     flags = np.ones((B, N), np.int32)
     for bi in range(B):
-        q = pts[bi][neigh[bi]]                                         # [N, 16, 3]
-        m = np.zeros((N, 3))
-        for k in range(16):
-            m = m + q[:, k]
-        m = m / 16.0
-        C = np.zeros((N, 3, 3))
-        for k in range(16):
-            e = q[:, k] - m
-            C = C + e[:, :, None] * e[:, None, :]
-        ok = np.isfinite(C).all((1, 2))
-        w, V = np.linalg.eigh(np.where(ok[:, None, None], C, 0.0))     # ascending eigenvalues
-        nv = V[:, :, 0]
-        nv = nv / np.sqrt((nv * nv).sum(1, keepdims=True))
-        t = (nv * (v[None] - pts[bi])).sum(1)
-        mx = np.argmax(np.abs(nv), 1)                                  # first maximum = the lower axis
-        flip = np.where(t == 0.0, nv[np.arange(N), mx] < 0.0, t < 0.0)
-        nv = np.where(flip[:, None], -nv, nv)
-        good = ok & (w[:, 2] > 0.0) & np.isfinite(t)
-        out[bi] = np.where(good[:, None], nv, 0.0).astype(F)
-        flags[bi] = np.where(good, 0, 1)
+        if neigh is not None:
+            lists, cnt = np.asarray(neigh[bi]), np.full(N, 16, np.int64)
+        else:
+            off = np.asarray(csr[0], np.int64)[bi * N:(bi + 1) * N + 1]
+            cnt = np.diff(off)
+            lists = np.zeros((N, max(int(cnt.max()) if N else 0, 1)), np.int64)
+            pos = np.arange(lists.shape[1])[None, :]
+            live = pos < cnt[:, None]
+            lists[live] = np.clip(np.asarray(csr[1], np.int64)[(off[:-1, None] + pos)[live]], 0, N - 1)
+        out[bi], flags[bi] = _normals_of(pts[bi], pts[bi][lists], cnt, v)
     return out, flags
 
 

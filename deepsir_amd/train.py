@@ -459,6 +459,40 @@ class NNIndex:
                         self.radius, self.bounds.ctypes.data, _ptr(counts), _ptr(nn) if fill and nn.numel() else None, _ptr(scratch))
         return counts, nn
 
+    def neighbors(self, jobs, poses: Optional[torch.Tensor] = None, max_nn: int = 0, with_dist: bool = False):
+        """Every neighbour within the index's radius (``max_nn`` = 0), or the ``max_nn`` nearest of them under the order (d2, original
+        index), as a CSR over the jobs' query rows in job order (``rows``): the rule at the head of csrc/radius_nn.hip, restated in
+        ``overlap.radius_neighbors_host``.  -> (offsets [rows + 1] i32, cols [total] i32: original indices in the target fragment,
+        ascending per row[, d2 [total] fp32 aligned with cols]).  Two passes and ONE 4-byte read of the total in between.  Raises
+        ValueError, launching nothing, where the library refuses the call (the index itself is already built); RuntimeError after
+        the count pass where the neighbours exceed 2^31 - 1 (the offsets' saturating sum reads -1), before any fill."""
+        ops = self.ops
+        jobs = np.ascontiguousarray(np.asarray(jobs, dtype=np.int32).reshape(-1, 2))
+        if int(max_nn) != max_nn or max_nn < 0 or max_nn > 0x7fffffff:
+            raise ValueError("nn_radius: max_nn must be 0 (the whole ball) or a positive int32")
+        self._refuse(jobs)
+        n = len(jobs)
+        if poses is not None and (tuple(poses.shape) != (n, 3, 4) or poses.dtype != torch.float32 or not poses.is_contiguous()):
+            raise ValueError("nn_radius: poses [n_jobs, 3, 4] fp32 contiguous expected")
+        rows = int(self.rows(jobs)[-1])
+        nb = int(ops.lib.dsir_t_nn_radius_scratch(n, rows))
+        if nb == 0:                                             # the job count passed _refuse: it is the rows
+            raise ValueError("nn_radius: more than 2^26 - 1 query rows in one job list (one workgroup per row): split it")
+        counts = ops.empty(max(rows, 1), dtype=torch.int32)
+        offsets = ops.empty(rows + 1, dtype=torch.int32)
+        scratch = torch.empty(nb, dtype=torch.uint8, device=ops.device)
+        head = (_ptr(self.index), self.offsets.ctypes.data, self.fragments, jobs.ctypes.data if n else None, n, _ptr(poses), self.radius,
+                self.bounds.ctypes.data, int(max_nn))
+        ops._launch("dsir_t_nn_radius_count", *head, _ptr(counts), _ptr(offsets), _ptr(scratch))
+        total = int(offsets[-1].item())
+        if total < 0:                                           # the scan saturates: -1 for every total above 2^31 - 1
+            raise RuntimeError("nn_radius: more than 2^31 - 1 neighbours: split the job list, lower the radius or set max_nn")
+        cols = ops.empty(total, dtype=torch.int32)
+        d2 = ops.empty(total) if with_dist else None
+        ops._launch("dsir_t_nn_radius_fill", *head, _ptr(offsets), _ptr(scratch), _ptr(cols) if total else None,
+                    _ptr(d2) if with_dist and total else None, total)
+        return (offsets, cols, d2) if with_dist else (offsets, cols)
+
     def rows(self, jobs) -> np.ndarray:
         """[n + 1]: where each job's query rows start in the ``nn`` of a fill-mode search."""
         jobs = np.asarray(jobs, dtype=np.int64).reshape(-1, 2)

@@ -45,6 +45,12 @@ def main():
                     help="pose stage of --method fpfh and --pipeline feat: seeded RANSAC or the spatial-consensus stage (no sampling)")
     ap.add_argument("--method", choices=["network", "fpfh"], default="network", help="fpfh: FPFH + RANSAC instead of the network")
     ap.add_argument("--fpfh-radius", type=float, default=None, help="with --method fpfh: radius lists instead of the 16-NN lists")
+    ap.add_argument("--fpfh-search", choices=["brute", "grid"], default="brute",
+                    help="with --fpfh-radius: brute-force radius lists, or the cell-indexed search (same lists, linear workspace)")
+    ap.add_argument("--fpfh-max-nn", type=int, default=0, help="with --fpfh-search grid: keep the max_nn nearest of a radius list (0 = all)")
+    ap.add_argument("--normal-radius", type=float, default=None,
+                    help="with --method fpfh: normals from radius neighbourhoods over the cell index instead of the 16-NN lists")
+    ap.add_argument("--normal-max-nn", type=int, default=0, help="with --normal-radius: the max_nn nearest of a neighbourhood (0 = all)")
     ap.add_argument("--match-k", type=int, default=1,
                     help="--method fpfh / --pipeline feat: the k nearest descriptors of every src point as candidate matches (1 .. 8)")
     ap.add_argument("--match-ratio", type=float, default=0.0,
@@ -75,7 +81,8 @@ def main():
     pairs = [D.as_batch(ds[i]) for i in range(n)]
     if a.method == "fpfh":
         pred, stats = register_fpfh(pairs, eng, voxel_size=voxel, radius=a.fpfh_radius, hypotheses=a.hypotheses, dataset_type=a.dataset,
-                                    batch=a.batch, pose=a.pose, match_k=a.match_k, match_ratio=a.match_ratio)
+                                    batch=a.batch, pose=a.pose, match_k=a.match_k, match_ratio=a.match_ratio, search=a.fpfh_search,
+                                    max_nn=a.fpfh_max_nn, normal_radius=a.normal_radius, normal_max_nn=a.normal_max_nn)
     elif feat:
         pred, stats = register_feat(pairs, model, voxel_size=voxel, hypotheses=a.hypotheses, dataset_type=a.dataset, batch=a.batch,
                                     pose=a.pose, match_k=a.match_k, match_ratio=a.match_ratio)

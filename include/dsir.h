@@ -143,6 +143,14 @@ int dsir_ppf_pre(dsir_ctx* ctx, int which, const float* rows, int stride, const 
  * angle() of a zero vector is 0, matchnet.py:16).  Any context serves. */
 int dsir_estimate_normals(dsir_ctx* ctx, const float* points, int stride, const int32_t* neigh_idx, int64_t neigh_cloud_stride,
                           int clouds, int n, const float* viewpoint, float* normals, int32_t* flags);
+/* The same normals from a CSR neighbour list in place of the fixed 16 (open3d's estimate_normals over KDTreeSearchParamRadius /
+ * Hybrid): csr_offsets [clouds * n + 1] / csr_cols with cloud-local columns, the form dsir_fpfh takes and dsir_t_nn_radius_fill
+ * (include/dsir_train.h) writes; offsets must be non-decreasing and stay inside csr_cols, columns are clamped into the cloud.  The
+ * arithmetic is dsir_estimate_normals' over the entries of the row in row order, the mean's divisor the row's length; a row of
+ * fewer than 3 entries gets flag 1 and a zero normal like any degenerate neighbourhood.  On a CSR that lists the 16 level-0
+ * neighbours in list order the two entries write the same bytes. */
+int dsir_estimate_normals_csr(dsir_ctx* ctx, const float* points, int stride, const int32_t* csr_offsets, const int32_t* csr_cols,
+                              int clouds, int n, const float* viewpoint, float* normals, int32_t* flags);
 
 /* FPFH descriptors (the classical feature of open3d's compute_fpfh_feature -> registration_ransac_based_on_feature_matching
  * baseline, unpinned here: the rule is this engine's own, stated in csrc/fpfh.hip and restated in deepsir_amd/fpfh.py) from

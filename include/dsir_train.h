@@ -303,6 +303,35 @@ size_t dsir_t_nn_within_scratch(int64_t n_jobs);
 int dsir_t_nn_within(void* stream, const void* index, const int64_t* offsets, int fragments, const int32_t* jobs, int64_t n_jobs,
                      const float* poses, float radius, const float* bounds, int32_t* counts, int32_t* nn, void* job_scratch);
 
+/* ---- neighbour lists: every neighbour within the radius, or the max_nn nearest, as a CSR (csrc/radius_nn.hip) -----------------------
+ * The search over dsir_t_nn_index_build's index that returns ALL neighbours instead of the nearest: what FPFH (dsir_fpfh's csr form),
+ * dsir_estimate_normals_csr and any later local-geometry stage read.  The same index, offsets, jobs, poses, radius and bounds as
+ * dsir_t_nn_within.  The rule (stated in full at the head of csrc/radius_nn.hip; deepsir_amd/overlap.py::radius_neighbors_host restates it):
+ *   the query a is moved first by ((T0 x + T1 y) + T2 z) + T3 when poses are given, read unmoved when poses == NULL;
+ *   d2 = (dx dx + dy dy) + dz dz, d = b - a, fp32, every operation rounded on its own; b is a neighbour iff d2 < r r, strict, r r one
+ *   fp32 product; a non-finite query has an empty row, a non-finite b is in no row, a query of the target fragment finds itself;
+ *   max_nn = 0: the whole ball; max_nn > 0: the max_nn smallest under the order (d2, original index) - min(count, max_nn) entries, a tie
+ *   at the boundary goes to the lower index; in both modes a row's columns ascend by original index within the target fragment.
+ * rows = the jobs' query rows concatenated in job order (the numbering of dsir_t_nn_within's nn).  Two passes, as the match lists:
+ *   _count: counts [rows] and row_offsets [rows + 1] = their exclusive sum, taken with a saturating add: every prefix above
+ *           2^31 - 1 is -1, so row_offsets[rows] = the total, or -1 for ANY total that does not fit an int32 (split the job list,
+ *           lower the radius or set max_nn; _fill writes nothing for a row whose offsets are -1);
+ *           scratch: dsir_t_nn_radius_scratch(n_jobs, rows) bytes (0: refused), it carries the job table over to _fill;
+ *   the caller reads row_offsets[rows] from the device and sizes cols (and d2);
+ *   _fill:  the SAME arguments, row_offsets and scratch -> cols [n_cols] i32, and d2 [n_cols] fp32 aligned with it unless NULL.
+ *           Nothing is written at or past n_cols.
+ * For max_nn = 0 and one job (i, j) the CSR is byte for byte dsir_t_radius_matches_count / _fill on the same two clouds.
+ * Refused before any launch: what dsir_t_nn_within_check refuses, max_nn < 0, and a job list of more than 2^26 - 1 query rows
+ * (one 64-lane workgroup per row).  No atomics, no sort: two runs write the same
+ * bytes, and a job's bytes do not depend on the rest of the list. */
+size_t dsir_t_nn_radius_scratch(int64_t n_jobs, int64_t rows);
+int dsir_t_nn_radius_count(void* stream, const void* index, const int64_t* offsets, int fragments, const int32_t* jobs, int64_t n_jobs,
+                           const float* poses, float radius, const float* bounds, int max_nn, int32_t* counts, int32_t* row_offsets,
+                           void* scratch);
+int dsir_t_nn_radius_fill(void* stream, const void* index, const int64_t* offsets, int fragments, const int32_t* jobs, int64_t n_jobs,
+                          const float* poses, float radius, const float* bounds, int max_nn, const int32_t* row_offsets, const void* scratch,
+                          int32_t* cols, float* d2, int64_t n_cols);
+
 #ifdef __cplusplus
 }
 #endif
