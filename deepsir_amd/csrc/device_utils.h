@@ -45,6 +45,14 @@ __device__ __forceinline__ T* smem_carve(char*& p, size_t count) {
   return r;
 }
 
+// order-preserving bits of a float: a < b as floats <=> order_bits(a) < order_bits(b) as unsigned (NaN with a clear sign bit above +inf)
+__device__ __forceinline__ unsigned int order_bits(float f) {
+  const unsigned int u = __float_as_uint(f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float unorder_bits(unsigned int b) {
+  return __uint_as_float((b & 0x80000000u) ? (b & 0x7fffffffu) : ~b);
+}
 // index half of a packed (order-preserving distance bits << 32 | column) arg-min slot.  A slot still at its preset
 // (all ones: every distance of the row was NaN, nothing ever won) yields 0, never -1: consumers gather by it.
 __device__ __forceinline__ int32_t packed_index(unsigned long long p) {

@@ -415,13 +415,15 @@ void launch_score(const float* feat, const float* logits, int ncls, const float*
                   const int32_t* neigh, int64_t neigh_cloud_stride, int clouds, int n, ScoreScratch s, float* score,
                   int32_t* label_out, hipStream_t st, bool red_preset = false);
 
-// fused distance GEMM + row arg-min (matchnet.py:96-113 + model.py:566); ev0/ev1 (optional) bracket the main kernel
+// fused distance GEMM + row arg-min (matchnet.py:96-113 + model.py:566); ev0/ev1 (optional) bracket the main kernel.  The distance
+// rule and the tile walk: exact_search_body.h; the launch geometry and the scratch layout (ExactScratch): search_plan.h
 size_t nn_match_scratch_bytes(int pairs, int J, int K);
 void launch_nn_match_ws(const float* a, const float* b, int pairs, int J, int K, int32_t* idx, void* scratch,
                         hipStream_t st, hipEvent_t ev0, hipEvent_t ev1, bool ref_norms_cached = false,
                         unsigned long long* tstamp = nullptr,    // tstamp: {min start, max end} device-clock slot or nullptr
                         bool src_norms_ready = false);           // the src norms and the preset result slots are already in the scratch
-// where launch_nn_match_ws keeps the src norms and the packed result slots inside its scratch (a producer may fill them: AggArgs)
+// where launch_nn_match_ws keeps the src norms and the packed result slots inside its scratch (nn_match_scratch() of search_plan.h;
+// a producer may fill them: AggArgs)
 void nn_match_scratch_layout(void* scratch, int pairs, int J, int K, float** sa, unsigned long long** packed);
 // exhaustive search of all rows of the pairs with gate[pair] >= gate_min and of the rows rowlist[pair][0 .. gate[pair]) of
 // the others; results left in `packed` (preset to all ones)
@@ -429,7 +431,7 @@ void launch_nn_match_gated(const float* a, const float* b, const float* sa, cons
                            unsigned long long* packed, const int32_t* gate, int gate_min, const int32_t* rowlist,
                            hipStream_t st);
 
-void launch_sqnorm(const float* x, int64_t rows, float* out, hipStream_t st);   // |x|^2 of [rows][64], nn_match's order
+void launch_sqnorm(const float* x, int64_t rows, float* out, hipStream_t st);   // |x|^2 of [rows][64] in sqnorm_row16's order
 
 // nn_screen.hip — the same arg-min, screened with fp16 MFMAs under a rigorous bound and decided in exact fp32
 size_t nn_screen_scratch_bytes(int pairs, int J);
@@ -605,7 +607,8 @@ void launch_eval_metrics(const float* pred, int64_t pred_stride, const float* gt
                          int pairs, int n, int stride, float rte_thresh, float rre_thresh, double* out, hipStream_t st);
 
 // nn_topk.hip — the k nearest ref descriptors of every src descriptor (the rule is stated in the file's header), k in [1, 8]:
-// idx [pairs][J][k], dist [pairs][J][k] or nullptr; scratch of nn_topk_scratch_bytes(); nn_topk_splits: the column splits taken
+// idx [pairs][J][k], dist [pairs][J][k] or nullptr; scratch of nn_topk_scratch_bytes() (nn_topk_scratch() of search_plan.h);
+// nn_topk_splits: the column splits taken (nn_topk_plan)
 size_t nn_topk_scratch_bytes(int pairs, int J, int K, int k);
 int nn_topk_splits(int pairs, int J, int K, int k);
 void launch_nn_topk(const float* a, const float* b, int pairs, int J, int K, int k, int32_t* idx, float* dist, void* scratch,

@@ -1,33 +1,22 @@
-// Fused nearest-descriptor search: for every src descriptor a_j the index of the
-// ref descriptor b_k minimising  ((-2 a_j.b_k) + |a_j|^2) + |b_k|^2  in fp32
-// (reference network/matchnet.py:96-113 square_distance_V2 + .min(dim=2)[1] at
-// network/model.py:558-569).  The reference materialises the [J,K] matrix in
-// 6000-row chunks; here it never leaves the MFMA accumulators.
+// Fused nearest-descriptor search: for every src descriptor a_j the index of the ref descriptor b_k minimising the exact
+// fp32 distance (reference network/matchnet.py:96-113 square_distance_V2 + .min(dim=2)[1] at network/model.py:558-569).  The
+// reference materialises the [J,K] matrix in 6000-row chunks; here it never leaves the MFMA accumulators.
 //
-// Block = 4 waves; wave w owns RT row tiles (16 src rows each) whose A fragments
-// (64 channels = 16 k-steps) stay in registers for the whole kernel.  Ref
-// descriptors stream through LDS in tiles of 64 columns ([col][64+2], the pad
-// makes fragment reads conflict free).  Per 16x16 tile: 16 exact-fp32 MFMAs
-// (v_mfma_f32_16x16x4_f32: a k-ordered fmaf chain, channels 0..63 ascending),
-// then 4 running (min, argmin) updates per lane.  The ref range is split over
-// blockIdx.y; partial results meet in a packed 64-bit atomicMin
-// (order-preserving distance bits << 32 | index), so ties go to the lower
-// index regardless of arrival order (deterministic).
+// The distance, its tile walk (block = 4 waves, RT row tiles of resident A fragments per wave, ref columns streaming through
+// a double-buffered LDS tile) and THE RULE they obey are exact_search_body.h's, shared with nn_topk.hip.  This file's own:
+// 4 running (min, argmin) updates per lane and 16x16 tile, a 16-lane reduce, and the ref range split over workgroups whose
+// partial results meet in a packed 64-bit atomicMin (order-preserving distance bits << 32 | index), so ties go to the lower
+// index regardless of arrival order (deterministic).  The launch geometry is search_plan.h's nn_match_plan.
 #include "kernels.h"
 #include "device_utils.h"
+#include "exact_search_body.h"
+#include "scratch.h"
+#include "search_plan.h"
 #include <cstdlib>
 
 namespace dsir {
 
 namespace {
-
-constexpr int BC = 64;        // ref columns per LDS tile
-constexpr int LDB = 64 + 2;   // padded row (floats)
-
-__device__ __forceinline__ unsigned int order_bits(float f) {
-  const unsigned int u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 
 // |x|^2 of every descriptor row: one wave per 4 rows... (16 lanes per row, float4 each)
 // `init` (optional): the row's packed (distance, index) result slot, set to all ones here instead of by a separate memset
@@ -58,13 +47,10 @@ __global__ __launch_bounds__(256) void nn_match_kernel(const float* __restrict__
   __shared__ float sbs[2][BC];
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);   // provably wave-uniform
   const int fr = lane & 15, fq = lane >> 4;
-  // XCD-aware work mapping (speed only): workgroups are dealt round-robin over the 8 XCDs, each with
-  // its own L2.  The bijective remap below hands every XCD a CONTIGUOUS range of work items, ordered
-  // (pair, ref split, row block) with the row block fastest, so the workgroups that stream the same
-  // ref descriptors share one L2 instead of re-fetching them through eight.
-  const int nwg = gridDim.x, id = blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = id & 7;
-  const int wi = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (id >> 3);
+  // XCD-aware work mapping (speed only): every XCD gets a CONTIGUOUS range of work items, ordered (pair, ref split, row block)
+  // with the row block fastest, so the workgroups that stream the same ref descriptors share one L2 instead of re-fetching
+  // them through eight.
+  const int id = blockIdx.x, wi = xcd_contiguous(id, gridDim.x);
   int rb = wi % rb_count;
   int split = (wi / rb_count) % splits;
   int pair = wi / (rb_count * splits);
@@ -92,24 +78,8 @@ __global__ __launch_bounds__(256) void nn_match_kernel(const float* __restrict__
   }
   const int32_t* lst = rowlist ? rowlist + (int64_t)pair * J : nullptr;
   auto rowof = [&](int v) { return v < vJ ? (lst ? lst[v] : v) : -1; };
-  const float* Ap = A + (int64_t)pair * J * 64;
-  const float* Bp = B + (int64_t)pair * K * 64;
   const int row0 = (rb * 4 + w) * (16 * RT);
 
-  // A fragments: lane holds A[row = fr][k = 4 s + fq]
-  float af[RT][16];
-  float san[RT][4];
-#pragma unroll
-  for (int rt = 0; rt < RT; ++rt) {
-    const int row = rowof(row0 + rt * 16 + fr);
-#pragma unroll
-    for (int s = 0; s < 16; ++s) af[rt][s] = row >= 0 ? Ap[(int64_t)row * 64 + 4 * s + fq] : 0.f;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int rr = rowof(row0 + rt * 16 + 4 * fq + r);
-      san[rt][r] = rr >= 0 ? sa[(int64_t)pair * J + rr] : 0.f;
-    }
-  }
   float best[RT][4];
   int bidx[RT][4];
 #pragma unroll
@@ -119,67 +89,14 @@ __global__ __launch_bounds__(256) void nn_match_kernel(const float* __restrict__
 
   const int c_begin = split * cols_per_split;
   const int c_end = min(K, c_begin + cols_per_split);
-  // Pipeline: the next 64-column ref tile is fetched into registers while the MFMAs of the current
-  // tile run, then written to the other LDS buffer; one barrier per tile.
-  float4 pre[4];
-  float pre_sb = 0.f;
-  auto gload = [&](int c0) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int f = tid + 256 * i;
-      const int r = f >> 4, c4 = f & 15;
-      pre[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (c0 + r < c_end) pre[i] = *reinterpret_cast<const float4*>(Bp + (int64_t)(c0 + r) * 64 + c4 * 4);
-    }
-    if (tid < BC) pre_sb = (c0 + tid < c_end) ? sb[(int64_t)pair * K + c0 + tid] : 0.f;
-  };
-  auto lstore = [&](int buf) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int f = tid + 256 * i;
-      const int r = f >> 4, c4 = f & 15;
-      float2* dst = reinterpret_cast<float2*>(&Bs[buf][r * LDB + c4 * 4]);
-      dst[0] = make_float2(pre[i].x, pre[i].y);
-      dst[1] = make_float2(pre[i].z, pre[i].w);
-    }
-    if (tid < BC) sbs[buf][tid] = pre_sb;
-  };
-  gload(c_begin);
-  lstore(0);
-  __syncthreads();
-  int buf = 0;
-  for (int c0 = c_begin; c0 < c_end; c0 += BC) {
-    const bool has_next = c0 + BC < c_end;
-    if (has_next) gload(c0 + BC);
-    const float* Bt = Bs[buf];
-#pragma unroll
-    for (int t = 0; t < BC / 16; ++t) {
-      f32x4 acc[RT];
-#pragma unroll
-      for (int rt = 0; rt < RT; ++rt) acc[rt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int s = 0; s < 16; ++s) {
-        const float b = Bt[(16 * t + fr) * LDB + 4 * s + fq];
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt) acc[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[rt][s], b, acc[rt], 0, 0, 0);
-      }
-      const int col = c0 + 16 * t + fr;
-      const float sbv = sbs[buf][16 * t + fr];
-      if (col < c_end) {
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            // fl(fl(-2*dot + |a|^2) + |b|^2): -2*dot is exact, so the fused form rounds exactly like the reference
-            const float d = __fadd_rn(__fmaf_rn(acc[rt][r], -2.f, san[rt][r]), sbv);
-            if (d < best[rt][r]) { best[rt][r] = d; bidx[rt][r] = col; }
-          }
-      }
-    }
-    if (has_next) lstore(buf ^ 1);   // last readers of that buffer finished before the previous barrier
-    __syncthreads();
-    buf ^= 1;
-  }
+  // the update spelled as two selects: all 4 RT of a tile stay compare + v_cndmask pairs beside packed distance arithmetic (as a
+  // conditional store through the lambda's references the last one became a branch and the packing went odd: + 7 % VALU per tile)
+  exact_search_stream<RT>(Bs, sbs, A + (int64_t)pair * J * 64, B + (int64_t)pair * K * 64, sa + (int64_t)pair * J, sb + (int64_t)pair * K,
+                          row0, rowof, c_begin, c_end, [&](int rt, int r, float d, int col) __attribute__((always_inline)) {
+                            const bool lt = d < best[rt][r];   // strict: ties stay with the lower column, NaN never wins
+                            best[rt][r] = lt ? d : best[rt][r];
+                            bidx[rt][r] = lt ? col : bidx[rt][r];
+                          });
   // reduce over the 16 lanes that share a row; ties -> lower column
 #pragma unroll
   for (int rt = 0; rt < RT; ++rt)
@@ -217,85 +134,39 @@ void launch_sqnorm(const float* x, int64_t rows, float* out, hipStream_t st) {
                      (unsigned long long*)nullptr);
 }
 
-// scratch layout (floats): sa[pairs*J] | sb[pairs*K] | packed (u64)[pairs*J]
-size_t nn_match_scratch_bytes(int pairs, int J, int K) {
-  size_t f = ((size_t)pairs * J + (size_t)pairs * K + 3) & ~(size_t)3;
-  return f * 4 + (size_t)pairs * J * 8;
-}
+size_t nn_match_scratch_bytes(int pairs, int J, int K) { return nn_match_scratch(pairs, J, K).bytes; }
 
 // the exhaustive kernel over [pairs] x J x K with norms and the packed result slots supplied (slots preset to all ones)
 static void launch_core(const float* a, const float* b, const float* sa, const float* sb, int pairs, int J, int K,
                         unsigned long long* packed, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1,
                         unsigned long long* tstamp, const int32_t* gate, int gate_min, const int32_t* rowlist = nullptr) {
-  // geometry: 2 row tiles per wave (128-row blocks) once there is enough work, else 64-row blocks; the ref
-  // range is split so that the grid is a whole number of residency rounds (256 CUs x 4 blocks: 34 KB LDS each)
-  static const int force_rt = (int)tuning_int("DSIR_MATCH_RT", 0);   // tuning hook
-  int rt = (int64_t)pairs * ((J + 127) / 128) >= 256 ? 2 : 1;
-  if (force_rt == 1 || force_rt == 2 || force_rt == 4) rt = force_rt;
-  if (rowlist) rt = 1;                          // few rows per pair: small row blocks, the ref range split as far as it goes
-  const int rows_per_block = 64 * rt;
-  const int resident = rt == 4 ? 768 : 1024;   // blocks the chip holds at once (VGPR- resp. LDS-limited)
-  // a row list holds fewer than gate_min rows
-  const int rb_count = ((rowlist ? (gate_min < J ? gate_min : J) : J) + rows_per_block - 1) / rows_per_block;
-  const int64_t base = (int64_t)pairs * rb_count;
-  const int tiles = (K + BC - 1) / BC;
-  int splits = 1;
-  double best_eff = -1.0;
-  if (rowlist) { splits = tiles / 8 < 1 ? 1 : (tiles / 8 > 16 ? 16 : tiles / 8); best_eff = 2.0; }
-  // A launch that fits the chip in ONE residency round (a single pair: 79 row blocks) is bound by the CU that gets the most
-  // workgroups: its matrix pipe serves ceil(blocks / 256) of them, each tiles_per tiles long plus ~2 tiles' worth of
-  // prologue / epilogue; one or two workgroups per CU run no faster than three (their load latencies no longer overlap).  (Measured at 1 x 5000 x 5000:
-  // 9 splits 3.595 ms per registration, 10 splits - what the balance formula below picks - 3.627, 12: 3.60, 8: 3.613, 4: 3.69.)
-  int max_nsp = 1;
-  for (int sp = 1; sp <= 16 && sp <= tiles; ++sp) {
-    const int tiles_per = (tiles + sp - 1) / sp;
-    if (sp > 1 && tiles_per < 8) break;
-    max_nsp = (tiles + tiles_per - 1) / tiles_per;
-  }
-  const bool one_round = !rowlist && base * max_nsp <= resident;
-  double best_cost = 1e30;
-  for (int sp = 1; sp <= 16 && sp <= tiles && !rowlist; ++sp) {
-    const int tiles_per = (tiles + sp - 1) / sp;
-    if (sp > 1 && tiles_per < 8) break;                    // keep the A-fragment preload amortised
-    const int nsp = (tiles + tiles_per - 1) / tiles_per;
-    const int64_t blocks = base * nsp;
-    if (one_round) {
-      const int64_t per_cu = (blocks + 255) / 256;
-      const double cost = (double)(per_cu < 3 ? 3 : per_cu) * (tiles_per + 2);   // < 3 workgroups per CU: no faster than 3
-      if (cost < best_cost - 1e-9) { best_cost = cost; splits = sp; }
-      continue;
-    }
-    const int64_t rounds = (blocks + resident - 1) / resident;
-    double eff = (double)blocks / (double)(rounds * resident);   // residency balance
-    eff *= (double)tiles / (double)(tiles_per * nsp);        // padding of the last split
-    if (eff > best_eff + 1e-9) { best_eff = eff; splits = sp; }
-  }
-  static const int force_splits = (int)tuning_int("DSIR_MATCH_SPLITS", 0);   // tuning hook
-  if (force_splits > 0) splits = force_splits < tiles ? force_splits : tiles;
-  int cols = ((tiles + splits - 1) / splits) * BC;
-  splits = (K + cols - 1) / cols;
-  dim3 grid((unsigned)((int64_t)rb_count * splits * pairs));
+  static const int force_rt = (int)tuning_int("DSIR_MATCH_RT", 0);           // tuning hooks
+  static const int force_splits = (int)tuning_int("DSIR_MATCH_SPLITS", 0);
+  const ExactPlan pl = nn_match_plan(pairs, J, K, rowlist ? gate_min : 0, force_rt, force_splits);   // a row list holds fewer than gate_min rows
+  const dim3 grid((unsigned)pl.blocks(pairs));
   if (ev0) hipEventRecord(ev0, st);
-  if (rt == 4)      hipLaunchKernelGGL((nn_match_kernel<4>), grid, dim3(256), 0, st, a, b, sa, sb, J, K, cols, rb_count, splits, packed, tstamp, gate, gate_min, rowlist);
-  else if (rt == 2) hipLaunchKernelGGL((nn_match_kernel<2>), grid, dim3(256), 0, st, a, b, sa, sb, J, K, cols, rb_count, splits, packed, tstamp, gate, gate_min, rowlist);
-  else              hipLaunchKernelGGL((nn_match_kernel<1>), grid, dim3(256), 0, st, a, b, sa, sb, J, K, cols, rb_count, splits, packed, tstamp, gate, gate_min, rowlist);
+#define DSIR_LAUNCH_MATCH(RTV)                                                                                                          \
+  hipLaunchKernelGGL((nn_match_kernel<RTV>), grid, dim3(256), 0, st, a, b, sa, sb, J, K, pl.cols_per_split, pl.rb_count, pl.splits, packed, \
+                     tstamp, gate, gate_min, rowlist)
+  if (pl.rt == 4)      DSIR_LAUNCH_MATCH(4);
+  else if (pl.rt == 2) DSIR_LAUNCH_MATCH(2);
+  else                 DSIR_LAUNCH_MATCH(1);
+#undef DSIR_LAUNCH_MATCH
   if (ev1) hipEventRecord(ev1, st);
 }
 
 void nn_match_scratch_layout(void* scratch, int pairs, int J, int K, float** sa, unsigned long long** packed) {
-  float* s = reinterpret_cast<float*>(scratch);
-  const size_t f = ((size_t)pairs * J + (size_t)pairs * K + 3) & ~(size_t)3;
-  *sa = s;
-  *packed = reinterpret_cast<unsigned long long*>(s + f);
+  const ExactScratch L = nn_match_scratch(pairs, J, K);
+  *sa = at<float>(scratch, L.sa);
+  *packed = at<unsigned long long>(scratch, L.tail);
 }
 
 void launch_nn_match_ws(const float* a, const float* b, int pairs, int J, int K, int32_t* idx, void* scratch,
                         hipStream_t st, hipEvent_t ev0, hipEvent_t ev1, bool ref_norms_cached, unsigned long long* tstamp,
                         bool src_norms_ready) {
-  float* sa = reinterpret_cast<float*>(scratch);
-  float* sb = sa + (size_t)pairs * J;
-  size_t f = ((size_t)pairs * J + (size_t)pairs * K + 3) & ~(size_t)3;
-  unsigned long long* packed = reinterpret_cast<unsigned long long*>(sa + f);
+  const ExactScratch L = nn_match_scratch(pairs, J, K);
+  float *sa = at<float>(scratch, L.sa), *sb = at<float>(scratch, L.sb);
+  unsigned long long* packed = at<unsigned long long>(scratch, L.tail);
   const int64_t ra = (int64_t)pairs * J, rb = (int64_t)pairs * K;
   if (!src_norms_ready) hipLaunchKernelGGL(sqnorm_kernel, dim3((unsigned)((ra + 15) / 16)), dim3(256), 0, st, a, ra, sa, packed);
   // the ref descriptors are loop invariant in dsir_register: their norms stay in the (persistent) scratch

@@ -2,8 +2,8 @@
 // correspondence lists built on them (ratio test, k candidates per src row).  The [J, K] matrix never exists.
 //
 // THE RULE (restated in DESIGN.md section 8 and on the host in deepsir_amd/match.py):
-//   distance   d(j, c) = ((-2 a_j.b_c) + |a_j|^2) + |b_c|^2 in fp32, dsir_nn_match's: a.b from the v_mfma_f32_16x16x4_f32 chain from
-//              a zero accumulator, channels 0..63 ascending; the norms from launch_sqnorm (nn_match.hip's sqnorm_kernel).
+//   distance   d(j, c): THE RULE of exact_search_body.h, by construction dsir_nn_match's - both kernels get their distances from the
+//              same exact_search_stream; the norms from launch_sqnorm (nn_match.hip's sqnorm_kernel).
 //   key        order_bits(d) << 32 | c, unsigned 64 bit - the packed value nn_match_kernel minimises.
 //   answer     a row's k smallest keys, ascending.  An integer rule: ties go to the lower column, nothing depends on the arrival
 //              order of workgroups (no atomics anywhere; every partial list has one writer).  Rank 0 is dsir_nn_match's result.
@@ -16,11 +16,10 @@
 //   candidates (j, c) for every rank < k of row j that has an entry; under `mutual` kept iff j is among the k smallest keys of
 //              column c in the ref -> src search; output in ascending j, then ascending rank; rows beyond counts[p] are -1.
 //
-// nn_topk_kernel<KK, RT> keeps nn_match_kernel's structure: block = 4 waves, wave w owns RT row tiles whose A fragments stay in
-// registers, ref columns stream through the double-buffered padded LDS tile of 64, the same XCD-aware work mapping with the column
-// range split over workgroups.  Per 16x16 tile a lane holds 4 rows x one column; per row it keeps a sorted list of KK (distance,
-// column) entries in registers: one comparison against the KK-th entry guards an unrolled compare-exchange ladder (static indices
-// only).  A lane meets its columns in ascending order, so the strict float comparison nn_match_kernel uses puts an equal distance
+// nn_topk_kernel<KK, RT> walks the tiles as nn_match_kernel does (exact_search_stream: block = 4 waves, wave w owns RT row tiles),
+// under the same XCD-aware work mapping with the column range split over workgroups (search_plan.h's nn_topk_plan).  Per 16x16 tile
+// a lane holds 4 rows x one column; per row it keeps a sorted list of KK (distance, column) entries in registers: one comparison
+// against the KK-th entry guards an unrolled compare-exchange ladder (static indices only).  A lane meets its columns in ascending order, so the strict float comparison nn_match_kernel uses puts an equal distance
 // behind the earlier (lower) column: the lane's list is in key order.  (A distance is never -0: |a|^2 and |b|^2 are sums of squares,
 // +0 at the least, and x + +0 is -0 only for x = -0, which (-2 dot) + |a|^2 cannot be.)  At the end of the column range the 16
 // lanes that share a row merge their lists as keys in a 4-step butterfly (merge_topk: a bitonic merge of two sorted lists, static
@@ -28,15 +27,14 @@
 // nn_topk_merge_kernel: one lane per row merges the splits' partials with the same merge_topk and writes idx / dist.
 #include "kernels.h"
 #include "device_utils.h"
-#include "screen_bound.h"
+#include "exact_search_body.h"
+#include "scratch.h"
 #include "search_plan.h"
 
 namespace dsir {
 
 namespace {
 
-constexpr int BC = 64;        // ref columns per LDS tile
-constexpr int LDB = 64 + 2;   // padded row (floats)
 constexpr unsigned long long kEmpty = ~0ull;
 
 __device__ __forceinline__ void cswap(unsigned long long& a, unsigned long long& b) {
@@ -77,24 +75,8 @@ __global__ __launch_bounds__(256) void nn_topk_kernel(const float* __restrict__ 
   const int rb = wi % rb_count;
   const int split = (wi / rb_count) % splits;
   const int pair = wi / (rb_count * splits);
-  const float* Ap = A + (int64_t)pair * J * 64;
-  const float* Bp = B + (int64_t)pair * K * 64;
   const int row0 = (rb * 4 + w) * (16 * RT);
 
-  // A fragments: lane holds A[row = fr][k = 4 s + fq]
-  float af[RT][16];
-  float san[RT][4];
-#pragma unroll
-  for (int rt = 0; rt < RT; ++rt) {
-    const int row = row0 + rt * 16 + fr;
-#pragma unroll
-    for (int s = 0; s < 16; ++s) af[rt][s] = row < J ? Ap[(int64_t)row * 64 + 4 * s + fq] : 0.f;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int rr = row0 + rt * 16 + 4 * fq + r;
-      san[rt][r] = rr < J ? sa[(int64_t)pair * J + rr] : 0.f;
-    }
-  }
   // the lists: ascending (distance, column), an empty entry is (+inf, -1)
   float ld[RT][4][KK];
   int lc[RT][4][KK];
@@ -107,75 +89,21 @@ __global__ __launch_bounds__(256) void nn_topk_kernel(const float* __restrict__ 
 
   const int c_begin = split * cols_per_split;
   const int c_end = min(K, c_begin + cols_per_split);
-  float4 pre[4];
-  float pre_sb = 0.f;
-  auto gload = [&](int c0) {
+  exact_search_stream<RT>(
+      Bs, sbs, A + (int64_t)pair * J * 64, B + (int64_t)pair * K * 64, sa + (int64_t)pair * J, sb + (int64_t)pair * K, row0,
+      [&](int v) { return v < J ? v : -1; }, c_begin, c_end, [&](int rt, int r, float d, int col) __attribute__((always_inline)) {
+        if (d < ld[rt][r][KK - 1]) {   // the guard: almost every candidate fails it after the first few tiles
+          ld[rt][r][KK - 1] = d; lc[rt][r][KK - 1] = col;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int f = tid + 256 * i;
-      const int r = f >> 4, c4 = f & 15;
-      pre[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (c0 + r < c_end) pre[i] = *reinterpret_cast<const float4*>(Bp + (int64_t)(c0 + r) * 64 + c4 * 4);
-    }
-    if (tid < BC) pre_sb = (c0 + tid < c_end) ? sb[(int64_t)pair * K + c0 + tid] : 0.f;
-  };
-  auto lstore = [&](int buf) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int f = tid + 256 * i;
-      const int r = f >> 4, c4 = f & 15;
-      float2* dst = reinterpret_cast<float2*>(&Bs[buf][r * LDB + c4 * 4]);
-      dst[0] = make_float2(pre[i].x, pre[i].y);
-      dst[1] = make_float2(pre[i].z, pre[i].w);
-    }
-    if (tid < BC) sbs[buf][tid] = pre_sb;
-  };
-  gload(c_begin);
-  lstore(0);
-  __syncthreads();
-  int buf = 0;
-  for (int c0 = c_begin; c0 < c_end; c0 += BC) {
-    const bool has_next = c0 + BC < c_end;
-    if (has_next) gload(c0 + BC);
-    const float* Bt = Bs[buf];
-#pragma unroll
-    for (int t = 0; t < BC / 16; ++t) {
-      f32x4 acc[RT];
-#pragma unroll
-      for (int rt = 0; rt < RT; ++rt) acc[rt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int s = 0; s < 16; ++s) {
-        const float b = Bt[(16 * t + fr) * LDB + 4 * s + fq];
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt) acc[rt] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[rt][s], b, acc[rt], 0, 0, 0);
-      }
-      const int col = c0 + 16 * t + fr;
-      const float sbv = sbs[buf][16 * t + fr];
-      if (col < c_end) {
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            // nn_match_kernel's expression, operand for operand
-            const float d = __fadd_rn(__fmaf_rn(acc[rt][r], -2.f, san[rt][r]), sbv);
-            if (d < ld[rt][r][KK - 1]) {   // the guard: almost every candidate fails it after the first few tiles
-              ld[rt][r][KK - 1] = d; lc[rt][r][KK - 1] = col;
-#pragma unroll
-              for (int i = KK - 1; i >= 1; --i) {
-                const bool up = ld[rt][r][i] < ld[rt][r][i - 1];   // strict: an equal distance stays behind the lower column
-                const float d0 = ld[rt][r][i - 1], d1 = ld[rt][r][i];
-                const int c0_ = lc[rt][r][i - 1], c1_ = lc[rt][r][i];
-                ld[rt][r][i - 1] = up ? d1 : d0; ld[rt][r][i] = up ? d0 : d1;
-                lc[rt][r][i - 1] = up ? c1_ : c0_; lc[rt][r][i] = up ? c0_ : c1_;
-              }
-            }
+          for (int i = KK - 1; i >= 1; --i) {
+            const bool up = ld[rt][r][i] < ld[rt][r][i - 1];   // strict: an equal distance stays behind the lower column
+            const float d0 = ld[rt][r][i - 1], d1 = ld[rt][r][i];
+            const int c0_ = lc[rt][r][i - 1], c1_ = lc[rt][r][i];
+            ld[rt][r][i - 1] = up ? d1 : d0; ld[rt][r][i] = up ? d0 : d1;
+            lc[rt][r][i - 1] = up ? c1_ : c0_; lc[rt][r][i] = up ? c0_ : c1_;
           }
-      }
-    }
-    if (has_next) lstore(buf ^ 1);   // last readers of that buffer finished before the previous barrier
-    __syncthreads();
-    buf ^= 1;
-  }
+        }
+      });
   // the 16 lanes that share a row (same fq): butterfly over fr, every lane ends with the row's merged list
 #pragma unroll
   for (int rt = 0; rt < RT; ++rt)
@@ -279,44 +207,36 @@ __global__ __launch_bounds__(256) void corr_topk_compact_kernel(const int32_t* _
   if (tid == 0) counts[pair] = base;
 }
 
-inline int topk_kk(int k) { return k <= 2 ? 2 : (k <= 4 ? 4 : 8); }
-inline size_t topk_norm_floats(int pairs, int J, int K) { return ((size_t)pairs * J + (size_t)pairs * K + 3) & ~(size_t)3; }
-
-template <int KK, int RT>
-void launch_kk(const float* a, const float* b, const float* sa, const float* sb, int pairs, int J, int K, const TopkPlan& pl,
-               unsigned long long* partial, hipStream_t st) {
-  const dim3 grid((unsigned)((int64_t)pl.rb_count * pl.splits * pairs));
-  hipLaunchKernelGGL((nn_topk_kernel<KK, RT>), grid, dim3(256), 0, st, a, b, sa, sb, J, K, pl.cols_per_split, pl.rb_count, pl.splits,
-                     partial);
+// one kernel per list length KK: the main kernel at rt row tiles per wave, then the merge of the splits' partials
+template <int KK>
+void launch_kk(const float* a, const float* b, const float* sa, const float* sb, int pairs, int J, int K, int k, const ExactPlan& pl,
+               unsigned long long* partial, int32_t* idx, float* dist, hipStream_t st) {
+  const dim3 grid((unsigned)pl.blocks(pairs));
+  constexpr int RT2 = KK <= 4 ? 2 : 1;   // nn_topk_plan takes two row tiles only where the lists fit beside them
+  const auto kernel = pl.rt == 2 ? nn_topk_kernel<KK, RT2> : nn_topk_kernel<KK, 1>;
+  hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, a, b, sa, sb, J, K, pl.cols_per_split, pl.rb_count, pl.splits, partial);
+  const unsigned blocks = (unsigned)(((int64_t)pairs * J + 255) / 256);
+  hipLaunchKernelGGL((nn_topk_merge_kernel<KK>), dim3(blocks), dim3(256), 0, st, partial, pairs, J, pl.splits, k, idx, dist);
 }
 
 }  // namespace
 
 int nn_topk_splits(int pairs, int J, int K, int k) { return nn_topk_plan(pairs, J, K, topk_kk(k)).splits; }
 
-// scratch layout: sa [pairs J] | sb [pairs K] (floats, padded to 4) | partial u64 [pairs][splits][J][KK]
-size_t nn_topk_scratch_bytes(int pairs, int J, int K, int k) {
-  const int kk = topk_kk(k);
-  const TopkPlan pl = nn_topk_plan(pairs, J, K, kk);
-  return topk_norm_floats(pairs, J, K) * 4 + (size_t)pairs * pl.splits * J * kk * 8;
-}
+size_t nn_topk_scratch_bytes(int pairs, int J, int K, int k) { return nn_topk_scratch(pairs, J, K, k).bytes; }
 
 void launch_nn_topk(const float* a, const float* b, int pairs, int J, int K, int k, int32_t* idx, float* dist, void* scratch,
                     hipStream_t st) {
   const int kk = topk_kk(k);
-  const TopkPlan pl = nn_topk_plan(pairs, J, K, kk);
-  float* sa = reinterpret_cast<float*>(scratch);
-  float* sb = sa + (size_t)pairs * J;
-  unsigned long long* partial = reinterpret_cast<unsigned long long*>(sa + topk_norm_floats(pairs, J, K));
+  const ExactPlan pl = nn_topk_plan(pairs, J, K, kk);
+  const ExactScratch L = nn_topk_scratch(pairs, J, K, k);
+  float *sa = at<float>(scratch, L.sa), *sb = at<float>(scratch, L.sb);
+  unsigned long long* partial = at<unsigned long long>(scratch, L.tail);
   launch_sqnorm(a, (int64_t)pairs * J, sa, st);
   launch_sqnorm(b, (int64_t)pairs * K, sb, st);
-  if (kk == 2)      { if (pl.rt == 2) launch_kk<2, 2>(a, b, sa, sb, pairs, J, K, pl, partial, st); else launch_kk<2, 1>(a, b, sa, sb, pairs, J, K, pl, partial, st); }
-  else if (kk == 4) { if (pl.rt == 2) launch_kk<4, 2>(a, b, sa, sb, pairs, J, K, pl, partial, st); else launch_kk<4, 1>(a, b, sa, sb, pairs, J, K, pl, partial, st); }
-  else              launch_kk<8, 1>(a, b, sa, sb, pairs, J, K, pl, partial, st);
-  const unsigned blocks = (unsigned)(((int64_t)pairs * J + 255) / 256);
-  if (kk == 2)      hipLaunchKernelGGL((nn_topk_merge_kernel<2>), dim3(blocks), dim3(256), 0, st, partial, pairs, J, pl.splits, k, idx, dist);
-  else if (kk == 4) hipLaunchKernelGGL((nn_topk_merge_kernel<4>), dim3(blocks), dim3(256), 0, st, partial, pairs, J, pl.splits, k, idx, dist);
-  else              hipLaunchKernelGGL((nn_topk_merge_kernel<8>), dim3(blocks), dim3(256), 0, st, partial, pairs, J, pl.splits, k, idx, dist);
+  if (kk == 2)      launch_kk<2>(a, b, sa, sb, pairs, J, K, k, pl, partial, idx, dist, st);
+  else if (kk == 4) launch_kk<4>(a, b, sa, sb, pairs, J, K, k, pl, partial, idx, dist, st);
+  else              launch_kk<8>(a, b, sa, sb, pairs, J, K, k, pl, partial, idx, dist, st);
 }
 
 void launch_corr_topk_compact(const int32_t* iab, const float* dab, int stride_ab, const int32_t* iba, int stride_ba, int pairs, int J,

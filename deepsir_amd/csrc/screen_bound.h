@@ -25,6 +25,7 @@
 // and never take that path).
 #pragma once
 #include "device_utils.h"
+#include "exact_search_body.h"
 
 namespace dsir {
 
@@ -44,14 +45,6 @@ constexpr float kLowerScale = -4.76837158203125e-7f;    // z' = 2^22 z: L = slo 
 constexpr float kMarginExact = 2e-5f;       // (1 + |a|^2 + |b|^2): on an exact fp32 distance used as a row's upper bound T
 constexpr float kMarginCentroid = 1e-5f;    // (1 + |a|^2 + |c|^2): D(a, c) against the true |a - c|^2, under the lower bound L
 constexpr float kMarginRoot = 1.00002f;     // on sqrt(T) and the tile radius: the factor 1 / 0.99999 on sqrt(L) and the rounding of sqrtf
-
-__device__ __forceinline__ unsigned int order_bits(float f) {
-  const unsigned int u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float unorder_bits(unsigned int b) {
-  return __uint_as_float((b & 0x80000000u) ? (b & 0x7fffffffu) : ~b);
-}
 
 // the accumulator seed of a column: the chain's first C operand.  A column that is not live takes -INFINITY instead and never wins;
 // the callers select (a flag passed through here costs the dense screen_kernel 2 VGPRs: its short-circuit is no longer threaded)
@@ -85,8 +78,8 @@ __device__ __forceinline__ f32x4 screen_chain(const ScreenFrag& a, const ScreenF
   return z;
 }
 
-// exact D(a, b) exactly as nn_match.hip evaluates it: the k-ordered fmaf chain of v_mfma_f32_16x16x4_f32 from a zero
-// accumulator, then fl(fl(-2 dot + |a|^2) + |b|^2).  a: the row as float4 [16] in registers, or a const float4* to it
+// exact D(a, b) by THE RULE of exact_search_body.h in scalar code: the k-ordered fmaf chain of v_mfma_f32_16x16x4_f32 from a zero
+// accumulator, then dist_from_dot.  a: the row as float4 [16] in registers, or a const float4* to it
 template <typename A>
 __device__ __forceinline__ float exact_dist(const A& a, const float* __restrict__ b, float san, float sbn) {
   float acc = 0.f;
@@ -95,7 +88,7 @@ __device__ __forceinline__ float exact_dist(const A& a, const float* __restrict_
     const float4 u = a[q], v = reinterpret_cast<const float4*>(b)[q];
     acc = fmaf(u.x, v.x, acc); acc = fmaf(u.y, v.y, acc); acc = fmaf(u.z, v.z, acc); acc = fmaf(u.w, v.w, acc);
   }
-  return __fadd_rn(__fmaf_rn(acc, -2.f, san), sbn);
+  return dist_from_dot(acc, san, sbn);
 }
 
 }  // namespace dsir

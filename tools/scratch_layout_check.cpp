@@ -2,6 +2,8 @@
 // resample.hip, ransac.hip, consensus.hip and match_targets.hip.  Every layout, at edge shapes: the parts start on 256 bytes, lie in
 // declaration order, do not overlap and end inside `bytes`; and `bytes` equals the sum the operator's size function was written as
 // before the layouts existed (spelled out below, term by term), with the library's temporary size an arbitrary number on both sides.
+// Also csrc/search_plan.h's ExactScratch, the layout of the exact descriptor search (nn_match.hip, nn_topk.hip): its closed form and the
+// byte counts of both size functions against recorded values.
 // Host code only, runs on the CPU, no GPU and no Python loader.
 //   hipcc -x c++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -Ideepsir_amd/csrc \
 //         tools/scratch_layout_check.cpp -o /tmp/scratch_layout_check && /tmp/scratch_layout_check
@@ -11,6 +13,7 @@
 #include <cstdlib>
 #include <vector>
 #include "op_layouts.h"
+#include "search_plan.h"
 using namespace dsir;
 
 static long checks = 0;
@@ -117,6 +120,48 @@ int main() {
       CHECK(co.bytes == pose + al(P * M * W * 8) + al(P * M * 4) + 2 * al(P * M * 8) + al((P + 1) * 4) + al(tmp) + al(P * H * 4) + al(P * H * 48) +
                             2 * al(P * H * 4));
     }
+  }
+
+  // ---- the exact descriptor search (search_plan.h): sa | sb | pad to 4 floats | tail of 8-byte words - a closed form of its own, no
+  // 256-byte parts.  {P, J, K} and the bytes nn_match_scratch_bytes / nn_topk_scratch_bytes (k = 1, 4, 8) gave when each spelled the
+  // layout out itself.
+  const struct { int P, J, K; size_t match, topk1, topk4, topk8; } ex[] = {
+      {1, 5000, 5000, 80000ull, 600000ull, 1160000ull, 2280000ull},
+      {2, 5000, 5000, 160000ull, 720000ull, 1360000ull, 2640000ull},
+      {128, 5000, 5000, 10240000ull, 15360000ull, 25600000ull, 46080000ull},
+      {256, 5000, 5000, 20480000ull, 30720000ull, 51200000ull, 92160000ull},
+      {1, 1, 1, 24ull, 32ull, 48ull, 80ull},
+      {1, 70, 63, 1104ull, 1664ull, 2784ull, 5024ull},
+      {128, 129, 70, 233984ull, 366080ull, 630272ull, 1158656ull},
+      {64, 385, 70, 313600ull, 510720ull, 904960ull, 1693440ull},
+      {1, 5000, 511, 62048ull, 102048ull, 182048ull, 342048ull},
+      {1, 5000, 512, 62048ull, 102048ull, 182048ull, 342048ull},
+      {1, 5000, 513, 62064ull, 102064ull, 182064ull, 342064ull},
+      {1, 5000, 1023, 64096ull, 184096ull, 344096ull, 664096ull},
+      {1, 5000, 1024, 64096ull, 184096ull, 344096ull, 664096ull},
+      {1, 5000, 1025, 64112ull, 184112ull, 344112ull, 664112ull},
+      {128, 5000, 511, 7941632ull, 13061632ull, 23301632ull, 43781632ull},
+      {128, 5000, 512, 7942144ull, 13062144ull, 23302144ull, 43782144ull},
+      {128, 5000, 513, 7942656ull, 13062656ull, 23302656ull, 43782656ull},
+      {128, 5000, 1023, 8203776ull, 13323776ull, 23563776ull, 44043776ull},
+      {128, 5000, 1024, 8204288ull, 13324288ull, 23564288ull, 44044288ull},
+      {128, 5000, 1025, 8204800ull, 13324800ull, 23564800ull, 44044800ull},
+      {4096, 1 << 20, 1 << 20, 68719476736ull, 103079215104ull, 171798691840ull, 309237645312ull},
+  };
+  for (const auto& e : ex) {
+    ++shapes;
+    const size_t PJ = (size_t)e.P * e.J, PK = (size_t)e.P * e.K;
+    for (size_t tail_bytes : {(size_t)0, (size_t)8, PJ * 8}) {
+      const ExactScratch L(e.P, e.J, e.K, tail_bytes);
+      CHECK(L.sa == 0 && L.sb == L.sa + PJ * 4 && L.tail >= L.sb + PK * 4 && L.tail < L.sb + PK * 4 + 16);   // ascending, the pad below 4 floats
+      CHECK(L.tail % 8 == 0 && L.tail % 16 == 0);
+      CHECK(L.bytes == ((PJ + PK + 3) & ~(size_t)3) * 4 + tail_bytes && L.bytes == L.tail + tail_bytes);
+    }
+    CHECK(nn_match_scratch(e.P, e.J, e.K).bytes == e.match);
+    CHECK(nn_topk_scratch(e.P, e.J, e.K, 1).bytes == e.topk1 && nn_topk_scratch(e.P, e.J, e.K, 2).bytes == e.topk1);
+    CHECK(nn_topk_scratch(e.P, e.J, e.K, 3).bytes == e.topk4 && nn_topk_scratch(e.P, e.J, e.K, 4).bytes == e.topk4);
+    CHECK(nn_topk_scratch(e.P, e.J, e.K, 5).bytes == e.topk8 && nn_topk_scratch(e.P, e.J, e.K, 8).bytes == e.topk8);
+    CHECK(nn_match_scratch(e.P, e.J, e.K).tail == nn_topk_scratch(e.P, e.J, e.K, 8).tail);
   }
   std::printf("scratch_layout: %ld checks passed, %ld shapes laid out\n", checks, shapes);
   return 0;
