@@ -9,7 +9,7 @@
 //     are then exactly the 16 neighbours of ONE point (lane half = point, register = neighbour).  Softmax and weighted sum run in
 //     registers: no cross-lane instruction at all;
 //   * the whole score contraction fc [fN[nb] ; E] runs on the fp16 matrix pipe at fp32 accuracy (x = fp16(x) + fp16(x - fp16(x)), three
-//     MFMAs per product: agg_chain_h.hip; weights split at load): lane half h = 0 forms the gathered-feature part of an A row (one
+//     MFMAs per product: split_f16.h; weights split at load): lane half h = 0 forms the gathered-feature part of an A row (one
 //     index, one row of the raw features, their GroupNorm + LeakyReLU), h = 1 the E part (from memory, or rebuilt from the per-point
 //     tables of lse_uv.hip); the normalised values double as the pooled operand through a wave-private LDS tile, so the epilogue
 //     gathers nothing.  (A first version kept round 3's split of the scores by linearity - S = G[nb] + W2 E with G = W1 fN a per-point
@@ -165,7 +165,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(UV ? 4 : 5,
       *reinterpret_cast<float4*>(row) = make_float4(a[t][0], a[t][1], a[t][2], a[t][3]);
       *reinterpret_cast<float4*>(row + 4) = make_float4(a[t][4], a[t][5], a[t][6], a[t][7]);
       h8 ah, al;
-      split8f(a[t], ah, al);
+      split8(a[t], ah, al);
       acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, t ? whB : whA, acc, 0, 0, 0);
       acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, t ? wlB : wlA, acc, 0, 0, 0);
       acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, t ? whB : whA, acc, 0, 0, 0);
@@ -303,7 +303,7 @@ __global__ __launch_bounds__(512) void att_full128_kernel(const AttPool16Args p)
         const float v = fmaf(a[c], s_sc[KH * h + c], s_sh[KH * h + c]);
         a[c] = fmaxf(v, slope * v);
       }
-      split8f(&a[8 * s], ah[s], al[s]);
+      split8(&a[8 * s], ah[s], al[s]);
     }
     const int pt = 2 * u + h;
     const int un = u + nw;

@@ -3,21 +3,12 @@
 #pragma once
 #include "kernels.h"
 #include "device_utils.h"
+#include "split_f16.h"
 
 namespace dsir {
 namespace attp {
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ void split8f(const float* x, h8& h, h8& l) {
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const _Float16 t = (_Float16)x[k];
-    h[k] = t;
-    l[k] = (_Float16)(x[k] - (float)t);
-  }
-}
 
 // ---------------------------------------------------------------- levels 1 / 2 (d = 64 / 128): the UNSPLIT form on the same organisation
 // All d channels [fN[nb] (d/2) ; E (d/2)] are contracted, like level 0 does: lane half h = 0 forms the gathered-feature part of an A row (one index,
@@ -141,7 +132,7 @@ __device__ __forceinline__ void att_full_body(const AttPool16Args& p, const int 
         const float v = fmaf(a[c], s_sc[KH * h + c], s_sh[KH * h + c]);
         a[c] = fmaxf(v, slope * v);
       }
-      split8f(&a[8 * s], ah[s], al[s]);
+      split8(&a[8 * s], ah[s], al[s]);
     }
     // the pooled operand of this workgroup's 64 columns: d = 64 both halves (32 + 32), d = 128 the half the columns belong to
     if (KH == 32 || h == cb) {

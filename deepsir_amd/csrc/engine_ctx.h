@@ -31,7 +31,7 @@ struct BlockW { Mlp2dW mlp1, lfa1, lfa2, mlp2, skip; AttW att1, att2; int d_in =
 struct LinW { const float *W = nullptr, *b = nullptr; int cin = 0, cout = 0; };
 struct RandlaW { Mlp2dW pre; BlockW blk[4]; Mlp2dW mid; Mlp2dW dec[4]; const float* out_w = nullptr; int dec_out = 0; LinW fc[3]; int cin = 0, ncls = 0;
                  bool ppf = false;   // DSIR_FLAG_PPF: mlp_pre is the point-pair-feature layer (ppf.hip), level 0 takes 12 channels
-                 const void* head_wh[4] = {}; const void* head_wl[4] = {}; };   // fp16 split of mlp_out + fc_label (head_mlp_h.hip)
+                 const void* head_wh[4] = {}; const void* head_wl[4] = {}; };   // fp16 split of mlp_out + fc_label (head_mlp.hip)
 struct NetW { RandlaW feat, inl; LinW mlp_feat[3], mlp_att[5], mlp_proj; };
 
 // ------------------------------------------------------------------ workspace
@@ -140,7 +140,7 @@ struct dsir_ctx {
   int screen_mode = 1;
   int prune_min_points = 8192;          // pruned search (nn_prune.hip) for ref clouds of that many points and more; 0 = off
   long long prune_min_rows = 65536;     // ... in launches of that many src rows (pairs x points) and more
-  // aggregation chain: 1 = fp16-split products on the fp16 matrix pipe (agg_chain_h.hip), 0 = exact-fp32 chain (agg_chain.hip)
+  // aggregation chain: 1 = fp16-split products on the fp16 matrix pipe, 0 = exact-fp32 chain (agg_chain.hip)
   int agg_split = 1;
   int kabsch_chunked_min = 0;           // clouds of that many points and more solve their pose in chunks; 0 = kKabschChunkedMin
   // device-clock brackets {first wave start, last wave end} of the timed nn_match launches

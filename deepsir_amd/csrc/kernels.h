@@ -224,13 +224,13 @@ struct HeadArgs {
   int ncls = 0, M = 0, clouds = 1;
   float* feat_out = nullptr;    // [clouds][M][64] or nullptr
   float* logits_out = nullptr;  // [clouds][M][ncls]
-  // head_mlp_h.hip only: the fp16 split (high, low; same [Cout][Cin] layout) of W1 .. W4, made at weight load
+  // split form only: the fp16 split (high, low; same [Cout][Cin] layout) of W1 .. W4, made at weight load
   const void* Wh[4] = {nullptr, nullptr, nullptr, nullptr};
   const void* Wl[4] = {nullptr, nullptr, nullptr, nullptr};
 };
-bool launch_head_mlp(const HeadArgs& a, hipStream_t st);   // false => shape outside the fused envelope
-// the same head as fp16-split products on the fp16 matrix pipe (fp32 accuracy); false => split weights missing / outside the envelope
-bool launch_head_mlp_h(const HeadArgs& a, hipStream_t st);
+// split: the four layers as fp16-split products on the fp16 matrix pipe (split_f16.h; fp32 accuracy), else exact fp32
+// false => shape outside the fused envelope / split weights missing (nothing launched)
+bool launch_head_mlp(const HeadArgs& a, bool split, hipStream_t st);
 
 // agg_chain.hip — mlp_att chain + residual + mlp_proj + L2 normalise in one launch (model.py:223-233)
 struct AggArgs {
@@ -245,7 +245,7 @@ struct AggArgs {
   const float *W6 = nullptr, *b6 = nullptr;         // mlp_proj [64][64]
   float* desc = nullptr;                            // [clouds][n][64]
   int n = 0, clouds = 0;
-  // agg_chain_h.hip only, optional: what the descriptor search needs of the descriptors, written by the same epilogue instead of a
+  // split form only, optional: what the descriptor search needs of the descriptors, written by the same epilogue instead of a
   // second pass over them (nn_screen.hip split_norm_kernel / nn_match.hip sqnorm_kernel: same arithmetic, same bits) -
   // sq [clouds * n] = |desc|^2; hi / lo [clouds * n][64] fp16 = the screening's operand pair; packed_init [clouds * n] u64 = all ones
   // (the exhaustive search's result slots); each may be nullptr
@@ -253,15 +253,15 @@ struct AggArgs {
   void* hi = nullptr;
   void* lo = nullptr;
   unsigned long long* packed_init = nullptr;
-  // agg_chain_h.hip only: the fp16 split (high, low part; same [Cout][Cin] layout) of W2 .. W6, made at weight load
+  // split form only: the fp16 split (high, low part; same [Cout][Cin] layout) of W2 .. W6, made at weight load
   const void* Wh[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   const void* Wl[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
 };
-bool launch_agg_chain(const AggArgs& a, hipStream_t st);
-// the same chain with its five wide layers as three fp16 MFMAs per product (fp32 accuracy, 3/16 of the fp32 MFMA time);
-// false => split weights missing
-bool launch_agg_chain_h(const AggArgs& a, hipStream_t st);
-void split_weights_f16(const float* w, size_t n, uint16_t* hi, uint16_t* lo);   // host: x -> fp16(x), fp16(x - fp16(x))
+// split: the five wide layers as three fp16 MFMAs per product (split_f16.h; fp32 accuracy, 3/16 of the fp32 MFMA time), else exact
+// fp32; false => split weights missing (nothing launched)
+bool launch_agg_chain(const AggArgs& a, bool split, hipStream_t st);
+// weights.hip, host: x -> fp16(x), fp16(x - fp16(x)), the operand split of split_f16.h
+void split_weights_f16(const float* w, size_t n, uint16_t* hi, uint16_t* lo);
 
 // select.hip — feat / label pipelines (model.py:650-651, :682-697)
 size_t topk_scratch_bytes(int clouds, int n);

@@ -51,7 +51,7 @@ typedef _Float16 h4 __attribute__((ext_vector_type(4)));
 #endif
 constexpr int SRS = DSIR_SCREEN_SRS;     // halfs per LDS row: 64 + 16 pad (160 B; measured 1 % faster than the 144 B of a minimal pad)
 constexpr int CAP = 16;     // entries kept per row; more => the row goes to the exhaustive kernel
-// four channels fp32 -> fp16 high / low parts (see the header): device_utils.h, screen_split4 (shared with agg_chain_h.hip's epilogue)
+// four channels fp32 -> fp16 high / low parts (see the header): device_utils.h, screen_split4 (shared with the aggregation chain's epilogue, agg_chain_body.h)
 __device__ __forceinline__ void split4(const float4 v, h4& h, h4& l, int32_t* __restrict__ bad) { screen_split4(v, h, l, bad); }
 
 // x [rows][64] fp32 -> hi, lo [rows][64] fp16; one thread per 4 channels

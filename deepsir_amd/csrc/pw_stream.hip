@@ -20,6 +20,7 @@
 // 6-channel inlier input), and the relative position encoding (RandLANet.py:197-212).
 #include "kernels.h"
 #include "device_utils.h"
+#include "split_f16.h"
 
 namespace dsir {
 
@@ -49,17 +50,6 @@ __device__ __forceinline__ void vec_load(const float* __restrict__ p, float (&v)
 
 __device__ __forceinline__ int src_row(const Seg& s, int cloud, int row) {
   return s.idx ? s.idx[cloud * s.idx_cloud_stride + row] : row;
-}
-
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-// x[0..8) -> fp16(x), fp16(x - fp16(x)): the operand split of agg_chain_h.hip (three fp16 MFMAs per fp32 product)
-__device__ __forceinline__ void split8(const float* x, h8& h, h8& l) {
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const _Float16 t = (_Float16)x[k];
-    h[k] = t;
-    l[k] = (_Float16)(x[k] - (float)t);
-  }
 }
 
 // Occupancy floor: the level-1 lfa.mlp2 with the table loader (32 channels in) runs at the latency of its gather -> MFMA -> store
@@ -378,9 +368,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(pw_stream_m
           split8(&cur.v[8 * u], ah, al);
 #pragma unroll
           for (int t = 0; t < NT; ++t) {
-            acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, wh[t][u], acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, wl[t][u], acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, wh[t][u], acc[t], 0, 0, 0);
+            mma3(acc[t], ah, al, wh[t][u], wl[t][u]);
           }
         }
       } else {

@@ -4,6 +4,7 @@
 #pragma once
 #include "kernels.h"
 #include "device_utils.h"
+#include "split_f16.h"
 
 namespace dsir {
 namespace tile {
@@ -11,7 +12,7 @@ namespace tile {
 
 constexpr int BK = 32;
 constexpr int LDS_LD = BK + 2;
-// H = true (round 3): the contraction on the fp16 matrix pipe at fp32 accuracy, by the operand split of agg_chain_h.hip
+// H = true (round 3): the contraction on the fp16 matrix pipe at fp32 accuracy, by the operand split of split_f16.h
 // (x = fp16(x) + fp16(x - fp16(x)); a.b = ah.bh + ah.bl + al.bh: three v_mfma_f32_16x16x32_f16).  A values are split when
 // they are staged (after GroupNorm + LeakyReLU), weights were split at load (GemmArgs::Wh / Wl); the LDS tiles hold the two
 // fp16 parts in rows of 32 + 8 halfs (80 bytes: 16-byte aligned, conflict-free ds_read_b128 fragment reads), and a
@@ -19,24 +20,6 @@ constexpr int LDS_LD = BK + 2;
 // 31 - 40 % busy with two waves per SIMD contending for it.  Results differ from the H = false kernels (exact fp32,
 // k-ordered fmaf chains; DSIR_TILE_F32=1) by ~1e-7 of the layer's scale.
 constexpr int LDH = BK + 8;
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void split4f(const float4 v, h4& h, h4& l) {
-  const float f[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const _Float16 t = (_Float16)f[k];
-    h[k] = t;
-    l[k] = (_Float16)(f[k] - (float)t);
-  }
-}
-#define DSIR_MMA3H(acc, ah, al, bh, bl)                                      \
-  do {                                                                        \
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh, acc, 0, 0, 0);       \
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl, acc, 0, 0, 0);       \
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, acc, 0, 0, 0);       \
-  } while (0)
 constexpr int BN = 64;
 constexpr int NT = 4;
 constexpr int MAXC = 768;
@@ -189,7 +172,7 @@ __device__ __forceinline__ void pw_tile_body(const GemmArgs& p, const int bx, co
       v.z = fmaxf(v.z, slope * v.z); v.w = fmaxf(v.w, slope * v.w);
       if (H) {
         h4 hh, ll;
-        split4f(v, hh, ll);
+        split4(v, hh, ll);
         *reinterpret_cast<h4*>(&AsH[buf][0][(sr0 + 32 * i) * LDH + c4]) = hh;
         *reinterpret_cast<h4*>(&AsH[buf][1][(sr0 + 32 * i) * LDH + c4]) = ll;
       } else {
@@ -284,7 +267,7 @@ __device__ __forceinline__ void pw_tile_body(const GemmArgs& p, const int bx, co
         const h8 bh = *reinterpret_cast<const h8*>(&WsH[buf][0][(16 * t + fr) * LDH + 8 * fq]);
         const h8 bl = *reinterpret_cast<const h8*>(&WsH[buf][1][(16 * t + fr) * LDH + 8 * fq]);
 #pragma unroll
-        for (int rt = 0; rt < RT; ++rt) DSIR_MMA3H(acc[rt][t], ah[rt], al[rt], bh, bl);
+        for (int rt = 0; rt < RT; ++rt) mma3(acc[rt][t], ah[rt], al[rt], bh, bl);
       }
     } else {
       const float* At = As[H ? 0 : buf];
@@ -524,7 +507,7 @@ __device__ __forceinline__ void pw_tile_small_body(const GemmArgs& p, const int 
       v.z = fmaxf(v.z, slope * v.z); v.w = fmaxf(v.w, slope * v.w);
       if (H) {
         h4 hh, ll;
-        split4f(v, hh, ll);
+        split4(v, hh, ll);
         *reinterpret_cast<h4*>(&AsH[buf][0][(sr0 + 32 * i) * LDH + c4]) = hh;
         *reinterpret_cast<h4*>(&AsH[buf][1][(sr0 + 32 * i) * LDH + c4]) = ll;
       } else {
@@ -564,7 +547,7 @@ __device__ __forceinline__ void pw_tile_small_body(const GemmArgs& p, const int 
         const h8 bh = *reinterpret_cast<const h8*>(&WsH[buf][0][(16 * (NTW * wc + t) + fr) * LDH + 8 * fq]);
         const h8 bl = *reinterpret_cast<const h8*>(&WsH[buf][1][(16 * (NTW * wc + t) + fr) * LDH + 8 * fq]);
 #pragma unroll
-        for (int rt = 0; rt < RTS; ++rt) DSIR_MMA3H(acc[rt][t], ah[rt], al[rt], bh, bl);
+        for (int rt = 0; rt < RTS; ++rt) mma3(acc[rt][t], ah[rt], al[rt], bh, bl);
       }
     } else {
       const float* At = As[H ? 0 : buf];

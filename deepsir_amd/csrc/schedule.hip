@@ -583,13 +583,13 @@ int randla_forward(dsir_ctx* c, const RandlaW& w, const Seg& in0, const Seg* in1
     h.W1 = w.out_w; h.W2 = w.fc[0].W; h.b2 = w.fc[0].b; h.W3 = w.fc[1].W; h.b3 = w.fc[1].b; h.W4 = w.fc[2].W; h.b4 = w.fc[2].b;
     h.ncls = w.ncls; h.M = n0; h.clouds = py.clouds; h.feat_out = feat_out; h.logits_out = logits_out;
     if (c->ws.overflow) return overflow_fail(c, "workspace exhausted in randla_forward (raise max_points / max_pairs)");
-    // default: the head's four layers as fp16-split products (head_mlp_h.hip; fp32 accuracy); dsir_enable_agg_split(0) /
+    // default: the head's four layers as fp16-split products (fp32 accuracy); dsir_enable_agg_split(0) /
     // DSIR_AGG_F32: the exact-fp32 head, bit-identical to the four separate launches
     if (c->agg_split) {
       for (int k = 0; k < 4; ++k) { h.Wh[k] = w.head_wh[k]; h.Wl[k] = w.head_wl[k]; }
-      fused = launch_head_mlp_h(h, st);
+      fused = launch_head_mlp(h, true, st);
     }
-    if (!fused) fused = launch_head_mlp(h, st);
+    if (!fused) fused = launch_head_mlp(h, false, st);
   }
   LinW ow; ow.W = w.out_w; ow.b = nullptr; ow.cin = w.dec_out; ow.cout = g.out_feat_dim;
   Act feat;
@@ -628,16 +628,16 @@ bool run_att_proj(dsir_ctx* c, const float* xyz, int64_t xyz_cs, const float* sc
     a.W1 = m[0].W; a.b1 = m[0].b; a.W2 = m[1].W; a.b2 = m[1].b; a.W3 = m[2].W; a.b3 = m[2].b;
     a.W4 = m[3].W; a.b4 = m[3].b; a.W5 = m[4].W; a.b5 = m[4].b; a.W6 = w.mlp_proj.W; a.b6 = w.mlp_proj.b;
     a.desc = desc; a.n = n; a.clouds = clouds;
-    // default: the chain's wide layers as fp16-split products on the fp16 matrix pipe (agg_chain_h.hip: fp32 accuracy, not the
+    // default: the chain's wide layers as fp16-split products on the fp16 matrix pipe (agg_chain.hip: fp32 accuracy, not the
     // fp32 kernel's bits); dsir_enable_agg_split(0) / DSIR_AGG_F32: the exact-fp32 chain, bit-identical to the unfused launches below
     static const bool no_fuse = tuning_flag("DSIR_NO_AGG_EXTRAS");   // A/B switch: the search prepares its operands itself
     if (c->agg_split) {
       for (int k = 0; k < 5; ++k) { a.Wh[k] = c->agg_wh[k]; a.Wl[k] = c->agg_wl[k]; }
       if (ex && !no_fuse) { a.sq = ex->sq; a.hi = ex->hi; a.lo = ex->lo; a.packed_init = ex->packed_init; }
-      if (launch_agg_chain_h(a, c->stream)) return ex && !no_fuse;
+      if (launch_agg_chain(a, true, c->stream)) return ex && !no_fuse;
       a.sq = nullptr; a.hi = a.lo = nullptr; a.packed_init = nullptr;
     }
-    if (launch_agg_chain(a, c->stream)) return false;
+    if (launch_agg_chain(a, false, c->stream)) return false;
   }
   const Seg sx = plain_seg(xyz, xyz_cs, 3, 3);
   const Seg ss = plain_seg(score, n, 1, 1);

@@ -250,6 +250,27 @@ RandlaW bind_randla(const float* base, const RandlaOff& o, const dsir_cfg& g) {
 
 }  // namespace
 
+// fp32 weights -> the two fp16 parts of the split (host side, at weight load; the whole blob: 2.6 M values).  The same loop
+// twice: compiled for the baseline x86-64 the fp32 <-> fp16 conversions are library calls (35 ms per load), with F16C they are
+// one instruction (2 ms); both round to nearest even, so the parts are the same bits either way.
+#define DSIR_SPLIT_LOOP                                 \
+  for (size_t i = 0; i < n; ++i) {                      \
+    const _Float16 t = (_Float16)w[i];                  \
+    const _Float16 l = (_Float16)(w[i] - (float)t);     \
+    __builtin_memcpy(hi + i, &t, 2);                    \
+    __builtin_memcpy(lo + i, &l, 2);                    \
+  }
+#if !defined(__HIP_DEVICE_COMPILE__) && defined(__x86_64__)
+__attribute__((target("f16c"))) static void split_weights_f16c(const float* w, size_t n, uint16_t* hi, uint16_t* lo) { DSIR_SPLIT_LOOP }
+#endif
+void split_weights_f16(const float* w, size_t n, uint16_t* hi, uint16_t* lo) {
+#if !defined(__HIP_DEVICE_COMPILE__) && defined(__x86_64__)
+  if (__builtin_cpu_supports("f16c")) { split_weights_f16c(w, n, hi, lo); return; }
+#endif
+  DSIR_SPLIT_LOOP
+}
+#undef DSIR_SPLIT_LOOP
+
 }  // namespace dsir
 
 using namespace dsir;
@@ -308,7 +329,7 @@ int dsir_finalize_weights(dsir_ctx* c) {
   }
   {
     // fp16 split (x -> fp16(x), fp16(x - fp16(x))) of the WHOLE blob (BatchNorm already folded), at the same offsets: the kernels
-    // with an fp16-split contraction (agg_chain_h.hip, head_mlp_h.hip, pw_tile.hip) find the two parts of any matrix W at
+    // with an fp16-split contraction (agg_chain.hip, head_mlp.hip, pw_tile.hip) find the two parts of any matrix W at
     // dweights16 + (W - dweights) and dweights16 + nweights + (W - dweights).  20 MB for the align pipeline.
     u.blob.resize((u.blob.size() + 63) & ~(size_t)63, 0.f);     // the low parts start at dweights16 + total: keep them 16-byte aligned too
     const size_t total = u.blob.size();

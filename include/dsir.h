@@ -535,11 +535,11 @@ int dsir_match_timer2(dsir_ctx* ctx, int reset, double* op_ms, double* kernel_ms
  * fp16-screened path for large problems.  Both return the same bits.  Initialised from DSIR_NO_SCREEN (behind the tuning gate, below). */
 int dsir_enable_screen(dsir_ctx* ctx, int enable);
 /* A/B switch (measurement / test): 1 (default) = the five wide layers of the aggregation chain (mlp_att 32 -> 64 -> 128 -> 256 ->
- * 64, mlp_proj; network/model.py:223-233) run as fp16-split products on the fp16 matrix pipe (csrc/agg_chain_h.hip: each fp32
+ * 64, mlp_proj; network/model.py:223-233) run as fp16-split products on the fp16 matrix pipe (csrc/agg_chain.hip, csrc/split_f16.h: each fp32
  * operand = two fp16 numbers, three MFMAs per product, fp32 accumulation - fp32 accuracy, descriptors within ~1e-7 of the
- * fp32 kernel's); 0 = the exact-fp32 chain (csrc/agg_chain.hip), bit-identical to the unfused layer-by-layer launches.
+ * fp32 kernel's); 0 = the exact-fp32 form of the same chain, bit-identical to the unfused layer-by-layer launches.
  * Initialised from DSIR_AGG_F32 (set => 0).
- * What the switch covers: the aggregation chain, the per-point head (csrc/head_mlp_h.hip) and the LDS-tiled GEMMs (csrc/pw_tile.hip,
+ * What the switch covers: the aggregation chain, the per-point head (csrc/head_mlp.hip) and the LDS-tiled GEMMs (csrc/pw_tile.hip,
  * through GemmArgs::Wh staying unset).  What it does NOT cover: the attentive-pooling score contraction, which is an fp16-split
  * product unconditionally - csrc/att_pool.hip (levels 0 - 2) and the kSplit epilogues of csrc/pw_stream.hip (level 3 and the
  * DSIR_NO_ATT_POOL reference) have no exact-fp32 twin at run time; their fp32 reference is the oracle (tests/test_gpu_parity.py). */

@@ -60,7 +60,7 @@ def test_product_never_imports_the_oracle():
 
 
 def test_fp16_operand_split_is_exact_to_2_pow_minus_22():
-    """dsir_split_f16 (host, no GPU): the split the fp16-matrix-pipe layers rest on (csrc/agg_chain_h.hip, head_mlp_h.hip,
+    """dsir_split_f16 (host, no GPU): the split the fp16-matrix-pipe layers rest on (csrc/split_f16.h: agg_chain.hip, head_mlp.hip,
     pw_tile.hip, pw_stream.hip).  hi = fp16(x) and lo = fp16(x - hi), both round-to-nearest-even (numpy's conversion is the
     oracle here), and x = hi + lo + r with |r| <= max(2^-22 |x|, 2^-25) over the whole fp16 range, sub-normals included."""
     import numpy as np

@@ -879,8 +879,8 @@ def test_screened_argmin_shapes(P, J, K):
 @pytest.mark.parametrize("n,clouds,extent,wseed,variant", [(5000, 6, 3.0, 0, "plain"), (1357, 2, 3.0, 2, "separated"), (16384, 2, 50.0, 1, "plain"),
                                                            (700, 1, 3.0, 3, "plain")])
 def test_agg_chain_split_matches_fp32_chain(n, clouds, extent, wseed, variant):
-    """csrc/agg_chain_h.hip (the aggregation chain's wide layers as fp16-split products: three fp16 MFMAs per fp32 product,
-    fp32 accumulation) against csrc/agg_chain.hip (exact-fp32 MFMA, bit-identical to the layer-by-layer launches) on the same
+    """The split form of csrc/agg_chain.hip (the aggregation chain's wide layers as fp16-split products: three fp16 MFMAs per fp32 product,
+    fp32 accumulation) against its fp32 form (exact-fp32 MFMA, bit-identical to the layer-by-layer launches) on the same
     inputs through dsir_aggregate: unit descriptors within 2e-6 (measured ~1e-7: the size of fp32's own summation-order noise
     on these 64..256-term sums, and 10 x below the 2e-5 at which the descriptors are compared with the reference's,
     test_stages_vs_oracle_and_golden).  Both large (128 points per block) and small launches, ragged n."""
@@ -910,8 +910,8 @@ def test_agg_chain_split_matches_fp32_chain(n, clouds, extent, wseed, variant):
 
 @pytest.mark.parametrize("name,which", [("stage_n1024_s1", "feat_extractor"), ("e2e_n5000_s5", "feat_extractor"), ("e2e_n2048_s6_f4", "inlier_model")])
 def test_head_split_matches_fp32_head(name, which):
-    """csrc/head_mlp_h.hip (mlp_out + fc_label as fp16-split products, three fp16 MFMAs per fp32 product) against
-    csrc/head_mlp.hip (exact fp32, bit-identical to the four separate launches) through dsir_randla_forward: the 64-d
+    """The split form of csrc/head_mlp.hip (mlp_out + fc_label as fp16-split products, three fp16 MFMAs per fp32 product) against
+    its fp32 form (exact fp32, bit-identical to the four separate launches) through dsir_randla_forward: the 64-d
     feature and the logits within 1e-5 of their scale (measured ~1e-6), for the feature extractor (19 classes) and the
     inlier model (1 logit)."""
     g, m, cfg, sd, data = build_case(name)
