@@ -257,6 +257,12 @@ SYMBOLS = {
     "dsir_nn_match_topk_splits": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
     "dsir_feature_correspondences_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                                   C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # scene registration: edge information matrices (csrc/info_matrix.hip) and the pose graph (csrc/pose_graph.hip)
+    "dsir_information_matrix": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p,
+                                          C.c_int, C.c_void_p, C.c_void_p]),
+    "dsir_pose_graph_scratch_bytes": (C.c_size_t, [C.c_int, c_i32_p, c_i32_p, c_i32_p]),
+    "dsir_pose_graph_optimize": (C.c_int, [C.c_void_p, C.c_int, c_i32_p, c_i32_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, c_i32_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

@@ -648,6 +648,50 @@ class Engine:
         self.sync()
         return idx, d2, stats
 
+    def information_matrix(self, points_src, points_ref, T, max_corr_dist: float, search: str = "brute"):
+        """open3d get_information_matrix_from_point_clouds counterpart for P pairs (include/dsir.h, dsir_information_matrix).
+        Arguments as for icp_correspondences, whose correspondence set this sums over -> (info [P,6,6] f64 in the order
+        [rotation; translation], symmetric; count [P] i32: the correspondences).  Same bytes for every ``search``."""
+        grid = self._icp_search(search, points_ref.shape[1])
+        points_src, points_ref = _chk(points_src, torch.float32, "points_src"), _chk(points_ref, torch.float32, "points_ref")
+        T = _chk(T, torch.float32, "T")
+        P, J, stride = points_src.shape
+        K = points_ref.shape[1]
+        assert points_ref.shape[0] == P and points_ref.shape[2] == stride and tuple(T.shape) == (P, 3, 4)
+        info, count = self._empty((P, 6, 6), torch.float64), self._empty((P,), torch.int32)
+        self._pre()
+        self._call(self.lib.dsir_information_matrix(self.h, _ptr(points_src), _ptr(points_ref), P, J, K, stride, float(max_corr_dist),
+                                                    _ptr(T), grid, _ptr(info), _ptr(count)))
+        self.sync()
+        return info, count
+
+    def pose_graph_optimize(self, graphs, max_iter: int = 100):
+        """open3d global_optimization counterpart for a list of graphs, one workgroup each (include/dsir.h,
+        dsir_pose_graph_optimize).  graphs: ``pose_graph.PoseGraph`` objects or dicts with their fields (X0 [N,3,4], st [E,2],
+        T [E,3,4], info [E,6,6], uncertain [E], mu, reference_node), numpy on the host; they are checked (ValueError: more than
+        128 nodes, disconnected, no edge, bad reference node - before any launch) and packed CSR-style here.
+        -> list of (X [N,3,4] f64, line [E] f64, stats [4] f64: F at X0, F at X, solves, status) as numpy, one per graph."""
+        from . import pose_graph as PG
+        p = PG.pack_graphs(graphs)
+        G = len(p["mu"])
+        i32p = lambda a: a.ctypes.data_as(_lib.c_i32_p)
+        nbytes = self.lib.dsir_pose_graph_scratch_bytes(G, i32p(p["node_off"]), i32p(p["edge_off"]), i32p(p["reference_node"]))
+        if nbytes == 0:
+            raise EngineError("dsir_pose_graph_scratch_bytes: the batch is refused")
+        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
+        X0, st, T, info, unc, mu = (dev(p[k]) for k in ("X0", "st", "T", "info", "uncertain", "mu"))
+        scratch = self._empty(((nbytes + 7) // 8,), torch.float64)
+        X, line = torch.empty_like(X0), self._empty((max(int(p["edge_off"][-1]), 1),), torch.float64)
+        stats = self._empty((G, 4), torch.float64)
+        self._pre()
+        self._call(self.lib.dsir_pose_graph_optimize(self.h, G, i32p(p["node_off"]), i32p(p["edge_off"]), _ptr(X0), _ptr(st), _ptr(T),
+                                                     _ptr(info), _ptr(unc), _ptr(mu), i32p(p["reference_node"]), int(max_iter),
+                                                     _ptr(scratch), _ptr(X), _ptr(line), _ptr(stats)))
+        self.sync()
+        X, line, stats = X.cpu().numpy(), line.cpu().numpy(), stats.cpu().numpy()
+        no, eo = p["node_off"], p["edge_off"]
+        return [(X[no[g]:no[g + 1]], line[eo[g]:eo[g + 1]], stats[g]) for g in range(G)]
+
     def icp_normals(self, points_ref, viewpoint=(0.0, 0.0, 0.0)):
         """The normals icp_refine(estimator="plane") estimates when it is given none: knn_pyramid on points_ref [P,K,>=3], then
         estimate_normals on the level-0 lists -> [P,K,3].  ValueError for a cloud the pyramid does not accept."""

@@ -501,3 +501,145 @@ def inference_label(pairs: Sequence[Dict[str, np.ndarray]], model, batch: int = 
     mean_iou, iou, mean_acc = metric.result()
     return preds, {"mean_iou": mean_iou, "iou": iou, "mean_acc": mean_acc,
                    "loss": float(np.nanmean(losses)) if losses else float("nan")}, total
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# scene registration: pairwise poses -> edge information matrices -> pose graph (include/dsir.h, dsir_information_matrix and
+# dsir_pose_graph_optimize; the host rules are deepsir_amd/pose_graph.py)
+OVERLAP_MIN = 0.3          # open3d's reconstruction rule: an edge needs info[5,5] / min(n_s, n_t) of at least this
+
+
+def _scene_pairs(fragments, pairs):
+    n = len(fragments)
+    return [(int(s), int(t)) for s, t in pairs] if pairs is not None else [(i, j) for i in range(n) for j in range(i + 1, n)]
+
+
+def _scene_table(fragments, pairs, register, **kw):
+    """The candidate-edge table of a scene from a pairwise registration: rows (s, t, T [3,4], uncertain), t = s + 1 certain."""
+    as_np = lambda f: f.cpu().numpy() if isinstance(f, torch.Tensor) else np.asarray(f)
+    st = _scene_pairs(fragments, pairs)
+    data = [{"points_src": as_np(fragments[s])[None].astype(np.float32), "points_ref": as_np(fragments[t])[None].astype(np.float32)} for s, t in st]
+    pred = register(data, **kw)[0]
+    return [(s, t, np.asarray(pred[k, -1], np.float64), t != s + 1) for k, (s, t) in enumerate(st)]
+
+
+def scene_edges_fpfh(fragments, engine, pairs=None, **kw):
+    """Candidate edges of a scene through ``register_fpfh`` (its keyword arguments pass through): all pairs s < t, or ``pairs``.
+    -> list of (s, t, T [3,4] with p_t = T p_s, uncertain); edges t = s + 1 are certain (odometry), the rest uncertain."""
+    return _scene_table(fragments, pairs, lambda d, **k: register_fpfh(d, engine, **k), **kw)
+
+
+def scene_edges_feat(fragments, model, pairs=None, **kw):
+    """``scene_edges_fpfh`` through ``register_feat`` and a 'feat' model."""
+    return _scene_table(fragments, pairs, lambda d, **k: register_feat(d, model, **k), **kw)
+
+
+def _chain_poses(N, edges, reference_node):
+    """Node poses implied by a spanning tree of the edges from the reference node (certain edges first): X_s = X_t T."""
+    inv = lambda A: np.hstack([A[:, :3].T, (-A[:, :3].T @ A[:, 3])[:, None]])
+    mul = lambda A, B: np.hstack([A[:, :3] @ B[:, :3], (A[:, :3] @ B[:, 3] + A[:, 3])[:, None]])
+    X = {int(reference_node): np.eye(3, 4)}
+    order = sorted(edges, key=lambda e: bool(e[3]))
+    for _ in range(N):
+        for s, t, T, _u in order:
+            if t in X and s not in X:
+                X[s] = mul(X[t], T)
+            elif s in X and t not in X:
+                X[t] = mul(X[s], inv(T))
+    if len(X) != N:
+        raise ValueError("register_scene: the kept edges do not connect the scene (disconnected)")
+    return np.stack([X[i] for i in range(N)])
+
+
+@torch.no_grad()
+def register_scene(fragments, engine, edges, voxel_size: float = 0.05, max_corr_dist: Optional[float] = None, icp_max_iter: int = 30,
+                   estimator: str = "point", search: str = "auto", preference: float = 1.0, overlap_min: float = OVERLAP_MIN,
+                   max_iter: int = 100, reference_node: int = 0, batch: int = 1):
+    """A scene from its pairwise registrations.  fragments: clouds [n_i, >=3] (numpy or tensors, any sizes the engine takes);
+    edges: rows (s, t, T_init [3,4] with p_t = T p_s, uncertain) from any pairwise path (``scene_edges_fpfh``, ...).  Per edge
+    ``icp_refine`` (radius ``max_corr_dist``, default 2 x voxel size) then ``information_matrix``; an edge with
+    info[5,5] / min(n_s, n_t) < ``overlap_min`` is dropped ("overlap"); ``pose_graph_optimize`` on the rest with
+    mu = ``line_process_weight(..., preference)`` from the chained poses; uncertain edges with l < 0.25 are dropped ("line") and the
+    graph is optimised again from the first result.  ``batch``: edges of equal shapes per ICP call (the engine's max_pairs).
+    -> {"X": [N,3,4] f64 node poses (fragment -> scene, reference node the identity), "edges": one dict per input edge
+    {s, t, T (refined), info, count, uncertain, line, dropped: None | "overlap" | "line"}, "stats": [stats of both optimisations]}."""
+    from . import pose_graph as PG
+    r = float(2.0 * voxel_size if max_corr_dist is None else max_corr_dist)
+    dev = engine.device
+    frs = [(f if isinstance(f, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(f, np.float32))).to(dev).float().contiguous() for f in fragments]
+    N = len(frs)
+    rows = [{"s": int(s), "t": int(t), "T": None, "info": None, "count": 0, "uncertain": bool(u), "line": 1.0, "dropped": None} for s, t, _, u in edges]
+    groups: Dict[tuple, list] = {}
+    for k, (s, t, _, _) in enumerate(edges):
+        groups.setdefault((tuple(frs[int(s)].shape), tuple(frs[int(t)].shape)), []).append(k)
+    for ks in groups.values():
+        for b0 in range(0, len(ks), batch):
+            kb = ks[b0:b0 + batch]
+            src = torch.stack([frs[rows[k]["s"]] for k in kb]).contiguous()
+            ref = torch.stack([frs[rows[k]["t"]] for k in kb]).contiguous()
+            T0 = torch.from_numpy(np.stack([np.asarray(edges[k][2], np.float32)[:3] for k in kb])).to(dev).contiguous()
+            T, _ = engine.icp_refine(src, ref, T0, r, max_iter=icp_max_iter, estimator=estimator, search=search)
+            info, count = engine.information_matrix(src, ref, T, r, search=search)
+            T, info, count = T.cpu().numpy().astype(np.float64), info.cpu().numpy(), count.cpu().numpy()
+            for j, k in enumerate(kb):
+                rows[k].update(T=T[j], info=info[j], count=int(count[j]))
+                if info[j, 5, 5] / min(src.shape[1], ref.shape[1]) < overlap_min:
+                    rows[k]["dropped"] = "overlap"
+
+    def graph(keep, X0):
+        return PG.PoseGraph(X0, np.array([(rows[k]["s"], rows[k]["t"]) for k in keep], np.int32).reshape(-1, 2),
+                            np.array([rows[k]["T"] for k in keep]).reshape(-1, 3, 4), np.array([rows[k]["info"] for k in keep]).reshape(-1, 6, 6),
+                            np.array([rows[k]["uncertain"] for k in keep], np.uint8),
+                            PG.line_process_weight([rows[k]["info"] for k in keep], [rows[k]["uncertain"] for k in keep], r, preference),
+                            reference_node)
+
+    keep = [k for k in range(len(rows)) if rows[k]["dropped"] is None]
+    X0 = _chain_poses(N, [(rows[k]["s"], rows[k]["t"], rows[k]["T"], rows[k]["uncertain"]) for k in keep], reference_node)
+    (X, line, st1), = engine.pose_graph_optimize([graph(keep, X0)], max_iter=max_iter)
+    for k, l in zip(keep, line):
+        rows[k]["line"] = float(l)
+        if rows[k]["uncertain"] and l < PG.PRUNE_LINE:
+            rows[k]["dropped"] = "line"
+    keep = [k for k in keep if rows[k]["dropped"] is None]
+    _chain_poses(N, [(rows[k]["s"], rows[k]["t"], rows[k]["T"], rows[k]["uncertain"]) for k in keep], reference_node)   # still connected
+    (X, line, st2), = engine.pose_graph_optimize([graph(keep, X)], max_iter=max_iter)
+    for k, l in zip(keep, line):
+        rows[k]["line"] = float(l)
+    return {"X": X, "edges": rows, "stats": [st1, st2]}
+
+
+def implied_pose(X, s: int, t: int) -> np.ndarray:
+    """The pair pose the node poses imply, p_t = T p_s: T = X_t^-1 X_s [3,4]."""
+    Rt = X[t][:, :3].T
+    return np.hstack([Rt @ X[s][:, :3], (Rt @ (X[s][:, 3] - X[t][:, 3]))[:, None]])
+
+
+def summarize_scene(result, gt: Optional[Dict[tuple, np.ndarray]] = None, dataset_type: str = "3DMatch", gt_info: Optional[Dict[tuple, np.ndarray]] = None):
+    """Counts of a ``register_scene`` result and, with ``gt`` {(s, t): T_gt [3,4]}, the pairwise recall (RTE / RRE thresholds) of the
+    refined pair poses and of the poses the optimised nodes imply; with ``gt_info`` {(s, t): info as read from gt.info} also under
+    ``metrics.info_rmse``."""
+    from .metrics import info_rmse
+    rows = result["edges"]
+    out = {"edges": len(rows), "dropped_overlap": sum(r["dropped"] == "overlap" for r in rows),
+           "dropped_line": sum(r["dropped"] == "line" for r in rows), "status": [int(s[3]) for s in result["stats"]]}
+    if gt:
+        rte_t, rre_t = THRESHOLDS[dataset_type]
+        inv = lambda A: np.hstack([A[:3, :3].T, (-A[:3, :3].T @ A[:3, 3])[:, None]])
+        raw, opt, raw_i, opt_i = [], [], [], []
+        for r in rows:                                        # a ground-truth record may be keyed (s, t) or, as gt.log is, (t, s)
+            key, flip = ((r["s"], r["t"]), False) if (r["s"], r["t"]) in gt else ((r["t"], r["s"]), True)
+            if key not in gt:
+                continue
+            T_raw, T_opt = r["T"], implied_pose(result["X"], r["s"], r["t"])
+            if flip:
+                T_raw, T_opt = inv(T_raw), inv(T_opt)
+            T_gt = np.asarray(gt[key], np.float64)[:3]
+            raw.append(rte_rre(T_raw, T_gt, rte_t, rre_t)[0])
+            opt.append(rte_rre(T_opt, T_gt, rte_t, rre_t)[0])
+            if gt_info and key in gt_info:
+                raw_i.append(info_rmse(T_raw, T_gt, gt_info[key])[1])
+                opt_i.append(info_rmse(T_opt, T_gt, gt_info[key])[1])
+        out.update(pairs=len(raw), recall_raw=float(np.mean(raw)) if raw else 0.0, recall_optimized=float(np.mean(opt)) if opt else 0.0)
+        if raw_i:
+            out.update(pairs_info=len(raw_i), recall_raw_info=float(np.mean(raw_i)), recall_optimized_info=float(np.mean(opt_i)))
+    return out

@@ -85,3 +85,58 @@ def make_batch(n: int, seeds, feat_len: int = 3, shape: str = "3dmatch",
     """Stack several pairs along the batch dimension."""
     pairs = [make_pair(n, s, feat_len, shape, partial_overlap) for s in seeds]
     return {k: np.concatenate([p[k] for p in pairs], 0) for k in pairs[0]}
+
+
+# ---------------------------------------------------------------------------------------------------------------------- pose graphs
+POSE_GRAPH_RADIUS = 0.05          # max_corr_dist the synthetic information matrices and mu of make_pose_graph stand for
+
+
+def _pg():
+    from . import pose_graph
+    return pose_graph
+
+
+def _rot(axis, angle):
+    ax = np.asarray(axis, np.float64) / np.linalg.norm(axis)
+    K = np.array([[0, -ax[2], ax[1]], [ax[2], 0, -ax[0]], [-ax[1], ax[0], 0]])
+    return np.eye(3) + np.sin(angle) * K + (1 - np.cos(angle)) * K @ K
+
+
+def se3_random(rng, angle, shift):
+    return np.hstack([_rot(rng.standard_normal(3), angle * rng.uniform(0.5, 1.0)), rng.uniform(-shift, shift, (3, 1))])
+
+
+def se3_mul(A, B):
+    return np.hstack([A[:, :3] @ B[:, :3], (A[:, :3] @ B[:, 3] + A[:, 3])[:, None]])
+
+
+def se3_inv(A):
+    return np.hstack([A[:, :3].T, (-A[:, :3].T @ A[:, 3])[:, None]])
+
+
+def make_pose_graph(N, seed, loops=4, noise=(0.0, 0.0), start=(0.1, 0.1), false_edges=0, ref=0, points=200):
+    """A ring of N random poses: certain edges (i, i+1), `loops` uncertain true loop closures, `false_edges` uncertain edges with an
+    unrelated transform (listed last).  noise = (radians, metres) on every true edge's T; start = the same on X0 around the truth.
+    Information matrices: information_matrix_host of `points` random points of a 3 m room.  -> (PoseGraph, X_true, is_false [E])"""
+    rng = np.random.default_rng(seed)
+    Xt = np.stack([se3_random(rng, 2.0, 2.0) for _ in range(N)])
+    st = [(i, i + 1) for i in range(N - 1)]
+    for _ in range(loops if N > 2 else 0):
+        s, t = sorted(rng.choice(N, 2, replace=False))
+        st.append((int(s), int(t)))
+    nt = len(st)
+    for _ in range(false_edges):
+        s, t = sorted(rng.choice(N, 2, replace=False))
+        st.append((int(s), int(t)))
+    T, info = [], []
+    for k, (s, t) in enumerate(st):
+        Tk = se3_mul(se3_inv(Xt[t]), Xt[s])                                      # X_s = X_t T
+        Tk = se3_mul(se3_random(rng, noise[0], noise[1]), Tk) if k < nt else se3_random(rng, 3.0, 1.5)
+        T.append(Tk)
+        q = rng.uniform(0, 3, (points, 3)).astype(np.float32)
+        info.append(_pg().information_matrix_host(q, np.arange(points)))
+    unc = np.array([0] * (N - 1) + [1] * (len(st) - (N - 1)), np.uint8)
+    X0 = np.stack([Xt[i] if i == ref else se3_mul(se3_random(rng, *start), Xt[i]) for i in range(N)])
+    g = _pg().PoseGraph(X0, np.array(st, np.int32).reshape(-1, 2), np.array(T).reshape(-1, 3, 4), np.array(info).reshape(-1, 6, 6), unc,
+                     mu=_pg().line_process_weight(info, unc, POSE_GRAPH_RADIUS), reference_node=ref)
+    return g, Xt, np.arange(len(st)) >= nt

@@ -633,6 +633,52 @@ int dsir_nn_match_topk_splits(dsir_ctx* ctx, int pairs, int J, int K, int k);
 int dsir_feature_correspondences_ex(dsir_ctx* ctx, const float* desc_src, const float* desc_ref, int pairs, int J, int K,
                                     int mutual, int k, float ratio, int32_t* corr, int32_t* counts, float* corr_dist);
 
+/* ---- scene registration: edge information matrices and the pose graph ------- */
+
+/* open3d's get_information_matrix_from_point_clouds(src, tgt, max_correspondence_distance, T) for P pairs at once (open3d is not
+ * pinned: the rule is this engine's own, stated in the header of csrc/info_matrix.hip and restated in deepsir_amd/pose_graph.py).
+ * Arguments as for dsir_icp_correspondences; the correspondence set is exactly the one that entry returns for the same arguments.
+ * For every source row with idx >= 0, q = (x, y, z) the fp32 reference point it matched:
+ *   G = [0 z -y 1 0 0; -z 0 x 0 1 0; y -x 0 0 0 1],  info = sum G^T G  in fp64 (ten sums; products of fp32 values are exact).
+ * info_out [P][6][6] float64 row-major, open3d's order [rotation; translation], symmetric, both triangles written;
+ * count_out [P] int32: the correspondences.  A pair without a correspondence gets the zero matrix and count 0; non-finite rows
+ * are never correspondences.  Same bytes on every run (fixed partition of the sums, no floating-point atomics), for both values
+ * of `search`, and for a pair whatever else is in the batch.  Scratch comes from the context workspace. */
+int dsir_information_matrix(dsir_ctx* ctx, const float* points_src, const float* points_ref, int pairs, int J, int K, int stride,
+                            float max_corr_dist, const float* T, int search, double* info_out, int32_t* count_out);
+
+#define DSIR_POSE_GRAPH_MAX_NODES 128
+#define DSIR_POSE_GRAPH_MAX_ITER 100        /* the default of the Python layer */
+/* status bits of dsir_pose_graph_optimize's stats[g][3]; 0: stopped on the relative decrease of F or on the relative step */
+#define DSIR_PG_MAX_ITER 1
+#define DSIR_PG_LAMBDA 2
+#define DSIR_PG_PIVOT 4
+#define DSIR_PG_NON_FINITE 8
+#define DSIR_PG_EDGE_INDEX 16
+
+/* open3d's global_optimization (pose graph with a line process over uncertain edges; Choi et al., robust reconstruction) for G
+ * graphs at once, one workgroup per graph (open3d is not pinned: the rule - residual, objective, Jacobians, damping, stops - is
+ * this engine's own, stated in the header of csrc/pose_graph.hip and restated in deepsir_amd/pose_graph.py, optimize_host).
+ * Node pose X_i maps fragment i's frame to the scene frame; edge (s, t, T, Lambda, uncertain) says p_t = T p_s, so a consistent
+ * graph has X_s = X_t T; e = [log rot; trans] of T^-1 X_t^-1 X_s;  F = sum l e^T Lambda e + sum_uncertain mu (sqrt(l) - 1)^2 with
+ * l = (mu / (mu + e^T Lambda e))^2 on uncertain edges, 1 on the others.  The default mu is the Python layer's
+ * pose_graph.line_process_weight: preference x max_corr_dist^2 x mean over the uncertain edges of Lambda[3][3].
+ * node_off, edge_off, reference_node: HOST arrays [G+1], [G+1], [G] (CSR over the batch; reference_node is graph-local and held
+ * fixed: its pose is returned as its input bits).  Device arrays: X0 [sum N][3][4] f64, edge_st [sum E][2] int32 (graph-local s, t),
+ * edge_T [sum E][3][4] f64, edge_info [sum E][6][6] f64, edge_uncertain [sum E] bytes, mu [G] f64; outputs X [sum N][3][4] f64,
+ * line [sum E] f64 (the final l), stats [G][4] f64 {F at X0, F at X, solves made, status}.  scratch: device memory of
+ * dsir_pose_graph_scratch_bytes(...) bytes (0 for a refused batch).
+ * Refused on the host, before any launch: a graph of more than DSIR_POSE_GRAPH_MAX_NODES nodes or of none, E = 0 with N > 1, a
+ * reference_node outside [0, N), offsets that do not ascend from 0.  (A graph whose edges do not connect it is refused by the Python
+ * layer, which sees the edge list.)  N = 1 returns its input.  On the device, a pivot that is not positive, an entry that is not
+ * finite (or mu <= 0) or an edge index outside the graph ends THAT graph with the bit set, X = X0 and line = 1; the other graphs
+ * of the call are unaffected bit for bit.  Same bytes on every run: edges are assembled in order, nothing is scatter-added. */
+size_t dsir_pose_graph_scratch_bytes(int graphs, const int32_t* node_off, const int32_t* edge_off, const int32_t* reference_node);
+int dsir_pose_graph_optimize(dsir_ctx* ctx, int graphs, const int32_t* node_off, const int32_t* edge_off, const double* X0,
+                             const int32_t* edge_st, const double* edge_T, const double* edge_info, const uint8_t* edge_uncertain,
+                             const double* mu, const int32_t* reference_node, int max_iter, void* scratch, double* X, double* line,
+                             double* stats);
+
 #ifdef __cplusplus
 }
 #endif
