@@ -1,5 +1,5 @@
-// One piece of scratch, many parts: the arithmetic every layout struct shares (op_layouts.h, icp_layout.h, icp_grid.h, cell_index.h and
-// the layouts that live beside their kernels).  Plain C++ that compiles for the host too (tools/scratch_layout_check.cpp).
+// One piece of scratch, many parts: the arithmetic every layout struct shares (op_layouts.h, train_layouts.h, icp_layout.h, icp_grid.h, cell_index.h
+// and the layouts that live beside their kernels).  Plain C++ that compiles for the host too (tools/scratch_layout_check.cpp).
 // A layout is built from an operator's shape alone, holds its parts' offsets and `bytes`, and is read by the size function and the
 // launcher alike: the two cannot disagree.
 #pragma once

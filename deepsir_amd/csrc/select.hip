@@ -130,7 +130,7 @@ inline size_t plan_sort_tmp_bytes(int64_t total) {
 }
 }  // namespace
 
-// The inverse of a gather index (train_ops.hip: the backward of gather_neighbour / nearest_interpolation / random_sample is a sum
+// The inverse of a gather index (train_gather.hip: the backward of gather_neighbour / nearest_interpolation / random_sample is a sum
 // over the SOURCES of every destination row): order = the sources grouped by destination, ascending source inside a group (one
 // stable radix sort of (destination, source) pairs - a library sort, not the hot path), offsets = the groups' bounds.  With it the
 // backward operators sum in a fixed order instead of racing float atomics.

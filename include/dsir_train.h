@@ -38,7 +38,7 @@ int dsir_t_gemm_dw(void* stream, const float* dY, int ldy, const float* X, int l
 /* nn.GroupNorm(groups, C) (+ LeakyReLU 0.2 when act) over one cloud's [M][C] block (RandLANet.py:90-107), also
  * nn.BatchNorm1d in training mode (clouds = 1, M = all rows, groups = C; RandLANet.py:44): biased variance, eps 1e-5.
  * stats [clouds][groups][2] = {mean, rstd} are kept for the backward.  scratch: dsir_t_gn_scratch(clouds, M, C) bytes
- * (partial sums of up to 64 row chunks per cloud, reduced in chunk order). */
+ * for either call (partial sums per row chunk, reduced in chunk order: csrc/train_layouts.h). */
 size_t dsir_t_gn_scratch(int clouds, int M, int C);
 int dsir_t_gn_fwd(void* stream, const float* Y, int clouds, int M, int C, int groups, const float* gamma, const float* beta,
                   int act, float* out, float* stats, void* scratch);

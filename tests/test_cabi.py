@@ -132,7 +132,7 @@ def test_groupnorm_statistics_meet_in_exact_atomics_only():
     assert "tomicAdd" not in util.replace(helper, "")                          # no other adding atomic among the shared helpers
     # the training path: the backward of the gathers sums through the index's inverse in a fixed order, the loss
     # terms are added in pair order - no adding atomic at all in these files
-    for f in ("train_ops.hip", "align_loss.hip"):
+    for f in ("train_gemm.hip", "train_norm.hip", "train_gather.hip", "train_loss.hip", "train_elem.hip", "align_loss.hip"):
         assert "tomicAdd" not in _strip_comments(open(os.path.join(csrc, f)).read()), f
 
 
@@ -167,10 +167,11 @@ def test_groupnorm_exactness_bound_limits_max_points():
     assert "b.vgrid = lse_uv_gn_contributions(a.n, a.KH);" in open(os.path.join(csrc, "lse_uv.hip")).read()
 
 
-@pytest.mark.parametrize("name", ["search_plan_check", "ppf_plan_check"])
+@pytest.mark.parametrize("name", ["search_plan_check", "ppf_plan_check", "train_layout_check"])
 def test_host_only_plan_checks(name, tmp_path):
-    """csrc/search_plan.h (which arg-min path a registration takes, the operand sizes) and csrc/ppf_plan.h hold no device code: their
-    stand-alone checks (tools/*_plan_check.cpp; the sanitizer command is in each file's header) build as plain host C++ and pass."""
+    """csrc/search_plan.h (which arg-min path a registration takes, the operand sizes), csrc/ppf_plan.h and csrc/train_layouts.h (the
+    training operators' plans and scratch layouts) hold no device code: their stand-alone checks (tools/*_plan_check.cpp,
+    tools/train_layout_check.cpp; the sanitizer command is in each file's header) build as plain host C++ and pass."""
     import subprocess
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     exe = str(tmp_path / name)
@@ -178,4 +179,4 @@ def test_host_only_plan_checks(name, tmp_path):
                         os.path.join(ROOT, "tools", name + ".cpp"), "-o", exe], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
     r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 0 and "_plan: " in r.stdout, r.stdout + r.stderr
+    assert r.returncode == 0 and ("_layout: " if name.endswith("_layout_check") else "_plan: ") in r.stdout, r.stdout + r.stderr

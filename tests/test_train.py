@@ -883,8 +883,9 @@ def test_optimizer_state_round_trips_with_torch_adam():
 # --------------------------------------------------------------------------- dW scratch sizing
 def test_dw_scratch_covers_both_plans_host_arithmetic():
     """dsir_t_gemm_dw plans its row split with or without the bias column; the sizing call must cover whichever needs more
-    partial matrices (N = K = 128 at 319 488 rows, db = NULL, needs 33.5 MB - the round-2 sizing returned 22.4 MB).  Host
-    arithmetic only: callable without a GPU."""
+    partial matrices (N = K = 128 at 319 488 rows, db = NULL, needs 33.5 MB - the round-2 sizing returned 22.4 MB).  `plan` restates
+    csrc/train_layouts.h::dw_plan (128 rows per split; tools/train_layout_check.cpp checks the header itself).  Host arithmetic only:
+    callable without a GPU."""
     from deepsir_amd import _lib
     lib = _lib.load()
     TB, TK = 64, 16
@@ -892,7 +893,7 @@ def test_dw_scratch_covers_both_plans_host_arithmetic():
     def plan(rows, N, K, bias):
         Kp = K + (1 if bias else 0)
         tiles = ((N + TB - 1) // TB) * ((Kp + TB - 1) // TB)
-        sp = min((rows + 511) // 512, 1 if tiles >= 2048 else 2048 // tiles, 1024)
+        sp = min((rows + 127) // 128, 1 if tiles >= 2048 else 2048 // tiles, 1024)
         sp = max(sp, 1)
         rps = (((rows + sp - 1) // sp) + TK - 1) // TK * TK
         return max((rows + rps - 1) // rps, 1) * N * Kp * 4
@@ -928,3 +929,142 @@ def test_dw_without_bias_stays_inside_its_scratch():
     ref = dy.double().t() @ x.double()
     err = float((dw.double() - ref).abs().max() / ref.abs().max())
     assert err < 1e-5, err
+
+
+# --------------------------------------------------------------------------- scratch layouts (csrc/train_layouts.h) on the device
+# Each operator through the raw ABI with a scratch of exactly dsir_t_*_scratch bytes and a guard region behind it: return code 0, the guard
+# untouched, the result equal to torch in fp64 within the tolerance the operator has above.  Shapes: the smallest at which a layout can
+# go wrong (ragged second GroupNorm chunk, a bias column that opens a tile column of its own, an odd float count ahead of the
+# CircleRow array, one row past a 256-row block).
+_GUARD, _SENTINEL = 1 << 16, 12345.0
+
+
+def _guarded_scratch(nbytes):
+    assert nbytes > 0 and nbytes % 4 == 0
+    return torch.full((nbytes // 4 + _GUARD,), _SENTINEL, device=_dev())
+
+
+def _guard_untouched(buf, nbytes):
+    return bool((buf[nbytes // 4:] == _SENTINEL).all())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("C_,groups", [(12, 3), (6, 2)])
+def test_gn_stays_inside_its_scratch(C_, groups):
+    import torch.nn.functional as F
+    lib = __import__("deepsir_amd._lib", fromlist=["load"]).load()
+    clouds, M, act = 2, 129, 1
+    g = torch.Generator().manual_seed(11)
+    y = torch.randn(clouds, C_, M, generator=g, dtype=torch.float64).float().double().requires_grad_()
+    ga = (torch.rand(C_, generator=g) + 0.5).double().requires_grad_()
+    be = torch.randn(C_, generator=g).double().requires_grad_()
+    dout = torch.randn(clouds, C_, M, generator=g).double()
+    ref = F.leaky_relu(F.group_norm(y, groups, ga, be, 1e-5), 0.2)
+    ref.backward(dout)
+    pm = lambda t: t.detach().permute(0, 2, 1).reshape(clouds * M, C_).contiguous()
+    yd, gad, bed, dod = pm(y).float().to(_dev()), ga.detach().float().to(_dev()), be.detach().float().to(_dev()), pm(dout).float().to(_dev())
+    nbytes = int(lib.dsir_t_gn_scratch(clouds, M, C_))
+    st = torch.cuda.current_stream(_dev()).cuda_stream
+    out, stats = torch.empty_like(yd), torch.empty(clouds, groups, 2, device=_dev())
+    buf = _guarded_scratch(nbytes)
+    rc = lib.dsir_t_gn_fwd(st, yd.data_ptr(), clouds, M, C_, groups, gad.data_ptr(), bed.data_ptr(), act, out.data_ptr(), stats.data_ptr(),
+                           buf.data_ptr())
+    torch.cuda.synchronize()
+    assert rc == 0 and _guard_untouched(buf, nbytes), "dsir_t_gn_fwd wrote past dsir_t_gn_scratch bytes"
+    assert torch.allclose(out.cpu().double(), pm(ref), rtol=1e-4, atol=1e-4)
+    dy, dga, dbe = torch.empty_like(yd), torch.zeros(C_, device=_dev()), torch.zeros(C_, device=_dev())
+    buf = _guarded_scratch(nbytes)
+    rc = lib.dsir_t_gn_bwd(st, dod.data_ptr(), yd.data_ptr(), stats.data_ptr(), clouds, M, C_, groups, gad.data_ptr(), bed.data_ptr(), act,
+                           dy.data_ptr(), dga.data_ptr(), dbe.data_ptr(), buf.data_ptr())
+    torch.cuda.synchronize()
+    assert rc == 0 and _guard_untouched(buf, nbytes), "dsir_t_gn_bwd wrote past dsir_t_gn_scratch bytes"
+    assert torch.allclose(dy.cpu().double(), pm(y.grad), rtol=1e-3, atol=1e-4)
+    assert torch.allclose(dga.cpu().double(), ga.grad, rtol=1e-4, atol=1e-3) and torch.allclose(dbe.cpu().double(), be.grad, rtol=1e-4, atol=1e-3)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("bias", [True, False])
+def test_dw_small_stays_inside_its_scratch(bias):
+    """rows = 129 (two splits, the second of one row), N = 65 (two tile rows), K = 64: with db the bias column is tile column 2."""
+    lib = __import__("deepsir_amd._lib", fromlist=["load"]).load()
+    rows, N, K = 129, 65, 64
+    g = torch.Generator().manual_seed(12)
+    dy, x = torch.randn(rows, N, generator=g).to(_dev()), torch.randn(rows, K, generator=g).to(_dev())
+    nbytes = int(lib.dsir_t_gemm_dw_scratch(rows, N, K))
+    buf = _guarded_scratch(nbytes)
+    dw, db = torch.zeros(N, K, device=_dev()), torch.zeros(N, device=_dev())
+    st = torch.cuda.current_stream(_dev()).cuda_stream
+    rc = lib.dsir_t_gemm_dw(st, dy.data_ptr(), N, x.data_ptr(), K, rows, N, K, dw.data_ptr(), db.data_ptr() if bias else None, buf.data_ptr())
+    torch.cuda.synchronize()
+    assert rc == 0 and _guard_untouched(buf, nbytes), "dsir_t_gemm_dw wrote past dsir_t_gemm_dw_scratch bytes"
+    ref = dy.double().t() @ x.double()
+    assert float((dw.double() - ref).abs().max() / ref.abs().max()) < 1e-5
+    if bias:
+        rb = dy.double().sum(0)
+        assert float((db.double() - rb).abs().max() / rb.abs().max()) < 1e-5
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("P,M", [(1, 3), (2, 5)])
+def test_det_des_loss_stays_inside_its_scratch(P, M):
+    """(1, 3): 99 floats lie ahead of the CircleRow array.  Coordinates and translations are multiples of 1 / 256 and the rotation is the
+    identity, so distances, the radius test and the exact coincidences are the same in fp32 and fp64."""
+    lib = __import__("deepsir_amd._lib", fromlist=["load"]).load()
+    C_, thres, det_w = 32, 0.2, 0.7
+    g = torch.Generator().manual_seed(13)
+    F64 = torch.float64
+    fr = torch.nn.functional.normalize(torch.randn(P, C_, M, generator=g), dim=1).to(F64).requires_grad_()
+    fs = torch.nn.functional.normalize(torch.randn(P, C_, M, generator=g), dim=1).to(F64).requires_grad_()
+    ps = torch.randint(0, 512, (P, 3, M), generator=g).to(F64) / 256
+    T = torch.eye(3, 4, dtype=F64)[None].repeat(P, 1, 1)
+    T[:, :, 3] = torch.randint(-32, 33, (P, 3), generator=g).to(F64) / 256
+    pr = (ps + T[:, :, 3:]).clone()
+    pr[:, :, M // 2:] += torch.randint(-64, 65, (P, 3, M - M // 2), generator=g).to(F64) / 256     # the first M // 2 coincide exactly after T_gt
+    sc = (torch.rand(P, M, generator=g) + 0.1).to(F64)
+    loss, acc = otrain.det_des_loss(fs, fr, ps, pr, sc, T, thres, det_w)
+    loss.backward()
+    pm = lambda x: x.detach().permute(0, 2, 1).contiguous().float().to(_dev())
+    frd, fsd, prd, psd, scd, Td = pm(fr), pm(fs), pm(pr), pm(ps), sc.float().to(_dev()), T.float().contiguous().to(_dev())
+    out = torch.empty(4, dtype=F64, device=_dev())
+    d_ref, d_src = torch.empty_like(frd), torch.empty_like(fsd)
+    nbytes = int(lib.dsir_t_det_des_loss_scratch(P, M))
+    buf = _guarded_scratch(nbytes)
+    st = torch.cuda.current_stream(_dev()).cuda_stream
+    rc = lib.dsir_t_det_des_loss(st, frd.data_ptr(), fsd.data_ptr(), prd.data_ptr(), psd.data_ptr(), scd.data_ptr(), Td.data_ptr(), P, M, C_,
+                                 thres, det_w, out.data_ptr(), d_ref.data_ptr(), d_src.data_ptr(), buf.data_ptr())
+    torch.cuda.synchronize()
+    assert rc == 0 and _guard_untouched(buf, nbytes), "dsir_t_det_des_loss wrote past dsir_t_det_des_loss_scratch bytes"
+    out = out.cpu().numpy()
+    assert abs(out[0] - float(loss.detach())) < 1e-4 * max(1.0, abs(float(loss.detach()))) and abs(out[3] - float(acc)) < 1.0
+    assert np.abs(d_ref.cpu().numpy() - fr.grad.permute(0, 2, 1).numpy()).max() <= 5e-3 * float(fr.grad.abs().max())
+    assert np.abs(d_src.cpu().numpy() - fs.grad.permute(0, 2, 1).numpy()).max() <= 5e-3 * float(fs.grad.abs().max())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("rows", [1, 256, 257])
+def test_weighted_ce_stays_inside_its_scratch(rows):
+    """257: one row in a second block.  The last row of the two larger cases carries the ignored label 0."""
+    import torch.nn.functional as F
+    lib = __import__("deepsir_amd._lib", fromlist=["load"]).load()
+    C_ = 3
+    g = torch.Generator().manual_seed(14)
+    lg = torch.randn(rows, C_, generator=g).double().requires_grad_()
+    lb = torch.randint(1, C_ + 1, (rows,), generator=g)
+    if rows > 1:
+        lb[-1] = 0
+    cw = (torch.rand(C_, generator=g) + 0.5).double()
+    keep = lb != 0
+    ref = F.cross_entropy(lg[keep], lb[keep] - 1, weight=cw)
+    ref.backward()
+    lgd, lbd, cwd = lg.detach().float().to(_dev()), lb.int().to(_dev()), cw.float().to(_dev())
+    d, out = torch.empty_like(lgd), torch.empty(4, dtype=torch.float64, device=_dev())
+    nbytes = int(lib.dsir_t_weighted_ce_scratch(rows))
+    buf = _guarded_scratch(nbytes)
+    st = torch.cuda.current_stream(_dev()).cuda_stream
+    rc = lib.dsir_t_weighted_ce(st, lgd.data_ptr(), lbd.data_ptr(), cwd.data_ptr(), rows, C_, 1.0, d.data_ptr(), out.data_ptr(), buf.data_ptr())
+    torch.cuda.synchronize()
+    assert rc == 0 and _guard_untouched(buf, nbytes), "dsir_t_weighted_ce wrote past dsir_t_weighted_ce_scratch bytes"
+    out = out.cpu().numpy()
+    assert abs(out[0] - float(ref)) < 1e-5 and out[3] == int(keep.sum())
+    assert out[2] == int((lg.detach()[keep].argmax(1) == lb[keep] - 1).sum())
+    assert torch.allclose(d.cpu().double(), lg.grad, rtol=1e-4, atol=1e-8)
