@@ -21,13 +21,13 @@
 #include "device_utils.h"
 #include "augment_params.h"
 #include "scratch.h"
+#include "train_ops.h"
 
 namespace dsir {
 namespace {
 
 constexpr int CB = 16;                 // centroid: blocks per cloud (stage 1)
 constexpr int CT = 256;                // centroid: threads per block
-inline int done() { return (int)hipGetLastError(); }
 
 // ---- centroids: stage 1, block (b, cloud) sums rows [b chunk, (b + 1) chunk) of the cloud's first n rows
 __global__ __launch_bounds__(CT) void centroid_partial_kernel(const float* __restrict__ pts, const int32_t* __restrict__ counts, int cap,

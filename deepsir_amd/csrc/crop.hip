@@ -34,6 +34,7 @@
 #include "dsir_train.h"
 #include "device_utils.h"
 #include "scratch.h"
+#include "train_ops.h"
 
 namespace dsir {
 namespace {
@@ -52,7 +53,6 @@ struct CropState {
 };
 
 inline int slices_of(int cap) { return (cap + ROWS - 1) / ROWS; }
-inline int done() { return (int)hipGetLastError(); }
 
 struct Layout {
   size_t keys, hist, state, q, block_counts, total;

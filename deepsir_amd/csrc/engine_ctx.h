@@ -1,6 +1,7 @@
-// What the host-side translation units of libdsir.so share: the context, its workspace, the weight tables and the functions that
-// cross files.  engine.hip: the C ABI and the registration; weights.hip: expected keys and uploads; schedule.hip: the layer
-// schedule of RandLA.forward / aggregation and the KNN pyramid; search.hip: the descriptor search.
+// What the host-side translation units of libdsir.so share: the context, its workspace, the scope of one C-ABI call (Call), the weight
+// tables and the functions that cross files.  engine.hip: life cycle, tuning gate, switches; register.hip: the registration and
+// forward_pair; entries_stage.hip / entries_pose.hip: the stage and pose entries; weights.hip: expected keys and uploads;
+// schedule.hip: the layer schedule of RandLA.forward / aggregation and the KNN pyramid; search.hip: the descriptor search.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -62,6 +63,16 @@ struct Pyramid {     // KNN pyramid of a cloud batch, levels concatenated (data_
   const int32_t* interp = nullptr;// [clouds][S]
 };
 
+// What is meaningful within ONE C-ABI call only: opening a call (Call, below) assigns CallState{} and rewinds the arena with it
+struct CallState {
+  const char* sched_error = nullptr;   // a launcher refused a layer (outside its envelope): reported by Call::finish / overflow_fail
+  size_t stats_top = 0;                // GroupNorm statistics slots handed out to the running pass
+  size_t stats_base = 0;               // dsir_register: the passes of one call take consecutive regions of an arena zeroed ONCE
+  bool stats_prezeroed = false;
+  int walk_used = 0;                   // walker programs of this call
+  bool walk_begun = false;             // this call took a pinned staging set (Call::begin_walker): its event is owed
+};
+
 // a tensor with a lazily applied GroupNorm (+activation)
 struct Act {
   float* p = nullptr;
@@ -84,7 +95,7 @@ struct dsir_ctx {
   hipStream_t stream = nullptr;        // where every launch of this context goes: own_stream, or a caller's (dsir_set_stream)
   hipStream_t own_stream = nullptr;
   std::string err;
-  const char* sched_error = nullptr;     // a launcher refused a layer (outside its envelope): reported by the schedule's caller
+  dsir::CallState call;                // reset, together with ws.top / ws.overflow, by every call's opening
   std::vector<dsir::HostParam> params;
   std::unordered_map<std::string, int> index;
   float* dweights = nullptr;
@@ -95,9 +106,7 @@ struct dsir_ctx {
   dsir::NetW net;
   dsir::Arena ws;
   double* stats = nullptr;   // GroupNorm statistics slots
-  size_t stats_cap = 0, stats_top = 0;
-  size_t stats_base = 0;          // dsir_register: the passes of one call take consecutive regions of an arena zeroed ONCE
-  bool stats_prezeroed = false;
+  size_t stats_cap = 0;
   // nn_match timing
   bool time_match = false;
   // hipGraph replay of dsir_register (launch-bound small batches)
@@ -111,7 +120,6 @@ struct dsir_ctx {
   static constexpr int kWalkClouds = 16;       // the walker serves launches of up to that many clouds
   int walk_mode = 0;                           // 1: the deep levels of a pass as one launch (dsir_enable_walk / DSIR_WALK=1); OFF by default -
                                                // measured slower than the launches it replaces (walk.hip, "What it measured")
-  int walk_used = 0;                           // programs of the current call
   dsir::WalkProgram* walk_dev = nullptr;             // eager calls: device programs, filled by in-stream copies from ...
   dsir::WalkProgram* walk_host[2] = {nullptr, nullptr};   // ... pinned staging, two sets taken in turn by consecutive calls
   hipEvent_t walk_ev[2] = {nullptr, nullptr};  // recorded after a call's last copy from the set
@@ -164,27 +172,48 @@ int fail(dsir_ctx* c, const char* fmt, ...);     // c == nullptr: the creation e
   } while (0)
 
 // ws.overflow is set: report the launcher's refusal that stopped the schedule (Sched::refuse), else the arena's exhaustion
-inline int overflow_fail(dsir_ctx* c, const char* exhausted) {
-  const char* why = c->sched_error;
-  c->sched_error = nullptr;
-  return fail(c, "%s", why ? why : exhausted);
-}
+inline int overflow_fail(dsir_ctx* c, const char* exhausted) { return fail(c, "%s", c->call.sched_error ? c->call.sched_error : exhausted); }
 
 static_assert(kMaxLevels == DSIR_MAX_LEVELS, "kernels.h and dsir.h disagree on the level count");
 
-inline int check_ready(dsir_ctx* c) {
-  if (!c) return 1;
-  if (!c->finalized) return fail(c, "weights not finalized (call dsir_load_weight for every key, then dsir_finalize_weights)");
-  c->ws.top = 0; c->ws.overflow = false; c->sched_error = nullptr;
+// the workspace is sized from max_pairs and max_points: inside them no allocation of a call can overflow
+inline int check_batch(dsir_ctx* c, const char* name, int clouds, int n) {
+  if (clouds > 2 * c->cfg.max_pairs || n > c->cfg.max_points) return fail(c, "%s: batch exceeds max_pairs/max_points", name);
   return 0;
 }
 
-inline int post(dsir_ctx* c) {
-  if (c->ws.overflow) return overflow_fail(c, "workspace exhausted (raise max_points / max_pairs in dsir_cfg)");
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(c, "HIP launch error: %s", hipGetErrorString(e));
-  return 0;
-}
+// The scope of one C-ABI call on a context.  Every entry that enqueues work opens one first - null context, weights (kWeights),
+// hipSetDevice, then the arena rewound and the call state reset - and leaves through finish().  An error return in between leaves
+// through the destructor: it still covers the walker's staging copies with their event and clears the call state; it makes no
+// other HIP call, never synchronises and never touches c->err.
+class Call {
+ public:
+  enum Needs { kContext, kWeights };
+  explicit Call(dsir_ctx* c, Needs needs = kContext) : c_(open(c, needs) ? nullptr : c) {}
+  ~Call() { if (c_) { end_walker(c_); reset(c_); } }
+  bool refused() const { return !c_; }
+  int begin_walker();     // schedule.hip: before the first RandLA pass of a call
+  int finish() {
+    dsir_ctx* c = c_;
+    c_ = nullptr;         // the call state stays readable until the next opening
+    if (hipError_t e = end_walker(c)) return fail(c, "hipEventRecord(c->walk_ev[c->walk_set], c->stream): %s", hipGetErrorString(e));
+    if (c->ws.overflow) return overflow_fail(c, "workspace exhausted (raise max_points / max_pairs in dsir_cfg)");
+    if (hipError_t e = hipGetLastError()) return fail(c, "HIP launch error: %s", hipGetErrorString(e));
+    return 0;
+  }
+
+ private:
+  dsir_ctx* c_;
+  static void reset(dsir_ctx* c) { c->ws.top = 0; c->ws.overflow = false; c->call = CallState{}; }
+  static int open(dsir_ctx* c, Needs needs) {
+    if (!c) return 1;
+    if (needs == kWeights && !c->finalized) return fail(c, "weights not finalized (call dsir_load_weight for every key, then dsir_finalize_weights)");
+    HIP_OK(c, hipSetDevice(c->device));
+    reset(c);
+    return 0;
+  }
+  static hipError_t end_walker(dsir_ctx* c);     // schedule.hip
+};
 
 // ------------------------------------------------------------------ GroupNorm statistics regions
 // Every RandLA pass takes one region of the statistics arena; the passes of a registration take consecutive regions of an arena zeroed
@@ -231,8 +260,6 @@ struct AggExtras { float* sq = nullptr; void* hi = nullptr; void* lo = nullptr; 
 
 void fill_pyramid_layout(const dsir_cfg& cfg, int clouds, int n, Pyramid& p);
 int gn_max_contributions(const dsir_cfg& g, int n, int flags = 0);
-int walk_begin_call(dsir_ctx* c);
-int walk_end_call(dsir_ctx* c);
 int randla_forward(dsir_ctx* c, const RandlaW& w, const Seg& in0, const Seg* in1, const Pyramid& py, float* feat_out,
                    float* logits_out, EncCache* cache = nullptr);
 int run_ppf_pre(dsir_ctx* c, const RandlaW& w, const float* rows, int stride, const int32_t* neigh, int64_t neigh_cs, int clouds, int n,

@@ -1,0 +1,160 @@
+// The stage entries of include/dsir.h: index narrowing, the KNN pyramid, one RandLA pass and the use_ppf front end, normals,
+// FPFH, score, aggregation, and the preprocessing (voxel down-sampling, resampling).
+#include "engine_ctx.h"
+
+using namespace dsir;
+
+extern "C" {
+
+int dsir_narrow_i64(dsir_ctx* c, const int64_t* src, int32_t* dst, int64_t n) {
+  Call call(c); if (call.refused()) return 1;
+  launch_narrow_i64(src, dst, n, c->stream);
+  return call.finish();
+}
+
+int dsir_knn_pyramid(dsir_ctx* c, const float* points, int stride, int clouds, int n, float* xyz, int32_t* neigh,
+                     int32_t* sub, int32_t* interp) {
+  Call call(c); if (call.refused()) return 1;
+  if (clouds < 1 || stride < 3) return fail(c, "dsir_knn_pyramid: bad arguments");
+  if (int r = build_pyramid(c, points, stride, clouds, n, xyz, neigh, sub, interp)) return r;
+  return call.finish();
+}
+
+int dsir_randla_forward(dsir_ctx* c, int which, const float* features, int cin, int clouds, int n, const float* xyz,
+                        const int32_t* neigh, const int32_t* sub, const int32_t* interp, float* feat, float* logits) {
+  Call call(c, Call::kWeights); if (call.refused()) return 1;
+  if (which != 0 && c->cfg.pipeline != DSIR_PIPELINE_ALIGN) return fail(c, "randla_forward: this context has no inlier_model (pipeline != align)");
+  const RandlaW& w = which == 0 ? c->net.feat : c->net.inl;
+  if (w.ppf ? cin < 6 : cin != w.cin)
+    return w.ppf ? fail(c, "randla_forward: use_ppf needs rows of xyz + normal, at least 6 columns, got %d (reference RandLANet.py:325)", cin)
+                 : fail(c, "randla_forward: expected %d input channels, got %d", w.cin, cin);
+  if (check_batch(c, "randla_forward", clouds, n)) return 1;
+  Pyramid py;
+  fill_pyramid_layout(c->cfg, clouds, n, py);
+  if (py.nl[3] < kKnn) return fail(c, "cloud too small (n=%d)", n);
+  py.xyz = xyz; py.neigh = neigh; py.sub = sub; py.interp = interp;
+  // use_ppf: the row's first three columns are the point, the next three its normal (RandLANet.py:326)
+  const Seg in0 = plain_seg(features, (int64_t)n * cin, w.ppf ? 3 : cin, cin);
+  const Seg in1 = plain_seg(features + 3, (int64_t)n * cin, 3, cin);
+  if (int r = call.begin_walker()) return r;
+  if (int r = randla_forward(c, w, in0, w.ppf ? &in1 : nullptr, py, feat, logits)) return r;
+  return call.finish();
+}
+
+int dsir_ppf_pre(dsir_ctx* c, int which, const float* rows, int stride, const int32_t* neigh, int64_t neigh_cs, int clouds, int n,
+                 float* out) {
+  Call call(c, Call::kWeights); if (call.refused()) return 1;
+  if (!(c->flags & DSIR_FLAG_PPF)) return fail(c, "dsir_ppf_pre: the context was not created with DSIR_FLAG_PPF");
+  if (which != 0 && c->cfg.pipeline != DSIR_PIPELINE_ALIGN) return fail(c, "dsir_ppf_pre: this context has no inlier_model (pipeline != align)");
+  if (!rows || !neigh || !out || clouds < 1 || n < kKnn) return fail(c, "dsir_ppf_pre: bad arguments");
+  if (stride < 6) return fail(c, "dsir_ppf_pre: rows of xyz + normal need at least 6 columns, got %d (reference RandLANet.py:325)", stride);
+  if (check_batch(c, "dsir_ppf_pre", clouds, n)) return 1;
+  if (int r = run_ppf_pre(c, which == 0 ? c->net.feat : c->net.inl, rows, stride, neigh, neigh_cs, clouds, n, out)) return r;
+  return call.finish();
+}
+
+int dsir_estimate_normals(dsir_ctx* c, const float* points, int stride, const int32_t* neigh, int64_t neigh_cs, int clouds, int n,
+                          const float* viewpoint, float* normals, int32_t* flags) {
+  Call call(c); if (call.refused()) return 1;
+  if (!points || !neigh || !normals || clouds < 1 || clouds > 65535 || n < 1 || stride < 3) return fail(c, "dsir_estimate_normals: bad arguments");
+  const float v[3] = {viewpoint ? viewpoint[0] : 0.f, viewpoint ? viewpoint[1] : 0.f, viewpoint ? viewpoint[2] : 0.f};
+  launch_estimate_normals(points, (int64_t)n * stride, stride, neigh, neigh_cs, n, clouds, v[0], v[1], v[2], normals, flags, c->stream);
+  return call.finish();
+}
+
+int dsir_estimate_normals_csr(dsir_ctx* c, const float* points, int stride, const int32_t* csr_offsets, const int32_t* csr_cols, int clouds,
+                              int n, const float* viewpoint, float* normals, int32_t* flags) {
+  Call call(c); if (call.refused()) return 1;
+  if (!points || !csr_offsets || !csr_cols || !normals || clouds < 1 || clouds > 65535 || n < 1 || stride < 3)
+    return fail(c, "dsir_estimate_normals_csr: bad arguments");
+  const float v[3] = {viewpoint ? viewpoint[0] : 0.f, viewpoint ? viewpoint[1] : 0.f, viewpoint ? viewpoint[2] : 0.f};
+  launch_estimate_normals_csr(points, (int64_t)n * stride, stride, csr_offsets, csr_cols, n, clouds, v[0], v[1], v[2], normals, flags, c->stream);
+  return call.finish();
+}
+
+int dsir_fpfh(dsir_ctx* c, const float* points, int stride, const float* normals, const int32_t* neigh, int64_t neigh_cs,
+              const int32_t* csr_offsets, const int32_t* csr_cols, int clouds, int n, float* desc, int out_ld, int32_t* flags) {
+  Call call(c); if (call.refused()) return 1;
+  if (!points || !desc || clouds < 1 || clouds > 65535 || n < 1 || stride < 3 || out_ld < kFpfhDim) return fail(c, "dsir_fpfh: bad arguments");
+  if (!normals && stride < 6) return fail(c, "dsir_fpfh: without normals the rows need xyz + normal, at least 6 columns, got %d", stride);
+  const bool fixed = neigh != nullptr, csr = csr_offsets != nullptr || csr_cols != nullptr;
+  if (fixed == csr) return fail(c, "dsir_fpfh: exactly one of neigh_idx and (csr_offsets, csr_cols) expected");
+  if (csr && (!csr_offsets || !csr_cols)) return fail(c, "dsir_fpfh: a CSR list needs both csr_offsets and csr_cols");
+  if ((int64_t)clouds * n > 0x7fffffffll / kFpfhRow) return fail(c, "dsir_fpfh: clouds x n = %lld rows beyond the int32 range of the SPFH table", (long long)clouds * n);
+  FpfhArgs a;
+  a.table = reinterpret_cast<int32_t*>(c->ws.raw(fpfh_scratch_bytes(clouds, n)));
+  if (c->ws.overflow) return fail(c, "workspace too small for dsir_fpfh (clouds x n x 136 bytes: raise max_points / max_pairs)");
+  a.pts = points; a.pts_cs = (int64_t)n * stride; a.pts_ld = stride;
+  a.nrm = normals ? normals : points + 3; a.nrm_ld = normals ? 3 : stride; a.nrm_cs = (int64_t)n * a.nrm_ld;
+  a.cols = fixed ? neigh : csr_cols; a.neigh_cs = neigh_cs; a.offsets = csr_offsets;
+  a.desc = desc; a.out_ld = out_ld; a.flags = flags; a.n = n; a.clouds = clouds;
+  if (!launch_fpfh(a, c->stream)) return fail(c, "dsir_fpfh: shape refused");
+  return call.finish();
+}
+
+int dsir_score(dsir_ctx* c, const float* feat, const float* logits, const float* xyz, int64_t xyz_cs,
+               const int32_t* neigh, int64_t neigh_cs, int clouds, int n, float* score, int32_t* label) {
+  Call call(c, Call::kWeights); if (call.refused()) return 1;
+  if (!feat || !logits || !xyz || !neigh || !score || clouds < 1 || n < 1) return fail(c, "dsir_score: bad arguments");
+  if (check_batch(c, "dsir_score", clouds, n)) return 1;
+  ScoreScratch s;
+  s.red = c->ws.get<float>((size_t)clouds * 4);
+  s.prob = c->ws.get<float>((size_t)clouds * n);
+  s.label = c->ws.get<int32_t>((size_t)clouds * n);
+  if (c->ws.overflow) return fail(c, "workspace exhausted in dsir_score");
+  launch_score(feat, logits, c->cfg.num_classes, xyz, xyz_cs, neigh, neigh_cs, clouds, n, s, score, label, c->stream);
+  return call.finish();
+}
+
+int dsir_aggregate(dsir_ctx* c, const float* xyz, int64_t xyz_cs, const float* feat0, const float* score, int clouds,
+                   int n, float* desc) {
+  Call call(c, Call::kWeights); if (call.refused()) return 1;
+  if (c->cfg.pipeline == DSIR_PIPELINE_LABEL) return fail(c, "dsir_aggregate: a label-pipeline context has no aggregation layers");
+  if (!xyz || !feat0 || !score || !desc || clouds < 1 || n < 1) return fail(c, "dsir_aggregate: bad arguments");
+  if (check_batch(c, "dsir_aggregate", clouds, n)) return 1;
+  float* F = run_mlp_feat(c, feat0, clouds, n);
+  run_att_proj(c, xyz, xyz_cs, score, F, clouds, n, desc);
+  return call.finish();
+}
+
+int dsir_voxel_downsample(dsir_ctx* c, const float* points, const int64_t* offsets, int clouds, int stride, float voxel_size,
+                          const float* crop, int cap, float* out, int32_t* counts) {
+  Call call(c); if (call.refused()) return 1;
+  if (!points || !offsets || !out || !counts || stride < 3 || stride > 16 || cap < 1 || !(voxel_size > 0.f))
+    return fail(c, "dsir_voxel_downsample: bad arguments");
+  if (clouds < 1 || clouds > 1000) return fail(c, "dsir_voxel_downsample: %d clouds in one call (1 to 1000 supported)", clouds);
+  const int64_t total = offsets[clouds];
+  if (total <= 0 || total > 0x7fffffffll) return fail(c, "dsir_voxel_downsample: %lld points unsupported", (long long)total);
+  void* scratch = c->ws.raw(voxel_downsample_scratch_bytes(total, clouds));
+  if (c->ws.overflow) return fail(c, "workspace too small for %lld raw points (raise max_points / max_pairs)", (long long)total);
+  // the host offsets are consumed by an async copy: make the call self-contained
+  HIP_OK(c, hipStreamSynchronize(c->stream));
+  const int32_t* bad_dev = nullptr;
+  if (int r = launch_voxel_downsample(points, offsets, clouds, stride, voxel_size, crop, cap, out, counts, scratch, c->stream,
+                                      &bad_dev))
+    return fail(c, "dsir_voxel_downsample: launch failed (%d)", r);
+  HIP_OK(c, hipStreamSynchronize(c->stream));
+  int32_t bad = kVoxelNoBadRow;
+  HIP_OK(c, hipMemcpy(&bad, bad_dev, sizeof(bad), hipMemcpyDeviceToHost));
+  if (bad != kVoxelNoBadRow) {                       // never dropped, never aliased into a neighbouring key field
+    int cloud = 0;
+    while (cloud + 1 < clouds && offsets[cloud + 1] <= bad) ++cloud;
+    return fail(c, "dsir_voxel_downsample: cloud %d row %lld survives the crop with a voxel index outside [0, 2^18) or a "
+                   "coordinate that is not finite (counts / out are unspecified)", cloud, (long long)(bad - offsets[cloud]));
+  }
+  return call.finish();
+}
+
+int dsir_resample(dsir_ctx* c, const float* in, const int32_t* counts, int clouds, int cap, int stride, int k, int mode,
+                  uint64_t seed, float* out) {
+  Call call(c); if (call.refused()) return 1;
+  if (!in || !counts || !out || clouds < 1 || cap < 1 || stride < 1 || k < 1 || (mode != 0 && mode != 1))
+    return fail(c, "dsir_resample: bad arguments");
+  void* scratch = c->ws.raw(resample_scratch_bytes(clouds, cap));
+  if (c->ws.overflow) return fail(c, "workspace too small for dsir_resample");
+  if (int r = launch_resample(in, counts, clouds, cap, stride, k, mode, seed, out, scratch, c->stream))
+    return fail(c, "dsir_resample: launch failed (%d)", r);
+  return call.finish();
+}
+
+}  // extern "C"

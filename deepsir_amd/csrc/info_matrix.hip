@@ -101,7 +101,7 @@ using namespace dsir;
 
 extern "C" int dsir_information_matrix(dsir_ctx* c, const float* points_src, const float* points_ref, int pairs, int J, int K, int stride,
                                        float max_corr_dist, const float* T, int search, double* info_out, int32_t* count_out) {
-  if (!c) return 1;
+  Call call(c); if (call.refused()) return 1;
   if (!points_src || !points_ref || !T || !info_out || !count_out || pairs < 1 || J < 1 || K < 1 || stride < 3 || !(max_corr_dist > 0.f) ||
       (search != 0 && search != 1))
     return fail(c, "dsir_information_matrix: bad arguments");
@@ -111,8 +111,6 @@ extern "C" int dsir_information_matrix(dsir_ctx* c, const float* points_src, con
   IcpArgs a{};
   a.src = points_src; a.ref = points_ref; a.pairs = pairs; a.J = J; a.K = K; a.stride = stride; a.max_corr_dist = max_corr_dist;
   a.T_init = T; a.search = search == 1 ? IcpSearch::Grid : IcpSearch::Brute;
-  HIP_OK(c, hipSetDevice(c->device));
-  c->ws.top = 0; c->ws.overflow = false;
   const InfoLayout l(pairs, J, icp_corr_scratch_bytes(a));
   void* scratch = c->ws.raw(l.bytes);
   if (c->ws.overflow) return fail(c, "workspace too small for dsir_information_matrix (raise max_points / max_pairs)");
@@ -123,5 +121,5 @@ extern "C" int dsir_information_matrix(dsir_ctx* c, const float* points_src, con
   double* part = at<double>(scratch, l.part);
   hipLaunchKernelGGL(info_accum_kernel, dim3(nch, pairs), dim3(PT), 0, c->stream, points_ref, stride, (const int32_t*)idx, J, K, part);
   hipLaunchKernelGGL(info_finish_kernel, dim3(pairs), dim3(64), 0, c->stream, (const double*)part, nch, info_out, count_out);
-  return post(c);
+  return call.finish();
 }

@@ -24,6 +24,7 @@
 #include "dsir_train.h"
 #include "op_layouts.h"
 #include "seg_sort.h"
+#include "train_ops.h"
 
 namespace dsir {
 namespace {
@@ -152,8 +153,6 @@ __global__ void targets_matches_kernel(const int64_t* __restrict__ keys, const i
   }
 }
 
-inline unsigned grid1(int64_t n) { const int64_t g = (n + 255) / 256; return (unsigned)(g < 1 ? 1 : (g > 8192 ? 8192 : g)); }
-inline int done() { return (int)hipGetLastError(); }
 
 // reference slices across the grid: enough blocks to fill the chip (about 2048 of 4 waves), no part shorter than one tile
 inline int match_split(int pairs, int J, int K) {

@@ -478,7 +478,7 @@ extern "C" int dsir_pose_graph_optimize(dsir_ctx* c, int graphs, const int32_t* 
                                         const int32_t* edge_st, const double* edge_T, const double* edge_info,
                                         const uint8_t* edge_uncertain, const double* mu, const int32_t* reference_node, int max_iter,
                                         void* scratch, double* X, double* line, double* stats) {
-  if (!c) return 1;
+  Call call(c); if (call.refused()) return 1;
   int which = -1;
   const int why = pose_graph_batch_refusal(graphs, node_off, edge_off, reference_node, &which);
   if (why == kPgTooManyNodes)
@@ -490,7 +490,6 @@ extern "C" int dsir_pose_graph_optimize(dsir_ctx* c, int graphs, const int32_t* 
   if (!X0 || !mu || !scratch || !X || !line || !stats || max_iter < 0 ||
       (edge_off[graphs] > 0 && (!edge_st || !edge_T || !edge_info || !edge_uncertain)))
     return fail(c, "dsir_pose_graph_optimize: bad arguments");
-  HIP_OK(c, hipSetDevice(c->device));
   const PoseGraphLayout l(graphs, node_off, edge_off);
   std::vector<int64_t> desc((size_t)graphs * kPoseGraphDescWords, 0);
   l.fill_desc(graphs, node_off, edge_off, reference_node, desc.data());
@@ -500,5 +499,5 @@ extern "C" int dsir_pose_graph_optimize(dsir_ctx* c, int graphs, const int32_t* 
   a.desc = at<int64_t>(scratch, l.desc); a.X0 = X0; a.st = edge_st; a.eT = edge_T; a.info = edge_info; a.unc = edge_uncertain; a.mu = mu;
   a.max_iter = max_iter; a.scratch = static_cast<char*>(scratch); a.ework = l.ework; a.X = X; a.line = line; a.stats = stats;
   hipLaunchKernelGGL(pose_graph_kernel, dim3(graphs), dim3(PT), 0, c->stream, a);
-  return post(c);
+  return call.finish();
 }

@@ -87,8 +87,8 @@ bool lse_uv_enabled() {
 // capture: collected on the host, uploaded once after the capture (dsir_register), the kernel node holds the final device address.
 int walk_flush(dsir_ctx* c, WalkProgram& P, hipStream_t st) {
   if (P.nphases <= 0) return 0;
-  if (c->walk_used >= dsir_ctx::kWalkSlots) return fail(c, "walker: more than %d programs in one call", dsir_ctx::kWalkSlots);
-  const int slot = c->walk_used++;
+  if (c->call.walk_used >= dsir_ctx::kWalkSlots) return fail(c, "walker: more than %d programs in one call", dsir_ctx::kWalkSlots);
+  const int slot = c->call.walk_used++;
   P.ctr = c->walk_ctr + (size_t)slot * dsir_ctx::kWalkClouds * kWalkCtrWords;
   P.trace = c->walk_trace ? c->walk_trace + (size_t)slot * kWalkMaxPhases * 4 : nullptr;
   const size_t bytes = offsetof(WalkProgram, job) + (size_t)P.nphases * sizeof(WalkJob);
@@ -103,31 +103,11 @@ int walk_flush(dsir_ctx* c, WalkProgram& P, hipStream_t st) {
     dev = c->walk_dev + slot;
   }
   // queues and counters of this program: part of the region a registration zeroes in its opening launch; otherwise here
-  if (!c->stats_prezeroed) HIP_OK(c, hipMemsetAsync(P.ctr, 0, sizeof(unsigned) * P.clouds * kWalkCtrWords, st));
+  if (!c->call.stats_prezeroed) HIP_OK(c, hipMemsetAsync(P.ctr, 0, sizeof(unsigned) * P.clouds * kWalkCtrWords, st));
   launch_walk(P, dev, st);
   P.nphases = 0;
   return 0;
 }
-
-}  // namespace
-
-// a call that may run RandLA passes: its programs start at slot 0; eager calls take the other staging set (the previous call's copies
-// may still be queued) after making sure that set's own last copy has run
-int walk_begin_call(dsir_ctx* c) {
-  c->walk_used = 0;
-  if (c->capturing || !c->walk_dev) return 0;
-  c->walk_set ^= 1;
-  if (c->walk_ev_armed[c->walk_set]) { HIP_OK(c, hipEventSynchronize(c->walk_ev[c->walk_set])); c->walk_ev_armed[c->walk_set] = false; }
-  return 0;
-}
-int walk_end_call(dsir_ctx* c) {
-  if (c->capturing || !c->walk_dev || c->walk_used == 0) return 0;
-  HIP_OK(c, hipEventRecord(c->walk_ev[c->walk_set], c->stream));
-  c->walk_ev_armed[c->walk_set] = true;
-  return 0;
-}
-
-namespace {
 
 struct Sched {
   dsir_ctx* c;
@@ -141,7 +121,7 @@ struct Sched {
   void rec_flush() {
     if (!rec) return;
     if (rec->nphases > 0 && walk_flush(c, *rec, st)) rec_error = 1;
-    if (c->walk_used >= dsir_ctx::kWalkSlots) rec = nullptr;
+    if (c->call.walk_used >= dsir_ctx::kWalkSlots) rec = nullptr;
   }
   // false: not recorded (no room) - the caller launches the layer itself
   bool rec_push(const WalkJob& j) {
@@ -155,7 +135,7 @@ struct Sched {
   }
   // a launcher refused the layer: nothing more runs (as on an exhausted arena), the schedule's caller reports why
   void refuse(const char* why) {
-    if (!c->ws.overflow) c->sched_error = why;
+    if (!c->ws.overflow) c->call.sched_error = why;
     c->ws.overflow = true;
   }
   // a point-wise GEMM launch: a phase when recording and plannable, else (after flushing what was recorded: order) its own launch
@@ -169,8 +149,8 @@ struct Sched {
   }
 
   double* stats_slot(int groups) {
-    double* p = c->stats + c->stats_top;
-    c->stats_top += (size_t)clouds * groups * kGnWords;
+    double* p = c->stats + c->call.stats_top;
+    c->call.stats_top += (size_t)clouds * groups * kGnWords;
     return p;
   }
   // the fp16 split of a weight matrix inside the context's blob (dsir_finalize_weights); off unless the split layers are on
@@ -401,6 +381,25 @@ struct Sched {
 
 }  // namespace
 
+// a call that may run RandLA passes: eager calls take the other pinned staging set (the previous call's copies may still be queued)
+// after making sure that set's own last copy has run; a capture collects its programs on the host instead
+int Call::begin_walker() {
+  dsir_ctx* c = c_;
+  if (c->capturing || !c->walk_dev) return 0;
+  c->walk_set ^= 1;
+  c->call.walk_begun = true;
+  if (c->walk_ev_armed[c->walk_set]) { HIP_OK(c, hipEventSynchronize(c->walk_ev[c->walk_set])); c->walk_ev_armed[c->walk_set] = false; }
+  return 0;
+}
+// the end of such a call, on every way out: the set's event after the last copy from it
+hipError_t Call::end_walker(dsir_ctx* c) {
+  if (!c->call.walk_begun || c->call.walk_used == 0) return hipSuccess;
+  c->call.walk_begun = false;
+  const hipError_t e = hipEventRecord(c->walk_ev[c->walk_set], c->stream);
+  if (e == hipSuccess) c->walk_ev_armed[c->walk_set] = true;
+  return e;
+}
+
 // persistent storage of the inlier model's position-encoding branch, alive across the iterations of a registration
 int EncCache::plan(dsir_ctx* c, const Pyramid& ps, double* prezeroed) {
   const dsir_cfg& g = c->cfg;
@@ -446,7 +445,7 @@ int run_ppf_pre(dsir_ctx* c, const RandlaW& w, const float* rows, int stride, co
                 float* out) {
   const size_t stats_need = gn_layer_words(clouds, 4);
   if (stats_need > c->stats_cap) return fail(c, "stats arena too small (%zu > %zu)", stats_need, c->stats_cap);
-  c->stats_top = 0;
+  c->call.stats_top = 0;
   HIP_OK(c, hipMemsetAsync(c->stats, 0, stats_need * sizeof(double), c->stream));
   Sched s{c, c->stream, clouds};
   s.ppf_pre(w.pre, plain_seg(rows, (int64_t)n * stride, 3, stride), plain_seg(rows + 3, (int64_t)n * stride, 3, stride), neigh, neigh_cs, n, out);
@@ -462,11 +461,11 @@ int randla_forward(dsir_ctx* c, const RandlaW& w, const Seg& in0, const Seg* in1
   hipStream_t st = c->stream;
   Sched s{c, st, py.clouds};
   const size_t stats_need = gn_pass_words(py.clouds);
-  if (c->stats_prezeroed && c->stats_base + stats_need <= c->stats_cap) {
-    c->stats_top = c->stats_base;               // zeroed by register_enqueue together with the other passes' regions
-    c->stats_base += stats_need;
+  if (c->call.stats_prezeroed && c->call.stats_base + stats_need <= c->stats_cap) {
+    c->call.stats_top = c->call.stats_base;               // zeroed by register_enqueue together with the other passes' regions
+    c->call.stats_base += stats_need;
   } else {
-    c->stats_top = 0;
+    c->call.stats_top = 0;
     if (stats_need > c->stats_cap) return fail(c, "stats arena too small (%zu > %zu)", stats_need, c->stats_cap);
     HIP_OK(c, hipMemsetAsync(c->stats, 0, stats_need * sizeof(double), st));
   }
@@ -478,7 +477,7 @@ int randla_forward(dsir_ctx* c, const RandlaW& w, const Seg& in0, const Seg* in1
   // inputs the pyramid alone) is computed ahead of the chain so that it does not cut the chain in pieces.
   static const int walk_from = 2;                            // first level inside the walker
   const bool walk = c->walk_mode && c->walk_dev && py.clouds <= dsir_ctx::kWalkClouds && L > walk_from &&
-                    c->walk_used < dsir_ctx::kWalkSlots;
+                    c->call.walk_used < dsir_ctx::kWalkSlots;
   WalkProgram wprog;
   wprog.clouds = py.clouds;
   wprog.flags = c->walk_flags;
@@ -534,7 +533,7 @@ int randla_forward(dsir_ctx* c, const RandlaW& w, const Seg& in0, const Seg* in1
     samp.p = c->ws.get<float>((size_t)py.clouds * samp.rows * samp.C);
     if (l == 0) enc_out.p = c->ws.get<float>((size_t)py.clouds * n * enc_out.C);
     if (c->ws.overflow) {
-      if (c->sched_error) { const char* m = c->sched_error; c->sched_error = nullptr; return fail(c, "randla_forward: %s (level %d)", m, l); }
+      if (c->call.sched_error) return fail(c, "randla_forward: %s (level %d)", c->call.sched_error, l);
       return fail(c, "workspace exhausted in randla_forward (raise max_points / max_pairs)");
     }
     if (l == 0) {

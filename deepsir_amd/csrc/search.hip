@@ -102,23 +102,19 @@ using namespace dsir;
 extern "C" {
 
 int dsir_nn_match(dsir_ctx* c, const float* a, const float* b, int pairs, int J, int K, int32_t* idx) {
-  if (!c) return 1;
+  Call call(c); if (call.refused()) return 1;
   if (!a || !b || !idx || pairs < 1 || J < 1 || K < 1) return fail(c, "dsir_nn_match: bad arguments");
-  HIP_OK(c, hipSetDevice(c->device));
-  c->ws.top = 0; c->ws.overflow = false;
   DescSearch s{c, SearchMode::exhaustive, pairs, J, K, /*timed=*/true};
   s.alloc(/*with_match_scratch=*/true);
   if (c->ws.overflow) return fail(c, "workspace exhausted in nn_match");
   if (int r = s.run(a, b, idx, {})) return r;
-  return post(c);
+  return call.finish();
 }
 
 int dsir_nn_match_screened(dsir_ctx* c, const float* a, const float* b, int pairs, int J, int K, int32_t* idx,
                            int64_t* stats) {
-  if (!c) return 1;
+  Call call(c); if (call.refused()) return 1;
   if (!a || !b || !idx || pairs < 1 || J < 1 || K < 1) return fail(c, "dsir_nn_match_screened: bad arguments");
-  HIP_OK(c, hipSetDevice(c->device));
-  c->ws.top = 0; c->ws.overflow = false;
   DescSearch s{c, SearchMode::screened, pairs, J, K};
   s.alloc(/*with_match_scratch=*/false, /*with_stats=*/true, /*with_bad=*/true);
   if (c->ws.overflow) return fail(c, "workspace exhausted in nn_match_screened");
@@ -132,18 +128,16 @@ int dsir_nn_match_screened(dsir_ctx* c, const float* a, const float* b, int pair
     HIP_OK(c, hipMemcpy(h, s.stats, 16, hipMemcpyDeviceToHost));
     stats[0] = (int64_t)h[0]; stats[1] = (int64_t)h[1];
   }
-  return post(c);
+  return call.finish();
 }
 
 int dsir_screen_bounds(dsir_ctx* c, const float* a, const float* b, int J, int K, float* lower, float* upper, float* exact,
                        float* zacc, int32_t* idx, float* thresh, int32_t* cand_count, int32_t* cand_code, float* cand_lower,
                        int32_t* out_of_domain) {
-  if (!c) return 1;
+  Call call(c); if (call.refused()) return 1;
   if (!a || !b || !lower || !upper || !exact || !idx || !thresh || !cand_count || !cand_code || !cand_lower || J < 1 || K < 1 ||
       (int64_t)J * K > ((int64_t)1 << 26))
     return fail(c, "dsir_screen_bounds: bad arguments (J x K <= 2^26)");
-  HIP_OK(c, hipSetDevice(c->device));
-  c->ws.top = 0; c->ws.overflow = false;
   DescSearch s{c, SearchMode::screened, 1, J, K};
   s.alloc(/*with_match_scratch=*/false, /*with_stats=*/false, /*with_bad=*/true);
   if (c->ws.overflow) return fail(c, "workspace exhausted in dsir_screen_bounds");
@@ -157,19 +151,17 @@ int dsir_screen_bounds(dsir_ctx* c, const float* a, const float* b, int J, int K
   if (int r = s.run(a, b, idx, one)) return r;
   launch_screen_export(s.scratch, J, thresh, cand_count, cand_code, cand_lower, st);
   if (out_of_domain) HIP_OK(c, hipMemcpyAsync(out_of_domain, s.bad, 4, hipMemcpyDeviceToDevice, st));
-  return post(c);
+  return call.finish();
 }
 int dsir_screen_cap(void) { return nn_screen_cap(); }
 
 int dsir_feature_correspondences(dsir_ctx* c, const float* desc_src, const float* desc_ref, int pairs, int J, int K, int mutual,
                                  int32_t* corr, int32_t* counts) {
-  if (!c) return 1;
+  Call call(c); if (call.refused()) return 1;
   if (!desc_src || !desc_ref || !corr || !counts || pairs < 1 || J < 1 || K < 1)
     return fail(c, "dsir_feature_correspondences: bad arguments");
   if (J > c->cfg.max_points || K > c->cfg.max_points)
     return fail(c, "dsir_feature_correspondences: J=%d or K=%d beyond max_points=%d", J, K, c->cfg.max_points);
-  HIP_OK(c, hipSetDevice(c->device));
-  c->ws.top = 0; c->ws.overflow = false;
   int32_t* ab = c->ws.get<int32_t>((size_t)pairs * J);
   int32_t* ba = c->ws.get<int32_t>((size_t)pairs * K);
   DescSearch s_ab{c, SearchMode::exhaustive, pairs, J, K}, s_ba{c, SearchMode::exhaustive, pairs, K, J};
@@ -179,7 +171,7 @@ int dsir_feature_correspondences(dsir_ctx* c, const float* desc_src, const float
   s_ab.run(desc_src, desc_ref, ab, {});
   if (mutual) s_ba.run(desc_ref, desc_src, ba, {});
   launch_corr_compact(ab, ba, pairs, J, K, mutual ? 1 : 0, corr, counts, c->stream);
-  return post(c);
+  return call.finish();
 }
 
 static int match_ts_reset(dsir_ctx* c) {
@@ -304,21 +296,19 @@ int topk_check_shape(dsir_ctx* c, const char* who, int pairs, int J, int K, int 
 extern "C" {
 
 int dsir_nn_match_topk(dsir_ctx* c, const float* a, const float* b, int pairs, int J, int K, int k, int32_t* idx, float* dist) {
-  if (!c) return 1;
+  Call call(c); if (call.refused()) return 1;
   if (!a || !b || !idx) return fail(c, "dsir_nn_match_topk: bad arguments");
   if (int r = topk_check_shape(c, "dsir_nn_match_topk", pairs, J, K, k)) return r;
-  HIP_OK(c, hipSetDevice(c->device));
   DescSearch s{c, SearchMode::exhaustive, pairs, J, K};
   // the whole scratch, checked before the first launch
   const size_t need = arena_pad(s.topk_bytes(k));
   if (need > c->ws.cap)
     return fail(c, "workspace too small for dsir_nn_match_topk: needs %zu bytes, the arena holds %zu (raise max_points / max_pairs, or pass "
                    "fewer pairs)", need, c->ws.cap);
-  c->ws.top = 0; c->ws.overflow = false;
   s.alloc_topk(k);
   if (c->ws.overflow) return fail(c, "workspace exhausted in dsir_nn_match_topk");
   if (int r = s.run_topk(a, b, k, idx, dist)) return r;
-  return post(c);
+  return call.finish();
 }
 
 int dsir_nn_match_topk_splits(dsir_ctx* c, int pairs, int J, int K, int k) {
@@ -328,7 +318,7 @@ int dsir_nn_match_topk_splits(dsir_ctx* c, int pairs, int J, int K, int k) {
 
 int dsir_feature_correspondences_ex(dsir_ctx* c, const float* desc_src, const float* desc_ref, int pairs, int J, int K, int mutual,
                                     int k, float ratio, int32_t* corr, int32_t* counts, float* corr_dist) {
-  if (!c) return 1;
+  Call call(c); if (call.refused()) return 1;
   if (!desc_src || !desc_ref || !corr || !counts) return fail(c, "dsir_feature_correspondences_ex: bad arguments");
   if (int r = topk_check_shape(c, "dsir_feature_correspondences_ex", pairs, J, K, k)) return r;
   if ((int64_t)J * k > c->cfg.max_points)
@@ -340,7 +330,6 @@ int dsir_feature_correspondences_ex(dsir_ctx* c, const float* desc_src, const fl
     return fail(c, "dsir_feature_correspondences_ex: the ratio test is defined on the 1-NN set (ratio=%g with k=%d)", (double)ratio, k);
   // today's rule on today's launches
   if (k == 1 && !(ratio > 0.f) && !corr_dist) return dsir_feature_correspondences(c, desc_src, desc_ref, pairs, J, K, mutual, corr, counts);
-  HIP_OK(c, hipSetDevice(c->device));
   const int ks = ratio > 0.f ? 2 : k;                 // ranks searched src -> ref: the ratio test reads rank 1
   const float r2 = ratio > 0.f ? ratio * ratio : 0.f;   // fp32, rounded once
   DescSearch s_ab{c, SearchMode::exhaustive, pairs, J, K}, s_ba{c, SearchMode::exhaustive, pairs, K, J};
@@ -349,7 +338,6 @@ int dsir_feature_correspondences_ex(dsir_ctx* c, const float* desc_src, const fl
   if (need > c->ws.cap)
     return fail(c, "workspace too small for dsir_feature_correspondences_ex: needs %zu bytes, the arena holds %zu (raise max_points / "
                    "max_pairs, or pass fewer pairs)", need, c->ws.cap);
-  c->ws.top = 0; c->ws.overflow = false;
   int32_t* iab = c->ws.get<int32_t>(n_ab);
   float* dab = c->ws.get<float>(n_ab);
   int32_t* iba = mutual ? c->ws.get<int32_t>(n_ba) : nullptr;
@@ -359,7 +347,7 @@ int dsir_feature_correspondences_ex(dsir_ctx* c, const float* desc_src, const fl
   if (int r = s_ab.run_topk(desc_src, desc_ref, ks, iab, dab)) return r;
   if (mutual) if (int r = s_ba.run_topk(desc_ref, desc_src, k, iba, nullptr)) return r;
   launch_corr_topk_compact(iab, dab, ks, iba, k, pairs, J, K, mutual ? 1 : 0, k, r2, corr, counts, corr_dist, c->stream);
-  return post(c);
+  return call.finish();
 }
 
 }  // extern "C"

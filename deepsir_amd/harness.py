@@ -430,7 +430,7 @@ def register_fpfh(pairs: Sequence[Dict[str, np.ndarray]], engine, voxel_size: fl
     ``search="grid"`` no pyramid is built, so clouds under 1024 points work, up to what the FPFH, correspondence and pose entries take.
 
     ``engine`` is a ``deepsir_amd.engine.Engine`` THE CALLER PREPARED: the descriptor itself needs no weights, but the pyramid and
-    the other existing entries this calls refuse a context whose weights are not loaded (``check_ready``, csrc/engine_ctx.h), so
+    the other existing entries this calls refuse a context whose weights are not loaded (``Call::kWeights``, csrc/engine_ctx.h), so
     load a state dict first - any, e.g. ``weights.generate_state_dict(cfg, 0)``; its values are never read here.  Its max_points /
     max_pairs must cover the clouds and ``batch``; unless both radii are set with ``search="grid"`` (no pyramid, above), the clouds
     must be ones the pyramid takes (>= 1024 points with the default ratios)."""
