@@ -99,11 +99,12 @@ int dsir_create_ex(int device, const dsir_cfg* cfg, int flags, dsir_ctx** out) {
   const size_t per_cloud = (size_t)cfg->max_points * 2560 * sizeof(float) + ((size_t)1 << 22);
   c->ws.cap = clouds * per_cloud + ((size_t)64 << 20);
   if (cfg->pipeline == DSIR_PIPELINE_ALIGN) {
-    // per pair: the inlier model's cached enc halves of the attention scores (EncCache::s2_buf), 2 x n_l x 16 x d_l floats
+    // per pair: the inlier model's cached enc halves of the attention scores (EncCache::s2_buf), 2 x n_l x 16 x d_l floats for
+    // the levels that keep them
     size_t s2 = 0;
     int nl = cfg->max_points;
     for (int l = 0; l < cfg->num_layers; ++l) {
-      if (cfg->d_out[l] >= 64) s2 += (size_t)2 * nl * kKnn * cfg->d_out[l] * sizeof(float) + 512;
+      if (att_keeps_score_cache(cfg->d_out[l])) s2 += (size_t)2 * nl * kKnn * cfg->d_out[l] * sizeof(float) + 512;
       nl /= cfg->sub_sampling_ratio[l];
     }
     c->ws.cap += (size_t)cfg->max_pairs * s2;

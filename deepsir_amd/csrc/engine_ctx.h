@@ -239,7 +239,7 @@ inline Seg plain_seg(const float* x, int64_t cloud_stride, int C, int ld, const 
 // storage and re-used afterwards: same kernels, same inputs, same bits (SURVEY §7.2 loop invariants).
 struct EncCache {
   bool valid = false;
-  float* s2_buf[DSIR_MAX_LEVELS][2] = {};   // enc half of the attention scores (W2 enc / W2 enc2) of the split levels (d >= 64)
+  float* s2_buf[DSIR_MAX_LEVELS][2] = {};   // enc half of the attention scores (W2 enc / W2 enc2) of the levels that keep them (att_keeps_score_cache)
   float* enc_buf[DSIR_MAX_LEVELS] = {};
   float* uv_buf[DSIR_MAX_LEVELS] = {};     // levels whose lfa.mlp1 rows are not stored (lse_uv.hip): tables + dist instead of enc_buf
   float* dist_buf[DSIR_MAX_LEVELS] = {};

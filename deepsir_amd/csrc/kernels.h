@@ -52,7 +52,7 @@ enum AMode { A_SEGS = 0, A_LSE = 1 };
 // EPI_ATT2 = attentive pooling with the score GEMM split by linearity:
 //   fc [gather(f); enc] = gather(W1 f) + W2 enc.   G = W1 f is a per-POINT GEMM (16x fewer rows) done
 //   beforehand; this launch contracts only the enc half (A = enc, W = fc[:, d/2:], ldw = d), adds the
-//   gathered G rows to the scores, and pools [gather(f); enc] exactly as EPI_ATT does.
+//   gathered G rows to the scores, and pools [gather(f); enc] exactly as EPI_ATT does.  One kernel family has it: pw_tile.hip.
 enum Epilogue { EPI_GN = 0, EPI_ACT = 1, EPI_LINEAR = 2, EPI_L2NORM = 3, EPI_ATT = 4, EPI_ATT2 = 5 };
 
 struct GemmArgs {
@@ -73,14 +73,15 @@ struct GemmArgs {
   const void* Wl = nullptr;
   const float* bias = nullptr;  // [Cout] or nullptr
   int Cin = 0, Cout = 0;
-  // EPI_ATT2 only: G = W1 f  [clouds][n][Cout] and the gathered-feature half of the pooled operand
+  // EPI_ATT2 (pw_tile.hip) only: G = W1 f  [clouds][n][Cout] and the gathered-feature half of the pooled operand
   const float* g = nullptr;
   int64_t g_cloud_stride = 0;
   Seg fseg = {};                // f [clouds][n][Cout/2] with its lazy GroupNorm; fseg.idx = neighbour index of every A row
-  // EPI_ATT2 only, optional: the enc half of the scores (W2 enc, the launch's own contraction) kept across launches.  In the
+  // EPI_ATT2 (pw_tile.hip) only, optional: the enc half of the scores (W2 enc, the launch's own contraction) kept across launches.  In the
   // inlier model it depends on the pyramid and the weights alone, so iteration 0 stores the accumulators
   // (s2_mode 1) and the later iterations load them instead of contracting (s2_mode 2): same values, bit for bit.
-  // Layout [clouds][M/16][Cout/16][64 lanes][4]: the MFMA C fragments as they sit in registers.
+  // Layout [clouds][M/16][Cout/16][64 lanes][4]: the MFMA C fragments as they sit in registers.  Which levels keep one:
+  // att_keeps_score_cache() below.
   float* s2 = nullptr;
   int64_t s2_cloud_stride = 0;
   int s2_mode = 0;
@@ -130,6 +131,10 @@ Launch launch_pw_stream(const GemmArgs& a, hipStream_t st);
 bool launch_pw_tile(const GemmArgs& a, hipStream_t st);
 // does launch_pw_tile serve this layer with pw_tile_small_kernel (the one kernel that takes GemmArgs::c_split)?
 bool pw_tile_small_serves(const GemmArgs& a);
+// The level widths whose attentive pooling runs as EPI_ATT2 in pw_tile.hip (Sched::att) - the one kernel that takes GemmArgs::s2, so
+// also the widths whose enc-half score cache exists: the workspace is sized for it (dsir_create), EncCache::plan allocates it and
+// Sched::att routes by it.  d = 16, 64 and 128 pool in att_pool.hip, which contracts both halves itself and keeps no cache.
+inline bool att_keeps_score_cache(int d) { return d == 256; }
 
 // att_pool.hip - attentive pooling of the k = 16 layers of levels 0 - 2 on v_mfma_f32_32x32x16_f16: softmax and weighted sum in registers
 // level 0 (d = 16), unsplit: scores = fc [gather(f) ; E] with both halves 8 channels wide; four points per wave

@@ -324,7 +324,7 @@ bool launch_pw_gemm(const GemmArgs& a, hipStream_t st) {
     case EPI_LINEAR: launch_bn<EPI_LINEAR, A_SEGS>(a, st); return true;
     case EPI_L2NORM: launch_t<64, EPI_L2NORM, A_SEGS>(a, st); return true;
     case EPI_ATT: launch_bn<EPI_ATT, A_SEGS>(a, st); return true;
-    default: return false;   // EPI_ATT2 exists only in pw_stream / pw_tile; the engine falls back to EPI_ATT itself (Sched::att)
+    default: return false;   // EPI_ATT2 exists only in pw_tile.hip; the engine falls back to EPI_ATT itself (Sched::att)
   }
 }
 

@@ -16,11 +16,12 @@
 //     block).
 // The sum over k is the same set of products as in pw_gemm.hip, associated in a
 // different (fixed) order; results are deterministic.
-// Loader modes: vector (aligned segments), element-wise (tiny Cin: xyz / score /
-// 6-channel inlier input), and the relative position encoding (RandLANet.py:197-212).
+// Epilogues: GroupNorm statistics, activation, linear (+ residual) and L2 normalisation; attentive pooling is not served here
+// (att_pool.hip, pw_tile.hip, pw_gemm.hip).
+// Loader modes: vector (S_VEC, aligned segments), element-wise (S_ELEM, tiny Cin: xyz / score / 6-channel inlier input), the
+// relative position encoding (S_LSE, RandLANet.py:197-212) and rows rebuilt from the per-point tables of lse_uv.hip (S_UV).
 #include "kernels.h"
 #include "device_utils.h"
-#include "split_f16.h"
 
 namespace dsir {
 
@@ -56,29 +57,17 @@ __device__ __forceinline__ int src_row(const Seg& s, int cloud, int row) {
 // chain, which a third resident wave per SIMD hides better than 12 bytes of spill cost (244 -> 217 us per launch).  The 64-channel
 // streams lose under the same floor (52 bytes of spill: 71 -> 85 us) and keep the allocator's choice.
 constexpr int pw_stream_min_waves(int KQ, int NT, int EPI, int MODE) {
-  return (EPI != EPI_ATT && EPI != EPI_ATT2 && KQ == 8 && MODE == S_UV) ? 3 : 1;
+  return (KQ == 8 && MODE == S_UV) ? 3 : 1;
 }
 
-template <int KQ, int NT, int EPI, int MODE, int SC = 0>   // SC: GemmArgs::s2_mode (EPI_ATT2 only)
+template <int KQ, int NT, int EPI, int MODE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(pw_stream_min_waves(KQ, NT, EPI, MODE)))) void pw_stream_kernel(const GemmArgs p) {
   constexpr int BN = NT * 16;
   constexpr bool kVec = MODE == S_VEC || MODE == S_UV;   // raw rows loaded first, normalised after the loads have landed
-  // Attentive pooling (round 3): the score contraction of a 16-neighbour tile runs on the fp16 matrix pipe at fp32 accuracy -
-  // a lane's 8 or 16 contiguous channels ARE the A fragment of v_mfma_f32_16x16x32_f16 (k = 8 fq + j per 32-channel step, the
-  // same re-ordered k index as the fp32 form), each operand split into two fp16 numbers, three MFMAs per product: 12 / 24 fp16
-  // MFMAs (192 / 384 matrix-pipe cycles) per tile instead of 32 / 64 fp32 ones (1024 / 2048), which two waves per SIMD
-  // contend for.  Scores differ from the fp32 form's by ~1e-7 of their scale; the cached enc halves (SC 1 / 2) come from
-  // this same arithmetic, so hoisted and recomputed iterations still agree bit for bit.  Compile-time and unconditional: dsir_enable_agg_split(0) /
-  // DSIR_AGG_F32 do NOT bring the fp32 form back (include/dsir.h says so); its reference is the oracle.
-  constexpr bool kSplit = (EPI == EPI_ATT || EPI == EPI_ATT2) && (KQ == 8 || KQ == 16) && MODE == S_VEC;
-  constexpr int NS = kSplit ? KQ / 8 : 1;
   constexpr int CP = KQ * 4;  // padded Cin
   __shared__ float s_sc[CP];
   __shared__ float s_sh[CP];
   __shared__ float s_red[EPI == EPI_GN ? 4 * BN * 2 : 1];
-  __shared__ float s_att[(EPI == EPI_ATT || EPI == EPI_ATT2) ? 4 * 16 * (CP + 4) : 1];
-  __shared__ float s_fsc[EPI == EPI_ATT2 ? 64 : 1];   // EPI_ATT2: GroupNorm scale/shift of the gathered-feature half
-  __shared__ float s_fsh[EPI == EPI_ATT2 ? 64 : 1];
 
   // the wave index is uniform across the wave, but only readfirstlane lets the compiler KNOW it: tile indices
   // derived from it then live in SGPRs and the per-tile bounds checks become scalar branches instead of
@@ -87,7 +76,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(pw_stream_m
   const int fr = lane & 15, fq = lane >> 4;
   // XCD-aware work mapping (speed only; per-cloud work and results are unchanged): workgroups are dealt round-robin
   // over the 8 XCDs, each with its own L2.  The bijective remap hands every XCD a CONTIGUOUS range of work items ordered
-  // (cloud, column block, row block), i.e. whole clouds, so the rows a cloud's blocks gather (neighbour features, G = W1 f)
+  // (cloud, column block, row block), i.e. whole clouds, so the rows a cloud's blocks gather (neighbour features, per-point tables)
   // live in ONE L2 instead of being replicated through eight.
   const int nwg = gridDim.x, id = blockIdx.x;
   const int q8 = nwg >> 3, r8 = nwg & 7, xcd = id & 7;
@@ -98,13 +87,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(pw_stream_m
   const int n0 = by * BN;
   const int ldw = p.ldw ? p.ldw : p.Cin;
 
-  // first column of the block's t-th 16-column tile.  EPI_ATT2 (Cout = 2 Cin = 8 KQ, NT = 4): a block owns 32 columns
-  // of the gathered-feature half and the matching 32 of the enc half, so "tile t pools a gathered feature" is the
-  // compile-time condition t < NT/2 for every block
-  auto col0_of = [&](int t) -> int {
-    if (EPI == EPI_ATT2) return t < NT / 2 ? (n0 >> 1) + 16 * t : p.fseg.C + (n0 >> 1) + 16 * (t - NT / 2);
-    return n0 + 16 * t;
-  };
   // The weight fragments are fetched FIRST: their global loads are in flight while the GroupNorm statistics below are decoded
   // (a dependent chain of fp64 arithmetic that opens every workgroup).
   const int c_lo = fq * KQ;                       // first channel of this lane's chunk
@@ -112,7 +94,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(pw_stream_m
   float bv[NT];
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
-    const int col = col0_of(t) + fr;
+    const int col = n0 + 16 * t + fr;
     if ((KQ % 4) == 0 && p.Cin == 4 * KQ) {          // rows of W are 16-byte aligned: vector loads
       if (col < p.Cout) vec_load<KQ>(p.W + (int64_t)col * ldw + c_lo, wf[t]);
       else {
@@ -131,26 +113,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(pw_stream_m
   // GroupNorm scale / shift of the operands -> LDS.  A dependent chain (statistics load, fixed-point decode, fp64 arithmetic, barrier)
   // that opens every workgroup: in vector mode it runs AFTER the first tile group's loads have been issued (below).
   auto stats_to_lds = [&]() {
-    if (EPI == EPI_ATT2) {
-      const Seg& s = p.fseg;
-      for (int c = tid; c < s.C; c += 256) {
-        float scale = 1.f, shift = 0.f;
-        if (s.gn.stats) {
-          const int g = c / (s.C / s.gn.groups);
-          const double* st = s.gn.stats + ((int64_t)cloud * s.gn.groups + g) * kGnWords;
-          const double mean = gn_stat_get(st) * s.gn.inv_count;
-          double var = gn_stat_get(st + 2) * s.gn.inv_count - mean * mean;
-          var = var > 0.0 ? var : 0.0;
-          const double rstd = gn_rstd(var);
-          const double scd = (double)s.gn.gamma[c] * rstd;
-          scale = (float)scd;
-          shift = (float)((double)s.gn.beta[c] - mean * scd);
-        }
-        s_fsc[c] = scale;
-        s_fsh[c] = shift;
-      }
-    }
-
     if (MODE != S_LSE) {
       for (int c = tid; c < CP; c += 256) {
         float scale = 1.f, shift = 0.f;
@@ -183,13 +145,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(pw_stream_m
     for (int j = 0; j < KQ; ++j) { sc[j] = (MODE != S_LSE) ? s_sc[c_lo + j] : 1.f; sh[j] = (MODE != S_LSE) ? s_sh[c_lo + j] : 0.f; }
   };
   if (!kVec) fill_scale_shift();
-  h8 wh[kSplit ? NT : 1][NS], wl[kSplit ? NT : 1][NS];   // kSplit: the weight fragments as fp16 pairs (wf is dead after this)
-  if (kSplit) {
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-      for (int u = 0; u < NS; ++u) split8(&wf[t][8 * u], wh[t][u], wl[t][u]);
-  }
   // vector mode: the chunk lies inside one segment
   const int C0 = p.seg[0].C;
   const bool in_seg1 = (MODE == S_VEC) && (p.nseg > 1) && (c_lo >= C0);
@@ -284,16 +239,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(pw_stream_m
   // HBM/L2 latency with the few waves a CU holds.  Tiles are therefore processed in GROUPS of D: first the
   // gather indices of all D tiles, then all their row loads (D independent vector loads in flight per
   // lane), then the D MFMA + epilogue passes.  D shrinks as the per-tile register footprint grows.
-  constexpr bool kAtt = (EPI == EPI_ATT || EPI == EPI_ATT2);
-  constexpr int D = kAtt ? (NT == 1 ? 4 : 1) : (KQ * NT <= 4 ? 8 : (KQ * NT <= 16 ? 4 : (KQ * NT <= 32 ? 2 : 1)));
-  constexpr int GA = EPI == EPI_ATT2 ? D : 1, GN_ = EPI == EPI_ATT2 ? NT : 1, GF_ = EPI == EPI_ATT2 ? NT / 2 : 1;
+  constexpr int D = KQ * NT <= 4 ? 8 : (KQ * NT <= 16 ? 4 : (KQ * NT <= 32 ? 2 : 1));
   // Two groups are alive at a time (ping-pong): the loads of group g+1 are issued before group g is computed,
   // so index -> row -> use latencies overlap with MFMA / epilogue work even at one wave per SIMD.
   struct Group {
     int srow[D];
     Chunk<KQ> buf[D];
-    float gpre_all[GA][GN_][4], fpre_all[GA][GF_][4];
-    int gi_all[GA][4];
   };
   // Vector mode issues every load unconditionally on CLAMPED tile / row indices (a group past the end re-reads the
   // last tile; its results are never used): straight-line code, no exec-mask or scalar branches between the loads,
@@ -301,42 +252,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(pw_stream_m
   auto issue_group = [&](Group& G, int tile0) {
     int (&srow)[D] = G.srow;
     Chunk<KQ> (&buf)[D] = G.buf;
-    float (&gpre_all)[GA][GN_][4] = G.gpre_all;
-    float (&fpre_all)[GA][GF_][4] = G.fpre_all;
-    int (&gi_all)[GA][4] = G.gi_all;
 #pragma unroll
     for (int d = 0; d < D; ++d) {
       const int tl = tile0 + d * nwaves;
-      const int tlc = min(tl, ntiles - 1);
-      srow[d] = kVec ? tile_srow(tlc) : (tl < ntiles ? tile_srow(tl) : 0);
-      if (EPI == EPI_ATT2) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          gi_all[d][r] = ld_i32(p.fseg.idx + cloud * p.fseg.idx_cloud_stride, 4u * (uint32_t)min(tlc * 16 + 4 * fq + r, p.M - 1));
-      }
+      srow[d] = kVec ? tile_srow(min(tl, ntiles - 1)) : (tl < ntiles ? tile_srow(tl) : 0);
     }
 #pragma unroll
     for (int d = 0; d < D; ++d) {
       const int tl = tile0 + d * nwaves;
       if (kVec) load_tile(min(tl, ntiles - 1), srow[d], buf[d]);
       else if (tl < ntiles) load_tile(tl, srow[d], buf[d]);
-      if (EPI == EPI_ATT2) {
-        // the gathered rows of G = W1 f (added to the scores; all NT tiles) and of f (pooled operand; the first
-        // NT/2 tiles) for this lane's 4 rows
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float* gp = p.g + cloud * p.g_cloud_stride;                 // wave-uniform bases
-          const float* fp = p.fseg.x + cloud * p.fseg.cloud_stride;
-          // G is stored in this kernel's order (weights.hip, up_fc_g): the block's column of lane fr in tiles 0..3 is one float4
-          const uint32_t go = 4u * ((uint32_t)gi_all[d][r] * (uint32_t)p.Cout + (uint32_t)(n0 + 4 * fr));
-          const uint32_t fo = 4u * ((uint32_t)gi_all[d][r] * (uint32_t)p.fseg.ld + (uint32_t)fr);
-          static_assert(EPI != EPI_ATT2 || NT == 4, "one float4 of G per gathered row");
-          const float4 g4 = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(gp) + go);
-          gpre_all[d][0][r] = g4.x; gpre_all[d][1 % GN_][r] = g4.y; gpre_all[d][2 % GN_][r] = g4.z; gpre_all[d][3 % GN_][r] = g4.w;
-#pragma unroll
-          for (int t = 0; t < NT / 2; ++t) fpre_all[d][t][r] = ld_f32(fp + col0_of(t), fo);
-        }
-      }
     }
   };
   auto compute_group = [&](Group& G, int tile0) {
@@ -346,42 +271,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(pw_stream_m
     if (tile < ntiles) {
     Chunk<KQ>& cur = G.buf[d];
     finish_tile(tile, cur);
-    float (&gpre)[GN_][4] = G.gpre_all[EPI == EPI_ATT2 ? d : 0];
-    float (&fpre)[GF_][4] = G.fpre_all[EPI == EPI_ATT2 ? d : 0];
     const int rbase = tile * 16 + 4 * fq;   // C layout: col = lane & 15, row = 4 * (lane >> 4) + reg
 
     f32x4 acc[NT];
-    // cached enc-half scores: C fragments of tile `tile`, column tiles n0/16 .. n0/16 + NT
-    float4* s2p = (SC != 0) ? reinterpret_cast<float4*>(p.s2 + cloud * p.s2_cloud_stride) +
-                                  ((int64_t)tile * (p.Cout >> 4) + (n0 >> 4)) * 64 + lane
-                            : nullptr;
-    if (SC == 2) {
 #pragma unroll
-      for (int t = 0; t < NT; ++t) { const float4 v = s2p[t * 64]; acc[t] = f32x4{v.x, v.y, v.z, v.w}; }
-    } else {
+    for (int t = 0; t < NT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int t = 0; t < NT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (kSplit) {
+    for (int s = 0; s < KQ; ++s)
 #pragma unroll
-        for (int u = 0; u < NS; ++u) {
-          h8 ah, al;
-          split8(&cur.v[8 * u], ah, al);
-#pragma unroll
-          for (int t = 0; t < NT; ++t) {
-            mma3(acc[t], ah, al, wh[t][u], wl[t][u]);
-          }
-        }
-      } else {
-#pragma unroll
-        for (int s = 0; s < KQ; ++s)
-#pragma unroll
-          for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(cur.v[s], wf[t][s], acc[t], 0, 0, 0);
-      }
-      if (SC == 1) {
-#pragma unroll
-        for (int t = 0; t < NT; ++t) s2p[t * 64] = make_float4(acc[t][0], acc[t][1], acc[t][2], acc[t][3]);
-      }
-    }
+      for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(cur.v[s], wf[t][s], acc[t], 0, 0, 0);
 
     if (EPI == EPI_GN) {
       float* Y = p.Y + cloud * p.y_cloud_stride;
@@ -442,59 +340,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(pw_stream_m
           }
         }
       }
-    } else if (EPI == EPI_ATT) {
-      // the tile's 16 rows are the 16 neighbours of point `tile` (RandLANet.py:152-155).
-      // f[row][col] (already normalised) is in the A fragments of OTHER lanes: transpose it
-      // through a wave-private LDS tile [16][CP+4] (conflict-free: rows shift by 4 banks).
-      // Requires gridDim.y == 1 (Cout == Cin <= 64), which launch_pw_stream guarantees.
-      float* Y = p.Y + cloud * p.y_cloud_stride;
-      float* T = &s_att[w * 16 * (CP + 4)];
-#pragma unroll
-      for (int j = 0; j < KQ; ++j) T[fr * (CP + 4) + c_lo + j] = cur.v[j];
-      __builtin_amdgcn_wave_barrier();
-#pragma unroll
-      for (int t = 0; t < NT; ++t) {
-        const int col = 16 * t + fr;
-        float f[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) f[r] = T[(4 * fq + r) * (CP + 4) + col];
-        const float o = att_pool_tile(acc[t], f);
-        if (lane < 16 && col < p.Cout) st_f32(Y, 4u * ((uint32_t)tile * (uint32_t)p.ldy + (uint32_t)col), o);
-      }
-      __builtin_amdgcn_wave_barrier();
-    } else if (EPI == EPI_ATT2) {
-      // split attentive pooling: scores = acc (enc half of the contraction) + gathered G rows;
-      // pooled operand = [gathered f (tiles t < NT/2) ; enc (tiles t >= NT/2, from the A fragments via LDS)]
-      float* Y = p.Y + cloud * p.y_cloud_stride;
-      float* T = &s_att[w * 16 * (CP + 4)];
-      const int ch = p.fseg.C;
-      const float fslope = p.fseg.act ? 0.2f : 1.f;
-#pragma unroll
-      for (int j = 0; j < KQ; ++j) T[fr * (CP + 4) + c_lo + j] = cur.v[j];
-      __builtin_amdgcn_wave_barrier();
-      float o[NT];
-#pragma unroll
-      for (int t = 0; t < NT; ++t) {
-        const int col = col0_of(t) + fr;
-        float f[4];
-        f32x4 sc4 = acc[t];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          sc4[r] += gpre[t][r];
-          if (t < NT / 2) {
-            const float v = fmaf(fpre[t < NT / 2 ? t : 0][r], s_fsc[col], s_fsh[col]);
-            f[r] = fmaxf(v, fslope * v);
-          } else {
-            f[r] = T[(4 * fq + r) * (CP + 4) + (col - ch)];
-          }
-        }
-        o[t] = att_pool_tile(sc4, f);
-      }
-      // every lane holds its column's result for all NT tiles: lane group fq stores tile fq -> one full-wave store
-      static_assert(EPI != EPI_ATT2 || NT == 4, "EPI_ATT2 stores one tile per 16-lane group");
-      const float ov = fq == 0 ? o[0] : (fq == 1 ? o[1 % NT] : (fq == 2 ? o[2 % NT] : o[3 % NT]));
-      st_f32(Y, 4u * ((uint32_t)tile * (uint32_t)p.ldy + (uint32_t)(col0_of(fq) + fr)), ov);
-      __builtin_amdgcn_wave_barrier();
     }
     }  // tile < ntiles
     }  // d
@@ -565,7 +410,7 @@ int stream_blocks(int M, int gy, bool big) {
   return blocks < 1 ? 1 : blocks;
 }
 
-template <int KQ, int NT, int EPI, int MODE, int SC = 0>
+template <int KQ, int NT, int EPI, int MODE>
 void launch_s(const GemmArgs& a, hipStream_t st) {
   const int ntiles = (a.M + 15) / 16;
   const int gy = (a.Cout + NT * 16 - 1) / (NT * 16);
@@ -603,7 +448,7 @@ void launch_s(const GemmArgs& a, hipStream_t st) {
   }
   b.grid_x = blocks; b.grid_y = gy;
   dim3 grid((unsigned)((int64_t)blocks * gy * a.clouds));
-  hipLaunchKernelGGL((pw_stream_kernel<KQ, NT, EPI, MODE, SC>), grid, dim3(256), 0, st, b);
+  hipLaunchKernelGGL((pw_stream_kernel<KQ, NT, EPI, MODE>), grid, dim3(256), 0, st, b);
 }
 
 template <int KQ, int NT, int MODE>
@@ -645,6 +490,7 @@ int pw_stream_gn_contributions(int M, int Cout) {
 Launch launch_pw_stream(const GemmArgs& a, hipStream_t st) {
   if (a.M <= 0 || a.clouds <= 0) return Launch::done;
   if (a.c_split > 0) return Launch::not_mine;             // two-layer launches: pw_tile_small_kernel only
+  if (a.epi == EPI_ATT || a.epi == EPI_ATT2) return Launch::not_mine;   // attentive pooling: att_pool.hip, pw_tile.hip, pw_gemm.hip
   if (a.amode == A_LSE) {
     if (a.epi != EPI_GN) return Launch::not_mine;
     return launch_nt<3, S_LSE>(a, st);
@@ -663,30 +509,8 @@ Launch launch_pw_stream(const GemmArgs& a, hipStream_t st) {
     if (a.Cin != 4 * KQ) continue;
     bool ok = seg_vec_ok(a.seg[0], KQ) && (a.nseg == 1 || (seg_vec_ok(a.seg[1], KQ) && (C0 % KQ) == 0));
     if (!ok) break;
-    if (a.epi == EPI_ATT) {
-      if (KQ == 4 && a.Cout == 16) { launch_s<4, 1, EPI_ATT, S_VEC>(a, st); return Launch::done; }
-      if (KQ == 16 && a.Cout == 64) { launch_s<16, 4, EPI_ATT, S_VEC>(a, st); return Launch::done; }
-      return Launch::not_mine;
-    }
     if (a.epi == EPI_L2NORM) {
       if (KQ == 16 && a.Cout == 64) { launch_s<16, 4, EPI_L2NORM, S_VEC>(a, st); return Launch::done; }
-      return Launch::not_mine;
-    }
-    if (a.epi == EPI_ATT2) {   // A = enc (Cin = d/2), Cout = d
-      if (a.nseg != 1 || a.Cout != 2 * a.Cin || !a.g || !a.fseg.idx) return Launch::not_mine;
-      const int sc = a.s2 ? a.s2_mode : 0;
-      if (KQ == 8) {                                                            // d = 64
-        if (sc == 1) launch_s<8, 4, EPI_ATT2, S_VEC, 1>(a, st);
-        else if (sc == 2) launch_s<8, 4, EPI_ATT2, S_VEC, 2>(a, st);
-        else launch_s<8, 4, EPI_ATT2, S_VEC>(a, st);
-        return Launch::done;
-      }
-      if (KQ == 16) {                                                           // d = 128 (two column blocks)
-        if (sc == 1) launch_s<16, 4, EPI_ATT2, S_VEC, 1>(a, st);
-        else if (sc == 2) launch_s<16, 4, EPI_ATT2, S_VEC, 2>(a, st);
-        else launch_s<16, 4, EPI_ATT2, S_VEC>(a, st);
-        return Launch::done;
-      }
       return Launch::not_mine;
     }
     switch (KQ) {

@@ -69,17 +69,11 @@ int gn_max_contributions(const dsir_cfg& g, int n, int flags) {
 
 namespace {
 
-// A/B switch: DSIR_NO_ATT_POOL = the round-3 EPI_ATT / EPI_ATT2 kernels (pw_stream.hip) for d = 16 / 64 / 128 instead of att_pool.hip
-bool att_pool_enabled() {
-  static const bool off = tuning_flag("DSIR_NO_ATT_POOL");
-  return !off;
-}
-
 // A/B switch: DSIR_NO_LSE_UV = lfa.mlp1 of levels 0 / 1 written to memory as up to round 3 (pw_stream.hip, loader S_LSE) instead of
 // the per-point tables of lse_uv.hip; the tables' consumers are att_pool.hip and pw_stream.hip (loader S_UV) only
 bool lse_uv_enabled() {
   static const bool off = tuning_flag("DSIR_NO_LSE_UV") || tuning_flag("DSIR_NO_STREAM");   // the tables' GEMM consumer is pw_stream.hip alone
-  return !off && att_pool_enabled();
+  return !off;
 }
 
 // ------------------------------------------------------------------ schedule helpers
@@ -289,16 +283,25 @@ struct Sched {
     a.Y = y.p; a.y_cs = (int64_t)n * w.d; a.n = n; a.clouds = clouds;
     return a;
   }
-  // Att_pooling up to (not including) its MLP2D: softmax_k(fc [gather(f); enc]) . [gather(f); enc]
-  // s2 / s2_mode: optional cache of the enc half of the scores (kernels.h, GemmArgs::s2)
+  // Att_pooling up to (not including) its MLP2D: softmax_k(fc [gather(f); enc]) . [gather(f); enc].  One ladder by the level width d:
+  //   16          att_pool.hip, four points per wave
+  //   64, 128     att_pool.hip, unsplit (a walker phase when recording)
+  //   256         pw_tile.hip, EPI_ATT2: the score GEMM split by linearity, after its G GEMM (both walker phases when recording)
+  //   otherwise, or when the width's own kernel refuses the layer: the general EPI_ATT kernel (pw_gemm.hip)
+  // s2 / s2_mode: the cache of the enc half of the scores (kernels.h, GemmArgs::s2), kept by the widths of att_keeps_score_cache()
   Act att(const AttW& w, const Act& f, const Act& enc, const int32_t* neigh, int64_t neigh_cs, int n, float* s2 = nullptr,
           int s2_mode = 0) {
     Act y;
     y.p = c->ws.get<float>((size_t)clouds * n * w.d);
     y.C = w.d; y.rows = n;
-    static const bool no_att2 = tuning_flag("DSIR_NO_ATT2");   // A/B switch
-    if (att_pool_enabled() && (w.d == 64 || w.d == 128) && f.C * 2 == w.d && enc.C * 2 == w.d && (enc.p || w.d == 64) && c->dweights16 && w.fc >= c->dweights && w.fc < c->dweights + c->nweights &&
-        !(s2 && s2_mode)) {
+    const bool halves = f.C * 2 == w.d && enc.C * 2 == w.d;
+    const bool fc16 = c->dweights16 && w.fc >= c->dweights && w.fc < c->dweights + c->nweights;   // att_pool.hip reads fc as its fp16 split
+    if (w.d == 16 && halves && fc16) {
+      // att_pool.hip, level 0: four points per wave, fp16-split scores, softmax in registers
+      const AttPool16Args a = att_pool_args(w, f, enc, neigh, neigh_cs, n, y);
+      rec_flush();
+      if (!c->ws.overflow && launch_att_pool16(a, st)) return y;
+    } else if ((w.d == 64 || w.d == 128) && halves && fc16 && (enc.p || w.d == 64)) {
       // att_pool.hip, levels 1 / 2 unsplit: the whole score contraction on the matrix pipe, nothing gathered in the epilogue
       const AttPool16Args a = att_pool_args(w, f, enc, neigh, neigh_cs, n, y);
       if (c->ws.overflow) return y;
@@ -308,12 +311,7 @@ struct Sched {
         rec_flush();
       }
       if (launch_att_full(a, w.d / 2, st)) return y;
-    }
-    if (!enc.p && w.d >= 64) {     // table-only rows have no other consumer (lse_uv_enabled() excludes this)
-      refuse("attentive pooling: no kernel took the table-only position encoding");
-      return y;
-    }
-    if (!no_att2 && w.d >= 64 && w.fc_g && f.C * 2 == w.d && enc.C * 2 == w.d) {   // d = 16: the extra gathers cost more than the MFMAs saved
+    } else if (att_keeps_score_cache(w.d) && w.fc_g && halves && enc.p) {
       // score GEMM split by linearity: fc [gather(f); enc] = gather(W1 f) + W2 enc  (kernels.h, EPI_ATT2).
       // G = W1 f runs on n rows instead of 16 n; the pooling launch contracts only the enc half.
       float* G = c->ws.get<float>((size_t)clouds * n * w.d);
@@ -331,21 +329,14 @@ struct Sched {
       a2.g = G; a2.g_cloud_stride = (int64_t)n * w.d; a2.fseg = seg_of(f, neigh, neigh_cs);
       a2.s2 = s2; a2.s2_mode = s2 ? s2_mode : 0; a2.s2_cloud_stride = (int64_t)n * kKnn * w.d;
       split_of(a2);
-      // G's column order is the consumer's (up_fc_g): d <= 128 belongs to pw_stream.hip, d = 256 to pw_tile.hip
-      if (rec && w.d > 128) {
+      if (rec) {
         WalkJob j;
         if (walk_plan_gemm(a2, &j) && rec_push(j)) return y;
       }
       rec_flush();
-      if (w.d <= 128 ? launch_pw_stream(a2, st) == Launch::done : launch_pw_tile(a2, st)) return y;
+      if (launch_pw_tile(a2, st)) return y;
     }
-    if (att_pool_enabled() && w.d == 16 && f.C == 8 && enc.C == 8 && c->dweights16 && w.fc >= c->dweights && w.fc < c->dweights + c->nweights) {
-      // att_pool.hip, level 0: four points per wave, fp16-split scores, softmax in registers
-      const AttPool16Args a = att_pool_args(w, f, enc, neigh, neigh_cs, n, y);
-      rec_flush();
-      if (!c->ws.overflow && launch_att_pool16(a, st)) return y;
-    }
-    if (!enc.p) {     // table-only rows have no other consumer (lse_uv_enabled() excludes this)
+    if (!enc.p) {     // table-only rows (lse_uv.hip) have no consumer but att_pool.hip
       refuse("attentive pooling: no kernel took the table-only position encoding");
       return y;
     }
@@ -415,14 +406,7 @@ int EncCache::plan(dsir_ctx* c, const Pyramid& ps, double* prezeroed) {
     }
     enc2_buf[l] = ws.get<float>(rows * ch);
     static const bool no_s2 = tuning_flag("DSIR_NO_S2");   // A/B switch: recompute the enc half of the scores every iteration
-    // level 1 (d = 64: a 32-channel contraction) caches its score halves only for a few pairs in flight: with the chip full
-    // re-reading 64 floats per row costs more HBM time than contracting 32 (same bits either way; +1.9 % pairs/s at 128
-    // pairs per launch, -0.02 ms of single-pair latency with the cache)
-    static const int s2_min_d = (int)tuning_int("DSIR_S2_MIN_D", 0);   // tuning hook: 0 = by launch size
-    // round 3: with the score contraction on the fp16 pipe, re-reading level 2's halves (2 x 5000 x 128 floats per cloud) also
-    // costs more than contracting them when the chip is full: only level 3 keeps its cache there (+0.7 % pairs/s; 64: -0.7 %)
-    const int min_d = s2_min_d > 0 ? s2_min_d : ((P <= 4 && !att_pool_enabled()) ? 64 : 256);   // att_pool.hip (d = 64, 128) keeps no score cache
-    if (g.d_out[l] >= 64 && g.d_out[l] >= min_d && !no_s2) {
+    if (att_keeps_score_cache(g.d_out[l]) && !no_s2) {
       s2_buf[l][0] = ws.get<float>(rows * (size_t)g.d_out[l]);
       s2_buf[l][1] = ws.get<float>(rows * (size_t)g.d_out[l]);
     }

@@ -145,8 +145,9 @@ LinW bind_lin(const float* base, const LinOff& o) { LinW l; l.W = base + o.W; l.
 // the gathered G values of its column in each of the block's four 16-column tiles.  W1 = fc[:, :d/2] is therefore uploaded
 // a second time with its rows permuted so that those four values are adjacent: G' column 64 b + 4 fr + t = the column of
 // tile t, lane fr of block b - one 16-byte gather instead of four 4-byte ones.  Which columns form tile t of block b is
-// the consumer's mapping: pw_stream.hip (d = 64, 128) pairs 32 columns of the gathered half with the matching 32 of the
-// enc half, pw_tile.hip (d = 256) takes 64 consecutive columns.
+// the consumer's mapping: pw_tile.hip (d = 256, the one width Sched::att pools this way: att_keeps_score_cache) takes 64
+// consecutive columns.  d = 64 and 128 are still uploaded, in the 32 + 32 pairing of a row-streaming kernel that no longer exists:
+// nothing reads them (att_pool.hip pools those levels unsplit), they only keep the blob's layout as it was.
 size_t up_fc_g(Uploader& u, const HostParam& fc, int d) {
   if (d < 64) return 0;
   const int h = d / 2;
