@@ -62,6 +62,11 @@ class dsir_consensus_diag(C.Structure):
                 ("seed_valid", C.c_void_p), ("seed_count", C.c_void_p)]
 
 
+class dsir_fgr_diag(C.Structure):
+    _fields_ = [("rows", C.c_void_p), ("n_rows", C.c_void_p), ("trials", C.c_void_p), ("norm", C.c_void_p), ("iter_T", C.c_void_p),
+                ("iter_mu", C.c_void_p), ("iter_energy", C.c_void_p), ("iters_run", C.c_void_p)]
+
+
 class dsir_cloud_out(C.Structure):
     _fields_ = [
         ("xyz", C.c_void_p), ("feat", C.c_void_p), ("logits", C.c_void_p), ("score", C.c_void_p), ("label", C.c_void_p),
@@ -119,6 +124,9 @@ SYMBOLS = {
     "dsir_consensus_correspondence": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                 C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_void_p, C.POINTER(dsir_consensus_diag)]),
+    "dsir_fgr_correspondence": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                          C.c_int, C.c_float, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_uint64,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(dsir_fgr_diag)]),
     "dsir_feature_correspondences": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                                C.c_void_p]),
     "dsir_pose_finetune": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_float,

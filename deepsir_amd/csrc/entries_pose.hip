@@ -1,4 +1,4 @@
-// The pose entries of include/dsir.h: weighted Kabsch, ICP, RANSAC and spatial consensus from correspondences, the pose
+// The pose entries of include/dsir.h: weighted Kabsch, ICP, RANSAC, spatial consensus and FGR from correspondences, the pose
 // fine-tune, the alignment loss with its backward, and the evaluation metrics.
 #include <cmath>
 
@@ -160,6 +160,51 @@ int dsir_consensus_correspondence(dsir_ctx* c, const float* points_src, const fl
     a.diag_T = diag->seed_T; a.diag_valid = diag->seed_valid; a.diag_count = diag->seed_count;
   }
   if (int r = launch_consensus(a, scratch, c->stream)) return fail(c, "dsir_consensus_correspondence: launch failed (%d)", r);
+  return call.finish();
+}
+
+int dsir_fgr_correspondence(dsir_ctx* c, const float* points_src, const float* points_ref, int pairs, int J, int K, int stride,
+                            const int32_t* corr, const int32_t* counts, int M, float max_dist, int tuple_test, float tuple_scale,
+                            int max_tuples, int max_trials, int iterations, float division_factor, int refine_iters, uint64_t seed,
+                            const float* T_init, float* T_out, double* stats, int32_t* invalid, const dsir_fgr_diag* diag) {
+  Call call(c); if (call.refused()) return 1;
+  if (!points_src || !points_ref || !corr || !T_out || !stats || !invalid || pairs < 1 || J < 1 || K < 1 || M < 1 || stride < 3 ||
+      !(max_dist > 0.f) || !std::isfinite(max_dist))
+    return fail(c, "dsir_fgr_correspondence: bad arguments");
+  if (!(tuple_scale > 0.f) || !(tuple_scale <= 1.f))
+    return fail(c, "dsir_fgr_correspondence: tuple_scale=%g outside (0,1]", (double)tuple_scale);
+  if (max_tuples < 1 || max_tuples > DSIR_FGR_MAX_TUPLES)
+    return fail(c, "dsir_fgr_correspondence: max_tuples=%d outside [1,%d]", max_tuples, DSIR_FGR_MAX_TUPLES);
+  if (max_trials < 1 || max_trials > DSIR_FGR_MAX_TRIALS)
+    return fail(c, "dsir_fgr_correspondence: max_trials=%d outside [1,%d]", max_trials, DSIR_FGR_MAX_TRIALS);
+  if (iterations < 1 || iterations > DSIR_FGR_MAX_ITERS)
+    return fail(c, "dsir_fgr_correspondence: iterations=%d outside [1,%d]", iterations, DSIR_FGR_MAX_ITERS);
+  if (!std::isfinite(division_factor)) return fail(c, "dsir_fgr_correspondence: division_factor must be finite");
+  if (refine_iters < 0 || refine_iters > DSIR_RANSAC_MAX_REFINE)
+    return fail(c, "dsir_fgr_correspondence: refine_iters=%d outside [0,%d]", refine_iters, DSIR_RANSAC_MAX_REFINE);
+  if (M > c->cfg.max_points || J > c->cfg.max_points || K > c->cfg.max_points)
+    return fail(c, "dsir_fgr_correspondence: M=%d, J=%d or K=%d beyond max_points=%d", M, J, K, c->cfg.max_points);
+  if (pairs > 65535 || (int64_t)pairs * ((int64_t)max_trials + 256) > 0x7fffffffll || (int64_t)pairs * M > 0x7fffffffll)
+    return fail(c, "dsir_fgr_correspondence: pairs=%d with max_trials=%d and M=%d unsupported (pairs <= 65535, pairs x max_trials and "
+                   "pairs x M below 2^31)", pairs, max_trials, M);
+  // the whole workspace, validated before the first launch
+  const size_t need = fgr_scratch_bytes(pairs, M, tuple_test ? 1 : 0, max_tuples, max_trials, refine_iters);
+  if (need > c->ws.cap)
+    return fail(c, "workspace too small for dsir_fgr_correspondence: needs %zu bytes (pairs x (M x 28 + rows x 52)-order, rows = %s), "
+                   "the arena holds %zu (raise max_points / max_pairs, or pass fewer pairs or a smaller max_tuples)", need,
+                tuple_test ? "3 x max_tuples" : "M", c->ws.cap);
+  void* scratch = c->ws.raw(need);
+  if (c->ws.overflow) return fail(c, "workspace too small for dsir_fgr_correspondence");
+  FgrArgs a{};
+  a.src = points_src; a.ref = points_ref; a.pairs = pairs; a.J = J; a.K = K; a.stride = stride; a.corr = corr; a.counts = counts;
+  a.M = M; a.max_dist = max_dist; a.tuple_test = tuple_test ? 1 : 0; a.ts2 = tuple_scale * tuple_scale;   // fp32, rounded once
+  a.max_tuples = max_tuples; a.max_trials = max_trials; a.iterations = iterations; a.division_factor = division_factor;
+  a.refine_iters = refine_iters; a.seed = seed; a.T_init = T_init; a.T_out = T_out; a.stats = stats; a.invalid = invalid;
+  if (diag) {
+    a.diag_rows = diag->rows; a.diag_n_rows = diag->n_rows; a.diag_trials = diag->trials; a.diag_norm = diag->norm;
+    a.diag_iter_T = diag->iter_T; a.diag_iter_mu = diag->iter_mu; a.diag_iter_energy = diag->iter_energy; a.diag_iters_run = diag->iters_run;
+  }
+  if (int r = launch_fgr(a, scratch, c->stream)) return fail(c, "dsir_fgr_correspondence: launch failed (%d)", r);
   return call.finish();
 }
 

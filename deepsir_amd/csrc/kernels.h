@@ -584,6 +584,24 @@ struct ConsensusArgs {
 size_t consensus_scratch_bytes(int pairs, int M, int seeds, int refine_iters);
 int launch_consensus(const ConsensusArgs& a, void* scratch, hipStream_t st);
 
+// fgr.hip — fast global registration pose from correspondences (tuple pre-filter, graduated Gauss-Newton; the rule is stated in the
+// file's header), all pairs at once; returns 0 on success
+struct FgrArgs {
+  const float* src; const float* ref;   // [pairs][J][stride], [pairs][K][stride]
+  int pairs, J, K, stride;
+  const int32_t* corr;                  // [pairs][M][2]
+  const int32_t* counts;                // [pairs] or nullptr
+  int M;
+  float max_dist; int tuple_test; float ts2; int max_tuples, max_trials, iterations; float division_factor; int refine_iters;
+  uint64_t seed;
+  const float* T_init;                  // [pairs][3][4] or nullptr (identity)
+  float* T_out; double* stats; int32_t* invalid;
+  int32_t* diag_rows; int32_t* diag_n_rows; int32_t* diag_trials; double* diag_norm;   // optional
+  double* diag_iter_T; double* diag_iter_mu; double* diag_iter_energy; int32_t* diag_iters_run;
+};
+size_t fgr_scratch_bytes(int pairs, int M, int tuple_test, int max_tuples, int max_trials, int refine_iters);
+int launch_fgr(const FgrArgs& a, void* scratch, hipStream_t st);
+
 // finetune.hip — Adam fine-tune of the pose on matched points (test.py:159-207), one workgroup per pair
 void launch_pose_finetune(const float* src, const float* ref, const float* w, int sigmoid, int pairs, int m, const float* T_init,
                           float quant, int max_iter, float break_ratio, int max_break, float* T_out, double* stats,

@@ -791,6 +791,55 @@ class Engine:
         self.sync()
         return (T, stats, invalid, d) if diag else (T, stats, invalid)
 
+    FGR_MAX_TUPLES = 65536             # DSIR_FGR_MAX_TUPLES
+    FGR_MAX_TRIALS = 1 << 22           # DSIR_FGR_MAX_TRIALS
+    FGR_MAX_ITERS = 1024               # DSIR_FGR_MAX_ITERS
+
+    def fgr_correspondence(self, points_src, points_ref, corr, max_dist: float, counts=None, tuple_test: bool = True,
+                           tuple_scale: float = 0.95, max_tuples: int = 1000, max_trials: int = 1 << 20, iterations: int = 64,
+                           division_factor: float = 1.4, refine_iters: int = 2, seed: int = 0, T_init=None, diag: bool = False):
+        """Fast global registration pose for P pairs (open3d registration_fgr_based_on_feature_matching's estimator on an explicit
+        correspondence list; parity unpinned, the rule is stated in csrc/fgr.hip and restated in deepsir_amd/fgr.py): a tuple
+        pre-filter, then ``iterations`` Gauss-Newton steps under a graduated robust weight - no hypotheses, no quadratic memory.
+        Arguments and results as ransac_correspondence.
+        -> (T [P,3,4], stats [P,5] f64: fitness, inlier_rmse, 0 or -1 (no pose), 1 or 0, inliers; invalid [P] i32) and, with
+        diag=True, a dict of rows [P,L] i32 (L = 3 max_tuples, or M without the tuple test; -1 padded), n_rows [P], trials [P],
+        norm [P,8] f64 (ms, mq, scale), iter_T [P,iterations,3,4] f64, iter_mu / iter_energy [P,iterations] f64, iters_run [P]."""
+        points_src, points_ref = _chk(points_src, torch.float32, "points_src"), _chk(points_ref, torch.float32, "points_ref")
+        corr = _chk(corr, torch.int32, "corr")
+        P, J, stride = points_src.shape
+        K, M = points_ref.shape[1], corr.shape[1]
+        if points_ref.shape[0] != P or points_ref.shape[2] != stride or tuple(corr.shape) != (P, M, 2):
+            raise EngineError("fgr_correspondence: points_* must be [P,N,stride] and corr [P,M,2]")
+        if counts is not None:
+            counts = _chk(counts, torch.int32, "counts")
+            if tuple(counts.shape) != (P,):
+                raise EngineError("fgr_correspondence: counts must be [P]")
+        if T_init is not None:
+            T_init = _chk(T_init, torch.float32, "T_init")
+            if tuple(T_init.shape) != (P, 3, 4):
+                raise EngineError("fgr_correspondence: T_init must be [P,3,4]")
+        T = self._empty((P, 3, 4))
+        stats = self._empty((P, 5), torch.float64)
+        invalid = self._empty((P,), torch.int32)
+        d, dref = None, None
+        if diag:
+            L = 3 * min(max(int(max_tuples), 1), self.FGR_MAX_TUPLES) if tuple_test else M
+            It = min(max(int(iterations), 1), self.FGR_MAX_ITERS)
+            d = {"rows": self._empty((P, L), torch.int32), "n_rows": self._empty((P,), torch.int32),
+                 "trials": self._empty((P,), torch.int32), "norm": self._empty((P, 8), torch.float64),
+                 "iter_T": self._empty((P, It, 3, 4), torch.float64), "iter_mu": self._empty((P, It), torch.float64),
+                 "iter_energy": self._empty((P, It), torch.float64), "iters_run": self._empty((P,), torch.int32)}
+            dref = C.byref(_lib.dsir_fgr_diag(*[_ptr(d[k]) for k in ("rows", "n_rows", "trials", "norm", "iter_T", "iter_mu",
+                                                                      "iter_energy", "iters_run")]))
+        self._pre()
+        self._call(self.lib.dsir_fgr_correspondence(self.h, _ptr(points_src), _ptr(points_ref), P, J, K, stride, _ptr(corr), _ptr(counts),
+                                                    M, float(max_dist), 1 if tuple_test else 0, float(tuple_scale), int(max_tuples),
+                                                    int(max_trials), int(iterations), float(division_factor), int(refine_iters),
+                                                    int(seed) & ((1 << 64) - 1), _ptr(T_init), _ptr(T), _ptr(stats), _ptr(invalid), dref))
+        self.sync()
+        return (T, stats, invalid, d) if diag else (T, stats, invalid)
+
     def feature_correspondences(self, desc_src, desc_ref, mutual: bool = True, k: int = 1, ratio: float = 0.0, with_dist: bool = False):
         """The correspondence set of open3d's registration_ransac_based_on_feature_matching (reference network/DGR.py:7-24),
         made explicit: exact descriptor arg-min src -> ref (nn_match), kept where the ref -> src arg-min points back (mutual),

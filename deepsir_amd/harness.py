@@ -36,6 +36,7 @@ def inference_align(pairs: Sequence[Dict[str, np.ndarray]], model, num_reg_iter:
     ``icp_search`` is ``Engine.icp_refine``'s ``search`` ("auto": the cell index on large clouds; the poses are the same bytes).
     ``pose_opt='ransac'``: DGR's safeguard (network/DGR.py:249-306) over the last iteration's correspondences, see below;
     ``pose_opt='consensus'``: the same correspondences through ``consensus_correspondence`` instead of the seeded sampling;
+    ``pose_opt='fgr'``: through ``fgr_correspondence`` (fast global registration; ``ransac_seed`` keys its tuple draws);
     ``safeguard_wsum``: only pairs whose summed sigmoid inlier weight is below it take the RANSAC pose (DGR.py:273-304).
     Returns (pred_transforms_all [n_pairs, n_iter+1, 3, 4], stats [n_pairs, 5]) gathered over ranks."""
     device = device or torch.device("cuda", torch.cuda.current_device())
@@ -104,7 +105,7 @@ def inference_align(pairs: Sequence[Dict[str, np.ndarray]], model, num_reg_iter:
                                                    transforms[-1].contiguous(), weights=endpoints["perm_matrices"][-1],
                                                    weights_are_logits=True, quantization_size=2.0 * voxel_size)
             transforms.append(T_opt)
-        elif pose_opt in ("ransac", "consensus"):
+        elif pose_opt in ("ransac", "consensus", "fgr"):
             # DGR.safeguard_registration (network/DGR.py:249-306): RANSAC over the last iteration's correspondences (row i of pt_src
             # with row i of pt_ref_new), threshold 2 x voxel size, DGR's 80 000 hypotheses by default; with safeguard_wsum only the
             # pairs whose inlier network assigned less total weight than that take it, the others keep the network's pose
@@ -115,6 +116,8 @@ def inference_align(pairs: Sequence[Dict[str, np.ndarray]], model, num_reg_iter:
             if pose_opt == "ransac":
                 T_opt, _, _ = _aux_engine(model, data).ransac_correspondence(xs, xr, corr, 2.0 * voxel_size, hypotheses=ransac_hypotheses,
                                                                              seed=ransac_seed, T_init=T_net)
+            elif pose_opt == "fgr":   # the same correspondences through fast global registration (csrc/fgr.hip); the seed keys its tuples
+                T_opt, _, _ = _aux_engine(model, data).fgr_correspondence(xs, xr, corr, 2.0 * voxel_size, seed=ransac_seed, T_init=T_net)
             else:             # the same correspondences through the spatial-consensus stage (csrc/consensus.hip): no sampling, no seed
                 T_opt, _, _ = _aux_engine(model, data).consensus_correspondence(xs, xr, corr, 2.0 * voxel_size, T_init=T_net)
             if safeguard_wsum is not None:
@@ -124,7 +127,7 @@ def inference_align(pairs: Sequence[Dict[str, np.ndarray]], model, num_reg_iter:
         elif pose_opt is None:
             transforms.append(transforms[-1].detach())        # pose_optimization == identity (test.py:215-216, :406-408)
         else:
-            raise ValueError("pose_opt must be None, 'icp', 'icp_plane', 'tune', 'ransac' or 'consensus'")
+            raise ValueError("pose_opt must be None, 'icp', 'icp_plane', 'tune', 'ransac', 'consensus' or 'fgr'")
         T = torch.stack(transforms, dim=1).cpu().numpy()      # [B, n_iter+1, 3, 4]
         preds.append(T)
         gt = data["transform_gt"].cpu().numpy()
@@ -315,26 +318,34 @@ def inference_feat(pairs: Sequence[Dict[str, np.ndarray]], model, batch: int = 1
     return out, total
 
 
-def _pose_from_corr(eng, pose, xs, xr, corr, counts, max_dist, ransac_n, edge_sim, hypotheses, refine_iters, seed, seeds, members):
-    """The pose stage of ``register_feat`` / ``register_fpfh``: 'ransac' (seeded sampling) or 'consensus' (spatial compatibility)."""
+def _pose_from_corr(eng, pose, xs, xr, corr, counts, max_dist, ransac_n, edge_sim, hypotheses, refine_iters, seed, seeds, members,
+                    fgr_iterations=64, tuple_scale=0.95, max_tuples=1000, tuple_test=True):
+    """The pose stage of ``register_feat`` / ``register_fpfh``: 'ransac' (seeded sampling), 'consensus' (spatial compatibility) or
+    'fgr' (fast global registration: tuple pre-filter and graduated Gauss-Newton)."""
     if pose == "ransac":
         return eng.ransac_correspondence(xs, xr, corr, max_dist, counts=counts, ransac_n=ransac_n, edge_sim=edge_sim,
                                          hypotheses=hypotheses, refine_iters=refine_iters, seed=seed)[0]
     if pose == "consensus":
         return eng.consensus_correspondence(xs, xr, corr, max_dist, counts=counts, seeds=seeds, members=members,
                                             refine_iters=refine_iters)[0]
-    raise ValueError("pose must be 'ransac' or 'consensus'")
+    if pose == "fgr":
+        return eng.fgr_correspondence(xs, xr, corr, max_dist, counts=counts, tuple_test=tuple_test, tuple_scale=tuple_scale,
+                                      max_tuples=max_tuples, iterations=fgr_iterations, refine_iters=refine_iters, seed=seed)[0]
+    raise ValueError("pose must be 'ransac', 'consensus' or 'fgr'")
 
 
 @torch.no_grad()
 def register_feat(pairs: Sequence[Dict[str, np.ndarray]], model, voxel_size: float = 0.3, hypotheses: int = 8192, mutual: bool = True,
                   num_reg: int = 1, dataset_type: str = "3DMatch", batch: int = 1, device: Optional[torch.device] = None,
                   ransac_n: int = 3, edge_sim: float = 0.9, refine_iters: int = 2, seed: int = 0, pose: str = "ransac",
-                  seeds: int = 64, members: int = 32, match_k: int = 1, match_ratio: float = 0.0):
+                  seeds: int = 64, members: int = 32, match_k: int = 1, match_ratio: float = 0.0, fgr_iterations: int = 64,
+                  tuple_scale: float = 0.95, max_tuples: int = 1000, tuple_test: bool = True):
     """The 'feat' pipeline as a registration (what the reference reaches through open3d's
     registration_ransac_based_on_feature_matching, network/DGR.py:7-24, test.py:259-263): forward_pair -> key points and
     descriptors -> (mutual) nearest-neighbour correspondences -> RANSAC pose (threshold 2 x voxel size), all on the device.
     ``pose='consensus'``: the pose from ``consensus_correspondence`` (``seeds``, ``members``; no sampling, no seed) instead.
+    ``pose='fgr'``: the pose from ``fgr_correspondence`` (``fgr_iterations``, ``tuple_scale``, ``max_tuples``, ``tuple_test``; ``seed``
+    keys its tuple draws) instead.
     ``match_k`` > 1: the k nearest descriptors of every src point as candidates (M = J x match_k rows for the pose stage);
     ``match_ratio`` in (0, 1): Lowe's ratio test on the 1-NN set (``Engine.feature_correspondences``).
     Returns (pred_transforms [n_pairs, num_reg, 3, 4] - the one pose repeated ``num_reg`` times, so that the result has
@@ -351,7 +362,7 @@ def register_feat(pairs: Sequence[Dict[str, np.ndarray]], model, voxel_size: flo
         corr, counts = eng.feature_correspondences(ep["feat_src"].permute(0, 2, 1).contiguous(), ep["feat_ref"].permute(0, 2, 1).contiguous(),
                                                    mutual=mutual, k=match_k, ratio=match_ratio)
         T = _pose_from_corr(eng, pose, xs, xr, corr, counts, 2.0 * voxel_size, ransac_n, edge_sim, hypotheses, refine_iters, seed, seeds,
-                            members)
+                            members, fgr_iterations, tuple_scale, max_tuples, tuple_test)
         torch.cuda.synchronize(device)
         dt = (time.time() - t0) / len(ids)
         T = T.cpu().numpy()
@@ -411,13 +422,15 @@ def register_fpfh(pairs: Sequence[Dict[str, np.ndarray]], engine, voxel_size: fl
                   device: Optional[torch.device] = None, ransac_n: int = 3, edge_sim: float = 0.9, refine_iters: int = 2, seed: int = 0,
                   want_corr: bool = False, pose: str = "ransac", seeds: int = 64, members: int = 32, match_k: int = 1,
                   match_ratio: float = 0.0, search: str = "brute", max_nn: int = 0, normal_radius: Optional[float] = None,
-                  normal_max_nn: int = 0):
+                  normal_max_nn: int = 0, fgr_iterations: int = 64, tuple_scale: float = 0.95, max_tuples: int = 1000,
+                  tuple_test: bool = True):
     """The weight-independent baseline of ``register_feat``: FPFH + feature-matching RANSAC (open3d compute_fpfh_feature ->
     registration_ransac_based_on_feature_matching; parity unpinned, the rules are the engine's own), all on the device.  Per batch
     and side: ``knn_pyramid`` -> ``estimate_normals`` on its level-0 lists (towards the pair's optional ``viewpoint_src`` /
     ``viewpoint_ref`` entry, 3 floats; default the origin) -> ``fpfh`` over those 16-NN lists, or with ``radius`` set over the CSR of
     ``radius_matches(x, x, identity, radius)`` -> ``feature_correspondences(mutual)`` -> ``ransac_correspondence`` (threshold
-    2 x voxel size), or with ``pose='consensus'`` -> ``consensus_correspondence`` (``seeds``, ``members``).  Returns what ``register_feat`` returns - (pred_transforms [n_pairs, num_reg, 3, 4], stats [n_pairs, 5] rows
+    2 x voxel size), or with ``pose='consensus'`` -> ``consensus_correspondence`` (``seeds``, ``members``), or with ``pose='fgr'`` ->
+    ``fgr_correspondence`` (``fgr_iterations``, ``tuple_scale``, ``max_tuples``, ``tuple_test``).  Returns what ``register_feat`` returns - (pred_transforms [n_pairs, num_reg, 3, 4], stats [n_pairs, 5] rows
     ``[succ, rte, rre, time, seq]``) - so ``evaluate_align`` and ``Engine.icp_refine`` take it the same way; with ``want_corr`` a
     third value, per pair the (corr [count, 2], flags_src [J], flags_ref [K]) numpy arrays.  ``match_k`` / ``match_ratio``: k candidate
     matches per src point (M = J x match_k) or Lowe's ratio test, as in ``register_feat``.
@@ -459,7 +472,7 @@ def register_fpfh(pairs: Sequence[Dict[str, np.ndarray]], engine, voxel_size: fl
         dr, fr, _ = _fpfh_side(engine, xr, [view(i, "ref") for i in ids], radius, *nbr)
         corr, counts = engine.feature_correspondences(ds, dr, mutual=mutual, k=match_k, ratio=match_ratio)
         T = _pose_from_corr(engine, pose, xs, xr, corr, counts, 2.0 * voxel_size, ransac_n, edge_sim, hypotheses, refine_iters, seed,
-                            seeds, members)
+                            seeds, members, fgr_iterations, tuple_scale, max_tuples, tuple_test)
         torch.cuda.synchronize(device)
         dt = (time.time() - t0) / len(ids)
         T = T.cpu().numpy()

@@ -34,15 +34,16 @@ def main():
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--limit", type=int, default=0)
-    ap.add_argument("--pose-opt", choices=["none", "icp", "icp_plane", "tune", "ransac", "consensus"], default="none")
+    ap.add_argument("--pose-opt", choices=["none", "icp", "icp_plane", "tune", "ransac", "consensus", "fgr"], default="none")
     ap.add_argument("--icp-search", choices=["brute", "grid", "auto"], default="auto",
                     help="with --pose-opt icp / icp_plane: the nearest-neighbour search of the refinement (same poses, other time)")
     ap.add_argument("--pipeline", choices=["align", "feat"], default="align")
     ap.add_argument("--ransac", action="store_true", help="with --pipeline feat: descriptors -> mutual nearest neighbours -> RANSAC pose")
     ap.add_argument("--num-sub", type=int, default=1024, help="key points per cloud of the feat pipeline")
     ap.add_argument("--hypotheses", type=int, default=8192)
-    ap.add_argument("--pose", choices=["ransac", "consensus"], default="ransac",
-                    help="pose stage of --method fpfh and --pipeline feat: seeded RANSAC or the spatial-consensus stage (no sampling)")
+    ap.add_argument("--pose", choices=["ransac", "consensus", "fgr"], default="ransac",
+                    help="pose stage of --method fpfh and --pipeline feat: seeded RANSAC, the spatial-consensus stage (no sampling) or "
+                         "fast global registration (tuple pre-filter, graduated Gauss-Newton)")
     ap.add_argument("--method", choices=["network", "fpfh"], default="network", help="fpfh: FPFH + RANSAC instead of the network")
     ap.add_argument("--fpfh-radius", type=float, default=None, help="with --method fpfh: radius lists instead of the 16-NN lists")
     ap.add_argument("--fpfh-search", choices=["brute", "grid"], default="brute",

@@ -447,6 +447,46 @@ int dsir_consensus_correspondence(dsir_ctx* ctx, const float* points_src, const 
                                   int seeds, int members, int refine_iters, const float* T_init, float* T_out, double* stats,
                                   int32_t* invalid, const dsir_consensus_diag* diag /* NULL in production */);
 
+/* Fast global registration pose from correspondences (FGR: Zhou, Park, Koltun 2016; open3d's
+ * registration_fgr_based_on_feature_matching): the third estimator behind the boundary of dsir_ransac_correspondence.  No hypotheses
+ * and no quadratic memory: a tuple pre-filter, then `iterations` 6 x 6 Gauss-Newton steps under a graduated robust weight, O(rows x
+ * iterations) per pair - for correspondence counts where consensus is refused for memory and RANSAC needs many hypotheses.
+ * open3d cannot be imported here: parity is UNPINNED, the engine owns the rule, stated once in the header of
+ * deepsir_amd/csrc/fgr.hip (and DESIGN.md section 8) and restated on the host in deepsir_amd/fgr.py.
+ * Same boundary as dsir_ransac_correspondence: points_src, points_ref, corr, counts, M, max_dist, seed, T_init in; T_out, invalid and
+ * stats [P][5] float64 {fitness, inlier RMSE, 0 or -1 (no pose), 1 or 0, inliers} out; P pairs at once, no host round trip, pairs
+ * independent bit for bit, two runs write the same bytes; pair p of a call is pair 0 of a call with seed ^ (p << 40).
+ * tuple_test != 0: min(100 x count, max_trials) keyed trials of three rows each; a trial whose three edges agree in length within
+ * tuple_scale (in (0, 1], default use: 0.95) on both sides is accepted, and the rows of the first max_tuples accepted trials in trial
+ * order (default use: 1000) are the optimisation's row list.  tuple_test == 0: every live finite row is listed (tuple_scale,
+ * max_tuples, max_trials and seed are checked but unused).
+ * iterations in [1, DSIR_FGR_MAX_ITERS] (default use: 64); division_factor (default use: 1.4; <= 1: the robust weight's mu stays 1);
+ * refine_iters in [0, DSIR_RANSAC_MAX_REFINE]: as for RANSAC, on the optimised pose.
+ * max_tuples in [1, DSIR_FGR_MAX_TUPLES] (a list of 3 x 65536 rows: 768 KiB of rows and 9 MiB of normalised points a pair),
+ * max_trials in [1, DSIR_FGR_MAX_TRIALS] (pairs x max_trials stays below 2^31: the selection's positions are int32),
+ * DSIR_FGR_MAX_ITERS bounds the per-iteration diagnostics.  M, J, K <= max_points.  The workspace holds P x (M x 28 + rows x 52)-order
+ * scratch, rows = 3 x max_tuples (tuple_test == 0: M); a call that does not fit is refused, naming the needed and the available
+ * bytes. */
+#define DSIR_FGR_MAX_TUPLES 65536
+#define DSIR_FGR_MAX_TRIALS (1 << 22)
+#define DSIR_FGR_MAX_ITERS 1024
+/* test / measurement outputs of dsir_fgr_correspondence (all optional, device memory), L = 3 x max_tuples (tuple_test == 0: M) */
+typedef struct dsir_fgr_diag {
+  int32_t* rows;         /* [P][L]: the row list, -1 padded */
+  int32_t* n_rows;       /* [P]: rows in the list */
+  int32_t* trials;       /* [P]: trials evaluated (tuple_test == 0: 0) */
+  double* norm;          /* [P][8]: ms, mq, scale, 0 (zeros where the list has fewer than 3 rows) */
+  double* iter_T;        /* [P][iterations][12]: T after the iteration, normalised frame; zeros for iterations that did not run */
+  double* iter_mu;       /* [P][iterations]: the mu the iteration's weights used */
+  double* iter_energy;   /* [P][iterations]: the energy at the iteration's start */
+  int32_t* iters_run;    /* [P]: iterations completed; -(it + 1) when the solve refused at iteration it */
+} dsir_fgr_diag;
+int dsir_fgr_correspondence(dsir_ctx* ctx, const float* points_src, const float* points_ref, int pairs, int J, int K, int stride,
+                            const int32_t* corr, const int32_t* counts, int M, float max_dist, int tuple_test, float tuple_scale,
+                            int max_tuples, int max_trials, int iterations, float division_factor, int refine_iters, uint64_t seed,
+                            const float* T_init, float* T_out, double* stats, int32_t* invalid,
+                            const dsir_fgr_diag* diag /* NULL in production */);
+
 /* The correspondence set open3d's registration_ransac_based_on_feature_matching (network/DGR.py:7-24; called at test.py:259-263)
  * draws from, made explicit (parity unpinned, as above): the exact descriptor arg-min of dsir_nn_match src -> ref, with mutual != 0
  * kept only where the ref -> src arg-min points back; survivors in ascending src index.  desc_src [P][J][64], desc_ref [P][K][64]
