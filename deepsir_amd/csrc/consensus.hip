@@ -3,9 +3,10 @@
 // UNPINNED: the engine owns the rule, states it here once, and deepsir_amd/consensus.py restates it on the host for the tests.
 // No sampling, no seed, no random number: a pose is a function of the inputs alone.
 //
-// THE RULE.  Per pair p, inputs as for dsir_ransac_correspondence:
-//   1 gather: ransac_gather_kernel's rule (ransac.hip): clamp with bit 2 of invalid, park non-finite rows and rows >= count at
-//     s = 0, q = FLT_MAX.  A parked row is compatible with nothing.
+// THE RULE.  Front (step 1) and tail (step 7) are those of every pose-from-correspondences stage: the head of pose_corr.hip states
+// them.  Per pair p:
+//   1 gather: the shared front: clamp with bit 2 of invalid, park non-finite rows and rows >= count at s = 0, q = FLT_MAX.  A parked
+//     row is compatible with nothing.
 //   2 first-order compatibility, i != j, neither parked:   C[i][j] = 1  iff  | |s_i - s_j| - |q_i - q_j| | < compat_dist
 //     in float64 on the fp32 coordinates, |d| = sqrt((dx dx + dy dy) + dz dz), every operation rounded once, no contraction (the
 //     convention of fpfh.hip); compat_dist is the fp32 argument widened.  d -> -d changes no square: C is symmetric by construction,
@@ -15,10 +16,10 @@
 //   4 seeds: the `seeds` rows with the largest (score, lower index), in that order; fewer if fewer have score > 0.  Seed rank r.
 //   5 members of seed i: i itself and the members - 1 rows j with the largest (S2[i][j], lower j) among those with S2[i][j] > 0,
 //     taken in ascending index.  Fewer than 3 members: the seed is invalid.
-//   6 fit: unweighted Kabsch of the members in member order - fit_rows64 of ransac_stages.h, the fit of a RANSAC hypothesis; T rounded
+//   6 fit: unweighted Kabsch of the members in member order - fit_rows64 of pose_corr.h, the fit of a RANSAC hypothesis; T rounded
 //     to fp32 once.  A non-finite T is invalid.
 //   7 the seed poses are scored, picked (largest inlier count under max_dist, ties to the lower seed rank), refitted refine_iters
-//     times on all inliers and finished by the kernels of ransac.hip (launch_ransac_tail), with H = seeds.
+//     times on all inliers and finished by the shared tail (launch_pose_tail), with H = seeds.
 //   output: T_out, stats {fitness, inlier RMSE, winning seed rank or -1, valid seeds, inliers}.  No valid seed: T_out = T_init
 //     (identity if NULL), stats {0, 0, -1, 0, 0} - not an error.
 //
@@ -39,7 +40,7 @@
 
 #include "kernels.h"
 #include "device_utils.h"
-#include "ransac_stages.h"
+#include "pose_corr.h"
 #include "seg_sort.h"
 #include "dsir.h"
 
@@ -256,26 +257,25 @@ __global__ __launch_bounds__(256) void consensus_members_kernel(const float* __r
 
 }  // namespace
 
-size_t consensus_scratch_bytes(int pairs, int M, int seeds, int refine_iters) { 
+size_t consensus_scratch_bytes(int pairs, int M, int seeds, int refine_iters) {
   return ConsensusLayout(pairs, M, seeds, refine_iters, seg_sort_keys_desc_tmp_bytes((int64_t)pairs * M, pairs)).bytes;
 }
 
 int launch_consensus(const ConsensusArgs& a, void* scratch, hipStream_t st) {
-  const int P = a.pairs, M = a.M, H = a.seeds, R = a.refine_iters, W = (M + 63) / 64;
-  if ((int64_t)P * M > 0x7fffffffll) return 1;
+  const CorrProblem& p = a.p;
+  const int P = p.pairs, M = p.M, H = a.seeds, W = (M + 63) / 64;
+  if (!pose_corr_shape_ok(P, M)) return 1;
   size_t tmp = seg_sort_keys_desc_tmp_bytes((int64_t)P * M, P);
-  const ConsensusLayout lay(P, M, H, R, tmp);
+  const ConsensusLayout lay(P, M, H, p.refine_iters, tmp);
   const PoseParts s(scratch, lay.pose);
+  const CandSet hyp(scratch, lay.hyp, H);
   unsigned long long *bits = at<unsigned long long>(scratch, lay.bits), *k0 = at<unsigned long long>(scratch, lay.k0),
                      *k1 = at<unsigned long long>(scratch, lay.k1);
   int32_t *score = at<int32_t>(scratch, lay.score), *seed = at<int32_t>(scratch, lay.seed);
   int* seg = at<int>(scratch, lay.seg);
-  float* hyp_T = at<float>(scratch, lay.hyp_T);
-  int32_t *hyp_valid = at<int32_t>(scratch, lay.hyp_valid), *hyp_count = at<int32_t>(scratch, lay.hyp_count);
-  const float thr2 = a.max_dist * a.max_dist;   // fp32 product, as in ransac.hip
-  const float cd = a.compat_dist > 0.f ? a.compat_dist : a.max_dist;
+  const float cd = a.compat_dist > 0.f ? a.compat_dist : p.max_dist;
 
-  launch_ransac_gather(a.src, a.ref, P, a.J, a.K, a.stride, a.corr, a.counts, M, s, a.invalid, st);
+  launch_pose_front(p, s, st);
   {
     const int tiles = (M + CT - 1) / CT;
     int slices = (int)((512 + (int64_t)tiles * P - 1) / ((int64_t)tiles * P));
@@ -294,15 +294,13 @@ int launch_consensus(const ConsensusArgs& a, void* scratch, hipStream_t st) {
     return 2;
   hipLaunchKernelGGL(consensus_seed_kernel, dim3((P * H + 255) / 256), dim3(256), 0, st, k1, P, M, H, seed);
   const size_t lds = (size_t)W * 8 + (size_t)M * 2;
-  hipLaunchKernelGGL(consensus_members_kernel, dim3(H, P), dim3(256), lds, st, s.cs, s.cq, bits, seed, M, W, H, a.members, hyp_T, hyp_valid,
+  hipLaunchKernelGGL(consensus_members_kernel, dim3(H, P), dim3(256), lds, st, s.cs, s.cq, bits, seed, M, W, H, a.members, hyp.T, hyp.valid,
                      a.diag_members);
-  launch_ransac_tail(s, a.counts, P, M, hyp_T, hyp_valid, hyp_count, H, R, thr2, a.T_init, a.T_out, a.stats, st);
+  launch_pose_tail(p, s, hyp, st);
   if (a.diag_bits) hipMemcpyAsync(a.diag_bits, bits, (size_t)P * M * W * 8, hipMemcpyDeviceToDevice, st);
   if (a.diag_score) hipMemcpyAsync(a.diag_score, score, (size_t)P * M * 4, hipMemcpyDeviceToDevice, st);
   if (a.diag_seed) hipMemcpyAsync(a.diag_seed, seed, (size_t)P * H * 4, hipMemcpyDeviceToDevice, st);
-  if (a.diag_T) hipMemcpyAsync(a.diag_T, hyp_T, (size_t)P * H * 48, hipMemcpyDeviceToDevice, st);
-  if (a.diag_valid) hipMemcpyAsync(a.diag_valid, hyp_valid, (size_t)P * H * 4, hipMemcpyDeviceToDevice, st);
-  if (a.diag_count) hipMemcpyAsync(a.diag_count, hyp_count, (size_t)P * H * 4, hipMemcpyDeviceToDevice, st);
+  copy_candidates(hyp, P, a.diag_T, a.diag_valid, a.diag_count, st);
   return 0;
 }
 

@@ -3,7 +3,9 @@
 #include <cmath>
 
 #include "engine_ctx.h"
+#include "fgr.h"
 #include "icp_grid.h"
+#include "pose_corr.h"
 
 using namespace dsir;
 
@@ -99,113 +101,97 @@ int dsir_icp_correspondences(dsir_ctx* c, const float* points_src, const float* 
   return icp_entry(c, "dsir_icp_correspondences", a, nullptr, search, &out);
 }
 
+// What the three pose-from-correspondences entries share, under the entry's own `name`: the Call scope and the checks of the common
+// arguments; after the entry's checks of its own parameters the whole scratch, validated before the first launch; the way out.
+struct CorrEntry {
+  Call call; dsir_ctx* c; const char* name; CorrProblem p; bool refused;
+  CorrEntry(dsir_ctx* c_, const char* name_, const CorrProblem& p_)
+      : call(c_), c(c_), name(name_), p(p_), refused(call.refused() || check()) {}
+  int check() {
+    if (!p.src || !p.ref || !p.corr || !p.T_out || !p.stats || !p.invalid || p.pairs < 1 || p.J < 1 || p.K < 1 || p.M < 1 || p.stride < 3 ||
+        !(p.max_dist > 0.f) || !std::isfinite(p.max_dist))
+      return fail(c, "%s: bad arguments", name);
+    if (p.refine_iters < 0 || p.refine_iters > DSIR_RANSAC_MAX_REFINE)
+      return fail(c, "%s: refine_iters=%d outside [0,%d]", name, p.refine_iters, DSIR_RANSAC_MAX_REFINE);
+    if (p.M > c->cfg.max_points || p.J > c->cfg.max_points || p.K > c->cfg.max_points)
+      return fail(c, "%s: M=%d, J=%d or K=%d beyond max_points=%d", name, p.M, p.J, p.K, c->cfg.max_points);
+    if (!pose_corr_shape_ok(p.pairs, p.M)) return fail(c, "%s: pairs x M = %lld unsupported", name, (long long)p.pairs * p.M);
+    return 0;
+  }
+  void* reserve(size_t need, const char* what) {   // the arena is empty here: `need` bytes fit iff they are no more than it holds
+    if (need <= c->ws.cap) return c->ws.raw(need);
+    fail(c, "workspace too small for %s: needs %zu bytes (%s), the arena holds %zu (raise max_points / max_pairs, or pass fewer pairs)",
+         name, need, what, c->ws.cap);
+    return nullptr;
+  }
+  int launched(int r) { return r ? fail(c, "%s: launch failed (%d)", name, r) : call.finish(); }
+};
+
 int dsir_ransac_correspondence(dsir_ctx* c, const float* points_src, const float* points_ref, int pairs, int J, int K, int stride,
                                const int32_t* corr, const int32_t* counts, int M, float max_dist, int ransac_n, float edge_sim,
                                int hypotheses, int refine_iters, uint64_t seed, const float* T_init, float* T_out, double* stats,
                                int32_t* invalid, const dsir_ransac_diag* diag) {
-  Call call(c); if (call.refused()) return 1;
-  if (!points_src || !points_ref || !corr || !T_out || !stats || !invalid || pairs < 1 || J < 1 || K < 1 || M < 1 || stride < 3 ||
-      !(max_dist > 0.f) || !std::isfinite(max_dist) || !std::isfinite(edge_sim))
-    return fail(c, "dsir_ransac_correspondence: bad arguments");
-  if (ransac_n != 3 && ransac_n != 4) return fail(c, "dsir_ransac_correspondence: ransac_n must be 3 or 4 (got %d)", ransac_n);
+  CorrEntry e(c, "dsir_ransac_correspondence",
+              {points_src, points_ref, pairs, J, K, stride, corr, counts, M, max_dist, refine_iters, T_init, T_out, stats, invalid});
+  if (e.refused) return 1;
+  if (!std::isfinite(edge_sim)) return fail(c, "%s: bad arguments (edge_sim must be finite)", e.name);
+  if (ransac_n != 3 && ransac_n != 4) return fail(c, "%s: ransac_n must be 3 or 4 (got %d)", e.name, ransac_n);
   if (hypotheses < 1 || hypotheses > DSIR_RANSAC_MAX_HYPOTHESES)
-    return fail(c, "dsir_ransac_correspondence: hypotheses=%d outside [1,%d]", hypotheses, DSIR_RANSAC_MAX_HYPOTHESES);
-  if (refine_iters < 0 || refine_iters > DSIR_RANSAC_MAX_REFINE)
-    return fail(c, "dsir_ransac_correspondence: refine_iters=%d outside [0,%d]", refine_iters, DSIR_RANSAC_MAX_REFINE);
-  if (M > c->cfg.max_points || J > c->cfg.max_points || K > c->cfg.max_points)
-    return fail(c, "dsir_ransac_correspondence: M=%d, J=%d or K=%d beyond max_points=%d", M, J, K, c->cfg.max_points);
-  void* scratch = c->ws.raw(ransac_scratch_bytes(pairs, M, hypotheses, refine_iters));
-  if (c->ws.overflow) return fail(c, "workspace too small for dsir_ransac_correspondence (pairs x (M x 28 + hypotheses x 56) bytes: raise max_points / max_pairs)");
-  RansacArgs a{};
-  a.src = points_src; a.ref = points_ref; a.pairs = pairs; a.J = J; a.K = K; a.stride = stride; a.corr = corr; a.counts = counts;
-  a.M = M; a.max_dist = max_dist; a.n = ransac_n; a.edge_sim = edge_sim; a.hypotheses = hypotheses; a.refine_iters = refine_iters;
-  a.seed = seed; a.T_init = T_init; a.T_out = T_out; a.stats = stats; a.invalid = invalid;
+    return fail(c, "%s: hypotheses=%d outside [1,%d]", e.name, hypotheses, DSIR_RANSAC_MAX_HYPOTHESES);
+  void* scratch = e.reserve(ransac_scratch_bytes(pairs, M, hypotheses, refine_iters), "pairs x (M x 28 + hypotheses x 56)-order");
+  if (!scratch) return 1;
+  RansacArgs a{e.p, ransac_n, edge_sim, hypotheses, seed};
   if (diag) { a.diag_sample = diag->hyp_sample; a.diag_T = diag->hyp_T; a.diag_valid = diag->hyp_valid; a.diag_count = diag->hyp_count; }
-  launch_ransac(a, scratch, c->stream);
-  return call.finish();
+  return e.launched(launch_ransac(a, scratch, c->stream));
 }
 
 int dsir_consensus_correspondence(dsir_ctx* c, const float* points_src, const float* points_ref, int pairs, int J, int K, int stride,
                                   const int32_t* corr, const int32_t* counts, int M, float max_dist, float compat_dist, int seeds,
                                   int members, int refine_iters, const float* T_init, float* T_out, double* stats, int32_t* invalid,
                                   const dsir_consensus_diag* diag) {
-  Call call(c); if (call.refused()) return 1;
-  if (!points_src || !points_ref || !corr || !T_out || !stats || !invalid || pairs < 1 || J < 1 || K < 1 || M < 1 || stride < 3 ||
-      !(max_dist > 0.f) || !std::isfinite(max_dist) || !std::isfinite(compat_dist))
-    return fail(c, "dsir_consensus_correspondence: bad arguments");
-  if (seeds < 1 || seeds > DSIR_CONSENSUS_MAX_SEEDS)
-    return fail(c, "dsir_consensus_correspondence: seeds=%d outside [1,%d]", seeds, DSIR_CONSENSUS_MAX_SEEDS);
+  CorrEntry e(c, "dsir_consensus_correspondence",
+              {points_src, points_ref, pairs, J, K, stride, corr, counts, M, max_dist, refine_iters, T_init, T_out, stats, invalid});
+  if (e.refused) return 1;
+  if (!std::isfinite(compat_dist)) return fail(c, "%s: bad arguments (compat_dist must be finite)", e.name);
+  if (seeds < 1 || seeds > DSIR_CONSENSUS_MAX_SEEDS) return fail(c, "%s: seeds=%d outside [1,%d]", e.name, seeds, DSIR_CONSENSUS_MAX_SEEDS);
   if (members < 3 || members > DSIR_CONSENSUS_MAX_MEMBERS)
-    return fail(c, "dsir_consensus_correspondence: members=%d outside [3,%d]", members, DSIR_CONSENSUS_MAX_MEMBERS);
-  if (refine_iters < 0 || refine_iters > DSIR_RANSAC_MAX_REFINE)
-    return fail(c, "dsir_consensus_correspondence: refine_iters=%d outside [0,%d]", refine_iters, DSIR_RANSAC_MAX_REFINE);
-  if (M > c->cfg.max_points || J > c->cfg.max_points || K > c->cfg.max_points)
-    return fail(c, "dsir_consensus_correspondence: M=%d, J=%d or K=%d beyond max_points=%d", M, J, K, c->cfg.max_points);
-  if (M > DSIR_CONSENSUS_MAX_M) return fail(c, "dsir_consensus_correspondence: M=%d beyond DSIR_CONSENSUS_MAX_M=%d", M, DSIR_CONSENSUS_MAX_M);
-  if ((int64_t)pairs * M > 0x7fffffffll) return fail(c, "dsir_consensus_correspondence: pairs x M = %lld unsupported", (long long)pairs * M);
-  // the whole workspace, validated before the first launch
-  const size_t need = consensus_scratch_bytes(pairs, M, seeds, refine_iters);
-  if (need > c->ws.cap)
-    return fail(c, "workspace too small for dsir_consensus_correspondence: needs %zu bytes (the bit matrix alone: pairs x M x ceil(M / 64) x 8 = "
-                   "%zu), the arena holds %zu (raise max_points / max_pairs, or pass fewer pairs)", need,
-                (size_t)pairs * M * ((size_t)(M + 63) / 64) * 8, c->ws.cap);
-  void* scratch = c->ws.raw(need);
-  if (c->ws.overflow) return fail(c, "workspace too small for dsir_consensus_correspondence");
-  ConsensusArgs a{};
-  a.src = points_src; a.ref = points_ref; a.pairs = pairs; a.J = J; a.K = K; a.stride = stride; a.corr = corr; a.counts = counts;
-  a.M = M; a.max_dist = max_dist; a.compat_dist = compat_dist; a.seeds = seeds; a.members = members; a.refine_iters = refine_iters;
-  a.T_init = T_init; a.T_out = T_out; a.stats = stats; a.invalid = invalid;
+    return fail(c, "%s: members=%d outside [3,%d]", e.name, members, DSIR_CONSENSUS_MAX_MEMBERS);
+  if (M > DSIR_CONSENSUS_MAX_M) return fail(c, "%s: M=%d beyond DSIR_CONSENSUS_MAX_M=%d", e.name, M, DSIR_CONSENSUS_MAX_M);
+  void* scratch = e.reserve(consensus_scratch_bytes(pairs, M, seeds, refine_iters), "the bit matrix alone: pairs x M x ceil(M / 64) x 8");
+  if (!scratch) return 1;
+  ConsensusArgs a{e.p, compat_dist, seeds, members};
   if (diag) {
     a.diag_bits = diag->bits; a.diag_score = diag->score; a.diag_seed = diag->seed; a.diag_members = diag->seed_members;
     a.diag_T = diag->seed_T; a.diag_valid = diag->seed_valid; a.diag_count = diag->seed_count;
   }
-  if (int r = launch_consensus(a, scratch, c->stream)) return fail(c, "dsir_consensus_correspondence: launch failed (%d)", r);
-  return call.finish();
+  return e.launched(launch_consensus(a, scratch, c->stream));
 }
 
 int dsir_fgr_correspondence(dsir_ctx* c, const float* points_src, const float* points_ref, int pairs, int J, int K, int stride,
                             const int32_t* corr, const int32_t* counts, int M, float max_dist, int tuple_test, float tuple_scale,
                             int max_tuples, int max_trials, int iterations, float division_factor, int refine_iters, uint64_t seed,
                             const float* T_init, float* T_out, double* stats, int32_t* invalid, const dsir_fgr_diag* diag) {
-  Call call(c); if (call.refused()) return 1;
-  if (!points_src || !points_ref || !corr || !T_out || !stats || !invalid || pairs < 1 || J < 1 || K < 1 || M < 1 || stride < 3 ||
-      !(max_dist > 0.f) || !std::isfinite(max_dist))
-    return fail(c, "dsir_fgr_correspondence: bad arguments");
-  if (!(tuple_scale > 0.f) || !(tuple_scale <= 1.f))
-    return fail(c, "dsir_fgr_correspondence: tuple_scale=%g outside (0,1]", (double)tuple_scale);
-  if (max_tuples < 1 || max_tuples > DSIR_FGR_MAX_TUPLES)
-    return fail(c, "dsir_fgr_correspondence: max_tuples=%d outside [1,%d]", max_tuples, DSIR_FGR_MAX_TUPLES);
-  if (max_trials < 1 || max_trials > DSIR_FGR_MAX_TRIALS)
-    return fail(c, "dsir_fgr_correspondence: max_trials=%d outside [1,%d]", max_trials, DSIR_FGR_MAX_TRIALS);
-  if (iterations < 1 || iterations > DSIR_FGR_MAX_ITERS)
-    return fail(c, "dsir_fgr_correspondence: iterations=%d outside [1,%d]", iterations, DSIR_FGR_MAX_ITERS);
-  if (!std::isfinite(division_factor)) return fail(c, "dsir_fgr_correspondence: division_factor must be finite");
-  if (refine_iters < 0 || refine_iters > DSIR_RANSAC_MAX_REFINE)
-    return fail(c, "dsir_fgr_correspondence: refine_iters=%d outside [0,%d]", refine_iters, DSIR_RANSAC_MAX_REFINE);
-  if (M > c->cfg.max_points || J > c->cfg.max_points || K > c->cfg.max_points)
-    return fail(c, "dsir_fgr_correspondence: M=%d, J=%d or K=%d beyond max_points=%d", M, J, K, c->cfg.max_points);
-  if (pairs > 65535 || (int64_t)pairs * ((int64_t)max_trials + 256) > 0x7fffffffll || (int64_t)pairs * M > 0x7fffffffll)
-    return fail(c, "dsir_fgr_correspondence: pairs=%d with max_trials=%d and M=%d unsupported (pairs <= 65535, pairs x max_trials and "
-                   "pairs x M below 2^31)", pairs, max_trials, M);
-  // the whole workspace, validated before the first launch
-  const size_t need = fgr_scratch_bytes(pairs, M, tuple_test ? 1 : 0, max_tuples, max_trials, refine_iters);
-  if (need > c->ws.cap)
-    return fail(c, "workspace too small for dsir_fgr_correspondence: needs %zu bytes (pairs x (M x 28 + rows x 52)-order, rows = %s), "
-                   "the arena holds %zu (raise max_points / max_pairs, or pass fewer pairs or a smaller max_tuples)", need,
-                tuple_test ? "3 x max_tuples" : "M", c->ws.cap);
-  void* scratch = c->ws.raw(need);
-  if (c->ws.overflow) return fail(c, "workspace too small for dsir_fgr_correspondence");
-  FgrArgs a{};
-  a.src = points_src; a.ref = points_ref; a.pairs = pairs; a.J = J; a.K = K; a.stride = stride; a.corr = corr; a.counts = counts;
-  a.M = M; a.max_dist = max_dist; a.tuple_test = tuple_test ? 1 : 0; a.ts2 = tuple_scale * tuple_scale;   // fp32, rounded once
-  a.max_tuples = max_tuples; a.max_trials = max_trials; a.iterations = iterations; a.division_factor = division_factor;
-  a.refine_iters = refine_iters; a.seed = seed; a.T_init = T_init; a.T_out = T_out; a.stats = stats; a.invalid = invalid;
+  CorrEntry e(c, "dsir_fgr_correspondence",
+              {points_src, points_ref, pairs, J, K, stride, corr, counts, M, max_dist, refine_iters, T_init, T_out, stats, invalid});
+  if (e.refused) return 1;
+  if (!(tuple_scale > 0.f) || !(tuple_scale <= 1.f)) return fail(c, "%s: tuple_scale=%g outside (0,1]", e.name, (double)tuple_scale);
+  if (max_tuples < 1 || max_tuples > DSIR_FGR_MAX_TUPLES) return fail(c, "%s: max_tuples=%d outside [1,%d]", e.name, max_tuples, DSIR_FGR_MAX_TUPLES);
+  if (max_trials < 1 || max_trials > DSIR_FGR_MAX_TRIALS) return fail(c, "%s: max_trials=%d outside [1,%d]", e.name, max_trials, DSIR_FGR_MAX_TRIALS);
+  if (iterations < 1 || iterations > DSIR_FGR_MAX_ITERS) return fail(c, "%s: iterations=%d outside [1,%d]", e.name, iterations, DSIR_FGR_MAX_ITERS);
+  if (!std::isfinite(division_factor)) return fail(c, "%s: division_factor must be finite", e.name);
+  if (!fgr_shape_ok(pairs, M, max_trials))
+    return fail(c, "%s: pairs=%d with max_trials=%d and M=%d unsupported (pairs <= 65535, pairs x max_trials and pairs x M below 2^31)",
+                e.name, pairs, max_trials, M);
+  const int tt = tuple_test ? 1 : 0;
+  void* scratch = e.reserve(fgr_scratch_bytes(pairs, M, tt, max_tuples, max_trials, refine_iters),
+                            tt ? "pairs x (M x 28 + rows x 52)-order, rows = 3 x max_tuples" : "pairs x (M x 28 + rows x 52)-order, rows = M");
+  if (!scratch) return 1;
+  FgrArgs a{e.p, tt, tuple_scale * tuple_scale, max_tuples, max_trials, iterations, division_factor, seed};   // ts2: fp32, rounded once
   if (diag) {
     a.diag_rows = diag->rows; a.diag_n_rows = diag->n_rows; a.diag_trials = diag->trials; a.diag_norm = diag->norm;
     a.diag_iter_T = diag->iter_T; a.diag_iter_mu = diag->iter_mu; a.diag_iter_energy = diag->iter_energy; a.diag_iters_run = diag->iters_run;
   }
-  if (int r = launch_fgr(a, scratch, c->stream)) return fail(c, "dsir_fgr_correspondence: launch failed (%d)", r);
-  return call.finish();
+  return e.launched(launch_fgr(a, scratch, c->stream));
 }
 
 int dsir_pose_finetune(dsir_ctx* c, const float* xyz_src, const float* xyz_ref, const float* weights, int weights_are_logits,

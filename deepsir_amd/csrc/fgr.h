@@ -7,7 +7,7 @@
 #include <stdint.h>
 
 #include "icp_plane.h"    // DSIR_HD, the 6 x 6 solve and the update the optimisation shares with the point-to-plane ICP
-#include "op_layouts.h"   // PoseLayout: the head of every pose stage's scratch
+#include "op_layouts.h"   // PoseLayout and CandLayout: the head and the end of every pose-from-correspondences stage's scratch
 
 namespace dsir {
 
@@ -50,11 +50,19 @@ DSIR_HD constexpr int64_t fgr_n_rows(int tuple_test, int M, int max_tuples, int6
   return (int64_t)fgr_rows_per(tuple_test) * (accepted < cap ? accepted : cap);
 }
 
+// What dsir_fgr_correspondence and launch_fgr take: the selection grids carry the pairs on grid.y (pairs <= 65535), and one int32
+// prefix sum ranks the accepted candidates of ALL pairs over blocks of kFgrBlock trials (or, without the tuple test, rows)
+DSIR_HD constexpr bool fgr_shape_ok(int pairs, int M, int max_trials) {
+  return pairs <= 65535 && (int64_t)pairs * ((int64_t)max_trials + kFgrBlock) <= 0x7fffffffll && pose_corr_shape_ok(pairs, M);
+}
+
 // launch_fgr: the PoseLayout head, then rows [P][L] int32, the selection's block counts and their exclusive prefix [P x blocks]
 // int32, the scan's temporary, the normalised points [P][L][6] float64 and the single candidate pose of the tail
 struct FgrLayout {
   PoseLayout pose;
-  size_t rows, blk_cnt, blk_pre, tmp, npts, hyp_T, hyp_valid, hyp_count, bytes;
+  size_t rows, blk_cnt, blk_pre, tmp, npts;
+  CandLayout hyp;
+  size_t bytes;
   FgrLayout(int pairs, int M, int tuple_test, int max_tuples, int max_trials, int refine_iters, size_t scan_tmp)
       : pose(pairs, M, refine_iters) {
     const size_t P = (size_t)pairs, L = (size_t)fgr_list_rows(tuple_test, M, max_tuples);
@@ -64,7 +72,7 @@ struct FgrLayout {
     blk_cnt = c.take(P * NB * 4); blk_pre = c.take(P * NB * 4);
     tmp = c.take(scan_tmp);
     npts = c.take(P * L * 48);
-    hyp_T = c.take(P * 48); hyp_valid = c.take(P * 4); hyp_count = c.take(P * 4);
+    hyp.take(c, P, 1);
     bytes = c.p;
   }
 };

@@ -4,9 +4,10 @@
 // the tests.  No hypotheses and no quadratic memory: a tuple pre-filter, then a few dozen 6 x 6 Gauss-Newton steps under a graduated
 // robust weight - O(rows x iterations) per pair.
 //
-// THE RULE.  Per pair p, inputs as for dsir_ransac_correspondence:
-//   1 gather: ransac_gather_kernel's rule (ransac.hip): clamp with bit 2 of invalid, park non-finite rows and rows >= count at
-//     s = 0, q = FLT_MAX.  A parked row enters nothing below.
+// THE RULE.  Front (step 1) and tail (step 6) are those of every pose-from-correspondences stage: the head of pose_corr.hip states
+// them.  Per pair p:
+//   1 gather: the shared front: clamp with bit 2 of invalid, park non-finite rows and rows >= count at s = 0, q = FLT_MAX.  A parked
+//     row enters nothing below.
 //   2 tuple test (tuple_test != 0): trial t of min(100 count, max_trials) draws three rows with RANSAC's key scheme, a trial in the
 //     place of a hypothesis:  row_k = ((splitmix64(splitmix64(seed ^ (p << 40)) ^ (t << 8) ^ k) >> 32) * count) >> 32,  k = 0, 1, 2.
 //     It is accepted iff for each of the edges (0,1), (0,2), (1,2):  d2s ts2 < d2q  and  d2q ts2 < d2s,  all in fp32 with every
@@ -27,7 +28,7 @@
 //       T <- M(x) T with icp_plane_transform (Rz Ry Rx, translation x_3..5);
 //       if division_factor > 1 and it % 4 == 0 and mu > floor: mu <- mu / division_factor.
 //   5 un-normalise, float64: R = T_R, t = scale T_t + mq - R ms; rounded to fp32 once.  A non-finite pose is no pose.
-//   6 tail: that pose is the single candidate (H = 1) of launch_ransac_tail (ransac.hip): inlier count under max_dist, refine_iters
+//   6 tail: that pose is the single candidate (H = 1) of the shared tail (launch_pose_tail): inlier count under max_dist, refine_iters
 //     refits on all inliers, T_out and stats {fitness, inlier RMSE, 0 or -1, 1 or 0, inliers}.  No pose: T_out = T_init (identity if
 //     NULL), stats {0, 0, -1, 0, 0} - not an error.
 // Where the rule leaves open3d's: open3d normalises the two whole clouds (here the listed correspondences alone: the stage reads
@@ -53,7 +54,7 @@
 
 #include "kernels.h"
 #include "device_utils.h"
-#include "ransac_stages.h"
+#include "pose_corr.h"
 #include "fgr.h"
 #include "dsir.h"
 
@@ -328,12 +329,13 @@ size_t fgr_scan_tmp_bytes(int64_t n) {
 template <bool TUPLE>
 void launch_select(const FgrArgs& a, const PoseParts& s, float ts2, int NB, int cap, int64_t L, int32_t* blk_cnt, int32_t* blk_pre,
                    int32_t* rows, bool fill, hipStream_t st) {
-  const dim3 grid(NB, a.pairs);
+  const CorrProblem& p = a.p;
+  const dim3 grid(NB, p.pairs);
   if (!fill)
-    hipLaunchKernelGGL((fgr_select_kernel<TUPLE, false>), grid, dim3(FB), 0, st, s.cs, s.cq, a.counts, a.M, a.max_trials, a.seed, ts2, NB,
+    hipLaunchKernelGGL((fgr_select_kernel<TUPLE, false>), grid, dim3(FB), 0, st, s.cs, s.cq, p.counts, p.M, a.max_trials, a.seed, ts2, NB,
                        cap, L, blk_cnt, blk_pre, rows);
   else
-    hipLaunchKernelGGL((fgr_select_kernel<TUPLE, true>), grid, dim3(FB), 0, st, s.cs, s.cq, a.counts, a.M, a.max_trials, a.seed, ts2, NB,
+    hipLaunchKernelGGL((fgr_select_kernel<TUPLE, true>), grid, dim3(FB), 0, st, s.cs, s.cq, p.counts, p.M, a.max_trials, a.seed, ts2, NB,
                        cap, L, blk_cnt, blk_pre, rows);
 }
 
@@ -345,21 +347,20 @@ size_t fgr_scratch_bytes(int pairs, int M, int tuple_test, int max_tuples, int m
 }
 
 int launch_fgr(const FgrArgs& a, void* scratch, hipStream_t st) {
-  const int P = a.pairs, M = a.M, R = a.refine_iters, tt = a.tuple_test ? 1 : 0;
+  const CorrProblem& p = a.p;
+  const int P = p.pairs, M = p.M, tt = a.tuple_test ? 1 : 0;
+  if (!fgr_shape_ok(P, M, a.max_trials)) return 1;
   const int NB = fgr_blocks(fgr_candidates(tt, M, a.max_trials));
   const int cap = fgr_accept_cap(tt, M, a.max_tuples);
   const int64_t L = fgr_list_rows(tt, M, a.max_tuples);
-  if ((int64_t)P * NB * kFgrBlock > 0x7fffffffll || P > 65535) return 1;
   size_t tmp = fgr_scan_tmp_bytes((int64_t)P * NB);
-  const FgrLayout lay(P, M, tt, a.max_tuples, a.max_trials, R, tmp);
+  const FgrLayout lay(P, M, tt, a.max_tuples, a.max_trials, p.refine_iters, tmp);
   const PoseParts s(scratch, lay.pose);
+  const CandSet hyp(scratch, lay.hyp, 1);
   int32_t *rows = at<int32_t>(scratch, lay.rows), *blk_cnt = at<int32_t>(scratch, lay.blk_cnt), *blk_pre = at<int32_t>(scratch, lay.blk_pre);
   double* npts = at<double>(scratch, lay.npts);
-  float* hyp_T = at<float>(scratch, lay.hyp_T);
-  int32_t *hyp_valid = at<int32_t>(scratch, lay.hyp_valid), *hyp_count = at<int32_t>(scratch, lay.hyp_count);
-  const float thr2 = a.max_dist * a.max_dist;   // fp32 product, as in ransac.hip
 
-  launch_ransac_gather(a.src, a.ref, P, a.J, a.K, a.stride, a.corr, a.counts, M, s, a.invalid, st);
+  launch_pose_front(p, s, st);
   hipMemsetAsync(rows, 0xFF, (size_t)P * L * 4, st);
   if (tt) launch_select<true>(a, s, a.ts2, NB, cap, L, blk_cnt, blk_pre, rows, false, st);
   else launch_select<false>(a, s, a.ts2, NB, cap, L, blk_cnt, blk_pre, rows, false, st);
@@ -367,9 +368,9 @@ int launch_fgr(const FgrArgs& a, void* scratch, hipStream_t st) {
   if (tt) launch_select<true>(a, s, a.ts2, NB, cap, L, blk_cnt, blk_pre, rows, true, st);
   else launch_select<false>(a, s, a.ts2, NB, cap, L, blk_cnt, blk_pre, rows, true, st);
   const FgrDiagPtrs dg{a.diag_n_rows, a.diag_trials, a.diag_iters_run, a.diag_norm, a.diag_iter_T, a.diag_iter_mu, a.diag_iter_energy};
-  hipLaunchKernelGGL(fgr_optimize_kernel, dim3(P), dim3(FB), 0, st, s.cs, s.cq, a.counts, M, rows, L, blk_cnt, blk_pre, NB, tt, a.max_tuples,
-                     a.max_trials, (double)a.max_dist, a.iterations, (double)a.division_factor, npts, hyp_T, hyp_valid, dg);
-  launch_ransac_tail(s, a.counts, P, M, hyp_T, hyp_valid, hyp_count, 1, R, thr2, a.T_init, a.T_out, a.stats, st);
+  hipLaunchKernelGGL(fgr_optimize_kernel, dim3(P), dim3(FB), 0, st, s.cs, s.cq, p.counts, M, rows, L, blk_cnt, blk_pre, NB, tt, a.max_tuples,
+                     a.max_trials, (double)p.max_dist, a.iterations, (double)a.division_factor, npts, hyp.T, hyp.valid, dg);
+  launch_pose_tail(p, s, hyp, st);
   if (a.diag_rows) hipMemcpyAsync(a.diag_rows, rows, (size_t)P * L * 4, hipMemcpyDeviceToDevice, st);
   return 0;
 }

@@ -548,59 +548,12 @@ int icp_grid_build(const float* ref, int stride, const float* cur, int pairs, in
 void launch_icp_nn_grid(const IcpGrid& g, const float* cur, int pairs, int J, int K, float r2, int32_t* idx, float* d2, const int32_t* skip,
                         hipStream_t st);
 
-// ransac.hip — RANSAC pose from correspondences (network/DGR.py:7-36, :249-306 / open3d registration_ransac_*; the rule is stated in
-// the file's header), all pairs at once; and the mutual-nearest-neighbour list of dsir_feature_correspondences
-struct RansacArgs {
-  const float* src; const float* ref;   // [pairs][J][stride], [pairs][K][stride]
-  int pairs, J, K, stride;
-  const int32_t* corr;                  // [pairs][M][2]
-  const int32_t* counts;                // [pairs] or nullptr
-  int M;
-  float max_dist; int n; float edge_sim; int hypotheses, refine_iters; uint64_t seed;
-  const float* T_init;                  // [pairs][3][4] or nullptr (identity)
-  float* T_out; double* stats; int32_t* invalid;
-  int32_t* diag_sample; float* diag_T; int32_t* diag_valid; int32_t* diag_count;   // optional
-};
-size_t ransac_scratch_bytes(int pairs, int M, int H, int refine_iters);
-void launch_ransac(const RansacArgs& a, void* scratch, hipStream_t st);
+// pose_corr.hip, ransac.hip, consensus.hip, fgr.hip — pose from a correspondence list: one front, three middles, one tail; their
+// argument structs and launchers are declared in pose_corr.h.  Here the producer of such lists, the mutual-nearest-neighbour list of
+// dsir_feature_correspondences (pose_corr.hip):
 // ab [pairs][J] (src -> ref arg-min), ba [pairs][K] (ref -> src; read with mutual != 0 only) -> corr [pairs][J][2], counts [pairs]
 void launch_corr_compact(const int32_t* ab, const int32_t* ba, int pairs, int J, int K, int mutual, int32_t* corr, int32_t* counts,
                          hipStream_t st);
-
-// consensus.hip — spatial-consensus pose from correspondences (second-order compatibility; the rule is stated in the file's header),
-// all pairs at once; returns 0 on success
-struct ConsensusArgs {
-  const float* src; const float* ref;   // [pairs][J][stride], [pairs][K][stride]
-  int pairs, J, K, stride;
-  const int32_t* corr;                  // [pairs][M][2]
-  const int32_t* counts;                // [pairs] or nullptr
-  int M;
-  float max_dist, compat_dist; int seeds, members, refine_iters;
-  const float* T_init;                  // [pairs][3][4] or nullptr (identity)
-  float* T_out; double* stats; int32_t* invalid;
-  uint64_t* diag_bits; int32_t* diag_score; int32_t* diag_seed; int32_t* diag_members;   // optional
-  float* diag_T; int32_t* diag_valid; int32_t* diag_count;
-};
-size_t consensus_scratch_bytes(int pairs, int M, int seeds, int refine_iters);
-int launch_consensus(const ConsensusArgs& a, void* scratch, hipStream_t st);
-
-// fgr.hip — fast global registration pose from correspondences (tuple pre-filter, graduated Gauss-Newton; the rule is stated in the
-// file's header), all pairs at once; returns 0 on success
-struct FgrArgs {
-  const float* src; const float* ref;   // [pairs][J][stride], [pairs][K][stride]
-  int pairs, J, K, stride;
-  const int32_t* corr;                  // [pairs][M][2]
-  const int32_t* counts;                // [pairs] or nullptr
-  int M;
-  float max_dist; int tuple_test; float ts2; int max_tuples, max_trials, iterations; float division_factor; int refine_iters;
-  uint64_t seed;
-  const float* T_init;                  // [pairs][3][4] or nullptr (identity)
-  float* T_out; double* stats; int32_t* invalid;
-  int32_t* diag_rows; int32_t* diag_n_rows; int32_t* diag_trials; double* diag_norm;   // optional
-  double* diag_iter_T; double* diag_iter_mu; double* diag_iter_energy; int32_t* diag_iters_run;
-};
-size_t fgr_scratch_bytes(int pairs, int M, int tuple_test, int max_tuples, int max_trials, int refine_iters);
-int launch_fgr(const FgrArgs& a, void* scratch, hipStream_t st);
 
 // finetune.hip — Adam fine-tune of the pose on matched points (test.py:159-207), one workgroup per pair
 void launch_pose_finetune(const float* src, const float* ref, const float* w, int sigmoid, int pairs, int m, const float* T_init,

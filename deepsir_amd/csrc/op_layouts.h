@@ -1,5 +1,5 @@
 // The scratch of select.hip, preprocess.hip, resample.hip, ransac.hip, consensus.hip and match_targets.hip as offsets into one piece
-// each: built from the operator's shape (and, where a library call needs temporary space, that size), read by the size function and
+// each (fgr.hip's, over the same head and candidate part, is in fgr.h): built from the operator's shape (and, where a library call needs temporary space, that size), read by the size function and
 // the launcher alike.  Plain host C++ on the model of icp_layout.h: tools/scratch_layout_check.cpp lays every one out on the CPU.
 #pragma once
 #include "scratch.h"
@@ -48,8 +48,9 @@ struct VoxelLayout {         // launch_voxel_downsample: the sort, then the scan
   }
 };
 
-// what both pose stages keep: matched points cs / cq [P][M][3], refit weights w [P][M], round state Tcand [R + 1][P][12],
-// cnt [R + 1][P], info [4][P].  It is the head of their scratch: RansacLayout and ConsensusLayout go on from `bytes`.
+// what every pose-from-correspondences stage keeps (pose_corr.hip): matched points cs / cq [P][M][3], refit weights w [P][M], round
+// state Tcand [R + 1][P][12], cnt [R + 1][P], info [4][P].  It is the head of their scratch: RansacLayout, ConsensusLayout and
+// FgrLayout (fgr.h) go on from `bytes` and end with a CandLayout.
 struct PoseLayout {
   size_t cs, cq, w, Tcand, cnt, info, bytes;
   PoseLayout(int pairs, int M, int refine_iters) {
@@ -60,21 +61,32 @@ struct PoseLayout {
     bytes = c.p;
   }
 };
+// the gather, the scoring and the refit index [P][M] rows with 32-bit products
+constexpr bool pose_corr_shape_ok(int pairs, int M) { return (int64_t)pairs * M <= 0x7fffffffll; }
+
+// the candidate poses the middle of a stage hands to the tail: T [P][H][12], valid [P][H], count [P][H] - the last three parts of
+// every stage's scratch
+struct CandLayout {
+  size_t T = 0, valid = 0, count = 0;
+  void take(Carve& c, size_t P, size_t H) { T = c.take(P * H * 48); valid = c.take(P * H * 4); count = c.take(P * H * 4); }
+};
 
 struct RansacLayout {        // launch_ransac: P (M 28 + H 56) bytes plus a few hundred bytes per pair of round state
   PoseLayout pose;
-  size_t hyp_T, hyp_valid, hyp_count, bytes;
+  CandLayout hyp;
+  size_t bytes;
   RansacLayout(int pairs, int M, int H, int refine_iters) : pose(pairs, M, refine_iters) {
-    const size_t P = (size_t)pairs;
     Carve c{pose.bytes};
-    hyp_T = c.take(P * H * 48); hyp_valid = c.take(P * H * 4); hyp_count = c.take(P * H * 4);
+    hyp.take(c, (size_t)pairs, (size_t)H);
     bytes = c.p;
   }
 };
 
 struct ConsensusLayout {     // launch_consensus: P M W 8 bytes of bit matrix, P (M 48 + seeds 56)-order scratch, the seed sort's own
   PoseLayout pose;
-  size_t bits, score, k0, k1, seg, tmp, seed, hyp_T, hyp_valid, hyp_count, bytes;
+  size_t bits, score, k0, k1, seg, tmp, seed;
+  CandLayout hyp;
+  size_t bytes;
   ConsensusLayout(int pairs, int M, int seeds, int refine_iters, size_t sort_tmp) : pose(pairs, M, refine_iters) {
     const size_t P = (size_t)pairs, W = (size_t)(M + 63) / 64;
     Carve c{pose.bytes};
@@ -84,7 +96,7 @@ struct ConsensusLayout {     // launch_consensus: P M W 8 bytes of bit matrix, P
     seg = c.take((P + 1) * 4);
     tmp = c.take(sort_tmp);
     seed = c.take(P * seeds * 4);
-    hyp_T = c.take(P * seeds * 48); hyp_valid = c.take(P * seeds * 4); hyp_count = c.take(P * seeds * 4);
+    hyp.take(c, P, (size_t)seeds);
     bytes = c.p;
   }
 };

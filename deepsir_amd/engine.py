@@ -703,6 +703,36 @@ class Engine:
         _, neigh, _, _ = self.knn_pyramid(points_ref)
         return self.estimate_normals(points_ref, neigh, viewpoint)[0]
 
+    def _correspondence_pose(self, name, points_src, points_ref, corr, counts, T_init, scalars, diag_type, diag_table, diag):
+        """What ransac_ / consensus_ / fgr_correspondence share: the tensor checks under the method's ``name``, the outputs, with ``diag``
+        the diagnostics of ``diag_table`` (key, shape after P, dtype; the fields of ``diag_type`` in order), the call (``scalars``: M .. T_init)."""
+        points_src, points_ref = _chk(points_src, torch.float32, "points_src"), _chk(points_ref, torch.float32, "points_ref")
+        corr = _chk(corr, torch.int32, "corr")
+        P, J, stride = points_src.shape
+        K, M = points_ref.shape[1], corr.shape[1]
+        if points_ref.shape[0] != P or points_ref.shape[2] != stride or tuple(corr.shape) != (P, M, 2):
+            raise EngineError(f"{name}: points_* must be [P,N,stride] and corr [P,M,2]")
+        if counts is not None:
+            counts = _chk(counts, torch.int32, "counts")
+            if tuple(counts.shape) != (P,):
+                raise EngineError(f"{name}: counts must be [P]")
+        if T_init is not None:
+            T_init = _chk(T_init, torch.float32, "T_init")
+            if tuple(T_init.shape) != (P, 3, 4):
+                raise EngineError(f"{name}: T_init must be [P,3,4]")
+        T = self._empty((P, 3, 4))
+        stats = self._empty((P, 5), torch.float64)
+        invalid = self._empty((P,), torch.int32)
+        d, dref = None, None
+        if diag:
+            d = {k: self._empty((P,) + shape, dtype) for k, shape, dtype in diag_table}
+            dref = C.byref(diag_type(*[_ptr(v) for v in d.values()]))
+        self._pre()
+        self._call(getattr(self.lib, "dsir_" + name)(self.h, _ptr(points_src), _ptr(points_ref), P, J, K, stride, _ptr(corr), _ptr(counts),
+                                                     M, *scalars, _ptr(T_init), _ptr(T), _ptr(stats), _ptr(invalid), dref))
+        self.sync()
+        return (T, stats, invalid, d) if diag else (T, stats, invalid)
+
     RANSAC_CHUNK = 256                 # DSIR_RANSAC_CHUNK: correspondences a scoring workgroup stages per step
     RANSAC_MAX_HYPOTHESES = 1 << 20    # DSIR_RANSAC_MAX_HYPOTHESES
 
@@ -714,36 +744,11 @@ class Engine:
         points_* [P,N,>=3] CUDA fp32, corr [P,M,2] i32 (src index, ref index), counts [P] i32 or None, T_init [P,3,4] or None
         -> (T [P,3,4], stats [P,5] f64: fitness, inlier_rmse, winning hypothesis or -1, valid hypotheses, inliers; invalid [P] i32)
         and, with diag=True, a dict of hyp_sample [P,H,4], hyp_T [P,H,3,4], hyp_valid [P,H], hyp_count [P,H]."""
-        points_src, points_ref = _chk(points_src, torch.float32, "points_src"), _chk(points_ref, torch.float32, "points_ref")
-        corr = _chk(corr, torch.int32, "corr")
-        P, J, stride = points_src.shape
-        K, M = points_ref.shape[1], corr.shape[1]
-        if points_ref.shape[0] != P or points_ref.shape[2] != stride or tuple(corr.shape) != (P, M, 2):
-            raise EngineError("ransac_correspondence: points_* must be [P,N,stride] and corr [P,M,2]")
-        if counts is not None:
-            counts = _chk(counts, torch.int32, "counts")
-            if tuple(counts.shape) != (P,):
-                raise EngineError("ransac_correspondence: counts must be [P]")
-        if T_init is not None:
-            T_init = _chk(T_init, torch.float32, "T_init")
-            if tuple(T_init.shape) != (P, 3, 4):
-                raise EngineError("ransac_correspondence: T_init must be [P,3,4]")
-        T = self._empty((P, 3, 4))
-        stats = self._empty((P, 5), torch.float64)
-        invalid = self._empty((P,), torch.int32)
-        d, dref = None, None
-        if diag:
-            Hn = max(int(hypotheses), 1)
-            d = {"hyp_sample": self._empty((P, Hn, 4), torch.int32), "hyp_T": self._empty((P, Hn, 3, 4)),
-                 "hyp_valid": self._empty((P, Hn), torch.int32), "hyp_count": self._empty((P, Hn), torch.int32)}
-            dref = C.byref(_lib.dsir_ransac_diag(*[_ptr(d[k]) for k in ("hyp_sample", "hyp_T", "hyp_valid", "hyp_count")]))
-        self._pre()
-        self._call(self.lib.dsir_ransac_correspondence(self.h, _ptr(points_src), _ptr(points_ref), P, J, K, stride, _ptr(corr),
-                                                       _ptr(counts), M, float(max_dist), int(ransac_n), float(edge_sim),
-                                                       int(hypotheses), int(refine_iters), int(seed) & ((1 << 64) - 1),
-                                                       _ptr(T_init), _ptr(T), _ptr(stats), _ptr(invalid), dref))
-        self.sync()
-        return (T, stats, invalid, d) if diag else (T, stats, invalid)
+        Hn, i32 = max(int(hypotheses), 1), torch.int32
+        table = [("hyp_sample", (Hn, 4), i32), ("hyp_T", (Hn, 3, 4), torch.float32), ("hyp_valid", (Hn,), i32), ("hyp_count", (Hn,), i32)]
+        scalars = (float(max_dist), int(ransac_n), float(edge_sim), int(hypotheses), int(refine_iters), int(seed) & ((1 << 64) - 1))
+        return self._correspondence_pose("ransac_correspondence", points_src, points_ref, corr, counts, T_init, scalars,
+                                    _lib.dsir_ransac_diag, table, diag)
 
     CONSENSUS_MAX_SEEDS = 256          # DSIR_CONSENSUS_MAX_SEEDS
     CONSENSUS_MAX_MEMBERS = 128        # DSIR_CONSENSUS_MAX_MEMBERS
@@ -757,39 +762,13 @@ class Engine:
         -> (T [P,3,4], stats [P,5] f64: fitness, inlier_rmse, winning seed rank or -1, valid seeds, inliers; invalid [P] i32) and, with
         diag=True, a dict of bits [P,M,W] i64 (the words of the compatibility matrix), score [P,M] i32, seed [P,seeds],
         seed_members [P,seeds,members], seed_T [P,seeds,3,4], seed_valid [P,seeds], seed_count [P,seeds]."""
-        points_src, points_ref = _chk(points_src, torch.float32, "points_src"), _chk(points_ref, torch.float32, "points_ref")
-        corr = _chk(corr, torch.int32, "corr")
-        P, J, stride = points_src.shape
-        K, M = points_ref.shape[1], corr.shape[1]
-        if points_ref.shape[0] != P or points_ref.shape[2] != stride or tuple(corr.shape) != (P, M, 2):
-            raise EngineError("consensus_correspondence: points_* must be [P,N,stride] and corr [P,M,2]")
-        if counts is not None:
-            counts = _chk(counts, torch.int32, "counts")
-            if tuple(counts.shape) != (P,):
-                raise EngineError("consensus_correspondence: counts must be [P]")
-        if T_init is not None:
-            T_init = _chk(T_init, torch.float32, "T_init")
-            if tuple(T_init.shape) != (P, 3, 4):
-                raise EngineError("consensus_correspondence: T_init must be [P,3,4]")
-        T = self._empty((P, 3, 4))
-        stats = self._empty((P, 5), torch.float64)
-        invalid = self._empty((P,), torch.int32)
-        d, dref = None, None
-        if diag:
-            Hn, Mn, W = min(max(int(seeds), 1), self.CONSENSUS_MAX_SEEDS), min(max(int(members), 1), self.CONSENSUS_MAX_MEMBERS), (M + 63) // 64
-            d = {"bits": self._empty((P, M, W), torch.int64), "score": self._empty((P, M), torch.int32),
-                 "seed": self._empty((P, Hn), torch.int32), "seed_members": self._empty((P, Hn, Mn), torch.int32),
-                 "seed_T": self._empty((P, Hn, 3, 4)), "seed_valid": self._empty((P, Hn), torch.int32),
-                 "seed_count": self._empty((P, Hn), torch.int32)}
-            dref = C.byref(_lib.dsir_consensus_diag(*[_ptr(d[k]) for k in ("bits", "score", "seed", "seed_members", "seed_T", "seed_valid",
-                                                                            "seed_count")]))
-        self._pre()
-        self._call(self.lib.dsir_consensus_correspondence(self.h, _ptr(points_src), _ptr(points_ref), P, J, K, stride, _ptr(corr),
-                                                          _ptr(counts), M, float(max_dist), float(compat_dist or 0.0), int(seeds),
-                                                          int(members), int(refine_iters), _ptr(T_init), _ptr(T), _ptr(stats),
-                                                          _ptr(invalid), dref))
-        self.sync()
-        return (T, stats, invalid, d) if diag else (T, stats, invalid)
+        Hn, Mn = min(max(int(seeds), 1), self.CONSENSUS_MAX_SEEDS), min(max(int(members), 1), self.CONSENSUS_MAX_MEMBERS)
+        M, i32 = corr.shape[1], torch.int32
+        table = [("bits", (M, (M + 63) // 64), torch.int64), ("score", (M,), i32), ("seed", (Hn,), i32), ("seed_members", (Hn, Mn), i32),
+                 ("seed_T", (Hn, 3, 4), torch.float32), ("seed_valid", (Hn,), i32), ("seed_count", (Hn,), i32)]
+        scalars = (float(max_dist), float(compat_dist or 0.0), int(seeds), int(members), int(refine_iters))
+        return self._correspondence_pose("consensus_correspondence", points_src, points_ref, corr, counts, T_init, scalars,
+                                    _lib.dsir_consensus_diag, table, diag)
 
     FGR_MAX_TUPLES = 65536             # DSIR_FGR_MAX_TUPLES
     FGR_MAX_TRIALS = 1 << 22           # DSIR_FGR_MAX_TRIALS
@@ -805,40 +784,14 @@ class Engine:
         -> (T [P,3,4], stats [P,5] f64: fitness, inlier_rmse, 0 or -1 (no pose), 1 or 0, inliers; invalid [P] i32) and, with
         diag=True, a dict of rows [P,L] i32 (L = 3 max_tuples, or M without the tuple test; -1 padded), n_rows [P], trials [P],
         norm [P,8] f64 (ms, mq, scale), iter_T [P,iterations,3,4] f64, iter_mu / iter_energy [P,iterations] f64, iters_run [P]."""
-        points_src, points_ref = _chk(points_src, torch.float32, "points_src"), _chk(points_ref, torch.float32, "points_ref")
-        corr = _chk(corr, torch.int32, "corr")
-        P, J, stride = points_src.shape
-        K, M = points_ref.shape[1], corr.shape[1]
-        if points_ref.shape[0] != P or points_ref.shape[2] != stride or tuple(corr.shape) != (P, M, 2):
-            raise EngineError("fgr_correspondence: points_* must be [P,N,stride] and corr [P,M,2]")
-        if counts is not None:
-            counts = _chk(counts, torch.int32, "counts")
-            if tuple(counts.shape) != (P,):
-                raise EngineError("fgr_correspondence: counts must be [P]")
-        if T_init is not None:
-            T_init = _chk(T_init, torch.float32, "T_init")
-            if tuple(T_init.shape) != (P, 3, 4):
-                raise EngineError("fgr_correspondence: T_init must be [P,3,4]")
-        T = self._empty((P, 3, 4))
-        stats = self._empty((P, 5), torch.float64)
-        invalid = self._empty((P,), torch.int32)
-        d, dref = None, None
-        if diag:
-            L = 3 * min(max(int(max_tuples), 1), self.FGR_MAX_TUPLES) if tuple_test else M
-            It = min(max(int(iterations), 1), self.FGR_MAX_ITERS)
-            d = {"rows": self._empty((P, L), torch.int32), "n_rows": self._empty((P,), torch.int32),
-                 "trials": self._empty((P,), torch.int32), "norm": self._empty((P, 8), torch.float64),
-                 "iter_T": self._empty((P, It, 3, 4), torch.float64), "iter_mu": self._empty((P, It), torch.float64),
-                 "iter_energy": self._empty((P, It), torch.float64), "iters_run": self._empty((P,), torch.int32)}
-            dref = C.byref(_lib.dsir_fgr_diag(*[_ptr(d[k]) for k in ("rows", "n_rows", "trials", "norm", "iter_T", "iter_mu",
-                                                                      "iter_energy", "iters_run")]))
-        self._pre()
-        self._call(self.lib.dsir_fgr_correspondence(self.h, _ptr(points_src), _ptr(points_ref), P, J, K, stride, _ptr(corr), _ptr(counts),
-                                                    M, float(max_dist), 1 if tuple_test else 0, float(tuple_scale), int(max_tuples),
-                                                    int(max_trials), int(iterations), float(division_factor), int(refine_iters),
-                                                    int(seed) & ((1 << 64) - 1), _ptr(T_init), _ptr(T), _ptr(stats), _ptr(invalid), dref))
-        self.sync()
-        return (T, stats, invalid, d) if diag else (T, stats, invalid)
+        L = 3 * min(max(int(max_tuples), 1), self.FGR_MAX_TUPLES) if tuple_test else corr.shape[1]
+        It, i32, f64 = min(max(int(iterations), 1), self.FGR_MAX_ITERS), torch.int32, torch.float64
+        table = [("rows", (L,), i32), ("n_rows", (), i32), ("trials", (), i32), ("norm", (8,), f64), ("iter_T", (It, 3, 4), f64),
+                 ("iter_mu", (It,), f64), ("iter_energy", (It,), f64), ("iters_run", (), i32)]
+        scalars = (float(max_dist), 1 if tuple_test else 0, float(tuple_scale), int(max_tuples), int(max_trials), int(iterations),
+                   float(division_factor), int(refine_iters), int(seed) & ((1 << 64) - 1))
+        return self._correspondence_pose("fgr_correspondence", points_src, points_ref, corr, counts, T_init, scalars, _lib.dsir_fgr_diag,
+                                    table, diag)
 
     def feature_correspondences(self, desc_src, desc_ref, mutual: bool = True, k: int = 1, ratio: float = 0.0, with_dist: bool = False):
         """The correspondence set of open3d's registration_ransac_based_on_feature_matching (reference network/DGR.py:7-24),

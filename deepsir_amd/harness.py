@@ -113,13 +113,9 @@ def inference_align(pairs: Sequence[Dict[str, np.ndarray]], model, num_reg_iter:
             m = xs.shape[1]
             corr = torch.arange(m, dtype=torch.int32, device=xs.device)[None, :, None].expand(xs.shape[0], m, 2).contiguous()
             T_net = transforms[-1].contiguous()
-            if pose_opt == "ransac":
-                T_opt, _, _ = _aux_engine(model, data).ransac_correspondence(xs, xr, corr, 2.0 * voxel_size, hypotheses=ransac_hypotheses,
-                                                                             seed=ransac_seed, T_init=T_net)
-            elif pose_opt == "fgr":   # the same correspondences through fast global registration (csrc/fgr.hip); the seed keys its tuples
-                T_opt, _, _ = _aux_engine(model, data).fgr_correspondence(xs, xr, corr, 2.0 * voxel_size, seed=ransac_seed, T_init=T_net)
-            else:             # the same correspondences through the spatial-consensus stage (csrc/consensus.hip): no sampling, no seed
-                T_opt, _, _ = _aux_engine(model, data).consensus_correspondence(xs, xr, corr, 2.0 * voxel_size, T_init=T_net)
+            # 'consensus' (csrc/consensus.hip) takes neither keyword: no sampling, no seed; for 'fgr' (csrc/fgr.hip) the seed keys its tuples
+            T_opt = _pose_from_corr(_aux_engine(model, data), pose_opt, xs, xr, corr, None, 2.0 * voxel_size, T_init=T_net,
+                                    hypotheses=ransac_hypotheses, seed=ransac_seed)
             if safeguard_wsum is not None:
                 wsum = torch.sigmoid(endpoints["perm_matrices"][-1].float()).reshape(xs.shape[0], -1).sum(1)
                 T_opt = torch.where((wsum < safeguard_wsum)[:, None, None], T_opt, T_net)
@@ -318,20 +314,20 @@ def inference_feat(pairs: Sequence[Dict[str, np.ndarray]], model, batch: int = 1
     return out, total
 
 
-def _pose_from_corr(eng, pose, xs, xr, corr, counts, max_dist, ransac_n, edge_sim, hypotheses, refine_iters, seed, seeds, members,
-                    fgr_iterations=64, tuple_scale=0.95, max_tuples=1000, tuple_test=True):
-    """The pose stage of ``register_feat`` / ``register_fpfh``: 'ransac' (seeded sampling), 'consensus' (spatial compatibility) or
-    'fgr' (fast global registration: tuple pre-filter and graduated Gauss-Newton)."""
-    if pose == "ransac":
-        return eng.ransac_correspondence(xs, xr, corr, max_dist, counts=counts, ransac_n=ransac_n, edge_sim=edge_sim,
-                                         hypotheses=hypotheses, refine_iters=refine_iters, seed=seed)[0]
-    if pose == "consensus":
-        return eng.consensus_correspondence(xs, xr, corr, max_dist, counts=counts, seeds=seeds, members=members,
-                                            refine_iters=refine_iters)[0]
-    if pose == "fgr":
-        return eng.fgr_correspondence(xs, xr, corr, max_dist, counts=counts, tuple_test=tuple_test, tuple_scale=tuple_scale,
-                                      max_tuples=max_tuples, iterations=fgr_iterations, refine_iters=refine_iters, seed=seed)[0]
-    raise ValueError("pose must be 'ransac', 'consensus' or 'fgr'")
+# pose name -> (Engine method, the harness keywords it takes; the harness's fgr_iterations is the method's `iterations`)
+_POSES = {"ransac": ("ransac_correspondence", ("ransac_n", "edge_sim", "hypotheses", "refine_iters", "seed")),
+          "consensus": ("consensus_correspondence", ("seeds", "members", "refine_iters")),
+          "fgr": ("fgr_correspondence", ("tuple_test", "tuple_scale", "max_tuples", "fgr_iterations", "refine_iters", "seed"))}
+
+
+def _pose_from_corr(eng, pose, xs, xr, corr, counts, max_dist, T_init=None, **opts):
+    """The pose stage of ``register_feat`` / ``register_fpfh`` / ``inference_align``: 'ransac' (seeded sampling), 'consensus' (spatial
+    compatibility) or 'fgr' (tuple pre-filter and graduated Gauss-Newton).  Of ``opts`` the estimator takes the keywords it knows."""
+    if pose not in _POSES:
+        raise ValueError("pose must be 'ransac', 'consensus' or 'fgr'")
+    method, names = _POSES[pose]
+    kw = {("iterations" if k == "fgr_iterations" else k): v for k, v in opts.items() if k in names}
+    return getattr(eng, method)(xs, xr, corr, max_dist, counts=counts, T_init=T_init, **kw)[0]
 
 
 @torch.no_grad()
@@ -361,8 +357,9 @@ def register_feat(pairs: Sequence[Dict[str, np.ndarray]], model, voxel_size: flo
         xs, xr = ep["pt_src"].permute(0, 2, 1).contiguous(), ep["pt_ref"].permute(0, 2, 1).contiguous()
         corr, counts = eng.feature_correspondences(ep["feat_src"].permute(0, 2, 1).contiguous(), ep["feat_ref"].permute(0, 2, 1).contiguous(),
                                                    mutual=mutual, k=match_k, ratio=match_ratio)
-        T = _pose_from_corr(eng, pose, xs, xr, corr, counts, 2.0 * voxel_size, ransac_n, edge_sim, hypotheses, refine_iters, seed, seeds,
-                            members, fgr_iterations, tuple_scale, max_tuples, tuple_test)
+        T = _pose_from_corr(eng, pose, xs, xr, corr, counts, 2.0 * voxel_size, ransac_n=ransac_n, edge_sim=edge_sim, hypotheses=hypotheses,
+                            refine_iters=refine_iters, seed=seed, seeds=seeds, members=members, fgr_iterations=fgr_iterations,
+                            tuple_scale=tuple_scale, max_tuples=max_tuples, tuple_test=tuple_test)
         torch.cuda.synchronize(device)
         dt = (time.time() - t0) / len(ids)
         T = T.cpu().numpy()
@@ -471,8 +468,9 @@ def register_fpfh(pairs: Sequence[Dict[str, np.ndarray]], engine, voxel_size: fl
         ds, fs, _ = _fpfh_side(engine, xs, [view(i, "src") for i in ids], radius, *nbr)
         dr, fr, _ = _fpfh_side(engine, xr, [view(i, "ref") for i in ids], radius, *nbr)
         corr, counts = engine.feature_correspondences(ds, dr, mutual=mutual, k=match_k, ratio=match_ratio)
-        T = _pose_from_corr(engine, pose, xs, xr, corr, counts, 2.0 * voxel_size, ransac_n, edge_sim, hypotheses, refine_iters, seed,
-                            seeds, members, fgr_iterations, tuple_scale, max_tuples, tuple_test)
+        T = _pose_from_corr(engine, pose, xs, xr, corr, counts, 2.0 * voxel_size, ransac_n=ransac_n, edge_sim=edge_sim, hypotheses=hypotheses,
+                            refine_iters=refine_iters, seed=seed, seeds=seeds, members=members, fgr_iterations=fgr_iterations,
+                            tuple_scale=tuple_scale, max_tuples=max_tuples, tuple_test=tuple_test)
         torch.cuda.synchronize(device)
         dt = (time.time() - t0) / len(ids)
         T = T.cpu().numpy()

@@ -8,7 +8,7 @@ Engine.fgr_correspondence, Engine.ransac_correspondence and Engine.consensus_cor
 against T_gt over the pairs.  An estimator that refuses the shape (consensus: its bit matrix) is reported as null with the refusal's
 text.  Prints one JSON line per shape.  The optimise kernel keeps one workgroup per pair busy: a call uses P of the 256 CUs in that
 phase.  Under `rocprofv3 --kernel-trace --stats -- python tools/bench_fgr.py ...` the split between the tuple selection
-(fgr_select_kernel), fgr_optimize_kernel and the tail (ransac_score / pick / weights / finish, kabsch) comes from the profiler's table."""
+(fgr_select_kernel), fgr_optimize_kernel and the tail (pose_score / pick / weights / finish, kabsch) comes from the profiler's table."""
 import argparse
 import json
 import os

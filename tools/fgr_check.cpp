@@ -45,7 +45,7 @@ int main() {
       for (int M : {1, 3, 257, 20000}) {
         const FgrLayout l(P, M, tt, 1000, 1 << 20, 2, 777);
         const size_t L = (size_t)fgr_list_rows(tt, M, 1000), NB = (size_t)fgr_blocks(fgr_candidates(tt, M, 1 << 20));
-        const size_t off[] = {l.pose.bytes, l.rows, l.blk_cnt, l.blk_pre, l.tmp, l.npts, l.hyp_T, l.hyp_valid, l.hyp_count, l.bytes};
+        const size_t off[] = {l.pose.bytes, l.rows, l.blk_cnt, l.blk_pre, l.tmp, l.npts, l.hyp.T, l.hyp.valid, l.hyp.count, l.bytes};
         const size_t need[] = {0, (size_t)P * L * 4, (size_t)P * NB * 4, (size_t)P * NB * 4, 777, (size_t)P * L * 48, (size_t)P * 48, (size_t)P * 4,
                                (size_t)P * 4};
         CHECK(l.rows == l.pose.bytes);
@@ -59,7 +59,7 @@ int main() {
           npts[(p * L + L - 1) * 6 + 5] = 1.0;
           at<int32_t>(buf.data(), l.blk_pre)[p * NB + NB - 1] = 1;
         }
-        at<int32_t>(buf.data(), l.hyp_count)[P - 1] = 1;
+        at<int32_t>(buf.data(), l.hyp.count)[P - 1] = 1;
       }
   // the solve the optimisation shares with the point-to-plane ICP refuses fewer than 6 rows: a list of one tuple moves nothing
   double A[21] = {}, b[6] = {}, x[6];

@@ -1,5 +1,5 @@
-// Stand-alone host check of deepsir_amd/csrc/scratch.h and csrc/op_layouts.h: the scratch layouts of select.hip, preprocess.hip,
-// resample.hip, ransac.hip, consensus.hip and match_targets.hip.  Every layout, at edge shapes: the parts start on 256 bytes, lie in
+// Stand-alone host check of deepsir_amd/csrc/scratch.h, csrc/op_layouts.h and csrc/fgr.h: the scratch layouts of select.hip,
+// preprocess.hip, resample.hip, ransac.hip, consensus.hip, fgr.hip and match_targets.hip.  Every layout, at edge shapes: the parts start on 256 bytes, lie in
 // declaration order, do not overlap and end inside `bytes`; and `bytes` equals the sum the operator's size function was written as
 // before the layouts existed (spelled out below, term by term), with the library's temporary size an arbitrary number on both sides.
 // Also csrc/search_plan.h's ExactScratch, the layout of the exact descriptor search (nn_match.hip, nn_topk.hip): its closed form and the
@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
+#include "fgr.h"
 #include "op_layouts.h"
 #include "search_plan.h"
 using namespace dsir;
@@ -110,15 +111,26 @@ int main() {
 
       const RansacLayout ra(pairs, M, H, R);
       CHECK(ra.pose.cs == po.cs && ra.pose.info == po.info && ra.pose.bytes == po.bytes);
-      check_parts({ra.hyp_T, ra.hyp_valid, ra.hyp_count}, {P * H * 48, P * H * 4, P * H * 4}, po.bytes, ra.bytes);
+      check_parts({ra.hyp.T, ra.hyp.valid, ra.hyp.count}, {P * H * 48, P * H * 4, P * H * 4}, po.bytes, ra.bytes);
       CHECK(ra.bytes == pose + al(P * H * 48) + 2 * al(P * H * 4));
 
       const ConsensusLayout co(pairs, M, H, R, tmp);
       CHECK(co.pose.cs == po.cs && co.pose.info == po.info && co.pose.bytes == po.bytes);
-      check_parts({co.bits, co.score, co.k0, co.k1, co.seg, co.tmp, co.seed, co.hyp_T, co.hyp_valid, co.hyp_count},
+      check_parts({co.bits, co.score, co.k0, co.k1, co.seg, co.tmp, co.seed, co.hyp.T, co.hyp.valid, co.hyp.count},
                   {P * M * W * 8, P * M * 4, P * M * 8, P * M * 8, (P + 1) * 4, tmp, P * H * 4, P * H * 48, P * H * 4, P * H * 4}, po.bytes, co.bytes);
       CHECK(co.bytes == pose + al(P * M * W * 8) + al(P * M * 4) + 2 * al(P * M * 8) + al((P + 1) * 4) + al(tmp) + al(P * H * 4) + al(P * H * 48) +
                             2 * al(P * H * 4));
+
+      // FGR: H as max_tuples, a trial cap below and above 100 x M; one candidate pose per pair
+      for (int tt = 0; tt < 2; ++tt) for (int trials : {300, 1 << 20}) {
+        const FgrLayout fg(pairs, M, tt, H, trials, R, tmp);
+        const size_t L = tt ? (size_t)3 * H : (size_t)M;
+        const size_t cand = tt ? (size_t)((int64_t)100 * M < trials ? 100 * M : trials) : (size_t)M, NB = (cand + 255) / 256;
+        CHECK(fg.pose.cs == po.cs && fg.pose.info == po.info && fg.pose.bytes == po.bytes);
+        check_parts({fg.rows, fg.blk_cnt, fg.blk_pre, fg.tmp, fg.npts, fg.hyp.T, fg.hyp.valid, fg.hyp.count},
+                    {P * L * 4, P * NB * 4, P * NB * 4, tmp, P * L * 48, P * 48, P * 4, P * 4}, po.bytes, fg.bytes);
+        CHECK(fg.bytes == pose + al(P * L * 4) + 2 * al(P * NB * 4) + al(tmp) + al(P * L * 48) + al(P * 48) + 2 * al(P * 4));
+      }
     }
   }
 
