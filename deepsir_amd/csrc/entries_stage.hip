@@ -1,5 +1,7 @@
 // The stage entries of include/dsir.h: index narrowing, the KNN pyramid, one RandLA pass and the use_ppf front end, normals,
-// FPFH, score, aggregation, and the preprocessing (voxel down-sampling, resampling).
+// FPFH, ISS keypoints, score, aggregation, and the preprocessing (voxel down-sampling, resampling).
+#include <cmath>
+
 #include "engine_ctx.h"
 
 using namespace dsir;
@@ -89,6 +91,29 @@ int dsir_fpfh(dsir_ctx* c, const float* points, int stride, const float* normals
   a.cols = fixed ? neigh : csr_cols; a.neigh_cs = neigh_cs; a.offsets = csr_offsets;
   a.desc = desc; a.out_ld = out_ld; a.flags = flags; a.n = n; a.clouds = clouds;
   if (!launch_fpfh(a, c->stream)) return fail(c, "dsir_fpfh: shape refused");
+  return call.finish();
+}
+
+int dsir_iss_keypoints(dsir_ctx* c, const float* points, int stride, const int32_t* sal_offsets, const int32_t* sal_cols,
+                       const int32_t* nms_offsets, const int32_t* nms_cols, int clouds, int n, double gamma_21, double gamma_32,
+                       int min_neighbors, float* saliency, int32_t* mask, int32_t* index, int32_t* counts) {
+  Call call(c); if (call.refused()) return 1;
+  if (!points || !sal_offsets || !sal_cols || !nms_offsets || !nms_cols || !saliency || !mask || !index || !counts)
+    return fail(c, "dsir_iss_keypoints: a null pointer among points, the two CSR lists and the four outputs");
+  if (clouds < 1 || clouds > 65535 || n < 1 || stride < 3)
+    return fail(c, "dsir_iss_keypoints: clouds in [1, 65535], n >= 1 and stride >= 3 expected, got clouds=%d n=%d stride=%d", clouds, n, stride);
+  if (!(gamma_21 > 0.0) || !(gamma_32 > 0.0) || std::isinf(gamma_21) || std::isinf(gamma_32))
+    return fail(c, "dsir_iss_keypoints: gamma_21 and gamma_32 must be finite and positive, got %g and %g", gamma_21, gamma_32);
+  if (min_neighbors < 1) return fail(c, "dsir_iss_keypoints: min_neighbors >= 1 expected, got %d", min_neighbors);
+  if ((int64_t)clouds * n > 0x7fffffffll - 1) return fail(c, "dsir_iss_keypoints: clouds x n = %lld rows beyond the int32 range of the offsets", (long long)clouds * n);
+  IssArgs a;
+  a.block_counts = reinterpret_cast<int32_t*>(c->ws.raw(iss_scratch_bytes(clouds, n)));
+  if (c->ws.overflow) return fail(c, "workspace too small for dsir_iss_keypoints (raise max_points / max_pairs)");
+  a.pts = points; a.pts_cs = (int64_t)n * stride; a.pts_ld = stride;
+  a.sal_offsets = sal_offsets; a.sal_cols = sal_cols; a.nms_offsets = nms_offsets; a.nms_cols = nms_cols;
+  a.gamma_21 = gamma_21; a.gamma_32 = gamma_32; a.min_neighbors = min_neighbors;
+  a.saliency = saliency; a.mask = mask; a.index = index; a.counts = counts; a.n = n; a.clouds = clouds;
+  if (!launch_iss_keypoints(a, c->stream)) return fail(c, "dsir_iss_keypoints: shape refused");
   return call.finish();
 }
 

@@ -219,6 +219,22 @@ struct FpfhArgs {
 size_t fpfh_scratch_bytes(int clouds, int n);
 bool launch_fpfh(const FpfhArgs& a, hipStream_t st);                  // false: outside the envelope (nothing launched)
 
+// iss.hip - ISS keypoints from a salient and a non-max CSR (the rule: the file's header).  Three launches: saliency (16 lanes per
+// row), selection (row scan + per-workgroup counts), compaction (ranks by ballots).
+struct IssArgs {
+  const float* pts = nullptr; int64_t pts_cs = 0; int pts_ld = 3;     // [clouds][n][pts_ld], 3 columns used
+  const int32_t *sal_offsets = nullptr, *sal_cols = nullptr;          // CSR [clouds * n + 1] / cloud-local columns: stage 1
+  const int32_t *nms_offsets = nullptr, *nms_cols = nullptr;          // the same for stage 2
+  double gamma_21 = 0.975, gamma_32 = 0.975;
+  int min_neighbors = 5;
+  float* saliency = nullptr;                                          // [clouds][n]
+  int32_t *mask = nullptr, *index = nullptr, *counts = nullptr;       // [clouds][n], [clouds][n], [clouds]
+  int32_t* block_counts = nullptr;                                    // scratch (iss_scratch_bytes)
+  int n = 0, clouds = 0;
+};
+size_t iss_scratch_bytes(int clouds, int n);
+bool launch_iss_keypoints(const IssArgs& a, hipStream_t st);          // false: outside the envelope (nothing launched)
+
 // mlp_out + fc_label fused (head_mlp.hip): x[32] -> feat[64] -> 64 -> 32 -> ncls   (RandLANet.py:363-367)
 struct HeadArgs {
   Seg in = {};                  // last decoder block, [clouds][M][32], lazy GroupNorm + LeakyReLU

@@ -159,6 +159,7 @@ class Engine:
         out = self._empty(t.shape, torch.int32)
         self._pre()
         self._call(self.lib.dsir_narrow_i64(self.h, _ptr(t), _ptr(out), t.numel()))
+        self.sync()                     # as every other stage: the result is ready for torch's stream when the call returns
         return out
 
     def knn_pyramid(self, points: torch.Tensor):
@@ -274,6 +275,44 @@ class Engine:
                                       c, n, _ptr(desc), int(pad_to), _ptr(flags)))
         self.sync()
         return desc, flags
+
+    def iss_keypoints(self, points, salient_radius=None, non_max_radius=None, gamma_21: float = 0.975, gamma_32: float = 0.975,
+                      min_neighbors: int = 5, csr_salient=None, csr_nms=None):
+        """ISS keypoints (include/dsir.h, dsir_iss_keypoints; the rule: csrc/iss.hip, restated in deepsir_amd/iss.py): points [c,n,>=3]
+        and, for each of the two stages, exactly one of a radius (the CSR is then ``radius_neighbors(points, r, 0)``) and a CSR
+        (offsets [c n + 1] i32, cols i32 with cloud-local columns, self included: what ``radius_neighbors`` returns) - the salient
+        neighbourhoods whose covariance gives the saliency, and the non-max neighbourhoods a keypoint must dominate ->
+        (index [c,n] i32: a cloud's keypoints in ascending point index, -1 beyond its count; counts [c] i32; saliency [c,n] f32;
+        mask [c,n] i32).  Two radii build two cell indices (``NNIndex`` serves one radius).  Needs no weights.  Raises ValueError
+        for arguments refused on the host (shapes, gammas, min_neighbors, the radius / CSR choice), EngineError where the library
+        refuses."""
+        points = _chk(points, torch.float32, "points")
+        if points.dim() != 3 or points.shape[2] < 3 or points.shape[0] < 1 or points.shape[1] < 1:
+            raise ValueError("iss_keypoints: points [clouds >= 1, n >= 1, C >= 3] expected")
+        for name, r, csr in (("salient", salient_radius, csr_salient), ("non_max", non_max_radius, csr_nms)):
+            if (r is None) == (csr is None):
+                raise ValueError(f"iss_keypoints: exactly one of {name}_radius and the {name} CSR expected")
+        g21, g32 = float(gamma_21), float(gamma_32)
+        if not (np.isfinite(g21) and g21 > 0.0 and np.isfinite(g32) and g32 > 0.0):
+            raise ValueError(f"iss_keypoints: gamma_21 and gamma_32 must be finite and positive, got {gamma_21} and {gamma_32}")
+        if int(min_neighbors) != min_neighbors or min_neighbors < 1 or min_neighbors > 0x7fffffff:
+            raise ValueError(f"iss_keypoints: min_neighbors must be a positive int32, got {min_neighbors}")
+        c, n, stride = points.shape
+        if csr_salient is None:
+            csr_salient = self.radius_neighbors(points, float(salient_radius), 0)
+        if csr_nms is None:
+            same = salient_radius is not None and float(non_max_radius) == float(salient_radius)
+            csr_nms = csr_salient if same else self.radius_neighbors(points, float(non_max_radius), 0)
+        so, sc = self._csr(csr_salient, c * n, "iss_keypoints")
+        no, nc = (so, sc) if csr_nms is csr_salient else self._csr(csr_nms, c * n, "iss_keypoints")
+        saliency = self._empty((c, n))
+        mask, index = self._empty((c, n), torch.int32), self._empty((c, n), torch.int32)
+        counts = self._empty((c,), torch.int32)
+        self._pre()
+        self._call(self.lib.dsir_iss_keypoints(self.h, _ptr(points), stride, _ptr(so), _ptr(sc), _ptr(no), _ptr(nc), c, n, g21, g32,
+                                               int(min_neighbors), _ptr(saliency), _ptr(mask), _ptr(index), _ptr(counts)))
+        self.sync()
+        return index, counts, saliency, mask
 
     def score(self, feat, logits, xyz_multi, neigh_multi):
         """torch.max(logits) + score_fun counterpart -> (score [c,n], label [c,n] i32)."""

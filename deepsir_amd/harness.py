@@ -413,6 +413,35 @@ def _fpfh_side(engine, pts, viewpoints, radius, search="brute", max_nn=0, normal
     return desc, flags, normals
 
 
+def _register_on_keypoints(engine, xs, xr, ds, dr, iss_kw, min_keypoints, pose, max_dist, match_kw, pose_kw):
+    """The matching and pose stages of ``register_fpfh(keypoints="iss")`` for one batch: xs / xr [B, N, C] points, ds / dr [B, N, 64]
+    descriptors of every point.  One ``iss_keypoints`` call per side, then per pair the gather of the keypoint rows (all rows where
+    either side has fewer than ``min_keypoints``) and one-pair calls of ``feature_correspondences`` and the pose stage.
+    -> (T [B, 3, 4], per pair corr [count, 2] int32 numpy in ORIGINAL point indices, per pair (idx_src, idx_ref, fell_back))."""
+    sides = []
+    for x in (xs, xr):
+        index, counts, _, _ = engine.iss_keypoints(x, **iss_kw)
+        sides.append((index, counts.cpu().numpy()))
+    Ts, corrs, kpts = [], [], []
+    for j in range(xs.shape[0]):
+        ks, kr = int(sides[0][1][j]), int(sides[1][1][j])
+        fell_back = ks < min_keypoints or kr < min_keypoints
+        if fell_back:
+            sel = [torch.arange(x.shape[1], dtype=torch.int32, device=x.device) for x in (xs, xr)]
+            px, pr, qs, qr = xs[j:j + 1].contiguous(), xr[j:j + 1].contiguous(), ds[j:j + 1].contiguous(), dr[j:j + 1].contiguous()
+        else:
+            sel = [sides[0][0][j, :ks], sides[1][0][j, :kr]]
+            rows_s, rows_r = sel[0].long(), sel[1].long()
+            px, pr = xs[j, rows_s][None].contiguous(), xr[j, rows_r][None].contiguous()
+            qs, qr = ds[j, rows_s][None].contiguous(), dr[j, rows_r][None].contiguous()
+        corr, counts = engine.feature_correspondences(qs, qr, **match_kw)
+        Ts.append(_pose_from_corr(engine, pose, px, pr, corr, counts, max_dist, **pose_kw))
+        cc = corr[0, :int(counts[0])].long()
+        corrs.append(torch.stack([sel[0][cc[:, 0]], sel[1][cc[:, 1]]], 1).to(torch.int32).cpu().numpy().reshape(-1, 2))
+        kpts.append((sel[0].cpu().numpy(), sel[1].cpu().numpy(), bool(fell_back)))
+    return torch.cat(Ts, 0), corrs, kpts
+
+
 @torch.no_grad()
 def register_fpfh(pairs: Sequence[Dict[str, np.ndarray]], engine, voxel_size: float = 0.3, radius: Optional[float] = None,
                   hypotheses: int = 8192, mutual: bool = True, num_reg: int = 1, dataset_type: str = "3DMatch", batch: int = 1,
@@ -420,7 +449,9 @@ def register_fpfh(pairs: Sequence[Dict[str, np.ndarray]], engine, voxel_size: fl
                   want_corr: bool = False, pose: str = "ransac", seeds: int = 64, members: int = 32, match_k: int = 1,
                   match_ratio: float = 0.0, search: str = "brute", max_nn: int = 0, normal_radius: Optional[float] = None,
                   normal_max_nn: int = 0, fgr_iterations: int = 64, tuple_scale: float = 0.95, max_tuples: int = 1000,
-                  tuple_test: bool = True):
+                  tuple_test: bool = True, keypoints: Optional[str] = None, salient_radius: Optional[float] = None,
+                  non_max_radius: Optional[float] = None, gamma_21: float = 0.975, gamma_32: float = 0.975, min_neighbors: int = 5,
+                  min_keypoints: int = 32, want_keypoints: bool = False):
     """The weight-independent baseline of ``register_feat``: FPFH + feature-matching RANSAC (open3d compute_fpfh_feature ->
     registration_ransac_based_on_feature_matching; parity unpinned, the rules are the engine's own), all on the device.  Per batch
     and side: ``knn_pyramid`` -> ``estimate_normals`` on its level-0 lists (towards the pair's optional ``viewpoint_src`` /
@@ -439,6 +470,16 @@ def register_fpfh(pairs: Sequence[Dict[str, np.ndarray]], engine, voxel_size: fl
     normal_max_nn = 30, radius = 5 voxel, max_nn = 100, search = "grid"``.  With ``normal_radius`` and ``radius`` both set and
     ``search="grid"`` no pyramid is built, so clouds under 1024 points work, up to what the FPFH, correspondence and pose entries take.
 
+    ``keypoints="iss"``: match and solve on ISS keypoints only (``Engine.iss_keypoints``, csrc/iss.hip; ``salient_radius`` default
+    6 x voxel size, ``non_max_radius`` default 4 x voxel size - open3d's multiples of the resolution with the voxel size standing in
+    for it -, ``gamma_21``, ``gamma_32``, ``min_neighbors``).  Normals and descriptors are still computed on every point (SPFH needs
+    the neighbours); then, per pair, the keypoint rows of points and descriptors are gathered and ``feature_correspondences`` and the
+    pose stage run on them as a batch of ONE pair (the counts are ragged), so a pair's result does not depend on ``batch``.  A pair
+    with fewer than ``min_keypoints`` keypoints on either side uses all of its points (the same one-pair calls).  ``corr`` under
+    ``want_corr`` holds original point indices.  ``want_keypoints`` appends one more value: per pair (idx_src, idx_ref, fell_back),
+    the original indices matched on (all points after a fall-back; with ``keypoints=None`` every pair is (all, all, False)).
+    ``keypoints=None`` (the default) is the path above, unchanged.
+
     ``engine`` is a ``deepsir_amd.engine.Engine`` THE CALLER PREPARED: the descriptor itself needs no weights, but the pyramid and
     the other existing entries this calls refuse a context whose weights are not loaded (``Call::kWeights``, csrc/engine_ctx.h), so
     load a state dict first - any, e.g. ``weights.generate_state_dict(cfg, 0)``; its values are never read here.  Its max_points /
@@ -453,9 +494,18 @@ def register_fpfh(pairs: Sequence[Dict[str, np.ndarray]], engine, voxel_size: fl
         raise ValueError("register_fpfh: max_nn needs radius and search='grid' (the brute-force lists have no cap)")
     if normal_max_nn > 0 and normal_radius is None:
         raise ValueError("register_fpfh: normal_max_nn needs normal_radius")
+    if keypoints not in (None, "iss"):
+        raise ValueError(f"register_fpfh: keypoints must be None or 'iss', got {keypoints!r}")
+    if min_keypoints < 1:
+        raise ValueError("register_fpfh: min_keypoints >= 1 expected")
     nbr = (search, int(max_nn), normal_radius, int(normal_max_nn))
     rte_t, rre_t = THRESHOLDS[dataset_type]
-    preds, corrs, stats = [], [], np.zeros((len(pairs), 5))
+    preds, corrs, kpts, stats = [], [], [], np.zeros((len(pairs), 5))
+    iss_kw = dict(salient_radius=float(6.0 * voxel_size if salient_radius is None else salient_radius),
+                  non_max_radius=float(4.0 * voxel_size if non_max_radius is None else non_max_radius),
+                  gamma_21=gamma_21, gamma_32=gamma_32, min_neighbors=min_neighbors)
+    pose_kw = dict(ransac_n=ransac_n, edge_sim=edge_sim, hypotheses=hypotheses, refine_iters=refine_iters, seed=seed, seeds=seeds,
+                   members=members, fgr_iterations=fgr_iterations, tuple_scale=tuple_scale, max_tuples=max_tuples, tuple_test=tuple_test)
 
     def view(i, side):
         v = pairs[i].get("viewpoint_" + side)
@@ -467,16 +517,24 @@ def register_fpfh(pairs: Sequence[Dict[str, np.ndarray]], engine, voxel_size: fl
         xs, xr = data["points_src"].float().contiguous(), data["points_ref"].float().contiguous()
         ds, fs, _ = _fpfh_side(engine, xs, [view(i, "src") for i in ids], radius, *nbr)
         dr, fr, _ = _fpfh_side(engine, xr, [view(i, "ref") for i in ids], radius, *nbr)
-        corr, counts = engine.feature_correspondences(ds, dr, mutual=mutual, k=match_k, ratio=match_ratio)
-        T = _pose_from_corr(engine, pose, xs, xr, corr, counts, 2.0 * voxel_size, ransac_n=ransac_n, edge_sim=edge_sim, hypotheses=hypotheses,
-                            refine_iters=refine_iters, seed=seed, seeds=seeds, members=members, fgr_iterations=fgr_iterations,
-                            tuple_scale=tuple_scale, max_tuples=max_tuples, tuple_test=tuple_test)
+        if keypoints is None:
+            corr, counts = engine.feature_correspondences(ds, dr, mutual=mutual, k=match_k, ratio=match_ratio)
+            T = _pose_from_corr(engine, pose, xs, xr, corr, counts, 2.0 * voxel_size, **pose_kw)
+            pair_corr = None
+        else:
+            T, pair_corr, pair_kpts = _register_on_keypoints(engine, xs, xr, ds, dr, iss_kw, int(min_keypoints), pose, 2.0 * voxel_size,
+                                                             dict(mutual=mutual, k=match_k, ratio=match_ratio), pose_kw)
+            kpts += pair_kpts
         torch.cuda.synchronize(device)
         dt = (time.time() - t0) / len(ids)
         T = T.cpu().numpy()
         preds.append(np.repeat(T[:, None], num_reg, 1))
         gt = data["transform_gt"].cpu().numpy() if "transform_gt" in data else None
-        if want_corr:
+        if want_keypoints and keypoints is None:
+            kpts += [(np.arange(xs.shape[1], dtype=np.int32), np.arange(xr.shape[1], dtype=np.int32), False) for _ in ids]
+        if want_corr and pair_corr is not None:
+            corrs += [(pair_corr[j], fs[j].cpu().numpy(), fr[j].cpu().numpy()) for j in range(len(ids))]
+        elif want_corr:
             cn, cc = counts.cpu().numpy(), corr.cpu().numpy()
             corrs += [(cc[j, :cn[j]], fs[j].cpu().numpy(), fr[j].cpu().numpy()) for j in range(len(ids))]
         for j, i in enumerate(ids):
@@ -486,7 +544,7 @@ def register_fpfh(pairs: Sequence[Dict[str, np.ndarray]], engine, voxel_size: fl
             others = pairs[i].get("others")
             stats[i, 4] = _seq_id(others[0]["seq"]) if others else -1
     pred = np.concatenate(preds, 0) if preds else np.zeros((0, num_reg, 3, 4), np.float32)
-    return (pred, stats, corrs) if want_corr else (pred, stats)
+    return (pred, stats) + ((corrs,) if want_corr else ()) + ((kpts,) if want_keypoints else ())
 
 
 @torch.no_grad()

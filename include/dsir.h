@@ -168,6 +168,21 @@ int dsir_fpfh(dsir_ctx* ctx, const float* points, int stride, const float* norma
               int64_t neigh_cloud_stride, const int32_t* csr_offsets, const int32_t* csr_cols, int clouds, int n, float* desc,
               int out_ld, int32_t* flags);
 
+/* ISS keypoints (intrinsic shape signatures; open3d's compute_iss_keypoints, unpinned here: the rule is this engine's own, stated in
+ * csrc/iss.hip and restated in deepsir_amd/iss.py).  points [clouds][n][stride] (xyz first); two CSR lists with cloud-local columns,
+ * self included, in the layout dsir_fpfh takes (offsets [clouds * n + 1], non-decreasing and inside cols; columns are clamped into
+ * the cloud): the salient neighbourhoods (stage 1) and the non-maximum-suppression neighbourhoods (stage 2).  Stage 1: a row of
+ * fewer than min_neighbors entries, a covariance that is not finite or all zero, or eigenvalues e1 >= e2 >= e3 of the fp64
+ * covariance that fail e2 / e1 < gamma_21 or e3 / e2 < gamma_32 give saliency 0, else (float)e3.  Stage 2: a point is a keypoint iff
+ * its saliency is > 0, its non-max row has at least min_neighbors entries, and no entry of that row has a larger saliency, or an
+ * equal one and a lower index (exact duplicates yield one keypoint, where open3d keeps both).  -> saliency [clouds][n] f32, mask
+ * [clouds][n] i32, index [clouds][n] i32 (the cloud's keypoints ascending, then -1), counts [clouds] i32.  Refused with a message,
+ * launching nothing: a null pointer, clouds < 1, n < 1, stride < 3, a gamma that is not finite and positive, min_neighbors < 1.
+ * No atomics: same bytes on every run; clouds are independent, bit for bit.  Any context serves (no weights needed). */
+int dsir_iss_keypoints(dsir_ctx* ctx, const float* points, int stride, const int32_t* sal_offsets, const int32_t* sal_cols,
+                       const int32_t* nms_offsets, const int32_t* nms_cols, int clouds, int n, double gamma_21, double gamma_32,
+                       int min_neighbors, float* saliency, int32_t* mask, int32_t* index, int32_t* counts);
+
 /* Replaces torch.max(logits,1) + Network.feat_score/score_fun with num_sub<=0
  * (network/model.py:638-644, :668-757).
  * feat [clouds][n][64], logits [clouds][n][ncls], xyz [clouds][n][3],
