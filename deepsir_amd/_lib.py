@@ -120,6 +120,12 @@ SYMBOLS = {
                                       C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "dsir_icp_correspondences": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p,
                                            C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # the same on clouds of unequal sizes: per-pair row counts (counts_src, counts_ref) appended
+    "dsir_icp_refine_ex3": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int,
+                                      C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                      C.c_void_p]),
+    "dsir_icp_correspondences_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p,
+                                              C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dsir_ransac_correspondence": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                              C.c_int, C.c_float, C.c_int, C.c_float, C.c_int, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_void_p, C.POINTER(dsir_ransac_diag)]),
@@ -270,6 +276,8 @@ SYMBOLS = {
     # scene registration: edge information matrices (csrc/info_matrix.hip) and the pose graph (csrc/pose_graph.hip)
     "dsir_information_matrix": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p,
                                           C.c_int, C.c_void_p, C.c_void_p]),
+    "dsir_information_matrix_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p,
+                                             C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dsir_pose_graph_scratch_bytes": (C.c_size_t, [C.c_int, c_i32_p, c_i32_p, c_i32_p]),
     "dsir_pose_graph_optimize": (C.c_int, [C.c_void_p, C.c_int, c_i32_p, c_i32_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, c_i32_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -36,7 +36,7 @@ static IcpSearch icp_search_mode(int search) {
 
 struct IcpCorrOut { int32_t* idx; float* d2; double* stats; };
 
-// What the four ICP entries share: the checks under the entry's own `name`, the workspace reset, the scratch, the normals
+// What the ICP entries share (a.counts_src / a.counts_ref set by the _ex3 / _ex entries, nullptr by the others: clamped, not refused): the checks under the entry's own `name`, the workspace reset, the scratch, the normals
 // (normals_ref [pairs][K][3], or columns 3..5 of the points_ref rows) and the launch; corr != nullptr: one search step, not the loop.
 static int icp_entry(dsir_ctx* c, const char* name, IcpArgs a, const float* normals_ref, int search, const IcpCorrOut* corr) {
   Call call(c); if (call.refused()) return 1;
@@ -94,11 +94,29 @@ int dsir_icp_refine_ex2(dsir_ctx* c, const float* points_src, const float* point
   return icp_entry(c, "dsir_icp_refine_ex2", a, normals_ref, search, nullptr);
 }
 
+int dsir_icp_refine_ex3(dsir_ctx* c, const float* points_src, const float* points_ref, int pairs, int J, int K, int stride,
+                        float max_corr_dist, int max_iter, float rel_fitness, float rel_rmse, const float* T_init, float* T_out,
+                        int estimator, const float* normals_ref, int search, double* stats, const int32_t* counts_src, const int32_t* counts_ref) {
+  IcpArgs a = icp_args(points_src, points_ref, pairs, J, K, stride, max_corr_dist, max_iter, rel_fitness, rel_rmse, T_init, T_out, estimator);
+  a.stats5_out = stats;
+  a.counts_src = counts_src; a.counts_ref = counts_ref;
+  return icp_entry(c, "dsir_icp_refine_ex3", a, normals_ref, search, nullptr);
+}
+
 int dsir_icp_correspondences(dsir_ctx* c, const float* points_src, const float* points_ref, int pairs, int J, int K, int stride,
                              float max_corr_dist, const float* T, int search, int32_t* idx_out, float* d2_out, double* stats_out) {
   const IcpArgs a = icp_args(points_src, points_ref, pairs, J, K, stride, max_corr_dist, 0, 0.f, 0.f, T, nullptr, 0);
   const IcpCorrOut out{idx_out, d2_out, stats_out};
   return icp_entry(c, "dsir_icp_correspondences", a, nullptr, search, &out);
+}
+
+int dsir_icp_correspondences_ex(dsir_ctx* c, const float* points_src, const float* points_ref, int pairs, int J, int K, int stride,
+                                float max_corr_dist, const float* T, int search, int32_t* idx_out, float* d2_out, double* stats_out,
+                                const int32_t* counts_src, const int32_t* counts_ref) {
+  IcpArgs a = icp_args(points_src, points_ref, pairs, J, K, stride, max_corr_dist, 0, 0.f, 0.f, T, nullptr, 0);
+  a.counts_src = counts_src; a.counts_ref = counts_ref;
+  const IcpCorrOut out{idx_out, d2_out, stats_out};
+  return icp_entry(c, "dsir_icp_correspondences_ex", a, nullptr, search, &out);
 }
 
 // What the three pose-from-correspondences entries share, under the entry's own `name`: the Call scope and the checks of the common

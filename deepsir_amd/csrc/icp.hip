@@ -33,6 +33,18 @@
 // points; its first workgroup composes T and hands the pair's `done` flag to the next search.  The partition depends on J alone,
 // so a pair's result depends neither on the run nor on the other pairs of the call.  An iteration is four launches, as in the
 // point-to-point loop (flags, Kabsch, search, statistics there; sums, step, search, statistics here).
+//
+// ---- Clouds of unequal sizes (IcpArgs::counts_src / counts_ref, dsir_icp_refine_ex3 and dsir_icp_correspondences_ex): J and K are the
+// row capacities of the arrays and the strides of every scratch part; pair p works on its first Jp = pair_rows(counts_src, p, J)
+// source and Kp = pair_rows(counts_ref, p, K) reference rows.  Every kernel stops at the pair's own count - the apply, the search
+// (slices of Kp; query blocks beyond Jp write "no correspondence" and leave block-uniformly), the statistics (fitness = matched / Jp,
+// 0 for Jp == 0), the Kabsch kernels (KabschArgs::counts), the plane sums and the move (chunks of Jp: last = min(Jp, first +
+// kIcpPlaneChunk), icp_plane_chunks(Jp) slots added) - so a padding row is never read into anything that reaches an output, and
+// every partition is the one the pair has in a call of its own: pair p gets, byte for byte, what the dense call on its first Jp
+// and Kp rows alone writes.  A pair with Jp == 0 or Kp == 0 has no correspondence: identity updates (the Kabsch kernels' frozen step,
+// the plane step's "fewer than 6 rows"), T carried over bit for bit, fitness and RMSE 0, frozen by the first convergence test.
+// As before: no floating-point atomics, no scratch shared between pairs, the same bytes on every run, and a pair's bytes do not
+// depend on the other pairs of the call - their counts included.  Without counts every launch, grid and byte is what it was.
 #include "kernels.h"
 #include "device_utils.h"
 #include "icp_layout.h"
@@ -45,12 +57,13 @@ constexpr int QB = 64;      // queries per block (one per lane)
 constexpr int NW = 4;       // waves per block = support slices
 constexpr int TILE = 256;   // support points staged per wave per step
 
-// cur[pair][j] = T[pair] * src[pair][j]
-__global__ void icp_apply_kernel(const float* __restrict__ src, int stride, int J, const float* __restrict__ T,
-                                 float* __restrict__ cur) {
+// cur[pair][j] = T[pair] * src[pair][j] for the pair's own rows (J: the row capacity)
+__global__ void icp_apply_kernel(const float* __restrict__ src, int stride, int J, const int32_t* __restrict__ counts_src,
+                                 const float* __restrict__ T, float* __restrict__ cur) {
   const int pair = blockIdx.y;
   const float* t = T + (int64_t)pair * 12;
-  for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < J; j += gridDim.x * blockDim.x) {
+  const int Jp = pair_rows(counts_src, pair, J);
+  for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < Jp; j += gridDim.x * blockDim.x) {
     const float* p = src + ((int64_t)pair * J + j) * stride;
     const float x = p[0], y = p[1], z = p[2];
     float* o = cur + ((int64_t)pair * J + j) * 3;
@@ -60,7 +73,8 @@ __global__ void icp_apply_kernel(const float* __restrict__ src, int stride, int 
 }
 
 __global__ __launch_bounds__(QB * NW) void icp_nn_kernel(const float* __restrict__ cur, const float* __restrict__ ref,
-                                                         int ref_stride, int J, int K, float r2,
+                                                         int ref_stride, int J, int K, const int32_t* __restrict__ counts_src,
+                                                         const int32_t* __restrict__ counts_ref, float r2,
                                                          int32_t* __restrict__ idx, float* __restrict__ d2,
                                                          const int32_t* __restrict__ skip) {
   // a converged pair keeps the correspondences of its last search: its points no longer move (block-uniform exit)
@@ -70,13 +84,19 @@ __global__ __launch_bounds__(QB * NW) void icp_nn_kernel(const float* __restrict
   __shared__ int mi[NW][QB];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int pair = blockIdx.y;
+  const int Jp = pair_rows(counts_src, pair, J), Kp = pair_rows(counts_ref, pair, K);   // the pair's own rows; J, K: the capacities
   const float* Q = cur + (int64_t)pair * J * 3;
   const float* S = ref + (int64_t)pair * K * ref_stride;
   const int q = blockIdx.x * QB + lane;
+  if (blockIdx.x * QB >= Jp) {   // a block of padding rows only: "no correspondence", and out before the first barrier (block-uniform)
+    if (w == 0 && q < J) { idx[(int64_t)pair * J + q] = -1; d2[(int64_t)pair * J + q] = 0.f; }
+    return;
+  }
   float qx = 0.f, qy = 0.f, qz = 0.f;
-  if (q < J) { qx = Q[(int64_t)q * 3]; qy = Q[(int64_t)q * 3 + 1]; qz = Q[(int64_t)q * 3 + 2]; }
-  const int slice = (K + NW - 1) / NW;
-  const int s_begin = w * slice, s_end = min(K, s_begin + slice);
+  if (q < Jp) { qx = Q[(int64_t)q * 3]; qy = Q[(int64_t)q * 3 + 1]; qz = Q[(int64_t)q * 3 + 2]; }
+  // the slices are a function of Kp alone (block-uniform trip counts); the arg-min with ties to the lower index does not depend on them
+  const int slice = (Kp + NW - 1) / NW;
+  const int s_begin = w * slice, s_end = min(Kp, s_begin + slice);
   float bd = INFINITY;
   int bi = -1;
   for (int t0 = 0; t0 < slice; t0 += TILE) {
@@ -103,23 +123,25 @@ __global__ __launch_bounds__(QB * NW) void icp_nn_kernel(const float* __restrict
       const float d = md[s][lane];
       if (d < bd) { bd = d; bi = mi[s][lane]; }   // slices are ascending in index: strict < keeps the lower index on a tie
     }
-    const bool in = bi >= 0 && bd <= r2;
+    const bool in = q < Jp && bi >= 0 && bd <= r2;            // a padding row of the last block: -1 and 0, whatever it met
     idx[(int64_t)pair * J + q] = in ? bi : -1;
     d2[(int64_t)pair * J + q] = in ? bd : 0.f;
   }
 }
 
-// per pair: fitness = |corr| / J, inlier RMSE = sqrt(sum d2 / |corr|); convergence test against the previous values;
-// correspondences turned into (clamped index, 0/1 weight) for the Kabsch kernel.  state = {fitness, rmse, done, iterations}
+// per pair: fitness = |corr| / Jp (0 for a pair without source rows), inlier RMSE = sqrt(sum d2 / |corr|); convergence test against
+// the previous values; correspondences turned into (clamped index, 0/1 weight) for the Kabsch kernel.  state = {fitness, rmse, done,
+// iterations}.  Jp = the pair's own rows of the capacity J; the rows beyond are neither read nor written.
 __global__ __launch_bounds__(256) void icp_stats_kernel(int32_t* __restrict__ idx, const float* __restrict__ d2,
-                                                        float* __restrict__ w, int J, int check, float rel_fitness,
-                                                        float rel_rmse, double* __restrict__ state) {
+                                                        float* __restrict__ w, int J, const int32_t* __restrict__ counts_src, int check,
+                                                        float rel_fitness, float rel_rmse, double* __restrict__ state) {
   __shared__ double s_cnt[4], s_sse[4];
   const int pair = blockIdx.x;
   double* st = state + (int64_t)pair * 4;
   if (st[2] != 0.0) return;   // converged earlier: frozen (block-uniform)
+  const int Jp = pair_rows(counts_src, pair, J);
   double cnt = 0.0, sse = 0.0;
-  for (int j = threadIdx.x; j < J; j += 256) {
+  for (int j = threadIdx.x; j < Jp; j += 256) {
     const int64_t o = (int64_t)pair * J + j;
     const int i = idx[o];
     const bool in = i >= 0;
@@ -134,7 +156,7 @@ __global__ __launch_bounds__(256) void icp_stats_kernel(int32_t* __restrict__ id
   if (threadIdx.x == 0) {
     cnt = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
     sse = s_sse[0] + s_sse[1] + s_sse[2] + s_sse[3];
-    const double fitness = cnt / (double)J;
+    const double fitness = Jp > 0 ? cnt / (double)Jp : 0.0;
     const double rmse = cnt > 0.0 ? sqrt(sse / cnt) : 0.0;
     if (check) {
       st[3] += 1.0;
@@ -146,11 +168,12 @@ __global__ __launch_bounds__(256) void icp_stats_kernel(int32_t* __restrict__ id
 
 // one search step's {fitness, inlier RMSE} in icp_stats_kernel's summation order, the correspondences left as the search wrote them
 __global__ __launch_bounds__(256) void icp_corr_stats_kernel(const int32_t* __restrict__ idx, const float* __restrict__ d2, int J,
-                                                             double* __restrict__ out) {
+                                                             const int32_t* __restrict__ counts_src, double* __restrict__ out) {
   __shared__ double s_cnt[4], s_sse[4];
   const int pair = blockIdx.x;
+  const int Jp = pair_rows(counts_src, pair, J);
   double cnt = 0.0, sse = 0.0;
-  for (int j = threadIdx.x; j < J; j += 256) {
+  for (int j = threadIdx.x; j < Jp; j += 256) {
     const int64_t o = (int64_t)pair * J + j;
     const bool in = idx[o] >= 0;
     cnt += in ? 1.0 : 0.0;
@@ -162,7 +185,7 @@ __global__ __launch_bounds__(256) void icp_corr_stats_kernel(const int32_t* __re
   if (threadIdx.x == 0) {
     cnt = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
     sse = s_sse[0] + s_sse[1] + s_sse[2] + s_sse[3];
-    out[(int64_t)pair * 2] = cnt / (double)J;
+    out[(int64_t)pair * 2] = Jp > 0 ? cnt / (double)Jp : 0.0;
     out[(int64_t)pair * 2 + 1] = cnt > 0.0 ? sqrt(sse / cnt) : 0.0;
   }
 }
@@ -190,14 +213,16 @@ struct PlaneNormals { const float* N; int64_t cs; int ld; };
 
 __global__ __launch_bounds__(PT) void icp_plane_accum_kernel(const float* __restrict__ cur, const float* __restrict__ ref, int ref_stride,
                                                              PlaneNormals nrm, const int32_t* __restrict__ idx,
-                                                             const float* __restrict__ w, int J, int K,
+                                                             const float* __restrict__ w, int J, int K, const int32_t* __restrict__ counts_src,
                                                              const double* __restrict__ state, double* __restrict__ part) {
   __shared__ double sh[(PT / 64 + 1) * kIcpPlaneSums];
   const int pair = blockIdx.y, ch = blockIdx.x;
   if (state[(int64_t)pair * 4 + 2] != 0.0) return;   // converged: the step is the identity (block-uniform)
+  const int Jp = pair_rows(counts_src, pair, J);
+  if (ch >= icp_plane_chunks(Jp)) return;            // a chunk of padding rows only: no slot of the pair's sum (block-uniform)
   const float* S = ref + (int64_t)pair * K * ref_stride;
   const float* N = nrm.N + pair * nrm.cs;
-  const int first = ch * kIcpPlaneChunk, last = min(J, first + kIcpPlaneChunk);
+  const int first = ch * kIcpPlaneChunk, last = min(Jp, first + kIcpPlaneChunk);
   double v[kIcpPlaneSums];
 #pragma unroll
   for (int k = 0; k < kIcpPlaneSums; ++k) v[k] = 0.0;
@@ -228,7 +253,9 @@ __global__ __launch_bounds__(PT) void icp_plane_accum_kernel(const float* __rest
     part[((int64_t)pair * gridDim.x + ch) * kIcpPlaneSlots + threadIdx.x] = sh[(PT / 64) * kIcpPlaneSums + threadIdx.x];
 }
 
-__global__ __launch_bounds__(PT) void icp_plane_step_kernel(float* __restrict__ cur, int J, int nch, const double* __restrict__ part,
+// nch: the slots a pair has (the capacity's chunks); the pair's sum adds the icp_plane_chunks(Jp) of them that its own rows fill
+__global__ __launch_bounds__(PT) void icp_plane_step_kernel(float* __restrict__ cur, int J, const int32_t* __restrict__ counts_src, int nch,
+                                                            const double* __restrict__ part,
                                                             const double* __restrict__ state, const float* __restrict__ T_prev,
                                                             float* __restrict__ T_cum, double* __restrict__ nsing,
                                                             int32_t* __restrict__ skip) {
@@ -244,9 +271,11 @@ __global__ __launch_bounds__(PT) void icp_plane_step_kernel(float* __restrict__ 
       for (int k = 0; k < 12; ++k) T_cum[pair * 12 + k] = T_prev[pair * 12 + k];
     return;
   }
+  const int Jp = pair_rows(counts_src, pair, J);
   if (threadIdx.x < kIcpPlaneSums) {
     double s = 0.0;
-    for (int c = 0; c < nch; ++c) s += part[((int64_t)pair * nch + c) * kIcpPlaneSlots + threadIdx.x];   // chunk order
+    const int used = icp_plane_chunks(Jp);
+    for (int c = 0; c < used; ++c) s += part[((int64_t)pair * nch + c) * kIcpPlaneSlots + threadIdx.x];   // chunk order
     tot[threadIdx.x] = s;
   }
   __syncthreads();
@@ -273,7 +302,7 @@ __global__ __launch_bounds__(PT) void icp_plane_step_kernel(float* __restrict__ 
   __syncthreads();
   if (!s_move) return;                                      // identity update: the points keep their bits (block-uniform)
   const int j = blockIdx.x * PT + threadIdx.x;
-  if (j < J) {
+  if (j < Jp) {
     float* p = cur + ((int64_t)pair * J + j) * 3;
     const float x = p[0], y = p[1], z = p[2];
 #pragma unroll
@@ -315,6 +344,7 @@ void step_point(const IcpArgs& a, const IcpParts& s, const float* Tp, float* Tn,
   k.src = s.cur; k.ref = a.ref; k.idx = s.idx; k.w = s.w; k.src_stride = (int64_t)a.J * 3; k.ref_stride = (int64_t)a.K * a.stride;
   k.ref_ld = a.stride; k.sigmoid = 0; k.pairs = a.pairs; k.m = a.J; k.T = s.Tstep; k.invalid = nullptr;
   k.src_out = s.cur; k.src_out_stride = (int64_t)a.J * 3; k.T_prev = Tp; k.T_cum = Tn; k.T_stride = 12; k.skip = s.skip;
+  k.counts = a.counts_src; k.ref_counts = a.counts_ref;   // a pair without a source or a reference row: the frozen step, no row of it read
   launch_kabsch(k, st);
 }
 
@@ -323,15 +353,16 @@ void step_plane(const IcpArgs& a, const IcpParts& s, const float* Tp, float* Tn,
   const int nch = icp_plane_chunks(a.J);
   hipLaunchKernelGGL(icp_plane_accum_kernel, dim3(nch, a.pairs), dim3(PT), 0, st, (const float*)s.cur, a.ref, a.stride,
                      PlaneNormals{a.normals, a.normals_cs, a.normals_ld}, (const int32_t*)s.idx, (const float*)s.w, a.J, a.K,
-                     (const double*)s.state, s.part);
-  hipLaunchKernelGGL(icp_plane_step_kernel, dim3((a.J + PT - 1) / PT, a.pairs), dim3(PT), 0, st, s.cur, a.J, nch, (const double*)s.part,
+                     a.counts_src, (const double*)s.state, s.part);
+  hipLaunchKernelGGL(icp_plane_step_kernel, dim3((a.J + PT - 1) / PT, a.pairs), dim3(PT), 0, st, s.cur, a.J, a.counts_src, nch, (const double*)s.part,
                      (const double*)s.state, Tp, Tn, s.nsing, s.skip);
 }
 
 // the search of cur [pairs][J][3]: the grid's kernel with an index (built by the caller), else the brute force
 void search(const IcpArgs& a, const IcpGrid* grid, const float* cur, float r2, int32_t* idx, float* d2, const int32_t* skip, hipStream_t st) {
-  if (grid) { launch_icp_nn_grid(*grid, cur, a.pairs, a.J, a.K, r2, idx, d2, skip, st); return; }
-  hipLaunchKernelGGL(icp_nn_kernel, dim3((a.J + QB - 1) / QB, a.pairs), dim3(QB * NW), 0, st, cur, a.ref, a.stride, a.J, a.K, r2, idx, d2, skip);
+  if (grid) { launch_icp_nn_grid(*grid, cur, a.pairs, a.J, a.K, a.counts_src, a.counts_ref, r2, idx, d2, skip, st); return; }
+  hipLaunchKernelGGL(icp_nn_kernel, dim3((a.J + QB - 1) / QB, a.pairs), dim3(QB * NW), 0, st, cur, a.ref, a.stride, a.J, a.K, a.counts_src, a.counts_ref,
+                     r2, idx, d2, skip);
 }
 
 }  // namespace
@@ -348,19 +379,19 @@ int launch_icp_refine(const IcpArgs& a, void* scratch, hipStream_t st) {
   const float r2 = a.max_corr_dist * a.max_corr_dist;
   hipMemsetAsync(s.state, 0, (size_t)pairs * 32, st);
   hipMemcpyAsync(s.Ta, a.T_init, (size_t)pairs * 48, hipMemcpyDeviceToDevice, st);
-  hipLaunchKernelGGL(icp_apply_kernel, dim3((J + 255) / 256, pairs), dim3(256), 0, st, a.src, a.stride, J, s.Ta, s.cur);
+  hipLaunchKernelGGL(icp_apply_kernel, dim3((J + 255) / 256, pairs), dim3(256), 0, st, a.src, a.stride, J, a.counts_src, s.Ta, s.cur);
   IcpGrid grid{};
   const IcpGrid* g = a.search != IcpSearch::Brute ? &grid : nullptr;
   if (g)
-    if (const int e = icp_grid_build(a.ref, a.stride, s.cur, pairs, J, a.K, a.max_corr_dist, a.search == IcpSearch::Grid, s.grid, st, &grid)) return e;
+    if (const int e = icp_grid_build(a.ref, a.stride, s.cur, pairs, J, a.K, a.counts_src, a.counts_ref, a.max_corr_dist, a.search == IcpSearch::Grid, s.grid, st, &grid)) return e;
   search(a, g, s.cur, r2, s.idx, s.d2, nullptr, st);
-  hipLaunchKernelGGL(icp_stats_kernel, dim3(pairs), dim3(256), 0, st, s.idx, s.d2, s.w, J, 0, a.rel_fitness, a.rel_rmse, s.state);
+  hipLaunchKernelGGL(icp_stats_kernel, dim3(pairs), dim3(256), 0, st, s.idx, s.d2, s.w, J, a.counts_src, 0, a.rel_fitness, a.rel_rmse, s.state);
   float *Tp = s.Ta, *Tn = s.Tb;
   for (int it = 0; it < a.max_iter; ++it) {
     if (plane) step_plane(a, s, Tp, Tn, st);
     else step_point(a, s, Tp, Tn, st);
     search(a, g, s.cur, r2, s.idx, s.d2, s.skip, st);
-    hipLaunchKernelGGL(icp_stats_kernel, dim3(pairs), dim3(256), 0, st, s.idx, s.d2, s.w, J, 1, a.rel_fitness, a.rel_rmse, s.state);
+    hipLaunchKernelGGL(icp_stats_kernel, dim3(pairs), dim3(256), 0, st, s.idx, s.d2, s.w, J, a.counts_src, 1, a.rel_fitness, a.rel_rmse, s.state);
     float* t = Tp; Tp = Tn; Tn = t;
   }
   hipMemcpyAsync(a.T_out, Tp, (size_t)pairs * 48, hipMemcpyDeviceToDevice, st);
@@ -377,15 +408,15 @@ size_t icp_corr_scratch_bytes(const IcpArgs& a) { return IcpCorrLayout(a.pairs, 
 int launch_icp_correspondences(const IcpArgs& a, int32_t* idx_out, float* d2_out, double* stats_out, void* scratch, hipStream_t st) {
   const IcpCorrLayout l(a.pairs, a.J, grid_bytes(a));
   float* cur = reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) + l.cur);
-  hipLaunchKernelGGL(icp_apply_kernel, dim3((a.J + 255) / 256, a.pairs), dim3(256), 0, st, a.src, a.stride, a.J, a.T_init, cur);
+  hipLaunchKernelGGL(icp_apply_kernel, dim3((a.J + 255) / 256, a.pairs), dim3(256), 0, st, a.src, a.stride, a.J, a.counts_src, a.T_init, cur);
   IcpGrid grid{};
   const IcpGrid* g = a.search != IcpSearch::Brute ? &grid : nullptr;
   if (g)
-    if (const int e = icp_grid_build(a.ref, a.stride, cur, a.pairs, a.J, a.K, a.max_corr_dist, a.search == IcpSearch::Grid,
+    if (const int e = icp_grid_build(a.ref, a.stride, cur, a.pairs, a.J, a.K, a.counts_src, a.counts_ref, a.max_corr_dist, a.search == IcpSearch::Grid,
                                      reinterpret_cast<char*>(scratch) + l.grid, st, &grid))
       return e;
   search(a, g, cur, a.max_corr_dist * a.max_corr_dist, idx_out, d2_out, nullptr, st);
-  if (stats_out) hipLaunchKernelGGL(icp_corr_stats_kernel, dim3(a.pairs), dim3(256), 0, st, (const int32_t*)idx_out, (const float*)d2_out, a.J, stats_out);
+  if (stats_out) hipLaunchKernelGGL(icp_corr_stats_kernel, dim3(a.pairs), dim3(256), 0, st, (const int32_t*)idx_out, (const float*)d2_out, a.J, a.counts_src, stats_out);
   return 0;
 }
 

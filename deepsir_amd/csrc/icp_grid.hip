@@ -45,6 +45,14 @@
 // reasons and the build's figures.  The same `skip` early-out as icp_nn_kernel.
 // No atomics on floating-point values, no scratch shared between pairs (csrc/icp_grid.h: part p of every array is pair p's), no
 // dependence on the order of arrival: two runs write the same bytes and a pair's bytes do not depend on the other pairs of the call.
+//
+// Clouds of unequal sizes (counts_src / counts_ref of IcpArgs; J, K the row capacities and the strides of every part): the bounds, the
+// lattice, the keys and the gather see a pair's own rows only; a padding row - reference or query - is not read and gets KEY_NONE,
+// so it sorts last, behind the pair's own non-finite rows and in index order (both sorts are stable; the SEG_MAX choice stays a
+// function of the capacity), and lies in no interval.  The first Kp sorted positions and the first Jp entries of the query order are
+// therefore those of the pair indexed alone, and the search takes Kp as the length of the pair's keys: the same probes, the same
+// runs, the same bytes as for a pair of J = Jp, K = Kp.  Query groups t >= Jp write -1 and 0.f and leave (whole groups: the xor
+// exchanges stay inside a group); a pair with Kp == 0 walks nothing.  The guarantees above hold as stated, counts included.
 #include <hipcub/hipcub.hpp>
 #include <hip/hip_runtime.h>
 
@@ -63,11 +71,11 @@ constexpr int UNROLL = 4;    // positions a lane has in flight
 constexpr int SEG_MAX = 4095;   // longer segments are sorted pair by pair with the device-wide sort: the segmented sort gives a
                                 // segment to one workgroup (10^5 keys: 3.4 ms measured on the MI355X)
 
-// lo [3 pairs], hi [3 pairs]: min / max xyz of each pair's finite reference rows, as ordered integers
-__global__ __launch_bounds__(256) void icp_grid_bounds_kernel(const float* __restrict__ ref, int stride, int K, int pairs,
-                                                              uint32_t* __restrict__ enc) {
+// lo [3 pairs], hi [3 pairs]: min / max xyz of each pair's finite reference rows (its own rows of the capacity K), as ordered integers
+__global__ __launch_bounds__(256) void icp_grid_bounds_kernel(const float* __restrict__ ref, int stride, int K, const int32_t* __restrict__ counts_ref,
+                                                              int pairs, uint32_t* __restrict__ enc) {
   const int pair = blockIdx.y;
-  finite_bounds_accumulate(ref + (int64_t)pair * K * stride, stride, K, (int64_t)blockIdx.x * blockDim.x + threadIdx.x,
+  finite_bounds_accumulate(ref + (int64_t)pair * K * stride, stride, pair_rows(counts_ref, pair, K), (int64_t)blockIdx.x * blockDim.x + threadIdx.x,
                            (int64_t)gridDim.x * blockDim.x, enc + pair * 3, enc + (pairs + pair) * 3);
 }
 
@@ -89,31 +97,38 @@ __global__ void icp_grid_lattice_kernel(const uint32_t* __restrict__ enc, int pa
   lat[p] = icp_grid_lattice(r, lo, hi, any);
 }
 
-// keys [pairs][n], vals [pairs][n] = the row's index inside its pair; rows of `stride` floats
-__global__ __launch_bounds__(256) void icp_grid_key_kernel(const float* __restrict__ pts, int stride, int n, const IcpLattice* __restrict__ lat,
-                                                           uint64_t* __restrict__ keys, uint32_t* __restrict__ vals) {
+// keys [pairs][n], vals [pairs][n] = the row's index inside its pair; rows of `stride` floats.  A row at or beyond the pair's count
+// is not read and gets KEY_NONE: the sorts are stable, so the padding sorts last, behind the pair's own non-finite rows, in index
+// order, and the first count positions of the sorted pair are those of the pair sorted alone
+__global__ __launch_bounds__(256) void icp_grid_key_kernel(const float* __restrict__ pts, int stride, int n, const int32_t* __restrict__ counts,
+                                                           const IcpLattice* __restrict__ lat, uint64_t* __restrict__ keys, uint32_t* __restrict__ vals) {
   const int pair = blockIdx.y;
   const IcpLattice L = lat[pair];
+  const int np = pair_rows(counts, pair, n);
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
     const int64_t o = (int64_t)pair * n + i;
     const float* p = pts + o * stride;
-    keys[o] = point_key(p[0], p[1], p[2], L);
+    keys[o] = i < np ? point_key(p[0], p[1], p[2], L) : KEY_NONE;
     vals[o] = (uint32_t)i;
   }
 }
 
-// sorted [pairs][K] = (x, y, z, original index) in key order
-__global__ __launch_bounds__(256) void icp_grid_gather_kernel(const float* __restrict__ ref, int stride, int K, const uint32_t* __restrict__ vals,
-                                                              float4* __restrict__ sorted) {
+// sorted [pairs][K] = (x, y, z, original index) in key order; of a pair with a count its first count positions, which hold its own rows
+__global__ __launch_bounds__(256) void icp_grid_gather_kernel(const float* __restrict__ ref, int stride, int K, const int32_t* __restrict__ counts_ref,
+                                                              const uint32_t* __restrict__ vals, float4* __restrict__ sorted) {
   const int pair = blockIdx.y;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < K; i += gridDim.x * blockDim.x) {
+  const int Kp = pair_rows(counts_ref, pair, K);
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < Kp; i += gridDim.x * blockDim.x) {
     const int64_t o = (int64_t)pair * K + i;
     const uint32_t v = vals[o];
     sorted[o] = gather_xyzi(ref + ((int64_t)pair * K + v) * stride, v);
   }
 }
 
-__global__ __launch_bounds__(GB) void icp_nn_grid_kernel(const float* __restrict__ cur, int J, int K, const uint64_t* __restrict__ keys,
+// J, K: the row capacities (the strides of every per-pair array); the pair searches its first Kp sorted positions for its first Jp
+// queries in cell order, exactly as the kernel does for a pair of J = Jp, K = Kp alone
+__global__ __launch_bounds__(GB) void icp_nn_grid_kernel(const float* __restrict__ cur, int J, int K, const int32_t* __restrict__ counts_src,
+                                                         const int32_t* __restrict__ counts_ref, const uint64_t* __restrict__ keys,
                                                          const float4* __restrict__ sorted, const int32_t* __restrict__ perm,
                                                          const IcpLattice* __restrict__ lat, float r2, int32_t* __restrict__ idx,
                                                          float* __restrict__ d2, const int32_t* __restrict__ skip) {
@@ -124,30 +139,35 @@ __global__ __launch_bounds__(GB) void icp_nn_grid_kernel(const float* __restrict
   const int sub = (int)(g % SUB);
   if (g / SUB >= J) return;                                        // whole groups leave: the shuffles below stay inside a group
   const int t = (int)(g / SUB);
+  const int Jp = pair_rows(counts_src, pair, J), Kp = pair_rows(counts_ref, pair, K);
+  if (t >= Jp) {                                                   // a padding row (position t of the query order is row t: the padding
+    if (sub == 0) { idx[(int64_t)pair * J + t] = -1; d2[(int64_t)pair * J + t] = 0.f; }   // sorts last, in index order): whole groups leave
+    return;
+  }
   const int q = perm ? perm[(int64_t)pair * J + t] : t;
   const float* c = cur + ((int64_t)pair * J + q) * 3;
   const float x = c[0], y = c[1], z = c[2];
   float bd = INFINITY;
   int bi = -1;
-  if (finite3(x, y, z)) {                                          // uniform in a group
+  if (finite3(x, y, z) && Kp > 0) {                                // uniform in a group
     const IcpLattice L = lat[pair];
     const int cx = cell_of(x, L.ox, L.h), cy = cell_of(y, L.oy, L.h), cz = cell_of(z, L.oz, L.h);
     const uint64_t* Kk = keys + (int64_t)pair * K;
     const float4* S = sorted + (int64_t)pair * K;
     walk_key_intervals(cx, cy, cz, -1, MAXC + 1, -1, MAXC + 1, [&](uint64_t klo, uint64_t khi) {
       // lane `sub` of the group takes positions lo + sub, lo + sub + SUB, ..: the group's loads are SUB neighbouring rows
-      for (int64_t i = (int64_t)key_lower_bound(Kk, K, klo) + sub; i < K; i += UNROLL * SUB) {
+      for (int64_t i = (int64_t)key_lower_bound(Kk, Kp, klo) + sub; i < Kp; i += UNROLL * SUB) {
         uint64_t k[UNROLL];
         float4 s[UNROLL];
 #pragma unroll
         for (int u = 0; u < UNROLL; ++u) {
-          const int64_t ii = min(i + (int64_t)u * SUB, (int64_t)K - 1);                              // never past the pair's K
+          const int64_t ii = min(i + (int64_t)u * SUB, (int64_t)Kp - 1);                             // never past the pair's Kp
           k[u] = Kk[ii]; s[u] = S[ii];
         }
         bool more = true;
 #pragma unroll
         for (int u = 0; u < UNROLL; ++u) {
-          const bool in = i + (int64_t)u * SUB < K && k[u] <= khi;   // keys ascend: the first position outside ends the lane's run
+          const bool in = i + (int64_t)u * SUB < Kp && k[u] <= khi;   // keys ascend: the first position outside ends the lane's run
           more = more && in;
           const float e2 = dist2_rn(s[u], x, y, z);
           const int ti = (int)__float_as_uint(s[u].w);
@@ -209,8 +229,10 @@ size_t icp_grid_scratch_bytes(int pairs, int J, int K) {
 }
 
 // cur [pairs][J][3]: the source points moved by T_init (the query order is taken from them; order = false: original numbering)
-int icp_grid_build(const float* ref, int stride, const float* cur, int pairs, int J, int K, float r, bool order, void* scratch,
-                   hipStream_t st, IcpGrid* out) {
+// counts_src / counts_ref (nullable): the pairs' own rows.  The segments of both sorts stay the capacities J and K (so does the SEG_MAX
+// choice): padding rows carry KEY_NONE and both sorts are stable, so a pair's own rows come out in the order of the pair sorted alone.
+int icp_grid_build(const float* ref, int stride, const float* cur, int pairs, int J, int K, const int32_t* counts_src, const int32_t* counts_ref,
+                   float r, bool order, void* scratch, hipStream_t st, IcpGrid* out) {
   if (!icp_grid_shape_ok(pairs, J, K) || !icp_grid_radius_ok(r) || !scratch || !out) return (int)hipErrorInvalidValue;
   const IcpGridLayout lay = layout(pairs, J, K);
   IcpLattice* lat = at<IcpLattice>(scratch, lay.lat);
@@ -227,14 +249,14 @@ int icp_grid_build(const float* ref, int stride, const float* cur, int pairs, in
   if (hipMemsetAsync(enc, 0xff, (size_t)pairs * 3 * sizeof(uint32_t), st) != hipSuccess ||
       hipMemsetAsync(enc + (size_t)pairs * 3, 0, (size_t)pairs * 3 * sizeof(uint32_t), st) != hipSuccess)
     return (int)hipGetLastError();
-  hipLaunchKernelGGL(icp_grid_bounds_kernel, dim3(blocks_for(K), pairs), dim3(256), 0, st, ref, stride, K, pairs, enc);
+  hipLaunchKernelGGL(icp_grid_bounds_kernel, dim3(blocks_for(K), pairs), dim3(256), 0, st, ref, stride, K, counts_ref, pairs, enc);
   hipLaunchKernelGGL(icp_grid_lattice_kernel, dim3((pairs + 256) / 256), dim3(256), 0, st, (const uint32_t*)enc, pairs, J, K, r, lat, off_ref,
                      off_qry);
-  hipLaunchKernelGGL(icp_grid_key_kernel, dim3(blocks_for(K), pairs), dim3(256), 0, st, ref, stride, K, (const IcpLattice*)lat, keys_raw, vals_raw);
+  hipLaunchKernelGGL(icp_grid_key_kernel, dim3(blocks_for(K), pairs), dim3(256), 0, st, ref, stride, K, counts_ref, (const IcpLattice*)lat, keys_raw, vals_raw);
   if (!sort_pairs(at<char>(scratch, lay.tmp), lay.tmp_bytes, keys_raw, keys, vals_raw, vals, pairs, K, off_ref, st)) return (int)hipErrorUnknown;
-  hipLaunchKernelGGL(icp_grid_gather_kernel, dim3(blocks_for(K), pairs), dim3(256), 0, st, ref, stride, K, (const uint32_t*)vals, sorted);
+  hipLaunchKernelGGL(icp_grid_gather_kernel, dim3(blocks_for(K), pairs), dim3(256), 0, st, ref, stride, K, counts_ref, (const uint32_t*)vals, sorted);
   if (order) {
-    hipLaunchKernelGGL(icp_grid_key_kernel, dim3(blocks_for(J), pairs), dim3(256), 0, st, cur, 3, J, (const IcpLattice*)lat, keys_raw, vals_raw);
+    hipLaunchKernelGGL(icp_grid_key_kernel, dim3(blocks_for(J), pairs), dim3(256), 0, st, cur, 3, J, counts_src, (const IcpLattice*)lat, keys_raw, vals_raw);
     if (!sort_pairs(at<char>(scratch, lay.tmp), lay.tmp_bytes, keys_raw, keys_qry, vals_raw, reinterpret_cast<uint32_t*>(perm), pairs, J, off_qry, st))
       return (int)hipErrorUnknown;
   }
@@ -242,9 +264,10 @@ int icp_grid_build(const float* ref, int stride, const float* cur, int pairs, in
   return (int)hipGetLastError();
 }
 
-void launch_icp_nn_grid(const IcpGrid& g, const float* cur, int pairs, int J, int K, float r2, int32_t* idx, float* d2, const int32_t* skip,
-                        hipStream_t st) {
-  hipLaunchKernelGGL(icp_nn_grid_kernel, dim3((unsigned)(((int64_t)J * SUB + GB - 1) / GB), pairs), dim3(GB), 0, st, cur, J, K, (const uint64_t*)g.keys,
+void launch_icp_nn_grid(const IcpGrid& g, const float* cur, int pairs, int J, int K, const int32_t* counts_src, const int32_t* counts_ref, float r2,
+                        int32_t* idx, float* d2, const int32_t* skip, hipStream_t st) {
+  hipLaunchKernelGGL(icp_nn_grid_kernel, dim3((unsigned)(((int64_t)J * SUB + GB - 1) / GB), pairs), dim3(GB), 0, st, cur, J, K, counts_src, counts_ref,
+                     (const uint64_t*)g.keys,
                      reinterpret_cast<const float4*>(g.sorted), g.perm, reinterpret_cast<const IcpLattice*>(g.lat), r2, idx, d2, skip);
 }
 

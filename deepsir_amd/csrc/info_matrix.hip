@@ -13,6 +13,11 @@
 // pair), wave butterflies, then the waves in order, into the chunk's own slot; info_finish_kernel, one thread per sum, adds a pair's
 // slots in chunk order and writes the 36 entries and the count.  No atomics: the partition depends on J alone, so a pair's bytes
 // depend neither on the run nor on the other pairs of the call.  A pair without a correspondence gets the zero matrix and count 0.
+// Clouds of unequal sizes (dsir_information_matrix_ex: per-pair counts, J and K the row capacities): the search is
+// launch_icp_correspondences' with the same counts; the chunks are those of the pair's own Jp rows (last = min(Jp, first +
+// kIcpPlaneChunk); chunks at or beyond icp_plane_chunks(Jp) leave without writing, and that many slots are added), so pair p gets,
+// byte for byte, the matrix and count of the dense call on its first Jp and Kp rows alone.  Jp == 0 or Kp == 0: the zero matrix, count 0.
+// No atomics, no scratch shared between pairs, the same bytes on every run - with counts as without.
 #include "device_utils.h"
 #include "engine_ctx.h"
 #include "icp_grid.h"
@@ -42,17 +47,20 @@ struct InfoLayout {
 };
 
 __global__ __launch_bounds__(PT) void info_accum_kernel(const float* __restrict__ ref, int ref_stride, const int32_t* __restrict__ idx,
-                                                        int J, int K, double* __restrict__ part) {
+                                                        int J, int K, const int32_t* __restrict__ counts_src,
+                                                        const int32_t* __restrict__ counts_ref, double* __restrict__ part) {
   __shared__ double sh[(PT / 64 + 1) * kInfoSums];
   const int pair = blockIdx.y, ch = blockIdx.x;
+  const int Jp = pair_rows(counts_src, pair, J), Kp = pair_rows(counts_ref, pair, K);   // the pair's own rows; J, K: the capacities
+  if (ch >= icp_plane_chunks(Jp)) return;                 // a chunk of padding rows only: no slot of the pair's sum (block-uniform)
   const float* S = ref + (int64_t)pair * K * ref_stride;
-  const int first = ch * kIcpPlaneChunk, last = min(J, first + kIcpPlaneChunk);
+  const int first = ch * kIcpPlaneChunk, last = min(Jp, first + kIcpPlaneChunk);
   double v[kInfoSums];
 #pragma unroll
   for (int k = 0; k < kInfoSums; ++k) v[k] = 0.0;
   for (int j = first + threadIdx.x; j < last; j += PT) {
     const int64_t i = idx[(int64_t)pair * J + j];
-    if (i < 0 || i >= K) continue;                        // no correspondence (the search writes -1 .. K-1 only)
+    if (i < 0 || i >= Kp) continue;                       // no correspondence (the search writes -1 .. Kp-1 only)
     const double x = (double)S[i * ref_stride], y = (double)S[i * ref_stride + 1], z = (double)S[i * ref_stride + 2];
     v[0] += 1.0; v[1] += x; v[2] += y; v[3] += z;
     v[4] += x * x; v[5] += y * y; v[6] += z * z; v[7] += x * y; v[8] += x * z; v[9] += y * z;
@@ -62,13 +70,15 @@ __global__ __launch_bounds__(PT) void info_accum_kernel(const float* __restrict_
     part[((int64_t)pair * gridDim.x + ch) * kInfoSlots + threadIdx.x] = sh[(PT / 64) * kInfoSums + threadIdx.x];
 }
 
-__global__ __launch_bounds__(64) void info_finish_kernel(const double* __restrict__ part, int nch, double* __restrict__ info,
-                                                         int32_t* __restrict__ count) {
+// nch: the slots a pair has (the capacity's chunks); the pair's sum adds the icp_plane_chunks(Jp) of them that its own rows fill
+__global__ __launch_bounds__(64) void info_finish_kernel(const double* __restrict__ part, int nch, int J, const int32_t* __restrict__ counts_src,
+                                                         double* __restrict__ info, int32_t* __restrict__ count) {
   __shared__ double t[kInfoSums];
   const int pair = blockIdx.x;
   if (threadIdx.x < kInfoSums) {
     double s = 0.0;
-    for (int c = 0; c < nch; ++c) s += part[((int64_t)pair * nch + c) * kInfoSlots + threadIdx.x];   // chunk order
+    const int used = icp_plane_chunks(pair_rows(counts_src, pair, J));
+    for (int c = 0; c < used; ++c) s += part[((int64_t)pair * nch + c) * kInfoSlots + threadIdx.x];   // chunk order
     t[threadIdx.x] = s;
   }
   __syncthreads();
@@ -99,27 +109,43 @@ __global__ __launch_bounds__(64) void info_finish_kernel(const double* __restric
 
 using namespace dsir;
 
-extern "C" int dsir_information_matrix(dsir_ctx* c, const float* points_src, const float* points_ref, int pairs, int J, int K, int stride,
-                                       float max_corr_dist, const float* T, int search, double* info_out, int32_t* count_out) {
+// both entries: the checks under the entry's own `name`, the search of launch_icp_correspondences, the sums
+static int info_entry(dsir_ctx* c, const char* name, const float* points_src, const float* points_ref, int pairs, int J, int K, int stride,
+                      float max_corr_dist, const float* T, int search, double* info_out, int32_t* count_out, const int32_t* counts_src,
+                      const int32_t* counts_ref) {
   Call call(c); if (call.refused()) return 1;
   if (!points_src || !points_ref || !T || !info_out || !count_out || pairs < 1 || J < 1 || K < 1 || stride < 3 || !(max_corr_dist > 0.f) ||
       (search != 0 && search != 1))
-    return fail(c, "dsir_information_matrix: bad arguments");
+    return fail(c, "%s: bad arguments", name);
   if (search == 1 && (!icp_grid_radius_ok(max_corr_dist) || !icp_grid_shape_ok(pairs, J, K)))
-    return fail(c, "dsir_information_matrix: bad arguments (the grid search needs a max_corr_dist whose fp32 square is finite, and "
-                   "pairs x J and pairs x K below 2^31)");
+    return fail(c, "%s: bad arguments (the grid search needs a max_corr_dist whose fp32 square is finite, and "
+                   "pairs x J and pairs x K below 2^31)", name);
   IcpArgs a{};
   a.src = points_src; a.ref = points_ref; a.pairs = pairs; a.J = J; a.K = K; a.stride = stride; a.max_corr_dist = max_corr_dist;
+  a.counts_src = counts_src; a.counts_ref = counts_ref;
   a.T_init = T; a.search = search == 1 ? IcpSearch::Grid : IcpSearch::Brute;
   const InfoLayout l(pairs, J, icp_corr_scratch_bytes(a));
   void* scratch = c->ws.raw(l.bytes);
-  if (c->ws.overflow) return fail(c, "workspace too small for dsir_information_matrix (raise max_points / max_pairs)");
+  if (c->ws.overflow) return fail(c, "workspace too small for %s (raise max_points / max_pairs)", name);
   int32_t* idx = at<int32_t>(scratch, l.idx);
   if (const int e = launch_icp_correspondences(a, idx, at<float>(scratch, l.d2), nullptr, at<char>(scratch, l.corr), c->stream))
-    return fail(c, "dsir_information_matrix: the index build failed (HIP error %d)", e);
+    return fail(c, "%s: the index build failed (HIP error %d)", name, e);
   const int nch = icp_plane_chunks(J);
   double* part = at<double>(scratch, l.part);
-  hipLaunchKernelGGL(info_accum_kernel, dim3(nch, pairs), dim3(PT), 0, c->stream, points_ref, stride, (const int32_t*)idx, J, K, part);
-  hipLaunchKernelGGL(info_finish_kernel, dim3(pairs), dim3(64), 0, c->stream, (const double*)part, nch, info_out, count_out);
+  hipLaunchKernelGGL(info_accum_kernel, dim3(nch, pairs), dim3(PT), 0, c->stream, points_ref, stride, (const int32_t*)idx, J, K, counts_src, counts_ref, part);
+  hipLaunchKernelGGL(info_finish_kernel, dim3(pairs), dim3(64), 0, c->stream, (const double*)part, nch, J, counts_src, info_out, count_out);
   return call.finish();
+}
+
+extern "C" int dsir_information_matrix_ex(dsir_ctx* c, const float* points_src, const float* points_ref, int pairs, int J, int K, int stride,
+                                          float max_corr_dist, const float* T, int search, double* info_out, int32_t* count_out,
+                                          const int32_t* counts_src, const int32_t* counts_ref) {
+  return info_entry(c, "dsir_information_matrix_ex", points_src, points_ref, pairs, J, K, stride, max_corr_dist, T, search, info_out, count_out,
+                    counts_src, counts_ref);
+}
+
+extern "C" int dsir_information_matrix(dsir_ctx* c, const float* points_src, const float* points_ref, int pairs, int J, int K, int stride,
+                                       float max_corr_dist, const float* T, int search, double* info_out, int32_t* count_out) {
+  return info_entry(c, "dsir_information_matrix", points_src, points_ref, pairs, J, K, stride, max_corr_dist, T, search, info_out, count_out,
+                    nullptr, nullptr);
 }

@@ -58,6 +58,11 @@ __device__ void kabsch_frozen(const KabschArgs& a, int pair) {
   }
 }
 
+// a pair that per-pair counts leave without a source or a reference row (kernels.h): no correspondence, the frozen step
+__device__ __forceinline__ bool pair_is_empty(const KabschArgs& a, int pair) {
+  return (a.counts && a.counts[pair] <= 0) || (a.ref_counts && a.ref_counts[pair] <= 0);
+}
+
 // thread 0 of a pair: H (fp32, as the reference forms it) -> SVD in fp64 -> R, t; the pair's transform, flag and cumulative
 // transform to global memory, the transform to sT (12 floats) for the apply step
 __device__ void kabsch_solve(const KabschArgs& a, int pair, const double (&v9)[9], const float (&cs)[3], const float (&ct)[3], float* sT) {
@@ -202,8 +207,8 @@ __global__ __launch_bounds__(NTHR) void kabsch_kernel(const KabschArgs a) {
   __shared__ double sh[NWAVE * 9 + 9];
   __shared__ float sT[12];
   const int pair = blockIdx.x;
-  const int m = a.m;
-  if (a.skip && a.skip[pair]) {   // block-uniform
+  const int m = pair_rows(a.counts, pair, a.m);   // the pair's own points; a.m stays the stride of idx, w and matched_out (block-uniform)
+  if ((a.skip && a.skip[pair]) || pair_is_empty(a, pair)) {   // block-uniform
     if (threadIdx.x == 0) kabsch_frozen(a, pair);
     return;
   }
@@ -225,7 +230,7 @@ __global__ __launch_bounds__(NTHR) void kabsch_kernel(const KabschArgs a) {
   __syncthreads();
   if (a.src_out || a.matched_out) {
     float* so = a.src_out ? a.src_out + pair * a.src_out_stride : nullptr;
-    float* mo = a.matched_out ? a.matched_out + (int64_t)pair * m * 3 : nullptr;
+    float* mo = a.matched_out ? a.matched_out + (int64_t)pair * a.m * 3 : nullptr;
     for (int i = threadIdx.x; i < m; i += NTHR) stream_apply(p, so, mo, i, sT);
   }
 }
@@ -240,8 +245,8 @@ __global__ __launch_bounds__(NTHR) void kabsch_reg_kernel(const KabschArgs a) {
   __shared__ double sh[NWAVE * 9 + 9];
   __shared__ float sT[12];
   const int pair = blockIdx.x;
-  const int m = a.m;
-  if (a.skip && a.skip[pair]) {   // block-uniform
+  const int m = pair_rows(a.counts, pair, a.m);   // the pair's own points; a.m stays the stride of idx, w and matched_out (block-uniform)
+  if ((a.skip && a.skip[pair]) || pair_is_empty(a, pair)) {   // block-uniform
     if (threadIdx.x == 0) kabsch_frozen(a, pair);
     return;
   }
@@ -289,7 +294,7 @@ __global__ __launch_bounds__(NTHR) void kabsch_reg_kernel(const KabschArgs a) {
   __syncthreads();
   if (a.src_out || a.matched_out) {
     float* so = a.src_out ? a.src_out + pair * a.src_out_stride : nullptr;
-    float* mo = a.matched_out ? a.matched_out + (int64_t)pair * m * 3 : nullptr;
+    float* mo = a.matched_out ? a.matched_out + (int64_t)pair * a.m * 3 : nullptr;
 #pragma unroll
     for (int k = 0; k < TR; ++k)
       if (threadIdx.x + k * NTHR < m) {
@@ -389,7 +394,7 @@ size_t kabsch_part_bytes(int pairs, int m, int chunk_min) {
 
 void launch_kabsch(const KabschArgs& a, hipStream_t st) {
   if (a.pairs <= 0) return;
-  if (a.part && a.m >= chunked_min(a.chunk_min)) {
+  if (a.part && !a.counts && !a.ref_counts && a.m >= chunked_min(a.chunk_min)) {
     // the choice depends on the cloud size alone: a pair's pose does not depend on what else is in the batch
     const int nch = (a.m + CHUNK - 1) / CHUNK;
     const dim3 grid(nch, a.pairs);
@@ -400,7 +405,8 @@ void launch_kabsch(const KabschArgs& a, hipStream_t st) {
     if (a.src_out || a.matched_out) hipLaunchKernelGGL(kabsch_apply_kernel, dim3((a.m + 255) / 256, a.pairs), dim3(256), 0, st, a);
     return;
   }
-  // (the choice depends on the cloud size alone, and the two kernels give the same bits)
+  // (the choice depends on the cloud size alone, and the two kernels give the same bits - which is why, with per-pair counts, the
+  // capacity m may choose for every pair of the launch: a pair's bits are those of the kernel its own count would have chosen)
   static const bool no_reg = tuning_flag("DSIR_KABSCH_STREAM");      // A/B switch: the streaming kernel for every size
   if (a.m <= 5 * NTHR && !no_reg) hipLaunchKernelGGL(kabsch_reg_kernel<5>, dim3(a.pairs), dim3(NTHR), 0, st, a);
   else if (a.m <= 8 * NTHR && !no_reg) hipLaunchKernelGGL(kabsch_reg_kernel<8>, dim3(a.pairs), dim3(NTHR), 0, st, a);

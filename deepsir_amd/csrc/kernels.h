@@ -526,7 +526,20 @@ struct KabschArgs {
   double* part;          // kabsch_part_bytes(pairs, m, chunk_min) of scratch, or nullptr: clouds of chunk_min points and more are
                          // then reduced in chunks by several workgroups per pair (same formulas; the fp64 sums in another order)
   int chunk_min;         // 0 => kKabschChunkedMin
+  const int32_t* counts; // [pairs] or nullptr: pair p solves over its first pair_rows(counts, p, m) points only (ICP on unequal sizes);
+                         // m stays the row capacity of idx, w and the outputs.  The kernels test the count themselves and streaming and
+                         // register kernels give the same bits, so the pair's pose is the one a call with m = its count writes.
+                         // Not combined with `part`: with counts the chunked reduction is not taken.
+  const int32_t* ref_counts;  // [pairs] or nullptr: the rows pair p has in ref.  A pair whose count here, or in `counts`, is <= 0 has no
+                         // correspondence: it takes the step of a skipped pair (identity, T_cum = T_prev bit for bit) and none of its rows
+                         // is read - its clamped indices would point at row 0 of a reference that has none.
 };
+// the rows of pair `pair` in arrays of `cap` rows per pair: counts[pair] clamped into [0, cap]; cap without counts
+__host__ __device__ __forceinline__ int pair_rows(const int32_t* counts, int pair, int cap) {
+  if (!counts) return cap;
+  const int n = counts[pair];
+  return n < 0 ? 0 : (n > cap ? cap : n);
+}
 constexpr int kKabschChunkedMin = 16384;
 size_t kabsch_part_bytes(int pairs, int m, int chunk_min = 0);   // 0 below the threshold
 void launch_kabsch(const KabschArgs& a, hipStream_t st);
@@ -540,6 +553,9 @@ enum class IcpSearch : int {
 struct IcpArgs {
   const float* src; const float* ref;   // [pairs][J][stride], [pairs][K][stride]
   int pairs, J, K, stride;
+  const int32_t* counts_src;            // [pairs] on the device or nullptr (each alone): pair p has pair_rows(counts_src, p, J) source and
+  const int32_t* counts_ref;            // pair_rows(counts_ref, p, K) reference rows; J and K are then the row capacities.  Rows at or beyond
+                                        // a count are never read into anything that reaches an output; both nullptr: every launch as without
   float max_corr_dist; int max_iter; float rel_fitness, rel_rmse;
   const float* T_init; float* T_out;    // [pairs][3][4]
   int estimator;                        // 0 point-to-point, 1 point-to-plane
@@ -559,10 +575,11 @@ int launch_icp_correspondences(const IcpArgs& a, int32_t* idx_out, float* d2_out
 // icp_grid.hip - the cell index of the ICP search (the rule, the lattice and the containment argument: the file's header)
 struct IcpGrid { const void* keys; const void* sorted; const int32_t* perm; const void* lat; };
 size_t icp_grid_scratch_bytes(int pairs, int J, int K);   // 0 for a shape the index does not take
-int icp_grid_build(const float* ref, int stride, const float* cur, int pairs, int J, int K, float r, bool order, void* scratch,
-                   hipStream_t st, IcpGrid* out);
-void launch_icp_nn_grid(const IcpGrid& g, const float* cur, int pairs, int J, int K, float r2, int32_t* idx, float* d2, const int32_t* skip,
-                        hipStream_t st);
+// counts_src / counts_ref: IcpArgs' (nullable); J and K the row capacities
+int icp_grid_build(const float* ref, int stride, const float* cur, int pairs, int J, int K, const int32_t* counts_src, const int32_t* counts_ref,
+                   float r, bool order, void* scratch, hipStream_t st, IcpGrid* out);
+void launch_icp_nn_grid(const IcpGrid& g, const float* cur, int pairs, int J, int K, const int32_t* counts_src, const int32_t* counts_ref, float r2,
+                        int32_t* idx, float* d2, const int32_t* skip, hipStream_t st);
 
 // pose_corr.hip, ransac.hip, consensus.hip, fgr.hip — pose from a correspondence list: one front, three middles, one tail; their
 // argument structs and launchers are declared in pose_corr.h.  Here the producer of such lists, the mutual-nearest-neighbour list of

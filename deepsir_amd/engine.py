@@ -42,6 +42,20 @@ def _chk(t: torch.Tensor, dtype, name: str) -> torch.Tensor:
     return t.contiguous()
 
 
+def pair_counts(counts, P: int, cap: int, name: str):
+    """Per-pair row counts as the ICP entries take them (include/dsir.h, dsir_icp_refine_ex3): None, or [P] integers in
+    [0, cap] as a sequence, an array or a tensor -> None, or the counts as a host int32 array.  ValueError for anything else:
+    the C ABI would clamp a count, the host wrapper refuses it."""
+    if counts is None:
+        return None
+    a = counts.detach().cpu().numpy() if isinstance(counts, torch.Tensor) else np.asarray(counts)
+    if a.shape != (P,) or a.dtype.kind not in "iu":
+        raise ValueError(f"{name} must hold {P} integers (one per pair), got shape {tuple(a.shape)} of {a.dtype}")
+    if P and (int(a.min()) < 0 or int(a.max()) > cap):
+        raise ValueError(f"{name} must lie in [0, {cap}] (the rows of the array), got {int(a.min())} .. {int(a.max())}")
+    return np.ascontiguousarray(a, np.int32)
+
+
 class Engine:
     def __init__(self, cfg: NetConfig, device: int = 0, max_points: int = 8192, max_pairs: int = 1):
         self.lib = _lib.load()
@@ -634,7 +648,7 @@ class Engine:
 
     def icp_refine(self, points_src, points_ref, T_init, max_corr_dist: float, max_iter: int = 30,
                    rel_fitness: float = 1e-6, rel_rmse: float = 1e-6, estimator: str = "point", normals_ref=None,
-                   viewpoint=(0.0, 0.0, 0.0), search: str = "brute"):
+                   viewpoint=(0.0, 0.0, 0.0), search: str = "brute", counts_src=None, counts_ref=None):
         """open3d registration_icp counterpart for P pairs (reference test.py:241-258, disabled there).
         points_* [P,N,>=3] CUDA fp32, T_init [P,3,4] -> (T [P,3,4], stats [P,4] f64: fitness, inlier_rmse, converged, iters).
         estimator="plane": the point-to-plane update (include/dsir.h, dsir_icp_refine_ex) and a fifth stats column, the identity
@@ -642,14 +656,23 @@ class Engine:
         rows of 6 columns and more (the use_ppf layout), else estimated here - knn_pyramid on points_ref, estimate_normals on its
         level-0 lists towards ``viewpoint`` - which needs a cloud the pyramid accepts (ValueError otherwise).
         search: "brute" (J x K distance tests per iteration), "grid" (a cell index of points_ref built once per call,
-        csrc/icp_grid.hip) or "auto" (the grid from ICP_GRID_MIN_REF reference points on).  Same bytes out, whichever is taken."""
+        csrc/icp_grid.hip) or "auto" (the grid from ICP_GRID_MIN_REF reference points on).  Same bytes out, whichever is taken.
+        counts_src / counts_ref: [P] int32 device tensors or sequences, the rows of each pair that hold points (clouds of unequal
+        sizes padded to one shape, harness.pad_clouds); None: all of them.  Rows beyond a count are never read, and pair p gets,
+        byte for byte, what the call on points_src[p:p+1, :counts_src[p]], points_ref[p:p+1, :counts_ref[p]] alone returns.  A
+        count outside [0, rows] is a ValueError.  With counts_ref the plane estimator's normals are not estimated here (the
+        pyramid takes dense clouds): pass normals_ref, or rows that carry them."""
         if estimator not in self.ICP_ESTIMATORS:
             raise ValueError("estimator must be 'point' or 'plane'")
         grid = self._icp_search(search, points_ref.shape[1])
-        points_src, points_ref = _chk(points_src, torch.float32, "points_src"), _chk(points_ref, torch.float32, "points_ref")
-        T_init = _chk(T_init, torch.float32, "T_init")
         P, J, stride = points_src.shape
         K = points_ref.shape[1]
+        counts_src, counts_ref = pair_counts(counts_src, P, J, "counts_src"), pair_counts(counts_ref, P, K, "counts_ref")
+        if estimator == "plane" and counts_ref is not None and normals_ref is None and stride < 6:
+            raise ValueError("estimator='plane' with counts_ref does not estimate the normals (the KNN pyramid takes dense clouds): "
+                             "pass normals_ref [P,K,3], or rows that carry the normals in columns 3..5")
+        points_src, points_ref = _chk(points_src, torch.float32, "points_src"), _chk(points_ref, torch.float32, "points_ref")
+        T_init = _chk(T_init, torch.float32, "T_init")
         assert points_ref.shape[0] == P and points_ref.shape[2] == stride and tuple(T_init.shape) == (P, 3, 4)
         plane = self.ICP_ESTIMATORS[estimator]
         if not plane:
@@ -662,45 +685,65 @@ class Engine:
             normals_ref = self.icp_normals(points_ref, viewpoint)
         T = self._empty((P, 3, 4))
         stats = self._empty((P, 5), torch.float64)
+        args = (self.h, _ptr(points_src), _ptr(points_ref), P, J, K, stride, float(max_corr_dist), int(max_iter), float(rel_fitness),
+                float(rel_rmse), _ptr(T_init), _ptr(T), plane, _ptr(normals_ref), grid, _ptr(stats))
+        cs, cr = self._counts(counts_src), self._counts(counts_ref)
         self._pre()
-        self._call(self.lib.dsir_icp_refine_ex2(self.h, _ptr(points_src), _ptr(points_ref), P, J, K, stride, float(max_corr_dist),
-                                                int(max_iter), float(rel_fitness), float(rel_rmse), _ptr(T_init), _ptr(T), plane,
-                                                _ptr(normals_ref), grid, _ptr(stats)))
+        if cs is None and cr is None:
+            self._call(self.lib.dsir_icp_refine_ex2(*args))
+        else:
+            self._call(self.lib.dsir_icp_refine_ex3(*args, _ptr(cs), _ptr(cr)))
         self.sync()
         return T, (stats if plane else stats[:, :4].contiguous())
 
-    def icp_correspondences(self, points_src, points_ref, T, max_corr_dist: float, search: str = "brute"):
+    def _counts(self, host):
+        """pair_counts' array on the device (None stays None)"""
+        return None if host is None else torch.from_numpy(host).to(self.device)
+
+    def icp_correspondences(self, points_src, points_ref, T, max_corr_dist: float, search: str = "brute", counts_src=None, counts_ref=None):
         """open3d evaluate_registration counterpart for P pairs: one search step of icp_refine under the pose T.
         points_* [P,N,>=3] CUDA fp32, T [P,3,4] -> (idx [P,J] i32: the reference point of each source point moved by T, or -1;
-        d2 [P,J] fp32: its squared distance, 0 where idx is -1; stats [P,2] f64: fitness, inlier_rmse).  search as for icp_refine."""
+        d2 [P,J] fp32: its squared distance, 0 where idx is -1; stats [P,2] f64: fitness, inlier_rmse).  search and counts_* as for
+        icp_refine; entries of idx and d2 at and beyond a pair's counts_src are -1 and 0, its fitness is matched / counts_src."""
         grid = self._icp_search(search, points_ref.shape[1])
-        points_src, points_ref = _chk(points_src, torch.float32, "points_src"), _chk(points_ref, torch.float32, "points_ref")
-        T = _chk(T, torch.float32, "T")
         P, J, stride = points_src.shape
         K = points_ref.shape[1]
+        counts_src, counts_ref = pair_counts(counts_src, P, J, "counts_src"), pair_counts(counts_ref, P, K, "counts_ref")
+        points_src, points_ref = _chk(points_src, torch.float32, "points_src"), _chk(points_ref, torch.float32, "points_ref")
+        T = _chk(T, torch.float32, "T")
         assert points_ref.shape[0] == P and points_ref.shape[2] == stride and tuple(T.shape) == (P, 3, 4)
         idx, d2 = self._empty((P, J), torch.int32), self._empty((P, J))
         stats = self._empty((P, 2), torch.float64)
+        args = (self.h, _ptr(points_src), _ptr(points_ref), P, J, K, stride, float(max_corr_dist), _ptr(T), grid, _ptr(idx), _ptr(d2), _ptr(stats))
+        cs, cr = self._counts(counts_src), self._counts(counts_ref)
         self._pre()
-        self._call(self.lib.dsir_icp_correspondences(self.h, _ptr(points_src), _ptr(points_ref), P, J, K, stride, float(max_corr_dist),
-                                                     _ptr(T), grid, _ptr(idx), _ptr(d2), _ptr(stats)))
+        if cs is None and cr is None:
+            self._call(self.lib.dsir_icp_correspondences(*args))
+        else:
+            self._call(self.lib.dsir_icp_correspondences_ex(*args, _ptr(cs), _ptr(cr)))
         self.sync()
         return idx, d2, stats
 
-    def information_matrix(self, points_src, points_ref, T, max_corr_dist: float, search: str = "brute"):
+    def information_matrix(self, points_src, points_ref, T, max_corr_dist: float, search: str = "brute", counts_src=None, counts_ref=None):
         """open3d get_information_matrix_from_point_clouds counterpart for P pairs (include/dsir.h, dsir_information_matrix).
         Arguments as for icp_correspondences, whose correspondence set this sums over -> (info [P,6,6] f64 in the order
-        [rotation; translation], symmetric; count [P] i32: the correspondences).  Same bytes for every ``search``."""
+        [rotation; translation], symmetric; count [P] i32: the correspondences).  Same bytes for every ``search``; counts_* as for
+        icp_refine (include/dsir.h, dsir_information_matrix_ex)."""
         grid = self._icp_search(search, points_ref.shape[1])
-        points_src, points_ref = _chk(points_src, torch.float32, "points_src"), _chk(points_ref, torch.float32, "points_ref")
-        T = _chk(T, torch.float32, "T")
         P, J, stride = points_src.shape
         K = points_ref.shape[1]
+        counts_src, counts_ref = pair_counts(counts_src, P, J, "counts_src"), pair_counts(counts_ref, P, K, "counts_ref")
+        points_src, points_ref = _chk(points_src, torch.float32, "points_src"), _chk(points_ref, torch.float32, "points_ref")
+        T = _chk(T, torch.float32, "T")
         assert points_ref.shape[0] == P and points_ref.shape[2] == stride and tuple(T.shape) == (P, 3, 4)
         info, count = self._empty((P, 6, 6), torch.float64), self._empty((P,), torch.int32)
+        args = (self.h, _ptr(points_src), _ptr(points_ref), P, J, K, stride, float(max_corr_dist), _ptr(T), grid, _ptr(info), _ptr(count))
+        cs, cr = self._counts(counts_src), self._counts(counts_ref)
         self._pre()
-        self._call(self.lib.dsir_information_matrix(self.h, _ptr(points_src), _ptr(points_ref), P, J, K, stride, float(max_corr_dist),
-                                                    _ptr(T), grid, _ptr(info), _ptr(count)))
+        if cs is None and cr is None:
+            self._call(self.lib.dsir_information_matrix(*args))
+        else:
+            self._call(self.lib.dsir_information_matrix_ex(*args, _ptr(cs), _ptr(cr)))
         self.sync()
         return info, count
 

@@ -620,6 +620,28 @@ def _chain_poses(N, edges, reference_node):
     return np.stack([X[i] for i in range(N)])
 
 
+def pad_clouds(clouds):
+    """Clouds [n_i, stride] of unequal sizes (tensors on one device, or numpy) as one batch for the entries that take per-pair
+    counts (``Engine.icp_refine(counts_src=, counts_ref=)``, ...): -> (tensor [P, cap, stride] float32, counts [P] int32), cap the
+    largest n_i (at least 1).  The padding rows are NaN on purpose: the engine never reads them, and a kernel that did would show."""
+    cl = [c if isinstance(c, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(c, np.float32)) for c in clouds]
+    if not cl or any(c.dim() != 2 or c.shape[1] != cl[0].shape[1] for c in cl):
+        raise ValueError("pad_clouds: expected at least one cloud, all [n_i, stride] with the same stride")
+    out = torch.full((len(cl), max(1, max(c.shape[0] for c in cl)), cl[0].shape[1]), float("nan"), dtype=torch.float32, device=cl[0].device)
+    for i, c in enumerate(cl):
+        out[i, :c.shape[0]] = c
+    return out, torch.tensor([c.shape[0] for c in cl], dtype=torch.int32, device=cl[0].device)
+
+
+def scene_batches(sizes, batch: int):
+    """The ICP calls of ``register_scene``: ``sizes`` = (n_s, n_t) per edge -> lists of edge numbers, ``batch`` at a time in the order
+    of a stable sort by n_s + n_t, so that a call's capacity stays close to its pairs' sizes.  Every edge is in exactly one list."""
+    if batch < 1:
+        raise ValueError("register_scene: batch must be at least 1")
+    order = sorted(range(len(sizes)), key=lambda k: int(sizes[k][0]) + int(sizes[k][1]))       # sorted() is stable
+    return [order[b0:b0 + batch] for b0 in range(0, len(order), batch)]
+
+
 @torch.no_grad()
 def register_scene(fragments, engine, edges, voxel_size: float = 0.05, max_corr_dist: Optional[float] = None, icp_max_iter: int = 30,
                    estimator: str = "point", search: str = "auto", preference: float = 1.0, overlap_min: float = OVERLAP_MIN,
@@ -629,7 +651,10 @@ def register_scene(fragments, engine, edges, voxel_size: float = 0.05, max_corr_
     ``icp_refine`` (radius ``max_corr_dist``, default 2 x voxel size) then ``information_matrix``; an edge with
     info[5,5] / min(n_s, n_t) < ``overlap_min`` is dropped ("overlap"); ``pose_graph_optimize`` on the rest with
     mu = ``line_process_weight(..., preference)`` from the chained poses; uncertain edges with l < 0.25 are dropped ("line") and the
-    graph is optimised again from the first result.  ``batch``: edges of equal shapes per ICP call (the engine's max_pairs).
+    graph is optimised again from the first result.  ``batch``: edges per ICP call (at most the engine's max_pairs), whatever their
+    sizes: each call pads its clouds (``pad_clouds``) and passes the sizes as counts, and by the contract of those entries
+    (include/dsir.h, dsir_icp_refine_ex3) the result is the same, byte for byte, for every ``batch``.  ``estimator="plane"`` on rows
+    without normals estimates each fragment's normals once (``engine.icp_normals``).
     -> {"X": [N,3,4] f64 node poses (fragment -> scene, reference node the identity), "edges": one dict per input edge
     {s, t, T (refined), info, count, uncertain, line, dropped: None | "overlap" | "line"}, "stats": [stats of both optimisations]}."""
     from . import pose_graph as PG
@@ -638,22 +663,23 @@ def register_scene(fragments, engine, edges, voxel_size: float = 0.05, max_corr_
     frs = [(f if isinstance(f, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(f, np.float32))).to(dev).float().contiguous() for f in fragments]
     N = len(frs)
     rows = [{"s": int(s), "t": int(t), "T": None, "info": None, "count": 0, "uncertain": bool(u), "line": 1.0, "dropped": None} for s, t, _, u in edges]
-    groups: Dict[tuple, list] = {}
-    for k, (s, t, _, _) in enumerate(edges):
-        groups.setdefault((tuple(frs[int(s)].shape), tuple(frs[int(t)].shape)), []).append(k)
-    for ks in groups.values():
-        for b0 in range(0, len(ks), batch):
-            kb = ks[b0:b0 + batch]
-            src = torch.stack([frs[rows[k]["s"]] for k in kb]).contiguous()
-            ref = torch.stack([frs[rows[k]["t"]] for k in kb]).contiguous()
-            T0 = torch.from_numpy(np.stack([np.asarray(edges[k][2], np.float32)[:3] for k in kb])).to(dev).contiguous()
-            T, _ = engine.icp_refine(src, ref, T0, r, max_iter=icp_max_iter, estimator=estimator, search=search)
-            info, count = engine.information_matrix(src, ref, T, r, search=search)
-            T, info, count = T.cpu().numpy().astype(np.float64), info.cpu().numpy(), count.cpu().numpy()
-            for j, k in enumerate(kb):
-                rows[k].update(T=T[j], info=info[j], count=int(count[j]))
-                if info[j, 5, 5] / min(src.shape[1], ref.shape[1]) < overlap_min:
-                    rows[k]["dropped"] = "overlap"
+    normals = {}                                                       # estimator "plane" on rows without normals: once per fragment
+    if estimator == "plane" and any(f.shape[1] < 6 for f in frs):
+        normals = {t: engine.icp_normals(frs[t][None])[0] for t in sorted({r_["t"] for r_ in rows})}
+    sizes = [(frs[r_["s"]].shape[0], frs[r_["t"]].shape[0]) for r_ in rows]
+    for kb in scene_batches(sizes, batch):
+        src, n_s = pad_clouds([frs[rows[k]["s"]] for k in kb])
+        ref, n_t = pad_clouds([frs[rows[k]["t"]] for k in kb])
+        nrm = pad_clouds([normals[rows[k]["t"]] for k in kb])[0] if normals else None
+        T0 = torch.from_numpy(np.stack([np.asarray(edges[k][2], np.float32)[:3] for k in kb])).to(dev).contiguous()
+        T, _ = engine.icp_refine(src, ref, T0, r, max_iter=icp_max_iter, estimator=estimator, normals_ref=nrm, search=search,
+                                 counts_src=n_s, counts_ref=n_t)
+        info, count = engine.information_matrix(src, ref, T, r, search=search, counts_src=n_s, counts_ref=n_t)
+        T, info, count = T.cpu().numpy().astype(np.float64), info.cpu().numpy(), count.cpu().numpy()
+        for j, k in enumerate(kb):
+            rows[k].update(T=T[j], info=info[j], count=int(count[j]))
+            if info[j, 5, 5] / max(1, min(sizes[k])) < overlap_min:
+                rows[k]["dropped"] = "overlap"
 
     def graph(keep, X0):
         return PG.PoseGraph(X0, np.array([(rows[k]["s"], rows[k]["t"]) for k in keep], np.int32).reshape(-1, 2),

@@ -52,8 +52,9 @@ def scene_files(root, scene, max_fragments=None):
     return [plys[i] for i in range(n)], records("gt.log", 4), records("gt.info", 6)
 
 
-def run_scene(root, scene, method="fpfh", voxel=0.05, max_fragments=None, weights=None, hypotheses=8192):
-    """One scene end to end -> the dict that is printed: `harness.summarize_scene`'s, or {"skipped": reason}"""
+def run_scene(root, scene, method="fpfh", voxel=0.05, max_fragments=None, weights=None, hypotheses=8192, icp_batch=1):
+    """One scene end to end -> the dict that is printed: `harness.summarize_scene`'s, or {"skipped": reason}.  icp_batch: edges per
+    ICP and information-matrix call of `harness.register_scene` (same result for every value; the engine is made for that many pairs)"""
     files, gt, gt_info = scene_files(root, scene, max_fragments)
     raw = [read_ply_xyz(f) for f in files]
     cfg = NetConfig(pipeline="feat") if method == "feat" else NetConfig()
@@ -61,7 +62,7 @@ def run_scene(root, scene, method="fpfh", voxel=0.05, max_fragments=None, weight
     try:
         if method == "fpfh":
             from deepsir_amd.engine import Engine
-            eng = Engine(cfg, 0, max_points=max(1024, max(len(p) for p in raw)), max_pairs=1)
+            eng = Engine(cfg, 0, max_points=max(1024, max(len(p) for p in raw)), max_pairs=max(1, icp_batch))
             eng.load_state_dict(generate_state_dict(cfg, 0))      # the FPFH path reads no weight; the context wants them loaded
             frags = _voxelize(eng, raw, voxel)
             edges = H.scene_edges_fpfh(frags, eng, voxel_size=voxel, radius=5 * voxel, normal_radius=2 * voxel, normal_max_nn=30,
@@ -72,12 +73,12 @@ def run_scene(root, scene, method="fpfh", voxel=0.05, max_fragments=None, weight
             model = Network(cfg).cuda()
             sd = torch.load(weights, map_location="cpu") if weights else generate_state_dict(cfg, 0)
             model.load_state_dict({k: torch.as_tensor(v) for k, v in sd.items()})
-            use = model._ensure_engine(max(1024, max(len(p) for p in raw)), 1)
+            use = model._ensure_engine(max(1024, max(len(p) for p in raw)), max(1, icp_batch))
             frags = _voxelize(use, raw, voxel)
             edges = H.scene_edges_feat(frags, model, voxel_size=voxel, hypotheses=hypotheses)
         out = {"scene": scene, "fragments": len(frags), "points": [int(len(f)) for f in frags]}
         try:
-            res = H.register_scene(frags, use, edges, voxel_size=voxel)
+            res = H.register_scene(frags, use, edges, voxel_size=voxel, batch=max(1, icp_batch))
         except ValueError as e:                                   # the kept edges do not connect the scene
             out["skipped"] = str(e)
             return out
@@ -97,12 +98,13 @@ def main(argv=None):
     ap.add_argument("--hypotheses", type=int, default=8192)
     ap.add_argument("--max-fragments", type=int, default=None)
     ap.add_argument("--weights", default=None)
+    ap.add_argument("--icp-batch", type=int, default=1, help="edges per ICP / information-matrix call of register_scene (any sizes; same result)")
     a = ap.parse_args(argv)
     if not os.path.isdir(os.path.join(a.root, "test")):
         raise FileNotFoundError(f"Invalid path: {os.path.join(a.root, 'test')}")
     outs = []
     for scene in a.scenes:
-        outs.append(run_scene(a.root, scene, a.method, a.voxel, a.max_fragments, a.weights, a.hypotheses))
+        outs.append(run_scene(a.root, scene, a.method, a.voxel, a.max_fragments, a.weights, a.hypotheses, a.icp_batch))
         print(outs[-1], flush=True)
     return outs
 

@@ -380,6 +380,35 @@ int dsir_icp_refine_ex2(dsir_ctx* ctx, const float* points_src, const float* poi
 int dsir_icp_correspondences(dsir_ctx* ctx, const float* points_src, const float* points_ref, int pairs, int J, int K, int stride,
                              float max_corr_dist, const float* T, int search, int32_t* idx_out, float* d2_out, double* stats_out);
 
+/* ICP on batches of clouds of unequal sizes: dsir_icp_refine_ex2 and dsir_icp_correspondences (and, further down,
+ * dsir_information_matrix) with per-pair row counts.  counts_src, counts_ref: [P] int32 on the device, or NULL.  J and K are then
+ * the row CAPACITIES of the arrays (their strides: points_src [P][J][stride], points_ref [P][K][stride], with estimator 1
+ * normals_ref [P][K][3], idx_out / d2_out [P][J]) and pair p has
+ *     Jp = clamp(counts_src[p], 0, J) source rows  and  Kp = clamp(counts_ref[p], 0, K) reference rows:
+ * a count outside the capacity is clamped, not refused.  One count NULL: that side is full (J or K) in every pair.  Both NULL:
+ * exactly the bytes of the entry that is extended, from the same launches.
+ * Padding is never read into a result: rows of points_src at or beyond Jp, rows of points_ref and normals_ref at or beyond Kp may
+ * hold anything - NaN, inf, or finite points that would be perfectly good queries and neighbours - and nothing that is written
+ * depends on them.  Entries [Jp, J) of idx_out and d2_out are written as -1 and 0.f.  fitness = matched / Jp.
+ * The contract: pair p of a call with counts gets the T_out, the stats, the information matrix and count, and the first Jp
+ * entries of idx_out and d2_out, that the dense entry writes for that pair ALONE with J = Jp and K = Kp on its first Jp and Kp
+ * rows - byte for byte, for both estimators and both searches.  (The sums are partitioned by the pair's own Jp, the brute search's
+ * arg-min does not depend on its slices, the cell index sorts padding behind the pair's own rows with stable sorts, and the two
+ * single-workgroup Kabsch kernels give the same bits, so nothing depends on the capacity.)
+ * Jp == 0 or Kp == 0 (not an error; the dense entries refuse J or K of 0, so there is no dense counterpart): the pair has no
+ * correspondence and is treated as such a pair always is - every update is the identity, T_out = T_init bit for bit, fitness and
+ * inlier_rmse are 0 (fitness is defined as 0 for Jp == 0), the convergence test freezes it at the first iteration, all stats are
+ * finite (estimator 1 counts that identity update in stats[4]), the information matrix is zero with count 0.
+ * The scratch is sized by the capacities: "workspace too small" compares P x J and P x K, as in the dense entries.  Same bytes on
+ * every run, and a pair's bytes do not depend on the other pairs of the call, their counts included. */
+int dsir_icp_refine_ex3(dsir_ctx* ctx, const float* points_src, const float* points_ref, int pairs, int J, int K, int stride,
+                        float max_corr_dist, int max_iter, float rel_fitness, float rel_rmse, const float* T_init,
+                        float* T_out, int estimator, const float* normals_ref, int search, double* stats,
+                        const int32_t* counts_src, const int32_t* counts_ref);
+int dsir_icp_correspondences_ex(dsir_ctx* ctx, const float* points_src, const float* points_ref, int pairs, int J, int K, int stride,
+                                float max_corr_dist, const float* T, int search, int32_t* idx_out, float* d2_out, double* stats_out,
+                                const int32_t* counts_src, const int32_t* counts_ref);
+
 /* Replaces the `use_tune` branch of pose_optimization (test.py:209-239): transformation_finetune (test.py:159-207) with
  * HighDimSmoothL1Loss (test.py:103-131) over the network's last correspondences, the pose re-parametrised as
  * network/DGR.py's Transformation (6-D rotation + translation, :60-132) and fitted by Adam (lr 0.1, ExponentialLR 0.999)
@@ -701,6 +730,11 @@ int dsir_feature_correspondences_ex(dsir_ctx* ctx, const float* desc_src, const 
  * of `search`, and for a pair whatever else is in the batch.  Scratch comes from the context workspace. */
 int dsir_information_matrix(dsir_ctx* ctx, const float* points_src, const float* points_ref, int pairs, int J, int K, int stride,
                             float max_corr_dist, const float* T, int search, double* info_out, int32_t* count_out);
+/* dsir_information_matrix with per-pair row counts: the rule, the Jp == 0 / Kp == 0 cases and the byte-for-byte contract are stated
+ * at dsir_icp_refine_ex3.  The correspondence set is dsir_icp_correspondences_ex's for the same arguments. */
+int dsir_information_matrix_ex(dsir_ctx* ctx, const float* points_src, const float* points_ref, int pairs, int J, int K, int stride,
+                               float max_corr_dist, const float* T, int search, double* info_out, int32_t* count_out,
+                               const int32_t* counts_src, const int32_t* counts_ref);
 
 #define DSIR_POSE_GRAPH_MAX_NODES 128
 #define DSIR_POSE_GRAPH_MAX_ITER 100        /* the default of the Python layer */
