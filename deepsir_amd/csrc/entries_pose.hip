@@ -5,6 +5,7 @@
 #include "engine_ctx.h"
 #include "fgr.h"
 #include "icp_grid.h"
+#include "icp_robust.h"
 #include "pose_corr.h"
 
 using namespace dsir;
@@ -47,6 +48,9 @@ static int icp_entry(dsir_ctx* c, const char* name, IcpArgs a, const float* norm
   if (a.estimator == 1 && !normals_ref && a.stride < 6)
     return fail(c, "%s: bad arguments (the plane estimator without normals_ref reads the normals from columns 3..5 "
                    "of the points_ref rows: stride=%d, needs >= 6)", name, a.stride);
+  if (!icp_robust_args_ok(a.kernel, a.kernel_scale))
+    return fail(c, "%s: bad arguments (kernel=%d must be 0 l2, 1 huber, 2 cauchy, 3 gm or 4 tukey, and with a kernel other than l2 "
+                   "kernel_scale=%g must be finite and positive)", name, a.kernel, (double)a.kernel_scale);
   if (search == 1 && (!icp_grid_radius_ok(a.max_corr_dist) || !icp_grid_shape_ok(a.pairs, a.J, a.K)))
     return fail(c, "%s: bad arguments (the grid search needs a max_corr_dist whose fp32 square is finite, and pairs x J "
                    "and pairs x K below 2^31)", name);
@@ -101,6 +105,17 @@ int dsir_icp_refine_ex3(dsir_ctx* c, const float* points_src, const float* point
   a.stats5_out = stats;
   a.counts_src = counts_src; a.counts_ref = counts_ref;
   return icp_entry(c, "dsir_icp_refine_ex3", a, normals_ref, search, nullptr);
+}
+
+int dsir_icp_refine_ex4(dsir_ctx* c, const float* points_src, const float* points_ref, int pairs, int J, int K, int stride,
+                        float max_corr_dist, int max_iter, float rel_fitness, float rel_rmse, const float* T_init, float* T_out,
+                        int estimator, const float* normals_ref, int search, double* stats, const int32_t* counts_src, const int32_t* counts_ref,
+                        int kernel, float kernel_scale) {
+  IcpArgs a = icp_args(points_src, points_ref, pairs, J, K, stride, max_corr_dist, max_iter, rel_fitness, rel_rmse, T_init, T_out, estimator);
+  a.stats5_out = stats;
+  a.counts_src = counts_src; a.counts_ref = counts_ref;
+  a.kernel = kernel; a.kernel_scale = kernel == kIcpL2 ? 0.f : kernel_scale;   // l2: the scale is ignored
+  return icp_entry(c, "dsir_icp_refine_ex4", a, normals_ref, search, nullptr);
 }
 
 int dsir_icp_correspondences(dsir_ctx* c, const float* points_src, const float* points_ref, int pairs, int J, int K, int stride,

@@ -45,9 +45,27 @@
 // the plane step's "fewer than 6 rows"), T carried over bit for bit, fitness and RMSE 0, frozen by the first convergence test.
 // As before: no floating-point atomics, no scratch shared between pairs, the same bytes on every run, and a pair's bytes do not
 // depend on the other pairs of the call - their counts included.  Without counts every launch, grid and byte is what it was.
+//
+// ---- Robust loss kernels (IcpArgs::kernel / kernel_scale, dsir_icp_refine_ex4): open3d's `robust_kernel` of both estimators.  open3d is
+// not installable here: parity is unpinned, THE RULE IS OWNED HERE (icp_robust.h holds the arithmetic) and restated in
+// tests/icp_robust_host.py.  The weight of a correspondence is a function of its squared residual q = r^2 and the scale k > 0, in fp64,
+// one correctly rounded operation after the other in the order written (k^2 = k * k first):
+//   l2 (0): 1    huber (1): q <= k^2 ? 1 : k / sqrt(q)    cauchy (2): 1 / (1 + q / k^2)    gm (3): k / ((k + q) * (k + q))
+//   tukey (4): q <= k^2 ? (1 - q / k^2)^2 : 0
+// Point-to-point: q = the fp32 squared point distance d2 of the search, w = (float)weight((double)d2, k) rounded once, written by
+// icp_stats_kernel<true> where the l2 loop writes 1; the weighted Kabsch step is the one the l2 loop runs.  A weight 0 on a matched
+// row leaves its index alone.  A pair whose weights are all 0 takes the frozen step (KabschArgs::zero_freeze; why: icp_robust.h): the
+// identity update, T carried over bit for bit.  Point-to-plane: q = r * r of the fp64 plane residual, wr = weight(q, k),
+// A += (wr J[a]) J[b], b += (wr J[a]) r in icp_plane_accum_kernel<true>; a row whose weight is not > 0 contributes nothing and is not
+// counted, then "fewer than 6 rows" and the singular-system rule apply as they are.
+// The kernel acts on the estimator ALONE, as in open3d: the search, the fitness, the inlier RMSE (unweighted point distances), the
+// convergence test, max_iter, the done flags, the stats columns and the information matrix do not see it.  l2 runs the <false>
+// instantiations of both kernels - the code they were - and zero_freeze = 0: the same bytes as before.  As before: no atomics, the same
+// bytes on every run, a pair's bytes independent of the other pairs, of the counts' padding and of the search.
 #include "kernels.h"
 #include "device_utils.h"
 #include "icp_layout.h"
+#include "icp_robust.h"
 
 namespace dsir {
 
@@ -132,9 +150,12 @@ __global__ __launch_bounds__(QB * NW) void icp_nn_kernel(const float* __restrict
 // per pair: fitness = |corr| / Jp (0 for a pair without source rows), inlier RMSE = sqrt(sum d2 / |corr|); convergence test against
 // the previous values; correspondences turned into (clamped index, 0/1 weight) for the Kabsch kernel.  state = {fitness, rmse, done,
 // iterations}.  Jp = the pair's own rows of the capacity J; the rows beyond are neither read nor written.
+// ROBUST: the weight of a matched row is the kernel's (icp_robust.h) of its squared point distance, rounded once to fp32 - possibly 0,
+// the index stays; count, sums and the convergence test do not see it.  ROBUST = false is the least-squares loop's kernel as it was.
+template <bool ROBUST>
 __global__ __launch_bounds__(256) void icp_stats_kernel(int32_t* __restrict__ idx, const float* __restrict__ d2,
                                                         float* __restrict__ w, int J, const int32_t* __restrict__ counts_src, int check,
-                                                        float rel_fitness, float rel_rmse, double* __restrict__ state) {
+                                                        float rel_fitness, float rel_rmse, double* __restrict__ state, int kernel, double kscale) {
   __shared__ double s_cnt[4], s_sse[4];
   const int pair = blockIdx.x;
   double* st = state + (int64_t)pair * 4;
@@ -145,7 +166,8 @@ __global__ __launch_bounds__(256) void icp_stats_kernel(int32_t* __restrict__ id
     const int64_t o = (int64_t)pair * J + j;
     const int i = idx[o];
     const bool in = i >= 0;
-    w[o] = in ? 1.f : 0.f;
+    if (ROBUST) w[o] = in ? (float)icp_robust_weight(kernel, (double)d2[o], kscale) : 0.f;
+    else w[o] = in ? 1.f : 0.f;
     if (!in) idx[o] = 0;
     cnt += in ? 1.0 : 0.0;
     sse += in ? (double)d2[o] : 0.0;
@@ -211,10 +233,15 @@ __device__ __forceinline__ void se3_compose(const float* T, const float* P, floa
 // normals of pair `pair`: N + pair * cs, `ld` floats between points ([P][K][3], or columns 3..5 of the reference rows)
 struct PlaneNormals { const float* N; int64_t cs; int ld; };
 
+// ROBUST: a row enters the sums with the kernel's weight (icp_robust.h) of its squared plane residual, wr = weight(r * r, k) in fp64:
+// A += (wr J[a]) J[b], b += (wr J[a]) r; a weight that is not > 0 contributes nothing and is not a row.  The fp32 array w only says
+// "has a correspondence" here: under every kernel the plane loop runs icp_stats_kernel<false>, which writes 1 or 0 (the kernel's
+// argument is the plane residual, not the point distance).  ROBUST = false is the least-squares kernel as it was.
+template <bool ROBUST>
 __global__ __launch_bounds__(PT) void icp_plane_accum_kernel(const float* __restrict__ cur, const float* __restrict__ ref, int ref_stride,
                                                              PlaneNormals nrm, const int32_t* __restrict__ idx,
                                                              const float* __restrict__ w, int J, int K, const int32_t* __restrict__ counts_src,
-                                                             const double* __restrict__ state, double* __restrict__ part) {
+                                                             const double* __restrict__ state, double* __restrict__ part, int kernel, double kscale) {
   __shared__ double sh[(PT / 64 + 1) * kIcpPlaneSums];
   const int pair = blockIdx.y, ch = blockIdx.x;
   if (state[(int64_t)pair * 4 + 2] != 0.0) return;   // converged: the step is the identity (block-uniform)
@@ -240,12 +267,26 @@ __global__ __launch_bounds__(PT) void icp_plane_accum_kernel(const float* __rest
     const double r = ((s[0] - (double)tx) * n[0] + (s[1] - (double)ty) * n[1]) + (s[2] - (double)tz) * n[2];
     const double Jr[6] = {s[1] * n[2] - s[2] * n[1], s[2] * n[0] - s[0] * n[2], s[0] * n[1] - s[1] * n[0], n[0], n[1], n[2]};
     int k = 0;
+    if (ROBUST) {
+      const double wr = icp_robust_weight(kernel, r * r, kscale);
+      if (!(wr > 0.0)) continue;
+      double wJ[6];
 #pragma unroll
-    for (int a = 0; a < 6; ++a)
+      for (int a = 0; a < 6; ++a) wJ[a] = wr * Jr[a];
 #pragma unroll
-      for (int b = a; b < 6; ++b) v[k++] += Jr[a] * Jr[b];
+      for (int a = 0; a < 6; ++a)
 #pragma unroll
-    for (int a = 0; a < 6; ++a) v[21 + a] += Jr[a] * r;
+        for (int b = a; b < 6; ++b) v[k++] += wJ[a] * Jr[b];
+#pragma unroll
+      for (int a = 0; a < 6; ++a) v[21 + a] += wJ[a] * r;
+    } else {
+#pragma unroll
+      for (int a = 0; a < 6; ++a)
+#pragma unroll
+        for (int b = a; b < 6; ++b) v[k++] += Jr[a] * Jr[b];
+#pragma unroll
+      for (int a = 0; a < 6; ++a) v[21 + a] += Jr[a] * r;
+    }
     v[27] += 1.0;
   }
   block_sum<PT / 64>(v, sh);
@@ -345,15 +386,17 @@ void step_point(const IcpArgs& a, const IcpParts& s, const float* Tp, float* Tn,
   k.ref_ld = a.stride; k.sigmoid = 0; k.pairs = a.pairs; k.m = a.J; k.T = s.Tstep; k.invalid = nullptr;
   k.src_out = s.cur; k.src_out_stride = (int64_t)a.J * 3; k.T_prev = Tp; k.T_cum = Tn; k.T_stride = 12; k.skip = s.skip;
   k.counts = a.counts_src; k.ref_counts = a.counts_ref;   // a pair without a source or a reference row: the frozen step, no row of it read
+  k.zero_freeze = a.kernel != kIcpL2;                      // a robust kernel may leave a pair without a non-zero weight: the frozen step too
   launch_kabsch(k, st);
 }
 
 // the point-to-plane update: the chunks' sums, then the solve and the move (its first workgroup composes Tn and writes the flags)
 void step_plane(const IcpArgs& a, const IcpParts& s, const float* Tp, float* Tn, hipStream_t st) {
   const int nch = icp_plane_chunks(a.J);
-  hipLaunchKernelGGL(icp_plane_accum_kernel, dim3(nch, a.pairs), dim3(PT), 0, st, (const float*)s.cur, a.ref, a.stride,
+  const auto accum = a.kernel != kIcpL2 ? icp_plane_accum_kernel<true> : icp_plane_accum_kernel<false>;
+  hipLaunchKernelGGL(accum, dim3(nch, a.pairs), dim3(PT), 0, st, (const float*)s.cur, a.ref, a.stride,
                      PlaneNormals{a.normals, a.normals_cs, a.normals_ld}, (const int32_t*)s.idx, (const float*)s.w, a.J, a.K,
-                     a.counts_src, (const double*)s.state, s.part);
+                     a.counts_src, (const double*)s.state, s.part, a.kernel, (double)a.kernel_scale);
   hipLaunchKernelGGL(icp_plane_step_kernel, dim3((a.J + PT - 1) / PT, a.pairs), dim3(PT), 0, st, s.cur, a.J, a.counts_src, nch, (const double*)s.part,
                      (const double*)s.state, Tp, Tn, s.nsing, s.skip);
 }
@@ -363,6 +406,14 @@ void search(const IcpArgs& a, const IcpGrid* grid, const float* cur, float r2, i
   if (grid) { launch_icp_nn_grid(*grid, cur, a.pairs, a.J, a.K, a.counts_src, a.counts_ref, r2, idx, d2, skip, st); return; }
   hipLaunchKernelGGL(icp_nn_kernel, dim3((a.J + QB - 1) / QB, a.pairs), dim3(QB * NW), 0, st, cur, a.ref, a.stride, a.J, a.K, a.counts_src, a.counts_ref,
                      r2, idx, d2, skip);
+}
+
+// the statistics of a search and the weights of the next update: the kernel's weights for the point estimator under a robust kernel,
+// else 1 / 0 (the plane sums weigh by the plane residual themselves)
+void stats(const IcpArgs& a, const IcpParts& s, int check, hipStream_t st) {
+  const auto k = a.kernel != kIcpL2 && a.estimator == 0 ? icp_stats_kernel<true> : icp_stats_kernel<false>;
+  hipLaunchKernelGGL(k, dim3(a.pairs), dim3(256), 0, st, s.idx, (const float*)s.d2, s.w, a.J, a.counts_src, check, a.rel_fitness, a.rel_rmse, s.state,
+                     a.kernel, (double)a.kernel_scale);
 }
 
 }  // namespace
@@ -385,13 +436,13 @@ int launch_icp_refine(const IcpArgs& a, void* scratch, hipStream_t st) {
   if (g)
     if (const int e = icp_grid_build(a.ref, a.stride, s.cur, pairs, J, a.K, a.counts_src, a.counts_ref, a.max_corr_dist, a.search == IcpSearch::Grid, s.grid, st, &grid)) return e;
   search(a, g, s.cur, r2, s.idx, s.d2, nullptr, st);
-  hipLaunchKernelGGL(icp_stats_kernel, dim3(pairs), dim3(256), 0, st, s.idx, s.d2, s.w, J, a.counts_src, 0, a.rel_fitness, a.rel_rmse, s.state);
+  stats(a, s, 0, st);
   float *Tp = s.Ta, *Tn = s.Tb;
   for (int it = 0; it < a.max_iter; ++it) {
     if (plane) step_plane(a, s, Tp, Tn, st);
     else step_point(a, s, Tp, Tn, st);
     search(a, g, s.cur, r2, s.idx, s.d2, s.skip, st);
-    hipLaunchKernelGGL(icp_stats_kernel, dim3(pairs), dim3(256), 0, st, s.idx, s.d2, s.w, J, a.counts_src, 1, a.rel_fitness, a.rel_rmse, s.state);
+    stats(a, s, 1, st);
     float* t = Tp; Tp = Tn; Tn = t;
   }
   hipMemcpyAsync(a.T_out, Tp, (size_t)pairs * 48, hipMemcpyDeviceToDevice, st);

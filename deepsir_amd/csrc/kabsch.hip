@@ -63,6 +63,11 @@ __device__ __forceinline__ bool pair_is_empty(const KabschArgs& a, int pair) {
   return (a.counts && a.counts[pair] <= 0) || (a.ref_counts && a.ref_counts[pair] <= 0);
 }
 
+// KabschArgs::zero_freeze: a pair whose S = sum |w| is exactly 0 takes the frozen step too.  Without the flag S = 0 runs on: wn = 0,
+// H = 0 (finite, not the `bad` branch), svd3 gives U = V = I, so R = I and t = 0 - the identity in value, but composing it adds +0
+// terms and turns a -0 of T_prev or of a point into +0 (icp_robust.h)
+__device__ __forceinline__ bool all_weights_zero(const KabschArgs& a, double S) { return a.zero_freeze && S == 0.0; }
+
 // thread 0 of a pair: H (fp32, as the reference forms it) -> SVD in fp64 -> R, t; the pair's transform, flag and cumulative
 // transform to global memory, the transform to sT (12 floats) for the apply step
 __device__ void kabsch_solve(const KabschArgs& a, int pair, const double (&v9)[9], const float (&cs)[3], const float (&ct)[3], float* sT) {
@@ -216,6 +221,10 @@ __global__ __launch_bounds__(NTHR) void kabsch_kernel(const KabschArgs a) {
   double v1[1] = {0.0};
   DSIR_KABSCH_FOR_POINTS(i, 0, m) stream_abs_weight(p, i, v1);
   block_sum<NWAVE>(v1, sh);
+  if (all_weights_zero(a, v1[0])) {   // block-uniform: block_sum leaves the block's sum with every thread
+    if (threadIdx.x == 0) kabsch_frozen(a, pair);
+    return;
+  }
   const float den = weight_den(v1[0]);
   double v6[6] = {0, 0, 0, 0, 0, 0};
   DSIR_KABSCH_FOR_POINTS(i, 0, m) stream_centroid_terms(p, i, den, v6);
@@ -271,6 +280,10 @@ __global__ __launch_bounds__(NTHR) void kabsch_reg_kernel(const KabschArgs a) {
   for (int k = 0; k < TR; ++k)
     if (threadIdx.x + k * NTHR < m) add_abs_weight(v1, w[k]);
   block_sum<NWAVE>(v1, sh);
+  if (all_weights_zero(a, v1[0])) {   // block-uniform: block_sum leaves the block's sum with every thread
+    if (threadIdx.x == 0) kabsch_frozen(a, pair);
+    return;
+  }
   const float den = weight_den(v1[0]);
 
   double v6[6] = {0, 0, 0, 0, 0, 0};

@@ -533,6 +533,8 @@ struct KabschArgs {
   const int32_t* ref_counts;  // [pairs] or nullptr: the rows pair p has in ref.  A pair whose count here, or in `counts`, is <= 0 has no
                          // correspondence: it takes the step of a skipped pair (identity, T_cum = T_prev bit for bit) and none of its rows
                          // is read - its clamped indices would point at row 0 of a reference that has none.
+  int zero_freeze;       // non-zero: a pair whose S = sum |w| is exactly 0 takes that frozen step as well (the ICP loop under a robust
+                         // kernel, icp_robust.h: all weights 0 => T_cum = T_prev bit for bit, src_out untouched); single-workgroup kernels only
 };
 // the rows of pair `pair` in arrays of `cap` rows per pair: counts[pair] clamped into [0, cap]; cap without counts
 __host__ __device__ __forceinline__ int pair_rows(const int32_t* counts, int pair, int cap) {
@@ -564,6 +566,8 @@ struct IcpArgs {
   IcpSearch search;
   double* stats_out;                    // [pairs][4] {fitness, inlier_rmse, converged, iterations} or nullptr
   double* stats5_out;                   // [pairs][5]: the same, then the identity updates taken for a singular system; or nullptr
+  int kernel; float kernel_scale;       // the estimator's robust loss (icp_robust.h: 0 l2, 1 huber, 2 cauchy, 3 gm, 4 tukey) and its scale k > 0
+                                        // (not read under l2); acts on the update alone - search, statistics and convergence test unchanged
 };
 size_t icp_scratch_bytes(const IcpArgs& a);
 int launch_icp_refine(const IcpArgs& a, void* scratch, hipStream_t st);   // 0, or a HIP error of the index build

@@ -56,6 +56,27 @@ def pair_counts(counts, P: int, cap: int, name: str):
     return np.ascontiguousarray(a, np.int32)
 
 
+ICP_KERNELS = {"l2": 0, "huber": 1, "cauchy": 2, "gm": 3, "tukey": 4}        # include/dsir.h DSIR_ICP_L2 .. DSIR_ICP_TUKEY
+
+
+def icp_kernel_args(kernel, kernel_scale):
+    """The robust-kernel arguments of the ICP entries (include/dsir.h, dsir_icp_refine_ex4): a name of ICP_KERNELS and, for a kernel
+    other than "l2", a scale whose fp32 value is finite and positive -> (kernel number, fp32 scale as a float; 0.0 under "l2", whose
+    scale is ignored).  ValueError for anything else."""
+    if not isinstance(kernel, str) or kernel not in ICP_KERNELS:
+        raise ValueError(f"kernel must be one of {', '.join(ICP_KERNELS)}, got {kernel!r}")
+    if kernel == "l2":
+        return 0, 0.0
+    try:
+        with np.errstate(over="ignore"):
+            k = float(np.float32(kernel_scale))
+    except (TypeError, ValueError):
+        k = float("nan")
+    if not (np.isfinite(k) and k > 0.0):
+        raise ValueError(f"kernel_scale must be a finite positive number (as fp32) with kernel={kernel!r}, got {kernel_scale!r}")
+    return ICP_KERNELS[kernel], k
+
+
 class Engine:
     def __init__(self, cfg: NetConfig, device: int = 0, max_points: int = 8192, max_pairs: int = 1):
         self.lib = _lib.load()
@@ -648,7 +669,8 @@ class Engine:
 
     def icp_refine(self, points_src, points_ref, T_init, max_corr_dist: float, max_iter: int = 30,
                    rel_fitness: float = 1e-6, rel_rmse: float = 1e-6, estimator: str = "point", normals_ref=None,
-                   viewpoint=(0.0, 0.0, 0.0), search: str = "brute", counts_src=None, counts_ref=None):
+                   viewpoint=(0.0, 0.0, 0.0), search: str = "brute", counts_src=None, counts_ref=None, kernel: str = "l2",
+                   kernel_scale=None):
         """open3d registration_icp counterpart for P pairs (reference test.py:241-258, disabled there).
         points_* [P,N,>=3] CUDA fp32, T_init [P,3,4] -> (T [P,3,4], stats [P,4] f64: fitness, inlier_rmse, converged, iters).
         estimator="plane": the point-to-plane update (include/dsir.h, dsir_icp_refine_ex) and a fifth stats column, the identity
@@ -661,9 +683,13 @@ class Engine:
         sizes padded to one shape, harness.pad_clouds); None: all of them.  Rows beyond a count are never read, and pair p gets,
         byte for byte, what the call on points_src[p:p+1, :counts_src[p]], points_ref[p:p+1, :counts_ref[p]] alone returns.  A
         count outside [0, rows] is a ValueError.  With counts_ref the plane estimator's normals are not estimated here (the
-        pyramid takes dense clouds): pass normals_ref, or rows that carry them."""
+        pyramid takes dense clouds): pass normals_ref, or rows that carry them.
+        kernel / kernel_scale: open3d's ``robust_kernel`` of the estimator (include/dsir.h, dsir_icp_refine_ex4): "l2" (every
+        correspondence weighs 1; the scale is ignored), "huber", "cauchy", "gm" or "tukey" with a finite scale k > 0 in the cloud's
+        length unit (ValueError otherwise).  It weighs the update alone; search, stats and the convergence test do not see it."""
         if estimator not in self.ICP_ESTIMATORS:
             raise ValueError("estimator must be 'point' or 'plane'")
+        kern, scale = icp_kernel_args(kernel, kernel_scale)
         grid = self._icp_search(search, points_ref.shape[1])
         P, J, stride = points_src.shape
         K = points_ref.shape[1]
@@ -689,7 +715,9 @@ class Engine:
                 float(rel_rmse), _ptr(T_init), _ptr(T), plane, _ptr(normals_ref), grid, _ptr(stats))
         cs, cr = self._counts(counts_src), self._counts(counts_ref)
         self._pre()
-        if cs is None and cr is None:
+        if kern:
+            self._call(self.lib.dsir_icp_refine_ex4(*args, _ptr(cs), _ptr(cr), kern, scale))
+        elif cs is None and cr is None:
             self._call(self.lib.dsir_icp_refine_ex2(*args))
         else:
             self._call(self.lib.dsir_icp_refine_ex3(*args, _ptr(cs), _ptr(cr)))

@@ -26,14 +26,16 @@ from .metrics import THRESHOLDS, rte_rre
 def inference_align(pairs: Sequence[Dict[str, np.ndarray]], model, num_reg_iter: int = 5, dataset_type: str = "3DMatch",
                     batch: int = 1, device: Optional[torch.device] = None, dist=None, pose_opt: Optional[str] = None,
                     voxel_size: float = 0.3, in_flight: int = 1, safeguard_wsum: Optional[float] = None,
-                    ransac_hypotheses: int = 80000, ransac_seed: int = 0, icp_search: str = "auto"):
+                    ransac_hypotheses: int = 80000, ransac_seed: int = 0, icp_search: str = "auto", icp_kernel: str = "l2",
+                    icp_kernel_scale: Optional[float] = None):
     """pairs: sequence of dicts with ``points_src/points_ref [1,N,C]``, ``transform_gt [1,3,4]`` and optionally the
     pyramid tensors and ``others`` (as the reference's collate, data_base.py:196-219).
     ``in_flight`` > 1: the reference's one-pair-per-call loop fed AHEAD - the pairs go one by one to a
     ``deepsir_amd.serve.PairServer`` that keeps that many requests outstanding (same results bit for bit; the per-pair
     time is then the shard's wall time divided by its size).
     ``pose_opt='icp'`` / ``'icp_plane'``: ICP on the raw clouds from the last pose, point-to-point / point-to-plane;
-    ``icp_search`` is ``Engine.icp_refine``'s ``search`` ("auto": the cell index on large clouds; the poses are the same bytes).
+    ``icp_search`` is ``Engine.icp_refine``'s ``search`` ("auto": the cell index on large clouds; the poses are the same bytes),
+    ``icp_kernel`` / ``icp_kernel_scale`` its robust ``kernel`` and ``kernel_scale`` (open3d's ``robust_kernel``; "l2": none).
     ``pose_opt='ransac'``: DGR's safeguard (network/DGR.py:249-306) over the last iteration's correspondences, see below;
     ``pose_opt='consensus'``: the same correspondences through ``consensus_correspondence`` instead of the seeded sampling;
     ``pose_opt='fgr'``: through ``fgr_correspondence`` (fast global registration; ``ransac_seed`` keys its tuple draws);
@@ -87,7 +89,8 @@ def inference_align(pairs: Sequence[Dict[str, np.ndarray]], model, num_reg_iter:
             # pose_optimization with use_icp (test.py:241-258; off in the reference): point-to-point ICP on the raw clouds,
             # correspondence radius 2 x voxel size (test.py:219), open3d's default criteria
             T_opt, _ = _aux_engine(model, data).icp_refine(data["points_src"].float(), data["points_ref"].float(),
-                                                transforms[-1].contiguous(), 2.0 * voxel_size, search=icp_search)
+                                                transforms[-1].contiguous(), 2.0 * voxel_size, search=icp_search,
+                                                kernel=icp_kernel, kernel_scale=icp_kernel_scale)
             transforms.append(T_opt)
         elif pose_opt == "icp_plane":
             # the same refinement with the point-to-plane estimator (open3d's TransformationEstimationPointToPlane; include/dsir.h,
@@ -95,7 +98,7 @@ def inference_align(pairs: Sequence[Dict[str, np.ndarray]], model, num_reg_iter:
             # the reference cloud's level-0 neighbour lists
             T_opt, _ = _aux_engine(model, data).icp_refine(data["points_src"].float(), data["points_ref"].float(),
                                                            transforms[-1].contiguous(), 2.0 * voxel_size, estimator="plane",
-                                                           search=icp_search)
+                                                           search=icp_search, kernel=icp_kernel, kernel_scale=icp_kernel_scale)
             transforms.append(T_opt)
         elif pose_opt == "tune":
             # pose_optimization with use_tune (test.py:218-239; off in the reference): Adam fine-tune of the 6-D-rotation
@@ -633,6 +636,82 @@ def pad_clouds(clouds):
     return out, torch.tensor([c.shape[0] for c in cl], dtype=torch.int32, device=cl[0].device)
 
 
+def _per_scale(value, n, name):
+    """None, a scalar or a sequence of n entries -> a list of n entries"""
+    if value is None or isinstance(value, (int, float)):
+        return [value] * n
+    if len(value) != n:
+        raise ValueError(f"icp_multiscale: {name} must have one entry per scale ({n}), got {len(value)}")
+    return list(value)
+
+
+@torch.no_grad()
+def icp_multiscale(src_clouds, ref_clouds, T_init, voxel_sizes, max_iters, radii=None, estimator: str = "point",
+                   kernel: str = "l2", kernel_scales=None, search: str = "auto", batch: Optional[int] = None, *, engine):
+    """open3d's ``multi_scale_icp`` for lists of clouds of any sizes: coarse to fine, every scale one ``Engine.icp_refine`` from the
+    previous scale's pose.  src_clouds / ref_clouds: P clouds [n_i, >=3] each (numpy or tensors), T_init [P,3,4] with p_ref = T p_src;
+    voxel_sizes, max_iters: one entry per scale, in the order they run (coarse first); radii: the correspondence radius per scale
+    (None, or a None entry: 2 x that scale's voxel size); kernel_scales: the robust kernel's scale per scale (a scalar: the same at
+    every scale).  ``engine`` (keyword): the ``Engine`` that runs it; ``batch``: pairs per engine call (default: all of them, at most
+    the engine's max_pairs).
+    Per scale, and per batch of pairs: ``voxel_downsample`` of both sides (a voxel size of None or 0: the clouds as given),
+    ``pad_clouds`` with the counts, for ``estimator="plane"`` the normals of the downsampled reference from
+    ``radius_neighbors(radius = 2 x voxel, max_nn = 30)`` and ``estimate_normals(csr=)`` cloud by cloud (this needs a non-zero voxel
+    size at that scale, or rows that carry the normals in columns 3..5), then ``icp_refine``.  No kernel of its own: exactly these
+    engine calls, so the result is theirs byte for byte.
+    -> (T [P,3,4] float32 tensor of the last scale, stats: one [P,4|5] float64 tensor per scale)."""
+    S = len(voxel_sizes)
+    if S < 1 or len(max_iters) != S:
+        raise ValueError("icp_multiscale: voxel_sizes and max_iters need one entry per scale, at least one")
+    radii, kernel_scales = _per_scale(radii, S, "radii"), _per_scale(kernel_scales, S, "kernel_scales")
+    dev = engine.device
+    as_dev = lambda c: (c if isinstance(c, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(c, np.float32))).to(dev).float().contiguous()
+    srcs, refs = [as_dev(c) for c in src_clouds], [as_dev(c) for c in ref_clouds]
+    P = len(srcs)
+    if P < 1 or len(refs) != P:
+        raise ValueError("icp_multiscale: as many reference clouds as source clouds, at least one pair")
+    T = as_dev(np.asarray(T_init.detach().cpu() if isinstance(T_init, torch.Tensor) else T_init, np.float32)[:, :3]).clone()
+    if tuple(T.shape) != (P, 3, 4):
+        raise ValueError(f"icp_multiscale: T_init must be [{P}, 3, 4]")
+    per = int(batch or min(P, engine.max_pairs))
+    if per < 1:
+        raise ValueError("icp_multiscale: batch must be at least 1")
+
+    def down(clouds, voxel):
+        if not voxel:
+            return clouds
+        vox, counts = engine.voxel_downsample(clouds, float(voxel))
+        engine.sync()
+        n = counts.cpu().tolist()
+        return [vox[i, :n[i]].contiguous() for i in range(len(clouds))]
+
+    stats = []
+    for voxel, iters, radius, kscale in zip(voxel_sizes, max_iters, radii, kernel_scales):
+        if radius is None:
+            if not voxel:
+                raise ValueError("icp_multiscale: a scale without a voxel size needs its radius given")
+            radius = 2.0 * float(voxel)
+        st_scale = []
+        for b0 in range(0, P, per):
+            ids = range(b0, min(P, b0 + per))
+            s_list, r_list = down([srcs[i] for i in ids], voxel), down([refs[i] for i in ids], voxel)
+            src, n_s = pad_clouds(s_list)
+            ref, n_t = pad_clouds(r_list)
+            nrm = None
+            if estimator == "plane" and ref.shape[2] < 6:
+                if not voxel:
+                    raise ValueError("icp_multiscale: estimator='plane' at a scale without a voxel size needs rows that carry the "
+                                     "normals in columns 3..5")
+                nrm = pad_clouds([engine.estimate_normals(c[None], csr=engine.radius_neighbors(c[None], 2.0 * float(voxel), max_nn=30))[0][0]
+                                  for c in r_list])[0]
+            Tb, st = engine.icp_refine(src, ref, T[b0:b0 + len(ids)].contiguous(), float(radius), max_iter=int(iters), estimator=estimator,
+                                       normals_ref=nrm, search=search, counts_src=n_s, counts_ref=n_t, kernel=kernel, kernel_scale=kscale)
+            T[b0:b0 + len(ids)] = Tb
+            st_scale.append(st)
+        stats.append(torch.cat(st_scale, 0))
+    return T, stats
+
+
 def scene_batches(sizes, batch: int):
     """The ICP calls of ``register_scene``: ``sizes`` = (n_s, n_t) per edge -> lists of edge numbers, ``batch`` at a time in the order
     of a stable sort by n_s + n_t, so that a call's capacity stays close to its pairs' sizes.  Every edge is in exactly one list."""
@@ -645,7 +724,8 @@ def scene_batches(sizes, batch: int):
 @torch.no_grad()
 def register_scene(fragments, engine, edges, voxel_size: float = 0.05, max_corr_dist: Optional[float] = None, icp_max_iter: int = 30,
                    estimator: str = "point", search: str = "auto", preference: float = 1.0, overlap_min: float = OVERLAP_MIN,
-                   max_iter: int = 100, reference_node: int = 0, batch: int = 1):
+                   max_iter: int = 100, reference_node: int = 0, batch: int = 1, icp_kernel: str = "l2",
+                   icp_kernel_scale: Optional[float] = None):
     """A scene from its pairwise registrations.  fragments: clouds [n_i, >=3] (numpy or tensors, any sizes the engine takes);
     edges: rows (s, t, T_init [3,4] with p_t = T p_s, uncertain) from any pairwise path (``scene_edges_fpfh``, ...).  Per edge
     ``icp_refine`` (radius ``max_corr_dist``, default 2 x voxel size) then ``information_matrix``; an edge with
@@ -654,7 +734,8 @@ def register_scene(fragments, engine, edges, voxel_size: float = 0.05, max_corr_
     graph is optimised again from the first result.  ``batch``: edges per ICP call (at most the engine's max_pairs), whatever their
     sizes: each call pads its clouds (``pad_clouds``) and passes the sizes as counts, and by the contract of those entries
     (include/dsir.h, dsir_icp_refine_ex3) the result is the same, byte for byte, for every ``batch``.  ``estimator="plane"`` on rows
-    without normals estimates each fragment's normals once (``engine.icp_normals``).
+    without normals estimates each fragment's normals once (``engine.icp_normals``).  ``icp_kernel`` / ``icp_kernel_scale``:
+    ``icp_refine``'s robust ``kernel`` and ``kernel_scale`` for the edge poses; the information matrices do not see them.
     -> {"X": [N,3,4] f64 node poses (fragment -> scene, reference node the identity), "edges": one dict per input edge
     {s, t, T (refined), info, count, uncertain, line, dropped: None | "overlap" | "line"}, "stats": [stats of both optimisations]}."""
     from . import pose_graph as PG
@@ -673,7 +754,7 @@ def register_scene(fragments, engine, edges, voxel_size: float = 0.05, max_corr_
         nrm = pad_clouds([normals[rows[k]["t"]] for k in kb])[0] if normals else None
         T0 = torch.from_numpy(np.stack([np.asarray(edges[k][2], np.float32)[:3] for k in kb])).to(dev).contiguous()
         T, _ = engine.icp_refine(src, ref, T0, r, max_iter=icp_max_iter, estimator=estimator, normals_ref=nrm, search=search,
-                                 counts_src=n_s, counts_ref=n_t)
+                                 counts_src=n_s, counts_ref=n_t, kernel=icp_kernel, kernel_scale=icp_kernel_scale)
         info, count = engine.information_matrix(src, ref, T, r, search=search, counts_src=n_s, counts_ref=n_t)
         T, info, count = T.cpu().numpy().astype(np.float64), info.cpu().numpy(), count.cpu().numpy()
         for j, k in enumerate(kb):

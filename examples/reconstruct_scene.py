@@ -52,9 +52,11 @@ def scene_files(root, scene, max_fragments=None):
     return [plys[i] for i in range(n)], records("gt.log", 4), records("gt.info", 6)
 
 
-def run_scene(root, scene, method="fpfh", voxel=0.05, max_fragments=None, weights=None, hypotheses=8192, icp_batch=1):
+def run_scene(root, scene, method="fpfh", voxel=0.05, max_fragments=None, weights=None, hypotheses=8192, icp_batch=1, icp_kernel="l2",
+              icp_kernel_scale=None):
     """One scene end to end -> the dict that is printed: `harness.summarize_scene`'s, or {"skipped": reason}.  icp_batch: edges per
-    ICP and information-matrix call of `harness.register_scene` (same result for every value; the engine is made for that many pairs)"""
+    ICP and information-matrix call of `harness.register_scene` (same result for every value; the engine is made for that many pairs);
+    icp_kernel / icp_kernel_scale: the robust kernel of its edge refinement (open3d's `robust_kernel`; "l2": none)"""
     files, gt, gt_info = scene_files(root, scene, max_fragments)
     raw = [read_ply_xyz(f) for f in files]
     cfg = NetConfig(pipeline="feat") if method == "feat" else NetConfig()
@@ -78,7 +80,7 @@ def run_scene(root, scene, method="fpfh", voxel=0.05, max_fragments=None, weight
             edges = H.scene_edges_feat(frags, model, voxel_size=voxel, hypotheses=hypotheses)
         out = {"scene": scene, "fragments": len(frags), "points": [int(len(f)) for f in frags]}
         try:
-            res = H.register_scene(frags, use, edges, voxel_size=voxel, batch=max(1, icp_batch))
+            res = H.register_scene(frags, use, edges, voxel_size=voxel, batch=max(1, icp_batch), icp_kernel=icp_kernel, icp_kernel_scale=icp_kernel_scale)
         except ValueError as e:                                   # the kept edges do not connect the scene
             out["skipped"] = str(e)
             return out
@@ -99,12 +101,15 @@ def main(argv=None):
     ap.add_argument("--max-fragments", type=int, default=None)
     ap.add_argument("--weights", default=None)
     ap.add_argument("--icp-batch", type=int, default=1, help="edges per ICP / information-matrix call of register_scene (any sizes; same result)")
+    ap.add_argument("--icp-kernel", choices=("l2", "huber", "cauchy", "gm", "tukey"), default="l2",
+                    help="robust loss kernel of the edges' ICP refinement (open3d's robust_kernel)")
+    ap.add_argument("--icp-kernel-scale", type=float, default=None, help="its scale k in metres (needed unless --icp-kernel l2), e.g. the voxel size")
     a = ap.parse_args(argv)
     if not os.path.isdir(os.path.join(a.root, "test")):
         raise FileNotFoundError(f"Invalid path: {os.path.join(a.root, 'test')}")
     outs = []
     for scene in a.scenes:
-        outs.append(run_scene(a.root, scene, a.method, a.voxel, a.max_fragments, a.weights, a.hypotheses, a.icp_batch))
+        outs.append(run_scene(a.root, scene, a.method, a.voxel, a.max_fragments, a.weights, a.hypotheses, a.icp_batch, a.icp_kernel, a.icp_kernel_scale))
         print(outs[-1], flush=True)
     return outs
 

@@ -409,6 +409,33 @@ int dsir_icp_correspondences_ex(dsir_ctx* ctx, const float* points_src, const fl
                                 float max_corr_dist, const float* T, int search, int32_t* idx_out, float* d2_out, double* stats_out,
                                 const int32_t* counts_src, const int32_t* counts_ref);
 
+/* dsir_icp_refine_ex3 with a robust loss kernel of the estimator: open3d's `robust_kernel` argument of
+ * TransformationEstimationPointToPoint / PointToPlane (open3d is not pinned: the rule is this engine's own, csrc/icp_robust.h and
+ * the header of csrc/icp.hip, restated in tests/icp_robust_host.py).  Arguments as for dsir_icp_refine_ex3, then
+ *   kernel        DSIR_ICP_L2 .. DSIR_ICP_TUKEY;  kernel_scale  k > 0, finite, in the cloud's length unit (not read under l2).
+ * The weight of a correspondence, from its squared residual q and k, in fp64, every operation rounded once in the order written:
+ *   l2 1;  huber q <= k^2 ? 1 : k / sqrt(q);  cauchy 1 / (1 + q / k^2);  gm k / ((k + q) * (k + q)) (open3d's GMLoss);
+ *   tukey q <= k^2 ? (1 - q / k^2)^2 : 0.        (open3d's L1Loss is left out: its weight is unbounded at an exact partner.)
+ * estimator 0: q = the fp32 squared distance of the correspondence; the weight, rounded once to fp32, is the correspondence's
+ * weight in the weighted Kabsch update.  A pair whose weights are all 0 takes the identity update: T is carried over bit for bit.
+ * estimator 1: q = r^2 of the fp64 plane residual; A = sum w J J^T, b = sum w J r; a correspondence of weight 0 is not a row, so
+ * "fewer than 6 rows" and the singular-system rule (identity update, counted in stats[4]) apply to what is left.
+ * The kernel acts on the update ALONE: the search, fitness, inlier_rmse (unweighted point distances), the convergence test,
+ * max_iter, the stats columns - and dsir_information_matrix - do not see it.  kernel = DSIR_ICP_L2 writes, byte for byte, what
+ * dsir_icp_refine_ex3 writes (the four older entries run the same path with it); huber with k >= max_corr_dist does too (every
+ * weight is exactly 1; for estimator 1 given normals no longer than 1, so that |r| <= the point distance).  Same bytes on every run, for both values of `search`, and for a pair whatever else is in the batch,
+ * the counts' padding included.  Refused before any launch, with the usual error code and message: a kernel outside 0..4, and
+ * under a kernel other than l2 a scale that is 0, negative, NaN or infinite. */
+#define DSIR_ICP_L2 0
+#define DSIR_ICP_HUBER 1
+#define DSIR_ICP_CAUCHY 2
+#define DSIR_ICP_GM 3
+#define DSIR_ICP_TUKEY 4
+int dsir_icp_refine_ex4(dsir_ctx* ctx, const float* points_src, const float* points_ref, int pairs, int J, int K, int stride,
+                        float max_corr_dist, int max_iter, float rel_fitness, float rel_rmse, const float* T_init,
+                        float* T_out, int estimator, const float* normals_ref, int search, double* stats,
+                        const int32_t* counts_src, const int32_t* counts_ref, int kernel, float kernel_scale);
+
 /* Replaces the `use_tune` branch of pose_optimization (test.py:209-239): transformation_finetune (test.py:159-207) with
  * HighDimSmoothL1Loss (test.py:103-131) over the network's last correspondences, the pose re-parametrised as
  * network/DGR.py's Transformation (6-D rotation + translation, :60-132) and fitted by Adam (lr 0.1, ExponentialLR 0.999)

@@ -21,6 +21,11 @@ Mode "per-pair" is one dense call per pair, 32 calls; mode "batched" is one call
 pairs (batches as harness.register_scene makes them, padded with harness.pad_clouds), and checks that its poses and statistics are
 the per-pair ones byte for byte.  One JSON line per estimator, search and mode: the time for all 32 pairs.
 
+``--kernel`` / ``--kernel-scale`` time the loop under a robust loss kernel of the estimator (csrc/icp_robust.h); the iteration counts
+change with the kernel, so every line also carries the time per iteration (the call's time over the largest iteration count of its pairs).
+
+    python tools/bench_icp.py --pairs 8 --points 5000 --kernel l2 huber cauchy gm tukey --kernel-scale 0.03
+
 One JSON line per estimator and search: median / min / max milliseconds per call over --reps calls (after --warmup), the iterations each pair
 took.  ``--estimator point`` alone runs on a build that predates the plane estimator, for A/B runs against it.  The per-kernel
 split is the profiler's: ``rocprofv3 --kernel-trace --stats -- python tools/bench_icp.py ...``."""
@@ -141,6 +146,9 @@ def main():
     ap.add_argument("--tag", default="")
     ap.add_argument("--ragged", action="store_true", help="32 pairs of unequal sizes (2000..6000): one call per pair against one call with counts")
     ap.add_argument("--ragged-modes", nargs="+", choices=["per-pair", "batched"], default=["per-pair", "batched"])
+    ap.add_argument("--kernel", nargs="+", choices=["l2", "huber", "cauchy", "gm", "tukey"], default=None,
+                    help="robust kernels to time; without the flag the call is made as before it existed (least squares)")
+    ap.add_argument("--kernel-scale", type=float, default=0.03, help="the kernels' scale k (gm takes k * k: its k is a squared length)")
     a = ap.parse_args()
     if a.ragged:
         return ragged(a)
@@ -154,9 +162,11 @@ def main():
         if est == "plane":
             kw = dict(estimator="plane", normals_ref=eng.icp_normals(ref))
         first = None
-        for search in a.search or [None]:
+        for search, kernel in [(s_, k_) for s_ in a.search or [None] for k_ in a.kernel or [None]]:
             if search is not None:
                 kw["search"] = search
+            if kernel is not None:
+                kw.update(kernel=kernel, kernel_scale=a.kernel_scale ** 2 if kernel == "gm" else a.kernel_scale)
             ms = []
             for i in range(a.warmup + a.reps):
                 torch.cuda.synchronize()
@@ -166,13 +176,17 @@ def main():
                 if i >= a.warmup:
                     ms.append((time.perf_counter() - t0) * 1e3)
             out = (T.cpu().numpy().tobytes(), st.cpu().numpy().tobytes())
-            first = first or out
+            first = first if kernel not in (None, "l2") or first else out      # same_bytes_as_first compares the least-squares runs
             st = st.cpu().numpy()
             row = {"tag": a.tag, "estimator": est, "pairs": a.pairs, "points": a.points, "ms_median": round(float(np.median(ms)), 3),
                    "ms_min": round(min(ms), 3), "ms_max": round(max(ms), 3), "iterations": st[:, 3].astype(int).tolist(),
                    "converged": st[:, 2].astype(int).tolist(), "fitness_mean": round(float(st[:, 0].mean()), 4)}
             if search is not None:
-                row.update(search=search, radius=a.radius, same_bytes_as_first=out == first)
+                row.update(search=search, radius=a.radius)
+                if kernel in (None, "l2"):
+                    row.update(same_bytes_as_first=out == first)
+            if kernel is not None:
+                row.update(kernel=kernel, kernel_scale=kw["kernel_scale"], ms_per_iteration=round(float(np.median(ms)) / max(1, int(st[:, 3].max())), 4))
             print(json.dumps(row), flush=True)
     eng.close()
 
