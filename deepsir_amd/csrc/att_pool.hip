@@ -12,7 +12,8 @@
 //     MFMAs per product: split_f16.h; weights split at load): lane half h = 0 forms the gathered-feature part of an A row (one
 //     index, one row of the raw features, their GroupNorm + LeakyReLU), h = 1 the E part (from memory, or rebuilt from the per-point
 //     tables of lse_uv.hip); the normalised values double as the pooled operand through a wave-private LDS tile, so the epilogue
-//     gathers nothing.  (A first version kept round 3's split of the scores by linearity - S = G[nb] + W2 E with G = W1 fN a per-point
+//     gathers nothing - and, at level 0 in the first pooling of a block, as the operand of lfa.mlp2, which the same launch then
+//     writes with its statistics (att_pool16_kernel<true, true> below).  (A first version kept round 3's split of the scores by linearity - S = G[nb] + W2 E with G = W1 fN a per-point
 //     GEMM - and gathered G and fN in the epilogue: 20 KB of L2 reads per two points at d = 64, the matrix pipe 8 % busy, no faster
 //     than the kernel it replaced; profiles/README.md, round 4);
 //   * software pipeline: the next unit's rows are in flight during the current unit's MFMAs and epilogue, its neighbour indices one
@@ -35,16 +36,33 @@ using namespace attp;
 // same weights placed in columns 16 .. 31.  C[m][c < 16] is then tile A's result and C[m][c >= 16] tile B's: every lane of
 // the wave owns (point, column) work in the epilogue, no accumulator is moved between lanes.  Lane half h = 0 forms the
 // gathered-feature part of an A row (one index load, one 32-byte row gather, the producer's GroupNorm + LeakyReLU), h = 1
-// the E part; the normalised values double as the pooled operand through the LDS tile.  Round 3's kernel (pw_stream.hip
+// the E part (read, or rebuilt from the tables: U row of the neighbour, V row and dist of the point, the same GroupNorm +
+// LeakyReLU); the normalised values double as the pooled operand through the LDS tile.  Round 3's kernel (pw_stream.hip
 // EPI_ATT, exact-fp32 16 x 16 x 4 MFMAs) ran the matrix pipe 79 % and the vector ALU 57 % busy; this one issues 6 fp16 MFMAs
 // (192 cycles) and ~250 vector instructions per four points.
-template <bool UV>   // UV: the E half of an A row rebuilt from the per-point tables of lse_uv.hip; occupancy floor: five (tables: four) waves per SIMD - the next step down spills 64 - 116 bytes and doubles the kernel time
+//
+// E2, the PRODUCING variant (the first pooling of a block, E from the tables): the launch also writes lfa.mlp2 of the E rows it has
+// just rebuilt and normalised - RandLANet.py:186, until now a launch of its own (pw_stream.hip, loader S_UV) that gathered the same
+// table rows and rebuilt the same 16 n rows a second time.  Every element and both statistics words keep that launch's bits:
+//   * the product is ITS product: exact-fp32 v_mfma_f32_16x16x4f32, a tile = the 16 neighbours of one point, lane (r, q) holding
+//     channels 2 q, 2 q + 1 of row r, two k steps, bias added after - the operands come back from the wave's LDS tile;
+//   * the statistics are ITS sums: that launch's tile t = point t belongs to wave t & 3 of virtual workgroup (t >> 2) mod V and is
+//     added in ascending t - i.e. unit u = t >> 2 of this kernel carries one tile of each of the four waves of virtual workgroup
+//     u mod V.  So here wave g < V walks the units g, g + V, ... (V = e2_vgx: the launcher sizes the grid by it), keeps the four waves'
+//     per-lane sums apart, reduces them as that launch does (lane butterfly, waves in ascending order) and commits the workgroup's
+//     contribution itself (gn_wave_commit).  One contribution per virtual workgroup, as before.
+template <bool UV, bool E2 = false>   // UV: the E half of an A row rebuilt from the per-point tables of lse_uv.hip; occupancy floor: five (tables: four) waves per SIMD - the next step down spills 64 - 116 bytes and doubles the kernel time
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(UV ? 4 : 5, UV ? 4 : 5))) void att_pool16_kernel(const AttPool16Args p) {
+  static_assert(UV || !E2, "the producing variant rebuilds E from the tables");
   constexpr int LD = 20;                  // LDS row stride (floats): rows 4 apart land 16 banks apart
   constexpr int TB = 32 * LD + 32;        // tile B's offset: 32 banks away from tile A
   __shared__ float s_sc[16];
   __shared__ float s_sh[16];
   __shared__ __attribute__((aligned(16))) float s_t[4][TB + 32 * LD];
+  // E2: the lfa.mlp2 fragments and bias by lane, and every wave's statistics [virtual wave][sum | sum of squares][lane] - in LDS, not in
+  // registers: the kernel sits at its occupancy floor with four registers to spare
+  __shared__ float s_e2w[E2 ? 3 * 64 : 1];
+  __shared__ float s_g[E2 ? 4 * 8 * 64 : 1];
 
   const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int m = lane & 31, h = lane >> 5;
@@ -78,8 +96,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(UV ? 4 : 5,
   const int etile = m >> 4, ecol = m & 15;                          // the epilogue's (tile, column) of this lane
 
   const int units = (p.n + 3) >> 2;
-  const int nw = p.grid_x * 4;
-  int u = bx * 4 + w;
+  const int nw = E2 ? p.e2_vgx : p.grid_x * 4;
+  const int gwave = bx * 4 + w;
+  int u = (E2 && gwave >= nw) ? units : gwave;      // E2: a wave past the virtual grid has no units (V <= units)
+  // E2: the lfa.mlp2 fragments of lane (fr = column / tile row, fq = channel pair) and the four virtual waves' statistics
+  const int fr = lane & 15, fq = lane >> 4;
+  float* G = &s_g[E2 ? w * 8 * 64 + lane : 0];
+  if (E2) {
+    if (w == 0) {
+      s_e2w[lane] = fr < 8 ? p.e2_W[fr * 8 + 2 * fq] : 0.f;
+      s_e2w[64 + lane] = fr < 8 ? p.e2_W[fr * 8 + 2 * fq + 1] : 0.f;
+      s_e2w[128 + lane] = (fr < 8 && p.e2_b) ? p.e2_b[fr] : 0.f;
+    }
+#pragma unroll
+    for (int q = 0; q < 8; ++q) G[q * 64] = 0.f;
+  }
+  float* E2b = E2 ? p.e2_Y + cloud * p.e2_cs : nullptr;
 
   // pipeline: rows of unit u + nw and indices of unit u + 2 nw are in flight while unit u is computed
   auto point_of = [&](int uu, int tile) { return min(4 * uu + 2 * tile + pm, p.n - 1); };
@@ -188,6 +220,31 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(UV ? 4 : 5,
     }
     const int pt = 4 * u + 2 * etile + h;
     if (pt < p.n) Yb[(uint32_t)pt * 16u + (uint32_t)ecol] = o * __builtin_amdgcn_rcpf(se);
+    if (E2) {
+      // lfa.mlp2 of the unit's four points: point 4 u + q sits in tile q >> 1 as point q & 1; its neighbour r is tile row
+      // 8 (r >> 2) + 4 (q & 1) + (r & 3), its normalised E channels columns 8 .. 15 of the row
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int mr = ((fr >> 2) << 3) | ((q & 1) << 2) | (fr & 3);
+        const float2 ev = *reinterpret_cast<const float2*>(&T[(q >> 1) * TB + mr * LD + 8 + 2 * fq]);
+        f32x4 c = f32x4{0.f, 0.f, 0.f, 0.f};
+        c = __builtin_amdgcn_mfma_f32_16x16x4f32(ev.x, s_e2w[lane], c, 0, 0, 0);
+        c = __builtin_amdgcn_mfma_f32_16x16x4f32(ev.y, s_e2w[64 + lane], c, 0, 0, 0);
+        const int pq = 4 * u + q;
+        if (pq < p.n && fr < 8) {
+          const float e2b = s_e2w[128 + lane];
+          float g1 = G[(2 * q) * 64], g2 = G[(2 * q + 1) * 64];
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float v = c[r] + e2b;
+            st_f32(E2b, 4u * ((uint32_t)(pq * 16 + 4 * fq + r) * 8u + (uint32_t)fr), v);
+            g1 += v;
+            g2 += v * v;
+          }
+          G[(2 * q) * 64] = g1; G[(2 * q + 1) * 64] = g2;
+        }
+      }
+    }
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
@@ -196,6 +253,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(UV ? 4 : 5,
       ad[t] = adn[t];
     }
     u = un;
+  }
+  if (E2 && gwave < nw) {
+    // the virtual workgroup's contribution: per wave the butterfly over the lane rows, the waves added in ascending order - then the
+    // per-column sums go through the wave's LDS tile to the commit
+    float c1 = 0.f, c2 = 0.f;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      float s1 = G[(2 * q) * 64], s2 = G[(2 * q + 1) * 64];
+      s1 += __shfl_xor(s1, 16); s1 += __shfl_xor(s1, 32);
+      s2 += __shfl_xor(s2, 16); s2 += __shfl_xor(s2, 32);
+      c1 += s1; c2 += s2;
+    }
+    if (lane < 16) { T[lane * 2] = c1; T[lane * 2 + 1] = c2; }
+    __builtin_amdgcn_wave_barrier();
+    gn_wave_commit(T, 0, 8, 8 / p.e2_groups, p.e2_stats + (int64_t)cloud * p.e2_groups * kGnWords);
   }
 }
 
@@ -368,8 +440,18 @@ __global__ __launch_bounds__(512) void att_full128_kernel(const AttPool16Args p)
 
 }  // namespace
 
+// the producing variant's own envelope (on top of launch_att_pool16's): tables, an 8 x 8 lfa.mlp2 in groups that divide 8, a virtual
+// grid within the exactness bound of the statistics
+bool att_pool16_produces(const AttPool16Args& a) {
+  if (!a.e2_W || a.enc || !a.uv || a.n <= 0) return false;
+  if (a.e2_groups < 1 || (8 % a.e2_groups) != 0) return false;
+  return att_pool16_gn_contributions(a.n) <= kGnMaxContrib;
+}
+int att_pool16_gn_contributions(int n) { return pw_stream_gn_contributions(n * 16, 8); }
+
 bool launch_att_pool16(const AttPool16Args& a, hipStream_t st) {
   if (a.n <= 0 || a.clouds <= 0) return true;
+  if ((a.e2_Y || a.e2_W) && (!a.e2_Y || !a.e2_stats || !att_pool16_produces(a))) return false;
   if (!a.Wh || !a.Wl || !a.f || !a.neigh || !a.Y) return false;
   if (!a.enc && (!a.uv || !a.dist || !a.w8 || (reinterpret_cast<uintptr_t>(a.uv) % 16) != 0 || (a.uv_cs % 4) != 0)) return false;
   if ((a.ldw % 8) != 0 || (reinterpret_cast<uintptr_t>(a.Wh) % 16) != 0 || (reinterpret_cast<uintptr_t>(a.Wl) % 16) != 0) return false;
@@ -386,6 +468,14 @@ bool launch_att_pool16(const AttPool16Args& a, hipStream_t st) {
   }
   if (blocks < 1) blocks = 1;
   AttPool16Args b = a;
+  if (a.e2_Y) {
+    // the grid is the row-streaming launch's VIRTUAL grid, one wave per virtual workgroup: a function of n alone, like its sums
+    b.e2_vgx = att_pool16_gn_contributions(a.n);
+    blocks = (b.e2_vgx + 3) / 4;
+    b.grid_x = blocks;
+    hipLaunchKernelGGL((att_pool16_kernel<true, true>), dim3((unsigned)((int64_t)blocks * a.clouds)), dim3(256), 0, st, b);
+    return true;
+  }
   b.grid_x = blocks;
   if (a.enc) hipLaunchKernelGGL(att_pool16_kernel<false>, dim3((unsigned)((int64_t)blocks * a.clouds)), dim3(256), 0, st, b);
   else hipLaunchKernelGGL(att_pool16_kernel<true>, dim3((unsigned)((int64_t)blocks * a.clouds)), dim3(256), 0, st, b);
@@ -396,6 +486,7 @@ bool launch_att_pool16(const AttPool16Args& a, hipStream_t st) {
 // tables [n][64]), fc [2 KH][ldw], Y [n][2 KH]
 bool launch_att_full(const AttPool16Args& a, int KH, hipStream_t st) {
   if (a.n <= 0 || a.clouds <= 0) return true;
+  if (a.e2_Y || a.e2_W) return false;        // levels 1 / 2 have no producing variant
   if ((KH != 32 && KH != 64) || !a.Wh || !a.Wl || !a.f || !a.neigh || !a.Y) return false;
   if (!a.enc && (KH != 32 || !a.uv || !a.dist || !a.w8 || (reinterpret_cast<uintptr_t>(a.uv) % 16) != 0 || (a.uv_cs % 4) != 0)) return false;
   if ((a.ldw % 8) != 0 || (reinterpret_cast<uintptr_t>(a.Wh) % 16) != 0 || (reinterpret_cast<uintptr_t>(a.Wl) % 16) != 0) return false;

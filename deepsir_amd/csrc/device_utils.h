@@ -140,13 +140,16 @@ __device__ __forceinline__ double gn_stat_limb(double v, int limb) {
 // sums part[col * 2 + {0: sum x, 1: sum x^2}] (LDS, complete and barrier-separated from this call).  Atomic INSTRUCTIONS are
 // what the chip rations (about one wave-instruction per 50 ns per CU, MI355X_MICROARCH.md), so the whole contribution - every
 // group the range touches x {sum, sum of squares} x {L1, L0} - leaves in one instruction per wave that holds any of it.
-// The order of every addition is fixed by the column index alone.  Call with ALL 256 threads of the block.
+// The order of every addition is fixed by the column index alone.  Call with ALL 256 threads of the block (NT = 64: with all lanes of
+// one wave, gn_wave_commit below).
+template <int NT = 256>
 __device__ __forceinline__ void gn_block_commit(const float* part, int n0, int ncols, int gw, double* stats_cloud) {
   const int g0 = n0 / gw, ng = (n0 + ncols - 1) / gw - g0 + 1;
   // 16 lanes per (group, statistic): lane j adds columns j, j + 16, ... of the group in ascending order, then a fixed butterfly
   // over the 16 lanes (a serial loop over up to 64 columns was the longest dependent chain of a workgroup's tail)
-  const int t = threadIdx.x, j = t & 15;
-  for (int q = t >> 4; q < ((ng * 2 + 15) & ~15); q += 16) {   // q = (group, statistic); one trip unless a range holds > 8 groups
+  const int t = NT == 256 ? threadIdx.x : threadIdx.x & (NT - 1), j = t & 15;
+  constexpr int QT = NT / 16;                                  // (group, statistic) pairs per trip
+  for (int q = t >> 4; q < ((ng * 2 + QT - 1) & ~(QT - 1)); q += QT) {   // q = (group, statistic); one trip unless a range holds > 8 groups
     const bool live = q < ng * 2;
     const int g = g0 + (q >> 1), stat = q & 1;
     const int c0 = max(g * gw, n0) - n0, c1 = min((g + 1) * gw, n0 + ncols) - n0;
@@ -157,6 +160,11 @@ __device__ __forceinline__ void gn_block_commit(const float* part, int n0, int n
     if (live && j < 2)                                       // lanes 0 / 1 of the quad carry the two limbs
       unsafeAtomicAdd(stats_cloud + (int64_t)g * kGnWords + 2 * stat + j, gn_stat_limb(d, j));   // global_atomic_add_f64, integer-valued operands
   }
+}
+// The same contribution from ONE wave that owns `part` alone: gn_block_commit<64> - per (group, statistic) the same 16 lanes' column
+// sums and the same butterfly, four of them per trip, so the committed limbs are those a 256-thread block forms of the same sums.
+__device__ __forceinline__ void gn_wave_commit(const float* part, int n0, int ncols, int gw, double* stats_cloud) {
+  gn_block_commit<64>(part, n0, ncols, gw, stats_cloud);
 }
 // 1 / sqrt(var + eps) of GroupNorm (eps = 1e-5, RandLANet.py:93): the hardware's v_rsq_f64 seed (about 2^-27 relative) and two
 // Newton steps in fp64 (error squared twice: far below 2^-52), a dozen instructions instead of the ~40 of a correctly rounded

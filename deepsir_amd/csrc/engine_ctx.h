@@ -262,6 +262,7 @@ void fill_pyramid_layout(const dsir_cfg& cfg, int clouds, int n, Pyramid& p);
 int gn_max_contributions(const dsir_cfg& g, int n, int flags = 0);
 int randla_forward(dsir_ctx* c, const RandlaW& w, const Seg& in0, const Seg* in1, const Pyramid& py, float* feat_out,
                    float* logits_out, EncCache* cache = nullptr);
+int run_lfa_enc2_probe(dsir_ctx* c, const RandlaW& w, int level, int fused, const Pyramid& py, float* rows_out, double* stats_out);
 int run_ppf_pre(dsir_ctx* c, const RandlaW& w, const float* rows, int stride, const int32_t* neigh, int64_t neigh_cs, int clouds, int n,
                 float* out);
 float* run_mlp_feat(dsir_ctx* c, const float* feat0, int clouds, int n, float* out = nullptr);   // out: caller-owned [clouds][n][64] or the arena

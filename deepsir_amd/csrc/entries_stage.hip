@@ -43,6 +43,20 @@ int dsir_randla_forward(dsir_ctx* c, int which, const float* features, int cin, 
   return call.finish();
 }
 
+int dsir_lfa_enc2_probe(dsir_ctx* c, int which, int level, int fused, int clouds, int n, const float* xyz, const int32_t* neigh,
+                        float* rows, double* stats) {
+  Call call(c, Call::kWeights); if (call.refused()) return 1;
+  if (which != 0 && c->cfg.pipeline != DSIR_PIPELINE_ALIGN) return fail(c, "dsir_lfa_enc2_probe: this context has no inlier_model (pipeline != align)");
+  if (!xyz || !neigh || !rows || !stats || clouds < 1 || level < 0 || level >= c->cfg.num_layers) return fail(c, "dsir_lfa_enc2_probe: bad arguments");
+  if (check_batch(c, "dsir_lfa_enc2_probe", clouds, n)) return 1;
+  Pyramid py;
+  fill_pyramid_layout(c->cfg, clouds, n, py);
+  if (py.nl[c->cfg.num_layers - 1] < kKnn) return fail(c, "cloud too small (n=%d)", n);
+  py.xyz = xyz; py.neigh = neigh;
+  if (int r = run_lfa_enc2_probe(c, which == 0 ? c->net.feat : c->net.inl, level, fused, py, rows, stats)) return r;
+  return call.finish();
+}
+
 int dsir_ppf_pre(dsir_ctx* c, int which, const float* rows, int stride, const int32_t* neigh, int64_t neigh_cs, int clouds, int n,
                  float* out) {
   Call call(c, Call::kWeights); if (call.refused()) return 1;

@@ -157,8 +157,23 @@ struct AttPool16Args {
   int64_t y_cs = 0;
   int n = 0, clouds = 0;
   int grid_x = 0;                    // filled by the launcher
+  // The PRODUCING variant (level 0, E rebuilt from the tables): the launch also writes lfa.mlp2 of the rows it rebuilds - the raw
+  // convolution outputs and their GroupNorm statistics, every bit what pw_stream.hip's table loader (S_UV) gives them.  Off: e2_W null.
+  const float* e2_W = nullptr;       // lfa.mlp2 weights [8][8] fp32, bias [8] (or nullptr)
+  const float* e2_b = nullptr;
+  float* e2_Y = nullptr;             // [clouds][n * 16][8]
+  int64_t e2_cs = 0;
+  double* e2_stats = nullptr;        // [clouds][e2_groups][kGnWords], zeroed
+  int e2_groups = 0;
+  int e2_vgx = 0;                    // filled by the launcher: the virtual workgroups per cloud of the row-streaming launch
 };
 bool launch_att_pool16(const AttPool16Args& a, hipStream_t st);
+// would launch_att_pool16 take the layer WITH its e2_* outputs?  Shapes only (e2_W, e2_groups set; e2_Y / e2_stats may still be
+// null): Sched::att asks before it takes storage for the second product
+bool att_pool16_produces(const AttPool16Args& a);
+// contributions per (cloud, group) statistic of lfa.mlp2 when the pooling launch produces it: one per wave that plays a virtual
+// workgroup of the row-streaming launch - the same count, by construction
+int att_pool16_gn_contributions(int n);
 // levels 1 / 2 (d = 64 / 128) in the same unsplit form: KH-channel halves (f [n][f_ld], E [n * 16][KH] or - KH = 32 - tables [n][64]),
 // fc [2 KH][ldw], Y [n][2 KH]
 bool launch_att_full(const AttPool16Args& a, int KH, hipStream_t st);

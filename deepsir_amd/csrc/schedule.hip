@@ -51,6 +51,7 @@ int gn_max_contributions(const dsir_cfg& g, int n, int flags) {
     if (ppf && l == 0) { const int c = pw_gemm_gn_contributions(m); if (c > worst) worst = c; }   // Cin = 12: the general kernel
     else { layer(m, dim, d / 2); layer(m, dim, 2 * d); }         // mlp1, mlp_skip
     if (d / 2 == 8 || d / 2 == 32) { const int c = lse_uv_gn_contributions(m, d / 2); if (c > worst) worst = c; }
+    if (d / 2 == 8) { const int c = att_pool16_gn_contributions(m); if (c > worst) worst = c; }   // lfa.mlp2 from the first pooling (= its own launch's count)
     layer(mk, 10, d / 2);                                        // lfa.mlp1 (also when the tables are switched off)
     layer(mk, d / 2, d / 2);                                     // lfa.mlp2
     layer(m, d, d / 2); layer(m, d, d); layer(m, d, 2 * d);      // att_pooling_1.mlp, att_pooling_2.mlp, mlp2
@@ -283,14 +284,23 @@ struct Sched {
     a.Y = y.p; a.y_cs = (int64_t)n * w.d; a.n = n; a.clouds = clouds;
     return a;
   }
+  // lfa.mlp2 as a second product of a block's FIRST pooling (att_pool.hip, the producing variant): what Sched::att is asked for and
+  // what it answers.  buf / stats: caller-owned storage (the registration's cache) or nullptr: the pass's arenas.
+  struct AttEnc2 {
+    const Mlp2dW* w = nullptr;
+    float* buf = nullptr;
+    double* stats = nullptr;
+    bool done = false;     // out is lfa.mlp2's activation, exactly mlp2d()'s: nothing more to launch
+    Act out;
+  };
   // Att_pooling up to (not including) its MLP2D: softmax_k(fc [gather(f); enc]) . [gather(f); enc].  One ladder by the level width d:
-  //   16          att_pool.hip, four points per wave
+  //   16          att_pool.hip, four points per wave; with table-only enc and e2 set it also writes lfa.mlp2 (e2->done)
   //   64, 128     att_pool.hip, unsplit (a walker phase when recording)
   //   256         pw_tile.hip, EPI_ATT2: the score GEMM split by linearity, after its G GEMM (both walker phases when recording)
   //   otherwise, or when the width's own kernel refuses the layer: the general EPI_ATT kernel (pw_gemm.hip)
   // s2 / s2_mode: the cache of the enc half of the scores (kernels.h, GemmArgs::s2), kept by the widths of att_keeps_score_cache()
   Act att(const AttW& w, const Act& f, const Act& enc, const int32_t* neigh, int64_t neigh_cs, int n, float* s2 = nullptr,
-          int s2_mode = 0) {
+          int s2_mode = 0, AttEnc2* e2 = nullptr) {
     Act y;
     y.p = c->ws.get<float>((size_t)clouds * n * w.d);
     y.C = w.d; y.rows = n;
@@ -298,8 +308,25 @@ struct Sched {
     const bool fc16 = c->dweights16 && w.fc >= c->dweights && w.fc < c->dweights + c->nweights;   // att_pool.hip reads fc as its fp16 split
     if (w.d == 16 && halves && fc16) {
       // att_pool.hip, level 0: four points per wave, fp16-split scores, softmax in registers
-      const AttPool16Args a = att_pool_args(w, f, enc, neigh, neigh_cs, n, y);
+      AttPool16Args a = att_pool_args(w, f, enc, neigh, neigh_cs, n, y);
       rec_flush();
+      if (e2 && e2->w && enc.uv && !enc.p && e2->w->cin == 8 && e2->w->cout == 8) {
+        a.e2_W = e2->w->W; a.e2_b = e2->w->b; a.e2_groups = e2->w->groups;
+        if (att_pool16_produces(a)) {
+          const int M = n * kKnn;
+          Act& o = e2->out;
+          o.p = e2->buf ? e2->buf : c->ws.get<float>((size_t)clouds * M * 8);
+          o.C = 8; o.rows = M; o.act = 1;
+          double* st_out = e2->stats ? e2->stats : stats_slot(e2->w->groups);
+          o.gn = gn_of(st_out, *e2->w, M);
+          a.e2_Y = o.p; a.e2_cs = (int64_t)M * 8; a.e2_stats = st_out;
+          if (c->ws.overflow) return y;
+          if (launch_att_pool16(a, st)) { e2->done = true; return y; }
+          refuse("attentive pooling: the producing variant refused a layer it had accepted");
+          return y;
+        }
+        a.e2_W = a.e2_b = nullptr; a.e2_groups = 0;
+      }
       if (!c->ws.overflow && launch_att_pool16(a, st)) return y;
     } else if ((w.d == 64 || w.d == 128) && halves && fc16 && (enc.p || w.d == 64)) {
       // att_pool.hip, levels 1 / 2 unsplit: the whole score contraction on the matrix pipe, nothing gathered in the epilogue
@@ -436,6 +463,45 @@ int run_ppf_pre(dsir_ctx* c, const RandlaW& w, const float* rows, int stride, co
   return 0;
 }
 
+// lfa.mlp2 of one level alone, by either of its producers (dsir_lfa_enc2_probe): lfa.mlp1's tables, then the row-streaming launch
+// (fused = 0) or the first pooling's producing variant on zero features (fused = 1; the second product does not read them).
+int run_lfa_enc2_probe(dsir_ctx* c, const RandlaW& w, int level, int fused, const Pyramid& py, float* rows_out, double* stats_out) {
+  const BlockW& b = w.blk[level];
+  if (!b.lse_w8 || !lse_uv_enabled()) return fail(c, "lfa_enc2_probe: level %d has no position-encoding tables", level);
+  const int n = py.nl[level], M = n * kKnn, ch = b.lfa2.cout;
+  hipStream_t st = c->stream;
+  const size_t stats_need = 2 * gn_layer_words(py.clouds);
+  if (stats_need > c->stats_cap) return fail(c, "stats arena too small (%zu > %zu)", stats_need, c->stats_cap);
+  c->call.stats_top = 0;
+  HIP_OK(c, hipMemsetAsync(c->stats, 0, stats_need * sizeof(double), st));
+  Sched s{c, st, py.clouds};
+  const int64_t xyz_cs = (int64_t)py.S * 3, neigh_cs = (int64_t)py.S * kKnn;
+  const int32_t* nb_l = py.neigh + (int64_t)py.off[level] * kKnn;
+  const Act enc = s.lse_uv(b.lfa1, b.lse_w8, py.xyz + (int64_t)py.off[level] * 3, xyz_cs, nb_l, neigh_cs, n, nullptr, nullptr, nullptr);
+  Act enc2;
+  if (fused) {
+    Act f;
+    f.C = b.d / 2; f.rows = n; f.act = 1;
+    f.p = c->ws.get<float>((size_t)py.clouds * n * f.C);
+    if (c->ws.overflow) return overflow_fail(c, "workspace exhausted in lfa_enc2_probe");
+    HIP_OK(c, hipMemsetAsync(f.p, 0, sizeof(float) * py.clouds * n * f.C, st));
+    Sched::AttEnc2 e2;
+    e2.w = &b.lfa2;
+    s.att(b.att1, f, enc, nb_l, neigh_cs, n, nullptr, 0, &e2);
+    if (!c->ws.overflow && !e2.done) return fail(c, "lfa_enc2_probe: the first pooling of level %d does not produce lfa.mlp2", level);
+    enc2 = e2.out;
+  } else {
+    enc2 = s.mlp2d(b.lfa2, Sched::seg_of(enc, nb_l, neigh_cs), nullptr, M, true);
+  }
+  if (c->ws.overflow) {
+    if (c->call.sched_error) return fail(c, "lfa_enc2_probe: %s (level %d)", c->call.sched_error, level);
+    return overflow_fail(c, "workspace exhausted in lfa_enc2_probe");
+  }
+  HIP_OK(c, hipMemcpyAsync(rows_out, enc2.p, sizeof(float) * py.clouds * M * ch, hipMemcpyDeviceToDevice, st));
+  HIP_OK(c, hipMemcpyAsync(stats_out, enc2.gn.stats, sizeof(double) * py.clouds * b.lfa2.groups * kGnWords, hipMemcpyDeviceToDevice, st));
+  return 0;
+}
+
 // RandLA.forward (RandLANet.py:311-372).  in0/in1: the (possibly concatenated / gathered) input features.
 // cache: the position-encoding branch computed once per registration (EncCache, engine_ctx.h).
 int randla_forward(dsir_ctx* c, const RandlaW& w, const Seg& in0, const Seg* in1, const Pyramid& py, float* feat_out,
@@ -502,9 +568,23 @@ int randla_forward(dsir_ctx* c, const RandlaW& w, const Seg& in0, const Seg* in1
     if (!paired) f = s.mlp2d(b.mlp1, xin, nullptr, n, true);
     const Act enc = ahead ? enc_pre[l] : enc_of(l);
     const int s2_mode = reuse ? 2 : 1;      // iteration 0 stores the pyramid-only half of the scores, later iterations load it
-    Act agg = s.att(b.att1, f, enc, nb_l, neigh_cs, n, cache ? cache->s2_buf[l][0] : nullptr, s2_mode);
+    // table-only rows, not from the cache: the first pooling rebuilds every row of lfa.mlp1 anyway and writes lfa.mlp2 of it as well
+    // (level 0), into the storage enc2_of() would have used - the cache's when there is one, so later iterations read it as before
+    // Only where that launch fills the chip: its grid is the virtual grid of the statistics (one wave per n / 32 rows of a cloud, fixed by
+    // n), while the pooling alone spreads a small launch over 512 workgroups of one-unit waves - with a few clouds in flight (the
+    // captured batch-1 registration) the two-launch schedule stands, unmeasured against the other there.
+    static const bool no_att_enc2 = tuning_flag("DSIR_NO_ATT_ENC2");   // A/B switch: lfa.mlp2 as a launch of its own (pw_stream.hip)
+    static const long long att_enc2_min = tuning_int("DSIR_ATT_ENC2_MIN_BLOCKS", 512);   // tuning hook: workgroups of the producing launch
+    Sched::AttEnc2 e2;
+    if (!no_att_enc2 && !reuse && !ahead && enc.uv && !enc.p && b.d == 16 &&
+        (int64_t)((att_pool16_gn_contributions(n) + 3) / 4) * py.clouds >= att_enc2_min) {
+      e2.w = &b.lfa2;
+      e2.buf = cache ? cache->enc2_buf[l] : nullptr;
+      e2.stats = cache ? cache->enc2_stats[l] : nullptr;
+    }
+    Act agg = s.att(b.att1, f, enc, nb_l, neigh_cs, n, cache ? cache->s2_buf[l][0] : nullptr, s2_mode, e2.w ? &e2 : nullptr);
     Act a1 = s.mlp2d(b.att1.mlp, Sched::seg_of(agg), nullptr, n, true);
-    const Act enc2 = ahead ? enc2_pre[l] : enc2_of(l, enc);
+    const Act enc2 = ahead ? enc2_pre[l] : (e2.done ? e2.out : enc2_of(l, enc));
     if (cache && !reuse) { cache->enc[l] = enc; cache->enc2[l] = enc2; }
     Act agg2 = s.att(b.att2, a1, enc2, nb_l, neigh_cs, n, cache ? cache->s2_buf[l][1] : nullptr, s2_mode);
     Act a2 = s.mlp2d(b.att2.mlp, Sched::seg_of(agg2), nullptr, n, true);

@@ -228,6 +228,26 @@ class Engine:
         self.sync()
         return feat, logits
 
+    def lfa_enc2_probe(self, which: str, level: int, fused: bool, xyz, neigh, n: int):
+        """Debug entry (include/dsir.h, dsir_lfa_enc2_probe): lfa.mlp2 of one pyramid level alone, by the row-streaming launch
+        (fused=False) or by the first pooling's producing variant (fused=True); xyz / neigh: the pyramid of clouds of n points ->
+        (rows [c, 16 n_level, d/2] raw convolution
+        outputs, stats [c, groups, 4] float64 as committed; groups as the engine assigns them: 8 from 64 channels up, else 4)."""
+        xyz, neigh = _chk(xyz, torch.float32, "xyz"), _chk(neigh, torch.int32, "neigh_idx")
+        c = xyz.shape[0]
+        assert xyz.shape[1] == self.pyramid_shapes(n)[0]
+        nl = n
+        for r in self.cfg.sub_sampling_ratio[:level]:
+            nl //= r
+        ch = self.cfg.d_out[level] // 2
+        rows = self._empty((c, 16 * nl, ch))
+        stats = self._empty((c, 8 if ch >= 64 else 4, 4), torch.float64)
+        self._pre()
+        self._call(self.lib.dsir_lfa_enc2_probe(self.h, {"feat_extractor": 0, "inlier_model": 1}[which], level, int(fused), c, n, _ptr(xyz),
+                                                _ptr(neigh), _ptr(rows), _ptr(stats)))
+        self.sync()
+        return rows, stats
+
     def ppf_pre(self, which: str, rows, neigh_multi):
         """The use_ppf front end of RandLA.forward (RandLANet.py:324-332; csrc/ppf.hip): rows [c,n,>=6] = xyz + normal,
         neigh_multi the pyramid's neigh_idx [c,S,16] (its level-0 rows are read) -> [c,n,12], the input of level 0."""

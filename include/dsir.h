@@ -122,6 +122,15 @@ int dsir_randla_forward(dsir_ctx* ctx, int which, const float* features, int cin
                         const float* xyz_multi, const int32_t* neigh_idx, const int32_t* sub_idx,
                         const int32_t* interp_idx, float* feat, float* logits);
 
+/* Debug entry: lfa.mlp2 (RandLANet.py:186) of pyramid level `level` of network `which`, alone, by either of its two producers on
+ * the per-point tables of lfa.mlp1: fused = 0 the row-streaming launch of its own, fused = 1 the producing variant of the block's
+ * first attentive pooling (an error where that level's pooling has none).  Pyramids as produced by dsir_knn_pyramid.
+ * Outputs: rows [clouds][16 n_level][d_out[level] / 2], the raw convolution outputs; stats [clouds][groups][4] doubles (groups = 8 from 64 channels up, else 4), the layer's
+ * GroupNorm statistics as committed ({L1, L0} limbs of the sum, then of the sum of squares, per group).  The two producers must
+ * agree in every bit of both. */
+int dsir_lfa_enc2_probe(dsir_ctx* ctx, int which, int level, int fused, int clouds, int n, const float* xyz_multi,
+                        const int32_t* neigh_idx, float* rows, double* stats);
+
 /* Under DSIR_FLAG_PPF dsir_randla_forward takes rows of cin >= 6 columns (xyz, normal) for either network (the reference's
  * inlier model is handed [moved src xyz ; matched ref xyz] there, model.py:574-577: its "normals" are the matched points),
  * and dsir_forward_pair / dsir_register read points_src / points_ref as rows of feat_len columns with the normal in 3 .. 5.
