@@ -265,7 +265,16 @@ int randla_forward(dsir_ctx* c, const RandlaW& w, const Seg& in0, const Seg* in1
 int run_lfa_enc2_probe(dsir_ctx* c, const RandlaW& w, int level, int fused, const Pyramid& py, float* rows_out, double* stats_out);
 int run_ppf_pre(dsir_ctx* c, const RandlaW& w, const float* rows, int stride, const int32_t* neigh, int64_t neigh_cs, int clouds, int n,
                 float* out);
-float* run_mlp_feat(dsir_ctx* c, const float* feat0, int clouds, int n, float* out = nullptr);   // out: caller-owned [clouds][n][64] or the arena
+// How mlp_feat is launched.  Auto: the fused launch (feat_chain.hip) where it takes the layers and the launch is large enough
+// (feat_chain_wanted, schedule.hip), else the three launches.  Three: the three launches.  Fused: the fused launch or nothing
+// (nullptr returned: refused).  max_blocks > 0 caps the fused launch's grid (the probe's way to several tiles per wave).
+enum class FeatForm { Auto, Three, Fused };
+// mlp_feat.  out: caller-owned [clouds][n][64] or the arena.
+float* run_mlp_feat(dsir_ctx* c, const float* feat0, int clouds, int n, float* out = nullptr, FeatForm form = FeatForm::Auto, int max_blocks = 0);
+// both sides of a registration, feat0 = [2 P][n][64]: the first P clouds into out_a (caller-owned), the others into the arena
+// (returned) - one launch where the fused form runs, else side by side as run_mlp_feat does them
+float* run_mlp_feat_pair(dsir_ctx* c, const float* feat0, int P, int n, float* out_a, FeatForm form = FeatForm::Auto, int max_blocks = 0);
+int run_mlp_feat_probe(dsir_ctx* c, const float* feat0, int clouds, int n, int fused, int max_blocks, float* out);
 bool run_att_proj(dsir_ctx* c, const float* xyz, int64_t xyz_cs, const float* score, const float* F, int clouds, int n,
                   float* desc, const AggExtras* ex = nullptr);
 int build_pyramid(dsir_ctx* c, const float* points, int stride, int clouds, int n, float* xyz, int32_t* neigh,

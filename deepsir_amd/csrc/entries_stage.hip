@@ -57,6 +57,15 @@ int dsir_lfa_enc2_probe(dsir_ctx* c, int which, int level, int fused, int clouds
   return call.finish();
 }
 
+int dsir_mlp_feat_probe(dsir_ctx* c, const float* feat0, int clouds, int n, int fused, int max_workgroups, float* out) {
+  Call call(c, Call::kWeights); if (call.refused()) return 1;
+  if (c->cfg.pipeline == DSIR_PIPELINE_LABEL) return fail(c, "dsir_mlp_feat_probe: a label-pipeline context has no aggregation layers");
+  if (!feat0 || !out || clouds < 1 || n < 1 || fused < 0 || fused > 2 || (fused == 2 && (clouds & 1)) || max_workgroups < 0) return fail(c, "dsir_mlp_feat_probe: bad arguments");
+  if (check_batch(c, "dsir_mlp_feat_probe", clouds, n)) return 1;
+  if (int r = run_mlp_feat_probe(c, feat0, clouds, n, fused, max_workgroups, out)) return r;
+  return call.finish();
+}
+
 int dsir_ppf_pre(dsir_ctx* c, int which, const float* rows, int stride, const int32_t* neigh, int64_t neigh_cs, int clouds, int n,
                  float* out) {
   Call call(c, Call::kWeights); if (call.refused()) return 1;

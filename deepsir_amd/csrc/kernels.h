@@ -296,6 +296,25 @@ struct AggArgs {
 // split: the five wide layers as three fp16 MFMAs per product (split_f16.h; fp32 accuracy, 3/16 of the fp32 MFMA time), else exact
 // fp32; false => split weights missing (nothing launched)
 bool launch_agg_chain(const AggArgs& a, bool split, hipStream_t st);
+
+// feat_chain.hip — mlp_feat (64 -> 64 -> 128 -> 64; model.py:218) in one launch, each element the chain of operations the three
+// launches of launch_pw_gemm give it
+struct FeatChainArgs {
+  const float* X = nullptr;                         // [clouds][n][64]
+  const float *W1 = nullptr, *b1 = nullptr;         // mlp_feat.0, BN folded: [64][64]
+  const float *W2 = nullptr, *b2 = nullptr;         // mlp_feat.3, BN folded: [128][64]
+  const float *W3 = nullptr, *b3 = nullptr;         // mlp_feat.6: [64][128]
+  const void *W3h = nullptr, *W3l = nullptr;        // the fp16 split of W3 (same layout) where the last layer runs split, else nullptr
+  float* out0 = nullptr;                            // [split_cloud][n][64]: clouds [0, split_cloud)
+  float* out1 = nullptr;                            // [clouds - split_cloud][n][64]: the others (both sides of a registration at once)
+  int split_cloud = 0;
+  int n = 0, clouds = 0;
+  int max_blocks = 0;                               // > 0: at most this many workgroups (dsir_mlp_feat_probe: a wave walks several tiles at any size)
+};
+// false => a configuration whose three launches run another arithmetic (dispatch switches, unaligned operands): nothing launched
+bool launch_feat_chain(const FeatChainArgs& a, hipStream_t st);
+// workgroups' worth of work in such a launch (8 waves, one 16-row tile each); the grid itself stops at one workgroup per CU
+long long feat_chain_blocks(int clouds, int n);
 // weights.hip, host: x -> fp16(x), fp16(x - fp16(x)), the operand split of split_f16.h
 void split_weights_f16(const float* w, size_t n, uint16_t* hi, uint16_t* lo);
 

@@ -185,9 +185,16 @@ static int register_enqueue(dsir_ctx* c, Call& call, const dsir_pair_batch* in, 
   if (ws.overflow) return overflow_fail(c, "workspace exhausted (raise max_points / max_pairs)");
   const size_t mark1 = ws.mark();
   {
-    run_mlp_feat(c, feat_s, P, J, F_s);       // straight into the storage that outlives the iterations
+    // mlp_feat of both sides: F_s straight into the storage that outlives the iterations, F_r into the arena.  Clouds of one size
+    // whose features lie one after the other (the extractor ran on 2 P clouds) are one launch where the fused form runs.
+    float* F_r;
+    if (J == K && feat_r == feat_s + (size_t)P * J * 64) {
+      F_r = run_mlp_feat_pair(c, feat_s, P, J, F_s);
+    } else {
+      run_mlp_feat(c, feat_s, P, J, F_s);
+      F_r = run_mlp_feat(c, feat_r, P, K);
+    }
     launch_copy_xyz(pxyz, (int64_t)ps.S * 3, 3, J, P, xyz_cur, (int64_t)J * 3, st);      // xyz_cur = level-0 src coordinates
-    float* F_r = run_mlp_feat(c, feat_r, P, K);
     const bool ref_prepared = run_att_proj(c, rxyz, (int64_t)pr.S * 3, score_r, F_r, P, K, desc_r, search.ref_extras());
     if (out->desc_ref) HIP_OK(c, hipMemcpyAsync(out->desc_ref, desc_r, sizeof(float) * P * K * 64, hipMemcpyDeviceToDevice, st));
     if (int r = search.prepare_ref(desc_r, ref_prepared, rxyz, (int64_t)pr.S * 3)) return r;

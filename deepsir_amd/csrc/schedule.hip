@@ -668,13 +668,78 @@ int randla_forward(dsir_ctx* c, const RandlaW& w, const Seg& in0, const Seg* in1
 }
 
 // mlp_feat (loop invariant part of Network.aggregation, model.py:218)
-float* run_mlp_feat(dsir_ctx* c, const float* feat0, int clouds, int n, float* out) {
+namespace {
+// Does a launch of this size take the fused form by default?  A/B switch: DSIR_NO_FEAT_CHAIN = three point-wise launches throughout.
+// The fused launch is taken from 64 workgroups of work up (feat_chain_blocks: 512 row tiles, 8192 points).  Timed at and above that
+// size only: one captured pair of 5000 points (79 workgroups) registers in 2.919 ms against 2.954, 128 pairs in 0.40 of the three
+// launches' time.  Smaller launches keep the three launches - untimed there, and the captured small registrations keep the launch
+// census that tests/test_gpu_search_sites.py pins.  DSIR_FEAT_CHAIN_MIN_BLOCKS: tuning hook (0 = every size).
+bool feat_chain_wanted(int clouds, int n) {
+  static const bool off = tuning_flag("DSIR_NO_FEAT_CHAIN");
+  static const long long min_blocks = tuning_int("DSIR_FEAT_CHAIN_MIN_BLOCKS", 64);
+  return !off && feat_chain_blocks(clouds, n) >= min_blocks;
+}
+// the three layers in one launch (feat_chain.hip): clouds [0, split_cloud) into out0, the others into out1.  False: not launched -
+// other layer shapes, or a configuration whose three launches run an arithmetic the kernel does not reproduce
+bool mlp_feat_chain(dsir_ctx* c, const float* feat0, int clouds, int n, float* out0, float* out1, int split_cloud, int max_blocks) {
+  const LinW* m = c->net.mlp_feat;
+  if (m[0].cin != 64 || m[0].cout != 64 || m[1].cin != 64 || m[1].cout != 128 || m[2].cin != 128 || m[2].cout != 64) return false;
+  FeatChainArgs a;
+  a.X = feat0;
+  a.W1 = m[0].W; a.b1 = m[0].b; a.W2 = m[1].W; a.b2 = m[1].b; a.W3 = m[2].W; a.b3 = m[2].b;
+  GemmArgs last;                  // the last layer runs split exactly where Sched::linear would hand pw_tile.hip split weights
+  last.W = m[2].W;
+  Sched{c, c->stream, clouds}.split_of(last);
+  a.W3h = last.Wh; a.W3l = last.Wl;
+  a.out0 = out0; a.out1 = out1; a.split_cloud = split_cloud; a.n = n; a.clouds = clouds; a.max_blocks = max_blocks;
+  return launch_feat_chain(a, c->stream);
+}
+bool takes_fused(FeatForm form, int clouds, int n) { return form == FeatForm::Fused || (form == FeatForm::Auto && feat_chain_wanted(clouds, n)); }
+}  // namespace
+
+float* run_mlp_feat(dsir_ctx* c, const float* feat0, int clouds, int n, float* out, FeatForm form, int max_blocks) {
   Sched s{c, c->stream, clouds};
   const NetW& w = c->net;
+  if (takes_fused(form, clouds, n)) {
+    float* y = out ? out : c->ws.get<float>((size_t)clouds * n * 64);
+    if (c->ws.overflow) return y;                  // an exhausted arena hands out its base: nothing may run on it
+    if (mlp_feat_chain(c, feat0, clouds, n, y, nullptr, clouds, max_blocks)) return y;
+    if (form == FeatForm::Fused) return nullptr;
+    out = y;
+  }
   Act h = s.linear(w.mlp_feat[0], plain_seg(feat0, (int64_t)n * 64, 64, 64), nullptr, n, EPI_ACT);
   h = s.linear(w.mlp_feat[1], Sched::seg_of(h), nullptr, n, EPI_ACT);
   h = s.linear(w.mlp_feat[2], Sched::seg_of(h), nullptr, n, EPI_LINEAR, out);
   return h.p;
+}
+float* run_mlp_feat_pair(dsir_ctx* c, const float* feat0, int P, int n, float* out_a, FeatForm form, int max_blocks) {
+  float* out_b = c->ws.get<float>((size_t)P * n * 64);
+  if (c->ws.overflow) return out_b;
+  if (takes_fused(form, 2 * P, n) && mlp_feat_chain(c, feat0, 2 * P, n, out_a, out_b, P, max_blocks)) return out_b;
+  if (form == FeatForm::Fused) return nullptr;
+  run_mlp_feat(c, feat0, P, n, out_a, FeatForm::Three);
+  run_mlp_feat(c, feat0 + (size_t)P * n * 64, P, n, out_b, FeatForm::Three);
+  return out_b;
+}
+// dsir_mlp_feat_probe: mlp_feat alone, by the three launches (fused = 0), the fused launch (1), or the fused launch on both halves
+// of the clouds at once with two output bases (2: the second half through the arena, as a registration's ref side); max_blocks > 0
+// caps the fused launch's grid
+int run_mlp_feat_probe(dsir_ctx* c, const float* feat0, int clouds, int n, int fused, int max_blocks, float* out) {
+  if (fused == 2) {
+    const int P = clouds / 2;
+    const float* half = run_mlp_feat_pair(c, feat0, P, n, out, FeatForm::Fused, max_blocks);
+    if (c->ws.overflow) return overflow_fail(c, "workspace exhausted in mlp_feat_probe");
+    if (!half) return fail(c, "mlp_feat_probe: the fused launch does not take this configuration");
+    HIP_OK(c, hipMemcpyAsync(out + (size_t)P * n * 64, half, sizeof(float) * P * n * 64, hipMemcpyDeviceToDevice, c->stream));
+    return 0;
+  }
+  const float* y = run_mlp_feat(c, feat0, clouds, n, out, fused ? FeatForm::Fused : FeatForm::Three, max_blocks);
+  if (c->ws.overflow) {
+    if (c->call.sched_error) return fail(c, "mlp_feat_probe: %s", c->call.sched_error);
+    return overflow_fail(c, "workspace exhausted in mlp_feat_probe");
+  }
+  if (!y) return fail(c, "mlp_feat_probe: the fused launch does not take this configuration");
+  return 0;
 }
 // normalize(mlp_proj(F + mlp_att([xyz; score])))   (model.py:223-234)
 // ex: what the descriptor search wants written besides the descriptors (AggExtras); true: the epilogue wrote it

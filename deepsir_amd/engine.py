@@ -248,6 +248,19 @@ class Engine:
         self.sync()
         return rows, stats
 
+    def mlp_feat_probe(self, feat0, fused: int, max_workgroups: int = 0):
+        """Debug entry (include/dsir.h, dsir_mlp_feat_probe): mlp_feat alone, feat0 [c,n,64] -> [c,n,64], by the three point-wise
+        launches (fused=0), the one fused launch (1), or the fused launch on both halves of the clouds with two output bases (2);
+        max_workgroups > 0 caps the fused launch's grid (a wave then walks several row tiles)."""
+        feat0 = _chk(feat0, torch.float32, "feat0")
+        c, n, ch = feat0.shape
+        assert ch == 64
+        out = self._empty((c, n, 64))
+        self._pre()
+        self._call(self.lib.dsir_mlp_feat_probe(self.h, _ptr(feat0), c, n, int(fused), int(max_workgroups), _ptr(out)))
+        self.sync()
+        return out
+
     def ppf_pre(self, which: str, rows, neigh_multi):
         """The use_ppf front end of RandLA.forward (RandLANet.py:324-332; csrc/ppf.hip): rows [c,n,>=6] = xyz + normal,
         neigh_multi the pyramid's neigh_idx [c,S,16] (its level-0 rows are read) -> [c,n,12], the input of level 0."""

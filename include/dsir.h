@@ -131,6 +131,13 @@ int dsir_randla_forward(dsir_ctx* ctx, int which, const float* features, int cin
 int dsir_lfa_enc2_probe(dsir_ctx* ctx, int which, int level, int fused, int clouds, int n, const float* xyz_multi,
                         const int32_t* neigh_idx, float* rows, double* stats);
 
+/* Debug entry: mlp_feat of Network.aggregation (model.py:218) alone, feat0 [clouds][n][64] -> out [clouds][n][64], by either of
+ * its forms: fused = 0 the three point-wise launches, fused = 1 the one launch of csrc/feat_chain.hip, fused = 2 that launch on
+ * both halves of the clouds at once with two output bases, as a registration runs its src and ref sides (clouds even).  An
+ * error where the fused launch does not take the configuration.  max_workgroups > 0 caps the fused launch's grid, so that a wave
+ * walks several row tiles at sizes a test can afford (0: the launch's own grid).  The forms must agree in every bit. */
+int dsir_mlp_feat_probe(dsir_ctx* ctx, const float* feat0, int clouds, int n, int fused, int max_workgroups, float* out);
+
 /* Under DSIR_FLAG_PPF dsir_randla_forward takes rows of cin >= 6 columns (xyz, normal) for either network (the reference's
  * inlier model is handed [moved src xyz ; matched ref xyz] there, model.py:574-577: its "normals" are the matched points),
  * and dsir_forward_pair / dsir_register read points_src / points_ref as rows of feat_len columns with the normal in 3 .. 5.
