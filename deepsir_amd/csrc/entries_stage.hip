@@ -1,8 +1,9 @@
 // The stage entries of include/dsir.h: index narrowing, the KNN pyramid, one RandLA pass and the use_ppf front end, normals,
-// FPFH, ISS keypoints, score, aggregation, and the preprocessing (voxel down-sampling, resampling).
+// FPFH, ISS keypoints, farthest-point sampling, score, aggregation, and the preprocessing (voxel down-sampling, resampling).
 #include <cmath>
 
 #include "engine_ctx.h"
+#include "fps.h"
 
 using namespace dsir;
 
@@ -137,6 +138,26 @@ int dsir_iss_keypoints(dsir_ctx* c, const float* points, int stride, const int32
   a.gamma_21 = gamma_21; a.gamma_32 = gamma_32; a.min_neighbors = min_neighbors;
   a.saliency = saliency; a.mask = mask; a.index = index; a.counts = counts; a.n = n; a.clouds = clouds;
   if (!launch_iss_keypoints(a, c->stream)) return fail(c, "dsir_iss_keypoints: shape refused");
+  return call.finish();
+}
+
+int dsir_farthest_point_sample(dsir_ctx* c, const float* points, int stride, const int32_t* counts, int clouds, int cap, int k, int start,
+                               int32_t* index, int32_t* counts_out, float* min_d2) {
+  Call call(c); if (call.refused()) return 1;
+  if (!points || !index || !counts_out || !min_d2)
+    return fail(c, "dsir_farthest_point_sample: a null pointer among points and the three outputs");
+  if (clouds < 1 || clouds > 65535 || cap < 1 || stride < 3)
+    return fail(c, "dsir_farthest_point_sample: clouds in [1, 65535], cap >= 1 and stride >= 3 expected, got clouds=%d cap=%d stride=%d", clouds, cap, stride);
+  if (k < 1 || k > cap) return fail(c, "dsir_farthest_point_sample: k in [1, cap] expected, got k=%d cap=%d", k, cap);
+  if (start < 0) return fail(c, "dsir_farthest_point_sample: start >= 0 expected, got %d", start);
+  if (cap > kFpsMaxRows) return fail(c, "dsir_farthest_point_sample: cap=%d beyond the limit of %d rows per cloud (one workgroup per cloud)", cap, kFpsMaxRows);
+  FpsArgs a;
+  a.scratch = c->ws.raw(fps_scratch_bytes(clouds, cap));
+  if (c->ws.overflow) return fail(c, "workspace too small for dsir_farthest_point_sample (raise max_points / max_pairs)");
+  a.pts = points; a.pts_cs = (int64_t)cap * stride; a.pts_ld = stride; a.counts = counts;
+  a.clouds = clouds; a.cap = cap; a.k = k; a.start = start;
+  a.index = index; a.counts_out = counts_out; a.min_d2 = min_d2;
+  if (!launch_fps(a, c->stream)) return fail(c, "dsir_farthest_point_sample: shape refused");
   return call.finish();
 }
 

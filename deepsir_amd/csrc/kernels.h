@@ -250,6 +250,19 @@ struct IssArgs {
 size_t iss_scratch_bytes(int clouds, int n);
 bool launch_iss_keypoints(const IssArgs& a, hipStream_t st);          // false: outside the envelope (nothing launched)
 
+// fps.hip - farthest-point sampling, one workgroup per cloud, the k steps inside one launch (the rule: the file's header; the key,
+// the tiers and the scratch layout: fps.h).
+struct FpsArgs {
+  const float* pts = nullptr; int64_t pts_cs = 0; int pts_ld = 3;     // [clouds][cap][pts_ld], 3 columns used
+  const int32_t* counts = nullptr;                                    // [clouds] or nullptr: cloud c has pair_rows(counts, c, cap) rows
+  int clouds = 0, cap = 0, k = 0, start = 0;
+  void* scratch = nullptr;                                            // fps_scratch_bytes (the streaming tier's packed copy; else 0 bytes)
+  int32_t *index = nullptr, *counts_out = nullptr;                    // [clouds][k], [clouds]
+  float* min_d2 = nullptr;                                            // [clouds][k]
+};
+size_t fps_scratch_bytes(int clouds, int cap);
+bool launch_fps(const FpsArgs& a, hipStream_t st);                    // false: outside the envelope (nothing launched)
+
 // mlp_out + fc_label fused (head_mlp.hip): x[32] -> feat[64] -> 64 -> 32 -> ncls   (RandLANet.py:363-367)
 struct HeadArgs {
   Seg in = {};                  // last decoder block, [clouds][M][32], lazy GroupNorm + LeakyReLU

@@ -382,6 +382,36 @@ class Engine:
         self.sync()
         return index, counts, saliency, mask
 
+    FPS_MAX_ROWS = 65536             # csrc/fps.h kFpsMaxRows: one workgroup per cloud
+
+    def farthest_point_sample(self, points, k: int, counts=None, start: int = 0):
+        """Farthest-point sampling (include/dsir.h, dsir_farthest_point_sample; the rule: csrc/fps.hip, restated in deepsir_amd/fps.py):
+        points [c,cap,>=3], k rows per cloud, ``counts`` [c] (a device int32 tensor or a sequence; clouds of unequal sizes padded
+        to one shape, harness.pad_clouds; None: every row), ``start`` the first row chosen where it exists and is finite ->
+        (index [c,k] i32 in selection order, -1 beyond a cloud's count; counts_out [c] i32; min_d2 [c,k] f32: each chosen row's
+        squared distance to the rows chosen before it, +inf for the first, 0 beyond the count).  Exactly k rows of a cloud with k
+        finite rows and more, so what belongs to the rows (descriptors, normals, labels) rides along by a gather.  One workgroup
+        per cloud, one launch; same bytes for a cloud alone or in a batch.  Needs no weights.  Raises ValueError for arguments
+        refused on the host (shapes, k, start, counts, cap > 65536), EngineError where the library refuses."""
+        points = _chk(points, torch.float32, "points")
+        if points.dim() != 3 or points.shape[2] < 3 or points.shape[0] < 1 or points.shape[1] < 1:
+            raise ValueError("farthest_point_sample: points [clouds >= 1, cap >= 1, C >= 3] expected")
+        c, cap, stride = points.shape
+        if cap > self.FPS_MAX_ROWS:
+            raise ValueError(f"farthest_point_sample: {cap} rows per cloud beyond the limit of {self.FPS_MAX_ROWS}")
+        if int(k) != k or k < 1 or k > cap:
+            raise ValueError(f"farthest_point_sample: k must be an integer in [1, {cap}] (the rows of the array), got {k}")
+        if int(start) != start or start < 0 or start > 0x7fffffff:
+            raise ValueError(f"farthest_point_sample: start must be a non-negative int32, got {start}")
+        cn = self._counts(pair_counts(counts, c, cap, "counts"))
+        index, min_d2 = self._empty((c, int(k)), torch.int32), self._empty((c, int(k)))
+        counts_out = self._empty((c,), torch.int32)
+        self._pre()
+        self._call(self.lib.dsir_farthest_point_sample(self.h, _ptr(points), stride, _ptr(cn), c, cap, int(k), int(start), _ptr(index),
+                                                       _ptr(counts_out), _ptr(min_d2)))
+        self.sync()
+        return index, counts_out, min_d2
+
     def score(self, feat, logits, xyz_multi, neigh_multi):
         """torch.max(logits) + score_fun counterpart -> (score [c,n], label [c,n] i32)."""
         feat, logits = _chk(feat, torch.float32, "feat"), _chk(logits, torch.float32, "logits")

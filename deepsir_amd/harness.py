@@ -416,6 +416,24 @@ def _fpfh_side(engine, pts, viewpoints, radius, search="brute", max_nn=0, normal
     return desc, flags, normals
 
 
+def _register_one_pair(engine, xs, xr, ds, dr, j, sel, pose, max_dist, match_kw, pose_kw):
+    """Pair j of a batch matched and solved alone (a batch of ONE pair) on the rows ``sel`` = (idx_src, idx_ref), int32 device
+    tensors of original point indices, or None for all rows -> (T [1, 3, 4], corr [count, 2] int32 numpy in ORIGINAL point indices,
+    (idx_src, idx_ref) as numpy)."""
+    if sel is None:
+        sel = [torch.arange(x.shape[1], dtype=torch.int32, device=x.device) for x in (xs, xr)]
+        px, pr, qs, qr = xs[j:j + 1].contiguous(), xr[j:j + 1].contiguous(), ds[j:j + 1].contiguous(), dr[j:j + 1].contiguous()
+    else:
+        rows_s, rows_r = sel[0].long(), sel[1].long()
+        px, pr = xs[j, rows_s][None].contiguous(), xr[j, rows_r][None].contiguous()
+        qs, qr = ds[j, rows_s][None].contiguous(), dr[j, rows_r][None].contiguous()
+    corr, counts = engine.feature_correspondences(qs, qr, **match_kw)
+    T = _pose_from_corr(engine, pose, px, pr, corr, counts, max_dist, **pose_kw)
+    cc = corr[0, :int(counts[0])].long()
+    orig = torch.stack([sel[0][cc[:, 0]], sel[1][cc[:, 1]]], 1).to(torch.int32).cpu().numpy().reshape(-1, 2)
+    return T, orig, (sel[0].cpu().numpy(), sel[1].cpu().numpy())
+
+
 def _register_on_keypoints(engine, xs, xr, ds, dr, iss_kw, min_keypoints, pose, max_dist, match_kw, pose_kw):
     """The matching and pose stages of ``register_fpfh(keypoints="iss")`` for one batch: xs / xr [B, N, C] points, ds / dr [B, N, 64]
     descriptors of every point.  One ``iss_keypoints`` call per side, then per pair the gather of the keypoint rows (all rows where
@@ -429,19 +447,48 @@ def _register_on_keypoints(engine, xs, xr, ds, dr, iss_kw, min_keypoints, pose, 
     for j in range(xs.shape[0]):
         ks, kr = int(sides[0][1][j]), int(sides[1][1][j])
         fell_back = ks < min_keypoints or kr < min_keypoints
-        if fell_back:
-            sel = [torch.arange(x.shape[1], dtype=torch.int32, device=x.device) for x in (xs, xr)]
-            px, pr, qs, qr = xs[j:j + 1].contiguous(), xr[j:j + 1].contiguous(), ds[j:j + 1].contiguous(), dr[j:j + 1].contiguous()
-        else:
-            sel = [sides[0][0][j, :ks], sides[1][0][j, :kr]]
-            rows_s, rows_r = sel[0].long(), sel[1].long()
-            px, pr = xs[j, rows_s][None].contiguous(), xr[j, rows_r][None].contiguous()
-            qs, qr = ds[j, rows_s][None].contiguous(), dr[j, rows_r][None].contiguous()
+        sel = None if fell_back else [sides[0][0][j, :ks], sides[1][0][j, :kr]]
+        T, corr, idx = _register_one_pair(engine, xs, xr, ds, dr, j, sel, pose, max_dist, match_kw, pose_kw)
+        Ts.append(T)
+        corrs.append(corr)
+        kpts.append(idx + (bool(fell_back),))
+    return torch.cat(Ts, 0), corrs, kpts
+
+
+def _register_on_fps(engine, xs, xr, ds, dr, num_keypoints, min_keypoints, pose, max_dist, match_kw, pose_kw):
+    """The matching and pose stages of ``register_fpfh(keypoints="fps")`` for one batch (arguments and result as
+    ``_register_on_keypoints``).  One ``farthest_point_sample`` call per side on the whole batch; the pairs that got exactly
+    ``num_keypoints`` rows on both sides are gathered to [F, num_keypoints, .] and go through ONE ``feature_correspondences`` call and
+    ONE pose call.  A pair with fewer than ``min_keypoints`` sampled rows on a side, or of clouds smaller than ``num_keypoints``,
+    falls back to all of its points; a pair in between (non-finite rows left fewer than ``num_keypoints`` candidates) keeps its
+    shorter lists.  Both go through the one-pair path."""
+    B, k = xs.shape[0], int(num_keypoints)
+    if min(xs.shape[1], xr.shape[1]) < k:
+        index, cs, cr = None, np.zeros(B, np.int64), np.zeros(B, np.int64)            # every pair of this batch falls back
+    else:
+        sides = [engine.farthest_point_sample(x, k) for x in (xs, xr)]
+        index, cs, cr = (sides[0][0], sides[1][0]), sides[0][1].cpu().numpy(), sides[1][1].cpu().numpy()
+    fell_back = (cs < min_keypoints) | (cr < min_keypoints)
+    full = [j for j in range(B) if not fell_back[j] and cs[j] == k and cr[j] == k]
+    Ts, corrs, kpts = [None] * B, [None] * B, [None] * B
+    if full:
+        at = torch.tensor(full, dtype=torch.long, device=xs.device)
+        rows_s, rows_r = index[0][at].long(), index[1][at].long()
+        pick = torch.arange(len(full), device=xs.device)[:, None]
+        px, pr = xs[at][pick, rows_s].contiguous(), xr[at][pick, rows_r].contiguous()
+        qs, qr = ds[at][pick, rows_s].contiguous(), dr[at][pick, rows_r].contiguous()
         corr, counts = engine.feature_correspondences(qs, qr, **match_kw)
-        Ts.append(_pose_from_corr(engine, pose, px, pr, corr, counts, max_dist, **pose_kw))
-        cc = corr[0, :int(counts[0])].long()
-        corrs.append(torch.stack([sel[0][cc[:, 0]], sel[1][cc[:, 1]]], 1).to(torch.int32).cpu().numpy().reshape(-1, 2))
-        kpts.append((sel[0].cpu().numpy(), sel[1].cpu().numpy(), bool(fell_back)))
+        T = _pose_from_corr(engine, pose, px, pr, corr, counts, max_dist, **pose_kw)
+        orig = torch.stack([torch.gather(rows_s, 1, corr[:, :, 0].long().clamp_(0, k - 1)),
+                            torch.gather(rows_r, 1, corr[:, :, 1].long().clamp_(0, k - 1))], 2).to(torch.int32).cpu().numpy()
+        cn, idx_s, idx_r = counts.cpu().numpy(), index[0][at].cpu().numpy(), index[1][at].cpu().numpy()
+        for f, j in enumerate(full):
+            Ts[j], corrs[j], kpts[j] = T[f:f + 1], orig[f, :cn[f]].reshape(-1, 2), (idx_s[f], idx_r[f], False)
+    for j in range(B):
+        if Ts[j] is None:
+            sel = None if fell_back[j] else [index[0][j, :int(cs[j])], index[1][j, :int(cr[j])]]
+            Ts[j], corrs[j], idx = _register_one_pair(engine, xs, xr, ds, dr, j, sel, pose, max_dist, match_kw, pose_kw)
+            kpts[j] = idx + (bool(fell_back[j]),)
     return torch.cat(Ts, 0), corrs, kpts
 
 
@@ -454,7 +501,7 @@ def register_fpfh(pairs: Sequence[Dict[str, np.ndarray]], engine, voxel_size: fl
                   normal_max_nn: int = 0, fgr_iterations: int = 64, tuple_scale: float = 0.95, max_tuples: int = 1000,
                   tuple_test: bool = True, keypoints: Optional[str] = None, salient_radius: Optional[float] = None,
                   non_max_radius: Optional[float] = None, gamma_21: float = 0.975, gamma_32: float = 0.975, min_neighbors: int = 5,
-                  min_keypoints: int = 32, want_keypoints: bool = False):
+                  min_keypoints: int = 32, want_keypoints: bool = False, num_keypoints: int = 1024):
     """The weight-independent baseline of ``register_feat``: FPFH + feature-matching RANSAC (open3d compute_fpfh_feature ->
     registration_ransac_based_on_feature_matching; parity unpinned, the rules are the engine's own), all on the device.  Per batch
     and side: ``knn_pyramid`` -> ``estimate_normals`` on its level-0 lists (towards the pair's optional ``viewpoint_src`` /
@@ -481,6 +528,13 @@ def register_fpfh(pairs: Sequence[Dict[str, np.ndarray]], engine, voxel_size: fl
     with fewer than ``min_keypoints`` keypoints on either side uses all of its points (the same one-pair calls).  ``corr`` under
     ``want_corr`` holds original point indices.  ``want_keypoints`` appends one more value: per pair (idx_src, idx_ref, fell_back),
     the original indices matched on (all points after a fall-back; with ``keypoints=None`` every pair is (all, all, False)).
+    ``keypoints="fps"``: match and solve on ``num_keypoints`` farthest-point samples per cloud (``Engine.farthest_point_sample``,
+    csrc/fps.hip; no radius, no index, no normals, and the same count for every cloud).  Descriptors are still computed on every
+    point; the sampled rows of the whole batch are gathered to [B, num_keypoints, .] and ``feature_correspondences`` and the pose
+    stage run ONCE per batch on them (under ``pose="ransac"`` / ``"fgr"`` a pair's draws are keyed by its position in that call, as on
+    the ``keypoints=None`` path).  A pair whose clouds hold fewer than ``num_keypoints`` points, or with fewer than ``min_keypoints``
+    sampled rows on a side, uses all of its points through the one-pair calls; ``corr`` and ``want_keypoints`` as above, the
+    indices in selection order.
     ``keypoints=None`` (the default) is the path above, unchanged.
 
     ``engine`` is a ``deepsir_amd.engine.Engine`` THE CALLER PREPARED: the descriptor itself needs no weights, but the pyramid and
@@ -497,10 +551,12 @@ def register_fpfh(pairs: Sequence[Dict[str, np.ndarray]], engine, voxel_size: fl
         raise ValueError("register_fpfh: max_nn needs radius and search='grid' (the brute-force lists have no cap)")
     if normal_max_nn > 0 and normal_radius is None:
         raise ValueError("register_fpfh: normal_max_nn needs normal_radius")
-    if keypoints not in (None, "iss"):
-        raise ValueError(f"register_fpfh: keypoints must be None or 'iss', got {keypoints!r}")
+    if keypoints not in (None, "iss", "fps"):
+        raise ValueError(f"register_fpfh: keypoints must be None, 'iss' or 'fps', got {keypoints!r}")
     if min_keypoints < 1:
         raise ValueError("register_fpfh: min_keypoints >= 1 expected")
+    if keypoints == "fps" and (int(num_keypoints) != num_keypoints or num_keypoints < 1):
+        raise ValueError(f"register_fpfh: num_keypoints must be a positive integer, got {num_keypoints}")
     nbr = (search, int(max_nn), normal_radius, int(normal_max_nn))
     rte_t, rre_t = THRESHOLDS[dataset_type]
     preds, corrs, kpts, stats = [], [], [], np.zeros((len(pairs), 5))
@@ -525,8 +581,9 @@ def register_fpfh(pairs: Sequence[Dict[str, np.ndarray]], engine, voxel_size: fl
             T = _pose_from_corr(engine, pose, xs, xr, corr, counts, 2.0 * voxel_size, **pose_kw)
             pair_corr = None
         else:
-            T, pair_corr, pair_kpts = _register_on_keypoints(engine, xs, xr, ds, dr, iss_kw, int(min_keypoints), pose, 2.0 * voxel_size,
-                                                             dict(mutual=mutual, k=match_k, ratio=match_ratio), pose_kw)
+            how = (_register_on_keypoints, iss_kw) if keypoints == "iss" else (_register_on_fps, int(num_keypoints))
+            T, pair_corr, pair_kpts = how[0](engine, xs, xr, ds, dr, how[1], int(min_keypoints), pose, 2.0 * voxel_size,
+                                             dict(mutual=mutual, k=match_k, ratio=match_ratio), pose_kw)
             kpts += pair_kpts
         torch.cuda.synchronize(device)
         dt = (time.time() - t0) / len(ids)

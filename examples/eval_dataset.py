@@ -9,7 +9,8 @@ Directory layouts are the reference's (dataloader/threeDMatch_loader.py, kitti_l
 Without --ckpt a seeded random state-dict is used (plumbing check only).  `--method fpfh` needs no checkpoint at all: the
 weight-independent baseline, FPFH descriptors + feature-matching RANSAC on the device (`harness.register_fpfh`; `--fpfh-radius R`
 takes the descriptors over radius lists instead of the pyramid's 16-NN lists; `--keypoints iss` matches and solves on ISS keypoints
-only, `--salient-radius` / `--non-max-radius` default to 6 and 4 voxel sizes)."""
+only, `--salient-radius` / `--non-max-radius` default to 6 and 4 voxel sizes; `--keypoints fps` on `--num-keypoints` farthest-point
+samples per cloud, one batched matching and pose call per batch)."""
 import argparse
 import os
 import sys
@@ -53,8 +54,10 @@ def main():
     ap.add_argument("--normal-radius", type=float, default=None,
                     help="with --method fpfh: normals from radius neighbourhoods over the cell index instead of the 16-NN lists")
     ap.add_argument("--normal-max-nn", type=int, default=0, help="with --normal-radius: the max_nn nearest of a neighbourhood (0 = all)")
-    ap.add_argument("--keypoints", choices=["none", "iss"], default="none",
-                    help="with --method fpfh: match and solve on ISS keypoints only (descriptors still come from every point)")
+    ap.add_argument("--keypoints", choices=["none", "iss", "fps"], default="none",
+                    help="with --method fpfh: match and solve on ISS keypoints, or on farthest-point samples, only (descriptors still come "
+                         "from every point)")
+    ap.add_argument("--num-keypoints", type=int, default=1024, help="with --keypoints fps: the samples per cloud")
     ap.add_argument("--salient-radius", type=float, default=None, help="with --keypoints iss: the covariance neighbourhood (default 6 x voxel size)")
     ap.add_argument("--non-max-radius", type=float, default=None, help="with --keypoints iss: the non-maximum-suppression radius (default 4 x voxel size)")
     ap.add_argument("--match-k", type=int, default=1,
@@ -90,7 +93,7 @@ def main():
                                     batch=a.batch, pose=a.pose, match_k=a.match_k, match_ratio=a.match_ratio, search=a.fpfh_search,
                                     max_nn=a.fpfh_max_nn, normal_radius=a.normal_radius, normal_max_nn=a.normal_max_nn,
                                     keypoints=None if a.keypoints == "none" else a.keypoints, salient_radius=a.salient_radius,
-                                    non_max_radius=a.non_max_radius)
+                                    non_max_radius=a.non_max_radius, num_keypoints=a.num_keypoints)
     elif feat:
         pred, stats = register_feat(pairs, model, voxel_size=voxel, hypotheses=a.hypotheses, dataset_type=a.dataset, batch=a.batch,
                                     pose=a.pose, match_k=a.match_k, match_ratio=a.match_ratio)

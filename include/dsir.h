@@ -199,6 +199,21 @@ int dsir_iss_keypoints(dsir_ctx* ctx, const float* points, int stride, const int
                        const int32_t* nms_offsets, const int32_t* nms_cols, int clouds, int n, double gamma_21, double gamma_32,
                        int min_neighbors, float* saliency, int32_t* mask, int32_t* index, int32_t* counts);
 
+/* Farthest-point sampling of a batch of clouds: what dataloader/data_base.py:328 (farthest_point_sampler) does on the host and
+ * network/tools.py:30 (farthest_point_sample) with a loop of torch ops, and open3d's farthest_point_down_sample (unpinned here: the
+ * rule is this engine's own, stated in csrc/fps.hip and restated in deepsir_amd/fps.py).  points [clouds][cap][stride] (xyz first);
+ * counts [clouds] on the device or NULL: cloud c has clamp(counts[c], 0, cap) rows (NULL: cap), rows at and past it are never read.
+ * s_0 = start if that row exists and is finite, else the lowest finite row; then, k - 1 times, every remaining candidate's
+ * dist = min(dist, d2 to the row chosen last) from +inf - fp32, d2 = (dx dx + dy dy) + dz dz - and the candidate of largest dist is
+ * chosen, ties to the lower index.  A row with a non-finite coordinate is never chosen, a chosen row never again; a cloud that runs
+ * out of candidates ends early.  -> index [clouds][k] i32 in selection order (-1 beyond the cloud's count), counts_out [clouds] i32,
+ * min_d2 [clouds][k] f32: the dist of each chosen row when it was chosen (+inf for s_0, 0 beyond the count), non-increasing.
+ * One workgroup per cloud, the k steps inside one launch.  Refused with a message, launching nothing: a null pointer (counts may be
+ * NULL), clouds outside [1, 65535], cap < 1, stride < 3, k < 1 or k > cap, start < 0, cap > 65536, a workspace too small.
+ * No atomics: same bytes on every run; clouds are independent, bit for bit.  Any context serves (no weights needed). */
+int dsir_farthest_point_sample(dsir_ctx* ctx, const float* points, int stride, const int32_t* counts, int clouds, int cap, int k, int start,
+                               int32_t* index, int32_t* counts_out, float* min_d2);
+
 /* Replaces torch.max(logits,1) + Network.feat_score/score_fun with num_sub<=0
  * (network/model.py:638-644, :668-757).
  * feat [clouds][n][64], logits [clouds][n][ncls], xyz [clouds][n][3],
