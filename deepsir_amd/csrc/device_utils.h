@@ -122,19 +122,23 @@ __device__ __forceinline__ float exp_neg(float x) {
 // ------------------------------------------------------------------ GroupNorm statistics across workgroups: DETERMINISTIC
 // The per-(cloud, group) sums of x and x^2 meet across workgroups in atomics whose result cannot depend on the arrival order:
 // every contribution v (a workgroup's partial sum, fp64) is split by a pure function into two INTEGER-VALUED doubles,
-//     L1 = rint(v 2^-24)          and          L0 = rint((v - L1 2^24) 2^16),        v = L1 2^24 + L0 2^-16 + r, |r| <= 2^-17,
-// which are added to two fp64 counters with the hardware's fp64 atomic add.  |L0| <= 2^39 and (for |v| < 2^64) |L1| < 2^40, so
+//     L1 = rint(v 2^-10)          and          L0 = rint((v - L1 2^10) 2^30),        v = L1 2^10 + L0 2^-30 + r, |r| <= 2^-31,
+// which are added to two fp64 counters with the hardware's fp64 atomic add.  |L0| <= 2^39 and (for |v| < 2^50) |L1| < 2^40, so
 // with at most 2^12 contributions per statistic every partial sum stays an integer below 2^53 - where IEEE addition is EXACT,
 // hence associative and commutative: the totals are the same bits under every order (an atomic add of the raw fp64 partial
 // sums, as up to round 3, rounds differently under different orders).  Integer counters do the same but gfx950 has no
 // conversion between fp64 and 64-bit integers; decoding them at the head of every consumer workgroup cost 2 % of the step,
-// this form costs a multiply-add.  Absolute error per contribution <= 2^-17; a layer's mean and variance carry at most
-// (workgroups x 2^-17) / elements <= 6e-9 - eps of GroupNorm is 1e-5.  A non-finite contribution makes L1 non-finite and the
+// this form costs a multiply-add.  Absolute error per contribution <= 2^-31; a layer's mean and variance carry at most
+// (workgroups x 2^-31) / elements <= 4e-13, which is 4e-8 of var + eps even where the variance vanishes against GroupNorm's eps of
+// 1e-5.  (The limbs were cut at 2^24 / 2^-16 once: 6e-9 absolute, up to 6e-4 of var + eps - a convolution whose weights are 2^-6
+// of He-normal size lost 3e-5 of its normalised output at the 16-point level, tests/test_gpu_split_magnitudes.py.)  A partial
+// sum of 2^50 or more (|x| ~ 3e5 over a workgroup's rows) still adds up correctly to fp64 rounding, but no longer exactly, so
+// not order-independently.  A non-finite contribution makes L1 non-finite and the
 // statistic NaN / Inf, as the plain sum did.  Slot layout per (cloud, group), kGnWords doubles: {L1, L0} sums of x, then of
 // x^2; zeroed by the host before the producing launch (one memset per registration).
 __device__ __forceinline__ double gn_stat_limb(double v, int limb) {
-  const double l1 = rint(v * 0x1p-24);
-  return limb ? rint(fma(-l1, 0x1p24, v) * 0x1p16) : l1;
+  const double l1 = rint(v * 0x1p-10);
+  return limb ? rint(fma(-l1, 0x1p10, v) * 0x1p30) : l1;
 }
 // A workgroup's contribution to the statistics of the column range [n0, n0 + ncols) it owns, from its per-column fp32 partial
 // sums part[col * 2 + {0: sum x, 1: sum x^2}] (LDS, complete and barrier-separated from this call).  Atomic INSTRUCTIONS are
@@ -186,9 +190,9 @@ __device__ __forceinline__ double gn_stat_get(const double* slot) {
 #ifdef DSIR_GN_STATS_COHERENT
   const double l1 = __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   const double l0 = __hip_atomic_load(slot + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  return fma(l1, 0x1p24, l0 * 0x1p-16);
+  return fma(l1, 0x1p10, l0 * 0x1p-30);
 #else
-  return fma(slot[0], 0x1p24, slot[1] * 0x1p-16);
+  return fma(slot[0], 0x1p10, slot[1] * 0x1p-30);
 #endif
 }
 

@@ -101,7 +101,15 @@ struct dsir_ctx {
   float* dweights = nullptr;
   uint16_t* dweights16 = nullptr;        // fp16 split of the WHOLE weight blob: high parts [0, n), low parts [n, 2 n), same offsets
   size_t nweights = 0;                   // floats in dweights
-  const void* agg_wh[5] = {}; const void* agg_wl[5] = {};
+  const void* agg_wh[5] = {}; const void* agg_wl[5] = {};   // unset when one of the five is outside the split's domain
+  // Matrices of the blob outside the split's domain (split_f16.h), as [first, end) offsets in load order: their layers run
+  // in exact fp32.  Empty for weights of ordinary magnitudes.
+  std::vector<std::pair<size_t, size_t>> split_off;
+  bool split_ok(size_t off) const {
+    for (const auto& r : split_off)
+      if (off >= r.first && off < r.second) return false;
+    return true;
+  }
   bool finalized = false;
   dsir::NetW net;
   dsir::Arena ws;

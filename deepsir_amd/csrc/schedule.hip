@@ -152,6 +152,7 @@ struct Sched {
   void split_of(GemmArgs& a) const {
     if (!c->agg_split || !c->dweights16 || a.W < c->dweights || a.W >= c->dweights + c->nweights) return;
     const size_t off = (size_t)(a.W - c->dweights);
+    if (!c->split_ok(off)) return;          // outside the split's domain (split_f16.h): the layer's exact-fp32 kernel
     a.Wh = c->dweights16 + off;
     a.Wl = c->dweights16 + c->nweights + off;
   }

@@ -9,7 +9,22 @@
 // the matrix core, whose accumulation error was measured at <= 12 fp32 roundings per 192 products,
 // tests/test_gpu_screen_bound.py).  Per dot product that is the error fp32 arithmetic itself makes in a 64..256-term sum
 // (K 2^-24 |a||b|), at 3/16 of the fp32 MFMA time.
-// Domain: |x| <= 65504 (fp16 range).  Larger values (or non-finite ones) make the result non-finite.
+// "fp32 accuracy" holds in one magnitude band only.  Per output the error is at most
+//       B(a, b) = sum_k (ra_k |b_k| + |a_k| rb_k + |al_k| |bl_k|) + (K / 16 + 1) 2^-24 sum_k |a_k b_k|,
+// and the floor 2^-25 of r is ABSOLUTE (the fp16 sub-normal spacing): below |x| ~ 2^-3 the low part is sub-normal and the
+// product's relative error grows like 1 / |x| (weights x 2^-10 at K = 256: 5e-5 of |a||b| against fp32's 1e-7;
+// tests/test_split_model_host.py).  |x| > 65504 (or a non-finite x) makes the result non-finite.
+// Domain, weights: a matrix is contracted split only if all its entries are within the fp16 range and its two parts carry it
+// to 2^-19 of its Frobenius norm (split_in_domain, weights.hip, decided at load).  Any other matrix runs in its layer's
+// exact-fp32 kernel; agg_chain.hip and head_mlp.hip take all their matrices split or none.  He-normal matrices and trained
+// ones of like size are inside; the same matrices times 2^-6 or 2^+20 are outside.  tests/test_gpu_split_magnitudes.py pins the result:
+// rescalings of a state dict that preserve its function keep every output within the oracle tolerances.
+// The one exception is att_pool.hip's score contraction, which has no fp32 twin: its scores feed a softmax, where the absolute
+// error counts, and that stays <= 2^-25 |f|_1 however small fc is; an fc entry above 65504 gives non-finite output.
+// Domain, activations (split in the kernels, as they are): the same floor.  Every split layer reads either GroupNorm / LeakyReLU
+// outputs of O(1) or caller-supplied rows (dsir_aggregate's feat0: pinned at 2^-12 .. 2^10 times N(0, 1)) whose product is added
+// to a bias of O(0.1), against which 2^-25 |w|_1 is nothing.  A chain whose INNER activations are tiny or beyond 65504 by a
+// BatchNorm gain has a matrix outside the weight domain next to them, and runs in fp32 for that reason.
 //
 // The order of the three products decides bits: every kernel that contracts split operands issues them through mma3.
 // Weights are split once at load (split_weights_f16, weights.hip: the same rule on the host).

@@ -96,13 +96,31 @@ namespace {
 // ------------------------------------------------------------------ weight upload
 struct Uploader {
   std::vector<float> blob;
+  std::vector<std::pair<size_t, size_t>> spans;      // [first, end) of every array, in upload order
   size_t put(const std::vector<float>& v) {
     size_t o = (blob.size() + 63) & ~(size_t)63;
     blob.resize(o + v.size());
     std::memcpy(blob.data() + o, v.data(), v.size() * sizeof(float));
+    spans.emplace_back(o, o + v.size());
     return o;
   }
 };
+
+// Is a matrix inside the domain of the fp16 split (split_f16.h)?  Every entry within the fp16 range, and the two parts
+// together carrying the matrix to 2^-19 of its Frobenius norm: sum (w - hi - lo)^2 <= 2^-38 sum w^2.  Entries whose low part
+// is sub-normal (|w| < 2^-3) lose up to 2^-25 each, whatever their size; He-normal matrices of 10..768 inputs sit at 2^-22,
+// the same matrix times 2^-6 at 2^-16.
+bool split_in_domain(const float* w, const uint16_t* hi, const uint16_t* lo, size_t n) {
+  double r2 = 0.0, f2 = 0.0;
+  for (size_t i = 0; i < n; ++i) {
+    if (!(std::fabs(w[i]) <= 65504.f)) return false;
+    _Float16 h, l;
+    std::memcpy(&h, hi + i, 2); std::memcpy(&l, lo + i, 2);
+    const double r = (double)w[i] - (double)(float)h - (double)(float)l;
+    r2 += r * r; f2 += (double)w[i] * (double)w[i];
+  }
+  return r2 <= 0x1p-38 * f2;
+}
 
 const HostParam& P(dsir_ctx* c, const std::string& name) { return c->params[c->index.at(name)]; }
 
@@ -339,13 +357,25 @@ int dsir_finalize_weights(dsir_ctx* c) {
     HIP_OK(c, hipMalloc((void**)&c->dweights16, h16.size() * sizeof(uint16_t)));
     HIP_OK(c, hipMemcpy(c->dweights16, h16.data(), h16.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
     c->nweights = total;
+    // layers whose matrix the split does not carry run in exact fp32: split_of (schedule.hip) consults this list, the chains
+    // that take all their matrices split or none (agg_chain.hip, head_mlp.hip) are decided here
+    c->split_off.clear();
+    for (const auto& s : u.spans)
+      if (!split_in_domain(u.blob.data() + s.first, h16.data() + s.first, h16.data() + total + s.first, s.second - s.first))
+        c->split_off.push_back(s);
     auto hi = [&](size_t off) -> const void* { return c->dweights16 + off; };
     auto lo = [&](size_t off) -> const void* { return c->dweights16 + total + off; };
     if (has_agg) {
       const LinOff* lay[5] = {&ma[1], &ma[2], &ma[3], &ma[4], &mp};
-      for (int k = 0; k < 5; ++k) { c->agg_wh[k] = hi(lay[k]->W); c->agg_wl[k] = lo(lay[k]->W); }
+      bool ok = true;
+      for (int k = 0; k < 5; ++k) ok = ok && c->split_ok(lay[k]->W);
+      for (int k = 0; k < 5 && ok; ++k) { c->agg_wh[k] = hi(lay[k]->W); c->agg_wl[k] = lo(lay[k]->W); }
     }
     auto head = [&](const RandlaOff& o, RandlaW& w) {
+      bool ok = c->split_ok(o.out_w);
+      for (int k = 0; k < 3; ++k) ok = ok && c->split_ok(o.fc[k].W);
+      for (int k = 0; k < 4; ++k) w.head_wh[k] = w.head_wl[k] = nullptr;
+      if (!ok) return;
       w.head_wh[0] = hi(o.out_w); w.head_wl[0] = lo(o.out_w);
       for (int k = 0; k < 3; ++k) { w.head_wh[k + 1] = hi(o.fc[k].W); w.head_wl[k + 1] = lo(o.fc[k].W); }
     };

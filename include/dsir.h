@@ -678,8 +678,16 @@ int dsir_match_timer2(dsir_ctx* ctx, int reset, double* op_ms, double* kernel_ms
 int dsir_enable_screen(dsir_ctx* ctx, int enable);
 /* A/B switch (measurement / test): 1 (default) = the five wide layers of the aggregation chain (mlp_att 32 -> 64 -> 128 -> 256 ->
  * 64, mlp_proj; network/model.py:223-233) run as fp16-split products on the fp16 matrix pipe (csrc/agg_chain.hip, csrc/split_f16.h: each fp32
- * operand = two fp16 numbers, three MFMAs per product, fp32 accumulation - fp32 accuracy, descriptors within ~1e-7 of the
- * fp32 kernel's); 0 = the exact-fp32 form of the same chain, bit-identical to the unfused layer-by-layer launches.
+ * operand = two fp16 numbers, three MFMAs per product, fp32 accumulation - descriptors within ~1e-7 of the fp32 kernel's for
+ * weights the split carries); 0 = the exact-fp32 form of the same chain, bit-identical to the unfused layer-by-layer launches.
+ * The split is as accurate as fp32 in one magnitude band only (csrc/split_f16.h): each part loses up to 2^-25 ABSOLUTE per
+ * element, so a matrix of small entries is carried badly and one with an entry above 65504 not at all.  dsir_finalize_weights
+ * therefore checks every matrix (all |w| <= 65504, and hi + lo within 2^-19 of the matrix in Frobenius norm); a layer whose matrix
+ * fails runs in exact fp32 even with the switch on, and the aggregation chain and the head do so as a whole if any of their
+ * matrices fails.  With that, state dicts rescaled by 2^-14 .. 2^+20 in ways that preserve the network's function keep
+ * descriptors, features and logits within the tolerances at which they are compared with the fp64 oracle
+ * (tests/test_gpu_split_magnitudes.py).  Inputs of dsir_aggregate for which the descriptor tolerance (rtol 1e-4, atol 2e-5)
+ * is pinned: feat0 of 2^-12 .. 2^10 times unit normal, scores down to U(0, 2^-8), coordinates up to +-50.
  * Initialised from DSIR_AGG_F32 (set => 0).
  * What the switch covers: the aggregation chain, the per-point head (csrc/head_mlp.hip) and the LDS-tiled GEMMs (csrc/pw_tile.hip,
  * through GemmArgs::Wh staying unset).  What it does NOT cover: the attentive-pooling score contraction, which is an fp16-split
@@ -688,7 +696,9 @@ int dsir_enable_screen(dsir_ctx* ctx, int enable);
 int dsir_enable_agg_split(dsir_ctx* ctx, int enable);
 /* The operand split those layers rest on, HOST buffers, no context, no GPU: hi[i] = fp16(x[i]) and lo[i] = fp16(x[i] - hi[i])
  * as IEEE binary16 bit patterns, both rounded to nearest even - what dsir_finalize_weights applies to every weight matrix (the
- * kernels apply the same rule to activations).  x = hi + lo + r with |r| <= max(2^-22 |x|, 2^-25) for |x| <= 65504. */
+ * kernels apply the same rule to activations).  x = hi + lo + r with |r| <= max(2^-22 |x|, 2^-25) for |x| <= 65504: the second
+ * term is an absolute floor (fp16 sub-normal spacing), so below |x| ~ 2^-3 the relative error of a split product grows like
+ * 1 / |x|, and above 65504 hi is infinite.  See dsir_enable_agg_split for which matrices are contracted this way. */
 void dsir_split_f16(const float* x, int64_t n, uint16_t* hi, uint16_t* lo);
 /* Same launches, bracketed on the DEVICE's constant-rate clock inside the kernel (first wave start .. last wave end,
  * the quantity a kernel trace reports): unlike the HIP-event bracket it does not include time the launch spends
