@@ -223,6 +223,13 @@ bool sort_pairs(void* tmp, size_t tmp_bytes, const uint64_t* kin, uint64_t* kout
 
 }  // namespace
 
+// the same per-pair sort for the other cell-indexed maps (ndt.hip): the SEG_MAX choice, the temporary size and the sort, as they are here
+size_t cell_sort_tmp_bytes(int pairs, int n) { return n > SEG_MAX ? dev_sort_tmp_bytes(n) : seg_sort_tmp_bytes((int64_t)pairs * n, pairs); }
+bool cell_sort_pairs(void* tmp, size_t tmp_bytes, const uint64_t* kin, uint64_t* kout, const uint32_t* vin, uint32_t* vout, int pairs, int n,
+                     const int32_t* off, hipStream_t st) {
+  return sort_pairs(tmp, tmp_bytes, kin, kout, vin, vout, pairs, n, off, st);
+}
+
 size_t icp_grid_scratch_bytes(int pairs, int J, int K) {
   if (!icp_grid_shape_ok(pairs, J, K)) return 0;
   return layout(pairs, J, K).bytes;

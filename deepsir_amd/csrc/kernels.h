@@ -631,6 +631,11 @@ int icp_grid_build(const float* ref, int stride, const float* cur, int pairs, in
                    float r, bool order, void* scratch, hipStream_t st, IcpGrid* out);
 void launch_icp_nn_grid(const IcpGrid& g, const float* cur, int pairs, int J, int K, const int32_t* counts_src, const int32_t* counts_ref, float r2,
                         int32_t* idx, float* d2, const int32_t* skip, hipStream_t st);
+// the index's stable per-pair sort of (key, original index), for the other per-pair cell maps (ndt.hip): keys / vals [pairs][n],
+// off [pairs + 1] = p n; tmp of cell_sort_tmp_bytes(pairs, n) bytes
+size_t cell_sort_tmp_bytes(int pairs, int n);
+bool cell_sort_pairs(void* tmp, size_t tmp_bytes, const uint64_t* kin, uint64_t* kout, const uint32_t* vin, uint32_t* vout, int pairs, int n,
+                     const int32_t* off, hipStream_t st);
 
 // pose_corr.hip, ransac.hip, consensus.hip, fgr.hip — pose from a correspondence list: one front, three middles, one tail; their
 // argument structs and launchers are declared in pose_corr.h.  Here the producer of such lists, the mutual-nearest-neighbour list of

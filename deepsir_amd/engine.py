@@ -791,6 +791,50 @@ class Engine:
         """pair_counts' array on the device (None stays None)"""
         return None if host is None else torch.from_numpy(host).to(self.device)
 
+    def ndt_refine(self, points_src, points_ref, T_init, resolution: float, neighbors: int = 7, max_iter: int = 30,
+                   step_tol: float = 1e-4, outlier_ratio: float = 0.55, counts_src=None, counts_ref=None):
+        """NDT registration for P pairs (include/dsir.h, dsir_ndt_refine; the rule: csrc/ndt.hip, restated in deepsir_amd/ndt.py):
+        the reference cloud as one Gaussian per occupied cell of edge ``resolution``, the source points pulled towards the Gaussians
+        of their own and (``neighbors=7``) face-adjacent cells - no nearest-neighbour search, no normals, a wider basin than ICP on
+        sparse scans.  points_* [P,N,>=3] CUDA fp32, T_init [P,3,4] -> (T [P,3,4], stats [P,5] fp32: mean likelihood, matched
+        fraction, converged, iterations, identity updates).  ``step_tol``: a pair stops when its update turns by less than that
+        (radians) and shifts by less than step_tol x resolution.  counts_src / counts_ref as for ``icp_refine``: pair p gets, byte
+        for byte, what the call on its own rows alone returns.  A bad argument is an EngineError and leaves the engine usable."""
+        P, J, stride = points_src.shape
+        K = points_ref.shape[1]
+        counts_src, counts_ref = pair_counts(counts_src, P, J, "counts_src"), pair_counts(counts_ref, P, K, "counts_ref")
+        points_src, points_ref = _chk(points_src, torch.float32, "points_src"), _chk(points_ref, torch.float32, "points_ref")
+        T_init = _chk(T_init, torch.float32, "T_init")
+        assert points_ref.shape[0] == P and points_ref.shape[2] == stride and tuple(T_init.shape) == (P, 3, 4)
+        T = self._empty((P, 3, 4))
+        stats = self._empty((P, 5))
+        cs, cr = self._counts(counts_src), self._counts(counts_ref)
+        self._pre()
+        self._call(self.lib.dsir_ndt_refine(self.h, _ptr(points_src), _ptr(points_ref), P, J, K, stride, _ptr(cs), _ptr(cr), _ptr(T_init),
+                                            float(resolution), int(neighbors), int(max_iter), float(step_tol), float(outlier_ratio),
+                                            _ptr(T), _ptr(stats)))
+        self.sync()
+        return T, stats
+
+    def ndt_map(self, points_ref, resolution: float, counts_ref=None):
+        """The map ``ndt_refine`` builds of points_ref [P,K,>=3] (include/dsir.h, dsir_ndt_map) -> (lattice [P,4] f64: origin and
+        cell edge; keys [P,K] int64: the sorted cell keys, -1 (all ones) for non-finite and padding rows; index [P,K] i32: the
+        original row of every sorted position; records [P,K,10] f64: mean, inverse covariance (00 01 02 11 12 22) and point count
+        at the first sorted position of every valid cell, zero elsewhere)."""
+        P, K, stride = points_ref.shape
+        counts_ref = pair_counts(counts_ref, P, K, "counts_ref")
+        points_ref = _chk(points_ref, torch.float32, "points_ref")
+        lattice = self._empty((P, 4), torch.float64)
+        keys = self._empty((P, K), torch.int64)
+        index = self._empty((P, K), torch.int32)
+        records = self._empty((P, K, 10), torch.float64)
+        cr = self._counts(counts_ref)
+        self._pre()
+        self._call(self.lib.dsir_ndt_map(self.h, _ptr(points_ref), P, K, stride, _ptr(cr), float(resolution), _ptr(lattice), _ptr(keys),
+                                         _ptr(index), _ptr(records)))
+        self.sync()
+        return lattice, keys, index, records
+
     def icp_correspondences(self, points_src, points_ref, T, max_corr_dist: float, search: str = "brute", counts_src=None, counts_ref=None):
         """open3d evaluate_registration counterpart for P pairs: one search step of icp_refine under the pose T.
         points_* [P,N,>=3] CUDA fp32, T [P,3,4] -> (idx [P,J] i32: the reference point of each source point moved by T, or -1;

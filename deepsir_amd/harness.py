@@ -27,7 +27,7 @@ def inference_align(pairs: Sequence[Dict[str, np.ndarray]], model, num_reg_iter:
                     batch: int = 1, device: Optional[torch.device] = None, dist=None, pose_opt: Optional[str] = None,
                     voxel_size: float = 0.3, in_flight: int = 1, safeguard_wsum: Optional[float] = None,
                     ransac_hypotheses: int = 80000, ransac_seed: int = 0, icp_search: str = "auto", icp_kernel: str = "l2",
-                    icp_kernel_scale: Optional[float] = None):
+                    icp_kernel_scale: Optional[float] = None, ndt_resolution: Optional[float] = None):
     """pairs: sequence of dicts with ``points_src/points_ref [1,N,C]``, ``transform_gt [1,3,4]`` and optionally the
     pyramid tensors and ``others`` (as the reference's collate, data_base.py:196-219).
     ``in_flight`` > 1: the reference's one-pair-per-call loop fed AHEAD - the pairs go one by one to a
@@ -36,6 +36,9 @@ def inference_align(pairs: Sequence[Dict[str, np.ndarray]], model, num_reg_iter:
     ``pose_opt='icp'`` / ``'icp_plane'``: ICP on the raw clouds from the last pose, point-to-point / point-to-plane;
     ``icp_search`` is ``Engine.icp_refine``'s ``search`` ("auto": the cell index on large clouds; the poses are the same bytes),
     ``icp_kernel`` / ``icp_kernel_scale`` its robust ``kernel`` and ``kernel_scale`` (open3d's ``robust_kernel``; "l2": none).
+    ``pose_opt='ndt'``: NDT registration on the raw clouds from the last pose (``Engine.ndt_refine``: no search, no normals);
+    ``ndt_resolution`` is its cell edge, by default 4 x ``voxel_size`` - a choice (a cell of a voxel grid then holds tens of
+    points), not a tuned value.
     ``pose_opt='ransac'``: DGR's safeguard (network/DGR.py:249-306) over the last iteration's correspondences, see below;
     ``pose_opt='consensus'``: the same correspondences through ``consensus_correspondence`` instead of the seeded sampling;
     ``pose_opt='fgr'``: through ``fgr_correspondence`` (fast global registration; ``ransac_seed`` keys its tuple draws);
@@ -100,6 +103,11 @@ def inference_align(pairs: Sequence[Dict[str, np.ndarray]], model, num_reg_iter:
                                                            transforms[-1].contiguous(), 2.0 * voxel_size, estimator="plane",
                                                            search=icp_search, kernel=icp_kernel, kernel_scale=icp_kernel_scale)
             transforms.append(T_opt)
+        elif pose_opt == "ndt":
+            # the correspondence-free refinement (csrc/ndt.hip): one Gaussian per cell of the reference cloud, cell edge 4 x voxel size
+            T_opt, _ = _aux_engine(model, data).ndt_refine(data["points_src"].float(), data["points_ref"].float(), transforms[-1].contiguous(),
+                                                           float(ndt_resolution) if ndt_resolution is not None else 4.0 * voxel_size)
+            transforms.append(T_opt)
         elif pose_opt == "tune":
             # pose_optimization with use_tune (test.py:218-239; off in the reference): Adam fine-tune of the 6-D-rotation
             # pose on the last iteration's correspondences, weights = sigmoid of its inlier logits, distances in units
@@ -126,7 +134,7 @@ def inference_align(pairs: Sequence[Dict[str, np.ndarray]], model, num_reg_iter:
         elif pose_opt is None:
             transforms.append(transforms[-1].detach())        # pose_optimization == identity (test.py:215-216, :406-408)
         else:
-            raise ValueError("pose_opt must be None, 'icp', 'icp_plane', 'tune', 'ransac', 'consensus' or 'fgr'")
+            raise ValueError("pose_opt must be None, 'icp', 'icp_plane', 'ndt', 'tune', 'ransac', 'consensus' or 'fgr'")
         T = torch.stack(transforms, dim=1).cpu().numpy()      # [B, n_iter+1, 3, 4]
         preds.append(T)
         gt = data["transform_gt"].cpu().numpy()
@@ -764,6 +772,46 @@ def icp_multiscale(src_clouds, ref_clouds, T_init, voxel_sizes, max_iters, radii
             Tb, st = engine.icp_refine(src, ref, T[b0:b0 + len(ids)].contiguous(), float(radius), max_iter=int(iters), estimator=estimator,
                                        normals_ref=nrm, search=search, counts_src=n_s, counts_ref=n_t, kernel=kernel, kernel_scale=kscale)
             T[b0:b0 + len(ids)] = Tb
+            st_scale.append(st)
+        stats.append(torch.cat(st_scale, 0))
+    return T, stats
+
+
+@torch.no_grad()
+def ndt_multiscale(src_clouds, ref_clouds, T_init, resolutions, max_iters, neighbors: int = 7, step_tol: float = 1e-4,
+                   outlier_ratio: float = 0.55, batch: Optional[int] = None, *, engine):
+    """NDT coarse to fine for lists of clouds of any sizes: every scale one ``Engine.ndt_refine`` on the clouds as given, from the
+    previous scale's pose.  src_clouds / ref_clouds: P clouds [n_i, >=3] each (numpy or tensors), T_init [P,3,4] with p_ref = T p_src;
+    resolutions, max_iters: one entry per scale, in the order they run (coarse first).  ``engine`` (keyword): the ``Engine`` that
+    runs it; ``batch``: pairs per engine call (default: all of them, at most the engine's max_pairs).  No kernel of its own:
+    ``pad_clouds`` with the counts and these engine calls, so the result is theirs byte for byte.
+    -> (T [P,3,4] float32 tensor of the last scale, stats: one [P,5] float32 tensor per scale)."""
+    S = len(resolutions)
+    if S < 1 or len(max_iters) != S:
+        raise ValueError("ndt_multiscale: resolutions and max_iters need one entry per scale, at least one")
+    dev = engine.device
+    as_dev = lambda c: (c if isinstance(c, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(c, np.float32))).to(dev).float().contiguous()
+    srcs, refs = [as_dev(c) for c in src_clouds], [as_dev(c) for c in ref_clouds]
+    P = len(srcs)
+    if P < 1 or len(refs) != P:
+        raise ValueError("ndt_multiscale: as many reference clouds as source clouds, at least one pair")
+    T = as_dev(np.asarray(T_init.detach().cpu() if isinstance(T_init, torch.Tensor) else T_init, np.float32)[:, :3]).clone()
+    if tuple(T.shape) != (P, 3, 4):
+        raise ValueError(f"ndt_multiscale: T_init must be [{P}, 3, 4]")
+    per = int(batch or min(P, engine.max_pairs))
+    if per < 1:
+        raise ValueError("ndt_multiscale: batch must be at least 1")
+    padded = []
+    for b0 in range(0, P, per):
+        ids = range(b0, min(P, b0 + per))
+        padded.append((b0, len(ids), pad_clouds([srcs[i] for i in ids]), pad_clouds([refs[i] for i in ids])))
+    stats = []
+    for res, iters in zip(resolutions, max_iters):
+        st_scale = []
+        for b0, n, (src, n_s), (ref, n_t) in padded:
+            Tb, st = engine.ndt_refine(src, ref, T[b0:b0 + n].contiguous(), float(res), neighbors=neighbors, max_iter=int(iters),
+                                       step_tol=step_tol, outlier_ratio=outlier_ratio, counts_src=n_s, counts_ref=n_t)
+            T[b0:b0 + n] = Tb
             st_scale.append(st)
         stats.append(torch.cat(st_scale, 0))
     return T, stats

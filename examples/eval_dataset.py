@@ -36,7 +36,9 @@ def main():
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--limit", type=int, default=0)
-    ap.add_argument("--pose-opt", choices=["none", "icp", "icp_plane", "tune", "ransac", "consensus", "fgr"], default="none")
+    ap.add_argument("--pose-opt", choices=["none", "icp", "icp_plane", "ndt", "tune", "ransac", "consensus", "fgr"], default="none")
+    ap.add_argument("--ndt-resolution", type=float, default=None,
+                    help="with --pose-opt ndt: the cell edge of the NDT map (default: 4 x the voxel size)")
     ap.add_argument("--icp-search", choices=["brute", "grid", "auto"], default="auto",
                     help="with --pose-opt icp / icp_plane: the nearest-neighbour search of the refinement (same poses, other time)")
     ap.add_argument("--pipeline", choices=["align", "feat"], default="align")
@@ -100,7 +102,7 @@ def main():
     else:
         pred, stats = inference_align(pairs, model, a.iters, a.dataset, batch=a.batch,
                                       pose_opt=None if a.pose_opt == "none" else a.pose_opt, voxel_size=voxel,
-                                      icp_search=a.icp_search)
+                                      icp_search=a.icp_search, ndt_resolution=a.ndt_resolution)
     print({k: round(float(v), 4) for k, v in summarize(stats).items()})
     _, summary = evaluate_align(pred, pairs, eng, a.dataset)
     print({k: round(float(v), 5) for k, v in summary.items()})

@@ -467,6 +467,40 @@ int dsir_icp_refine_ex4(dsir_ctx* ctx, const float* points_src, const float* poi
                         float* T_out, int estimator, const float* normals_ref, int search, double* stats,
                         const int32_t* counts_src, const int32_t* counts_ref, int kernel, float kernel_scale);
 
+/* NDT registration (the normal-distributions transform of PCL / Autoware / ndt_omp) for P pairs at once, entirely on device: the
+ * correspondence-free refinement beside the ICP entries, for sparse scans on which a nearest neighbour is a point of the same
+ * ring.  PCL is not pinned: the rule is this engine's own, stated in the header of csrc/ndt.hip and restated in numpy fp64 in
+ * deepsir_amd/ndt.py.  The reference cloud becomes one Gaussian per occupied cell of edge `resolution`; every moved source point
+ * is pulled towards the Gaussians of its own cell and, with neighbors = 7, of the six face-adjacent cells (neighbors = 1: the own
+ * cell alone).  The step is iteratively reweighted Gauss-Newton on PCL's score (constants d1..d3 from outlier_ratio and
+ * resolution), solved by the point-to-plane entry's 6 x 6 solve; no line search, monotone descent is not promised.
+ *   points_src [P][J][stride], points_ref [P][K][stride] fp32 rows (xyz first); counts_src / counts_ref [P] int32 device arrays or
+ *   NULL: the rows of each pair that hold points, clamped to [0, J] / [0, K], as for dsir_icp_refine_ex3 - rows beyond are never read;
+ *   T_init / T_out [P][3][4];  resolution > 0 and finite, in the cloud's length unit;  max_iter >= 0;
+ *   step_tol > 0 and finite: a pair is converged when the update's rotation vector is shorter than step_tol and its translation
+ *   shorter than step_tol x resolution, or after an identity update;  outlier_ratio inside (0, 1) (PCL's default 0.55);
+ *   stats [P][5] fp32 or NULL: mean likelihood score / Jp and matched fraction matched / Jp after the last move (0 for Jp == 0),
+ *   converged, iterations run, identity updates.
+ * The update is the identity (T and the moved points keep their bits; counted) when fewer than 6 visits contributed, the system is
+ * singular (icp_plane.h), a moved source point is not finite, or Jp == 0 or Kp == 0.  A non-finite reference row is in no cell; a
+ * cell of fewer than 6 points, or whose covariance has no positive finite largest eigenvalue, has no Gaussian.  max_iter = 0: T_out
+ * is T_init bit for bit.  Same bytes on every run (no floating-point atomics, fixed partition of the sums), and pair p gets, byte
+ * for byte, what the call on its first Jp and Kp rows alone writes, whatever else is in the batch.  Bad arguments - resolution or
+ * step_tol not positive and finite, outlier_ratio outside (0, 1), neighbors not 1 or 7, shapes beyond the context's workspace -
+ * return the usual error code and message before any launch.  Scratch comes from the context workspace (NdtLayout, csrc/ndt.h). */
+int dsir_ndt_refine(dsir_ctx* ctx, const float* points_src, const float* points_ref, int pairs, int J, int K, int stride,
+                    const int32_t* counts_src, const int32_t* counts_ref, const float* T_init, float resolution, int neighbors,
+                    int max_iter, float step_tol, float outlier_ratio, float* T_out, float* stats);
+/* The map dsir_ndt_refine builds of points_ref, for tests and for users who want it.  Device outputs:
+ *   lattice_out [P][4] f64: origin (the per-axis minimum of the pair's finite rows; 0 without one) and cell edge
+ *   h = max(resolution, longest extent / 2^20);   keys_out [P][K] u64: the pair's cell keys x | y << 21 | z << 42, ascending, ~0 for
+ *   non-finite and padding rows (last);   index_out [P][K] i32: the original row of every sorted position (the sort is stable);
+ *   records_out [P][K][10] f64: at the first sorted position of every valid cell (>= 6 points, positive finite largest eigenvalue)
+ *   its mean (3), inverse regularised covariance B (6: 00 01 02 11 12 22; eigenvalues floored at 0.01 of the largest) and point
+ *   count; zero everywhere else. */
+int dsir_ndt_map(dsir_ctx* ctx, const float* points_ref, int pairs, int K, int stride, const int32_t* counts_ref, float resolution,
+                 double* lattice_out, uint64_t* keys_out, int32_t* index_out, double* records_out);
+
 /* Replaces the `use_tune` branch of pose_optimization (test.py:209-239): transformation_finetune (test.py:159-207) with
  * HighDimSmoothL1Loss (test.py:103-131) over the network's last correspondences, the pose re-parametrised as
  * network/DGR.py's Transformation (6-D rotation + translation, :60-132) and fitted by Adam (lr 0.1, ExponentialLR 0.999)
