@@ -469,6 +469,10 @@ void launch_copy_xyz_levels(const float* pts, int64_t cloud_stride, int stride, 
                             int64_t xyz_cs, hipStream_t st);
 void launch_copy_sub_levels(const int32_t* neigh, int64_t neigh_cs, const PyramidLevels& lv, int clouds, int32_t* sub, int64_t sub_cs,
                             hipStream_t st);
+// sub as launch_copy_sub_levels writes it, and interp[off[l] + i] = the nearest of the first nl[l + 1] points of `pts` to point i of
+// level l, read off the finished lists `neigh` (knn.hip, interp_lists_kernel): what launch_nn1 / launch_nn1_grid give, bit for bit
+void launch_interp_lists(const float* pts, int64_t cloud_stride, int stride, const int32_t* neigh, int64_t neigh_cs, const PyramidLevels& lv,
+                         int clouds, int32_t* sub, int64_t sub_cs, int32_t* interp, int64_t interp_cs, hipStream_t st);
 void launch_copy_rows_i32(const int32_t* src, int64_t src_cloud_stride, int rows, int width, int clouds, int32_t* dst,
                           int64_t dst_cloud_stride, hipStream_t st);
 

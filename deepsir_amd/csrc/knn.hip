@@ -8,6 +8,10 @@
 // partial lists are merged through LDS by wave 0.  Tie rule = oracle/knn.py:
 // fp32 d = (dx*dx + dy*dy) + dz*dz without FMA contraction, ties to the lower
 // support index (scan order is ascending and every comparison is strict).
+//
+// interp_idx (the nearest point of level l + 1 for every point of level l) is not searched for: interp_lists_kernel reads it off the
+// finished 16-NN lists, and scans only for the ~1 % of the queries whose 16 neighbours all lie outside level l + 1 (rule and proof at
+// its head).  nn1_kernel (and knn_grid.hip's grid_nn1_kernel) are the searches it replaces, kept behind DSIR_NO_INTERP_LISTS.
 #include "kernels.h"
 #include "device_utils.h"
 
@@ -286,6 +290,86 @@ __global__ __launch_bounds__(256) void knn_small_levels_kernel(const float* __re
   else if constexpr (K16) knn16_body(P, stride, jb.n, jb.out + blockIdx.y * jb.ocs, bx, sm.k16);
 }
 
+// interp_idx of ALL levels from the finished 16-NN lists, and sub_idx on the way (sub_idx of level l = the lists of its first n_{l+1}
+// queries, which this kernel reads anyway: it takes the place of misc.hip's copy_sub_levels_kernel).
+//
+// The rule.  Level l + 1 is the first m = n_{l+1} points of level l.  interp_idx[q] = the minimum over the support indices j < m with
+// d(q, j) < inf of the total order (fp32 d, then lower j) - what nn1_body's ascending scan under strict `<` and grid_nn1_kernel's keys
+// give; 0 if there is none.  The 16-NN list of q holds, in ascending order, the 16 smallest j < n_l with d(q, j) < inf under the SAME
+// order with the same sqdist bits (Top16, the wave kernel's and knn_grid.hip's keys, oracle/knn.py).
+//   * A candidate that precedes a member of the 16 smallest is itself one of the 16 smallest.  So if some list entry is < m, the
+//     minimum a over j < m precedes or equals it, is in the list, and - the list being sorted - is the FIRST entry < m in list order.
+//   * No entry < m: the list says nothing; the wave SCANS the m support points for that query (below), nn1_body's search itself.
+//   * A list with fewer than 16 finite candidates is padded at its END with q itself (knn16_body, knn16_wave_body, TopLex::index_or),
+//     not with an out-of-range value.  If the list has a real entry at all, q is finite, d(q, q) = 0 < inf and q is a real entry ahead
+//     of the padding, so the padding cannot be the first entry < m.  Only a list WITHOUT a real entry (q non-finite: the answer is 0)
+//     could pass q off as an answer; it reads q, q, ... like the list of a finite q that is the level's only finite point.  Both go to
+//     the scan, which is right for any input: a list whose first two entries are q never answers (real entries are distinct).
+// Four lanes per query, one int4 of the list each (a wave reads 1 KB of lists per instruction and writes sub_idx the same way).  The
+// queries that need the scan are balloted and settled one by one by the whole wave: lane t takes support points t, t + 64, ... in
+// ascending order under strict `<`, the lanes meet in a butterfly under (d, lower index).  ~1 % of the queries of a shuffled cloud
+// (15 other neighbours, each in the prefix with probability 1/4: 0.75^15), m / 64 steps each; most waves have none.  No atomics, no
+// LDS, no scratch, no workspace.
+__global__ __launch_bounds__(256) void interp_lists_kernel(const float* __restrict__ pts, int64_t cs, int stride,
+                                                           const int32_t* __restrict__ neigh, int64_t ncs, const PyramidLevels lv,
+                                                           int32_t* __restrict__ sub, int64_t scs, int32_t* __restrict__ interp, int64_t ics) {
+  const int cloud = blockIdx.y;
+  const int lane = threadIdx.x & 63, part = threadIdx.x & 3;
+  const int p = (int)((blockIdx.x * 256 + threadIdx.x) >> 2);      // row of the concatenated levels
+  const bool valid = p < lv.S;
+  int l = 0;
+#pragma unroll
+  for (int k = 1; k < kMaxLevels; ++k) l += (k < lv.L && p >= lv.off[k]) ? 1 : 0;
+  const int q = p - lv.off[l];                                     // the query's index in its level (list entries are level-local too)
+  const int m = lv.nl[l + 1];
+  int4 e = make_int4(-1, -1, -1, -1);
+  if (valid) e = *reinterpret_cast<const int4*>(neigh + cloud * ncs + (int64_t)p * kKnn + part * 4);
+  if (valid && q < m) *reinterpret_cast<int4*>(sub + cloud * scs + (int64_t)(lv.soff[l] + q) * kKnn + part * 4) = e;
+  // this lane's first entry inside the prefix (unsigned compare: 0 <= e < m)
+  int c = -1;
+  c = (unsigned)e.w < (unsigned)m ? e.w : c;
+  c = (unsigned)e.z < (unsigned)m ? e.z : c;
+  c = (unsigned)e.y < (unsigned)m ? e.y : c;
+  c = (unsigned)e.x < (unsigned)m ? e.x : c;
+  const unsigned long long has = __ballot(c >= 0);
+  const unsigned long long padded = __ballot(part == 0 && e.x == q && e.y == q);      // no real entry, or q alone: the scan decides
+  const int base = lane & ~3;
+  const unsigned mine = (unsigned)(has >> base) & 15u;
+  int ans = __shfl(c, base + (mine ? __ffs((int)mine) - 1 : 0));   // the query's first entry inside the prefix, in all its four lanes
+  if (!mine || ((padded >> base) & 1)) ans = -1;
+  unsigned long long need = __ballot(valid && part == 0 && ans < 0);
+  const float* P = pts + cloud * cs;
+  while (need) {                                                   // wave-uniform
+    const int src = __ffsll((long long)need) - 1;
+    need &= need - 1;
+    const int fq = __shfl(q, src), fm = __shfl(m, src);
+    const float qx = P[(int64_t)fq * stride], qy = P[(int64_t)fq * stride + 1], qz = P[(int64_t)fq * stride + 2];
+    float bd = INFINITY;
+    int bi = -1;
+    for (int j0 = lane; j0 < fm + lane; j0 += 256) {               // j0 - lane < fm: the same trip count in every lane
+      float4 s[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int64_t j = min(j0 + 64 * u, fm - 1);
+        s[u] = make_float4(P[j * stride], P[j * stride + 1], P[j * stride + 2], 0.f);
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const float d = sqdist(qx, qy, qz, s[u]);
+        if (j0 + 64 * u < fm && d < bd) { bd = d; bi = j0 + 64 * u; }
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float od = __shfl_xor(bd, o);
+      const int oi = __shfl_xor(bi, o);
+      if (od < bd || (od == bd && oi < bi)) { bd = od; bi = oi; }  // both inf: both -1, nothing moves
+    }
+    if (lane == src) ans = bi < 0 ? 0 : bi;                        // no finite distance (non-finite coordinates): stay in range
+  }
+  if (valid && part == 0) interp[cloud * ics + p] = ans;
+}
+
 }  // namespace
 
 void launch_knn16(const float* pts, int64_t cs, int stride, int n, int clouds, int32_t* out, int64_t ocs, hipStream_t st) {
@@ -317,6 +401,13 @@ void launch_knn_small_levels(const float* pts, int64_t cs, int stride, int cloud
   if (b == 0 || clouds <= 0) return;
   if (k16) hipLaunchKernelGGL(knn_small_levels_kernel<true>, dim3(b, clouds), dim3(256), 0, st, pts, cs, stride, S);
   else hipLaunchKernelGGL(knn_small_levels_kernel<false>, dim3(b, clouds), dim3(256), 0, st, pts, cs, stride, S);
+}
+
+void launch_interp_lists(const float* pts, int64_t cs, int stride, const int32_t* neigh, int64_t ncs, const PyramidLevels& lv, int clouds,
+                         int32_t* sub, int64_t scs, int32_t* interp, int64_t ics, hipStream_t st) {
+  if (lv.S <= 0 || clouds <= 0) return;
+  hipLaunchKernelGGL(interp_lists_kernel, dim3((lv.S + 63) / 64, clouds), dim3(256), 0, st, pts, cs, stride, neigh, ncs, lv, sub, scs,
+                     interp, ics);
 }
 
 void launch_nn1(const float* pts, int64_t cs, int stride, int n_query, int n_support, int clouds, int32_t* out,

@@ -796,6 +796,13 @@ int build_pyramid(dsir_ctx* c, const float* points, int stride, int clouds, int 
   static const int grid_min = (int)tuning_int("DSIR_GRID_MIN", 1024);   // tuning hook
   static const bool no_nn1_grid = tuning_flag("DSIR_NO_NN1_GRID");   // A/B switch: brute-force interpolation search throughout
   static const long long nn1_grid_min = tuning_int("DSIR_NN1_GRID_MIN", 65536);   // tuning hook
+  // interp_idx is read off the finished 16-NN lists by the launch that writes sub_idx (knn.hip, interp_lists_kernel: same bits), in
+  // place of one search per level.  A/B switch: the searches (the kind-0 jobs, launch_nn1_grid, launch_nn1) and launch_copy_sub_levels
+  static const bool nn1_search = tuning_flag("DSIR_NO_INTERP_LISTS");
+  auto finish = [&]() {      // the last launch: every list exists
+    if (nn1_search) launch_copy_sub_levels(neigh, neigh_cs, lv, clouds, sub, sub_cs, st);
+    else launch_interp_lists(points, (int64_t)n * stride, stride, neigh, neigh_cs, lv, clouds, sub, sub_cs, interp, p.S, st);
+  };
   // interpolation search of level l (support = level l + 1) through level l + 1's grid: when that level has one and the launch has
   // queries enough to fill the chip with one lane per query (same bits either way)
   auto nn1_by_grid = [&](int l) {
@@ -824,7 +831,7 @@ int build_pyramid(dsir_ctx* c, const float* points, int stride, int clouds, int 
       } else {
         jobs.job[jobs.njobs++] = {knn16_takes_wave_kernel(p.nl[l], clouds) ? 1 : 2, p.nl[l], 0, neigh + (int64_t)p.off[l] * kKnn, neigh_cs, 0};
       }
-      if (!nn1_by_grid(l)) jobs.job[jobs.njobs++] = {0, p.nl[l], p.nl[l + 1], interp + p.off[l], (int64_t)p.S, 0};
+      if (nn1_search && !nn1_by_grid(l)) jobs.job[jobs.njobs++] = {0, p.nl[l], p.nl[l + 1], interp + p.off[l], (int64_t)p.S, 0};
     }
     if (ok) {
       void* gscr[4];
@@ -833,10 +840,10 @@ int build_pyramid(dsir_ctx* c, const float* points, int stride, int clouds, int 
       if (ngrid) launch_knn16_grid_levels(points, (int64_t)n * stride, stride, ngrid, gn, clouds, gout, neigh_cs, gscr, st);
       launch_knn_small_levels(points, (int64_t)n * stride, stride, clouds, jobs, st);
       for (int l = 0; l + 1 < g.num_layers; ++l)
-        if (nn1_by_grid(l))      // level l + 1 has a grid, hence the larger level l too: the search walks the one, its queries in the cell order of the other
+        if (nn1_search && nn1_by_grid(l))      // level l + 1 has a grid, hence the larger level l too: the search walks the one, its queries in the cell order of the other
           launch_nn1_grid(p.nl[l], p.nl[l + 1], clouds, interp + p.off[l], p.S, gscr[grid_of[l + 1]], gscr[grid_of[l]], st);
       c->ws.release(mark);
-      launch_copy_sub_levels(neigh, neigh_cs, lv, clouds, sub, sub_cs, st);
+      finish();
       return 0;
     }
   }
@@ -849,18 +856,18 @@ int build_pyramid(dsir_ctx* c, const float* points, int stride, int clouds, int 
                         scratch, st);
       // this level's points are the support of the level above's interpolation search: it walks the grid just built (the level above
       // is no smaller, so it took this branch too and prev_scratch is its grid)
-      if (l > 0 && nn1_by_grid(l - 1))
+      if (nn1_search && l > 0 && nn1_by_grid(l - 1))
         launch_nn1_grid(p.nl[l - 1], p.nl[l], clouds, interp + p.off[l - 1], p.S, scratch, prev_scratch, st);
       prev_scratch = scratch;
     } else {
       prev_scratch = nullptr;
       launch_knn16(points, (int64_t)n * stride, stride, p.nl[l], clouds, neigh + (int64_t)p.off[l] * kKnn, neigh_cs, st);
     }
-    if (!nn1_by_grid(l)) launch_nn1(points, (int64_t)n * stride, stride, p.nl[l], p.nl[l + 1], clouds, interp + p.off[l], p.S, st);
+    if (nn1_search && !nn1_by_grid(l)) launch_nn1(points, (int64_t)n * stride, stride, p.nl[l], p.nl[l + 1], clouds, interp + p.off[l], p.S, st);
   }
   c->ws.release(mark);   // stream-ordered: later users of this memory run after the query kernels
   // sub_idx of level l = the neighbour lists of its first n_{l+1} points: all levels in one launch
-  launch_copy_sub_levels(neigh, neigh_cs, lv, clouds, sub, sub_cs, st);
+  finish();
   return 0;
 }
 

@@ -4,6 +4,7 @@
     python tools/microbench.py randla    --clouds 32 --n 5000 --reps 10
     python tools/microbench.py match     --clouds 16 --n 5000 --reps 20
     python tools/microbench.py knn       --clouds 32 --n 5000 --reps 10
+    python tools/microbench.py knn       --clouds 256 --n 5000 --reps 100 --sorted     (worst case of interp_idx from the lists)
 """
 import argparse
 import os
@@ -23,6 +24,8 @@ ap.add_argument("what", choices=["aggregate", "randla", "inlier", "match", "matc
 ap.add_argument("--clouds", type=int, default=16)
 ap.add_argument("--n", type=int, default=5000)
 ap.add_argument("--reps", type=int, default=20)
+ap.add_argument("--sorted", action="store_true",
+                help="every cloud sorted along x: each level's prefix is a slab, so most interp_idx queries find no list entry inside it")
 a = ap.parse_args()
 
 cfg = NetConfig(feat_len=3)
@@ -30,7 +33,10 @@ eng = Engine(cfg, 0, max_points=a.n, max_pairs=max(1, (a.clouds + 1) // 2))
 eng.load_state_dict(generate_state_dict(cfg, 0))
 dev = torch.device("cuda", 0)
 g = torch.Generator(device="cpu").manual_seed(0)
-pts = (torch.rand(a.clouds, a.n, 3, generator=g) * 3).to(dev)
+pts = torch.rand(a.clouds, a.n, 3, generator=g) * 3
+if a.sorted:
+    pts = torch.gather(pts, 1, pts[:, :, 0].argsort(1)[:, :, None].expand(-1, -1, 3)).contiguous()
+pts = pts.to(dev)
 xyz, neigh, sub, interp = eng.knn_pyramid(pts)
 feat = torch.randn(a.clouds, a.n, 64, generator=g).to(dev)
 score = torch.rand(a.clouds, a.n, generator=g).to(dev)
@@ -60,4 +66,4 @@ t0 = time.perf_counter()
 for _ in range(a.reps):
     run()
 torch.cuda.synchronize()
-print(f"{a.what}: {(time.perf_counter() - t0) / a.reps * 1e3:.3f} ms per call (clouds={a.clouds}, n={a.n})")
+print(f"{a.what}: {(time.perf_counter() - t0) / a.reps * 1e3:.3f} ms per call (clouds={a.clouds}, n={a.n}{', sorted' if a.sorted else ''})")
