@@ -1,9 +1,10 @@
 // The stage entries of include/dsir.h: index narrowing, the KNN pyramid, one RandLA pass and the use_ppf front end, normals,
-// FPFH, ISS keypoints, farthest-point sampling, score, aggregation, and the preprocessing (voxel down-sampling, resampling).
+// FPFH, ISS keypoints, farthest-point sampling, plane segmentation, score, aggregation, and the preprocessing (voxel down-sampling, resampling).
 #include <cmath>
 
 #include "engine_ctx.h"
 #include "fps.h"
+#include "plane.h"
 
 using namespace dsir;
 
@@ -158,6 +159,36 @@ int dsir_farthest_point_sample(dsir_ctx* c, const float* points, int stride, con
   a.clouds = clouds; a.cap = cap; a.k = k; a.start = start;
   a.index = index; a.counts_out = counts_out; a.min_d2 = min_d2;
   if (!launch_fps(a, c->stream)) return fail(c, "dsir_farthest_point_sample: shape refused");
+  return call.finish();
+}
+
+int dsir_segment_plane(dsir_ctx* c, const float* points, int stride, const int32_t* counts, const int32_t* cloud_ids, int clouds, int cap,
+                       float distance_threshold, int hypotheses, int max_planes, int min_inliers, int refine_iters, float axis_x,
+                       float axis_y, float axis_z, double cos_min, uint64_t seed, int32_t* labels, int32_t* num_planes, float* planes,
+                       float* anchors, int32_t* plane_counts, int32_t* stats) {
+  Call call(c); if (call.refused()) return 1;
+  if (!points || !labels || !num_planes || !planes || !anchors || !plane_counts || !stats)
+    return fail(c, "dsir_segment_plane: a null pointer among points and the six outputs");
+  if (clouds < 1 || clouds > kPlaneMaxClouds) return fail(c, "dsir_segment_plane: clouds in [1, %d] expected, got %d", kPlaneMaxClouds, clouds);
+  if (cap < 1 || (int64_t)clouds * cap >= ((int64_t)1 << 31))
+    return fail(c, "dsir_segment_plane: cap >= 1 with clouds x cap < 2^31 expected, got clouds=%d cap=%d", clouds, cap);
+  if (stride < 3) return fail(c, "dsir_segment_plane: stride >= 3 expected, got %d", stride);
+  if (hypotheses < 1 || hypotheses > kPlaneMaxHyp) return fail(c, "dsir_segment_plane: hypotheses in [1, %d] expected, got %d", kPlaneMaxHyp, hypotheses);
+  if (!(distance_threshold > 0.f) || !std::isfinite(distance_threshold))
+    return fail(c, "dsir_segment_plane: distance_threshold finite and positive expected, got %g", (double)distance_threshold);
+  if (max_planes < 1 || max_planes > kPlaneMaxPlanes) return fail(c, "dsir_segment_plane: max_planes in [1, %d] expected, got %d", kPlaneMaxPlanes, max_planes);
+  if (min_inliers < kPlaneMinInliers) return fail(c, "dsir_segment_plane: min_inliers >= %d expected, got %d", kPlaneMinInliers, min_inliers);
+  if (refine_iters < 0 || refine_iters > kPlaneMaxRefits) return fail(c, "dsir_segment_plane: refine_iters in [0, %d] expected, got %d", kPlaneMaxRefits, refine_iters);
+  if (!std::isfinite(axis_x) || !std::isfinite(axis_y) || !std::isfinite(axis_z) || !std::isfinite(cos_min))
+    return fail(c, "dsir_segment_plane: axis and cos_min must be finite");
+  PlaneArgs a;
+  a.scratch = c->ws.raw(plane_scratch_bytes(clouds, cap, hypotheses));
+  if (c->ws.overflow) return fail(c, "workspace too small for dsir_segment_plane (raise max_points / max_pairs)");
+  a.pts = points; a.pts_cs = (int64_t)cap * stride; a.pts_ld = stride; a.counts = counts; a.cloud_ids = cloud_ids;
+  a.clouds = clouds; a.cap = cap; a.H = hypotheses; a.max_planes = max_planes; a.min_inliers = min_inliers; a.refine_iters = refine_iters;
+  a.thr = distance_threshold; a.axis[0] = axis_x; a.axis[1] = axis_y; a.axis[2] = axis_z; a.cos_min = cos_min; a.seed = seed;
+  a.labels = labels; a.num_planes = num_planes; a.planes = planes; a.anchors = anchors; a.plane_counts = plane_counts; a.stats = stats;
+  if (!launch_segment_plane(a, c->stream)) return fail(c, "dsir_segment_plane: shape refused");
   return call.finish();
 }
 

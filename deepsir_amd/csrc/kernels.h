@@ -263,6 +263,24 @@ struct FpsArgs {
 size_t fps_scratch_bytes(int clouds, int cap);
 bool launch_fps(const FpsArgs& a, hipStream_t st);                    // false: outside the envelope (nothing launched)
 
+// plane.hip - RANSAC plane segmentation, up to 8 planes per cloud peeled in one call (the rule: the file's header; draws, pick key,
+// geometry, limits and the scratch layout: plane.h).
+struct PlaneArgs {
+  const float* pts = nullptr; int64_t pts_cs = 0; int pts_ld = 3;     // [clouds][cap][pts_ld], 3 columns used
+  const int32_t* counts = nullptr;                                    // [clouds] or nullptr: cloud c has pair_rows(counts, c, cap) rows
+  const int32_t* cloud_ids = nullptr;                                 // [clouds] or nullptr: the id that enters cloud c's draws (nullptr: c)
+  int clouds = 0, cap = 0, H = 0, max_planes = 1, min_inliers = 3, refine_iters = 1;
+  float thr = 0.f;
+  float axis[3] = {0.f, 0.f, 0.f}; double cos_min = 0.0;              // all zero: no angle constraint
+  uint64_t seed = 0;
+  void* scratch = nullptr;                                            // plane_scratch_bytes
+  int32_t *labels = nullptr, *num_planes = nullptr;                   // [clouds][cap], [clouds]
+  float *planes = nullptr, *anchors = nullptr;                        // [clouds][max_planes][4], [clouds][max_planes][3]
+  int32_t *plane_counts = nullptr, *stats = nullptr;                  // [clouds][max_planes], [clouds][max_planes][4]
+};
+size_t plane_scratch_bytes(int clouds, int cap, int H);
+bool launch_segment_plane(const PlaneArgs& a, hipStream_t st);        // false: outside the limits (nothing launched)
+
 // mlp_out + fc_label fused (head_mlp.hip): x[32] -> feat[64] -> 64 -> 32 -> ncls   (RandLANet.py:363-367)
 struct HeadArgs {
   Seg in = {};                  // last decoder block, [clouds][M][32], lazy GroupNorm + LeakyReLU

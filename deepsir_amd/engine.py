@@ -412,6 +412,58 @@ class Engine:
         self.sync()
         return index, counts_out, min_d2
 
+    def segment_plane(self, points, distance_threshold: float, counts=None, hypotheses: int = 1024, max_planes: int = 1,
+                      min_inliers: int = 3, axis=None, max_angle_deg=None, refine_iters: int = 1, seed: int = 0, cloud_ids=None):
+        """RANSAC plane segmentation (include/dsir.h, dsir_segment_plane; the rule: csrc/plane.hip, restated in deepsir_amd/plane.py):
+        points [c,cap,>=3], ``counts`` [c] as for ``farthest_point_sample``; per cloud up to ``max_planes`` planes are peeled, each
+        the best of ``hypotheses`` three-row draws by its integer inlier count (|e| < distance_threshold), refitted ``refine_iters``
+        times while the count does not drop; a cloud stops when no hypothesis is valid or the winner counts fewer than
+        ``min_inliers``.  ``axis`` (3 numbers) orients the normals and, with ``max_angle_deg``, rejects planes whose normal is
+        farther than that from it.  ``cloud_ids`` [c]: the id that enters each cloud's draws (None: its position), so that cloud c
+        of a batch is cloud 0 of a call with seed ^ (c << 40).  -> (labels [c,cap] i32, -1 where no plane took the row; num_planes
+        [c] i32; planes [c,max_planes,4] (n, d); anchors [c,max_planes,3]; plane_counts [c,max_planes] i32; stats
+        [c,max_planes,4] i32 = winning hypothesis, valid hypotheses, count before the refits, refits kept), zeros at and behind
+        num_planes.  Same bytes on every run and for a cloud alone or in a batch.  Needs no weights.  Raises ValueError for
+        arguments refused on the host, EngineError where the library refuses."""
+        from . import plane as _plane
+        points = _chk(points, torch.float32, "points")
+        if points.dim() != 3 or points.shape[2] < 3 or points.shape[0] < 1 or points.shape[1] < 1:
+            raise ValueError("segment_plane: points [clouds >= 1, cap >= 1, C >= 3] expected")
+        c, cap, stride = points.shape
+        if c > _plane.MAX_CLOUDS or c * cap >= 1 << 31:
+            raise ValueError(f"segment_plane: clouds in [1, {_plane.MAX_CLOUDS}] with clouds x cap < 2^31 expected, got {c} x {cap}")
+        thr = float(distance_threshold)
+        if not (np.isfinite(np.float32(thr)) and np.float32(thr) > 0):
+            raise ValueError(f"segment_plane: distance_threshold must be finite and positive in fp32, got {distance_threshold}")
+        for name, v, lo, hi in (("hypotheses", hypotheses, 1, _plane.MAX_HYPOTHESES), ("max_planes", max_planes, 1, _plane.MAX_PLANES),
+                                ("min_inliers", min_inliers, _plane.MIN_INLIERS, 0x7fffffff), ("refine_iters", refine_iters, 0, _plane.MAX_REFITS)):
+            if int(v) != v or not lo <= v <= hi:
+                raise ValueError(f"segment_plane: {name} must be an integer in [{lo}, {hi}], got {v}")
+        if int(seed) != seed or not 0 <= seed < 1 << 64:
+            raise ValueError(f"segment_plane: seed must be an unsigned 64-bit integer, got {seed}")
+        try:
+            ax, cos_min = _plane.axis_args(axis, max_angle_deg)
+        except ValueError as e:
+            raise ValueError(f"segment_plane: {e}") from None
+        cn = self._counts(pair_counts(counts, c, cap, "counts"))
+        ids = None
+        if cloud_ids is not None:
+            a = cloud_ids.detach().cpu().numpy() if isinstance(cloud_ids, torch.Tensor) else np.asarray(cloud_ids)
+            if a.shape != (c,) or a.dtype.kind not in "iu" or (c and (int(a.min()) < 0 or int(a.max()) > 0x7fffffff)):
+                raise ValueError(f"segment_plane: cloud_ids must hold {c} non-negative int32 values")
+            ids = torch.from_numpy(np.ascontiguousarray(a, np.int32)).to(self.device)
+        m = int(max_planes)
+        labels, num_planes = self._empty((c, cap), torch.int32), self._empty((c,), torch.int32)
+        planes, anchors = self._empty((c, m, 4)), self._empty((c, m, 3))
+        plane_counts, stats = self._empty((c, m), torch.int32), self._empty((c, m, 4), torch.int32)
+        self._pre()
+        self._call(self.lib.dsir_segment_plane(self.h, _ptr(points), stride, _ptr(cn), _ptr(ids), c, cap, thr, int(hypotheses), m,
+                                               int(min_inliers), int(refine_iters), float(ax[0]), float(ax[1]), float(ax[2]), cos_min,
+                                               int(seed), _ptr(labels), _ptr(num_planes), _ptr(planes), _ptr(anchors), _ptr(plane_counts),
+                                               _ptr(stats)))
+        self.sync()
+        return labels, num_planes, planes, anchors, plane_counts, stats
+
     def score(self, feat, logits, xyz_multi, neigh_multi):
         """torch.max(logits) + score_fun counterpart -> (score [c,n], label [c,n] i32)."""
         feat, logits = _chk(feat, torch.float32, "feat"), _chk(logits, torch.float32, "logits")

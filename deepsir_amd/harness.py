@@ -509,7 +509,7 @@ def register_fpfh(pairs: Sequence[Dict[str, np.ndarray]], engine, voxel_size: fl
                   normal_max_nn: int = 0, fgr_iterations: int = 64, tuple_scale: float = 0.95, max_tuples: int = 1000,
                   tuple_test: bool = True, keypoints: Optional[str] = None, salient_radius: Optional[float] = None,
                   non_max_radius: Optional[float] = None, gamma_21: float = 0.975, gamma_32: float = 0.975, min_neighbors: int = 5,
-                  min_keypoints: int = 32, want_keypoints: bool = False, num_keypoints: int = 1024):
+                  min_keypoints: int = 32, want_keypoints: bool = False, num_keypoints: int = 1024, ground: Optional[dict] = None):
     """The weight-independent baseline of ``register_feat``: FPFH + feature-matching RANSAC (open3d compute_fpfh_feature ->
     registration_ransac_based_on_feature_matching; parity unpinned, the rules are the engine's own), all on the device.  Per batch
     and side: ``knn_pyramid`` -> ``estimate_normals`` on its level-0 lists (towards the pair's optional ``viewpoint_src`` /
@@ -544,6 +544,9 @@ def register_fpfh(pairs: Sequence[Dict[str, np.ndarray]], engine, voxel_size: fl
     sampled rows on a side, uses all of its points through the one-pair calls; ``corr`` and ``want_keypoints`` as above, the
     indices in selection order.
     ``keypoints=None`` (the default) is the path above, unchanged.
+    ``ground``: a dict of ``remove_ground`` arguments (``distance_threshold`` and what else it takes): ``points_src`` and
+    ``points_ref`` of every pair lose their ground plane before anything else, so the result is that of the call on pairs holding
+    the clouds ``remove_ground`` returns (the sizes become ragged: use ``batch=1``).  None (the default): nothing is removed.
 
     ``engine`` is a ``deepsir_amd.engine.Engine`` THE CALLER PREPARED: the descriptor itself needs no weights, but the pyramid and
     the other existing entries this calls refuse a context whose weights are not loaded (``Call::kWeights``, csrc/engine_ctx.h), so
@@ -565,6 +568,9 @@ def register_fpfh(pairs: Sequence[Dict[str, np.ndarray]], engine, voxel_size: fl
         raise ValueError("register_fpfh: min_keypoints >= 1 expected")
     if keypoints == "fps" and (int(num_keypoints) != num_keypoints or num_keypoints < 1):
         raise ValueError(f"register_fpfh: num_keypoints must be a positive integer, got {num_keypoints}")
+    if ground is not None and len(pairs):
+        sides = {k: _without_ground([p[k][0] for p in pairs], engine, ground, "register_fpfh") for k in ("points_src", "points_ref")}
+        pairs = [dict(p, points_src=sides["points_src"][i][None], points_ref=sides["points_ref"][i][None]) for i, p in enumerate(pairs)]
     nbr = (search, int(max_nn), normal_radius, int(normal_max_nn))
     rte_t, rre_t = THRESHOLDS[dataset_type]
     preds, corrs, kpts, stats = [], [], [], np.zeros((len(pairs), 5))
@@ -701,6 +707,60 @@ def pad_clouds(clouds):
     return out, torch.tensor([c.shape[0] for c in cl], dtype=torch.int32, device=cl[0].device)
 
 
+@torch.no_grad()
+def remove_planes(clouds, engine, distance_threshold: float, keep: str = "rest", batch: Optional[int] = None, **segment_kw):
+    """Split clouds by ``Engine.segment_plane`` (csrc/plane.hip): clouds [n_i, C >= 3] of any sizes (numpy or tensors) ->
+    (kept: per cloud the rows no plane took (``keep="rest"``) or the rows of the planes (``keep="planes"``), in input order, all
+    columns; planes [P, max_planes, 4]; num_planes [P]; removed [P] float64: the share of each cloud's rows that was dropped).
+    ``pad_clouds``, then one ``segment_plane`` call per ``batch`` clouds (default: all, at most the engine's max_pairs), cloud i
+    drawing with id i (``cloud_ids`` in ``segment_kw`` overrides it), so a cloud's split does not depend on ``batch``; the split
+    itself is torch boolean indexing per cloud.  ``segment_kw``: hypotheses, max_planes, min_inliers, axis, max_angle_deg,
+    refine_iters, seed."""
+    if keep not in ("rest", "planes"):
+        raise ValueError(f"remove_planes: keep must be 'rest' or 'planes', got {keep!r}")
+    dev = engine.device
+    cl = [(c if isinstance(c, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(c, np.float32))).to(dev).float().contiguous() for c in clouds]
+    P = len(cl)
+    if P < 1:
+        raise ValueError("remove_planes: at least one cloud expected")
+    per = int(batch or min(P, engine.max_pairs))
+    if per < 1:
+        raise ValueError("remove_planes: batch must be at least 1")
+    kw = dict(segment_kw)
+    ids = kw.pop("cloud_ids", None)
+    ids = list(range(P)) if ids is None else [int(i) for i in (ids.cpu().tolist() if isinstance(ids, torch.Tensor) else ids)]
+    if len(ids) != P:
+        raise ValueError(f"remove_planes: cloud_ids must hold one id per cloud ({P})")
+    kept, planes, nums, removed = [], [], [], np.zeros(P)
+    for b0 in range(0, P, per):
+        part = cl[b0:b0 + per]
+        pad, counts = pad_clouds(part)
+        labels, num, pl = engine.segment_plane(pad, distance_threshold, counts=counts, cloud_ids=ids[b0:b0 + per], **kw)[:3]
+        for i, c in enumerate(part):
+            taken = labels[i, :c.shape[0]] >= 0
+            kept.append(c[taken if keep == "planes" else ~taken])
+            removed[b0 + i] = 1.0 - kept[-1].shape[0] / max(c.shape[0], 1)
+        planes.append(pl)
+        nums.append(num)
+    return kept, torch.cat(planes, 0), torch.cat(nums, 0), removed
+
+
+def remove_ground(clouds, engine, distance_threshold: float, axis=(0.0, 0.0, 1.0), max_angle_deg: float = 15.0, **kw):
+    """``remove_planes`` with ``max_planes=1`` and the angle constraint: the dominant plane whose normal lies within ``max_angle_deg``
+    of ``axis`` (the road of a lidar scan, the floor of a fragment) is dropped (or, with ``keep="planes"``, kept alone)."""
+    if kw.get("max_planes", 1) != 1:
+        raise ValueError("remove_ground: one plane only (max_planes=1); use remove_planes for more")
+    return remove_planes(clouds, engine, distance_threshold, axis=axis, max_angle_deg=max_angle_deg, **dict(kw, max_planes=1))
+
+
+def _without_ground(clouds, engine, ground, who):
+    """the ``ground=`` option of register_fpfh / icp_multiscale / ndt_multiscale: a dict of ``remove_ground`` arguments"""
+    if not isinstance(ground, dict) or "distance_threshold" not in ground:
+        raise ValueError(f"{who}: ground must be a dict of remove_ground arguments with a 'distance_threshold'")
+    kw = dict(ground)
+    return remove_ground(clouds, engine, kw.pop("distance_threshold"), **kw)[0]
+
+
 def _per_scale(value, n, name):
     """None, a scalar or a sequence of n entries -> a list of n entries"""
     if value is None or isinstance(value, (int, float)):
@@ -712,7 +772,8 @@ def _per_scale(value, n, name):
 
 @torch.no_grad()
 def icp_multiscale(src_clouds, ref_clouds, T_init, voxel_sizes, max_iters, radii=None, estimator: str = "point",
-                   kernel: str = "l2", kernel_scales=None, search: str = "auto", batch: Optional[int] = None, *, engine):
+                   kernel: str = "l2", kernel_scales=None, search: str = "auto", batch: Optional[int] = None, *, engine,
+                   ground: Optional[dict] = None):
     """open3d's ``multi_scale_icp`` for lists of clouds of any sizes: coarse to fine, every scale one ``Engine.icp_refine`` from the
     previous scale's pose.  src_clouds / ref_clouds: P clouds [n_i, >=3] each (numpy or tensors), T_init [P,3,4] with p_ref = T p_src;
     voxel_sizes, max_iters: one entry per scale, in the order they run (coarse first); radii: the correspondence radius per scale
@@ -723,7 +784,9 @@ def icp_multiscale(src_clouds, ref_clouds, T_init, voxel_sizes, max_iters, radii
     ``pad_clouds`` with the counts, for ``estimator="plane"`` the normals of the downsampled reference from
     ``radius_neighbors(radius = 2 x voxel, max_nn = 30)`` and ``estimate_normals(csr=)`` cloud by cloud (this needs a non-zero voxel
     size at that scale, or rows that carry the normals in columns 3..5), then ``icp_refine``.  No kernel of its own: exactly these
-    engine calls, so the result is theirs byte for byte.
+    engine calls, so the result is theirs byte for byte.  ``ground``: a dict of ``remove_ground`` arguments (``distance_threshold``
+    and what else it takes); both sides lose their ground plane before anything else, so the result is that of the call on the
+    clouds ``remove_ground`` returns.  None (the default): nothing is removed.
     -> (T [P,3,4] float32 tensor of the last scale, stats: one [P,4|5] float64 tensor per scale)."""
     S = len(voxel_sizes)
     if S < 1 or len(max_iters) != S:
@@ -735,6 +798,8 @@ def icp_multiscale(src_clouds, ref_clouds, T_init, voxel_sizes, max_iters, radii
     P = len(srcs)
     if P < 1 or len(refs) != P:
         raise ValueError("icp_multiscale: as many reference clouds as source clouds, at least one pair")
+    if ground is not None:
+        srcs, refs = _without_ground(srcs, engine, ground, "icp_multiscale"), _without_ground(refs, engine, ground, "icp_multiscale")
     T = as_dev(np.asarray(T_init.detach().cpu() if isinstance(T_init, torch.Tensor) else T_init, np.float32)[:, :3]).clone()
     if tuple(T.shape) != (P, 3, 4):
         raise ValueError(f"icp_multiscale: T_init must be [{P}, 3, 4]")
@@ -779,12 +844,13 @@ def icp_multiscale(src_clouds, ref_clouds, T_init, voxel_sizes, max_iters, radii
 
 @torch.no_grad()
 def ndt_multiscale(src_clouds, ref_clouds, T_init, resolutions, max_iters, neighbors: int = 7, step_tol: float = 1e-4,
-                   outlier_ratio: float = 0.55, batch: Optional[int] = None, *, engine):
+                   outlier_ratio: float = 0.55, batch: Optional[int] = None, *, engine, ground: Optional[dict] = None):
     """NDT coarse to fine for lists of clouds of any sizes: every scale one ``Engine.ndt_refine`` on the clouds as given, from the
     previous scale's pose.  src_clouds / ref_clouds: P clouds [n_i, >=3] each (numpy or tensors), T_init [P,3,4] with p_ref = T p_src;
     resolutions, max_iters: one entry per scale, in the order they run (coarse first).  ``engine`` (keyword): the ``Engine`` that
     runs it; ``batch``: pairs per engine call (default: all of them, at most the engine's max_pairs).  No kernel of its own:
     ``pad_clouds`` with the counts and these engine calls, so the result is theirs byte for byte.
+    ``ground``: a dict of ``remove_ground`` arguments; both sides lose their ground plane before anything else (None: nothing removed).
     -> (T [P,3,4] float32 tensor of the last scale, stats: one [P,5] float32 tensor per scale)."""
     S = len(resolutions)
     if S < 1 or len(max_iters) != S:
@@ -795,6 +861,8 @@ def ndt_multiscale(src_clouds, ref_clouds, T_init, resolutions, max_iters, neigh
     P = len(srcs)
     if P < 1 or len(refs) != P:
         raise ValueError("ndt_multiscale: as many reference clouds as source clouds, at least one pair")
+    if ground is not None:
+        srcs, refs = _without_ground(srcs, engine, ground, "ndt_multiscale"), _without_ground(refs, engine, ground, "ndt_multiscale")
     T = as_dev(np.asarray(T_init.detach().cpu() if isinstance(T_init, torch.Tensor) else T_init, np.float32)[:, :3]).clone()
     if tuple(T.shape) != (P, 3, 4):
         raise ValueError(f"ndt_multiscale: T_init must be [{P}, 3, 4]")

@@ -66,7 +66,14 @@ def main():
                     help="--method fpfh / --pipeline feat: the k nearest descriptors of every src point as candidate matches (1 .. 8)")
     ap.add_argument("--match-ratio", type=float, default=0.0,
                     help="--method fpfh / --pipeline feat: Lowe's ratio test on the 1-NN matches (0 < ratio < 1; 0 = off; needs --match-k 1)")
+    ap.add_argument("--remove-ground", type=float, default=None, metavar="THR",
+                    help="--method fpfh: drop the dominant near-horizontal plane of both clouds first (harness.remove_ground, RANSAC "
+                         "inlier distance THR in metres; pairs then run one at a time).  Default: off.  The network paths take no such option")
+    ap.add_argument("--ground-angle", type=float, default=15.0, metavar="DEG", help="with --remove-ground: the cone about +z the plane's normal must lie in")
     a = ap.parse_args()
+    if a.remove_ground is not None and a.method != "fpfh":
+        ap.error("--remove-ground applies to --method fpfh only (the network was trained on clouds with their ground)")
+    ground = None if a.remove_ground is None else dict(distance_threshold=a.remove_ground, max_angle_deg=a.ground_angle)
     kitti = a.dataset == "KITTI"
     cfg = NetConfig(feat_len=4 if kitti else 3)
     if a.pipeline == "feat" and not a.ransac:
@@ -92,7 +99,7 @@ def main():
     pairs = [D.as_batch(ds[i]) for i in range(n)]
     if a.method == "fpfh":
         pred, stats = register_fpfh(pairs, eng, voxel_size=voxel, radius=a.fpfh_radius, hypotheses=a.hypotheses, dataset_type=a.dataset,
-                                    batch=a.batch, pose=a.pose, match_k=a.match_k, match_ratio=a.match_ratio, search=a.fpfh_search,
+                                    batch=1 if ground else a.batch, ground=ground, pose=a.pose, match_k=a.match_k, match_ratio=a.match_ratio, search=a.fpfh_search,
                                     max_nn=a.fpfh_max_nn, normal_radius=a.normal_radius, normal_max_nn=a.normal_max_nn,
                                     keypoints=None if a.keypoints == "none" else a.keypoints, salient_radius=a.salient_radius,
                                     non_max_radius=a.non_max_radius, num_keypoints=a.num_keypoints)

@@ -214,6 +214,29 @@ int dsir_iss_keypoints(dsir_ctx* ctx, const float* points, int stride, const int
 int dsir_farthest_point_sample(dsir_ctx* ctx, const float* points, int stride, const int32_t* counts, int clouds, int cap, int k, int start,
                                int32_t* index, int32_t* counts_out, float* min_d2);
 
+/* RANSAC plane segmentation of a batch of clouds, up to max_planes planes peeled per cloud in one call: what open3d's segment_plane
+ * and PCL's SACSegmentation do in front of a lidar registration (unpinned here: the rule is this engine's own, stated in
+ * csrc/plane.hip and restated in deepsir_amd/plane.py).  points [clouds][cap][stride] (xyz first); counts [clouds] on the device or
+ * NULL: cloud c has clamp(counts[c], 0, cap) rows (NULL: cap), rows at and past it are never read; cloud_ids [clouds] on the device or
+ * NULL: the id that enters cloud c's draws (NULL: c), so that cloud c of a batch is cloud 0 of a call with seed ^ (c << 40).
+ * Per round j: `hypotheses` keyed draws of three live rows, an fp64 fit (normal, anchor) rounded to fp32 once, the fp32 residual
+ * e = ((nx (x - ax)) + (ny (y - ay))) + (nz (z - az)) with |e| < distance_threshold counted over the live rows, the largest count
+ * wins (ties to the lower hypothesis), refine_iters refits through the fp64 covariance of the inliers kept while the count does not
+ * drop; the inliers get labels = j and leave.  A cloud is finished when no hypothesis is valid or the winner counts fewer than
+ * min_inliers.  axis_x/y/z: a unit vector, all zero for none; with one a plane is accepted only if |n . axis| >= cos_min.
+ * -> labels [clouds][cap] i32 (-1: no plane), num_planes [clouds] i32, planes [clouds][max_planes][4] f32 (nx, ny, nz, d with
+ * n . p + d = 0; oriented n . axis >= 0, or d >= 0 without an axis), anchors [clouds][max_planes][3] f32, plane_counts
+ * [clouds][max_planes] i32, stats [clouds][max_planes][4] i32 = {winning hypothesis, valid hypotheses, count before the refits,
+ * refits kept}; rows at and behind num_planes are 0.  Refused with a message, launching nothing: a null pointer (counts and
+ * cloud_ids may be NULL), clouds outside [1, 65535], cap < 1 or clouds x cap >= 2^31, stride < 3, hypotheses outside [1, 2^20],
+ * distance_threshold not finite and positive, max_planes outside [1, 8], min_inliers < 3, refine_iters outside [0, 8], a non-finite
+ * axis or cos_min, a workspace too small.  Integer atomics only: same bytes on every run; clouds are independent, bit for bit.
+ * Any context serves (no weights needed). */
+int dsir_segment_plane(dsir_ctx* ctx, const float* points, int stride, const int32_t* counts, const int32_t* cloud_ids, int clouds, int cap,
+                       float distance_threshold, int hypotheses, int max_planes, int min_inliers, int refine_iters, float axis_x,
+                       float axis_y, float axis_z, double cos_min, uint64_t seed, int32_t* labels, int32_t* num_planes, float* planes,
+                       float* anchors, int32_t* plane_counts, int32_t* stats);
+
 /* Replaces torch.max(logits,1) + Network.feat_score/score_fun with num_sub<=0
  * (network/model.py:638-644, :668-757).
  * feat [clouds][n][64], logits [clouds][n][ncls], xyz [clouds][n][3],
